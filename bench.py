@@ -15,9 +15,16 @@ final mask, label map, detections, rows -- is written inside the timed region.
 Independent streams shard one per GPU (weak scaling, no data-path collective; torch.distributed is
 used only for the barrier and the max-over-ranks time).
 
-One JSON line on rank 0: frames/s (whole job), the roofline of the threshold kernel measured live
-with HIP events on the launch stream, and the CPU oracle timed on this host's cores on a bounded
-sample of the same clip (a reported baseline, not the target).
+One JSON line on rank 0: frames/s (whole job), ms_per_step and the roofline of the threshold kernel
+measured live with HIP events set by its own dispatch.  A plain run does only that: it sets up, warms
+up, times --steps steps and prints the line.
+
+    --full              also the per-kernel diagnostics (labelling chain and link sampled with HIP events
+                        inside the timed region, host call times, clocks) and the CPU oracle timed on this
+                        host's cores on a bounded sample of the same clip (a reported baseline, not the target)
+    --dump-outputs DIR  after the timed steps, what the last step handed its caller, as float32/float64
+                        DIR/<name>.npy (dump_outputs(); rank 0, stream 0): the same arguments give the same
+                        inputs, so two builds can be compared output for output
 """
 import argparse
 import json
@@ -63,7 +70,11 @@ def parse():
                          "to rehearse the multi-rank path on a box with fewer GPUs than ranks)")
     ap.add_argument("--device-index", type=int, default=None,
                     help="GPU of this rank (default LOCAL_RANK); rehearsals put several ranks on one GPU")
-    ap.add_argument("--cpu-sample", type=int, default=200, help="frames of the clip timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=200, help="frames of the clip timed on the CPU oracle with --full (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel diagnostics and the CPU oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32/float64, at most 64 MB)")
     args = ap.parse_args()
     if args.config == 0:
         args.blobs = 50
@@ -141,6 +152,76 @@ def stats_us(vals):
     return {"avg": sum(vals) / len(vals), "min": vals[0], "p50": pick(0.5), "p99": pick(0.99), "max": vals[-1], "n": len(vals)}
 
 
+#: --dump-outputs stays within 64 MB: larger outputs are written as a fixed, seeded sample of this many entries
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_ROWS = 400_000      # x 8 float64 columns: 25.6 MB (the default clip's step emits ~250 k rows)
+DUMP_DETS = 500_000      # x 5 float32 columns + one float64 anchor: 14 MB
+DUMP_PIXELS = 1 << 19    # flat index (float64) + class map, mask (float32) + labels (float64): 12.6 MB
+
+
+def _sample(n, k, seed):
+    """All n indices, or a fixed, seeded sample of k of them; ascending."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def dump_outputs(out_dir, pipe, batches, H, W):
+    """--dump-outputs: what the timed path handed its caller in its last step, one DIR/<name>.npy per array.
+
+    rows.npy               float64 (n, 8): frame, track_id, x, y, w, h, angle, disappeared of the rows the step's link
+                           emitted, in the order take_rows(sort=True) hands them over: by (track_id, frame)
+    detections.npy         float32 (m, 5): cx, cy, w, h, angle of each detection, frame by frame
+    detection_anchors.npy  float64 (m,): the anchor beside each detection
+    detection_counts.npy   float64 (f, 2): frame of the clip, detections in that frame
+    pixel_index.npy        float64 (p,): frame * H * W + y * W + x of a fixed, seeded sample of pixels of those frames
+    class_map.npy, mask.npy, labels.npy: float32, float32, float64 (p,): the maps at those pixels
+    The two detectors ping-pong, so the detection outputs still held are those of the step's last two batches (the whole
+    step at the default sizes); `batches` is [(first frame, DetectResult), ...] of them."""
+    import numpy as np
+    import torch
+    from ysmr_amd.tracker import rows_to_numpy
+    os.makedirs(out_dir, exist_ok=True)
+    batches = sorted(batches, key=lambda b: b[0])
+    out = {}
+    rows = rows_to_numpy(pipe.rows, int(pipe.row_count.item()))
+    rows = rows[np.lexsort((rows["frame"], rows["track_id"]))]
+    rows = rows[_sample(len(rows), DUMP_ROWS, 1)]
+    out["rows"] = np.stack([rows[name].astype(np.float64) for name in rows.dtype.names], axis=1)
+    dets, anchors, counts = [], [], []
+    for f0, res in batches:
+        cnt = res.det_count.cpu().numpy()
+        det, anc = res.det.cpu().numpy(), res.anchors.cpu().numpy()
+        for i, c in enumerate(cnt):
+            dets.append(det[i, :c]); anchors.append(anc[i, :c]); counts.append((f0 + i, c))
+    keep = _sample(sum(len(d) for d in dets), DUMP_DETS, 2)
+    out["detections"] = np.concatenate(dets).astype(np.float32).reshape(-1, 5)[keep]
+    out["detection_anchors"] = np.concatenate(anchors).astype(np.float64)[keep]
+    out["detection_counts"] = np.array(counts, dtype=np.float64).reshape(-1, 2)
+    px, maps = H * W, {"class_map": [], "mask": [], "labels": []}
+    n_px = [res.cls.shape[0] * px for _, res in batches]
+    pick = _sample(sum(n_px), DUMP_PIXELS, 3)
+    index, start = [], 0
+    for (f0, res), n in zip(batches, n_px):
+        local = pick[(pick >= start) & (pick < start + n)] - start
+        start += n
+        at = torch.from_numpy(local).to(res.cls.device)
+        index.append(local + f0 * px)
+        for name, t in (("class_map", res.cls), ("mask", res.mask), ("labels", res.labels)):
+            if t is not None:
+                maps[name].append(torch.take(t, at).cpu().numpy())
+    out["pixel_index"] = np.concatenate(index).astype(np.float64)
+    for name, parts in maps.items():
+        if parts:
+            out[name] = np.concatenate(parts).astype(np.float64 if name == "labels" else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (> {DUMP_LIMIT_BYTES})")
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse()
     # (re)build the library before anything touches the GPU: no child process is started from a process that
@@ -191,7 +272,8 @@ def main():
         link_streams.append(torch.cuda.current_stream(dev) if S == 1 else torch.cuda.Stream(device=dev))
     frames_np, pipe = clips_np[0], pipes[0]
     thr_events, chain_events, link_events, enqueue_s = [], [], [], []
-    DIAG = int(os.environ.get('YSMR_BENCH_DIAG', '3'))
+    # (--full: the labelling chain's and the link's events, sampled in the timed region, for the diagnostics)
+    DIAG = int(os.environ.get('YSMR_BENCH_DIAG', '3')) if args.full else 0
     # timing events are created (first record) BEFORE the timed region and reused inside it: creating one costs the host
     # tens of microseconds, and the host has only ~1.4x the time it needs to keep this pipeline fed
     n_batches = (F + B - 1) // B
@@ -202,11 +284,13 @@ def main():
     torch.cuda.synchronize()
     pool_i = [0]
     host_calls = {"detect_async": [], "link": [], "reset": []}   # seconds per call of the timed steps (where a slow host loses its time)
+    last_batches = []   # [(first frame, DetectResult)] of stream 0's last two batches of the latest step (--dump-outputs)
 
     def step(timed):
         # one clip per stream, fresh trackers; detection of batch b+1 (side stream) overlaps the link of
         # batch b; with several streams per GPU their (serial) link chains interleave as well
         pending = [None] * S
+        last_batches.clear()
         t_host = time.perf_counter()
         for k in range(S):
             with torch.cuda.stream(link_streams[k]):
@@ -231,6 +315,8 @@ def main():
                                                      chain_events if (sampled and DIAG & 1) else None, events=evs,
                                                      frames_ready=False), f0, evs, sampled)   # (the clip is resident in HBM)
                         if timed: host_calls["detect_async"].append(time.perf_counter() - tc)
+                        if k == 0:
+                            last_batches[:] = last_batches[-1:] + [(f0, nxt[0][1])]
                     if pending[k] is not None and not args.detect_only:
                         (slot, res, ready), p0, pevs, psampled = pending[k]
                         tc = time.perf_counter()
@@ -287,6 +373,8 @@ def main():
         if err or status or (rows_k <= 0 and not args.detect_only):
             raise SystemExit(f"hot path reported errors: tracker={err} detect_status={status} rows={rows_k}")
         n_rows += rows_k
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pipe, last_batches, H, W)
 
     if rank == 0:
         ms = [e0.elapsed_time(e1) for e0, e1, _ in thr_events]
@@ -342,29 +430,30 @@ def main():
                                         "HIP events set by the kernel's own dispatch (hipExtLaunchKernel start/stop): the duration "
                                         "a kernel trace reports, inside the timed region")},
         }
-        # what the headline is made of, so that one line says which part was slow on this box: the link of a batch is one
-        # launch on one compute unit (k_batch), frames strictly in order, so `value` ~ 1e6 / link.us_per_frame.avg as long
-        # as detection (threshold + chain, on the other stream) hides behind it and the host keeps ahead
-        diag = {"frames_per_batch": B,
-                # (per 64 frames: what earlier rounds' lines, at 64 frames per batch, called "per batch")
-                "threshold_us_per_64_frames": sum(ms) / len(ms) * 1e3 * 64.0 / B,
-                "components_us_per_64_frames": (sum(e0.elapsed_time(e1) for e0, e1, _ in chain_events) / len(chain_events) * 1e3 * 64.0 / B) if chain_events else None,
-                "threshold_us_per_batch": stats_us([m * 1e3 for m in ms]),
-                # in launch order (two per step): a launch at twice the others' time had a workgroup wait for a compute unit
-                "threshold_us_by_launch": [round(m * 1e3) for m in ms],
-                "components_us_per_batch": stats_us([e0.elapsed_time(e1) * 1e3 for e0, e1, _ in chain_events]),
-                "link_us_per_frame": stats_us([e0.elapsed_time(e1) * 1e3 / n for e0, e1, n, _ in link_events]),
-                "link_host_issue_us_per_frame": stats_us([h * 1e6 / n for _, _, n, h in link_events]),
-                "host_enqueue_ms_per_step": sum(enqueue_s) / len(enqueue_s) * 1e3 if enqueue_s else None,
-                # per call of the step loop: a host that blocks somewhere shows as a max far above the p50
-                "host_call_us": {k: stats_us([x * 1e6 for x in v]) for k, v in host_calls.items() if v},
-                "clocks": gpu_clocks(local_rank), "kernargs_in_device_memory": os.environ.get("HIP_FORCE_DEV_KERNARG") == "1",
-                "host_cpus": os.cpu_count(),
-                "cpus_usable": len(os.sched_getaffinity(0)), "pinned_to_gpu_numa_node": bool(pinned),
-                "host_load_1m": os.getloadavg()[0]}
-        out["diagnostics"] = diag
-        if world == 1:
-            out["cpu_baseline"] = cpu_baseline(frames_np, args.cpu_sample, fps_video, args.adt, args.detect_only)
+        if args.full:
+            # --full: what the headline is made of, so that one line says which part was slow on this box: the link of a batch is
+            # one launch on one compute unit (k_batch), frames strictly in order, so `value` ~ 1e6 / link.us_per_frame.avg as long
+            # as detection (threshold + chain, on the other stream) hides behind it and the host keeps ahead
+            diag = {"frames_per_batch": B,
+                    # (per 64 frames: what earlier rounds' lines, at 64 frames per batch, called "per batch")
+                    "threshold_us_per_64_frames": sum(ms) / len(ms) * 1e3 * 64.0 / B,
+                    "components_us_per_64_frames": (sum(e0.elapsed_time(e1) for e0, e1, _ in chain_events) / len(chain_events) * 1e3 * 64.0 / B) if chain_events else None,
+                    "threshold_us_per_batch": stats_us([m * 1e3 for m in ms]),
+                    # in launch order (two per step): a launch at twice the others' time had a workgroup wait for a compute unit
+                    "threshold_us_by_launch": [round(m * 1e3) for m in ms],
+                    "components_us_per_batch": stats_us([e0.elapsed_time(e1) * 1e3 for e0, e1, _ in chain_events]),
+                    "link_us_per_frame": stats_us([e0.elapsed_time(e1) * 1e3 / n for e0, e1, n, _ in link_events]),
+                    "link_host_issue_us_per_frame": stats_us([h * 1e6 / n for _, _, n, h in link_events]),
+                    "host_enqueue_ms_per_step": sum(enqueue_s) / len(enqueue_s) * 1e3 if enqueue_s else None,
+                    # per call of the step loop: a host that blocks somewhere shows as a max far above the p50
+                    "host_call_us": {k: stats_us([x * 1e6 for x in v]) for k, v in host_calls.items() if v},
+                    "clocks": gpu_clocks(local_rank), "kernargs_in_device_memory": os.environ.get("HIP_FORCE_DEV_KERNARG") == "1",
+                    "host_cpus": os.cpu_count(),
+                    "cpus_usable": len(os.sched_getaffinity(0)), "pinned_to_gpu_numa_node": bool(pinned),
+                    "host_load_1m": os.getloadavg()[0]}
+            out["diagnostics"] = diag
+            if world == 1:
+                out["cpu_baseline"] = cpu_baseline(frames_np, args.cpu_sample, fps_video, args.adt, args.detect_only)
         print(json.dumps(out), flush=True)
     dist.finish(info)
 

@@ -6,7 +6,7 @@ C=$1; shift
 for rep in 1 2; do
 for lib in "$@"; do
   unset YSMR_HIP_LIB; [ "$lib" = default ] || export YSMR_HIP_LIB=$lib
-  python3 bench.py --config $C --cpu-sample 0 2>/dev/null | python3 -c "
+  python3 bench.py --full --config $C --cpu-sample 0 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.readline()); g = d['diagnostics']
 lk = (g.get('link_us_per_frame') or {}).get('avg'); cp = (g.get('components_us_per_batch') or {}).get('avg')

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 for lib in "$@"; do
   unset YSMR_HIP_LIB YSMR_LINK_MODE
   case "$lib" in default) ;; waves:*) export YSMR_LINK_MODE=waves YSMR_HIP_LIB=${lib#waves:} ;; *) export YSMR_HIP_LIB=$lib ;; esac
-  python3 bench.py --config 4 --steps 12 --warmup 3 2>/dev/null | python3 -c "
+  python3 bench.py --full --config 4 --steps 12 --warmup 3 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.readline()); g = d['diagnostics']
 print('$lib', round(d['value']), 'frames/s  link', round(g['link_us_per_frame']['avg'], 1), 'us/frame  tracks', d['config']['tracks_alive'])"

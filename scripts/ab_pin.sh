@@ -19,6 +19,6 @@ for d in sorted(glob.glob("/sys/bus/pci/devices/*/local_cpulist")):
 PY
 nproc; cat /sys/fs/cgroup/cpu.max 2>/dev/null
 for rep in 1 2 3; do
-  echo -n "unpinned: "; python3 bench.py --steps 10 --warmup 3 --cpu-sample 0 2>/dev/null | python3 -c "$pick"
-  echo -n "pinned:   "; YSMR_BENCH_PIN=1 python3 bench.py --steps 10 --warmup 3 --cpu-sample 0 2>/dev/null | python3 -c "$pick"
+  echo -n "unpinned: "; python3 bench.py --full --steps 10 --warmup 3 --cpu-sample 0 2>/dev/null | python3 -c "$pick"
+  echo -n "pinned:   "; YSMR_BENCH_PIN=1 python3 bench.py --full --steps 10 --warmup 3 --cpu-sample 0 2>/dev/null | python3 -c "$pick"
 done

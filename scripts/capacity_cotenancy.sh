@@ -8,7 +8,7 @@ d=json.loads(sys.stdin.readlines()[-1]); r=d['roofline']; g=d['diagnostics']
 print('%-44s %9.0f frames/s   %-18s %6.1f us/launch  frac %.3f   link %5.2f us/frame' % (sys.argv[1], d['value'], r['kernel'], r['avg_launch_ms']*1e3, r['frac'], (g['link_us_per_frame'] or {'avg':0})['avg']))" "$1"; }
 for cap in 2048 1024; do
   for m in beside-strip beside-mfma; do
-    YSMR_THRESHOLD_MODE=$m python3 $R/bench.py --steps 20 --warmup 5 --cpu-sample 0 --capacity $cap --max-det $cap 2>/dev/null | show "capacity $cap $m"
+    YSMR_THRESHOLD_MODE=$m python3 $R/bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --capacity $cap --max-det $cap 2>/dev/null | show "capacity $cap $m"
   done
-  [ -f $R/scripts/var_tm_HALF.so ] && YSMR_HIP_LIB=$R/scripts/var_tm_HALF.so YSMR_THRESHOLD_MODE=beside-mfma python3 $R/bench.py --steps 20 --warmup 5 --cpu-sample 0 --capacity $cap --max-det $cap 2>/dev/null | show "capacity $cap beside-mfma, half-row 8-wave build"
+  [ -f $R/scripts/var_tm_HALF.so ] && YSMR_HIP_LIB=$R/scripts/var_tm_HALF.so YSMR_THRESHOLD_MODE=beside-mfma python3 $R/bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --capacity $cap --max-det $cap 2>/dev/null | show "capacity $cap beside-mfma, half-row 8-wave build"
 done

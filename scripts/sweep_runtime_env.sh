@@ -2,7 +2,7 @@
 # End-to-end frames/s against HIP runtime switches that touch how a launch reaches the GPU (kernel arguments, fences,
 # signals).  The link is one short kernel per frame, so the launch path is on the critical path.  Run through gpurun.
 R=$GRAFT_REPO_ROOT
-run() { echo -n "$*: "; timeout -k 5 90 env "$@" python3 $R/bench.py --steps 20 --warmup 5 --cpu-sample 0 2>/dev/null | python3 -c "
+run() { echo -n "$*: "; timeout -k 5 90 env "$@" python3 $R/bench.py --full --steps 20 --warmup 5 --cpu-sample 0 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read()); g = d['diagnostics']
 print(round(d['value']), 'frames/s  link', round(g['link_us_per_frame']['avg'], 2), 'us/frame  host issue', round(g['link_host_issue_us_per_frame']['p50'], 2), 'us/frame (p50)')"; echo; }

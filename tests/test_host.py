@@ -551,8 +551,12 @@ def test_ysmr_multiprocess_stays_in_process_once_the_gpu_is_initialised(tmp_path
 def test_worker_selects_the_device_of_its_job(monkeypatch):
     """_worker makes its job's GPU current before anything is allocated (a fresh worker's current device
     is cuda:0 whatever GPU the job was dealt to)."""
+    import torch
     from ysmr_amd import _lib, main
     seen = []
+    # a host with six or more GPUs, whatever this one has (with fewer, _visible folds cuda:5 onto a device it sees)
+    monkeypatch.setattr(torch._C, "_cuda_getDeviceCount", lambda: 8, raising=False)
+    monkeypatch.setattr(torch.cuda, "device_count", lambda: 8)
 
     class Ctx:
         def __init__(self, dev): self.dev = dev
