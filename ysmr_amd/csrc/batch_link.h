@@ -7,13 +7,15 @@
 //
 //   detections   k_bgrid (one workgroup per frame, the whole batch at once, before this kernel) bins every frame's
 //                detections into a uniform grid of cells (counting sort) and leaves header | cell starts (u16) |
-//                centres in cell order | their column numbers (u16) as one contiguous block per frame; this kernel
+//                centres in cell order | their column numbers (u16) | candidates per cell as one contiguous block per frame; this kernel
 //                brings the block of frame f+1 into LDS by LDS-DMA while it works on frame f.
-//   row minimum  tracker.py:151-163 reads only D.min(1) and D.argmin(1): a lane looks at the 3 x 3 cells around its
-//                prediction, in float, and evaluates the winner once in float64 (bl_search); what float cannot decide
-//                -- a candidate a hair from the best, a nearer detection possibly outside the block -- the wave settles
-//                exactly over all detections (bl_search_wave: rowmin_wave's tie rule, lowest column among equal ROUNDED
-//                distances).
+//   row minimum  tracker.py:151-163 reads only D.min(1) and D.argmin(1): a lane reads the candidate list k_bgrid left for
+//                its prediction's cell (every detection that can be nearest to a point of the cell, <= 8), in float, and
+//                evaluates the winner once in float64 (bl_search); outside the grid, in a cell with more candidates, or
+//                in frames of more than 600 detections (no lists) it looks at the 3 x 3 cells around the prediction
+//                (bl_search_block); what float cannot decide -- a candidate a hair from the best, a nearer detection
+//                possibly outside the block -- the wave settles exactly over all detections (bl_search_wave:
+//                rowmin_wave's tie rule, lowest column among equal ROUNDED distances).
 //   claims       the winner of a detection column is the proposer with the smallest (distance, id): two LDS atomicMin
 //                rounds (ids ascend with table rows, so (distance, id) orders like the reference's (distance, row)).
 //   lifecycle    ageing / deregistration per lane; a lane that loses its track is simply free; new tracks take free
@@ -46,19 +48,33 @@
 // (BL_* constants and struct BatchDev: track.hip, next to TrackerDev -- the host handle holds one)
 
 // ---- a frame's detections as this kernel wants them: one block of dwords per frame ------------------------------
-//   [0, 16)            header: x0, y0, cell, 1 / cell (f32), cells per side G, m (i32)
+//   [0, 16)            header: x0, y0, cell, 1 / cell (f32), cells per side G, m, candidates per cell (0: no lists) (i32)
 //   [16, 16 + SW)      start[G * G + 1] as u16: first item of each cell (row-major), the last entry = m
-//   [.., + 2 * MP)     centres (x, y) f32 of the detections in cell order;  MP = m rounded up to 8
+//   [.., + 2 * MP)     centres (x, y) f32 of the detections in cell order;  MP = m + 1 rounded up to 8 (entry m and the
+//                      rest: 1e30, far from everything -- the sentinel the candidate lists are padded with)
 //   [.., + MP / 2)     their column numbers as u16
+//   [.., + 4 G G)      G <= 32 only: per cell BL_LIST u16 positions in the cell-ordered centres -- every detection that can
+//                      be nearest to, or within the float tie band of the nearest to, a point of the cell (k_bgrid, below),
+//                      ascending, padded with m; 0xFFFF first: more than BL_LIST, the cell's lanes search the 3 x 3 block
 // (cells per side so that a cell holds ~0.45 detections: the three cells of a row of the 3 x 3 block around a prediction
 // then hold more than five candidates once in 200 rows, and the block reaches one cell -- ~1.7 mean nearest-neighbour
 // distances -- beyond the prediction's own cell)
+constexpr int BL_LIST = 8;        // candidates per cell: one ds_read_b128 per lane
 __host__ __device__ inline int bl_grid_n(int m) { return m <= 128 ? 16 : (m <= 600 ? 32 : (m <= 1300 ? 48 : 64)); }
+// (the lists of 48 x 48 cells would take 36 KB per block: two of them beside the tables of max_det = 2048 do not fit a
+// compute unit's 160 KB; those frames keep the 3 x 3 search)
+__host__ __device__ inline bool bl_has_lists(int m) { return bl_grid_n(m) <= 32; }
 __host__ __device__ inline int bl_start_dwords(int G) { return ((G * G + 2) / 2 + 3) / 4 * 4; }
 __host__ __device__ inline int bl_pad8(int m) { return (m + 7) / 8 * 8; }
+__host__ __device__ inline int bl_mp(int m) { return bl_pad8(m + 1); }
+__host__ __device__ inline int bl_list_off(int m)      // dword offset of the lists in the block (a multiple of 4)
+{
+    return 16 + bl_start_dwords(bl_grid_n(m)) + 2 * bl_mp(m) + bl_mp(m) / 2;
+}
 __host__ __device__ inline int bl_grid_dwords(int m)   // rounded up to whole 1-KiB pieces (one LDS-DMA wave-instruction)
 {
-    const int raw = 16 + bl_start_dwords(bl_grid_n(m)) + 2 * bl_pad8(m) + bl_pad8(m) / 2;
+    const int G = bl_grid_n(m);
+    const int raw = bl_list_off(m) + (bl_has_lists(m) ? G * G * BL_LIST / 2 : 0);
     return (raw + 255) / 256 * 256;
 }
 __host__ __device__ inline int bl_grid_dwords_max(int max_det)
@@ -75,6 +91,100 @@ __host__ __device__ inline int bl_grid_dwords_max(int max_det)
 // in LDS and leaves with 16-byte stores: one round of loads and one of stores instead of the five dependent round trips of
 // the first version (35 us per batch beside the next batch's detection kernels).
 constexpr int BG_THREADS = 256, BG_PER = 10;      // 2560 >= the 2456 detections a one-launch link serves
+constexpr int BG_CAND = 32;                       // candidates of a cell before the pruning (more: the cell is flagged)
+
+// The candidate list of cell c (G <= 32).  R = the cell's rectangle grown by e on every side: a prediction that bl_search
+// places in cell c lies in R (below).  Every point p of R has a detection within U = min over d of maxdist(d, R) -- found by
+// a walk over rings of cells around c, which stops once no farther ring can hold a detection nearer than that -- so only
+// detections with mindist(d, R) <= U + 1 px can matter: those are gathered (ascending, row-runs of cells), then pruned.
+// d is left out when another candidate d' is nearer at EVERY point of R by the margin below,
+//     s_d(p) > (1 + 3e-5) s_d'(p) + 0.6 px^2        (s: squared distance),
+// which is tested at the four corners only: s_d - (1 + eps) s_d' = -eps |p|^2 + (linear in p) is concave, so its minimum
+// over a rectangle lies at a corner.  Such a d is not the float64 argmin of any p in R, and it lies outside bl_search's float
+// tie band (s <= best + 0.2 + 5e-6 best, on float distances each off by at most 0.1 + 3e-6 s for coordinates below 4096)
+// around it: s_d,f >= (1 - 3e-6) s_d - 0.1 > s_d',f (1 + 5e-6) + 0.2 needs eps > 1.2e-5 and 0.4 px^2 -- the rest covers the
+// float arithmetic here (corners to ~1e-3 px: below 2e-3 + 1.3e-6 s per distance).  The same bound, in distances, sets the
+// gathering's 1 px.  The pruned set is never empty (in float too, "nearer at a corner by the margin" cannot go round in a
+// circle), and at most a few detections per cell survive: uniform frames of 500 detections keep <= BL_LIST in 99.7 % of cells.
+// e: a prediction's cell is floor((fx - x0) * inv) in float, fx = (float)px: off by |fx - px| <= 2.4e-4 px, plus 2.4e-4 px
+// for fx - x0 and ~1e-5 cells for the product -- e = 4e-3 px + 2e-4 cells covers that and the corners' own rounding here.
+__device__ __forceinline__ void bl_cell_list(int c, int G, int m, float x0, float y0, float cell, float inv, const unsigned short *start16,
+                                             const float2 *xy, unsigned short *list16, unsigned short *cand)
+{
+    const int cx = c % G, cy = c / G;
+    const float e = 4e-3f + 2e-4f * cell;
+    const float ax = x0 + (float)cx * cell - e, bx = x0 + (float)(cx + 1) * cell + e;
+    const float ay = y0 + (float)cy * cell - e, by = y0 + (float)(cy + 1) * cell + e;
+    // U^2: rings 0, 1, 2, ... (a detection of ring r + 1 is at least (r + 1) cells from the rectangle's far side)
+    float u2 = 3.0e38f;
+    int ju = 0;                 // the detection that sets U: tried first as the nearer one in the pruning
+    auto far2 = [&](int a, int b) {
+        for (int j = a; j < b; ++j) {
+            const float2 d = xy[j];
+            const float dx = fmaxf(fabsf(d.x - ax), fabsf(d.x - bx)), dy = fmaxf(fabsf(d.y - ay), fabsf(d.y - by));
+            const float v = dx * dx + dy * dy;
+            ju = v < u2 ? j : ju;
+            u2 = fminf(u2, v);
+        }
+    };
+    for (int r = 0; r < G; ++r) {
+        const int xl = max(cx - r, 0), xh = min(cx + r, G - 1);
+        for (int y = max(cy - r, 0); y <= min(cy + r, G - 1); ++y) {
+            if (y == cy - r || y == cy + r) far2(start16[y * G + xl], start16[y * G + xh + 1]);
+            else {
+                if (cx - r >= 0) far2(start16[y * G + cx - r], start16[y * G + cx - r + 1]);
+                if (cx + r < G) far2(start16[y * G + cx + r], start16[y * G + cx + r + 1]);
+            }
+        }
+        const float reach = (float)(r + 1) * cell;
+        if (u2 <= reach * reach) break;
+    }
+    // the candidates: mindist(d, R) <= T, from the cells whose float assignment can hold such a detection
+    const float T = sqrtf(u2) * 1.0001f + 1.0f, T2 = T * T;
+    const int rho = min((int)((T + e) * inv) + 2, G);
+    int n = 0;
+    for (int y = max(cy - rho, 0); y <= min(cy + rho, G - 1); ++y) {
+        const int a = start16[y * G + max(cx - rho, 0)], b = start16[y * G + min(cx + rho, G - 1) + 1];
+        for (int j = a; j < b; ++j) {
+            const float2 d = xy[j];
+            const float dx = fmaxf(fmaxf(ax - d.x, d.x - bx), 0.f), dy = fmaxf(fmaxf(ay - d.y, d.y - by), 0.f);
+            if (dx * dx + dy * dy <= T2) {
+                if (n < BG_CAND) cand[n * BG_THREADS] = (unsigned short)j;
+                ++n;
+            }
+        }
+    }
+    // the pruning: d_i stays unless some d_k is nearer by the margin at all four corners (any detection will do as d_k;
+    // the one that sets U removes most candidates at once, the others are tried after it)
+    int kept = 0;
+    const float2 du = xy[ju];
+    const float ua = ax - du.x, ub = bx - du.x, va = ay - du.y, vb = by - du.y;
+    const float eps = 1.00003f, beta = 0.6f;
+    const float u0 = (ua * ua + va * va) * eps + beta, u1 = (ub * ub + va * va) * eps + beta;
+    const float u2c = (ua * ua + vb * vb) * eps + beta, u3 = (ub * ub + vb * vb) * eps + beta;
+    if (n <= BG_CAND)
+        for (int i = 0; i < n; ++i) {
+            const int ji = cand[i * BG_THREADS];
+            const float2 di = xy[ji];
+            const float xa = ax - di.x, xb = bx - di.x, ya = ay - di.y, yb = by - di.y;
+            const float s0 = xa * xa + ya * ya, s1 = xb * xb + ya * ya, s2 = xa * xa + yb * yb, s3 = xb * xb + yb * yb;
+            bool beaten = ji != ju && s0 > u0 && s1 > u1 && s2 > u2c && s3 > u3;
+            for (int k = 0; k < n && !beaten; ++k) {
+                const float2 dk = xy[cand[k * BG_THREADS]];
+                const float ka = ax - dk.x, kb = bx - dk.x, la = ay - dk.y, lb = by - dk.y;
+                beaten = k != i && s0 > (ka * ka + la * la) * eps + beta && s1 > (kb * kb + la * la) * eps + beta &&
+                         s2 > (ka * ka + lb * lb) * eps + beta && s3 > (kb * kb + lb * lb) * eps + beta;
+            }
+            if (!beaten) {
+                if (kept < BL_LIST) list16[c * BL_LIST + kept] = (unsigned short)ji;
+                ++kept;
+            }
+        }
+    if (n > BG_CAND || kept > BL_LIST) list16[c * BL_LIST] = 0xFFFFu;
+    else
+        for (int k = kept; k < BL_LIST; ++k) list16[c * BL_LIST + k] = (unsigned short)m;
+}
+
 __global__ __launch_bounds__(BG_THREADS) void k_bgrid(const float *__restrict__ det_all, const int32_t *__restrict__ det_count,
                                                       int max_det, char *grid, unsigned grid_stride)
 {
@@ -83,13 +193,15 @@ __global__ __launch_bounds__(BG_THREADS) void k_bgrid(const float *__restrict__ 
     __shared__ float s_red[4][4];
     __shared__ int s_wave_sum[4];
     const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    __shared__ unsigned short s_cand[BG_CAND][BG_THREADS];      // a cell's candidates, per thread
     const float *det = det_all + (size_t)f * max_det * 5;
     int m = det_count[f];
     m = m < 0 ? 0 : (m > max_det ? max_det : m);
     const int G = bl_grid_n(m), cells = G * G;
     unsigned short *start16 = reinterpret_cast<unsigned short *>(s_out + 16);
     float2 *xy = reinterpret_cast<float2 *>(s_out + 16 + bl_start_dwords(G));
-    unsigned short *items = reinterpret_cast<unsigned short *>(s_out + 16 + bl_start_dwords(G) + 2 * bl_pad8(m));
+    unsigned short *items = reinterpret_cast<unsigned short *>(s_out + 16 + bl_start_dwords(G) + 2 * bl_mp(m));
+    unsigned short *list16 = reinterpret_cast<unsigned short *>(s_out + bl_list_off(m));
     float x[BG_PER], y[BG_PER];
 #pragma unroll
     for (int k = 0; k < BG_PER; ++k) {
@@ -123,7 +235,7 @@ __global__ __launch_bounds__(BG_THREADS) void k_bgrid(const float *__restrict__ 
     if (tid == 0) {
         float *h = reinterpret_cast<float *>(s_out);
         h[0] = x0; h[1] = y0; h[2] = cell; h[3] = inv;
-        s_out[4] = (uint32_t)G; s_out[5] = (uint32_t)m;
+        s_out[4] = (uint32_t)G; s_out[5] = (uint32_t)m; s_out[6] = bl_has_lists(m) ? BL_LIST : 0;
     }
     int cell_of[BG_PER];
 #pragma unroll
@@ -157,7 +269,7 @@ __global__ __launch_bounds__(BG_THREADS) void k_bgrid(const float *__restrict__ 
         }
     if (tid == BG_THREADS - 1) { start16[cells] = (unsigned short)m; start16[cells + 1] = 0; }
     // (the padding of the lists reads as far away, should a lane ever look at it)
-    for (int j = m + tid; j < bl_pad8(m); j += BG_THREADS) { xy[j] = make_float2(1.0e30f, 1.0e30f); items[j] = 0; }
+    for (int j = m + tid; j < bl_mp(m); j += BG_THREADS) { xy[j] = make_float2(1.0e30f, 1.0e30f); items[j] = 0; }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < BG_PER; ++k) {
@@ -169,6 +281,10 @@ __global__ __launch_bounds__(BG_THREADS) void k_bgrid(const float *__restrict__ 
         }
     }
     __syncthreads();
+    if (bl_has_lists(m) && m > 0) {
+        for (int c = tid; c < cells; c += BG_THREADS) bl_cell_list(c, G, m, x0, y0, cell, inv, start16, xy, list16, &s_cand[0][tid]);
+        __syncthreads();
+    }
     uint4 *out = reinterpret_cast<uint4 *>(grid + (size_t)grid_stride * f);
     const uint4 *img = reinterpret_cast<const uint4 *>(s_out);
     for (int i = tid; i < bl_grid_dwords(m) / 4; i += BG_THREADS) out[i] = img[i];
@@ -378,7 +494,7 @@ struct BlNear { double s; float zx, zy; int col; bool done; };
 extern __shared__ __attribute__((aligned(16))) unsigned long long bl_lds[];
 __device__ __forceinline__ uint32_t *bl_u32(int dword_off) { return reinterpret_cast<uint32_t *>(bl_lds) + dword_off; }
 struct BlGridView {
-    int start, xy, items, G;       // dword offsets into bl_lds; cells per side
+    int start, xy, items, lists, G;      // dword offsets into bl_lds (lists: -1, none); cells per side
     float x0, y0, cell, inv;
     __device__ __forceinline__ int start_at(int i) const { return reinterpret_cast<const unsigned short *>(bl_u32(start))[i]; }
     __device__ __forceinline__ int item_at(int i) const { return reinterpret_cast<const unsigned short *>(bl_u32(items))[i]; }
@@ -391,7 +507,8 @@ __device__ __forceinline__ BlGridView bl_grid_view(int buf, int m)     // buf: d
     g.G = bl_grid_n(m);
     g.start = buf + 16;
     g.xy = buf + 16 + bl_start_dwords(g.G);
-    g.items = buf + 16 + bl_start_dwords(g.G) + 2 * bl_pad8(m);
+    g.items = buf + 16 + bl_start_dwords(g.G) + 2 * bl_mp(m);
+    g.lists = bl_has_lists(m) ? buf + bl_list_off(m) : -1;
     g.x0 = hdr[0]; g.y0 = hdr[1]; g.cell = hdr[2]; g.inv = hdr[3];
     return g;
 }
@@ -414,7 +531,7 @@ __device__ __forceinline__ uint32_t bl_med3(uint32_t a, uint32_t b, uint32_t c)
     asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
-__device__ __forceinline__ BlNear bl_search(const BlGridView &g, double px, double py, int m)
+__device__ __forceinline__ BlNear bl_search_block(const BlGridView &g, double px, double py, int m)
 {
     constexpr int R = 3, C = 5;
     const int G = g.G;
@@ -495,6 +612,50 @@ __device__ __forceinline__ BlNear bl_search(const BlGridView &g, double px, doub
     r.zx = cw.x; r.zy = cw.y;
     r.col = g.item_at(found ? bq : 0);
     r.done = found && inside && !(second <= band);     // (hi = 0xFFFFFFFF reads as a NaN: no second candidate)
+    return r;
+}
+
+// The same from the candidate list of the prediction's cell (frames with G <= 32, predictions inside the grid): one LDS
+// round for the list, one for the centres, eight keys as above -- the slot is the list position -- and no bounds, masks or
+// outside test: the list holds the float64 argmin of every point of the cell and every detection within the float band of
+// it (k_bgrid: bl_cell_list), so what it leaves open is what the 3 x 3 block would (the band), and that goes to the wave.
+// A lane outside the grid or in a flagged cell takes bl_search_block; the wave runs it only when some lane needs it.
+__device__ __forceinline__ BlNear bl_search(const BlGridView &g, double px, double py, int m)
+{
+    const int G = g.G;
+    const float fx = (float)px, fy = (float)py;
+    const int cx = (int)floorf((fx - g.x0) * g.inv), cy = (int)floorf((fy - g.y0) * g.inv);
+    bool listed = g.lists >= 0 && cx >= 0 && cx < G && cy >= 0 && cy < G;
+    uint4 l = make_uint4(0u, 0u, 0u, 0u);
+    if (listed) l = reinterpret_cast<const uint4 *>(bl_u32(g.lists))[cy * G + cx];
+    listed = listed && (l.x & 0xFFFFu) != 0xFFFFu;
+    BlNear r;
+    if (listed) {
+        const uint32_t w[4] = {l.x, l.y, l.z, l.w};
+        float2 c[BL_LIST];
+#pragma unroll
+        for (int k = 0; k < BL_LIST; ++k) c[k] = g.xy_at((w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu);
+        __builtin_amdgcn_sched_barrier(0);
+        uint32_t lo = 0xFFFFFFFFu, hi = 0xFFFFFFFFu;
+#pragma unroll
+        for (int k = 0; k < BL_LIST; ++k) {
+            const uint32_t key = (__float_as_uint(bl_dist2f(fx, fy, c[k])) & 0xFFFFFFF0u) | (uint32_t)k;
+            hi = bl_med3(lo, hi, key);
+            lo = min(lo, key);
+        }
+        const float best = __uint_as_float(lo & 0xFFFFFFF0u), second = __uint_as_float(hi & 0xFFFFFFF0u);
+        const float band = best + (0.2f + 5e-6f * best);
+        const uint32_t slot = lo & 15u;
+        const uint32_t wd = (slot & 4u) ? ((slot & 2u) ? l.w : l.z) : ((slot & 2u) ? l.y : l.x);
+        const int bq = (int)((wd >> (16u * (slot & 1u))) & 0xFFFFu);
+        const float2 cw = g.xy_at(bq);
+        r.s = bl_dist2(px, py, cw);
+        r.zx = cw.x; r.zy = cw.y;
+        r.col = g.item_at(bq);
+        r.done = !(second <= band);      // (a padding slot is 1e30 away: its distance is +inf, never within the band)
+    } else {
+        r = bl_search_block(g, px, py, m);
+    }
     return r;
 }
 
