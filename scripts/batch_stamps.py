@@ -19,6 +19,10 @@ NW = int(os.environ.get("BL_WAVES", "16"))
 buf = (ctypes.c_ulonglong * (NW * 16))()
 names = ["dma issue", "search + key atomic", "barrier A", "clear next tables + id atomic", "barrier B", "claims / ageing / registration",
          "filter bank", "wait vmcnt(0)", "barrier D", "ranks + row"]
+# per wave over the launch's frames (g_bcounts): how often each rarely taken path ran
+count_names = ["wave-frames with a lane on the 3 x 3 block search", "lanes on the 3 x 3 block search",
+               "wave-frames seeding a new track's filter bank", "wave-frames with a grown filter bank (old track)",
+               "frames with registration", "wave-frames refreshing the sums from the ring", "frames with deaths", "deaths"]
 acc = []
 # BESIDE=1: the stamped launch runs while another stream loops over the matrix-pipe threshold kernel on 248 workgroups, as
 # in the pipeline (which phase of a frame the memory system's load stretches)
@@ -47,6 +51,12 @@ for rep in range(12 if beside else 6):
     rt0, rt1, mt0, mt1 = int(full[0, 15]), int(full[1, 15]), int(full[2, 15]), int(full[3, 15])
     if rt1 > rt0:
         print(f"   shader clock over frames 8..56: {(mt1 - mt0) / (rt1 - rt0) * 100:.0f} MHz; {(rt1 - rt0) / 100 / 48:.2f} us and {(mt1 - mt0) / 48:.0f} cycles per frame")
+    if hasattr(L, "ysmr_debug_read_bcounts"):
+        cnt = (ctypes.c_ulonglong * (NW * 8))()
+        L.ysmr_debug_read_bcounts(cnt)
+        cn = np.array(cnt[:], dtype=np.int64).reshape(NW, 8)
+        for k, what in enumerate(count_names):
+            print(f"   {what:58s}", cn[:, k].tolist())
     print(f"rep {rep}: launch pair {t0.elapsed_time(t1) * 1e3:.1f} us for {B} frames; frame (wave 0) {a[0, 10] - a[0, 0]} cycles")
 a = np.mean(np.array(acc), axis=0) if beside else np.median(np.array(acc), axis=0)
 d = np.diff(a, axis=1)

@@ -745,6 +745,11 @@ __device__ unsigned long long g_bstamps[BL_WAVES][16];
 #define YSMR_BL_FRAME 40
 #endif
 #define BLSTAMP(k) do { if (f == YSMR_BL_FRAME && lane == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); g_bstamps[wave][k] = t_; } } while (0)
+// per wave, over the launch's frames, how often a rarely taken path ran: 0 wave-frames with a lane on the 3 x 3 block search,
+// 1 such lanes, 2 wave-frames with a lane seeding a new track's filter bank, 3 with a lane whose filter bank grew (not new),
+// 4 frames with registration, 5 wave-frames refreshing the window sums from the ring, 6 frames with deaths, 7 deaths
+__device__ unsigned long long g_bcounts[BL_WAVES][8];
+#define BLCOUNT(k, cond) do { const unsigned long long b_ = __ballot(cond); if (lane == 0 && b_) g_bcounts[wave][k] += 1; } while (0)
 #else
 #define BLSTAMP(k) do {} while (0)
 #endif
@@ -785,6 +790,11 @@ __device__ __forceinline__ BlKernArgsPtr bl_kernargs()
     asm volatile("" : "+s"(p));          // (opaque: a load through it is not merged with the preloaded arguments)
     return p;
 }
+
+// s_waitcnt vmcnt(0) through the builtin: the compiler's own wait insertion then knows that every vector memory access of
+// the wave is complete here.  Inline assembly is opaque to it: behind one, the claimed box's load still counted as
+// outstanding, and the compiler waited for vmcnt(0) again after the row store -- a store's round trip in every frame.
+__device__ __forceinline__ void bl_wait_vmem() { __builtin_amdgcn_s_waitcnt(0x0F70); }     // vmcnt 0, expcnt 7, lgkmcnt 15
 
 __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
 {
@@ -851,15 +861,24 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
     };
     dma(0);
     for (int c = tid; c < sh.cnt[0]; c += BL_THREADS) { key_at(0)[c] = ~0ull; cid_at(0)[c] = 0xFFFFFFFFu; }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    bl_wait_vmem();
     __syncthreads();
 
     for (int f = 0; f < batch; ++f) {
         const int par = f & 1;
         const int m = sh.cnt[f], m_next = f + 1 < batch ? sh.cnt[f + 1] : 0;
         BLSTAMP(0);
-        if (((frame0 + f) & (BL_REFRESH - 1)) == 0 && S.alive && t.use_gsff)      // (uniform but for `alive`: see bl_sums_from_ring)
+#ifdef YSMR_STAMPS
+        if (f == 0 && lane == 0)
+            for (int k = 0; k < 8; ++k) g_bcounts[wave][k] = 0;
+        BLCOUNT(5, ((frame0 + f) & (BL_REFRESH - 1)) == 0 && S.alive && t.use_gsff);
+#endif
+        if (((frame0 + f) & (BL_REFRESH - 1)) == 0 && S.alive && t.use_gsff) {     // (uniform but for `alive`: see bl_sums_from_ring)
             bl_sums_from_ring(S, bd, tid, head, t.n_i[0], nf > 1 ? t.n_i[1] : 0, nf > 2 ? t.n_i[2] : 0);
+            // (nothing of the ring left outstanding in the compiler's books: it would otherwise wait for vmcnt(0) -- last
+            // frame's row stores -- in the search of every frame)
+            bl_wait_vmem();
+        }
         if (f + 1 < batch) dma(f + 1);
         BLSTAMP(1);
         // ---- each track proposes its nearest detection (tracker.py:151-163)
@@ -868,6 +887,19 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         BlNear nr{0.0, 0.f, 0.f, 0, true};
         unsigned long long key = 0;
         if (propose) nr = bl_search(gv, S.px, S.py, m);
+#ifdef YSMR_STAMPS
+        {   // (bl_search's test for the candidate list, repeated)
+            bool block = false;
+            if (propose) {
+                const int cx = (int)floorf(((float)S.px - gv.x0) * gv.inv), cy = (int)floorf(((float)S.py - gv.y0) * gv.inv);
+                block = gv.lists < 0 || cx < 0 || cx >= gv.G || cy < 0 || cy >= gv.G ||
+                        (reinterpret_cast<const uint4 *>(bl_u32(gv.lists))[cy * gv.G + cx].x & 0xFFFFu) == 0xFFFFu;
+            }
+            BLCOUNT(0, block);
+            const unsigned long long bb = __ballot(block);
+            if (lane == 0) g_bcounts[wave][1] += __popcll(bb);
+        }
+#endif
         BLSTAMP(11);
         {   // the lanes the 5 x 5 cells did not settle, one after the other, by the whole wave
             unsigned long long todo = __ballot(propose && !nr.done);
@@ -951,47 +983,54 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         }
         // ---- registration (tracker.py:135-137, 212-217): unclaimed columns become tracks, in CPython set order
         int n_new = 0, n_new_all = 0;
+#ifdef YSMR_STAMPS
+        BLCOUNT(4, m > 0 && (n == 0 || n < m));
+#endif
         if (m > 0 && (n == 0 || n < m)) {        // (uniform; nobody was aged in such a frame)
-            int *unused = reinterpret_cast<int *>(key_at(par ^ 1)), *newcols = unused + mdp;
+            // (the thread, its wave and lane as values of this frame: the compiler hoisted the comparisons with them out of
+            // the frame loop, a pair of scalar registers each, held for the whole launch and spilled into vector lanes)
+            int tl = tid, wv = wave, ln = lane, mp = mdp;
+            asm volatile("" : "+v"(tl), "+s"(wv), "+v"(ln), "+s"(mp));
+            int *unused = reinterpret_cast<int *>(key_at(par ^ 1)), *newcols = unused + mp;
             uint32_t *list = cid_at(par ^ 1);
             __syncthreads();
             if (n == 0) {
-                for (int c = tid; c < m; c += BL_THREADS) newcols[c] = c;
+                for (int c = tl; c < m; c += BL_THREADS) newcols[c] = c;
                 n_new_all = m;
             } else {
                 // the unclaimed columns in ascending order: K consecutive columns per thread, ranked by a wave scan
                 const int K = (m + BL_THREADS - 1) / BL_THREADS;
-                const int c0 = tid * K, c1 = min(c0 + K, m);
+                const int c0 = tl * K, c1 = min(c0 + K, m);
                 int cnt = 0;
                 for (int c = c0; c < c1; ++c) cnt += cid_at(par)[c] == 0xFFFFFFFFu;
                 int incl = cnt;
 #pragma unroll
-                for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
-                if (lane == 63) sh.wave_cnt[0][wave] = incl;
+                for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (ln >= d) incl += o; }
+                if (ln == 63) sh.wave_cnt[0][wv] = incl;
                 __syncthreads();
                 int at = incl - cnt, total = 0;
 #pragma unroll
-                for (int k = 0; k < BL_WAVES; ++k) { const int v = sh.wave_cnt[0][k]; at += k < wave ? v : 0; total += v; }
+                for (int k = 0; k < BL_WAVES; ++k) { const int v = sh.wave_cnt[0][k]; at += k < wv ? v : 0; total += v; }
                 for (int c = c0; c < c1; ++c)
                     if (cid_at(par)[c] == 0xFFFFFFFFu) unused[at++] = c;
                 __syncthreads();
                 int cnt_set = cpython_order_lds<BL_THREADS, BL_TABLE>(unused, total, m, sh.used[par], newcols, bl_u32(tab_off), list, sh.set_state);
-                if (cnt_set < 0) { if (tid == 0) atomicOr(bl_kernargs()->t.err, ERR_TRACK_CAPACITY); cnt_set = 0; }
+                if (cnt_set < 0) { if (tl == 0) atomicOr(bl_kernargs()->t.err, ERR_TRACK_CAPACITY); cnt_set = 0; }
                 n_new_all = cnt_set;
             }
             n_new = n_new_all;
             if (n + n_new > seats) {
-                if (tid == 0) atomicOr(bl_kernargs()->t.err, ERR_TRACK_CAPACITY);
+                if (tl == 0) atomicOr(bl_kernargs()->t.err, ERR_TRACK_CAPACITY);
                 n_new = seats - n;
             }
             // free lanes take the new tracks, in lane order
-            const bool free_lane = !S.alive && tid < seats;
+            const bool free_lane = !S.alive && tl < seats;
             const unsigned long long bf = __ballot(free_lane);
-            if (lane == 0) sh.wave_cnt[1][wave] = (int)__popcll(bf);
+            if (ln == 0) sh.wave_cnt[1][wv] = (int)__popcll(bf);
             __syncthreads();
             int fr = (int)__popcll(bf & below);
 #pragma unroll
-            for (int k = 0; k < BL_WAVES; ++k) fr += k < wave ? sh.wave_cnt[1][k] : 0;
+            for (int k = 0; k < BL_WAVES; ++k) fr += k < wv ? sh.wave_cnt[1][k] : 0;
             if (free_lane && fr < n_new) {
                 const int c = newcols[fr];
                 const float *d = bl_kernargs()->det_all + ((size_t)f * md + c) * 5;
@@ -999,15 +1038,19 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
                 box[0] = d[2]; box[1] = d[3]; box[2] = d[4];
                 S.id = next_id + fr; S.rank = n + fr; S.gone = 0;
                 S.alive = true; fresh = true;
-                atomicMax(&sh.top, tid + 1);
+                atomicMax(&sh.top, tl + 1);
             }
             __syncthreads();     // (the lists lived in the next frame's tables)
-            for (int c = tid; c < m_next; c += BL_THREADS) { key_at(par ^ 1)[c] = ~0ull; cid_at(par ^ 1)[c] = 0xFFFFFFFFu; }
+            for (int c = tl; c < m_next; c += BL_THREADS) { key_at(par ^ 1)[c] = ~0ull; cid_at(par ^ 1)[c] = 0xFFFFFFFFu; }
             helpers_from = (sh.top + 63) >> 6;
         }
         // ---- the filter bank (tracker.py:219-227)
         BLSTAMP(6);
         double o0 = z0, o1 = z1;
+#ifdef YSMR_STAMPS
+        const int mode_before = S.mode;
+        BLCOUNT(2, S.alive && t.use_gsff && fresh);
+#endif
         if (S.alive) {
             if (t.use_gsff) {
                 // (the twelve gain constants come out of the scalar cache in every frame: as kernel arguments they sat in 24
@@ -1020,12 +1063,18 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
             else { S.px = z0; S.py = z1; }
         }
         // ---- end of the frame: the next frame's detections have landed, the frame's counts are complete
+#ifdef YSMR_STAMPS
+        BLCOUNT(3, S.alive && t.use_gsff && !fresh && S.mode != mode_before);
+#endif
         BLSTAMP(7);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        bl_wait_vmem();
         BLSTAMP(8);
         __syncthreads();
         BLSTAMP(9);
         const int n_dead = sh.n_dead[par];
+#ifdef YSMR_STAMPS
+        if (lane == 0 && n_dead) { g_bcounts[wave][6] += 1; g_bcounts[wave][7] += n_dead; }
+#endif
         if (n_dead && S.alive)
             for (int k = 0; k < n_dead; ++k) S.rank -= sh.dead_id[par][k] < S.id;
         if (S.alive) { S.info[0] = box[0]; S.info[1] = box[1]; S.info[2] = box[2]; }   // (the claimed box: requested before the filter bank)

@@ -1564,7 +1564,10 @@ template <int THREADS, int TABLE>
 __device__ int cpython_order_lds(const int *unused, int n_unused, int m, int n_used, int *out, uint32_t *table,
                                  uint32_t *list, int *s_state)
 {
-    const int tid = threadIdx.x;
+    // (the thread index as a value of this call: called in a frame loop, the comparisons with it are otherwise hoisted
+    // out of the loop and held in scalar registers for the whole launch)
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
     if ((m >> 2) > n_used) {
         for (int k = tid; k < n_unused; k += THREADS) out[k] = unused[k];
         __syncthreads();
@@ -2343,6 +2346,7 @@ int ysmr_tracker_link_mode(ysmr_tracker *t, int mode)
 
 #ifdef YSMR_STAMPS
 int ysmr_debug_read_bstamps(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bstamps), sizeof(unsigned long long) * BL_WAVES * 16); }
+int ysmr_debug_read_bcounts(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bcounts), sizeof(unsigned long long) * BL_WAVES * 8); }
 #endif
 
 int ysmr_tracker_batched(ysmr_tracker *t) { return t && t->use_batch() ? 1 : 0; }
