@@ -17,12 +17,13 @@ res0 = pipe.det[0].detect(frames[:B]); res1 = pipe.det[1].detect(frames[B:]); to
 L = _lib.lib()
 NW = int(os.environ.get("BL_WAVES", "16"))
 buf = (ctypes.c_ulonglong * (NW * 16))()
-names = ["dma issue", "search + key atomic", "barrier A", "clear next tables + id atomic", "barrier B", "claims / ageing / registration",
-         "filter bank", "wait vmcnt(0)", "barrier D", "ranks + row"]
+names = ["dma issue + clear next keys", "search + key atomic", "barrier A", "key read (+ exact claim path)", "ageing / deregistration",
+         "registration", "filter bank", "wait vmcnt(0)", "end barrier", "ranks + row"]
 # per wave over the launch's frames (g_bcounts): how often each rarely taken path ran
 count_names = ["wave-frames with a lane on the 3 x 3 block search", "lanes on the 3 x 3 block search",
                "wave-frames seeding a new track's filter bank", "wave-frames with a grown filter bank (old track)",
-               "frames with registration", "wave-frames refreshing the sums from the ring", "frames with deaths", "deaths"]
+               "frames with registration", "wave-frames refreshing the sums from the ring", "frames with deaths", "deaths",
+               "frames on the exact claim path (row of wave 0)"]
 acc = []
 # BESIDE=1: the stamped launch runs while another stream loops over the matrix-pipe threshold kernel on 248 workgroups, as
 # in the pipeline (which phase of a frame the memory system's load stretches)
@@ -52,9 +53,9 @@ for rep in range(12 if beside else 6):
     if rt1 > rt0:
         print(f"   shader clock over frames 8..56: {(mt1 - mt0) / (rt1 - rt0) * 100:.0f} MHz; {(rt1 - rt0) / 100 / 48:.2f} us and {(mt1 - mt0) / 48:.0f} cycles per frame")
     if hasattr(L, "ysmr_debug_read_bcounts"):
-        cnt = (ctypes.c_ulonglong * (NW * 8))()
+        cnt = (ctypes.c_ulonglong * (NW * len(count_names)))()
         L.ysmr_debug_read_bcounts(cnt)
-        cn = np.array(cnt[:], dtype=np.int64).reshape(NW, 8)
+        cn = np.array(cnt[:], dtype=np.int64).reshape(NW, len(count_names))
         for k, what in enumerate(count_names):
             print(f"   {what:58s}", cn[:, k].tolist())
     print(f"rep {rep}: launch pair {t0.elapsed_time(t1) * 1e3:.1f} us for {B} frames; frame (wave 0) {a[0, 10] - a[0, 0]} cycles")

@@ -16,8 +16,10 @@
 //                (bl_search_block); what float cannot decide -- a candidate a hair from the best, a nearer detection
 //                possibly outside the block -- the wave settles exactly over all detections (bl_search_wave:
 //                rowmin_wave's tie rule, lowest column among equal ROUNDED distances).
-//   claims       the winner of a detection column is the proposer with the smallest (distance, id): two LDS atomicMin
-//                rounds (ids ascend with table rows, so (distance, id) orders like the reference's (distance, row)).
+//   claims       the winner of a detection column is the proposer with the smallest (distance, id).  Table rows ascend
+//                with the ids, so ONE LDS atomicMin on (squared distance without its ten lowest bits, table row) settles a
+//                column; a frame in which two proposals of a column come closer than that key resolves -- an exact tie,
+//                mostly -- repeats the claims exactly: full distance, rounded roots, id (k_batch: "claims").
 //   lifecycle    ageing / deregistration per lane; a lane that loses its track is simply free; new tracks take free
 //                lanes, in CPython set order of the unclaimed columns (cpython_order_lds).  Table ROWS (the order of the
 //                reference's OrderedDict = ascending id = the order of a frame's rows) are kept as a per-lane rank:
@@ -35,7 +37,7 @@
 //                so rounding drift is bounded by 64 updates: ~1e-11 px, the size of a from-scratch sum's own rounding.
 //   rows         one 40-byte ysmr_row per live lane at rows[base + rank], fire and forget.
 //
-// Three workgroup barriers per frame (after each atomic round, and at the end of the frame, where the next frame's
+// Two workgroup barriers per frame (after the atomic round, and at the end of the frame, where the next frame's
 // detections must have landed).  Why not the history in registers (the first build of this kernel: 158 registers per
 // track): 512 tracks fill a compute unit's register file, BASELINE configs[2] holds up to 535; and a frame then costs the
 // 186 float64 operations of re-summing and shifting 62 values per track, on ONE unit's float64 pipe (7.4 us per frame).
@@ -739,6 +741,7 @@ __device__ __forceinline__ BlNear bl_search_wave(const BlGridView &g, double px,
 }
 
 // ---- the kernel ----------------------------------------------------------------------------------------------------
+constexpr int BL_COUNTS = 9;
 #ifdef YSMR_STAMPS
 __device__ unsigned long long g_bstamps[BL_WAVES][16];
 #ifndef YSMR_BL_FRAME
@@ -747,8 +750,9 @@ __device__ unsigned long long g_bstamps[BL_WAVES][16];
 #define BLSTAMP(k) do { if (f == YSMR_BL_FRAME && lane == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); g_bstamps[wave][k] = t_; } } while (0)
 // per wave, over the launch's frames, how often a rarely taken path ran: 0 wave-frames with a lane on the 3 x 3 block search,
 // 1 such lanes, 2 wave-frames with a lane seeding a new track's filter bank, 3 with a lane whose filter bank grew (not new),
-// 4 frames with registration, 5 wave-frames refreshing the window sums from the ring, 6 frames with deaths, 7 deaths
-__device__ unsigned long long g_bcounts[BL_WAVES][8];
+// 4 frames with registration, 5 wave-frames refreshing the window sums from the ring, 6 frames with deaths, 7 deaths,
+// 8 frames on the exact claim path
+__device__ unsigned long long g_bcounts[BL_WAVES][BL_COUNTS];
 #define BLCOUNT(k, cond) do { const unsigned long long b_ = __ballot(cond); if (lane == 0 && b_) g_bcounts[wave][k] += 1; } while (0)
 #else
 #define BLSTAMP(k) do {} while (0)
@@ -756,6 +760,7 @@ __device__ unsigned long long g_bcounts[BL_WAVES][8];
 struct BlShared {      // static part of the LDS
     int cnt[BL_MAX_BATCH];           // detections per frame (clamped)
     int used[2], n_dead[2];          // per frame parity: claims made, tracks deregistered
+    int tie[2];                      // per frame parity: some column's proposals are too close for the short key
     int dead_id[2][BL_THREADS];      // ids of the tracks deregistered in the frame
     int wave_cnt[2][BL_WAVES];       // registration: per-wave counts of the two ranked lists
     int set_state[2];
@@ -809,8 +814,9 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
     const unsigned long long below = (1ull << lane) - 1ull;
     const int md = t.max_det, mdp = bl_md_padded(md);
     const int bufw = bl_grid_dwords_max(md);
-    // LDS by offset (bl_lds): per frame parity p the smallest proposing distance per column (u64), the winning id per
-    // column (u32) and the frame's detections (k_bgrid's block); the CPython set model's table
+    // LDS by offset (bl_lds): per frame parity p the smallest proposing key per column (u64), the winning id per column
+    // (u32: the exact claim path's second round, and scratch of the registration) and the frame's detections (k_bgrid's
+    // block); the CPython set model's table
     auto key_at = [&](int p) { return bl_lds + p * mdp; };
     auto cid_at = [&](int p) { return bl_u32(4 * mdp + p * mdp); };
     auto buf_off = [&](int p) { return 6 * mdp + p * bufw; };
@@ -829,7 +835,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         if (m > md) { m = md; atomicOr(t.err, ERR_DET_CLAMPED); }
         sh.cnt[f] = m < 0 ? 0 : m;
     }
-    if (tid < 2) { sh.used[tid] = 0; sh.n_dead[tid] = 0; }
+    if (tid < 2) { sh.used[tid] = 0; sh.n_dead[tid] = 0; sh.tie[tid] = 0; }
     if (tid == 0) sh.top = 0;
     BlSeat S;
     bl_seat_blank(S);
@@ -860,7 +866,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         }
     };
     dma(0);
-    for (int c = tid; c < sh.cnt[0]; c += BL_THREADS) { key_at(0)[c] = ~0ull; cid_at(0)[c] = 0xFFFFFFFFu; }
+    for (int c = tid; c < sh.cnt[0]; c += BL_THREADS) key_at(0)[c] = ~0ull;
     bl_wait_vmem();
     __syncthreads();
 
@@ -870,7 +876,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         BLSTAMP(0);
 #ifdef YSMR_STAMPS
         if (f == 0 && lane == 0)
-            for (int k = 0; k < 8; ++k) g_bcounts[wave][k] = 0;
+            for (int k = 0; k < BL_COUNTS; ++k) g_bcounts[wave][k] = 0;
         BLCOUNT(5, ((frame0 + f) & (BL_REFRESH - 1)) == 0 && S.alive && t.use_gsff);
 #endif
         if (((frame0 + f) & (BL_REFRESH - 1)) == 0 && S.alive && t.use_gsff) {     // (uniform but for `alive`: see bl_sums_from_ring)
@@ -880,6 +886,14 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
             bl_wait_vmem();
         }
         if (f + 1 < batch) dma(f + 1);
+        // The next frame's keys are cleared here, by the waves that would otherwise wait at barrier A.  Parity par ^ 1 was
+        // last touched in frame f - 1: its keys were read by the claims and the registration's scan, and the registration
+        // of a frame uses the OTHER parity's tables as scratch -- in frame f - 1 that was parity par, cleared again before
+        // that frame's end barrier; this frame's registration uses par ^ 1 behind barrier A, after these stores, and clears
+        // it again itself.  All of frame f - 1's accesses lie before its end barrier, which every wave has passed; the
+        // exact claim path below touches the tables of parity par only.  Frame f + 1 reads them behind this frame's end
+        // barrier.
+        for (int c = chore_first(); c >= 0 && c < m_next; c += chore_stride()) key_at(par ^ 1)[c] = ~0ull;
         BLSTAMP(1);
         // ---- each track proposes its nearest detection (tracker.py:151-163)
         const bool propose = S.alive && m > 0;
@@ -930,34 +944,64 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
             for (int k = 0; k < BL_NF; ++k)
                 if (k < nf) leave[k] = bl_ring_load(bd, (head - hn[k]) & (BL_HB - 1), tid);
         }
-        if (propose) {      // (round 1 on the SQUARED distance: a non-negative double orders like its bits)
-            key = (unsigned long long)__double_as_longlong(nr.s);
-            atomicMin(&key_at(par)[nr.col], key);
+        // ---- claims (tracker.py:151-189): a column goes to the proposer with the smallest (distance, id)
+        // ONE key per proposal: the bits of the squared distance s without their ten lowest (a non-negative double orders
+        // like its bits), and in their place the lane's table row -- below 768, unique among the live tracks, ascending
+        // with the id (the order the reference breaks ties in, tracker.py:158), as last frame's "ranks + row" or the
+        // registration left it.  The smallest key of a column is its winner unless two proposals are so close that the
+        // dropped bits could matter: their s agree in the 54 bits kept, or differ by one step there (a pair a few ulps
+        // apart can straddle a truncation boundary).  Only then can two different s round to the same root, or the smaller
+        // s belong to the higher row.  Every other key lies at least two steps above the minimum: its s is larger by more
+        // than 2^-43 of it, its root differs, and it loses under the exact rule too.
+        // Such a pair is noticed from what the atomic returns.  Let M be the column's final minimum and X another key
+        // within one step of M.  Whichever of the two did its atomic later got back a value between M (the column never
+        // goes below its final minimum) and the earlier one's key (already in place): a value within the band of both, so
+        // that lane raises the frame's flag.  Keys farther above M need no flag.
+        if (propose) {
+            key = ((unsigned long long)__double_as_longlong(nr.s) & ~0x3FFull) | (unsigned long long)S.rank;
+            const unsigned long long before = atomicMin(&key_at(par)[nr.col], key);
+            if ((before >> 10) - (key >> 10) + 1ull <= 2ull) sh.tie[par] = 1;     // (an empty column: 2^54 - 1, far from every s)
         }
         BLSTAMP(2);
         block_sync<true>();
         BLSTAMP(3);
-        // (the other parity's tables and counters were last read before the end of the previous frame)
-        for (int c = chore_first(); c >= 0 && c < m_next; c += chore_stride()) { key_at(par ^ 1)[c] = ~0ull; cid_at(par ^ 1)[c] = 0xFFFFFFFFu; }
-        if (tid == BL_THREADS - 1) { sh.used[par ^ 1] = 0; sh.n_dead[par ^ 1] = 0; }
-        if (propose) {
-            // the proposers at the column's smallest DISTANCE contend by id (tracker.py:158: ascending row minimum, then
-            // row).  sqrt is monotone, so that is the smallest s -- and, once in a blue moon, an s a few ulps above it
-            // that rounds to the same root: only those take the square roots
-            const unsigned long long kmin = key_at(par)[nr.col];
-            bool tie = key == kmin;
-            if (!tie) {
-                const double smin = __longlong_as_double((long long)kmin);
-                if (nr.s <= smin + smin * 0x1p-48) tie = sqrt(nr.s) == sqrt(smin);
+        // (the other parity's counters were last read behind the end barrier of the previous frame, its flag before it)
+        if (tid == BL_THREADS - 1) { sh.used[par ^ 1] = 0; sh.n_dead[par ^ 1] = 0; sh.tie[par ^ 1] = 0; }
+        // (both reads in one LDS round: every lane reads a key -- column 0 where it proposed nothing -- and the flag rides along)
+        const unsigned long long k_won = key_at(par)[nr.col];
+        const int exact = sh.tie[par];
+        bool mine = propose && k_won == key;
+        if (exact) {
+            // The exact rule, for every column of the frame (uniform: the flag was set before barrier A and stands until
+            // the next frame's): the smallest s in full, then the proposers at the column's smallest DISTANCE contend by
+            // id.  sqrt is monotone, so that is the smallest s -- and an s a few ulps above it that rounds to the same
+            // root: only those take the square roots.  A wave that comes here late may have read a key above that the
+            // clearing had already replaced; its `mine` is set again below.
+#ifdef YSMR_STAMPS
+            if (wave == 0 && lane == 0) g_bcounts[0][8] += 1;
+#endif
+            for (int c = tid; c < m; c += BL_THREADS) { key_at(par)[c] = ~0ull; cid_at(par)[c] = 0xFFFFFFFFu; }
+            block_sync<true>();
+            if (propose) {
+                key = (unsigned long long)__double_as_longlong(nr.s);
+                atomicMin(&key_at(par)[nr.col], key);
             }
-            if (tie) atomicMin(&cid_at(par)[nr.col], (uint32_t)S.id);
+            block_sync<true>();
+            if (propose) {
+                const unsigned long long kmin = key_at(par)[nr.col];
+                bool tie = key == kmin;
+                if (!tie) {
+                    const double smin = __longlong_as_double((long long)kmin);
+                    if (nr.s <= smin + smin * 0x1p-48) tie = sqrt(nr.s) == sqrt(smin);
+                }
+                if (tie) atomicMin(&cid_at(par)[nr.col], (uint32_t)S.id);
+            }
+            block_sync<true>();
+            mine = propose && cid_at(par)[nr.col] == (uint32_t)S.id;
         }
         BLSTAMP(4);
-        block_sync<true>();
-        BLSTAMP(5);
-        // ---- claims (tracker.py:171-189), ageing and deregistration (:95-107, 198-211)
+        // ---- ageing and deregistration (tracker.py:95-107, 198-211)
         const bool age = (m == 0) || (n > 0 && n >= m);
-        const bool mine = propose && cid_at(par)[nr.col] == (uint32_t)S.id;
         double z0 = S.px, z1 = S.py;
         float box[3] = {S.info[0], S.info[1], S.info[2]};
         bool fresh = false, died = false;
@@ -981,6 +1025,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
                 if (died) sh.dead_id[par][at + __popcll(bx & below)] = S.id;
             }
         }
+        BLSTAMP(5);
         // ---- registration (tracker.py:135-137, 212-217): unclaimed columns become tracks, in CPython set order
         int n_new = 0, n_new_all = 0;
 #ifdef YSMR_STAMPS
@@ -1002,7 +1047,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
                 const int K = (m + BL_THREADS - 1) / BL_THREADS;
                 const int c0 = tl * K, c1 = min(c0 + K, m);
                 int cnt = 0;
-                for (int c = c0; c < c1; ++c) cnt += cid_at(par)[c] == 0xFFFFFFFFu;
+                for (int c = c0; c < c1; ++c) cnt += key_at(par)[c] == ~0ull;      // (a column with a proposer has a winner)
                 int incl = cnt;
 #pragma unroll
                 for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (ln >= d) incl += o; }
@@ -1012,7 +1057,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
 #pragma unroll
                 for (int k = 0; k < BL_WAVES; ++k) { const int v = sh.wave_cnt[0][k]; at += k < wv ? v : 0; total += v; }
                 for (int c = c0; c < c1; ++c)
-                    if (cid_at(par)[c] == 0xFFFFFFFFu) unused[at++] = c;
+                    if (key_at(par)[c] == ~0ull) unused[at++] = c;
                 __syncthreads();
                 int cnt_set = cpython_order_lds<BL_THREADS, BL_TABLE>(unused, total, m, sh.used[par], newcols, bl_u32(tab_off), list, sh.set_state);
                 if (cnt_set < 0) { if (tl == 0) atomicOr(bl_kernargs()->t.err, ERR_TRACK_CAPACITY); cnt_set = 0; }
@@ -1041,7 +1086,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
                 atomicMax(&sh.top, tl + 1);
             }
             __syncthreads();     // (the lists lived in the next frame's tables)
-            for (int c = tl; c < m_next; c += BL_THREADS) { key_at(par ^ 1)[c] = ~0ull; cid_at(par ^ 1)[c] = 0xFFFFFFFFu; }
+            for (int c = tl; c < m_next; c += BL_THREADS) key_at(par ^ 1)[c] = ~0ull;
             helpers_from = (sh.top + 63) >> 6;
         }
         // ---- the filter bank (tracker.py:219-227)

@@ -2346,7 +2346,7 @@ int ysmr_tracker_link_mode(ysmr_tracker *t, int mode)
 
 #ifdef YSMR_STAMPS
 int ysmr_debug_read_bstamps(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bstamps), sizeof(unsigned long long) * BL_WAVES * 16); }
-int ysmr_debug_read_bcounts(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bcounts), sizeof(unsigned long long) * BL_WAVES * 8); }
+int ysmr_debug_read_bcounts(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bcounts), sizeof(unsigned long long) * BL_WAVES * BL_COUNTS); }
 #endif
 
 int ysmr_tracker_batched(ysmr_tracker *t) { return t && t->use_batch() ? 1 : 0; }
