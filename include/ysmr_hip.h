@@ -16,7 +16,11 @@
  *   ysmr_components_batch scipy binary_propagation + cv2.findContours + cv2.minAreaRect +
  *                         reshape_result   ysmr/track_eval.py:211-303, ysmr/helper_file.py:1336-1347
  *   ysmr_detect_batch     both of the above in one call
+ *   ysmr_luminosity_batch cv2.boxPoints + cv2.fillPoly + cv2.mean per contour ('include luminosity in tracking
+ *                         calculation')   ysmr/track_eval.py:290-300
  *   ysmr_tracker_*        CentroidTracker.__init__/update   ysmr/tracker.py:37-71, 93-230
+ *                         (ysmr_tracker_dimensions / _update3 / _run3 / _peek3: the same with (x, y, luminosity)
+ *                         centroids, tracker.py:111, 151)
  *                         GaussianSumFIR.correct/predict    ysmr/gsff.py:204-347
  *                         row emission                      ysmr/track_eval.py:313-316
  *   ysmr_gsff_gains       GaussianSumFIR.generate_n_i/compute_lsf_gain  ysmr/gsff.py:87-153
@@ -218,6 +222,36 @@ int ysmr_detect_batch(void *stream, const uint8_t *frames_dev, int batch, int he
                       float *det_dev, int32_t *anchors_dev, int max_det, int32_t *status_dev,
                       int cv_flavour);
 
+/* ---- luminosity: the third tracking coordinate ------------------------------------------------------ */
+
+/* What the reference's frame loop does per contour when 'include luminosity in tracking calculation' is set
+ * (ysmr/track_eval.py:290-300): box = np.intp(cv2.boxPoints(rect)), cv2.fillPoly(mask, [box], 255) on an empty mask,
+ * cv2.mean(gray, mask)[0] / 100 -- the mean gray value under the detection's min-area rectangle, as the third coordinate
+ * the tracker links with.  One launch for a batch; the mask is never stored (csrc/luminosity.hip).
+ *   frames_dev    u8 [batch][height][width][channels], the frames the threshold call read (4-byte aligned; at most 2^24
+ *                 pixels per frame).  channels 3: the gray value is the fixed-point BGR2GRAY of the threshold kernels,
+ *                 YSMR_CV_GRAY_3X in cv_flavour honoured; the other cv_flavour bits are ignored
+ *   det_dev, det_count_dev   as ysmr_components_batch / ysmr_detect_batch leave them: the five values are used as they
+ *                 stand (the angle convention of cv_flavour is already in them)
+ *   lum_dev       f64 [batch][max_det]  mean / 100; 0.0 for a box that covers no pixel of the frame.  Entries past
+ *                 det_count[b] are left UNTOUCHED (as are those of the three arrays below)
+ *   sum_dev, count_dev   u32 [batch][max_det], each may be NULL: the integers the value was made from -- the sum of the gray
+ *                 values under the filled box and the number of its pixels inside the frame
+ *   corners_dev   i32 [batch][max_det][4][2] (x, y), may be NULL, 16-byte aligned: np.intp(boxPoints(rect)); a coordinate
+ *                 beyond +-2^20 is moved there
+ * The fill is OpenCV's (upstream recollection, parity-unpinned like the rest of the image half): the four
+ * edges as 8-connected lines drawn left to right plus the edge table's scanline spans in 16.16 fixed point, clipped to the
+ * frame.  A rectangle of size (0, 0) fills its own pixel. */
+int ysmr_luminosity_batch(void *stream, const uint8_t *frames_dev, int batch, int height, int width, int channels,
+                          const float *det_dev, const int32_t *det_count_dev, int max_det, int cv_flavour, double *lum_dev,
+                          uint32_t *sum_dev, uint32_t *count_dev, int32_t *corners_dev);
+/* HOST function: the same arithmetic -- the code that decides a pixel is shared with the kernel -- on host arrays, a
+ * detection at a time.  What the CPU tests compare with the NumPy model where no GPU is present; cos / sin are the host's
+ * there and the device's in the kernel (both rounded to float32 before use, as cv2.boxPoints does). */
+int ysmr_luminosity_batch_host(const uint8_t *frames_host, int batch, int height, int width, int channels,
+                               const float *det_host, const int32_t *det_count_host, int max_det, int cv_flavour,
+                               double *lum_host, uint32_t *sum_host, uint32_t *count_host, int32_t *corners_host);
+
 /* ---- linking: a7-a19 -------------------------------------------------------------------- */
 
 /* Horizon sizes n_i (gsff.py:87-109) and rows 0/1 of each least-squares gain (gsff.py:111-153,
@@ -236,6 +270,21 @@ int ysmr_tracker_create(double max_disappeared, double fps, int n_min, double n_
 int ysmr_tracker_destroy(ysmr_tracker *t);
 int ysmr_tracker_reset(ysmr_tracker *t, void *stream);
 
+/* A handle links (x, y) centroids (2, the default) or (x, y, third) centroids (3: the reference's
+ * input_centroids of width 3, tracker.py:111 -- the third coordinate is the luminosity of ysmr_luminosity_batch).  The
+ * distance is sqrt(dx*dx + dy*dy + dl*dl) in float64, summed in that order; claims, ageing, ids, registration order and the
+ * rows are the 2-D handle's (rows carry x and y).  Set before the handle's first frame:
+ *   YSMR_ERR_ARG    dimensions other than 2 or 3; 3 on a handle created with use_gsff = 1 (the reference has no such mode: its
+ *                   filter bank is built for (x, y) and CentroidTracker.update raises on the first frame)
+ *   YSMR_ERR_STATE  a frame has been linked since the handle was created or last reset
+ * ysmr_tracker_reset keeps the dimension.  A 3-D handle is driven by ysmr_tracker_update3 / ysmr_tracker_run3 /
+ * ysmr_tracker_peek3 -- ysmr_tracker_update and ysmr_tracker_run return YSMR_ERR_STATE on it, as the three do on a 2-D
+ * handle.  It links with one launch per frame (k_frame), or two (k_link + k_track) where a 2-D handle of that capacity and
+ * max_det would, and finds every row minimum by the all-pairs search: the grid searches and the one-launch batch link are
+ * two-dimensional by construction, so ysmr_tracker_batched is 0 and ysmr_tracker_prepare a no-op for it.  Without a filter
+ * bank the position of a track is the last point it claimed, all three coordinates; a lost track keeps it. */
+int ysmr_tracker_dimensions(ysmr_tracker *t, int dimensions);
+
 /* One CentroidTracker.update(rects).  det_dev: [m][5] = cx, cy, w, h, angle; f32 as written by
  * ysmr_detect_batch (det_is_f64 = 0) or f64 (det_is_f64 = 1; for callers holding float64
  * centroids, like the reference's input_centroids, tracker.py:111).  m >= 0: detection count known
@@ -253,6 +302,11 @@ int ysmr_tracker_update(ysmr_tracker *t, void *stream, const void *det_dev, int 
                         const int32_t *m_dev, int32_t frame_index, ysmr_row *rows_dev,
                         int32_t *n_rows_dev, int32_t *claim_col_dev, int32_t *n_before_dev,
                         int32_t *new_cols_dev, int32_t *n_new_dev);
+
+/* ysmr_tracker_update for a 3-D handle: third_dev f64 [m], the third coordinate of each detection. */
+int ysmr_tracker_update3(ysmr_tracker *t, void *stream, const void *det_dev, int det_is_f64, const double *third_dev, int m,
+                         const int32_t *m_dev, int32_t frame_index, ysmr_row *rows_dev, int32_t *n_rows_dev,
+                         int32_t *claim_col_dev, int32_t *n_before_dev, int32_t *new_cols_dev, int32_t *n_new_dev);
 
 /* The frame loop of track_bacteria for `batch` consecutive frames whose detections are already
  * on the device: det_dev f32 [batch][max_det][5], det_count_dev i32 [batch].  Rows are appended
@@ -293,12 +347,19 @@ int ysmr_tracker_prepare(ysmr_tracker *t, void *stream, const float *det_dev, co
 int ysmr_tracker_run(ysmr_tracker *t, void *stream, const float *det_dev,
                      const int32_t *det_count_dev, int batch, int32_t first_frame_index,
                      ysmr_row *rows_dev, int64_t rows_capacity, int64_t *row_count_dev);
+/* ... for a 3-D handle: third_dev f64 [batch][max_det], as ysmr_luminosity_batch writes it. */
+int ysmr_tracker_run3(ysmr_tracker *t, void *stream, const float *det_dev, const double *third_dev,
+                      const int32_t *det_count_dev, int batch, int32_t first_frame_index, ysmr_row *rows_dev,
+                      int64_t rows_capacity, int64_t *row_count_dev);
 
 /* Current track table in id order: ids i32 [capacity], positions f64 [capacity][2] (the
  * CentroidTracker.objects values: GSFF predictions, or raw centroids without GSFF), disappeared
  * counters, count.  Device outputs, each may be NULL. */
 int ysmr_tracker_peek(ysmr_tracker *t, void *stream, int32_t *ids_dev, double *xy_dev,
                       int32_t *disappeared_dev, int32_t *n_dev);
+/* ... of a 3-D handle, with third_dev f64 [capacity]: each track's third coordinate, in the same order. */
+int ysmr_tracker_peek3(ysmr_tracker *t, void *stream, int32_t *ids_dev, double *xy_dev, double *third_dev,
+                       int32_t *disappeared_dev, int32_t *n_dev);
 
 /* Host-visible counters (synchronises the stream): live tracks, next id, sticky error bits. */
 int ysmr_tracker_info(ysmr_tracker *t, void *stream, int32_t *n_tracks, int32_t *next_id,

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("YSMR_HIP_LIB") or os.path.join(_HERE, "csrc", "libysm
 
 YSMR_OK = 0
 YSMR_ERR_ARG = 1
+YSMR_ERR_STATE = 4
 DET_OVERFLOW = 1
 DET_ARENA = 2
 DET_STALLED = 4
@@ -57,7 +58,9 @@ EXPORTS = ("ysmr_abi_version", "ysmr_last_error", "ysmr_detect_workspace_bytes",
            "ysmr_tracker_reset", "ysmr_tracker_update", "ysmr_tracker_run", "ysmr_tracker_fused", "ysmr_tracker_batched", "ysmr_tracker_link_mode", "ysmr_tracker_prepare", "ysmr_tracker_peek",
            "ysmr_tracker_info", "ysmr_rows_sort_workspace_bytes", "ysmr_rows_sort", "ysmr_rows_csv_bound",
            "ysmr_rows_format_csv", "ysmr_rows_write_csv", "ysmr_rows_write_csv_columns", "ysmr_rows_format_device_workspace_bytes", "ysmr_rows_format_device", "ysmr_rows_format_csv_devicelike", "ysmr_rows_stream_create", "ysmr_rows_stream_push", "ysmr_rows_stream_count", "ysmr_rows_stream_finish", "ysmr_rows_stream_destroy", "ysmr_rows_columns", "ysmr_select_workspace_bytes", "ysmr_select_tracks",
-           "ysmr_evaluate_workspace_bytes", "ysmr_evaluate_tracks", "ysmr_unpack_dib_batch", "ysmr_file_read")
+           "ysmr_evaluate_workspace_bytes", "ysmr_evaluate_tracks", "ysmr_unpack_dib_batch", "ysmr_file_read",
+           "ysmr_luminosity_batch", "ysmr_luminosity_batch_host", "ysmr_tracker_dimensions", "ysmr_tracker_update3",
+           "ysmr_tracker_run3", "ysmr_tracker_peek3")
 
 SELECT_OK, SELECT_TOO_SHORT, SELECT_TOO_SHORT_CLEANED, SELECT_NONE = 0, 1, 2, 3
 
@@ -148,6 +151,12 @@ def lib():
     L.ysmr_tracker_batched.argtypes = [vp]
     L.ysmr_tracker_link_mode.argtypes = [vp, ci]
     L.ysmr_tracker_prepare.argtypes = [vp, vp, vp, vp, ci, ci]
+    L.ysmr_luminosity_batch.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp]
+    L.ysmr_luminosity_batch_host.argtypes = [vp, ci, ci, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp]
+    L.ysmr_tracker_dimensions.argtypes = [vp, ci]
+    L.ysmr_tracker_update3.argtypes = [vp, vp, vp, ci, vp, ci, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp]
+    L.ysmr_tracker_run3.argtypes = [vp, vp, vp, vp, vp, ci, ctypes.c_int32, vp, ctypes.c_int64, vp]
+    L.ysmr_tracker_peek3.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.ysmr_tracker_info.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                                     ctypes.POINTER(ctypes.c_int32)]
     L.ysmr_rows_sort_workspace_bytes.argtypes = [ctypes.c_longlong]

@@ -146,6 +146,13 @@ struct ysmr_tracker {
     // slot in `bd` from the start; the ring's head is kept here (every live track appends one measurement per frame)
     bool lanes = false;
     int lanes_head = 0;
+    // ysmr_tracker_dimensions: 2 (x, y) or 3 (x, y, luminosity).  A 3-D handle links frame by frame with all-pairs row minima
+    // (the grid searches and the batch link are two-dimensional): `batchable` and `lanes` are false while it is one, and what
+    // they were for the 2-D handle is kept beside them.
+    int dims = 2;
+    bool batchable_2d = false, lanes_2d = false;
+    bool linked = false;           // a frame has been linked since creation / the last reset: the dimension is fixed
+    double *pos3 = nullptr;        // [capacity] third coordinate of the track in a slot
     bool use_batch() const { return batchable && link_mode == 0; }
     DetGrid grid(int f) const
     {
@@ -253,6 +260,17 @@ __device__ __forceinline__ int wave_min(int v) { return __builtin_amdgcn_readlan
 
 constexpr int ROWMIN_U = 8;   // detections per lane per chunk (all loads of a chunk in flight together)
 
+// The third tracking coordinate of a 3-D handle (ysmr_tracker_dimensions: the mean luminosity under a detection's box,
+// tracker.py:111, 151).  The per-frame kernels are instantiated twice: D3 = false is the code they were before the third
+// coordinate existed (the argument is empty and nothing reads it), D3 = true adds one float64 per track and per detection to
+// the distances and to the stored position -- nothing else of the link changes.  There is no filter bank on a 3-D handle.
+template <bool D3> struct Third3 {};
+template <> struct Third3<true> {
+    double *pos3;           // [capacity] by slot, beside TrackerDev::pos
+    const double *det3;     // [m] of the frame being linked
+    const double *next3;    // [m_next] of the frame whose row minima the launch prepares (NULL without one)
+};
+
 template <typename DetT>
 struct DetChunk { DetT qx[ROWMIN_U], qy[ROWMIN_U]; };   // raw: converting here would wait for the loads here
 
@@ -269,10 +287,20 @@ __device__ __forceinline__ void load_chunk(DetChunk<DetT> &c, const DetT *__rest
 
 // `first` holds detections [0, 64*ROWMIN_U) already loaded by the caller (issued before the GSFF so
 // that their latency hides behind it).  With m <= 64*ROWMIN_U every pass runs out of registers.
-template <typename DetT>
+template <typename DetT, bool D3 = false>
 __device__ __forceinline__ void rowmin_wave(const TrackerDev &t, int row, double px, double py,
-                                            const DetT *__restrict__ det, int m, int lane, DetChunk<DetT> &first)
+                                            const DetT *__restrict__ det, int m, int lane, DetChunk<DetT> &first,
+                                            double pl = 0.0, const double *__restrict__ det3 = nullptr)
 {
+    // (3-D: cdist sums dx*dx + dy*dy + dl*dl in that order; the third coordinate is fetched where it is used -- a masked
+    // tail entry reads the last real one and is moved out of the way by its x as before)
+    auto third = [&](double s, int j) {
+        if constexpr (D3) {
+            const double dl = pl - det3[min(j, m - 1)];
+            s = s + dl * dl;
+        }
+        return s;
+    };
     constexpr int CHUNK = 64 * ROWMIN_U;
     const bool multi = m > CHUNK;
     const double inf = __longlong_as_double(0x7FF0000000000000ll);
@@ -294,6 +322,7 @@ __device__ __forceinline__ void rowmin_wave(const TrackerDev &t, int row, double
             const double dy = py - (double)first.qy[u];
             double s = dx * dx;
             s = s + dy * dy;
+            s = third(s, j0 + u * 64 + lane);
             lane_min = __builtin_fmin(s, lane_min);
         }
     }
@@ -310,6 +339,7 @@ __device__ __forceinline__ void rowmin_wave(const TrackerDev &t, int row, double
             const double dy = py - (double)first.qy[u];
             double s = dx * dx;
             s = s + dy * dy;
+            s = third(s, j);
             const bool near = s <= near_limit;
             cand = near ? min(cand, j) : cand;
             inexact = inexact || (near && s != s_min);
@@ -323,6 +353,7 @@ __device__ __forceinline__ void rowmin_wave(const TrackerDev &t, int row, double
             const double dy = py - (double)det[(size_t)j * 5 + 1];
             double s = dx * dx;
             s = s + dy * dy;
+            s = third(s, j);
             if (s <= near_limit && sqrt(s) == d_min) cand = min(cand, j);
         }
     }
@@ -491,10 +522,10 @@ __device__ __forceinline__ bool rowmin_grid(const TrackerDev &t, int row, double
 
 // Stand-alone row-min pass (first frame of a batch / single-frame updates); inside a batch the
 // row-min of frame f+1 rides on k_track of frame f.
-template <typename DetT>
+template <typename DetT, bool D3 = false>
 __global__ __launch_bounds__(256) void k_rowmin(TrackerDev t, const DetT *__restrict__ det, int m_host,
                                                 const int32_t *m_dev, int set_row_base, const long long *row_count_ext,
-                                                DetGrid grid)
+                                                DetGrid grid, Third3<D3> th)
 {
     // (fused path, start of ysmr_tracker_run / _update: row_base of the current state := the caller's
     // running row count; folded in here to save a launch per batch)
@@ -510,7 +541,8 @@ __global__ __launch_bounds__(256) void k_rowmin(TrackerDev t, const DetT *__rest
     if (grid.start && rowmin_grid(t, row, t.pos[slot], t.pos[t.capacity + slot], det, grid, lane, gh)) return;
     DetChunk<DetT> first;
     load_chunk(first, det, m, 0, lane);
-    rowmin_wave(t, row, t.pos[slot], t.pos[t.capacity + slot], det, m, lane, first);
+    if constexpr (D3) rowmin_wave<DetT, true>(t, row, t.pos[slot], t.pos[t.capacity + slot], det, m, lane, first, th.pos3[slot], th.det3);
+    else rowmin_wave(t, row, t.pos[slot], t.pos[t.capacity + slot], det, m, lane, first);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -878,10 +910,10 @@ __device__ __forceinline__ void gsff_wave(const TrackerDev &t, const double *gai
     GSTAMP(6);
 }
 
-template <typename DetT, int NF>
+template <typename DetT, int NF, bool D3 = false>
 __global__ __launch_bounds__(256) void k_track(TrackerDev t, int frame, ysmr_row *rows, long long rows_capacity,
                                                const DetT *__restrict__ det, const DetT *__restrict__ next_det,
-                                               int next_m_host, const int32_t *next_m_dev, DetGrid next_grid)
+                                               int next_m_host, const int32_t *next_m_dev, DetGrid next_grid, Third3<D3> th)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) RING((4ull << 40) | (unsigned)frame);   // k_track entry
     BSTAMP(0);
@@ -913,18 +945,22 @@ __global__ __launch_bounds__(256) void k_track(TrackerDev t, int frame, ysmr_row
     if (t.use_gsff) gsff_fetch(t, slot, lane, st);
     const int c = __builtin_amdgcn_readfirstlane(claims_by_row ? claim_spec : t.claim_slot[slot]);
     double z0, z1;
+    [[maybe_unused]] double z2 = 0.0;      // (3-D handles)
     float bw, bh, ba;
     if (c >= 0) {
         const DetT *d = det + (size_t)c * 5;
         z0 = (double)d[0]; z1 = (double)d[1];
         bw = (float)d[2]; bh = (float)d[3]; ba = (float)d[4];
+        if constexpr (D3) z2 = th.det3[c];
         if (lane == 0) {
             t.pos[slot] = z0; t.pos[cap + slot] = z1;
             t.info[slot] = bw; t.info[cap + slot] = bh; t.info[2 * cap + slot] = ba;
+            if constexpr (D3) th.pos3[slot] = z2;
         }
     } else {
         z0 = t.pos[slot]; z1 = t.pos[cap + slot];
         bw = t.info[slot]; bh = t.info[cap + slot]; ba = t.info[2 * cap + slot];
+        if constexpr (D3) z2 = th.pos3[slot];
     }
     double o0 = z0, o1 = z1, p0 = z0, p1 = z1;
     if (t.use_gsff) gsff_wave(t, t.gains, slot, lane, z0, z1, false, st, G, o0, o1, p0, p1);
@@ -955,7 +991,8 @@ __global__ __launch_bounds__(256) void k_track(TrackerDev t, int frame, ysmr_row
             }
             load_chunk(first, next_det, m_next, 0, lane);
         }
-        rowmin_wave(t, i, p0, p1, next_det, m_next, lane, first);
+        if constexpr (D3) rowmin_wave<DetT, true>(t, i, p0, p1, next_det, m_next, lane, first, z2, th.next3);
+        else rowmin_wave(t, i, p0, p1, next_det, m_next, lane, first);
     }
 }
 
@@ -1154,12 +1191,12 @@ __device__ int cpython_order_block(const int *unused, int n_unused, int m, int n
 // LDS_TABLES: the per-column winner tables fit in LDS (12 B per detection column <= 140 KiB, e.g. 96 KiB at 8192; the
 // per-row claims are in HBM): the claim rounds cost LDS atomics.  Otherwise the tables live in HBM (three rounds of
 // device-scope atomics, ~6 us more at 5000 rows) and capacity / max_det are only bounded by 65536.
-template <typename DetT, bool LDS_TABLES>
+template <typename DetT, bool LDS_TABLES, bool D3 = false>
 __global__ __launch_bounds__(LINK_THREADS) void k_link(TrackerDev t, const DetT *__restrict__ det, int m_host,
                                                        const int32_t *m_dev, int frame, ysmr_row *rows,
                                                        long long rows_capacity, long long *row_count,
                                                        int32_t *n_rows_out, int32_t *claim_out, int32_t *n_before_out,
-                                                       int32_t *new_cols_out, int32_t *n_new_out)
+                                                       int32_t *new_cols_out, int32_t *n_new_out, Third3<D3> th)
 {
     extern __shared__ unsigned long long s_dyn[];
     unsigned long long *s_col_key = LDS_TABLES ? s_dyn : t.link_key;                                        // [max_det]
@@ -1466,6 +1503,7 @@ __global__ __launch_bounds__(LINK_THREADS) void k_link(TrackerDev t, const DetT 
             t.id[slot] = id0 + j;
             t.pos[slot] = (double)det[(size_t)c * 5 + 0];
             t.pos[cap + slot] = (double)det[(size_t)c * 5 + 1];
+            if constexpr (D3) th.pos3[slot] = th.det3[c];
             t.info[slot] = (float)det[(size_t)c * 5 + 2];
             t.info[cap + slot] = (float)det[(size_t)c * 5 + 3];
             t.info[2 * cap + slot] = (float)det[(size_t)c * 5 + 4];
@@ -1631,14 +1669,14 @@ __device__ int cpython_order_lds(const int *unused, int n_unused, int m, int n_u
 #define STAMP(k) do {} while (0)
 #endif
 
-template <typename DetT, int NF>
+template <typename DetT, int NF, bool D3 = false>
 __global__ __launch_bounds__(FRAME_THREADS) void k_frame(TrackerDev a, TrackerDev b, const DetT *__restrict__ det,
                                                          int m_host, const int32_t *m_dev, int frame, ysmr_row *rows,
                                                          long long rows_capacity, long long *row_count_ext,
                                                          int32_t *n_rows_out, int32_t *claim_out, int32_t *n_before_out,
                                                          int32_t *new_cols_out, int32_t *n_new_out,
                                                          const DetT *__restrict__ next_det, const int32_t *next_m_dev,
-                                                         int base_from_ext)
+                                                         int base_from_ext, Third3<D3> th)
 {
     extern __shared__ unsigned long long s_raw[];
     __shared__ int s_n_used, s_n_dead, s_set_state[2];
@@ -1717,18 +1755,21 @@ __global__ __launch_bounds__(FRAME_THREADS) void k_frame(TrackerDev a, TrackerDe
     c_s = __builtin_amdgcn_readfirstlane((i < n && m > 0) ? c_s : -1);
     GsffState<NF> S;
     double zs0 = 0.0, zs1 = 0.0;
+    [[maybe_unused]] double zs2 = 0.0, d3 = 0.0;   // (3-D handles: the track's and the claimed detection's third coordinate)
     int id_s = 0;
     float in_s[3] = {0.f, 0.f, 0.f};
     DetT dd[5] = {0, 0, 0, 0, 0};
     if (slot_s >= 0) {
         if (a.use_gsff) gsff_fetch(a, slot_s, lane, S);
         zs0 = a.pos[slot_s]; zs1 = a.pos[cap + slot_s];
+        if constexpr (D3) zs2 = th.pos3[slot_s];
         id_s = a.id[slot_s];
 #pragma unroll
         for (int k = 0; k < 3; ++k) in_s[k] = a.info[k * cap + slot_s];
         if (c_s >= 0) {
 #pragma unroll
             for (int k = 0; k < 5; ++k) dd[k] = det[(size_t)c_s * 5 + k];
+            if constexpr (D3) d3 = th.det3[c_s];
         }
     }
     // row r = tid + 256 k of the old table: from the registers above for k < SPEC_ROWS (the passes over them are
@@ -1858,12 +1899,14 @@ __global__ __launch_bounds__(FRAME_THREADS) void k_frame(TrackerDev a, TrackerDe
                 slot = __builtin_amdgcn_readfirstlane(a.order[r]);
                 if (a.use_gsff) gsff_fetch(a, slot, lane, S);
                 zs0 = a.pos[slot]; zs1 = a.pos[cap + slot];
+                if constexpr (D3) zs2 = th.pos3[slot];
                 id_s = a.id[slot];
 #pragma unroll
                 for (int k = 0; k < 3; ++k) in_s[k] = a.info[k * cap + slot];
                 if (c >= 0) {
 #pragma unroll
                     for (int k = 0; k < 5; ++k) dd[k] = det[(size_t)c * 5 + k];
+                    if constexpr (D3) d3 = th.det3[c];
                 }
             }
             if (c < 0) {
@@ -1878,6 +1921,7 @@ __global__ __launch_bounds__(FRAME_THREADS) void k_frame(TrackerDev a, TrackerDe
             id_s = id0 + j;
 #pragma unroll
             for (int k = 0; k < 5; ++k) dd[k] = det[(size_t)c * 5 + k];
+            if constexpr (D3) d3 = th.det3[c];
             gsff_blank(S);    // nothing of the slot's previous owner is read
             gsff_point(a, slot, S);
             if (lane == 0) a.id[slot] = id_s;
@@ -1892,7 +1936,10 @@ __global__ __launch_bounds__(FRAME_THREADS) void k_frame(TrackerDev a, TrackerDe
         double o0 = z0, o1 = z1, p0 = z0, p1 = z1;
         STAMP(5);
         if (a.use_gsff) gsff_wave(a, a.gains, slot, lane, z0, z1, fresh_track, S, G, o0, o1, p0, p1);
-        else if (lane == 0) { a.pos[slot] = z0; a.pos[cap + slot] = z1; }
+        else if (lane == 0) {
+            a.pos[slot] = z0; a.pos[cap + slot] = z1;
+            if constexpr (D3) th.pos3[slot] = c >= 0 ? d3 : zs2;
+        }
         STAMP(6);
         if (lane == 0) {
             b.order[i] = slot;
@@ -1914,7 +1961,11 @@ __global__ __launch_bounds__(FRAME_THREADS) void k_frame(TrackerDev a, TrackerDe
             }
         }
         STAMP(7);
-        if (m_next > 0) rowmin_wave(b, i, p0, p1, next_det, m_next, lane, first);
+        if constexpr (D3) {
+            if (m_next > 0) rowmin_wave<DetT, true>(b, i, p0, p1, next_det, m_next, lane, first, c >= 0 ? d3 : zs2, th.next3);
+        } else {
+            if (m_next > 0) rowmin_wave(b, i, p0, p1, next_det, m_next, lane, first);
+        }
         STAMP(8);
     }
     BSTAMP(2);
@@ -1987,29 +2038,64 @@ int launch_update_t(ysmr_tracker *t, hipStream_t st, const DetT *det, int m, con
                     ysmr_row *rows, long long rows_capacity, long long *row_count, int32_t *n_rows, int32_t *claim,
                     int32_t *n_before, int32_t *new_cols, int32_t *n_new, bool rowmin_done, const DetT *next_det,
                     const int32_t *next_m_dev, DetGrid grid = DetGrid{nullptr, nullptr, nullptr, nullptr},
-                    DetGrid next_grid = DetGrid{nullptr, nullptr, nullptr, nullptr}, bool base_from_ext = false)
+                    DetGrid next_grid = DetGrid{nullptr, nullptr, nullptr, nullptr}, bool base_from_ext = false,
+                    const double *third = nullptr, const double *next_third = nullptr)
 {
     const DetGrid no_grid{nullptr, nullptr, nullptr, nullptr};
     const dim3 wgrid((t->d.capacity + 3) / 4);
+    t->linked = true;
+    if (t->dims == 3) {
+        // the same launches with the third coordinate: all-pairs row minima (no grids), no filter bank (n_f = 1), k_track
+        // with a wave per track
+        const Third3<true> th{t->pos3, third, next_det ? next_third : nullptr};
+        if (t->fused) {
+            const TrackerDev &a = t->cur(), &b = t->nxt();
+            if (!rowmin_done) {
+                hipLaunchKernelGGL((k_rowmin<DetT, true>), wgrid, dim3(256), 0, st, a, det, m, m_dev, t->set_base ? 1 : 0, t->base_ptr,
+                                   no_grid, th);
+                t->set_base = false;
+            }
+            hipLaunchKernelGGL((k_frame<DetT, 3, true>), wgrid, dim3(FRAME_THREADS), t->frame_lds, st, a, b, det, m, m_dev, frame,
+                               rows, rows_capacity, row_count, n_rows, claim, n_before, new_cols, n_new, next_det, next_m_dev,
+                               base_from_ext ? 1 : 0, th);
+            t->par ^= 1;
+        } else {
+            const TrackerDev &d = t->d;
+            if (!rowmin_done)
+                hipLaunchKernelGGL((k_rowmin<DetT, true>), wgrid, dim3(256), 0, st, d, det, m, m_dev, 0, nullptr, no_grid, th);
+            const size_t link_lds = 12 * (size_t)d.max_det;
+            if (link_lds <= 140 * 1024)
+                hipLaunchKernelGGL((k_link<DetT, true, true>), dim3(1), dim3(LINK_THREADS), link_lds, st, d, det, m, m_dev, frame,
+                                   rows, rows_capacity, row_count, n_rows, claim, n_before, new_cols, n_new, th);
+            else
+                hipLaunchKernelGGL((k_link<DetT, false, true>), dim3(1), dim3(LINK_THREADS), 0, st, d, det, m, m_dev, frame, rows,
+                                   rows_capacity, row_count, n_rows, claim, n_before, new_cols, n_new, th);
+            hipLaunchKernelGGL((k_track<DetT, 3, true>), wgrid, dim3(256), 0, st, d, frame, rows, rows_capacity, det, next_det, -1,
+                               next_m_dev, no_grid, th);
+        }
+        YSMR_LAUNCH_CHECK();
+        return YSMR_OK;
+    }
+    const Third3<false> th{};
     if (t->fused) {
         const TrackerDev &a = t->cur(), &b = t->nxt();
         if (!rowmin_done) {
-            hipLaunchKernelGGL(k_rowmin<DetT>, wgrid, dim3(256), 0, st, a, det, m, m_dev, t->set_base ? 1 : 0, t->base_ptr, no_grid);
+            hipLaunchKernelGGL(k_rowmin<DetT>, wgrid, dim3(256), 0, st, a, det, m, m_dev, t->set_base ? 1 : 0, t->base_ptr, no_grid, th);
             t->set_base = false;
         }
         // the filter bank is unrolled at compile time: 3 covers tracking.ini's default (and 1, 2), 8 the rest
         if (a.n_f <= 3)
             hipLaunchKernelGGL((k_frame<DetT, 3>), wgrid, dim3(FRAME_THREADS), t->frame_lds, st, a, b, det, m, m_dev, frame,
                                rows, rows_capacity, row_count, n_rows, claim, n_before, new_cols, n_new, next_det, next_m_dev,
-                               base_from_ext ? 1 : 0);
+                               base_from_ext ? 1 : 0, th);
         else
             hipLaunchKernelGGL((k_frame<DetT, YSMR_MAX_FILTERS>), wgrid, dim3(FRAME_THREADS), t->frame_lds, st, a, b, det, m,
                                m_dev, frame, rows, rows_capacity, row_count, n_rows, claim, n_before, new_cols, n_new,
-                               next_det, next_m_dev, base_from_ext ? 1 : 0);
+                               next_det, next_m_dev, base_from_ext ? 1 : 0, th);
         t->par ^= 1;
     } else {
         const TrackerDev &d = t->d;
-        if (!rowmin_done) hipLaunchKernelGGL(k_rowmin<DetT>, wgrid, dim3(256), 0, st, d, det, m, m_dev, 0, nullptr, grid);
+        if (!rowmin_done) hipLaunchKernelGGL(k_rowmin<DetT>, wgrid, dim3(256), 0, st, d, det, m, m_dev, 0, nullptr, grid, th);
         const size_t link_lds = 12 * (size_t)d.max_det;
 #ifdef YSMR_TUNING
         static const bool hbm_tables = getenv("YSMR_LINK_TABLES") && !strcmp(getenv("YSMR_LINK_TABLES"), "hbm");
@@ -2018,20 +2104,20 @@ int launch_update_t(ysmr_tracker *t, hipStream_t st, const DetT *det, int m, con
 #endif
         if (link_lds <= 140 * 1024 && !hbm_tables)
             hipLaunchKernelGGL((k_link<DetT, true>), dim3(1), dim3(LINK_THREADS), link_lds, st, d, det, m, m_dev, frame, rows,
-                               rows_capacity, row_count, n_rows, claim, n_before, new_cols, n_new);
+                               rows_capacity, row_count, n_rows, claim, n_before, new_cols, n_new, th);
         else
             hipLaunchKernelGGL((k_link<DetT, false>), dim3(1), dim3(LINK_THREADS), 0, st, d, det, m, m_dev, frame, rows,
-                               rows_capacity, row_count, n_rows, claim, n_before, new_cols, n_new);
+                               rows_capacity, row_count, n_rows, claim, n_before, new_cols, n_new, th);
         if (t->lanes) {
             hipLaunchKernelGGL(k_track_lanes<DetT>, dim3((d.capacity + TL_THREADS - 1) / TL_THREADS), dim3(TL_THREADS), 0, st, d, t->bd,
                                t->bgains_dev, t->lanes_head, frame, rows, rows_capacity, det, next_det, next_m_dev, next_grid);
             t->lanes_head = (t->lanes_head + 1) & (BL_HB - 1);
         } else if (d.n_f <= 3)
             hipLaunchKernelGGL((k_track<DetT, 3>), wgrid, dim3(256), 0, st, d, frame, rows, rows_capacity, det, next_det, -1,
-                               next_m_dev, next_grid);
+                               next_m_dev, next_grid, th);
         else
             hipLaunchKernelGGL((k_track<DetT, YSMR_MAX_FILTERS>), wgrid, dim3(256), 0, st, d, frame, rows, rows_capacity, det,
-                               next_det, -1, next_m_dev, next_grid);
+                               next_det, -1, next_m_dev, next_grid, th);
     }
     YSMR_LAUNCH_CHECK();
     return YSMR_OK;
@@ -2047,6 +2133,13 @@ __global__ void k_peek(TrackerDev t, int32_t *ids, double *xy, int32_t *gone, in
     if (ids) ids[i] = t.id[slot];
     if (xy) { xy[2 * i] = t.pos[slot]; xy[2 * i + 1] = t.pos[t.capacity + slot]; }
     if (gone) gone[i] = t.gone[t.gone_by_row ? i : slot];
+}
+
+// the third coordinate of every track in id order (ysmr_tracker_peek3, behind k_peek)
+__global__ void k_peek_third(TrackerDev t, const double *pos3, double *third)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < *t.n_tracks) third[i] = pos3[t.order[i]];
 }
 
 }  // namespace
@@ -2137,6 +2230,7 @@ int ysmr_tracker_create(double max_disappeared, double fps, int n_min, double n_
     const size_t o_order = take(sizeof(int) * cap), o_free = take(sizeof(int) * cap);
     const size_t o_id = take(sizeof(int) * cap), o_gone = take(sizeof(int) * cap);
     const size_t o_pos = take(sizeof(double) * 2 * cap), o_info = take(sizeof(float) * 3 * cap);
+    const size_t o_pos3 = take(sizeof(double) * cap);      // (a 3-D handle's third coordinate: ysmr_tracker_dimensions)
     const size_t o_hist = take(sizeof(double) * 2 * cap * d.hist_cap);
     d.rec_stride = (2 + 3 * nf + 7) / 8 * 8;
     const size_t o_rec = take(sizeof(double) * (size_t)d.rec_stride * cap);
@@ -2168,6 +2262,7 @@ int ysmr_tracker_create(double max_disappeared, double fps, int n_min, double n_
     d.order = (int *)(b + o_order); d.free_slots = (int *)(b + o_free);
     d.id = (int *)(b + o_id); d.gone = (int *)(b + o_gone);
     d.pos = (double *)(b + o_pos); d.info = (float *)(b + o_info); d.hist = (double *)(b + o_hist);
+    t->pos3 = (double *)(b + o_pos3);
     d.rec = (double *)(b + o_rec);
     d.gains = (const double *)(b + o_gain);
     d.unused = (int *)(b + o_unused);
@@ -2275,8 +2370,31 @@ int ysmr_tracker_create(double max_disappeared, double fps, int n_min, double n_
         delete t;
         return ysmr::fail(YSMR_ERR_HIP, "tracker state initialisation failed: %s", hipGetErrorString(e));
     }
+    t->batchable_2d = t->batchable;
+    t->lanes_2d = t->lanes;
     *out = t;
     return ysmr_tracker_reset(t, nullptr);
+}
+
+int ysmr_tracker_dimensions(ysmr_tracker *t, int dimensions)
+{
+    if (!t) return ysmr::fail(YSMR_ERR_ARG, "tracker handle is NULL");
+    if (dimensions != 2 && dimensions != 3) return ysmr::fail(YSMR_ERR_ARG, "a tracker links in 2 or 3 dimensions, got %d", dimensions);
+    if (dimensions == 3 && t->d.use_gsff)
+        return ysmr::fail(YSMR_ERR_ARG, "3 dimensions need a handle created with use_gsff = 0 (the reference's filter bank takes "
+                                        "(x, y) only: its CentroidTracker raises on a third coordinate, ysmr/tracker.py:68-69, 222)");
+    if (t->linked)
+        return ysmr::fail(YSMR_ERR_STATE, "the dimension of a tracker is fixed with its first frame (ysmr_tracker_reset frees it)");
+    if (dimensions == 3 && t->fused) {
+        const void *variants[2] = {(const void *)k_frame<float, 3, true>, (const void *)k_frame<double, 3, true>};
+        for (const void *fn : variants) YSMR_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->frame_lds));
+    }
+    t->dims = dimensions;
+    t->batchable = dimensions == 2 && t->batchable_2d;
+    t->lanes = dimensions == 2 && t->lanes_2d;
+    t->in_batch = t->use_batch();      // (the table is empty: the same in both layouts)
+    t->prepared[0] = t->prepared[1] = ysmr_tracker::Prepared();
+    return YSMR_OK;
 }
 
 int ysmr_tracker_reset(ysmr_tracker *t, void *stream)
@@ -2291,6 +2409,7 @@ int ysmr_tracker_reset(ysmr_tracker *t, void *stream)
         t->lanes_head = 0;
     }
     t->in_batch = t->use_batch();      // (an empty table is the same in both layouts)
+    t->linked = false;
     hipLaunchKernelGGL(k_tracker_reset, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, t->d);
     YSMR_LAUNCH_CHECK();
     return YSMR_OK;
@@ -2372,6 +2491,7 @@ int ysmr_tracker_update(ysmr_tracker *t, void *stream, const void *det_dev, int 
     if (m < 0 && !m_dev) return ysmr::fail(YSMR_ERR_ARG, "m < 0 requires m_dev");
     if (m > t->d.max_det) return ysmr::fail(YSMR_ERR_CAPACITY, "m = %d exceeds max_det = %d", m, t->d.max_det);
     if (!det_dev && m != 0) return ysmr::fail(YSMR_ERR_ARG, "det_dev is NULL");
+    if (t->dims != 2) return ysmr::fail(YSMR_ERR_STATE, "a 3-D handle is updated with ysmr_tracker_update3");
     if (int rc = state_to_std(t, (hipStream_t)stream)) return rc;     // (one frame at a time: the per-frame kernels)
     t->rowmin_for = nullptr;
     if (t->fused) { t->set_base = true; t->base_ptr = nullptr; }
@@ -2390,6 +2510,8 @@ int ysmr_tracker_run(ysmr_tracker *t, void *stream, const float *det_dev, const 
     if (!t) return ysmr::fail(YSMR_ERR_ARG, "tracker handle is NULL");
     if (!det_dev || !det_count_dev || !rows_dev || !row_count_dev || batch <= 0)
         return ysmr::fail(YSMR_ERR_ARG, "det_dev, det_count_dev, rows_dev, row_count_dev must be set and batch > 0");
+    if (t->dims != 2) return ysmr::fail(YSMR_ERR_STATE, "a 3-D handle is run with ysmr_tracker_run3");
+    t->linked = true;
     // (ysmr_tracker_run_chained, which also took the NEXT call's first frame, left the ABI with version 12: its look-ahead
     // had been ignored since version 10 -- a launch that had the next call's first row minima ready had to take its first
     // output row from *row_count_dev, the word its own first workgroup advances, ADVICE r03 -- and a batch-link handle
@@ -2466,6 +2588,50 @@ int ysmr_tracker_run(ysmr_tracker *t, void *stream, const float *det_dev, const 
     return YSMR_OK;
 }
 
+int ysmr_tracker_update3(ysmr_tracker *t, void *stream, const void *det_dev, int det_is_f64, const double *third_dev, int m,
+                         const int32_t *m_dev, int32_t frame_index, ysmr_row *rows_dev, int32_t *n_rows_dev,
+                         int32_t *claim_col_dev, int32_t *n_before_dev, int32_t *new_cols_dev, int32_t *n_new_dev)
+{
+    if (!t) return ysmr::fail(YSMR_ERR_ARG, "tracker handle is NULL");
+    if (m < 0 && !m_dev) return ysmr::fail(YSMR_ERR_ARG, "m < 0 requires m_dev");
+    if (m > t->d.max_det) return ysmr::fail(YSMR_ERR_CAPACITY, "m = %d exceeds max_det = %d", m, t->d.max_det);
+    if ((!det_dev || !third_dev) && m != 0) return ysmr::fail(YSMR_ERR_ARG, "det_dev / third_dev is NULL");
+    if (t->dims != 3) return ysmr::fail(YSMR_ERR_STATE, "ysmr_tracker_update3 needs a 3-D handle (ysmr_tracker_dimensions)");
+    t->rowmin_for = nullptr;
+    if (t->fused) { t->set_base = true; t->base_ptr = nullptr; }
+    const DetGrid no_grid{nullptr, nullptr, nullptr, nullptr};
+    if (det_is_f64)
+        return launch_update_t<double>(t, (hipStream_t)stream, (const double *)det_dev, m, m_dev, frame_index, rows_dev,
+                                       t->d.capacity, nullptr, n_rows_dev, claim_col_dev, n_before_dev, new_cols_dev,
+                                       n_new_dev, false, nullptr, nullptr, no_grid, no_grid, false, third_dev, nullptr);
+    return launch_update_t<float>(t, (hipStream_t)stream, (const float *)det_dev, m, m_dev, frame_index, rows_dev,
+                                  t->d.capacity, nullptr, n_rows_dev, claim_col_dev, n_before_dev, new_cols_dev,
+                                  n_new_dev, false, nullptr, nullptr, no_grid, no_grid, false, third_dev, nullptr);
+}
+
+int ysmr_tracker_run3(ysmr_tracker *t, void *stream, const float *det_dev, const double *third_dev, const int32_t *det_count_dev,
+                      int batch, int32_t first_frame_index, ysmr_row *rows_dev, int64_t rows_capacity, int64_t *row_count_dev)
+{
+    if (!t) return ysmr::fail(YSMR_ERR_ARG, "tracker handle is NULL");
+    if (!det_dev || !third_dev || !det_count_dev || !rows_dev || !row_count_dev || batch <= 0)
+        return ysmr::fail(YSMR_ERR_ARG, "det_dev, third_dev, det_count_dev, rows_dev, row_count_dev must be set and batch > 0");
+    if (t->dims != 3) return ysmr::fail(YSMR_ERR_STATE, "ysmr_tracker_run3 needs a 3-D handle (ysmr_tracker_dimensions)");
+    t->rowmin_for = nullptr;
+    if (t->fused) { t->set_base = true; t->base_ptr = (const long long *)row_count_dev; }
+    const DetGrid no_grid{nullptr, nullptr, nullptr, nullptr};
+    const size_t md = (size_t)t->d.max_det;
+    for (int f = 0; f < batch; ++f) {       // one launch per frame (or two); a frame's launch leaves the next frame's row minima
+        const bool inside = f + 1 < batch;
+        int rc = launch_update_t<float>(t, (hipStream_t)stream, det_dev + (size_t)f * md * 5, -1, det_count_dev + f,
+                                        first_frame_index + f, rows_dev, (long long)rows_capacity, (long long *)row_count_dev,
+                                        nullptr, nullptr, nullptr, nullptr, nullptr, f > 0,
+                                        inside ? det_dev + (size_t)(f + 1) * md * 5 : nullptr, inside ? det_count_dev + f + 1 : nullptr,
+                                        no_grid, no_grid, false, third_dev + (size_t)f * md, inside ? third_dev + (size_t)(f + 1) * md : nullptr);
+        if (rc) return rc;
+    }
+    return YSMR_OK;
+}
+
 int ysmr_tracker_fused(ysmr_tracker *t) { return t && t->fused && !t->use_batch() ? 1 : 0; }
 
 int ysmr_tracker_peek(ysmr_tracker *t, void *stream, int32_t *ids_dev, double *xy_dev, int32_t *disappeared_dev,
@@ -2479,6 +2645,20 @@ int ysmr_tracker_peek(ysmr_tracker *t, void *stream, int32_t *ids_dev, double *x
         hipLaunchKernelGGL(k_peek, dim3((t->d.capacity + 255) / 256), dim3(256), 0, (hipStream_t)stream, t->cur(), ids_dev,
                            xy_dev, disappeared_dev, n_dev);
     YSMR_LAUNCH_CHECK();
+    return YSMR_OK;
+}
+
+int ysmr_tracker_peek3(ysmr_tracker *t, void *stream, int32_t *ids_dev, double *xy_dev, double *third_dev,
+                       int32_t *disappeared_dev, int32_t *n_dev)
+{
+    if (!t) return ysmr::fail(YSMR_ERR_ARG, "tracker handle is NULL");
+    if (t->dims != 3) return ysmr::fail(YSMR_ERR_STATE, "ysmr_tracker_peek3 needs a 3-D handle (ysmr_tracker_dimensions)");
+    if (int rc = ysmr_tracker_peek(t, stream, ids_dev, xy_dev, disappeared_dev, n_dev)) return rc;
+    if (third_dev) {
+        hipLaunchKernelGGL(k_peek_third, dim3((t->d.capacity + 255) / 256), dim3(256), 0, (hipStream_t)stream, t->cur(), t->pos3,
+                           third_dev);
+        YSMR_LAUNCH_CHECK();
+    }
     return YSMR_OK;
 }
 

@@ -89,6 +89,7 @@ class DetectResult:
     det: torch.Tensor        # f32 [B,max_det,5]  cx, cy, w, h, angle
     anchors: torch.Tensor    # i32 [B,max_det]
     status: torch.Tensor     # i32 [B]  _lib.DET_* bits
+    lum: torch.Tensor | None = None   # f64 [B,max_det]  mean gray under each box / 100 (detectors built with luminosity=True)
 
 
 def _on_own_device(method):
@@ -111,7 +112,7 @@ class Detector:
 
     def __init__(self, batch, height, width, max_det=2048, params: ThresholdParams | MeanGrayParams | None = None,
                  device="cuda:0", want_mask=True, mean_state: MeanGrayState | None = None, cv_flavour=0,
-                 threshold_variant=0, beside_batch_link=False, beside_split_link=False):
+                 threshold_variant=0, beside_batch_link=False, beside_split_link=False, luminosity=False):
         self.B, self.H, self.W, self.max_det = int(batch), int(height), int(width), int(max_det)
         #: which threshold kernel ``detect`` / ``threshold`` take (``ysmr_threshold_batch_variant``): 0 = the library's choice
         #: (the matrix-pipe kernel, which fills whole compute units); 1 = the float32-chain kernels, whose resident grid
@@ -147,6 +148,10 @@ class Detector:
         self.det = torch.zeros(self.B, self.max_det, 5, dtype=torch.float32, device=self.device)
         self.anchors = torch.zeros(self.B, self.max_det, dtype=torch.int32, device=self.device)
         self.status = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        #: 'include luminosity in tracking calculation' (ysmr/track_eval.py:290-300): ``detect`` -- and ``components``, when it
+        #: is handed the frames -- also work out each detection's third tracking coordinate (``luminosity``)
+        self.with_luminosity = bool(luminosity)
+        self.lum = torch.zeros(self.B, self.max_det, dtype=torch.float64, device=self.device) if luminosity else None
 
     def _view(self, buf, batch):
         n = batch * self.H * self.W
@@ -195,8 +200,9 @@ class Detector:
         return self._view(self._cls, b)
 
     @_on_own_device
-    def components(self, batch=None, cls: torch.Tensor | None = None) -> DetectResult:
-        """a4-a6 on the class map left by ``threshold`` (or on a caller-supplied u8 [b,H,W] map)."""
+    def components(self, batch=None, cls: torch.Tensor | None = None, frames: torch.Tensor | None = None) -> DetectResult:
+        """a4-a6 on the class map left by ``threshold`` (or on a caller-supplied u8 [b,H,W] map).  ``frames``: the frames
+        the class map was made from, for a detector built with ``luminosity=True`` (else call ``luminosity`` yourself)."""
         if cls is not None:
             batch = cls.shape[0]
             self._view(self._cls, batch).copy_(cls)
@@ -207,13 +213,33 @@ class Detector:
             self.det_count.data_ptr(), self.det.data_ptr(), self.anchors.data_ptr(), self.max_det,
             self.status.data_ptr(), self.cv_flavour)
         _lib.check(rc, "ysmr_components_batch")
+        if self.with_luminosity and frames is not None:
+            self.luminosity(frames, b)
         return self._result(b)
+
+    @_on_own_device
+    def luminosity(self, frames: torch.Tensor, batch=None, sums=None, counts=None, corners=None) -> torch.Tensor:
+        """The mean gray value / 100 under the min-area rectangle of every detection the last ``components`` / ``detect``
+        call left in ``det`` (``ysmr_luminosity_batch``): f64 [b,max_det], entries past ``det_count`` are not written.
+        Asynchronous on the current stream, which must be behind that call.  ``sums`` / ``counts`` (u32 [b,max_det]) and
+        ``corners`` (i32 [b,max_det,4,2]) optionally receive the integers the value was made from."""
+        if self.lum is None:
+            self.lum = torch.zeros(self.B, self.max_det, dtype=torch.float64, device=self.device)
+        b, ch = self._check_frames(frames)
+        if batch is not None and int(batch) != b:
+            raise ValueError(f"{b} frames for a batch of {batch}")
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        rc = _lib.lib().ysmr_luminosity_batch(_lib.stream_ptr(self.device), frames.data_ptr(), b, self.H, self.W, ch,
+                                              self.det.data_ptr(), self.det_count.data_ptr(), self.max_det, self.cv_flavour,
+                                              self.lum.data_ptr(), ptr(sums), ptr(counts), ptr(corners))
+        _lib.check(rc, "ysmr_luminosity_batch")
+        return self.lum[:b]
 
     def _result(self, b):
         return DetectResult(self._view(self._cls, b),
                             self._view(self._mask, b) if self._mask is not None else None,
                             self._view(self._labels, b), self.det_count[:b], self.det[:b], self.anchors[:b],
-                            self.status[:b])
+                            self.status[:b], None if self.lum is None else self.lum[:b])
 
     @_on_own_device
     def detect(self, frames: torch.Tensor) -> DetectResult:
@@ -222,7 +248,7 @@ class Detector:
         p = self.params
         if self.mean_state is not None or self.threshold_variant:
             self.threshold(frames)
-            return self.components(b)
+            return self.components(b, frames=frames)
         rc = _lib.lib().ysmr_detect_batch(
             _lib.stream_ptr(self.device), frames.data_ptr(), b, self.H, self.W, ch, p.inv, p.t_low, p.t_high, p.use_high,
             self._ws.data_ptr(), self._ws.numel(), self._cls.data_ptr(),
@@ -230,4 +256,6 @@ class Detector:
             self.det_count.data_ptr(), self.det.data_ptr(), self.anchors.data_ptr(), self.max_det,
             self.status.data_ptr(), self.cv_flavour)
         _lib.check(rc, "ysmr_detect_batch")
+        if self.with_luminosity:
+            self.luminosity(frames, b)
         return self._result(b)

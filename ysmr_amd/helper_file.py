@@ -328,9 +328,14 @@ def save_list(path, result_folder=None, coords=None, first_call=False, rename_ol
     """Create ``<name>_list.csv`` with its header (first_call) or append rows.
 
     ``coords`` items are ``(frame, id, (x, y), (w, h, deg))`` like upstream; formatting follows
-    helper_file.py:1455-1475 byte for byte (``str.format`` of ints/floats)."""
-    if illumination:
-        raise NotImplementedError("luminosity tracking is out of scope")
+    helper_file.py:1455-1475 byte for byte (``str.format`` of ints/floats).
+
+    ``illumination`` as upstream (helper_file.py:1450-1475): the header ends in ``,ILLUMINATION`` and a row's eighth field
+    is ``xy[2]`` of its ``(x, y, luminosity)``.  Deviation: ``track_bacteria`` does not go through this function -- the rows
+    of a video stay on the device and ``ysmr_row`` has no third coordinate -- so with 'hip persist rows' the chunks
+    appended while a luminosity run is under way keep seven columns under the seven-column header.  The final
+    ``<name>_list.csv`` is the same either way: upstream's ``sort_list`` reads the eight-column file back through
+    ``get_data``'s seven default columns and rewrites it with those."""
     if first_call:
         folder = result_folder if result_folder is not None else os.path.dirname(path)
         name = os.path.splitext(os.path.basename(path))[0]
@@ -344,12 +349,13 @@ def save_list(path, result_folder=None, coords=None, first_call=False, rename_ol
             else:
                 _remove_previous_list(csv_path)
         with open(csv_path, "w+", newline="") as fh:
-            fh.write(CSV_HEADER)
+            fh.write(CSV_HEADER[:-1] + ",ILLUMINATION\n" if illumination else CSV_HEADER)
         return old, csv_path
     if coords:
         lines = []
         for frame, obj_id, xy, (w, h, deg) in coords:
-            lines.append("{0},{1},{2},{3},{4},{5},{6}\n".format(int(obj_id), int(frame), xy[0], xy[1], w, h, deg))
+            line = "{0},{1},{2},{3},{4},{5},{6}".format(int(obj_id), int(frame), xy[0], xy[1], w, h, deg)
+            lines.append("{},{}\n".format(line, xy[2]) if illumination else line + "\n")
         with open(path, "a", newline="") as fh:
             fh.write("".join(lines))
     return None, None

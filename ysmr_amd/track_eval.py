@@ -10,6 +10,10 @@ The loop body (track_eval.py:156-366) is replaced by batched device work:
                      <--D2H-- rows, every `list save length interval` rows
 
 Detection of batch b+1 is issued on a second HIP stream while batch b is being linked.
+
+'include luminosity in tracking calculation' (track_eval.py:290-300; with 'disable gsff' = True, the combination upstream
+runs): ``ysmr_luminosity_batch`` follows the detection on that stream and the link is ``ysmr_tracker_run3``, one launch
+per frame, with the mean gray value under each detection's box as a third coordinate.
 """
 from __future__ import annotations
 
@@ -106,10 +110,17 @@ class TrackingPipeline:
         # register) and the link waits for them: 80.7 k against 85.7 k frames/s end to end, and giving it the chip to itself
         # between two batches' link chains costs more (77.8 k) than its 15 % buy (profiles/r03_threshold_kernels_in_the_pipeline.log;
         # at 4K 14.8 k against 15.2 k).  Detection without a link has no neighbour and takes the matrix-pipe kernel.
+        # 'include luminosity in tracking calculation' (track_eval.py:290-300): every detection's mean gray value / 100 is a
+        # third tracking coordinate.  Upstream offers it with 'disable gsff' only (with the filter bank its tracker raises in
+        # the first update), so the tracker is built in three dimensions -- which links frame by frame, never with the batch
+        # launch -- and both detectors also run the luminosity kernel
+        self.luminosity = bool(settings.get("include luminosity in tracking calculation", False))
+        if self.luminosity and not settings["disable gsff"]:
+            raise ValueError("'include luminosity in tracking calculation' needs 'disable gsff' = True")
         self.trk = DeviceTracker(max_disappeared=fps, fps=fps, n_min=settings["minimum horizon size"],
                                  n_max=settings["maximum horizon size"], n_f=settings["number of LSFFs"],
                                  use_gsff=not settings["disable gsff"], capacity=capacity, max_det=max_det,
-                                 device=self.device)
+                                 device=self.device, dimensions=3 if self.luminosity else 2)
         # (a handle that links a whole batch with ONE launch -- one workgroup on one compute unit -- is nobody's neighbour:
         # detection then takes the matrix-pipe kernel and its full resident grids; beside the per-frame kernels, one-launch
         # or split (4K), it keeps round 3's choice: 21.0 k against 22.3 k frames/s at 4K with the matrix-pipe kernel)
@@ -127,7 +138,8 @@ class TrackingPipeline:
         self.det = [Detector(self.B, height, width, max_det=max_det, params=params, device=self.device,
                              mean_state=mean_state, cv_flavour=settings.get("opencv version"),
                              threshold_variant=1 if beside_fused_link else 0,
-                             beside_batch_link=bool(link) and self.trk.batched, beside_split_link=beside_split_link)
+                             beside_batch_link=bool(link) and self.trk.batched, beside_split_link=beside_split_link,
+                             luminosity=self.luminosity)
                     for _ in range(2)]
         self.capacity = int(capacity)
         self._link = bool(link)
@@ -173,7 +185,7 @@ class TrackingPipeline:
             if self._done[slot] is not None:
                 self.side.wait_event(self._done[slot])
             if thresholded is not None:
-                res = det.components(frames_dev.shape[0])
+                res = det.components(frames_dev.shape[0], frames=frames_dev)
                 if chain_events is not None:
                     e2 = events[2] if events else torch.cuda.Event(enable_timing=True)
                     e2.record(self.side)
@@ -184,13 +196,15 @@ class TrackingPipeline:
                 e0, e1 = (events[0], events[1]) if events else (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 self._timed_threshold(det, frames_dev, self.side, e0, e1, True, bool(events))   # (the detector's own choice of kernel)
                 threshold_events.append((e0, e1, frames_dev.shape[0]))
-                res = det.components(frames_dev.shape[0])
+                res = det.components(frames_dev.shape[0], frames=frames_dev)
                 if chain_events is not None:
                     e2 = events[2] if events else torch.cuda.Event(enable_timing=True)
                     e2.record(self.side)
                     chain_events.append((e1, e2, frames_dev.shape[0]))
             if self._link and self.trk.batched:      # the link's binning of these detections, off the link stream
                 self.trk.prepare(res.det, res.det_count, slot)
+            # (with luminosity on, the calls above have also issued ysmr_luminosity_batch behind the components call, here on
+            # the side stream: it reads the batch's frames, which a frame feed frees on `ready`)
             ready = self._ev[slot]["ready"]
             ready.record(self.side)
         return slot, res, ready
@@ -225,7 +239,8 @@ class TrackingPipeline:
         n = int(res.det_count.shape[0])
 
         def run():
-            self.trk.run(res.det, res.det_count, first_frame, self.rows, self.row_count)
+            self.trk.run(res.det, res.det_count, first_frame, self.rows, self.row_count,
+                         third=res.lum if self.luminosity else None)
 
         if link_events is None:
             run()
@@ -305,6 +320,9 @@ def track_bacteria(video_path, settings=None, result_folder=None, batch=None, ma
     tracks) size the device buffers; the reference has no such limits, so they may also be given as the
     optional settings keys 'hip frames per batch', 'hip max detections per frame', 'hip max tracks', and a
     video that overflows them is run again with both doubled (checked after the first batch and at the end).
+    'include luminosity in tracking calculation' = True needs 'disable gsff' = True (with the GSFF on, the reference's own
+    tracker raises in its first update: logged, ``None``); the returned table and the final csv keep their seven columns,
+    as upstream's ``sort_list`` leaves them.
     Optional settings key 'hip persist rows' (default False): keep at most 'list save length interval' rows on the
     device and append every full buffer to ``<name>_list.csv`` as the reference does (helper_file.py:1403-1478), so
     that an interrupted run leaves the rows tracked so far; the file is rewritten in order at the end either way.
@@ -323,11 +341,15 @@ def track_bacteria(video_path, settings=None, result_folder=None, batch=None, ma
     if not os.path.isfile(video_path):
         logger.critical("File {} does not exist".format(video_path))
         return None
-    for key, why in (("include luminosity in tracking calculation", "luminosity as a third tracking dimension"),
-                     ("display video analysis", "interactive display")):
-        if settings[key]:
-            logger.critical("'{}' = True ({}) is not supported by the HIP path".format(key, why))
-            return None
+    if settings["display video analysis"]:
+        logger.critical("'display video analysis' = True (interactive display) is not supported by the HIP path")
+        return None
+    if settings["include luminosity in tracking calculation"] and not settings["disable gsff"]:
+        # (ysmr/tracker.py:68-69, 222: the filter bank is built for (x, y); fed (x, y, luminosity) its first update raises
+        # "ValueError: shapes (4,20) and (30,) not aligned".  The mode runs with 'disable gsff' = True, there and here.)
+        logger.critical("'include luminosity in tracking calculation' = True needs 'disable gsff' = True: with the GSFF on the "
+                        "reference's own tracker raises in its first update, and the HIP path has no such mode either")
+        return None
     if settings["color filter"] != COLOR_BGR2GRAY:
         logger.critical("Only 'color filter = COLOR_BGR2GRAY' is supported by the HIP path")
         return None

@@ -35,10 +35,17 @@ class DeviceTracker:
     """Owns one ``ysmr_tracker`` handle (one video stream)."""
 
     def __init__(self, max_disappeared=50, fps=30, n_min=0, n_max=None, n_f=3, use_gsff=True,
-                 capacity=1024, max_det=2048, device="cuda:0", gains=None):
+                 capacity=1024, max_det=2048, device="cuda:0", gains=None, dimensions=2):
+        if dimensions not in (2, 3):
+            raise ValueError(f"a tracker links in 2 or 3 dimensions, got {dimensions}")
+        if dimensions == 3 and use_gsff:
+            raise ValueError("dimensions=3 (luminosity as a tracking coordinate) needs use_gsff=False: the reference's filter "
+                             "bank takes (x, y) only and its CentroidTracker raises on the first 3-D frame")
         self.device = torch.device(device)
         self.capacity, self.max_det = int(capacity), int(max_det)
         self.use_gsff = bool(use_gsff)
+        #: 2: (x, y) centroids; 3: (x, y, luminosity) -- ``update`` / ``run`` then take the third coordinate as ``third``
+        self.dimensions = int(dimensions)
         self._handle = ctypes.c_void_p()
         # gains: None = the library's closed form of the least-squares gain (gsff.py:111-153); an array laid
         # out as ysmr_gsff_gains() writes it overrides it (experiments with other gains)
@@ -49,6 +56,8 @@ class DeviceTracker:
                 int(self.use_gsff), self.capacity, self.max_det, None if g is None else g.ctypes.data,
                 ctypes.byref(self._handle))
         _lib.check(rc, "ysmr_tracker_create")
+        if self.dimensions == 3:
+            _lib.check(_lib.lib().ysmr_tracker_dimensions(self._handle, 3), "ysmr_tracker_dimensions")
 
     def close(self):
         if self._handle:
@@ -67,22 +76,43 @@ class DeviceTracker:
 
     @_on_own_device
     def update(self, det, m=None, m_dev=None, frame=0, rows=None, n_rows=None, claim=None, n_before=None,
-               new_cols=None, n_new=None):
-        """One frame.  det: device tensor [m,5] float32 or float64."""
+               new_cols=None, n_new=None, third=None):
+        """One frame.  det: device tensor [m,5] float32 or float64; third: float64 [m], a 3-D handle's third coordinate."""
         f64 = int(det.dtype == torch.float64)
         ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        if self.dimensions == 3:
+            if third is None or third.dtype != torch.float64 or not third.is_contiguous():
+                raise ValueError("a 3-D tracker needs `third`: a contiguous float64 device tensor [m]")
+            rc = _lib.lib().ysmr_tracker_update3(self._handle, _lib.stream_ptr(self.device), det.data_ptr(), f64,
+                                                 third.data_ptr(), -1 if m is None else int(m), ptr(m_dev), int(frame),
+                                                 ptr(rows), ptr(n_rows), ptr(claim), ptr(n_before), ptr(new_cols), ptr(n_new))
+            _lib.check(rc, "ysmr_tracker_update3")
+            return
+        if third is not None:
+            raise ValueError("`third` needs a tracker made with dimensions=3")
         rc = _lib.lib().ysmr_tracker_update(self._handle, _lib.stream_ptr(self.device), det.data_ptr(), f64,
                                             -1 if m is None else int(m), ptr(m_dev), int(frame), ptr(rows),
                                             ptr(n_rows), ptr(claim), ptr(n_before), ptr(new_cols), ptr(n_new))
         _lib.check(rc, "ysmr_tracker_update")
 
     @_on_own_device
-    def run(self, det, det_count, first_frame, rows, row_count):
+    def run(self, det, det_count, first_frame, rows, row_count, third=None):
         """Frames [first_frame, first_frame + B): det f32 [B,max_det,5], det_count i32 [B] on device;
-        rows: uint8 buffer viewed as ysmr_row[]; row_count: int64 device scalar (advanced)."""
+        rows: uint8 buffer viewed as ysmr_row[]; row_count: int64 device scalar (advanced).  third: f64 [B,max_det], the
+        third coordinate of a 3-D handle's detections (``Detector.luminosity``)."""
         b = det_count.numel()
         if det.shape[1] != self.max_det:
             raise ValueError("det must be [B, max_det, 5] with the tracker's max_det")
+        if self.dimensions == 3:
+            if third is None or third.dtype != torch.float64 or third.shape[1] != self.max_det or not third.is_contiguous():
+                raise ValueError("a 3-D tracker needs `third`: a contiguous float64 device tensor [B, max_det]")
+            rc = _lib.lib().ysmr_tracker_run3(self._handle, _lib.stream_ptr(self.device), det.data_ptr(), third.data_ptr(),
+                                              det_count.data_ptr(), b, int(first_frame), rows.data_ptr(),
+                                              rows.numel() // _lib.ROW_DTYPE.itemsize, row_count.data_ptr())
+            _lib.check(rc, "ysmr_tracker_run3")
+            return
+        if third is not None:
+            raise ValueError("`third` needs a tracker made with dimensions=3")
         rc = _lib.lib().ysmr_tracker_run(self._handle, _lib.stream_ptr(self.device), det.data_ptr(),
                                          det_count.data_ptr(), b, int(first_frame), rows.data_ptr(),
                                          rows.numel() // _lib.ROW_DTYPE.itemsize, row_count.data_ptr())
@@ -122,11 +152,18 @@ class DeviceTracker:
 
     @_on_own_device
     def peek(self):
-        """Current (ids, positions (n,2) float64, disappeared) in id order; synchronises."""
+        """Current (ids, positions (n,2) float64 -- (n,3) of a 3-D handle --, disappeared) in id order; synchronises."""
         ids = torch.empty(self.capacity, dtype=torch.int32, device=self.device)
         xy = torch.empty(self.capacity, 2, dtype=torch.float64, device=self.device)
         gone = torch.empty(self.capacity, dtype=torch.int32, device=self.device)
         n = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if self.dimensions == 3:
+            third = torch.empty(self.capacity, dtype=torch.float64, device=self.device)
+            rc = _lib.lib().ysmr_tracker_peek3(self._handle, _lib.stream_ptr(self.device), ids.data_ptr(), xy.data_ptr(),
+                                               third.data_ptr(), gone.data_ptr(), n.data_ptr())
+            _lib.check(rc, "ysmr_tracker_peek3")
+            k = int(n.item())
+            return (ids[:k].cpu().numpy(), torch.cat([xy[:k], third[:k, None]], 1).cpu().numpy(), gone[:k].cpu().numpy())
         rc = _lib.lib().ysmr_tracker_peek(self._handle, _lib.stream_ptr(self.device), ids.data_ptr(), xy.data_ptr(),
                                           gone.data_ptr(), n.data_ptr())
         _lib.check(rc, "ysmr_tracker_peek")
@@ -200,17 +237,21 @@ class CentroidTracker:
     ``update(rects)`` takes ``[((x, y), additional_info), ...]`` and returns
     ``(OrderedDict id -> np.array([x, y]), OrderedDict id -> additional_info)``: the filtered
     centroids when the GSFF is on (tracker.py:219-227), the raw ones otherwise (:228-230).
-    Only 2-D centroids are supported (the luminosity dimension is off by default upstream and
-    out of scope here).
+    ``dimensions=3`` (only with ``use_gsff=False``: upstream raises in its first ``update`` otherwise) takes
+    ``[((x, y, luminosity), additional_info), ...]``; ``objects`` and the returned dict then hold 3-vectors, as
+    upstream's do.  The dimension is fixed at construction -- upstream fixes it with the first frame, and a table
+    of 2-D points fed a 3-D one fails in its ``cdist``.
     """
 
     def __init__(self, max_disappeared=50, fps=30, n_min=0, n_max=None, n_f=3, use_gsff=True,
-                 capacity=4096, max_det=4096, device="cuda:0"):
+                 capacity=4096, max_det=4096, device="cuda:0", dimensions=2):
         self.maxDisappeared = max_disappeared
         self.use_gsff = use_gsff
+        self.dimensions = int(dimensions)
         self.additional_info = OrderedDict()
         self._ids = []
-        self._dev = DeviceTracker(max_disappeared, fps, n_min, n_max, n_f, use_gsff, capacity, max_det, device)
+        self._dev = DeviceTracker(max_disappeared, fps, n_min, n_max, n_f, use_gsff, capacity, max_det, device,
+                                  dimensions=dimensions)
         d = self._dev.device
         self._rows = torch.empty(capacity * _lib.ROW_DTYPE.itemsize, dtype=torch.uint8, device=d)
         self._claim = torch.empty(capacity, dtype=torch.int32, device=d)
@@ -236,23 +277,32 @@ class CentroidTracker:
     def update(self, rects):
         m = len(rects)
         if m:
-            if len(rects[0][0]) != 2:
-                raise NotImplementedError("only (x, y) centroids are supported (luminosity tracking is out of scope)")
+            if len(rects[0][0]) != self.dimensions:
+                if self.dimensions == 2:
+                    raise NotImplementedError("this tracker links (x, y) centroids: make it with dimensions=3 (and "
+                                              "use_gsff=False) for (x, y, luminosity)")
+                raise ValueError(f"a tracker made with dimensions=3 takes (x, y, luminosity) centroids, got "
+                                 f"{len(rects[0][0])} coordinates")
             if m > self._dev.max_det:
                 raise ValueError(f"{m} detections exceed max_det={self._dev.max_det}")
             host = np.zeros((m, 5), np.float64)
+            lum = np.zeros(m, np.float64)
             for i, (xy, info) in enumerate(rects):
-                host[i, 0], host[i, 1] = xy
+                host[i, 0], host[i, 1] = xy[0], xy[1]
+                if self.dimensions == 3:
+                    lum[i] = xy[2]
                 try:
                     host[i, 2:5] = info
                 except (TypeError, ValueError):
                     pass  # non-numeric payload: kept on the host only
             det = torch.from_numpy(host).to(self._dev.device)
+            third = torch.from_numpy(lum).to(self._dev.device) if self.dimensions == 3 else None
         else:
             det = torch.zeros((1, 5), dtype=torch.float64, device=self._dev.device)
+            third = torch.zeros(1, dtype=torch.float64, device=self._dev.device) if self.dimensions == 3 else None
         s = self._scal
         self._dev.update(det, m=m, rows=self._rows, n_rows=s[0:1], claim=self._claim, n_before=s[1:2],
-                         new_cols=self._new, n_new=s[2:3])
+                         new_cols=self._new, n_new=s[2:3], third=third)
         n_rows, n_before, n_new = (int(v) for v in s[:3].cpu().numpy())
         rows = rows_to_numpy(self._rows, n_rows)
         claim = self._claim[:n_before].cpu().numpy()
@@ -278,6 +328,8 @@ class CentroidTracker:
             self.additional_info[tid] = rects[int(c)][1]
         self._ids = alive
         self._last_rows = rows
+        if self.dimensions == 3:     # (rows carry x and y; without a filter bank the returned points ARE the table's)
+            return self.objects, self.additional_info
         out = OrderedDict((int(r["track_id"]), np.array([r["x"], r["y"]])) for r in rows)
         return out, self.additional_info
 
