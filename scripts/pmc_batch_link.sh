@@ -1,5 +1,5 @@
 #!/bin/bash
-# SQ counters of k_batch (per launch of 256 frames) inside the running pipeline: separate rocprofv3 --pmc passes over
+# SQ counters of k_batch (per launch of 248 frames, bench.py's batch) inside the running pipeline: separate rocprofv3 --pmc passes over
 # bench.py, no tracing domains.  Output: gpurun_out/r04_pmc_batch_link.log
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/pmc_kb; rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
@@ -12,7 +12,7 @@ for f in glob.glob("$O/*/*/*counter_collection.csv"):
     for r in csv.DictReader(open(f)):
         if "k_batch" in r["Kernel_Name"]:
             acc[r["Counter_Name"]].append(float(r["Counter_Value"]))
-print("k_batch, per launch of 256 frames (mean over %d launches):" % max(len(v) for v in acc.values()))
-for k in sorted(acc): print(f"  {k:24s} {sum(acc[k]) / len(acc[k]):14.0f}   per frame {sum(acc[k]) / len(acc[k]) / 256:10.1f}")
+print("k_batch, per launch of 248 frames (mean over %d launches):" % max(len(v) for v in acc.values()))
+for k in sorted(acc): print(f"  {k:24s} {sum(acc[k]) / len(acc[k]):14.0f}   per frame {sum(acc[k]) / len(acc[k]) / 248:10.1f}")
 PY
 rm -rf $O

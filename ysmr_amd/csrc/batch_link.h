@@ -389,11 +389,45 @@ __device__ __forceinline__ void bl_sums_from_ring(BlSeat &S, const BatchDev &bd,
     }
 }
 
+// exp(x) of BL_NF arguments x <= 0 at once, with the device library's own arithmetic for float64 (x log2(e) rounded to
+// an integer n, the reduction r = x - n ln 2 with ln 2 in two constants, its degree-11 polynomial in Horner form, ldexp by
+// n) -- every operation, operand and constant as in the listing of exp(), so every result bit -- but for two things.
+// The three chains of dependent operations advance in step, not one after the other.  And the library's two range tests
+// are left out (x > 1024: +inf; x < -1075: 0): the caller replaces everything below lik_min by lik_min, and that is where
+// ldexp's own underflow ends as well (0 or a denormal).  Holds for -1e40 < x <= 0, squared distances no frame has: beyond
+// it the rounding of n makes r large, far beyond that the polynomial overflows.
+__device__ __forceinline__ void bl_exp_nonpos(const double (&x)[BL_NF], double (&e)[BL_NF])
+{
+    auto c = [](unsigned long long bits) { return __longlong_as_double((long long)bits); };
+    const double coef[9] = {c(0x3ec71dee623fde64ull), c(0x3efa01997c89e6b0ull), c(0x3f2a01a014761f6eull), c(0x3f56c16c1852b7b0ull),
+                            c(0x3f81111111122322ull), c(0x3fa55555555502a1ull), c(0x3fc5555555555511ull), c(0x3fe000000000000bull), 1.0};
+    double n[BL_NF], r[BL_NF], p[BL_NF];
+#pragma unroll
+    for (int f = 0; f < BL_NF; ++f) n[f] = __builtin_rint(x[f] * c(0x3ff71547652b82feull));
+#pragma unroll
+    for (int f = 0; f < BL_NF; ++f) r[f] = __builtin_fma(c(0xbfe62e42fefa39efull), n[f], x[f]);
+#pragma unroll
+    for (int f = 0; f < BL_NF; ++f) r[f] = __builtin_fma(c(0xbc7abc9e3b39803full), n[f], r[f]);
+#pragma unroll
+    for (int f = 0; f < BL_NF; ++f) p[f] = __builtin_fma(c(0x3e5ade156a5dcb37ull), r[f], c(0x3e928af3fca7ab0cull));
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+#pragma unroll
+        for (int f = 0; f < BL_NF; ++f) p[f] = __builtin_fma(r[f], p[f], coef[k]);
+#pragma unroll
+    for (int f = 0; f < BL_NF; ++f) p[f] = __builtin_fma(r[f], p[f], 1.0);
+#pragma unroll
+    for (int f = 0; f < BL_NF; ++f) e[f] = __builtin_ldexp(p[f], (int)n[f]);
+}
+
 // GaussianSumFIR.correct + predict of one track by its lane (gsff.py:204-347; the statement order of gsff_wave).
 // leave[f]: the measurement of age N_f - 1 (requested by the caller before the claims); head: the ring position this
 // frame's measurement takes.
 // (struct BlGains { alpha[filter][x / y row], beta[..][..] }: track.hip, the host handle holds one)
-__device__ __forceinline__ void bl_gsff(BlSeat &S, const TrackerDev &t, const BatchDev &bd, const BlGains &g, int seat, int head,
+// Gains: BlGains behind a plain pointer (k_track_lanes), or in the constant address space (k_batch: the gains then come
+// with scalar loads and enter the multiplications as scalar operands)
+template <typename Gains>
+__device__ __forceinline__ void bl_gsff(BlSeat &S, const TrackerDev &t, const BatchDev &bd, const Gains &g, int seat, int head,
                                         const double2 (&leave)[BL_NF], double z0, double z1, bool fresh, double &o0, double &o1)
 {
     const int nf = t.n_f, L = t.hist_cap;
@@ -447,15 +481,21 @@ __device__ __forceinline__ void bl_gsff(BlSeat &S, const TrackerDev &t, const Ba
     if (len < L) ++len;
     // likelihoods of the measurement under last frame's estimates (gsff.py:179-202)
     double lik[BL_NF], total = 0.0;
+    double ex[BL_NF];
 #pragma unroll
     for (int f = 0; f < BL_NF; ++f) {
         const double d0 = z0 - S.xa[f], d1 = z1 - S.xb[f];
         double q = d0 * d0;
         q = q + d1 * d1;
-        double l = exp(-0.5 * q);
+        ex[f] = -0.5 * q;
+    }
+    bl_exp_nonpos(ex, lik);
+#pragma unroll
+    for (int f = 0; f < BL_NF; ++f) {
+        double l = lik[f];
         if (l < t.lik_min) l = t.lik_min;
         lik[f] = l;
-        total = total + l * S.w[f];
+        total = f == 0 ? l * S.w[f] : total + l * S.w[f];      // (0.0 + a product of non-negative factors is that product)
     }
     // w_i <- lik_i w_i / total (gsff.py:333-336) as lik_i w_i * (1 / total): one division for the three weights; a weight
     // may differ from the quotient in its last bit (the per-frame kernels divide three times)
@@ -789,6 +829,7 @@ struct BlKernArgs {
     const BlGains *gains;
 };
 typedef const __attribute__((address_space(4))) BlKernArgs *BlKernArgsPtr;
+typedef const __attribute__((address_space(4))) BlGains *BlGainsPtr;     // (written once when the handle is made, before any launch)
 __device__ __forceinline__ BlKernArgsPtr bl_kernargs()
 {
     BlKernArgsPtr p = (BlKernArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
@@ -1098,11 +1139,15 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
 #endif
         if (S.alive) {
             if (t.use_gsff) {
-                // (the twelve gain constants come out of the scalar cache in every frame: as kernel arguments they sat in 24
-                // scalar registers for the whole launch, and this kernel spilled 113 of them into vector lanes -- a tenth of a frame's
-                // vector instructions were v_readlane / v_writelane)
-                const BlGains *gq = gains;
-                asm volatile("" : "+s"(gq));
+                // (the twelve gain constants are read in every frame: as kernel arguments they sat in 24 scalar registers for
+                // the whole launch, and this kernel spilled 113 of them into vector lanes -- a tenth of a frame's vector
+                // instructions were v_readlane / v_writelane.  Through a pointer in the CONSTANT address space they come out
+                // of the scalar cache, s_load_dwordx16 + s_load_dwordx8 and one wait; a plain pointer that went through the
+                // asm below came back generic, and the listing had six flat_load_dwordx4 per wave and frame with two
+                // vmcnt(0) lgkmcnt(0) waits in the middle of the float64 chain: tests/test_kernel_listing.py)
+                unsigned long long ga = (unsigned long long)gains;
+                asm volatile("" : "+s"(ga));
+                const BlGainsPtr gq = (BlGainsPtr)ga;
                 bl_gsff(S, t, bd, *gq, tid, head, leave, z0, z1, fresh, o0, o1);
             }
             else { S.px = z0; S.py = z1; }
