@@ -1,0 +1,290 @@
+#!/usr/bin/env python3
+"""Hot-path census of k_batch: what a track wave issues in a steady frame, read off the gfx950 listing (no GPU needed).
+
+    python scripts/k_batch_census.py [ysmr_amd/csrc/libysmr_hip.so | track.s | k_batch.dis]
+
+The argument is the built library (its gfx950 code object is disassembled with llvm-objdump), a listing that llvm-objdump -d
+wrote, or the compiler's own -S output.  The walk starts at the head of the frame loop and follows the steady frame:
+
+  * it falls through, and follows unconditional branches;
+  * a FORWARD conditional branch (s_cbranch_execz / vccz / vccnz / scc0 / scc1) jumps over a guarded block.  The block is
+    skipped -- it is a rare path: the 3 x 3 search, the wave search, the exact claims, the registration, the seeding of a new
+    track, a filter bank that grows -- unless it holds one of the landmarks below (the blocks under `propose`, `alive` and
+    the row's bounds check ARE the steady frame) or vector-memory loads without a barrier or a loop (the ring entries that
+    leave the windows, the claimed detection's box);
+  * of an if / else (s_andn2_saveexec / s_or_saveexec between the halves) whose first half was skipped, the second half
+    is the steady one (the candidate list's search, behind the 3 x 3 block search);
+  * a forward s_cbranch_execnz leads to a rare block laid out of line, and a backward branch closes an inner loop (the ring
+    stores of a seeding, a run's later candidates): neither is taken -- unless the fall-through is an s_branch that would
+    jump over a landmark (a steady block the compiler laid out of line).
+
+Landmarks, in the order a frame meets them: the ds_read_b128 of the candidate list, ds_min_rtn_u64 (the claim), the
+s_barrier behind it (barrier A), v_div_fixup_f64 (the weights' reciprocal), the end-of-frame s_barrier, the row's
+global_store_dwordx4 pair.  They cut the frame into phases:
+
+  chores + search    loop head .. the claim's atomic
+  claims             .. behind the claim's own wait and barrier A
+  ageing             .. the end of the seeding block (the last skipped block in front of the reciprocal that stores to the
+                     ring in a loop; without one: the last skipped block in front of the reciprocal)
+  filter bank        .. the end-of-frame barrier
+  ranks + row        .. the loop's closing branch
+
+Per phase: VALU (every v_* instruction; the lane moves v_readlane / v_writelane / v_readfirstlane are part of it and listed
+again on their own), float64 (v_*_f64, compares included), v_cndmask, lane moves, v_mov, compares, SALU, LDS, VMEM.
+The last line, "filter bank, by hand", adds what the round-11 issue's hand count of the parent included beyond the steady
+path (the seeding block's tail behind its ring-store loop, the instructions an s_branch jumps over): 242 VALU there.
+`census()` returns the same as a dict for tests/test_kernel_hot_path.py.
+"""
+import os
+import re
+import shutil
+import struct
+import subprocess
+import sys
+import tempfile
+
+KERNEL = "_ZN12_GLOBAL__N_17k_batchENS_10BlKernArgsE"
+BUNDLE_MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+COND = ("s_cbranch_execz", "s_cbranch_vccz", "s_cbranch_vccnz", "s_cbranch_scc0", "s_cbranch_scc1")
+STEADY_MARKS = ("ds_read_b128", "ds_min_rtn_u64", "v_div_fixup_f64")
+PHASES = ("chores + search", "claims", "ageing", "filter bank", "ranks + row")
+COLUMNS = ("valu", "f64", "cndmask", "lane", "mov", "cmp", "salu", "lds", "vmem")
+
+
+def _tool(name):
+    for d in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin"), "/opt/rocm/llvm/bin"):
+        p = os.path.join(d, name)
+        if os.path.exists(p):
+            return p
+    return shutil.which(name)
+
+
+def listing_of_library(lib):
+    """llvm-objdump -d of k_batch out of the library's gfx950 code object; None where the tools or the kernel are missing."""
+    objcopy, objdump = _tool("llvm-objcopy"), _tool("llvm-objdump")
+    if not objcopy or not objdump or not os.path.exists(lib):
+        return None
+    with tempfile.TemporaryDirectory() as tmp:
+        fat = os.path.join(tmp, "fatbin")
+        subprocess.run([objcopy, f"--dump-section=.hip_fatbin={fat}", lib, os.path.join(tmp, "host.so")], check=True,
+                       capture_output=True)
+        data = open(fat, "rb").read()
+        at, k = data.find(BUNDLE_MAGIC), 0
+        while at >= 0:
+            (n,) = struct.unpack_from("<Q", data, at + len(BUNDLE_MAGIC))
+            p = at + len(BUNDLE_MAGIC) + 8
+            for _ in range(n):
+                off, size, tlen = struct.unpack_from("<QQQ", data, p)
+                triple = data[p + 24:p + 24 + tlen].decode()
+                p += 24 + tlen
+                if triple.endswith("gfx950") and size:
+                    path = os.path.join(tmp, f"co{k}.o")
+                    k += 1
+                    with open(path, "wb") as fh:
+                        fh.write(data[at + off:at + off + size])
+                    text = subprocess.run([objdump, "-d", f"--disassemble-symbols={KERNEL}", path], check=True,
+                                          capture_output=True, text=True).stdout
+                    if re.search(r"^[0-9a-f]+ <" + re.escape(KERNEL) + r">:", text, re.M):
+                        return text
+            at = data.find(BUNDLE_MAGIC, at + 1)
+    return None
+
+
+def parse(text):
+    """[(mnemonic, operands, target index or None)] of k_batch, from an objdump listing or from -S output."""
+    ins, labels, pending = [], {}, []
+    m = re.search(r"^[0-9a-f]+ <" + re.escape(KERNEL) + r">:\n", text, re.M)
+    if m:                                   # llvm-objdump: "\tmnemonic operands  // ADDRESS: ENCODING <symbol+0xOFFSET>"
+        body = text[m.end():]
+        end = re.search(r"^[0-9a-f]+ <[^>]+>:\n", body, re.M)
+        body = body[:end.start()] if end else body
+        base = None
+        for line in body.splitlines():
+            mm = re.match(r"\s+([a-z][a-z0-9_]*)\s*(.*?)\s*//\s*([0-9A-Fa-f]+):(.*)$", line)
+            if not mm:
+                continue
+            addr = int(mm.group(3), 16)
+            base = addr if base is None else base
+            labels[addr - base] = len(ins)
+            t = re.search(r"<[^>]*\+0x([0-9a-fA-F]+)>", mm.group(4))
+            tgt = int(t.group(1), 16) if t else (0 if re.search(r"<" + re.escape(KERNEL) + r">", mm.group(4)) else None)
+            pending.append(tgt if mm.group(1).startswith(("s_cbranch", "s_branch")) else None)
+            ins.append((mm.group(1), mm.group(2)))
+    else:                                   # -S: the function between its label and .Lfunc_end
+        m = re.search(r"^" + re.escape(KERNEL) + r":.*\n", text, re.M)
+        if not m:
+            raise SystemExit(f"{KERNEL} not found in the listing")
+        body = text[m.end():]
+        end = re.search(r"^\.Lfunc_end\d+:", body, re.M)
+        body = body[:end.start()] if end else body
+        for line in body.splitlines():
+            line = line.split(";")[0].rstrip()
+            lm = re.match(r"^(\.?[A-Za-z_][\w.$]*):\s*$", line)
+            if lm:
+                labels[lm.group(1)] = len(ins)
+                continue
+            mm = re.match(r"\s+([a-z][a-z0-9_]*)\s*(.*)$", line)
+            if not mm or mm.group(1).startswith("."):
+                continue
+            pending.append(mm.group(2).strip() if mm.group(1).startswith(("s_cbranch", "s_branch")) else None)
+            ins.append((mm.group(1), mm.group(2)))
+    return [(op, args, labels.get(t) if t is not None else None) for (op, args), t in zip(ins, pending)]
+
+
+def _loop_head(ins):
+    """The frame loop: the backward branch with the longest reach around the candidate list's ds_read_b128."""
+    mark = next(i for i, (op, _, _) in enumerate(ins) if op == "ds_read_b128")
+    best = None
+    for i, (op, _, tgt) in enumerate(ins):
+        if tgt is not None and tgt <= mark < i and (best is None or i - tgt > best[1] - best[0]):
+            best = (tgt, i)
+    if best is None:
+        raise SystemExit("no loop around ds_read_b128: is this k_batch?")
+    return best
+
+
+def walk(ins):
+    """Indices of the steady frame's instructions, and the skipped blocks as (first, one past last)."""
+    head, close = _loop_head(ins)
+    path, skipped, i, seen = [], [], head, set()
+    while i not in seen and i < len(ins):
+        seen.add(i)
+        op, _, tgt = ins[i]
+        path.append(i)
+        if i == close:
+            break
+        if op == "s_branch" and tgt is not None and tgt > i:
+            i = tgt
+            continue
+        if op == "s_cbranch_execnz" and tgt is not None and tgt > i and ins[i + 1][0] == "s_branch":
+            over = ins[i + 1][2]         # (a steady block laid out of line: the fall-through would jump over it)
+            if over is not None and over > tgt and any(o in STEADY_MARKS for o, _, _ in ins[tgt:over]):
+                i = tgt
+                continue
+        if op in COND and tgt is not None and tgt > i and tgt <= close + 1:
+            block = [o for o, _, _ in ins[i + 1:tgt]]
+            other_half = skipped and skipped[-1][1] == i - 1 and ins[i - 1][0] in ("s_andn2_saveexec_b64", "s_or_saveexec_b64")
+            if other_half:               # (if / else: the first half was skipped as rare, so this half is the steady one)
+                i += 1
+                continue
+            # (the row: two 16-byte stores in straight-line code; a seeding's ring stores sit in a loop)
+            row = sum(o == "global_store_dwordx4" for o in block) >= 2 and \
+                not any(t is not None and t <= j for j, (_, _, t) in enumerate(ins[i + 1:tgt], i + 1))
+            # (what a track requests from memory in every frame -- the ring entries that leave its windows, the claimed
+            # detection's box -- sits in short blocks of its own: loads, no barrier, no loop)
+            loop = any(t is not None and t <= j for j, (_, _, t) in enumerate(ins[i + 1:tgt], i + 1))
+            loads = any(o.startswith("global_load") and not o.startswith("global_load_lds") for o in block) \
+                and "s_barrier" not in block and not loop
+            if not any(o in STEADY_MARKS for o in block) and not row and not loads:
+                skipped.append((i + 1, tgt))
+                i = tgt
+                continue
+        i += 1
+    return path, skipped
+
+
+def classify(op):
+    out = []
+    if op.startswith("v_"):
+        out.append("valu")
+        if op.startswith("v_cmp"):
+            out.append("cmp")
+        if "_f64" in op:
+            out.append("f64")
+        if op.startswith("v_cndmask"):
+            out.append("cndmask")
+        if op.startswith(("v_readlane", "v_writelane", "v_readfirstlane")):
+            out.append("lane")
+        if op.startswith("v_mov") or op.startswith("v_accvgpr"):
+            out.append("mov")
+    elif op.startswith("ds_"):
+        out.append("lds")
+    elif op.startswith(("global_", "buffer_", "flat_", "scratch_")):
+        out.append("vmem")
+    elif op.startswith("s_") and not op.startswith(("s_waitcnt", "s_nop", "s_barrier")):
+        out.append("salu")
+    return out
+
+
+def census(text):
+    ins = parse(text)
+    path, skipped = walk(ins)
+    pos = {i: k for k, i in enumerate(path)}
+    ops = [ins[i][0] for i in path]
+
+    def first(op, start=0):
+        return next(k for k in range(start, len(ops)) if ops[k] == op)
+
+    claim = first("ds_min_rtn_u64")
+    bar_a = first("s_barrier", claim)
+    div = first("v_div_fixup_f64")
+    bar_end = first("s_barrier", div)
+    # the seeding block: skipped, in front of the reciprocal, behind barrier A, with a loop that stores ring entries
+    before = [(a, b) for a, b in skipped if a - 1 in pos and bar_a < pos[a - 1] < div]
+    seeding = [(a, b) for a, b in before
+               if any(o == "global_store_dwordx4" for o, _, _ in ins[a:b]) and any(t is not None and t < j + a for j, (_, _, t) in enumerate(ins[a:b]))]
+    cut = (seeding or before)[-1] if (seeding or before) else None
+    fb = pos[cut[0] - 1] + 1 if cut else bar_a + 1
+    bounds = [0, claim, bar_a + 1, fb, bar_end + 1, len(path)]
+    out = {}
+    for name, a, b in zip(PHASES, bounds, bounds[1:]):
+        row = dict.fromkeys(COLUMNS, 0)
+        row["instructions"] = b - a
+        for k in range(a, b):
+            for c in classify(ops[k]):
+                row[c] += 1
+        row["ops"] = ops[a:b]
+        row["lines"] = [ins[path[k]][:2] for k in range(a, b)]
+        out[name] = row
+    # The filter bank as the round-11 issue counted it by hand: from behind the seeding block's ring-store loop (the block's
+    # tail, which a steady frame does not run) and without following the s_branch in front of the end barrier.
+    extra = []
+    if seeding:
+        a, b = seeding[-1]
+        back = max(j for j in range(a, b) if ins[j][2] is not None and ins[j][2] <= j)
+        extra += [ins[j][0] for j in range(back + 1, b)]
+    for k in range(fb, bar_end + 1):
+        i = path[k]
+        if ops[k] == "s_branch" and ins[i][2] is not None and ins[i][2] > i:
+            extra += [ins[j][0] for j in range(i + 1, ins[i][2])]
+    hand = {c: out["filter bank"][c] for c in COLUMNS}
+    hand["instructions"] = out["filter bank"]["instructions"] + len(extra)
+    for o in extra:
+        for c in classify(o):
+            hand[c] += 1
+    out["filter bank, by hand"] = hand
+    total = dict.fromkeys(COLUMNS, 0)
+    for r in (out[name] for name in PHASES):
+        for c in COLUMNS:
+            total[c] += r[c]
+    total["instructions"] = len(path)
+    out["frame"] = total
+    out["skipped blocks"] = len(skipped)
+    out["kernel instructions"] = len(ins)
+    return out
+
+
+def report(c):
+    lines = [f"k_batch: {c['kernel instructions']} instructions, steady frame {c['frame']['instructions']}, "
+             f"{c['skipped blocks']} guarded blocks skipped",
+             f"{'phase':18s}" + "".join(f"{k:>9s}" for k in ("instr",) + COLUMNS)]
+    for name in PHASES + ("frame", "filter bank, by hand"):
+        r = c[name]
+        lead = f"{name:18s}" if len(name) <= 18 else f"{name}\n{'':18s}"
+        lines.append(lead + f"{r['instructions']:9d}" + "".join(f"{r[k]:9d}" for k in COLUMNS))
+    return "\n".join(lines)
+
+
+def main():
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(root, "ysmr_amd", "csrc", "libysmr_hip.so")
+    with open(src, "rb") as fh:
+        elf = fh.read(4) == b"\x7fELF"
+    text = listing_of_library(src) if elf else open(src).read()
+    if text is None:
+        raise SystemExit("no gfx950 listing of k_batch: llvm-objcopy / llvm-objdump or the kernel are missing")
+    print(report(census(text)))
+
+
+if __name__ == "__main__":
+    main()

@@ -420,62 +420,95 @@ __device__ __forceinline__ void bl_exp_nonpos(const double (&x)[BL_NF], double (
     for (int f = 0; f < BL_NF; ++f) e[f] = __builtin_ldexp(p[f], (int)n[f]);
 }
 
+// The history length at which a lane's filter bank next leaves the steady path (k_batch): 0 for a track without history
+// (the seeding), n_i[mode] while a filter is still to be switched on, INT_MAX once all are.  One compare of the length
+// against it guards everything a track does in three frames of its life.  It is not part of the rest format: n_i ascends
+// strictly (ysmr_tracker_create), so the mode is the number of horizons below it, and the threshold is derived from the
+// stored mode when a seat is loaded (bl_grow_at) and turned back into it in the rare block and at the store (bl_mode_of).
+__device__ __forceinline__ int bl_grow_at(int len, int mode, int nf, const int (&n_i)[BL_NF])
+{
+    if (len == 0) return 0;
+    return mode == 0 && 0 < nf ? n_i[0] : (mode == 1 && 1 < nf ? n_i[1] : (mode == 2 && 2 < nf ? n_i[2] : 0x7FFFFFFF));
+}
+__device__ __forceinline__ int bl_mode_of(int grow_at, int nf, const int (&n_i)[BL_NF])
+{
+    return (int)(0 < nf && n_i[0] < grow_at) + (int)(1 < nf && n_i[1] < grow_at) + (int)(2 < nf && n_i[2] < grow_at);
+}
+
 // GaussianSumFIR.correct + predict of one track by its lane (gsff.py:204-347; the statement order of gsff_wave).
 // leave[f]: the measurement of age N_f - 1 (requested by the caller before the claims); head: the ring position this
 // frame's measurement takes.
 // (struct BlGains { alpha[filter][x / y row], beta[..][..] }: track.hip, the host handle holds one)
 // Gains: BlGains behind a plain pointer (k_track_lanes), or in the constant address space (k_batch: the gains then come
 // with scalar loads and enter the multiplications as scalar operands)
-template <typename Gains>
-__device__ __forceinline__ void bl_gsff(BlSeat &S, const TrackerDev &t, const BatchDev &bd, const Gains &g, int seat, int head,
-                                        const double2 (&leave)[BL_NF], double z0, double z1, bool fresh, double &o0, double &o1)
+// GATED (k_batch): the caller requested leave[f] only where the window of filter f is full and left 0.0 elsewhere, a new
+// track comes with S.len = 0, and grow_at (above) stands in for S.mode, which is not read and not written.  The steady
+// path then has no select on `full` / `fresh` and no mode cascade: those sit behind `len >= grow_at`.  Not GATED
+// (k_track_lanes, whose ring loads leave in the same round as the seat that would gate them): leave[] is whatever the
+// ring held, fresh says that the seat's state is not this track's, grow_at is unused.
+// tr: the tracker's arguments again, for what only the rare block and the tail need (horizons, hist_cap, lik_min) -- k_batch
+// passes the argument segment itself, so that they come with scalar loads where they are used.
+template <bool GATED, typename Args, typename Gains>
+__device__ __forceinline__ void bl_gsff(BlSeat &S, const TrackerDev &t, const Args &tr, const BatchDev &bd, const Gains &g, int seat, int head,
+                                        double2 (&leave)[BL_NF], double z0, double z1, bool fresh, int &grow_at, double &o0, double &o1)
 {
-    const int nf = t.n_f, L = t.hist_cap;
-    const int n_i[BL_NF] = {t.n_i[0], nf > 1 ? t.n_i[1] : 0x7FFFFFFF, nf > 2 ? t.n_i[2] : 0x7FFFFFFF};
-    int len = fresh ? 0 : S.len, mode = fresh ? 0 : S.mode;
-    if (len == 0) {      // history starts as n_i[0] copies of the first measurement (gsff.py:281)
-        const int n0 = n_i[0];
+    const int nf = t.n_f, L = tr.hist_cap;
+    const double lik_min = tr.lik_min;
+    int len = GATED ? S.len : (fresh ? 0 : S.len), mode = GATED ? 0 : (fresh ? 0 : S.mode);
+    if (!GATED || len >= grow_at) {
+        const int n_i[BL_NF] = {tr.n_i[0], nf > 1 ? tr.n_i[1] : 0x7FFFFFFF, nf > 2 ? tr.n_i[2] : 0x7FFFFFFF};
+        if (GATED) mode = bl_mode_of(grow_at, nf, n_i);
+        if (len == 0) {      // history starts as n_i[0] copies of the first measurement (gsff.py:281)
+            const int n0 = n_i[0];
 #pragma unroll
-        for (int f = 0; f < BL_NF; ++f) { S.w[f] = 0.0; S.xa[f] = 0.0; S.xb[f] = 0.0; }
-        const double c1 = (double)(n0 * (n0 - 1) / 2);
+            for (int f = 0; f < BL_NF; ++f) { S.w[f] = 0.0; S.xa[f] = 0.0; S.xb[f] = 0.0; }
+            const double c1 = (double)(n0 * (n0 - 1) / 2);
 #pragma unroll
-        for (int f = 0; f < BL_NF; ++f) {
-            S.s0x[f] = (double)n0 * z0; S.s1x[f] = c1 * z0;
-            S.s0y[f] = (double)n0 * z1; S.s1y[f] = c1 * z1;
-        }
-        for (int a = 0; a < n0; ++a) bl_ring_store(bd, (head - 1 - a) & (BL_HB - 1), seat, z0, z1);
-        len = n0;
-    }
-    bool grew = false;   // gsff.py:283-289: while len(history) >= n_i[mode]: mode += 1
-    if (mode == 0 && 0 < nf && len >= n_i[0]) { mode = 1; grew = true; }
-    if (mode == 1 && 1 < nf && len >= n_i[1]) { mode = 2; grew = true; }
-    if (mode == 2 && 2 < nf && len >= n_i[2]) { mode = 3; grew = true; }
-    // Filters that are not switched on yet carry weight 0 (and finite estimates): every sum below may then run over all
-    // three without a select -- adding a zero term is exact, so a0 + (a1 + a2) is the reference's a0, or a0 + a1
-    if (grew) {          // the estimates of every active filter from the history as it stands, uniform weights
-        const double w0 = mode == 1 ? 1.0 : (mode == 2 ? 0.5 : 1.0 / 3.0);
-#pragma unroll
-        for (int f = 0; f < BL_NF; ++f)
-            if (f < mode) {
-                S.xa[f] = __builtin_fma(-g.beta[f][0], S.s1x[f], g.alpha[f][0] * S.s0x[f]);
-                S.xb[f] = __builtin_fma(-g.beta[f][1], S.s1y[f], g.alpha[f][1] * S.s0y[f]);
-                S.w[f] = w0;
+            for (int f = 0; f < BL_NF; ++f) {
+                S.s0x[f] = (double)n0 * z0; S.s1x[f] = c1 * z0;
+                S.s0y[f] = (double)n0 * z1; S.s1y[f] = c1 * z1;
             }
+            for (int a = 0; a < n0; ++a) bl_ring_store(bd, (head - 1 - a) & (BL_HB - 1), seat, z0, z1);
+            len = n0;
+            if (GATED) {     // what leaves a window that these copies fill is a copy
+#pragma unroll
+                for (int f = 0; f < BL_NF; ++f)
+                    if (len >= n_i[f]) leave[f] = make_double2(z0, z1);
+            }
+        }
+        bool grew = false;   // gsff.py:283-289: while len(history) >= n_i[mode]: mode += 1
+        if (mode == 0 && 0 < nf && len >= n_i[0]) { mode = 1; grew = true; }
+        if (mode == 1 && 1 < nf && len >= n_i[1]) { mode = 2; grew = true; }
+        if (mode == 2 && 2 < nf && len >= n_i[2]) { mode = 3; grew = true; }
+        // Filters that are not switched on yet carry weight 0 (and finite estimates): every sum below may then run over all
+        // three without a select -- adding a zero term is exact, so a0 + (a1 + a2) is the reference's a0, or a0 + a1
+        if (grew) {          // the estimates of every active filter from the history as it stands, uniform weights
+            const double w0 = mode == 1 ? 1.0 : (mode == 2 ? 0.5 : 1.0 / 3.0);
+#pragma unroll
+            for (int f = 0; f < BL_NF; ++f)
+                if (f < mode) {
+                    S.xa[f] = __builtin_fma(-g.beta[f][0], S.s1x[f], g.alpha[f][0] * S.s0x[f]);
+                    S.xb[f] = __builtin_fma(-g.beta[f][1], S.s1y[f], g.alpha[f][1] * S.s0y[f]);
+                    S.w[f] = w0;
+                }
+        }
+        if (GATED) grow_at = mode == 0 ? n_i[0] : (mode == 1 ? n_i[1] : (mode == 2 ? n_i[2] : 0x7FFFFFFF));
     }
     // append the measurement: every entry one frame older, the entry of age N - 1 leaves a full window
-    double nx0[BL_NF], nx1[BL_NF];
 #pragma unroll
     for (int f = 0; f < BL_NF; ++f) {
-        const bool full = len >= n_i[f];
-        // (a track born in this frame: its history is copies of z, written above -- after `leave` was requested)
-        const double lx = full ? (fresh ? z0 : leave[f].x) : 0.0, ly = full ? (fresh ? z1 : leave[f].y) : 0.0;
-        const double nn = -(double)(f < nf ? n_i[f] : 0);
+        double lx = leave[f].x, ly = leave[f].y;
+        if (!GATED) {
+            const bool full = f < nf && len >= t.n_i[f];
+            // (a track born in this frame: its history is copies of z, written above -- after `leave` was requested)
+            lx = full ? (fresh ? z0 : lx) : 0.0; ly = full ? (fresh ? z1 : ly) : 0.0;
+        }
+        // (GATED, a window that is not full: fma(nn, 0.0, s) = s and (s0 + z) - 0.0 = s0 + z, the bits of the line above)
+        const double nn = -(double)(f < nf ? t.n_i[f] : 0);
         S.s1x[f] = __builtin_fma(nn, lx, S.s1x[f] + S.s0x[f]);
         S.s1y[f] = __builtin_fma(nn, ly, S.s1y[f] + S.s0y[f]);
         S.s0x[f] = (S.s0x[f] + z0) - lx;
         S.s0y[f] = (S.s0y[f] + z1) - ly;
-        nx0[f] = __builtin_fma(-g.beta[f][0], S.s1x[f], g.alpha[f][0] * S.s0x[f]);
-        nx1[f] = __builtin_fma(-g.beta[f][1], S.s1y[f], g.alpha[f][1] * S.s0y[f]);
     }
     bl_ring_store(bd, head, seat, z0, z1);
     if (len < L) ++len;
@@ -490,10 +523,11 @@ __device__ __forceinline__ void bl_gsff(BlSeat &S, const TrackerDev &t, const Ba
         ex[f] = -0.5 * q;
     }
     bl_exp_nonpos(ex, lik);
+    // (max, not compare and select: the same value for every l that is not a NaN, and bl_exp_nonpos's domain -- finite
+    // squared distances -- has none)
 #pragma unroll
     for (int f = 0; f < BL_NF; ++f) {
-        double l = lik[f];
-        if (l < t.lik_min) l = t.lik_min;
+        const double l = __builtin_fmax(lik[f], lik_min);
         lik[f] = l;
         total = f == 0 ? l * S.w[f] : total + l * S.w[f];      // (0.0 + a product of non-negative factors is that product)
     }
@@ -505,12 +539,16 @@ __device__ __forceinline__ void bl_gsff(BlSeat &S, const TrackerDev &t, const Ba
     // output = np.sum(x_hat * w, axis=1) = a0 + (a1 + a2)
     o0 = S.xa[0] * S.w[0] + (S.xa[1] * S.w[1] + S.xa[2] * S.w[2]);
     o1 = S.xb[0] * S.w[0] + (S.xb[1] * S.w[1] + S.xb[2] * S.w[2]);
-    // predict: the new estimates, weighted
+    // predict: the new estimates (behind the outputs, which need the old ones: straight into their registers), weighted
 #pragma unroll
-    for (int f = 0; f < BL_NF; ++f) { S.xa[f] = nx0[f]; S.xb[f] = nx1[f]; }
+    for (int f = 0; f < BL_NF; ++f) {
+        S.xa[f] = __builtin_fma(-g.beta[f][0], S.s1x[f], g.alpha[f][0] * S.s0x[f]);
+        S.xb[f] = __builtin_fma(-g.beta[f][1], S.s1y[f], g.alpha[f][1] * S.s0y[f]);
+    }
     S.px = S.xa[0] * S.w[0] + (S.xa[1] * S.w[1] + S.xa[2] * S.w[2]);
     S.py = S.xb[0] * S.w[0] + (S.xb[1] * S.w[1] + S.xb[2] * S.w[2]);
-    S.len = len; S.mode = mode;
+    S.len = len;
+    if (!GATED) S.mode = mode;
 }
 
 // Nearest detection of a prediction among the frame's detections in LDS: D.min(1) / D.argmin(1) of tracker.py:151-163.
@@ -866,7 +904,9 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
     const int nf = t.n_f;
     const int gone_max = (int)floor(t.max_gone);        // tracker.py:104, 208: disappeared > maxDisappeared, a float
     // (max_disappeared < 32000 for a one-launch handle, so the conversion is exact)
-    const int hn[BL_NF] = {t.n_i[0], nf > 1 ? t.n_i[1] : 1, nf > 2 ? t.n_i[2] : 1};    // horizons (ring offsets of the leavers)
+    // horizons: the history length from which a window is full, and the ring offset of its leaver (a filter the handle does
+    // not have: never full -- one compare per filter then gates its load, with no test of nf beside it)
+    const int hn[BL_NF] = {t.n_i[0], nf > 1 ? t.n_i[1] : 0x7FFFFFFF, nf > 2 ? t.n_i[2] : 0x7FFFFFFF};
 
     // ---- start of the batch: counters, this lane's track, the first frame's detections
     int n = *t.n_tracks, next_id = *t.next_id, head = *bd.head & (BL_HB - 1);
@@ -884,6 +924,8 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         bl_seat_load(S, bd, tid);
         S.alive = true;
     }
+    // (S.mode is carried as the threshold it implies, bl_grow_at: the frame loop neither reads nor writes it)
+    int grow_at = bl_grow_at(S.len, S.mode, nf, hn);
     __syncthreads();
     {   // (the ballot outside the branch: under `lane == 0 &&` only lane 0 would vote)
         const unsigned long long ba = __ballot(S.alive);
@@ -976,14 +1018,16 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
                 if (lane == l) nr = w;
             }
         }
-        // the measurements that leave the filters' windows with this frame (used behind the claims)
+        // the measurements that leave the filters' windows with this frame (used behind the claims): requested where the
+        // window is full, 0.0 elsewhere -- bl_gsff then uses them as they are (a track born in this frame has none: its
+        // seeding supplies them)
         double2 leave[BL_NF];
 #pragma unroll
         for (int k = 0; k < BL_NF; ++k) leave[k] = make_double2(0.0, 0.0);
         if (S.alive && t.use_gsff) {
 #pragma unroll
             for (int k = 0; k < BL_NF; ++k)
-                if (k < nf) leave[k] = bl_ring_load(bd, (head - hn[k]) & (BL_HB - 1), tid);
+                if (S.len >= hn[k]) leave[k] = bl_ring_load(bd, (head - hn[k]) & (BL_HB - 1), tid);
         }
         // ---- claims (tracker.py:151-189): a column goes to the proposer with the smallest (distance, id)
         // ONE key per proposal: the bits of the squared distance s without their ten lowest (a non-negative double orders
@@ -1123,6 +1167,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
                 z0 = (double)d[0]; z1 = (double)d[1];
                 box[0] = d[2]; box[1] = d[3]; box[2] = d[4];
                 S.id = next_id + fr; S.rank = n + fr; S.gone = 0;
+                S.len = 0; grow_at = 0;      // (no history: the filter bank seeds it)
                 S.alive = true; fresh = true;
                 atomicMax(&sh.top, tl + 1);
             }
@@ -1134,7 +1179,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         BLSTAMP(6);
         double o0 = z0, o1 = z1;
 #ifdef YSMR_STAMPS
-        const int mode_before = S.mode;
+        const int mode_before = grow_at;      // (the threshold moves when the mode does)
         BLCOUNT(2, S.alive && t.use_gsff && fresh);
 #endif
         if (S.alive) {
@@ -1148,13 +1193,15 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
                 unsigned long long ga = (unsigned long long)gains;
                 asm volatile("" : "+s"(ga));
                 const BlGainsPtr gq = (BlGainsPtr)ga;
-                bl_gsff(S, t, bd, *gq, tid, head, leave, z0, z1, fresh, o0, o1);
+                // (hist_cap, lik_min and the rare block's horizons likewise: read from the argument segment here, beside the
+                // gains, they hold no scalar register across the frame)
+                bl_gsff<true>(S, t, bl_kernargs()->t, bd, *gq, tid, head, leave, z0, z1, fresh, grow_at, o0, o1);
             }
             else { S.px = z0; S.py = z1; }
         }
         // ---- end of the frame: the next frame's detections have landed, the frame's counts are complete
 #ifdef YSMR_STAMPS
-        BLCOUNT(3, S.alive && t.use_gsff && !fresh && S.mode != mode_before);
+        BLCOUNT(3, S.alive && t.use_gsff && !fresh && grow_at != mode_before);
 #endif
         BLSTAMP(7);
         bl_wait_vmem();
@@ -1167,7 +1214,9 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
 #endif
         if (n_dead && S.alive)
             for (int k = 0; k < n_dead; ++k) S.rank -= sh.dead_id[par][k] < S.id;
-        if (S.alive) { S.info[0] = box[0]; S.info[1] = box[1]; S.info[2] = box[2]; }   // (the claimed box: requested before the filter bank)
+        // (the claimed box: requested before the filter bank.  Unconditional: a lane without a track copies its own info, or
+        // the zeros of the track it just lost -- never stored, never in a row, overwritten by the next registration)
+        S.info[0] = box[0]; S.info[1] = box[1]; S.info[2] = box[2];
         const int n_live = n - n_dead + n_new;
         const BlKernArgsPtr kr = bl_kernargs();
         ysmr_row *rows = kr->rows;
@@ -1196,6 +1245,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         be.grid = ke->bd.grid; be.grid_stride = ke->bd.grid_stride; be.seat_cap = ke->bd.seat_cap;
         if (tid < seats) {
             be.i32[5 * (size_t)be.seat_cap + tid] = S.alive ? 1 : 0;
+            S.mode = bl_mode_of(grow_at, nf, {ke->t.n_i[0], nf > 1 ? ke->t.n_i[1] : 0x7FFFFFFF, nf > 2 ? ke->t.n_i[2] : 0x7FFFFFFF});
             if (S.alive) bl_seat_store(S, be, tid);
         }
         if (tid == 0) { *ke->t.n_tracks = n; *ke->t.next_id = next_id; *ke->row_count = base; *be.head = head; }
@@ -1350,7 +1400,7 @@ __global__ __launch_bounds__(TL_THREADS) void k_track_lanes(TrackerDev t, BatchD
             if (fresh) bl_seat_blank(S);
             else if ((frame & (BL_REFRESH - 1)) == 0)          // (on the frame NUMBER, as k_batch: rows must not depend on the batching)
                 bl_sums_from_ring(S, bd, slot, head, t.n_i[0], nf > 1 ? t.n_i[1] : 0, nf > 2 ? t.n_i[2] : 0);
-            bl_gsff(S, t, bd, *gains, slot, head, leave, z0, z1, fresh, o0, o1);
+            { int unused = 0; bl_gsff<false>(S, t, t, bd, *gains, slot, head, leave, z0, z1, fresh, unused, o0, o1); }
             p0 = S.px; p1 = S.py;
             S.id = id;
             bl_seat_store(S, bd, slot);
