@@ -17,8 +17,12 @@ res0 = pipe.det[0].detect(frames[:B]); res1 = pipe.det[1].detect(frames[B:]); to
 L = _lib.lib()
 NW = int(os.environ.get("BL_WAVES", "16"))
 buf = (ctypes.c_ulonglong * (NW * 16))()
-names = ["dma issue + clear next keys", "search + key atomic", "barrier A", "key read (+ exact claim path)", "ageing / deregistration",
-         "registration", "filter bank", "wait vmcnt(0)", "end barrier", "ranks + row"]
+# (a pass of the frame loop: the search and the claim of a frame, barrier A, the ranks and the row of the frame before, the
+# rest of the frame; one barrier)
+names = ["search + key atomic", "wait (grid block) + barrier A", "dma issue + key read + ranks, row of the frame before",
+         "exact claim path", "ageing / deregistration", "registration + clear keys two frames ahead",
+         "wait vmcnt(0) + filter bank"]
+LAST = len(names)
 # per wave over the launch's frames (g_bcounts): how often each rarely taken path ran
 count_names = ["wave-frames with a lane on the 3 x 3 block search", "lanes on the 3 x 3 block search",
                "wave-frames seeding a new track's filter bank", "wave-frames with a grown filter bank (old track)",
@@ -45,9 +49,9 @@ for rep in range(12 if beside else 6):
     torch.cuda.synchronize()
     L.ysmr_debug_read_bstamps(buf)
     full = np.array(buf[:], dtype=np.int64).reshape(NW, 16)
-    a = full[:, :11]
+    a = full[:, :LAST + 1]
     acc.append(a)
-    print("   fast path per wave:", (full[:, 11] - full[:, 1]).tolist(), " lanes left to the wave search:", full[:, 12].tolist())
+    print("   fast path per wave:", (full[:, 11] - full[:, 0]).tolist(), " lanes left to the wave search:", full[:, 12].tolist())
     print("   over the launch's frames: lanes left to the wave search per wave", full[:, 13].tolist(), "= %.2f per frame; frames in which a wave ran it:" % (full[:, 13].sum() / B), full[:, 14].tolist())
     rt0, rt1, mt0, mt1 = int(full[0, 15]), int(full[1, 15]), int(full[2, 15]), int(full[3, 15])
     if rt1 > rt0:
@@ -58,11 +62,11 @@ for rep in range(12 if beside else 6):
         cn = np.array(cnt[:], dtype=np.int64).reshape(NW, len(count_names))
         for k, what in enumerate(count_names):
             print(f"   {what:58s}", cn[:, k].tolist())
-    print(f"rep {rep}: launch pair {t0.elapsed_time(t1) * 1e3:.1f} us for {B} frames; frame (wave 0) {a[0, 10] - a[0, 0]} cycles")
+    print(f"rep {rep}: launch pair {t0.elapsed_time(t1) * 1e3:.1f} us for {B} frames; frame (wave 0) {a[0, LAST] - a[0, 0]} cycles")
 a = np.mean(np.array(acc), axis=0) if beside else np.median(np.array(acc), axis=0)
 d = np.diff(a, axis=1)
 print("%-44s" % "phase (cycles of s_memtime, 100 MHz? no: shader clock)", " ".join(f"w{w:<6d}" for w in range(NW)))
 for k, n in enumerate(names):
     print("%-44s" % n, " ".join(f"{d[w, k]:<7.0f}" for w in range(NW)))
-print("%-44s" % "frame", " ".join(f"{a[w, 10] - a[w, 0]:<7.0f}" for w in range(NW)))
+print("%-44s" % "frame", " ".join(f"{a[w, LAST] - a[w, 0]:<7.0f}" for w in range(NW)))
 print(pipe.trk.info())

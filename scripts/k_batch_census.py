@@ -18,16 +18,22 @@ wrote, or the compiler's own -S output.  The walk starts at the head of the fram
     stores of a seeding, a run's later candidates): neither is taken -- unless the fall-through is an s_branch that would
     jump over a landmark (a steady block the compiler laid out of line).
 
-Landmarks, in the order a frame meets them: the ds_read_b128 of the candidate list, ds_min_rtn_u64 (the claim), the
-s_barrier behind it (barrier A), v_div_fixup_f64 (the weights' reciprocal), the end-of-frame s_barrier, the row's
-global_store_dwordx4 pair.  They cut the frame into phases:
+The frame has ONE barrier: a pass of the loop is the search and the claim of a frame, barrier A, the ranks and the row of
+the frame before, then the rest of the frame up to its filter bank.  Landmarks, in the order a pass meets them: the
+ds_read_b128 of the candidate list, ds_min_rtn_u64 (the claim), the s_barrier behind it (barrier A), the row's
+global_store_dwordx4 pair, v_div_fixup_f64 (the weights' reciprocal).  They cut the pass into phases:
 
-  chores + search    loop head .. the claim's atomic
+  chores + search    loop head .. the claim's atomic; and the loop's tail behind the filter bank (the frame's bookkeeping
+                     and the closing branch), which runs straight into the next pass's search
   claims             .. behind the claim's own wait and barrier A
+  ranks + row        .. behind the row's last store (of the frame before: its deaths are known behind barrier A)
   ageing             .. the end of the seeding block (the last skipped block in front of the reciprocal that stores to the
                      ring in a loop; without one: the last skipped block in front of the reciprocal)
-  filter bank        .. the end-of-frame barrier
-  ranks + row        .. the loop's closing branch
+  filter bank        .. behind its last float64 instruction or the ring store (global_store_dwordx4), whichever comes
+                     later.  (The source puts a scheduling barrier between the filter bank and what follows, so no
+                     instruction of the next search is counted here and none of the filter bank is counted there.)
+
+The report ends with the number of s_barrier on the walked path.
 
 Per phase: VALU (every v_* instruction; the lane moves v_readlane / v_writelane / v_readfirstlane are part of it and listed
 again on their own), float64 (v_*_f64, compares included), v_cndmask, lane moves, v_mov, compares, SALU, LDS, VMEM.
@@ -47,7 +53,7 @@ KERNEL = "_ZN12_GLOBAL__N_17k_batchENS_10BlKernArgsE"
 BUNDLE_MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 COND = ("s_cbranch_execz", "s_cbranch_vccz", "s_cbranch_vccnz", "s_cbranch_scc0", "s_cbranch_scc1")
 STEADY_MARKS = ("ds_read_b128", "ds_min_rtn_u64", "v_div_fixup_f64")
-PHASES = ("chores + search", "claims", "ageing", "filter bank", "ranks + row")
+PHASES = ("chores + search", "claims", "ranks + row", "ageing", "filter bank")
 COLUMNS = ("valu", "f64", "cndmask", "lane", "mov", "cmp", "salu", "lds", "vmem")
 
 
@@ -218,32 +224,40 @@ def census(text):
     claim = first("ds_min_rtn_u64")
     bar_a = first("s_barrier", claim)
     div = first("v_div_fixup_f64")
-    bar_end = first("s_barrier", div)
+    # the row: the first pair of 16-byte stores behind barrier A, and the stores that follow them directly
+    row_end = first("global_store_dwordx4", first("global_store_dwordx4", bar_a) + 1) + 1
+    while row_end < len(ops) and (ops[row_end].startswith("global_store") or ops[row_end].startswith("s_waitcnt")):
+        row_end += 1
+    # the filter bank ends behind its last float64 instruction or the ring store
+    fb_end = max(k for k in range(div, len(ops)) if "_f64" in ops[k] or ops[k] == "global_store_dwordx4") + 1
     # the seeding block: skipped, in front of the reciprocal, behind barrier A, with a loop that stores ring entries
     before = [(a, b) for a, b in skipped if a - 1 in pos and bar_a < pos[a - 1] < div]
     seeding = [(a, b) for a, b in before
                if any(o == "global_store_dwordx4" for o, _, _ in ins[a:b]) and any(t is not None and t < j + a for j, (_, _, t) in enumerate(ins[a:b]))]
     cut = (seeding or before)[-1] if (seeding or before) else None
     fb = pos[cut[0] - 1] + 1 if cut else bar_a + 1
-    bounds = [0, claim, bar_a + 1, fb, bar_end + 1, len(path)]
+    if not bar_a < row_end <= fb <= div < fb_end <= len(path):
+        raise SystemExit("the walked path does not have the frame's shape: claim, barrier A, row, filter bank")
+    bounds = [0, claim, bar_a + 1, row_end, fb, fb_end]
     out = {}
     for name, a, b in zip(PHASES, bounds, bounds[1:]):
+        ks = list(range(a, b)) + (list(range(fb_end, len(path))) if name == "chores + search" else [])
         row = dict.fromkeys(COLUMNS, 0)
-        row["instructions"] = b - a
-        for k in range(a, b):
+        row["instructions"] = len(ks)
+        for k in ks:
             for c in classify(ops[k]):
                 row[c] += 1
-        row["ops"] = ops[a:b]
-        row["lines"] = [ins[path[k]][:2] for k in range(a, b)]
+        row["ops"] = [ops[k] for k in ks]
+        row["lines"] = [ins[path[k]][:2] for k in ks]
         out[name] = row
     # The filter bank as the round-11 issue counted it by hand: from behind the seeding block's ring-store loop (the block's
-    # tail, which a steady frame does not run) and without following the s_branch in front of the end barrier.
+    # tail, which a steady frame does not run) and without following an s_branch inside the phase.
     extra = []
     if seeding:
         a, b = seeding[-1]
         back = max(j for j in range(a, b) if ins[j][2] is not None and ins[j][2] <= j)
         extra += [ins[j][0] for j in range(back + 1, b)]
-    for k in range(fb, bar_end + 1):
+    for k in range(fb, fb_end):
         i = path[k]
         if ops[k] == "s_branch" and ins[i][2] is not None and ins[i][2] > i:
             extra += [ins[j][0] for j in range(i + 1, ins[i][2])]
@@ -260,6 +274,9 @@ def census(text):
     total["instructions"] = len(path)
     out["frame"] = total
     out["skipped blocks"] = len(skipped)
+    out["barriers"] = sum(o == "s_barrier" for o in ops)
+    out["path"] = [ins[i][:2] for i in path]
+    out["marks"] = {"claim": claim, "barrier A": bar_a, "row end": row_end, "filter bank": fb, "filter bank end": fb_end}
     out["kernel instructions"] = len(ins)
     return out
 
@@ -272,6 +289,7 @@ def report(c):
         r = c[name]
         lead = f"{name:18s}" if len(name) <= 18 else f"{name}\n{'':18s}"
         lines.append(lead + f"{r['instructions']:9d}" + "".join(f"{r[k]:9d}" for k in COLUMNS))
+    lines.append(f"s_barrier on the walked path: {c['barriers']}")
     return "\n".join(lines)
 
 

@@ -8,7 +8,7 @@
 //   detections   k_bgrid (one workgroup per frame, the whole batch at once, before this kernel) bins every frame's
 //                detections into a uniform grid of cells (counting sort) and leaves header | cell starts (u16) |
 //                centres in cell order | their column numbers (u16) | candidates per cell as one contiguous block per frame; this kernel
-//                brings the block of frame f+1 into LDS by LDS-DMA while it works on frame f.
+//                brings the block of frame f+2 into LDS by LDS-DMA while it works on frames f and f+1.
 //   row minimum  tracker.py:151-163 reads only D.min(1) and D.argmin(1): a lane reads the candidate list k_bgrid left for
 //                its prediction's cell (every detection that can be nearest to a point of the cell, <= 8), in float, and
 //                evaluates the winner once in float64 (bl_search); outside the grid, in a cell with more candidates, or
@@ -37,8 +37,9 @@
 //                so rounding drift is bounded by 64 updates: ~1e-11 px, the size of a from-scratch sum's own rounding.
 //   rows         one 40-byte ysmr_row per live lane at rows[base + rank], fire and forget.
 //
-// Two workgroup barriers per frame (after the atomic round, and at the end of the frame, where the next frame's
-// detections must have landed).  Why not the history in registers (the first build of this kernel: 158 registers per
+// One workgroup barrier per frame, behind the atomic round of the claims: the ranks, the row and the counts of a frame --
+// all that needs every wave to be past the frame's ageing -- are settled behind the NEXT frame's barrier, and a wave goes
+// from its filter bank straight into the next frame's search (k_batch, above the frame loop).  Why not the history in registers (the first build of this kernel: 158 registers per
 // track): 512 tracks fill a compute unit's register file, BASELINE configs[2] holds up to 535; and a frame then costs the
 // 186 float64 operations of re-summing and shifting 62 values per track, on ONE unit's float64 pipe (7.4 us per frame).
 //
@@ -837,8 +838,10 @@ __device__ unsigned long long g_bcounts[BL_WAVES][BL_COUNTS];
 #endif
 struct BlShared {      // static part of the LDS
     int cnt[BL_MAX_BATCH];           // detections per frame (clamped)
-    int used[2], n_dead[2];          // per frame parity: claims made, tracks deregistered
-    int tie[2];                      // per frame parity: some column's proposals are too close for the short key
+    int used[2];                     // per frame parity: claims made
+    int n_dead[2];                   // per frame parity: tracks deregistered, as a RUNNING count over the launch (k_batch)
+    int tie[2];                      // per frame parity: the last frame in which some column's proposals were too close
+                                     // for the short key (a frame NUMBER: never reset)
     int dead_id[2][BL_THREADS];      // ids of the tracks deregistered in the frame
     int wave_cnt[2][BL_WAVES];       // registration: per-wave counts of the two ranked lists
     int set_state[2];
@@ -846,10 +849,14 @@ struct BlShared {      // static part of the LDS
 };
 
 __host__ __device__ inline int bl_md_padded(int max_det) { return (max_det + 3) / 4 * 4; }
+// dynamic part: three key tables (u64 per column), one table of winning ids (u32), two grid blocks, the set model's table
 __host__ __device__ inline size_t bl_lds_bytes(int max_det)
 {
-    return 2 * 4 * (size_t)bl_grid_dwords_max(max_det) + 2 * 12 * (size_t)bl_md_padded(max_det) + 4 * BL_TABLE + 64;
+    return 2 * 4 * (size_t)bl_grid_dwords_max(max_det) + (3 * 8 + 4) * (size_t)bl_md_padded(max_det) + 4 * BL_TABLE + 64;
 }
+// all of it: what one workgroup of k_batch takes of a compute unit's 160 KiB (the static part is BlShared and nothing else)
+__host__ __device__ inline size_t bl_lds_total(int max_det) { return bl_lds_bytes(max_det) + (sizeof(BlShared) + 15) / 16 * 16; }
+constexpr size_t BL_LDS_LIMIT = 160 * 1024;
 
 // The kernel's arguments as ONE structure: the kernel argument segment then IS this structure, and an argument that one
 // phase of a frame needs (the row buffer, the detections' boxes, the error word, the state arrays at the end) is read
@@ -893,13 +900,14 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
     const unsigned long long below = (1ull << lane) - 1ull;
     const int md = t.max_det, mdp = bl_md_padded(md);
     const int bufw = bl_grid_dwords_max(md);
-    // LDS by offset (bl_lds): per frame parity p the smallest proposing key per column (u64), the winning id per column
-    // (u32: the exact claim path's second round, and scratch of the registration) and the frame's detections (k_bgrid's
-    // block); the CPython set model's table
-    auto key_at = [&](int p) { return bl_lds + p * mdp; };
-    auto cid_at = [&](int p) { return bl_u32(4 * mdp + p * mdp); };
-    auto buf_off = [&](int p) { return 6 * mdp + p * bufw; };
-    const int tab_off = 6 * mdp + 2 * bufw;
+    // LDS by offset (bl_lds): THREE tables of the smallest proposing key per column (u64; frame f uses table f % 3, see the
+    // frame loop), one table of the winning id per column (u32: the exact claim path's second round and the registration's
+    // list, which never overlap -- the registration starts with a barrier), per frame parity the frame's detections
+    // (k_bgrid's block); the CPython set model's table
+    auto key_at = [&](int k) { return bl_lds + k * mdp; };
+    auto cid_at = [&]() { return bl_u32(6 * mdp); };
+    auto buf_off = [&](int p) { return 7 * mdp + p * bufw; };
+    const int tab_off = 7 * mdp + 2 * bufw;
     const int seats = min(t.capacity, BL_THREADS);
     const int nf = t.n_f;
     const int gone_max = (int)floor(t.max_gone);        // tracker.py:104, 208: disappeared > maxDisappeared, a float
@@ -916,7 +924,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         if (m > md) { m = md; atomicOr(t.err, ERR_DET_CLAMPED); }
         sh.cnt[f] = m < 0 ? 0 : m;
     }
-    if (tid < 2) { sh.used[tid] = 0; sh.n_dead[tid] = 0; sh.tie[tid] = 0; }
+    if (tid < 2) { sh.used[tid] = 0; sh.n_dead[tid] = 0; sh.tie[tid] = -1; }
     if (tid == 0) sh.top = 0;
     BlSeat S;
     bl_seat_blank(S);
@@ -932,9 +940,10 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         if (lane == 0 && ba) atomicMax(&sh.top, 64 * (wave + 1));
     }
     __syncthreads();
-    // The chores of a frame -- the next frame's LDS-DMA, clearing its tables -- go to the waves that hold no track, when
-    // there are any: with 9 of 12 waves in use, three of them share one SIMD and set the frame's pace, and the idle waves
-    // sit on the other SIMDs.  (Seats are handed out lowest first, so the waves in use are the first ones.)
+    // The chores of a frame -- the LDS-DMA of the detections two frames ahead, clearing their key table -- go to the waves
+    // that hold no track, when there are any: with 9 of 12 waves in use, three of them share one SIMD and set the frame's
+    // pace, and the idle waves sit on the other SIMDs.  (Seats are handed out lowest first, so the waves in use are the
+    // first ones.)
     int helpers_from = (sh.top + 63) >> 6;               // first wave without a track; BL_WAVES: none
     auto chore_first = [&]() { return helpers_from < BL_WAVES ? tid - 64 * helpers_from : tid; };
     auto chore_stride = [&]() { return helpers_from < BL_WAVES ? 64 * (BL_WAVES - helpers_from) : BL_THREADS; };
@@ -948,14 +957,81 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
             asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(__builtin_amdgcn_readfirstlane(lds)), "v"(off), "s"(src) : "memory");
         }
     };
-    dma(0);
+    // the first two frames' detections and key tables
+#pragma nounroll
+    for (int k = 0; k < 2 && k < batch; ++k) dma(k);
     for (int c = tid; c < sh.cnt[0]; c += BL_THREADS) key_at(0)[c] = ~0ull;
+    if (batch > 1)
+        for (int c = tid; c < sh.cnt[1]; c += BL_THREADS) key_at(1)[c] = ~0ull;
     bl_wait_vmem();
     __syncthreads();
 
+    // ---- the frame loop: ONE workgroup barrier per frame, barrier A behind the claims' atomic round.
+    // Between A(f) and A(f + 1) a wave runs, in this order: the ranks and the row of frame f - 1 (settle), the counts; the
+    // key read of frame f, ageing / deregistration, registration (rare, with barriers of its own), the filter bank; then
+    // the search of frame f + 1 and its claim.  Nothing frame f + 1's search needs waits for the other waves: the lane's
+    // own prediction, and the grid block of f + 1, which landed before A(f).  What does need "every wave is past frame
+    // f's ageing" -- n_dead / dead_id of frame f, hence the ranks, the row and the counts -- is read behind A(f + 1).
+    // What the end-of-frame barrier of earlier versions ordered, and what orders it now (A(f) = barrier A of frame f):
+    //   key tables   three.  Table (f + 2) % 3 is cleared for frame f + 2 between A(f) and A(f + 1); its last readers (the
+    //                key read, the exact path and the registration's scan of frame f - 1) finished before they arrived at
+    //                A(f), which the clearing wave has passed; frame f + 2's atomics come behind A(f + 1).  Behind A(f)
+    //                that table is dead, so it is frame f's registration's scratch first; the clearing follows the
+    //                registration's last barrier in program order.
+    //   cid          one table: the exact path's last read of it and the registration's first write are a barrier apart.
+    //   grid blocks  two.  Block f + 2 is requested behind A(f) into the buffer of frame f, last read (search, wave
+    //                search) in front of A(f); the requesting waves wait vmcnt(0) in front of A(f + 1), the search of
+    //                f + 2 starts behind it.
+    //   sh.tie       holds a frame number per parity, compared with the frame's own: no reset, which would race with
+    //                the next frame's setters in the same interval.
+    //   sh.n_dead    a running count per parity, never reset: written (atomicAdd) between A(f) and A(f + 1), read behind
+    //                A(f + 1), written again behind A(f + 2), which every reader has passed.  Every wave keeps the value
+    //                a parity's count had when the frame started (d_cur, d_prev: read behind a barrier, so uniform) and
+    //                subtracts it.  dead_id likewise: rewritten behind A(f + 2).
+    //   sh.used      as before: parity par ^ 1 is reset behind A(f); it was last read by frame f - 1's registration, in
+    //                front of A(f), and is next added to behind A(f + 1).
+    // The claim key carries S.rank as it stood BEFORE frame f - 1's deaths were taken off (they are, behind A(f)).  It is
+    // still a valid tie-breaker: for two live tracks a < b (by id) the stale ranks are the true ranks plus the number of
+    // frame f - 1's dead with a smaller id, which is no smaller for b than for a -- so stale ranks stay unique among the
+    // live tracks, ascend with the id, and stay below the seat count (10 bits).  A birth's rank n + fr is exact: a frame
+    // that registers ages nobody (`age` is false when n < m), n has had every earlier frame's deaths taken off behind
+    // A(f), and its births are added where they happen.
+    int kc = 0;                      // the frame's key table: f % 3
+    int d_cur = 0, d_prev = 0;       // sh.n_dead[par], sh.n_dead[par ^ 1] as they stood before frame f, frame f - 1
+    double o0 = 0.0, o1 = 0.0;       // the filter bank's outputs: a frame's row leaves behind the next frame's barrier A
+    // ranks, row and counts of frame `fr`, whose deaths were counted in sh.n_dead[slot] from `start` on; behind the barrier
+    // that follows the frame's ageing.  Returns the running count.
+    auto settle = [&](int slot, int start, int fr, bool row) {
+        const int total = sh.n_dead[slot];
+        const int n_dead = total - start;
+#ifdef YSMR_STAMPS
+        if (lane == 0 && n_dead) { g_bcounts[wave][6] += 1; g_bcounts[wave][7] += n_dead; }
+#endif
+        if (n_dead && S.alive)
+            for (int k = 0; k < n_dead; ++k) S.rank -= sh.dead_id[slot][k] < S.id;
+        n -= n_dead;
+        if (row) {
+            const BlKernArgsPtr kr = bl_kernargs();
+            ysmr_row *rows = kr->rows;
+            const long long rows_capacity = kr->rows_capacity;
+            if (S.alive && base + S.rank < rows_capacity) {      // track_eval.py:313-316
+                ysmr_row rr;
+                rr.frame = frame0 + fr;
+                rr.track_id = S.id;
+                rr.x = o0; rr.y = o1;
+                rr.w = S.info[0]; rr.h = S.info[1]; rr.angle = S.info[2];
+                rr.disappeared = S.gone;
+                rows[base + S.rank] = rr;
+            }
+            if (tid == 0 && base + n > rows_capacity) atomicOr(kr->t.err, ERR_ROWS_CAPACITY);
+            base += n;
+        }
+        return total;
+    };
     for (int f = 0; f < batch; ++f) {
         const int par = f & 1;
-        const int m = sh.cnt[f], m_next = f + 1 < batch ? sh.cnt[f + 1] : 0;
+        const int kn = kc == 2 ? 0 : kc + 1, ks = kc == 0 ? 2 : kc - 1;      // the tables of frame f + 1, and of f + 2 = f - 1
+        const int m = sh.cnt[f];
         BLSTAMP(0);
 #ifdef YSMR_STAMPS
         if (f == 0 && lane == 0)
@@ -963,21 +1039,12 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         BLCOUNT(5, ((frame0 + f) & (BL_REFRESH - 1)) == 0 && S.alive && t.use_gsff);
 #endif
         if (((frame0 + f) & (BL_REFRESH - 1)) == 0 && S.alive && t.use_gsff) {     // (uniform but for `alive`: see bl_sums_from_ring)
+            // (the lane's own ring stores of the frame before are complete, and nothing of the ring is left outstanding
+            // in the compiler's books: it would otherwise wait for vmcnt(0) -- the row stores -- in the search of every frame)
+            bl_wait_vmem();
             bl_sums_from_ring(S, bd, tid, head, t.n_i[0], nf > 1 ? t.n_i[1] : 0, nf > 2 ? t.n_i[2] : 0);
-            // (nothing of the ring left outstanding in the compiler's books: it would otherwise wait for vmcnt(0) -- last
-            // frame's row stores -- in the search of every frame)
             bl_wait_vmem();
         }
-        if (f + 1 < batch) dma(f + 1);
-        // The next frame's keys are cleared here, by the waves that would otherwise wait at barrier A.  Parity par ^ 1 was
-        // last touched in frame f - 1: its keys were read by the claims and the registration's scan, and the registration
-        // of a frame uses the OTHER parity's tables as scratch -- in frame f - 1 that was parity par, cleared again before
-        // that frame's end barrier; this frame's registration uses par ^ 1 behind barrier A, after these stores, and clears
-        // it again itself.  All of frame f - 1's accesses lie before its end barrier, which every wave has passed; the
-        // exact claim path below touches the tables of parity par only.  Frame f + 1 reads them behind this frame's end
-        // barrier.
-        for (int c = chore_first(); c >= 0 && c < m_next; c += chore_stride()) key_at(par ^ 1)[c] = ~0ull;
-        BLSTAMP(1);
         // ---- each track proposes its nearest detection (tracker.py:151-163)
         const bool propose = S.alive && m > 0;
         const BlGridView gv = bl_grid_view(buf_off(par), m);
@@ -1020,7 +1087,17 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         }
         // the measurements that leave the filters' windows with this frame (used behind the claims): requested where the
         // window is full, 0.0 elsewhere -- bl_gsff then uses them as they are (a track born in this frame has none: its
-        // seeding supplies them)
+        // seeding supplies them).  An entry a lane reads here it wrote itself, frames ago as a rule; in the frame before
+        // only when the track was born in it, and that frame waited for its ring stores (below, behind the filter bank).
+        // The box of the proposed detection, requested before the claim is settled (a proposer that loses its column has
+        // asked for nothing it uses) and taken in front of the filter bank: behind barrier A the load would be the
+        // youngest in flight where the filter bank waits for the leaving measurements, and the wait for those -- counted
+        // in order -- would wait for it as well, a round trip to HBM a few dozen instructions old.
+        float bx[3] = {0.f, 0.f, 0.f};
+        if (propose) {
+            const float *d = bl_kernargs()->det_all + ((size_t)f * md + nr.col) * 5;
+            bx[0] = d[2]; bx[1] = d[3]; bx[2] = d[4];
+        }
         double2 leave[BL_NF];
 #pragma unroll
         for (int k = 0; k < BL_NF; ++k) leave[k] = make_double2(0.0, 0.0);
@@ -1032,9 +1109,9 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         // ---- claims (tracker.py:151-189): a column goes to the proposer with the smallest (distance, id)
         // ONE key per proposal: the bits of the squared distance s without their ten lowest (a non-negative double orders
         // like its bits), and in their place the lane's table row -- below 768, unique among the live tracks, ascending
-        // with the id (the order the reference breaks ties in, tracker.py:158), as last frame's "ranks + row" or the
-        // registration left it.  The smallest key of a column is its winner unless two proposals are so close that the
-        // dropped bits could matter: their s agree in the 54 bits kept, or differ by one step there (a pair a few ulps
+        // with the id (the order the reference breaks ties in, tracker.py:158), as the settling of the frame before last
+        // or a registration left it (stale by the last frame's deaths: see above the loop).  The smallest key of a column
+        // is its winner unless two proposals are so close that the dropped bits could matter: their s agree in the 54 bits kept, or differ by one step there (a pair a few ulps
         // apart can straddle a truncation boundary).  Only then can two different s round to the same root, or the smaller
         // s belong to the higher row.  Every other key lies at least two steps above the minimum: its s is larger by more
         // than 2^-43 of it, its root differs, and it loses under the exact rule too.
@@ -1044,86 +1121,91 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         // that lane raises the frame's flag.  Keys farther above M need no flag.
         if (propose) {
             key = ((unsigned long long)__double_as_longlong(nr.s) & ~0x3FFull) | (unsigned long long)S.rank;
-            const unsigned long long before = atomicMin(&key_at(par)[nr.col], key);
-            if ((before >> 10) - (key >> 10) + 1ull <= 2ull) sh.tie[par] = 1;     // (an empty column: 2^54 - 1, far from every s)
+            const unsigned long long before = atomicMin(&key_at(kc)[nr.col], key);
+            if ((before >> 10) - (key >> 10) + 1ull <= 2ull) sh.tie[par] = f;     // (an empty column: 2^54 - 1, far from every s)
         }
-        BLSTAMP(2);
+        BLSTAMP(1);
+        // (the waves that requested a grid block behind the barrier before: it has landed.  Track waves beside helper
+        // waves requested none and wait for no vector memory access here: their row and ring stores go on in flight)
+        if (helpers_from >= BL_WAVES || wave >= helpers_from) bl_wait_vmem();
         block_sync<true>();
-        BLSTAMP(3);
-        // (the other parity's counters were last read behind the end barrier of the previous frame, its flag before it)
-        if (tid == BL_THREADS - 1) { sh.used[par ^ 1] = 0; sh.n_dead[par ^ 1] = 0; sh.tie[par ^ 1] = 0; }
+        BLSTAMP(2);
+        // ---- behind barrier A: every wave is past frame f - 1's ageing and registration, and past frame f's search
+        if (tid == BL_THREADS - 1) sh.used[par ^ 1] = 0;
+        if (f + 2 < batch) dma(f + 2);
         // (both reads in one LDS round: every lane reads a key -- column 0 where it proposed nothing -- and the flag rides along)
-        const unsigned long long k_won = key_at(par)[nr.col];
-        const int exact = sh.tie[par];
+        const unsigned long long k_won = key_at(kc)[nr.col];
+        const int exact = sh.tie[par] == f;
+        const int d_total = settle(par ^ 1, d_prev, f - 1, f > 0);
+        BLSTAMP(3);
         bool mine = propose && k_won == key;
         if (exact) {
             // The exact rule, for every column of the frame (uniform: the flag was set before barrier A and stands until
-            // the next frame's): the smallest s in full, then the proposers at the column's smallest DISTANCE contend by
-            // id.  sqrt is monotone, so that is the smallest s -- and an s a few ulps above it that rounds to the same
+            // frame f + 2 sets it again, behind A(f + 1)): the smallest s in full, then the proposers at the column's
+            // smallest DISTANCE contend by id.  sqrt is monotone, so that is the smallest s -- and an s a few ulps above it that rounds to the same
             // root: only those take the square roots.  A wave that comes here late may have read a key above that the
             // clearing had already replaced; its `mine` is set again below.
 #ifdef YSMR_STAMPS
             if (wave == 0 && lane == 0) g_bcounts[0][8] += 1;
 #endif
-            for (int c = tid; c < m; c += BL_THREADS) { key_at(par)[c] = ~0ull; cid_at(par)[c] = 0xFFFFFFFFu; }
+            for (int c = tid; c < m; c += BL_THREADS) { key_at(kc)[c] = ~0ull; cid_at()[c] = 0xFFFFFFFFu; }
             block_sync<true>();
             if (propose) {
                 key = (unsigned long long)__double_as_longlong(nr.s);
-                atomicMin(&key_at(par)[nr.col], key);
+                atomicMin(&key_at(kc)[nr.col], key);
             }
             block_sync<true>();
             if (propose) {
-                const unsigned long long kmin = key_at(par)[nr.col];
+                const unsigned long long kmin = key_at(kc)[nr.col];
                 bool tie = key == kmin;
                 if (!tie) {
                     const double smin = __longlong_as_double((long long)kmin);
                     if (nr.s <= smin + smin * 0x1p-48) tie = sqrt(nr.s) == sqrt(smin);
                 }
-                if (tie) atomicMin(&cid_at(par)[nr.col], (uint32_t)S.id);
+                if (tie) atomicMin(&cid_at()[nr.col], (uint32_t)S.id);
             }
             block_sync<true>();
-            mine = propose && cid_at(par)[nr.col] == (uint32_t)S.id;
+            mine = propose && cid_at()[nr.col] == (uint32_t)S.id;
         }
         BLSTAMP(4);
         // ---- ageing and deregistration (tracker.py:95-107, 198-211)
         const bool age = (m == 0) || (n > 0 && n >= m);
         double z0 = S.px, z1 = S.py;
-        float box[3] = {S.info[0], S.info[1], S.info[2]};
         bool fresh = false, died = false;
         if (mine) {
             z0 = (double)nr.zx; z1 = (double)nr.zy;
-            const float *d = bl_kernargs()->det_all + ((size_t)f * md + nr.col) * 5;
-            box[0] = d[2]; box[1] = d[3]; box[2] = d[4];
-            S.gone = 0;
+            S.gone = 0;      // (the claimed box: in front of the filter bank)
         } else if (S.alive && age) {
             ++S.gone;
-            box[0] = box[1] = box[2] = 0.f;
+            S.info[0] = S.info[1] = S.info[2] = 0.f;
             if (S.gone > gone_max) { S.alive = false; died = true; }
         }
         {
             const unsigned long long bm = __ballot(mine), bx = __ballot(died);
             if (lane == 0 && bm) atomicAdd(&sh.used[par], (int)__popcll(bm));
-            if (bx) {      // the ids of the deregistered tracks: every younger track moves up one table row
+            if (bx) {      // the ids of the deregistered tracks: every younger track moves up one table row (settle)
                 int at = 0;
                 if (lane == 0) at = atomicAdd(&sh.n_dead[par], (int)__popcll(bx));
-                at = __builtin_amdgcn_readfirstlane(at);
+                at = __builtin_amdgcn_readfirstlane(at) - d_cur;
                 if (died) sh.dead_id[par][at + __popcll(bx & below)] = S.id;
             }
         }
         BLSTAMP(5);
         // ---- registration (tracker.py:135-137, 212-217): unclaimed columns become tracks, in CPython set order
-        int n_new = 0, n_new_all = 0;
+        const bool births = m > 0 && (n == 0 || n < m);        // (uniform; nobody was aged in such a frame)
 #ifdef YSMR_STAMPS
-        BLCOUNT(4, m > 0 && (n == 0 || n < m));
+        BLCOUNT(4, births);
 #endif
-        if (m > 0 && (n == 0 || n < m)) {        // (uniform; nobody was aged in such a frame)
+        if (births) {
             // (the thread, its wave and lane as values of this frame: the compiler hoisted the comparisons with them out of
             // the frame loop, a pair of scalar registers each, held for the whole launch and spilled into vector lanes)
             int tl = tid, wv = wave, ln = lane, mp = mdp;
             asm volatile("" : "+v"(tl), "+s"(wv), "+v"(ln), "+s"(mp));
-            int *unused = reinterpret_cast<int *>(key_at(par ^ 1)), *newcols = unused + mp;
-            uint32_t *list = cid_at(par ^ 1);
+            // scratch: the key table of frame f - 1, dead behind A(f) and cleared for frame f + 2 below
+            int *unused = reinterpret_cast<int *>(key_at(ks)), *newcols = unused + mp;
+            uint32_t *list = cid_at();
             __syncthreads();
+            int n_new = 0, n_new_all = 0;
             if (n == 0) {
                 for (int c = tl; c < m; c += BL_THREADS) newcols[c] = c;
                 n_new_all = m;
@@ -1132,7 +1214,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
                 const int K = (m + BL_THREADS - 1) / BL_THREADS;
                 const int c0 = tl * K, c1 = min(c0 + K, m);
                 int cnt = 0;
-                for (int c = c0; c < c1; ++c) cnt += key_at(par)[c] == ~0ull;      // (a column with a proposer has a winner)
+                for (int c = c0; c < c1; ++c) cnt += key_at(kc)[c] == ~0ull;      // (a column with a proposer has a winner)
                 int incl = cnt;
 #pragma unroll
                 for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (ln >= d) incl += o; }
@@ -1142,7 +1224,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
 #pragma unroll
                 for (int k = 0; k < BL_WAVES; ++k) { const int v = sh.wave_cnt[0][k]; at += k < wv ? v : 0; total += v; }
                 for (int c = c0; c < c1; ++c)
-                    if (key_at(par)[c] == ~0ull) unused[at++] = c;
+                    if (key_at(kc)[c] == ~0ull) unused[at++] = c;
                 __syncthreads();
                 int cnt_set = cpython_order_lds<BL_THREADS, BL_TABLE>(unused, total, m, sh.used[par], newcols, bl_u32(tab_off), list, sh.set_state);
                 if (cnt_set < 0) { if (tl == 0) atomicOr(bl_kernargs()->t.err, ERR_TRACK_CAPACITY); cnt_set = 0; }
@@ -1165,19 +1247,37 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
                 const int c = newcols[fr];
                 const float *d = bl_kernargs()->det_all + ((size_t)f * md + c) * 5;
                 z0 = (double)d[0]; z1 = (double)d[1];
-                box[0] = d[2]; box[1] = d[3]; box[2] = d[4];
+                S.info[0] = d[2]; S.info[1] = d[3]; S.info[2] = d[4];
                 S.id = next_id + fr; S.rank = n + fr; S.gone = 0;
                 S.len = 0; grow_at = 0;      // (no history: the filter bank seeds it)
                 S.alive = true; fresh = true;
                 atomicMax(&sh.top, tl + 1);
             }
-            __syncthreads();     // (the lists lived in the next frame's tables)
-            for (int c = tl; c < m_next; c += BL_THREADS) key_at(par ^ 1)[c] = ~0ull;
+            // (the counts take the births where they happen: nothing between here and the settling reads them, and the
+            // deaths -- none in this frame -- come off behind the next barrier A)
+            n += n_new;
+            next_id += n_new_all;
+            // (a wave that stops being a helper here has requested its pieces of a grid block: they land before it
+            // forgets; __syncthreads: the lists lived in the table that is cleared next, and sh.top is complete)
+            bl_wait_vmem();
+            __syncthreads();
             helpers_from = (sh.top + 63) >> 6;
+        }
+        // The keys of frame f + 2 are cleared here, by the waves that would otherwise wait at barrier A: see above the loop
+        // (behind the registration, whose scratch this table was)
+        {
+            const int m_ahead = f + 2 < batch ? sh.cnt[f + 2] : 0;
+            for (int c = chore_first(); c >= 0 && c < m_ahead; c += chore_stride()) key_at(ks)[c] = ~0ull;
         }
         // ---- the filter bank (tracker.py:219-227)
         BLSTAMP(6);
-        double o0 = z0, o1 = z1;
+        // The one wait for vector memory of a track wave's frame: the leaving measurements and the box, requested in front
+        // of barrier A, and with them (the count is in order) the row stores of the frame before, a hundred instructions
+        // old.  For every lane, with or without a track: the compiler then knows that no load is in flight at the head of
+        // the loop, and does not guard the search's registers with waits that would catch the ring store.
+        bl_wait_vmem();
+        if (mine) { S.info[0] = bx[0]; S.info[1] = bx[1]; S.info[2] = bx[2]; }
+        o0 = z0; o1 = z1;
 #ifdef YSMR_STAMPS
         const int mode_before = grow_at;      // (the threshold moves when the mode does)
         BLCOUNT(2, S.alive && t.use_gsff && fresh);
@@ -1199,44 +1299,23 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
             }
             else { S.px = z0; S.py = z1; }
         }
-        // ---- end of the frame: the next frame's detections have landed, the frame's counts are complete
 #ifdef YSMR_STAMPS
         BLCOUNT(3, S.alive && t.use_gsff && !fresh && grow_at != mode_before);
 #endif
+        // (a frame that registered: the seeding's ring stores are complete before the next frame reads the entries that
+        // leave the new tracks' windows -- the only ring entries a lane reads in the frame after it wrote them)
+        if (births) bl_wait_vmem();
+        // (the search below is the next frame's: nothing of it is scheduled into the filter bank, nor the reverse --
+        // scripts/k_batch_census.py ends the filter bank's phase at its last float64 instruction / the ring store)
+        __builtin_amdgcn_sched_barrier(0);
         BLSTAMP(7);
-        bl_wait_vmem();
-        BLSTAMP(8);
-        __syncthreads();
-        BLSTAMP(9);
-        const int n_dead = sh.n_dead[par];
-#ifdef YSMR_STAMPS
-        if (lane == 0 && n_dead) { g_bcounts[wave][6] += 1; g_bcounts[wave][7] += n_dead; }
-#endif
-        if (n_dead && S.alive)
-            for (int k = 0; k < n_dead; ++k) S.rank -= sh.dead_id[par][k] < S.id;
-        // (the claimed box: requested before the filter bank.  Unconditional: a lane without a track copies its own info, or
-        // the zeros of the track it just lost -- never stored, never in a row, overwritten by the next registration)
-        S.info[0] = box[0]; S.info[1] = box[1]; S.info[2] = box[2];
-        const int n_live = n - n_dead + n_new;
-        const BlKernArgsPtr kr = bl_kernargs();
-        ysmr_row *rows = kr->rows;
-        const long long rows_capacity = kr->rows_capacity;
-        if (S.alive && base + S.rank < rows_capacity) {      // track_eval.py:313-316
-            ysmr_row rr;
-            rr.frame = frame0 + f;
-            rr.track_id = S.id;
-            rr.x = o0; rr.y = o1;
-            rr.w = S.info[0]; rr.h = S.info[1]; rr.angle = S.info[2];
-            rr.disappeared = S.gone;
-            rows[base + S.rank] = rr;
-        }
-        if (tid == 0 && base + n_live > rows_capacity) atomicOr(kr->t.err, ERR_ROWS_CAPACITY);
-        base += n_live;
-        n = n_live;
-        next_id += n_new_all;
+        d_prev = d_cur; d_cur = d_total;
+        kc = kn;
         head = (head + 1) & (BL_HB - 1);
-        BLSTAMP(10);
     }
+    // ---- the last frame's ranks, row and counts, behind a barrier that every wave's ageing of it has reached
+    block_sync<true>();
+    settle((batch - 1) & 1, d_prev, batch - 1, true);
     // ---- end of the batch: the small state goes back to HBM, seat by seat
     {
         const BlKernArgsPtr ke = bl_kernargs();

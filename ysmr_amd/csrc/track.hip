@@ -2313,7 +2313,7 @@ int ysmr_tracker_create(double max_disappeared, double fps, int n_min, double n_
     // frame as before.
     t->batch_lds = bl_lds_bytes(max_det);
     t->batchable = t->fused && d.n_f <= BL_NF && d.hist_cap <= BL_HB && (!use_gsff || d.gains_decoupled) &&
-                   capacity <= BL_THREADS && t->batch_lds <= 140 * 1024 && !(mode_env && strcmp(mode_env, "batch"));
+                   capacity <= BL_THREADS && bl_lds_total(max_det) <= BL_LDS_LIMIT && !(mode_env && strcmp(mode_env, "batch"));
     if (t->batchable &&
         hipFuncSetAttribute((const void *)k_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->batch_lds) != hipSuccess)
         t->batchable = false;
