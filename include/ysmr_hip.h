@@ -281,8 +281,10 @@ int ysmr_tracker_reset(ysmr_tracker *t, void *stream);
  * ysmr_tracker_peek3 -- ysmr_tracker_update and ysmr_tracker_run return YSMR_ERR_STATE on it, as the three do on a 2-D
  * handle.  It links with one launch per frame (k_frame), or two (k_link + k_track) where a 2-D handle of that capacity and
  * max_det would, and finds every row minimum by the all-pairs search: the grid searches and the one-launch batch link are
- * two-dimensional by construction, so ysmr_tracker_batched is 0 and ysmr_tracker_prepare a no-op for it.  Without a filter
- * bank the position of a track is the last point it claimed, all three coordinates; a lost track keeps it. */
+ * two-dimensional by construction, so ysmr_tracker_batched is 0 and ysmr_tracker_prepare a no-op for it -- except that
+ * ysmr_tracker_link_mode(t, 2) asks for the 3-D batch link (below): ysmr_tracker_batched then answers 1 for a handle that
+ * link serves, and its binning is prepared with ysmr_tracker_prepare3 (ysmr_tracker_prepare stays a no-op).  Without a
+ * filter bank the position of a track is the last point it claimed, all three coordinates; a lost track keeps it. */
 int ysmr_tracker_dimensions(ysmr_tracker *t, int dimensions);
 
 /* One CentroidTracker.update(rects).  det_dev: [m][5] = cx, cy, w, h, angle; f32 as written by
@@ -328,7 +330,14 @@ int ysmr_tracker_fused(ysmr_tracker *t);
  *   ysmr_tracker_batched    1 when ysmr_tracker_run takes the one-launch-per-batch path, else 0
  *   ysmr_tracker_link_mode  mode 0: the library's choice (default); 1: one launch per frame even where a batch launch
  *                           would serve (measurement and tests).  Takes effect with the next call; the track table is
- *                           carried over. */
+ *                           carried over.
+ *                           2: as 0, and a 3-D handle whose configuration allows it -- linked with one launch per frame,
+ *                           capacity <= 768, max_det small enough for the kernel's LDS (2048 is) -- also links a batch of
+ *                           ysmr_tracker_run3 with ONE launch (k_batch3: the same workgroup without a filter bank, the third
+ *                           coordinate in the distances and in the stored point).  ysmr_tracker_batched then answers 1 for
+ *                           it; every other 3-D handle keeps the per-frame link, and on a 2-D handle mode 2 is mode 0.  The
+ *                           memory the 3-D batch link needs is allocated by the first such call.  Both paths of a 3-D
+ *                           handle emit the same rows and keep the same points, bit for bit (no filter is involved). */
 int ysmr_tracker_batched(ysmr_tracker *t);
 int ysmr_tracker_link_mode(ysmr_tracker *t, int mode);
 
@@ -343,11 +352,18 @@ int ysmr_tracker_link_mode(ysmr_tracker *t, int mode);
  * detections and you call it again. */
 int ysmr_tracker_prepare(ysmr_tracker *t, void *stream, const float *det_dev, const int32_t *det_count_dev, int batch,
                          int slot);
+/* ... for a 3-D handle (ysmr_tracker_prepare is a no-op on one; this returns YSMR_ERR_STATE on a 2-D handle, like the
+ * other 3-D calls): the same contract and the same two slots, with third_dev f64 [batch][max_det] binned beside the
+ * centres; good for ONE ysmr_tracker_run3 with the same det_dev, third_dev, det_count_dev and batch.  A no-op unless
+ * ysmr_tracker_batched. */
+int ysmr_tracker_prepare3(ysmr_tracker *t, void *stream, const float *det_dev, const double *third_dev,
+                          const int32_t *det_count_dev, int batch, int slot);
 
 int ysmr_tracker_run(ysmr_tracker *t, void *stream, const float *det_dev,
                      const int32_t *det_count_dev, int batch, int32_t first_frame_index,
                      ysmr_row *rows_dev, int64_t rows_capacity, int64_t *row_count_dev);
-/* ... for a 3-D handle: third_dev f64 [batch][max_det], as ysmr_luminosity_batch writes it. */
+/* ... for a 3-D handle: third_dev f64 [batch][max_det], as ysmr_luminosity_batch writes it (slots at or beyond a frame's
+ * count are never read).  One launch per frame, or per batch in link mode 2 (above). */
 int ysmr_tracker_run3(ysmr_tracker *t, void *stream, const float *det_dev, const double *third_dev,
                       const int32_t *det_count_dev, int batch, int32_t first_frame_index, ysmr_row *rows_dev,
                       int64_t rows_capacity, int64_t *row_count_dev);

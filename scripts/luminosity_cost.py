@@ -2,16 +2,19 @@
 """What 'include luminosity in tracking calculation' costs on the bench clip (recorded, not gated: DESIGN.md 4).
 
 The bench workload (1228 x 922, ~500 blobs, a clip of two batches resident in HBM, detection of batch b+1 beside the link of
-batch b) with 'disable gsff' = True, in three forms on one build:
+batch b) with 'disable gsff' = True, in four forms on one build:
 
-  batch-2d   the default 2-D link (one launch per batch)            -- for orientation
-  frame-2d   2-D with ysmr_tracker_link_mode(t, 1): one launch per frame, the link a 3-D handle also takes
-  lum-3d     luminosity on: k_luminosity behind the labelling chain, ysmr_tracker_run3
+  batch-2d       the default 2-D link (one launch per batch)            -- for orientation
+  frame-2d       2-D with ysmr_tracker_link_mode(t, 1): one launch per frame
+  lum-3d         luminosity on: k_luminosity behind the labelling chain, ysmr_tracker_run3 as the pipeline runs it (link
+                 mode 2: one k_batch3 launch per batch for this shape)
+  lum-3d-frame   the same with the handle forced to link mode 1: one launch per frame, what a 3-D handle took before the
+                 3-D batch link
 
     python scripts/luminosity_cost.py [--steps 10] [--warmup 3] [--only lum-3d]
 
 One JSON line per form.  ``--only lum-3d`` under ``rocprofv3 --kernel-trace --stats`` gives k_luminosity's time per batch
-beside the labelling chain's.
+beside the labelling chain's, and k_bgrid3 / k_batch3 per batch.
 """
 import argparse
 import json
@@ -43,15 +46,15 @@ def main():
     B = auto_batch(H, W)
     F = 2 * B
     frames = torch.from_numpy(SyntheticVideo(H, W, blobs, seed=0, fps=30.0).frames(F)).cuda()
-    for form in ("batch-2d", "frame-2d", "lum-3d"):
+    for form in ("batch-2d", "frame-2d", "lum-3d", "lum-3d-frame"):
         if args.only and form != args.only:
             continue
         s = default_settings()
         s["disable gsff"] = True
-        s["include luminosity in tracking calculation"] = form == "lum-3d"
-        # (frame-2d: the handle is told before the detectors are built, so that they take the threshold kernel and the
-        # resident grids that go with a per-frame link beside them -- as they do for a 3-D handle)
-        te.DeviceTracker = PerFrameTracker if form == "frame-2d" else DeviceTracker
+        s["include luminosity in tracking calculation"] = form.startswith("lum-3d")
+        # (frame-2d, lum-3d-frame: the handle is told before the detectors are built, so that they take the threshold kernel
+        # and the resident grids that go with a per-frame link beside them)
+        te.DeviceTracker = PerFrameTracker if form in ("frame-2d", "lum-3d-frame") else DeviceTracker
         pipe = TrackingPipeline(H, W, 30.0, s, batch=B, max_det=2048, capacity=768, rows_per_flush=F * 768)
         te.DeviceTracker = DeviceTracker
 

@@ -60,7 +60,7 @@ EXPORTS = ("ysmr_abi_version", "ysmr_last_error", "ysmr_detect_workspace_bytes",
            "ysmr_rows_format_csv", "ysmr_rows_write_csv", "ysmr_rows_write_csv_columns", "ysmr_rows_format_device_workspace_bytes", "ysmr_rows_format_device", "ysmr_rows_format_csv_devicelike", "ysmr_rows_stream_create", "ysmr_rows_stream_push", "ysmr_rows_stream_count", "ysmr_rows_stream_finish", "ysmr_rows_stream_destroy", "ysmr_rows_columns", "ysmr_select_workspace_bytes", "ysmr_select_tracks",
            "ysmr_evaluate_workspace_bytes", "ysmr_evaluate_tracks", "ysmr_unpack_dib_batch", "ysmr_file_read",
            "ysmr_luminosity_batch", "ysmr_luminosity_batch_host", "ysmr_tracker_dimensions", "ysmr_tracker_update3",
-           "ysmr_tracker_run3", "ysmr_tracker_peek3")
+           "ysmr_tracker_run3", "ysmr_tracker_peek3", "ysmr_tracker_prepare3")
 
 SELECT_OK, SELECT_TOO_SHORT, SELECT_TOO_SHORT_CLEANED, SELECT_NONE = 0, 1, 2, 3
 
@@ -151,6 +151,7 @@ def lib():
     L.ysmr_tracker_batched.argtypes = [vp]
     L.ysmr_tracker_link_mode.argtypes = [vp, ci]
     L.ysmr_tracker_prepare.argtypes = [vp, vp, vp, vp, ci, ci]
+    L.ysmr_tracker_prepare3.argtypes = [vp, vp, vp, vp, vp, ci, ci]
     L.ysmr_luminosity_batch.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp]
     L.ysmr_luminosity_batch_host.argtypes = [vp, ci, ci, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp]
     L.ysmr_tracker_dimensions.argtypes = [vp, ci]

@@ -1530,7 +1530,8 @@ __global__ __launch_bounds__(TL_THREADS) void k_track_lanes(TrackerDev t, BatchD
 
 // ---- conversions between the seat-major rest format and the per-slot layout of k_frame / k_link + k_track ----------
 // (a: the CURRENT parity view of the per-slot state; table row r takes seat r)
-__global__ void k_to_batch(TrackerDev a, BatchDev bd)
+// pos3 / seat3: a 3-D handle's third coordinate by slot, and seat-major f64 [seat_cap] (NULL on a 2-D handle)
+__global__ void k_to_batch(TrackerDev a, BatchDev bd, const double *pos3, double *seat3)
 {
     const int n = *a.n_tracks, cap = a.capacity, L = a.hist_cap, nf = a.n_f;
     const int head = *bd.head & (BL_HB - 1);
@@ -1553,6 +1554,7 @@ __global__ void k_to_batch(TrackerDev a, BatchDev bd)
         }
         p[sc * (3 * BL_NF)] = a.pos[slot];
         p[sc * (3 * BL_NF + 1)] = a.pos[cap + slot];
+        if (seat3) seat3[r] = pos3[slot];
         {   // the window sums, exactly as bl_sums_from_ring forms them
             const int len = (int)(__double_as_longlong(rec[0]) & 0xFFFFFFFFll);
             double s0x = 0.0, s1x = 0.0, s0y = 0.0, s1y = 0.0;
@@ -1581,7 +1583,7 @@ __global__ void k_to_batch(TrackerDev a, BatchDev bd)
 
 // (d: the parity-0 view; the track in seat s goes to table row rank[s], which takes slot rank[s]; the free stack hands
 // out slot n next)
-__global__ void k_to_std(TrackerDev d, BatchDev bd)
+__global__ void k_to_std(TrackerDev d, BatchDev bd, double *pos3, const double *seat3)
 {
     const int n = *d.n_tracks, cap = d.capacity, L = d.hist_cap, nf = d.n_f;
     const int head = *bd.head & (BL_HB - 1);
@@ -1608,6 +1610,7 @@ __global__ void k_to_std(TrackerDev d, BatchDev bd)
         }
         d.pos[r] = p[sc * (3 * BL_NF)];
         d.pos[cap + r] = p[sc * (3 * BL_NF + 1)];
+        if (seat3) pos3[r] = seat3[s];
         for (int k = 0; k < 3; ++k) d.info[k * cap + r] = bd.f32[sc * k + s];
         d.id[r] = bd.i32[s];
         d.order[r] = r;
@@ -1627,4 +1630,687 @@ __global__ void k_peek_batch(TrackerDev t, BatchDev bd, int32_t *ids, double *xy
     if (ids) ids[i] = bd.i32[s];
     if (xy) { xy[2 * i] = bd.f64[sc * (3 * BL_NF) + s]; xy[2 * i + 1] = bd.f64[sc * (3 * BL_NF + 1) + s]; }
     if (gone) gone[i] = bd.i32[sc + s];
+}
+
+// the third coordinate of every track in id order from the seat-major rest format (ysmr_tracker_peek3, behind k_peek_batch)
+__global__ void k_peek_third_batch(TrackerDev t, BatchDev bd, const double *seat3, double *third)
+{
+    const size_t sc = (size_t)bd.seat_cap;
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= bd.seat_cap || *t.n_tracks == 0 || !bd.i32[5 * sc + s]) return;
+    third[bd.i32[4 * sc + s]] = seat3[s];
+}
+
+// ==== the batch link of a 3-D handle (ysmr_tracker_dimensions(t, 3), ysmr_tracker_link_mode(t, 2)) ====================
+// CentroidTracker.update on (x, y, luminosity) points without a filter bank (the reference raises with one): k_batch without
+// the ring, the gains and bl_gsff, and with a third coordinate in the prediction, in the distances and in the stored
+// position.  One workgroup, a track per lane, a batch per launch; the frame loop, its one barrier, the claim keys, the
+// registration and the rows are k_batch's (the comments above its loop hold here word for word).  Rows carry x and y only.
+//
+// A frame's block, written by k_bgrid3 (cells in the plane, exactly as k_bgrid bins them):
+//   [0, 16)            header as above; [6] = 0 (no candidate lists); [7] = 1 when some |third| of the frame is not below
+//                      4096 (or not a number): the float stage's error band does not hold, every lane searches exactly
+//   [16, ..)           start (u16), centres (x, y) f32 in cell order, column numbers (u16): as above
+//   [.., + MP)         the third coordinate in cell order, ROUNDED to f32 (padding: 0): the float stage's plane
+//   -- up to here, rounded up to whole KiB, the block is brought into LDS; at the same offset in every block of a handle
+//      (bl3_lds_dwords_max(max_det) dwords from its start) follows, in HBM only:
+//   [.., + 2 MP)       the third coordinate in cell order as the f64 the caller gave
+// No candidate lists: bl_cell_list drops a detection that is farther IN THE PLANE at every point of the cell, and in three
+// dimensions such a detection can still be the nearest.  The search is the 3 x 3 block's, in every frame.
+// Why the f64 plane stays in HBM: the two LDS buffers, the three key tables, the id table and the set model take 140 KB at
+// max_det = 2048; an f64 plane in both buffers would add 33 KB, the f32 plane adds 16 (157 KB with the static part, of 160).
+// A lane's float-stage winner costs one 8-byte load from the tail before its claim key is built; the exact wave search
+// reads the tail coalesced, in cell order like the centres.
+__host__ __device__ inline int bl3_lds_dwords(int m) { return (bl_list_off(m) + bl_mp(m) + 255) / 256 * 256; }
+// (without candidate lists the size only grows with m -- bl_grid_n and bl_mp do -- so the largest block is max_det's)
+__host__ __device__ inline int bl3_lds_dwords_max(int max_det) { return bl3_lds_dwords(max_det); }
+__host__ __device__ inline size_t bl3_grid_stride(int max_det)      // bytes per frame: the LDS part and the f64 tail, whole KiB
+{
+    return 4 * (size_t)bl3_lds_dwords_max(max_det) + (8 * (size_t)bl_mp(max_det) + 1023) / 1024 * 1024;
+}
+__host__ __device__ inline size_t bl3_lds_bytes(int max_det)
+{
+    return 2 * 4 * (size_t)bl3_lds_dwords_max(max_det) + (3 * 8 + 4) * (size_t)bl_md_padded(max_det) + 4 * BL_TABLE + 64;
+}
+__host__ __device__ inline size_t bl3_lds_total(int max_det) { return bl3_lds_bytes(max_det) + (sizeof(BlShared) + 15) / 16 * 16; }
+
+// One workgroup per frame, as k_bgrid: the same cells and the same counting sort (a frame's centres come out in the same
+// order), without the candidate lists.  The bounding box, the cells' size, the cell of a detection, the scan of the counts
+// and the scatter are k_bgrid's lines VERBATIM (k_bgrid itself is frozen by the tests that read k_batch's listing from the
+// same header; once that lifts, the two should share one __device__ body) -- a fix to the binning there belongs here too.
+// New here: z[], `wide` / s_wide and header word 7, the z32 / z64 planes, and the copy-out's length.  A detection's third coordinate is read where its centre is (slots at or beyond the
+// frame's count are never read) and follows it into its cell: rounded into the LDS part, as it is into the tail -- which
+// does not pass through this kernel's LDS (the block's image here is the LDS part alone).
+__global__ __launch_bounds__(BG_THREADS) void k_bgrid3(const float *__restrict__ det_all, const double *__restrict__ third_all,
+                                                       const int32_t *__restrict__ det_count, int max_det, char *grid, unsigned grid_stride)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_out[];
+    __shared__ int s_cnt[64 * 64];
+    __shared__ float s_red[4][4];
+    __shared__ int s_wave_sum[4];
+    __shared__ int s_wide;
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const float *det = det_all + (size_t)f * max_det * 5;
+    const double *third = third_all + (size_t)f * max_det;
+    int m = det_count[f];
+    m = m < 0 ? 0 : (m > max_det ? max_det : m);
+    const int G = bl_grid_n(m), cells = G * G;
+    unsigned short *start16 = reinterpret_cast<unsigned short *>(s_out + 16);
+    float2 *xy = reinterpret_cast<float2 *>(s_out + 16 + bl_start_dwords(G));
+    unsigned short *items = reinterpret_cast<unsigned short *>(s_out + 16 + bl_start_dwords(G) + 2 * bl_mp(m));
+    float *z32 = reinterpret_cast<float *>(s_out + bl_list_off(m));
+    double *z64 = reinterpret_cast<double *>(grid + (size_t)grid_stride * f + 4 * (size_t)bl3_lds_dwords_max(max_det));
+    float x[BG_PER], y[BG_PER];
+    double z[BG_PER];
+    bool wide = false;
+#pragma unroll
+    for (int k = 0; k < BG_PER; ++k) {
+        const int j = tid + k * BG_THREADS;
+        x[k] = j < m ? det[(size_t)j * 5] : 0.f;
+        y[k] = j < m ? det[(size_t)j * 5 + 1] : 0.f;
+        z[k] = j < m ? third[j] : 0.0;
+        wide = wide || !(fabs(z[k]) < 4096.0);
+    }
+    for (int c = tid; c < cells; c += BG_THREADS) s_cnt[c] = 0;
+    if (tid == 0) s_wide = 0;
+    float lo_x = 3.0e38f, lo_y = 3.0e38f, hi_x = -3.0e38f, hi_y = -3.0e38f;
+#pragma unroll
+    for (int k = 0; k < BG_PER; ++k)
+        if (tid + k * BG_THREADS < m) { lo_x = fminf(lo_x, x[k]); hi_x = fmaxf(hi_x, x[k]); lo_y = fminf(lo_y, y[k]); hi_y = fmaxf(hi_y, y[k]); }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        lo_x = fminf(lo_x, __shfl_xor(lo_x, d)); hi_x = fmaxf(hi_x, __shfl_xor(hi_x, d));
+        lo_y = fminf(lo_y, __shfl_xor(lo_y, d)); hi_y = fmaxf(hi_y, __shfl_xor(hi_y, d));
+    }
+    if (lane == 0) { s_red[0][w] = lo_x; s_red[1][w] = hi_x; s_red[2][w] = lo_y; s_red[3][w] = hi_y; }
+    __syncthreads();
+    if (wide) s_wide = 1;
+    lo_x = s_red[0][0]; hi_x = s_red[1][0]; lo_y = s_red[2][0]; hi_y = s_red[3][0];
+    for (int k = 1; k < 4; ++k) {
+        lo_x = fminf(lo_x, s_red[0][k]); hi_x = fmaxf(hi_x, s_red[1][k]);
+        lo_y = fminf(lo_y, s_red[2][k]); hi_y = fmaxf(hi_y, s_red[3][k]);
+    }
+    if (m == 0) { lo_x = lo_y = 0.f; hi_x = hi_y = 1.f; }
+    const float extent = fmaxf(fmaxf(hi_x - lo_x, hi_y - lo_y), 1.0f);
+    const float cell = extent / (float)(G - 2), inv = 1.0f / cell;
+    const float x0 = lo_x - cell, y0 = lo_y - cell;
+    if (tid < 16) s_out[tid] = 0;
+    __syncthreads();
+    if (tid == 0) {
+        float *h = reinterpret_cast<float *>(s_out);
+        h[0] = x0; h[1] = y0; h[2] = cell; h[3] = inv;
+        s_out[4] = (uint32_t)G; s_out[5] = (uint32_t)m; s_out[6] = 0; s_out[7] = (uint32_t)s_wide;
+    }
+    int cell_of[BG_PER];
+#pragma unroll
+    for (int k = 0; k < BG_PER; ++k) {
+        int cx = (int)floorf((x[k] - x0) * inv), cy = (int)floorf((y[k] - y0) * inv);
+        cx = cx < 0 ? 0 : (cx > G - 1 ? G - 1 : cx);
+        cy = cy < 0 ? 0 : (cy > G - 1 ? G - 1 : cy);
+        cell_of[k] = cy * G + cx;
+        if (tid + k * BG_THREADS < m) atomicAdd(&s_cnt[cell_of[k]], 1);
+    }
+    __syncthreads();
+    // exclusive scan of the counts, as k_bgrid
+    const int K = cells / BG_THREADS;
+    int local[16], sum = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        if (k < K) { local[k] = sum; sum += s_cnt[tid * K + k]; }
+    int incl = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
+    if (lane == 63) s_wave_sum[w] = incl;
+    __syncthreads();
+    int before = incl - sum;
+    for (int k = 0; k < w; ++k) before += s_wave_sum[k];
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        if (k < K) {
+            const int at = before + local[k];
+            s_cnt[tid * K + k] = at;
+            start16[tid * K + k] = (unsigned short)at;
+        }
+    if (tid == BG_THREADS - 1) { start16[cells] = (unsigned short)m; start16[cells + 1] = 0; }
+    for (int j = m + tid; j < bl_mp(m); j += BG_THREADS) { xy[j] = make_float2(1.0e30f, 1.0e30f); items[j] = 0; z32[j] = 0.f; z64[j] = 0.0; }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < BG_PER; ++k) {
+        const int j = tid + k * BG_THREADS;
+        if (j < m) {
+            const int at = atomicAdd(&s_cnt[cell_of[k]], 1);
+            items[at] = (unsigned short)j;
+            xy[at] = make_float2(x[k], y[k]);
+            z32[at] = (float)z[k];
+            z64[at] = z[k];
+        }
+    }
+    __syncthreads();
+    uint4 *out = reinterpret_cast<uint4 *>(grid + (size_t)grid_stride * f);
+    const uint4 *img = reinterpret_cast<const uint4 *>(s_out);
+    for (int i = tid; i < bl3_lds_dwords(m) / 4; i += BG_THREADS) out[i] = img[i];
+}
+
+// ---- a 3-D track in registers: the point the reference keeps in objects[id], the box, id, counters -------------------
+struct Bl3Seat {
+    double px, py, pz;
+    float info[3];
+    int id, gone, rank;
+    bool alive;
+};
+// rest format: px, py, the box, id, gone, rank and the seat flag where k_batch keeps them in BatchDev (k_peek_batch reads both),
+// history length and mode 0, pz in seat3 f64 [seat_cap]
+
+struct BlNear3 { double s, z; float zx, zy; int col; bool done; };
+
+__device__ __forceinline__ double bl_dist3(double px, double py, double pz, float2 c, double cz)
+{
+    // cdist's order (luminosity_model.cdist; rowmin_wave<.., true>): dx * dx + dy * dy + dz * dz, summed left to right
+    const double dx = px - (double)c.x;
+    const double dy = py - (double)c.y;
+    const double dz = pz - cz;
+    double s = dx * dx;
+    s = s + dy * dy;
+    s = s + dz * dz;
+    return s;
+}
+__device__ __forceinline__ float bl_dist3f(float fx, float fy, float fz, float2 c, float cz)
+{
+    const float dx = fx - c.x, dy = fy - c.y, dz = fz - cz;
+    return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+}
+// Float error band of a 3-D squared distance, for |px|, |py|, |pz| and every |third| below 4096 (k_bgrid3 flags a frame
+// with a larger one, the caller tests pz).  (float)px, (float)py and (float)pz are off by at most 2^-24 * 4096 = 2.4e-4; the
+// centres are float already, but the candidate's third coordinate was ROUNDED to float as well: dz is off by 4.9e-4, dx
+// and dy by 2.4e-4.  Unlike a planar distance inside a 3 x 3 block, dz has no bound but 8192, so the error is taken relative
+// to the distance: |s_f - s| <= 2 (|dx| + |dy|) 2.4e-4 + 2 |dz| 4.9e-4 + 4 * 2^-24 s <= 9.8e-4 * sqrt(3 s) + 2.4e-7 s, and with
+// a sqrt(s) <= t + a^2 s / (4 t) at t = 0.05: <= 0.05 + 1.5e-5 s; the key drops 2^-19 s more: e(s) <= 0.05 + 1.7e-5 s.
+// A detection that is truly as near as the float winner (float distance b) has a float distance of at most
+// b + 2 e(s_winner) <= b + 0.1002 + 3.5e-5 b: the band below is that with a margin (twice in the constant, 1.4 x in the slope).
+__device__ __forceinline__ float bl3_band(float best) { return best + (0.2f + 5e-5f * best); }
+
+// bl_search_block in three dimensions: float keys of dx^2 + dy^2 + dz^2 over the 3 x 3 cells.  "Nothing outside the block
+// is as near" stays a test in the PLANE: a detection's 3-D distance is never below its planar distance, so one that lies
+// beyond the block's boundary in the plane is farther than the boundary in space.  z32: dword offset of the block's f32
+// plane in LDS; z64: its f64 plane in HBM.
+__device__ __forceinline__ BlNear3 bl_search_block3(const BlGridView &g, int z32, const double *__restrict__ z64, double px, double py,
+                                                    double pz, int m)
+{
+    constexpr int R = 3, C = 5;
+    const int G = g.G;
+    const float fx = (float)px, fy = (float)py, fz = (float)pz;
+    int cx = (int)floorf((fx - g.x0) * g.inv), cy = (int)floorf((fy - g.y0) * g.inv);
+    const bool in_grid = cx >= 0 && cx < G && cy >= 0 && cy < G;
+    cx = cx < 0 ? 0 : (cx > G - 1 ? G - 1 : cx);
+    cy = cy < 0 ? 0 : (cy > G - 1 ? G - 1 : cy);
+    const int xl = max(cx - 1, 0), xh = min(cx + 1, G - 1), yl = max(cy - 1, 0), yh = min(cy + 1, G - 1);
+    int a[R], b[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int iy = min(yl + r, G - 1);
+        a[r] = g.start_at(iy * G + xl);
+        b[r] = g.start_at(iy * G + xh + 1);
+        if (yl + r > yh) b[r] = a[r];
+    }
+    // (every read issued before the first is used; a slot beyond the end of its run reads what follows in LDS -- inside the
+    // block's LDS part: a run starts at or below m, and entry m + 4 lies in the padding or in the next plane -- and is masked)
+    float2 c[R * C];
+    float cz[R * C];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const float2 *run = reinterpret_cast<const float2 *>(bl_u32(g.xy)) + a[r];
+        const float *runz = reinterpret_cast<const float *>(bl_u32(z32)) + a[r];
+#pragma unroll
+        for (int j = 0; j < C; ++j) { c[C * r + j] = run[j]; cz[C * r + j] = runz[j]; }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    uint32_t lo = 0xFFFFFFFFu, hi = 0xFFFFFFFFu;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int j = 0; j < C; ++j) {
+            const float d2 = bl_dist3f(fx, fy, fz, c[C * r + j], cz[C * r + j]);
+            uint32_t key = (__float_as_uint(d2) & 0xFFFFFFF0u) | (uint32_t)(C * r + j);
+            key = a[r] + j < b[r] ? key : 0xFFFFFFFFu;
+            hi = bl_med3(lo, hi, key);
+            lo = min(lo, key);
+        }
+    int q_extra = 0;
+    bool more = false;
+#pragma unroll
+    for (int r = 0; r < R; ++r) more = more || (b[r] - a[r] > C);
+    if (more) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            for (int qq = a[r] + C; qq < b[r]; ++qq) {
+                const float d2 = bl_dist3f(fx, fy, fz, g.xy_at(qq), reinterpret_cast<const float *>(bl_u32(z32))[qq]);
+                const uint32_t key = (__float_as_uint(d2) & 0xFFFFFFF0u) | 15u;
+                q_extra = key < lo ? qq : q_extra;
+                hi = bl_med3(lo, hi, key);
+                lo = min(lo, key);
+            }
+    }
+    const float best = __uint_as_float(lo & 0xFFFFFFF0u), second = __uint_as_float(hi & 0xFFFFFFF0u);
+    const float band = bl3_band(best);
+    const int slot = (int)(lo & 15u);
+    const int run = slot >= 2 * C ? 2 : (slot >= C ? 1 : 0);
+    const int bq = slot == 15 ? q_extra : (run == 2 ? a[2] : (run == 1 ? a[1] : a[0])) + slot - C * run;
+    const bool found = lo != 0xFFFFFFFFu;
+    const double wz = z64[found ? bq : 0];               // (the winner's exact third coordinate: requested at once)
+    const float reach = 0.998f * g.cell;
+    bool inside = in_grid && band < reach * reach;
+    if (!inside) {
+        const float big = 3.0e38f;
+        float bound = big;
+        if (xl > 0) bound = fminf(bound, fx - (g.x0 + (float)xl * g.cell));
+        if (xh < G - 1) bound = fminf(bound, (g.x0 + (float)(xh + 1) * g.cell) - fx);
+        if (yl > 0) bound = fminf(bound, fy - (g.y0 + (float)yl * g.cell));
+        if (yh < G - 1) bound = fminf(bound, (g.y0 + (float)(yh + 1) * g.cell) - fy);
+        bound -= 1e-3f * g.cell;
+        inside = bound >= big * 0.5f || (bound > 0.f && bound * bound > band);
+    }
+    const float2 cw = g.xy_at(found ? bq : 0);
+    BlNear3 r;
+    r.s = bl_dist3(px, py, pz, cw, wz);
+    r.z = wz;
+    r.zx = cw.x; r.zy = cw.y;
+    r.col = g.item_at(found ? bq : 0);
+    r.done = found && inside && !(second <= band);
+    return r;
+}
+
+// bl_search_wave in three dimensions: ONE track by the whole wave over every detection of the frame.  The float pre-pass
+// (frames of at most 512 detections, and only where the band holds: `narrow`) reads the f32 plane in LDS; the exact passes
+// read the f64 plane in HBM, coalesced.  The same three passes and tie rule: the smallest s; the lowest column within 2^-48
+// of it; the rounded roots only if some s differs from the smallest.  px, py, pz, narrow, the result: wave-uniform.
+__device__ __forceinline__ BlNear3 bl_search_wave3(const BlGridView &g, int z32, const double *__restrict__ z64, double px, double py,
+                                                   double pz, int m, int lane, bool narrow)
+{
+    const double inf = __longlong_as_double(0x7FF0000000000000ll);
+    BlNear3 r;
+    r.done = true;
+    if (m <= 512 && narrow) {
+        const float fx = (float)px, fy = (float)py, fz = (float)pz;
+        float sf[8];
+        int lo = 0x7F800000;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int j = u * 64 + lane, jc = min(j, m - 1);
+            sf[u] = j < m ? bl_dist3f(fx, fy, fz, g.xy_at(jc), reinterpret_cast<const float *>(bl_u32(z32))[jc]) : 3.0e38f;
+            lo = min(lo, (int)__float_as_uint(sf[u]));
+        }
+        const float best = __uint_as_float((uint32_t)wave_min(lo));
+        const float band = bl3_band(best);
+        int n_near = 0, jn = 0;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const unsigned long long b = __ballot(sf[u] <= band);
+            n_near += (int)__popcll(b);
+            if (b) jn = u * 64 + __builtin_ctzll(b);
+        }
+        if (n_near == 1) {
+            const float2 c = g.xy_at(jn);
+            r.z = z64[jn];
+            r.s = bl_dist3(px, py, pz, c, r.z); r.zx = c.x; r.zy = c.y; r.col = g.item_at(jn);
+            return r;
+        }
+    }
+    double lane_min = inf;
+    for (int j0 = 0; j0 < m; j0 += 512) {
+        float2 c[8];
+        double cz[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { const int j = min(j0 + u * 64 + lane, m - 1); c[u] = g.xy_at(j); cz[u] = z64[j]; }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const double s = bl_dist3(px, py, pz, c[u], cz[u]);
+            lane_min = (j0 + u * 64 + lane < m) ? __builtin_fmin(lane_min, s) : lane_min;
+        }
+    }
+    const double s_min = wave_min(lane_min);
+    const double near_limit = s_min + s_min * 0x1p-48;
+    int cand = 0x7FFFFFFF;
+    bool inexact = false;
+    for (int j0 = 0; j0 < m; j0 += 512) {
+        float2 c[8];
+        double cz[8];
+        int it[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { const int j = min(j0 + u * 64 + lane, m - 1); c[u] = g.xy_at(j); it[u] = g.item_at(j); cz[u] = z64[j]; }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int j = j0 + u * 64 + lane;
+            const double s = bl_dist3(px, py, pz, c[u], cz[u]);
+            const bool near = j < m && s <= near_limit;
+            cand = near ? min(cand, (it[u] << 15) | j) : cand;
+            inexact = inexact || (near && s != s_min);
+        }
+    }
+    if (__any(inexact)) {
+        const double d_min = sqrt(s_min);
+        cand = 0x7FFFFFFF;
+        for (int j = lane; j < m; j += 64) {
+            const double s = bl_dist3(px, py, pz, g.xy_at(j), z64[j]);
+            if (s <= near_limit && sqrt(s) == d_min) cand = min(cand, (g.item_at(j) << 15) | j);
+        }
+    }
+    const int win = wave_min(cand);
+    const float2 c = g.xy_at(win & 0x7FFF);
+    r.z = z64[win & 0x7FFF];
+    r.s = s_min; r.zx = c.x; r.zy = c.y; r.col = win >> 15;
+    return r;
+}
+
+struct BlKernArgs3 {
+    TrackerDev t;
+    BatchDev bd;                  // grid / grid_stride: the 3-D blocks
+    const float *det_all;
+    const double *third_all;      // [batch][max_det]: read at a frame's columns below its count only
+    const int32_t *det_count;
+    int batch, frame0;
+    ysmr_row *rows;
+    long long rows_capacity;
+    long long *row_count;
+    double *seat3;                // [seat_cap] the third coordinate at rest
+};
+typedef const __attribute__((address_space(4))) BlKernArgs3 *BlKernArgs3Ptr;
+__device__ __forceinline__ BlKernArgs3Ptr bl_kernargs3()
+{
+    BlKernArgs3Ptr p = (BlKernArgs3Ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+
+__global__ __launch_bounds__(BL_THREADS) void k_batch3(BlKernArgs3 ka)
+{
+    const TrackerDev &t = ka.t;
+    const BatchDev &bd = ka.bd;
+    const int32_t *__restrict__ det_count = ka.det_count;
+    const int batch = ka.batch;
+    long long *row_count = ka.row_count;
+    __shared__ BlShared sh;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int md = t.max_det, mdp = bl_md_padded(md);
+    int bufw = bl3_lds_dwords_max(md);
+    // LDS by offset, laid out as k_batch's: three key tables, the id table, two grid blocks (their LDS part), the set model
+    auto key_at = [&](int k) { return bl_lds + k * mdp; };
+    auto cid_at = [&]() { return bl_u32(6 * mdp); };
+    auto buf_off = [&](int p) { return 7 * mdp + p * bufw; };
+    auto tab_off = [&]() { return 7 * mdp + 2 * bufw; };
+    const int seats = min(t.capacity, BL_THREADS);
+    const int gone_max = (int)floor(t.max_gone);
+
+    // ---- start of the batch
+    int n = *t.n_tracks, next_id = *t.next_id;
+    long long base = *row_count;
+    for (int f = tid; f < batch; f += BL_THREADS) {
+        int m = det_count[f];
+        if (m > md) { m = md; atomicOr(t.err, ERR_DET_CLAMPED); }
+        sh.cnt[f] = m < 0 ? 0 : m;
+    }
+    if (tid < 2) { sh.used[tid] = 0; sh.n_dead[tid] = 0; sh.tie[tid] = -1; }
+    if (tid == 0) sh.top = 0;
+    Bl3Seat S;
+    S.px = S.py = S.pz = 0.0;
+    S.info[0] = S.info[1] = S.info[2] = 0.f;
+    S.id = S.gone = S.rank = 0;
+    S.alive = false;
+    {
+        const size_t sc = (size_t)bd.seat_cap;
+        if (n > 0 && tid < seats && bd.i32[5 * sc + tid]) {
+            S.px = bd.f64[sc * (3 * BL_NF) + tid]; S.py = bd.f64[sc * (3 * BL_NF + 1) + tid]; S.pz = ka.seat3[tid];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) S.info[k] = bd.f32[sc * k + tid];
+            S.id = bd.i32[tid]; S.gone = bd.i32[sc + tid]; S.rank = bd.i32[4 * sc + tid];
+            S.alive = true;
+        }
+    }
+    __syncthreads();
+    {
+        const unsigned long long ba = __ballot(S.alive);
+        if (lane == 0 && ba) atomicMax(&sh.top, 64 * (wave + 1));
+    }
+    __syncthreads();
+    int helpers_from = (sh.top + 63) >> 6;
+    auto chore_first = [&]() { return helpers_from < BL_WAVES ? tid - 64 * helpers_from : tid; };
+    auto chore_stride = [&]() { return helpers_from < BL_WAVES ? 64 * (BL_WAVES - helpers_from) : BL_THREADS; };
+    auto dma = [&](int f) {        // the LDS part of frame f's block -> buffer f & 1, whole 1-KiB pieces
+        const int pieces = bl3_lds_dwords(sh.cnt[f]) >> 8;
+        const BlKernArgs3Ptr kd = bl_kernargs3();
+        const char *src = kd->bd.grid + (size_t)kd->bd.grid_stride * f;
+        const int w0 = helpers_from < BL_WAVES ? helpers_from : 0, nw = BL_WAVES - w0;
+        for (int c = wave - w0; c >= 0 && c < pieces; c += nw) {
+            const uint32_t lds = (uint32_t)(uintptr_t)(bl_u32(buf_off(f & 1) + c * 256));
+            const uint32_t off = (uint32_t)c * 1024u + (uint32_t)lane * 16u;
+            asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(__builtin_amdgcn_readfirstlane(lds)), "v"(off), "s"(src) : "memory");
+        }
+    };
+#pragma nounroll
+    for (int k = 0; k < 2 && k < batch; ++k) dma(k);
+    for (int c = tid; c < sh.cnt[0]; c += BL_THREADS) key_at(0)[c] = ~0ull;
+    if (batch > 1)
+        for (int c = tid; c < sh.cnt[1]; c += BL_THREADS) key_at(1)[c] = ~0ull;
+    bl_wait_vmem();
+    __syncthreads();
+
+    // ---- the frame loop: k_batch's, one barrier A per frame (what orders what: above k_batch's loop)
+    int kc = 0;
+    int d_cur = 0, d_prev = 0;
+    double o0 = 0.0, o1 = 0.0;
+    auto settle = [&](int slot, int start, int fr, bool row) {
+        const int total = sh.n_dead[slot];
+        const int n_dead = total - start;
+        if (n_dead && S.alive)
+            for (int k = 0; k < n_dead; ++k) S.rank -= sh.dead_id[slot][k] < S.id;
+        n -= n_dead;
+        if (row) {
+            const BlKernArgs3Ptr kr = bl_kernargs3();
+            ysmr_row *rows = kr->rows;
+            const long long rows_capacity = kr->rows_capacity;
+            if (S.alive && base + S.rank < rows_capacity) {
+                ysmr_row rr;
+                rr.frame = kr->frame0 + fr;
+                rr.track_id = S.id;
+                rr.x = o0; rr.y = o1;
+                rr.w = S.info[0]; rr.h = S.info[1]; rr.angle = S.info[2];
+                rr.disappeared = S.gone;
+                rows[base + S.rank] = rr;
+            }
+            if (tid == 0 && base + n > rows_capacity) atomicOr(kr->t.err, ERR_ROWS_CAPACITY);
+            base += n;
+        }
+        return total;
+    };
+    for (int f = 0; f < batch; ++f) {
+        const int par = f & 1;
+        const int kn = kc == 2 ? 0 : kc + 1, ks = kc == 0 ? 2 : kc - 1;
+        const int m = sh.cnt[f];
+        // (the sizes every LDS offset derives from, as values of this frame: left to itself the compiler works out each
+        // table's and buffer's address once in front of the loop, holds a scalar register for every one of them through the
+        // launch and spills a dozen into vector lanes; worked out again where they are used they cost a scalar add or two)
+        asm volatile("" : "+s"(md), "+s"(mdp), "+s"(bufw));
+        // ---- each track proposes its nearest detection in (x, y, third)
+        const bool propose = S.alive && m > 0;
+        const BlGridView gv = bl_grid_view(buf_off(par), m);
+        const int z32 = buf_off(par) + bl_list_off(m);
+        const bool wide = bl_u32(buf_off(par))[7] != 0u;          // some |third| of the frame >= 4096: no float stage
+        // (the blocks' address and stride: read from the argument segment here, they hold no scalar register across the frame)
+        const double *z64 = reinterpret_cast<const double *>(bl_kernargs3()->bd.grid + (size_t)bl_kernargs3()->bd.grid_stride * f + 4 * (size_t)bufw);
+        const bool narrow = !wide && __builtin_fabs(S.pz) < 4096.0;
+        BlNear3 nr{0.0, 0.0, 0.f, 0.f, 0, true};
+        unsigned long long key = 0;
+        if (propose) {
+            if (narrow) nr = bl_search_block3(gv, z32, z64, S.px, S.py, S.pz, m);
+            else nr.done = false;
+        }
+        {
+            unsigned long long todo = __ballot(propose && !nr.done);
+#ifdef YSMR_STAMPS
+            if (lane == 0) { if (f == 0) { g_bstamps[wave][13] = 0; g_bstamps[wave][14] = 0; } g_bstamps[wave][13] += __popcll(todo); g_bstamps[wave][14] += todo ? 1 : 0; }
+#endif
+            while (todo) {
+                const int l = __builtin_ctzll(todo);
+                todo &= todo - 1ull;
+                const bool nw = __builtin_amdgcn_readlane((int)narrow, l) != 0;
+                const BlNear3 w = bl_search_wave3(gv, z32, z64, lane_value(S.px, l), lane_value(S.py, l), lane_value(S.pz, l), m, lane, nw);
+                if (lane == l) nr = w;
+            }
+        }
+        float bx[3] = {0.f, 0.f, 0.f};
+        if (propose) {
+            const float *d = bl_kernargs3()->det_all + ((size_t)f * md + nr.col) * 5;
+            bx[0] = d[2]; bx[1] = d[3]; bx[2] = d[4];
+        }
+        // ---- claims: k_batch's key (the squared distance without its ten lowest bits | table row) and flag
+        if (propose) {
+            key = ((unsigned long long)__double_as_longlong(nr.s) & ~0x3FFull) | (unsigned long long)S.rank;
+            const unsigned long long before = atomicMin(&key_at(kc)[nr.col], key);
+            if ((before >> 10) - (key >> 10) + 1ull <= 2ull) sh.tie[par] = f;
+        }
+        if (helpers_from >= BL_WAVES || wave >= helpers_from) bl_wait_vmem();
+        block_sync<true>();
+        // ---- behind barrier A
+        if (tid == BL_THREADS - 1) sh.used[par ^ 1] = 0;
+        if (f + 2 < batch) dma(f + 2);
+        const unsigned long long k_won = key_at(kc)[nr.col];
+        const int exact = sh.tie[par] == f;
+        const int d_total = settle(par ^ 1, d_prev, f - 1, f > 0);
+        bool mine = propose && k_won == key;
+        if (exact) {
+            for (int c = tid; c < m; c += BL_THREADS) { key_at(kc)[c] = ~0ull; cid_at()[c] = 0xFFFFFFFFu; }
+            block_sync<true>();
+            if (propose) {
+                key = (unsigned long long)__double_as_longlong(nr.s);
+                atomicMin(&key_at(kc)[nr.col], key);
+            }
+            block_sync<true>();
+            if (propose) {
+                const unsigned long long kmin = key_at(kc)[nr.col];
+                bool tie = key == kmin;
+                if (!tie) {
+                    const double smin = __longlong_as_double((long long)kmin);
+                    if (nr.s <= smin + smin * 0x1p-48) tie = sqrt(nr.s) == sqrt(smin);
+                }
+                if (tie) atomicMin(&cid_at()[nr.col], (uint32_t)S.id);
+            }
+            block_sync<true>();
+            mine = propose && cid_at()[nr.col] == (uint32_t)S.id;
+        }
+        // ---- ageing and deregistration
+        const bool age = (m == 0) || (n > 0 && n >= m);
+        double z0 = S.px, z1 = S.py, z2 = S.pz;
+        bool died = false;
+        if (mine) {
+            z0 = (double)nr.zx; z1 = (double)nr.zy; z2 = nr.z;
+            S.gone = 0;
+        } else if (S.alive && age) {
+            ++S.gone;
+            S.info[0] = S.info[1] = S.info[2] = 0.f;
+            if (S.gone > gone_max) { S.alive = false; died = true; }
+        }
+        {
+            const unsigned long long bm = __ballot(mine), bxd = __ballot(died);
+            if (lane == 0 && bm) atomicAdd(&sh.used[par], (int)__popcll(bm));
+            if (bxd) {
+                int at = 0;
+                if (lane == 0) at = atomicAdd(&sh.n_dead[par], (int)__popcll(bxd));
+                at = __builtin_amdgcn_readfirstlane(at) - d_cur;
+                if (died) sh.dead_id[par][at + __popcll(bxd & below)] = S.id;
+            }
+        }
+        // ---- registration: unclaimed columns become tracks, in CPython set order
+        const bool births = m > 0 && (n == 0 || n < m);
+        if (births) {
+            int tl = tid, wv = wave, ln = lane, mp = mdp;
+            asm volatile("" : "+v"(tl), "+s"(wv), "+v"(ln));
+            int *unused = reinterpret_cast<int *>(key_at(ks)), *newcols = unused + mp;
+            uint32_t *list = cid_at();
+            __syncthreads();
+            int n_new = 0, n_new_all = 0;
+            if (n == 0) {
+                for (int c = tl; c < m; c += BL_THREADS) newcols[c] = c;
+                n_new_all = m;
+            } else {
+                const int K = (m + BL_THREADS - 1) / BL_THREADS;
+                const int c0 = tl * K, c1 = min(c0 + K, m);
+                int cnt = 0;
+                for (int c = c0; c < c1; ++c) cnt += key_at(kc)[c] == ~0ull;
+                int incl = cnt;
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (ln >= d) incl += o; }
+                if (ln == 63) sh.wave_cnt[0][wv] = incl;
+                __syncthreads();
+                int at = incl - cnt, total = 0;
+#pragma unroll
+                for (int k = 0; k < BL_WAVES; ++k) { const int v = sh.wave_cnt[0][k]; at += k < wv ? v : 0; total += v; }
+                for (int c = c0; c < c1; ++c)
+                    if (key_at(kc)[c] == ~0ull) unused[at++] = c;
+                __syncthreads();
+                int cnt_set = cpython_order_lds<BL_THREADS, BL_TABLE>(unused, total, m, sh.used[par], newcols, bl_u32(tab_off()), list, sh.set_state);
+                if (cnt_set < 0) { if (tl == 0) atomicOr(bl_kernargs3()->t.err, ERR_TRACK_CAPACITY); cnt_set = 0; }
+                n_new_all = cnt_set;
+            }
+            n_new = n_new_all;
+            const int seats = min(bl_kernargs3()->t.capacity, BL_THREADS);
+            if (n + n_new > seats) {
+                if (tl == 0) atomicOr(bl_kernargs3()->t.err, ERR_TRACK_CAPACITY);
+                n_new = seats - n;
+            }
+            const bool free_lane = !S.alive && tl < seats;
+            const unsigned long long bf = __ballot(free_lane);
+            if (ln == 0) sh.wave_cnt[1][wv] = (int)__popcll(bf);
+            __syncthreads();
+            int fr = (int)__popcll(bf & below);
+#pragma unroll
+            for (int k = 0; k < BL_WAVES; ++k) fr += k < wv ? sh.wave_cnt[1][k] : 0;
+            if (free_lane && fr < n_new) {
+                const int c = newcols[fr];
+                const BlKernArgs3Ptr kb = bl_kernargs3();
+                const float *d = kb->det_all + ((size_t)f * md + c) * 5;
+                z0 = (double)d[0]; z1 = (double)d[1];
+                z2 = kb->third_all[(size_t)f * md + c];        // (c < m: a slot at or beyond the count is never read)
+                S.info[0] = d[2]; S.info[1] = d[3]; S.info[2] = d[4];
+                S.id = next_id + fr; S.rank = n + fr; S.gone = 0;
+                S.alive = true;
+                atomicMax(&sh.top, tl + 1);
+            }
+            n += n_new;
+            next_id += n_new_all;
+            bl_wait_vmem();
+            __syncthreads();
+            helpers_from = (sh.top + 63) >> 6;
+        }
+        {
+            const int m_ahead = f + 2 < batch ? sh.cnt[f + 2] : 0;
+            for (int c = chore_first(); c >= 0 && c < m_ahead; c += chore_stride()) key_at(ks)[c] = ~0ull;
+        }
+        // ---- the point the track keeps (tracker.py:181, 228-230: the claimed detection, or where it was)
+        bl_wait_vmem();
+        if (mine) { S.info[0] = bx[0]; S.info[1] = bx[1]; S.info[2] = bx[2]; }
+        o0 = z0; o1 = z1;
+        if (S.alive) { S.px = z0; S.py = z1; S.pz = z2; }
+        d_prev = d_cur; d_cur = d_total;
+        kc = kn;
+    }
+    block_sync<true>();
+    settle((batch - 1) & 1, d_prev, batch - 1, true);
+    // ---- end of the batch: the state goes back to HBM, seat by seat
+    {
+        const BlKernArgs3Ptr ke = bl_kernargs3();
+        const size_t sc = (size_t)ke->bd.seat_cap;
+        double *f64 = ke->bd.f64;
+        float *f32 = ke->bd.f32;
+        int *i32 = ke->bd.i32;
+        if (tid < min(ke->t.capacity, BL_THREADS)) {      // (from the argument segment: no lane mask kept since the first frame)
+            i32[5 * sc + tid] = S.alive ? 1 : 0;
+            if (S.alive) {
+                f64[sc * (3 * BL_NF) + tid] = S.px; f64[sc * (3 * BL_NF + 1) + tid] = S.py; ke->seat3[tid] = S.pz;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) f32[sc * k + tid] = S.info[k];
+                i32[tid] = S.id; i32[sc + tid] = S.gone; i32[2 * sc + tid] = 0; i32[3 * sc + tid] = 0; i32[4 * sc + tid] = S.rank;
+            }
+        }
+        if (tid == 0) { *ke->t.n_tracks = n; *ke->t.next_id = next_id; *ke->row_count = base; }
+    }
 }

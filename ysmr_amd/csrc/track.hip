@@ -136,12 +136,13 @@ struct ysmr_tracker {
     BatchDev bd;
     bool batchable = false;        // configuration served by k_batch (three filters of <= 31 frames, <= 1024 tracks, ...)
     bool in_batch = false;         // the state rests in the seat-major arrays of `bd` (else: the per-slot layout)
-    int link_mode = 0;             // ysmr_tracker_link_mode: 0 = the library's choice, 1 = one (or two) launches per frame
+    int link_mode = 0;             // ysmr_tracker_link_mode: 0 = the library's choice, 1 = one (or two) launches per frame,
+                                   // 2 = as 0, and a 3-D handle that can also links a batch with one launch (k_batch3)
     size_t batch_lds = 0;
     BlGains bgains;
     const BlGains *bgains_dev = nullptr;     // the same in device memory (behind the grid blocks): k_batch reads it frame by frame
     // ysmr_tracker_prepare: which batch each of the two caller-named grid blocks was binned for (block 2 is run's own)
-    struct Prepared { const void *det = nullptr; const void *count = nullptr; int batch = 0; } prepared[2];
+    struct Prepared { const void *det = nullptr; const void *count = nullptr; const void *third = nullptr; int batch = 0; } prepared[2];
     // split link with a track per lane (batch_link.h: k_track_lanes): the filter state of a non-fused handle lives seat-major by
     // slot in `bd` from the start; the ring's head is kept here (every live track appends one measurement per frame)
     bool lanes = false;
@@ -153,7 +154,16 @@ struct ysmr_tracker {
     bool batchable_2d = false, lanes_2d = false;
     bool linked = false;           // a frame has been linked since creation / the last reset: the dimension is fixed
     double *pos3 = nullptr;        // [capacity] third coordinate of the track in a slot
-    bool use_batch() const { return batchable && link_mode == 0; }
+    // the batch link of a 3-D handle (batch_link.h: k_bgrid3 + k_batch3), on request only (link mode 2): its grid blocks -- a
+    // larger stride than the 2-D ones, for the third coordinate's two planes -- and the seat-major third coordinate are
+    // allocated when the mode is first selected on a 3-D handle, so a 2-D handle's footprint is what it was
+    bool batchable3 = false;       // set up and served by k_batch3
+    bool tried3 = false;           // ... or found not to be (asked once)
+    void *grid3_block = nullptr;   // [3][BL_MAX_BATCH][grid3_stride] bytes, then seat3 f64 [seat_cap]
+    unsigned grid3_stride = 0;
+    double *seat3 = nullptr;
+    size_t batch3_lds = 0;
+    bool use_batch() const { return dims == 3 ? (batchable3 && link_mode == 2) : (batchable && link_mode != 1); }
     DetGrid grid(int f) const
     {
         char *b = (char *)grid_block;
@@ -2376,6 +2386,39 @@ int ysmr_tracker_create(double max_disappeared, double fps, int n_min, double n_
     return ysmr_tracker_reset(t, nullptr);
 }
 
+// The 3-D batch link of a handle, set up the first time link mode 2 meets three dimensions: "batchable in 3-D" is fused,
+// at most BL_THREADS tracks, and k_batch3's LDS within a compute unit's for the handle's max_det (capacity 768 with
+// max_det 2048, the pipeline's shape, is).  A handle that is not keeps the per-frame link, silently, as 2-D handles do.
+static int setup_batch3(ysmr_tracker *t)
+{
+    if (t->tried3) return YSMR_OK;
+    // (tried3 is set on a definite answer only -- the shape does not qualify, the device refuses the LDS, or everything is
+    // in place: after a failed allocation the next call tries again)
+    const int max_det = t->d.max_det;
+    if (!t->fused || t->d.use_gsff || t->d.capacity > BL_THREADS || bl3_lds_total(max_det) > BL_LDS_LIMIT) {
+        t->tried3 = true;
+        return YSMR_OK;
+    }
+    t->batch3_lds = bl3_lds_bytes(max_det);
+    if (hipFuncSetAttribute((const void *)k_batch3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->batch3_lds) != hipSuccess) {
+        (void)hipGetLastError();
+        t->tried3 = true;
+        return YSMR_OK;
+    }
+    const size_t per = bl3_grid_stride(max_det), grids = per * BL_MAX_BATCH * 3;
+    hipError_t e = hipMalloc(&t->grid3_block, grids + sizeof(double) * (size_t)t->bd.seat_cap);
+    if (e != hipSuccess) {
+        t->grid3_block = nullptr;
+        (void)hipGetLastError();
+        return ysmr::fail(YSMR_ERR_HIP, "hipMalloc(%zu) failed: %s", grids, hipGetErrorString(e));
+    }
+    t->tried3 = true;
+    t->grid3_stride = (unsigned)per;
+    t->seat3 = reinterpret_cast<double *>((char *)t->grid3_block + grids);
+    t->batchable3 = true;
+    return YSMR_OK;
+}
+
 int ysmr_tracker_dimensions(ysmr_tracker *t, int dimensions)
 {
     if (!t) return ysmr::fail(YSMR_ERR_ARG, "tracker handle is NULL");
@@ -2389,6 +2432,8 @@ int ysmr_tracker_dimensions(ysmr_tracker *t, int dimensions)
         const void *variants[2] = {(const void *)k_frame<float, 3, true>, (const void *)k_frame<double, 3, true>};
         for (const void *fn : variants) YSMR_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->frame_lds));
     }
+    if (dimensions == 3 && t->link_mode == 2)      // (in front of every change to the handle: a failure leaves it as it was)
+        if (int rc = setup_batch3(t)) return rc;
     t->dims = dimensions;
     t->batchable = dimensions == 2 && t->batchable_2d;
     t->lanes = dimensions == 2 && t->lanes_2d;
@@ -2420,6 +2465,7 @@ int ysmr_tracker_destroy(ysmr_tracker *t)
     if (!t) return YSMR_OK;
     hipError_t e = hipFree(t->block);
     if (t->grid_block) (void)hipFree(t->grid_block);
+    if (t->grid3_block) (void)hipFree(t->grid3_block);
     delete t;
     if (e != hipSuccess) return ysmr::fail(YSMR_ERR_HIP, "hipFree failed: %s", hipGetErrorString(e));
     return YSMR_OK;
@@ -2433,7 +2479,8 @@ static int state_to_std(ysmr_tracker *t, hipStream_t st)
     // later batch run must not take the old binning for the new contents
     t->prepared[0] = t->prepared[1] = ysmr_tracker::Prepared();
     if (!t->in_batch) return YSMR_OK;
-    hipLaunchKernelGGL(k_to_std, dim3((std::max(t->d.capacity, t->bd.seat_cap) + 255) / 256), dim3(256), 0, st, t->d, t->bd);
+    hipLaunchKernelGGL(k_to_std, dim3((std::max(t->d.capacity, t->bd.seat_cap) + 255) / 256), dim3(256), 0, st, t->d, t->bd,
+                       t->dims == 3 ? t->pos3 : nullptr, t->dims == 3 ? t->seat3 : nullptr);
     YSMR_LAUNCH_CHECK();
     t->in_batch = false;
     t->par = 0;
@@ -2443,7 +2490,8 @@ static int state_to_std(ysmr_tracker *t, hipStream_t st)
 static int state_to_batch(ysmr_tracker *t, hipStream_t st)
 {
     if (t->in_batch) return YSMR_OK;
-    hipLaunchKernelGGL(k_to_batch, dim3((t->bd.seat_cap + 255) / 256), dim3(256), 0, st, t->cur(), t->bd);
+    hipLaunchKernelGGL(k_to_batch, dim3((t->bd.seat_cap + 255) / 256), dim3(256), 0, st, t->cur(), t->bd,
+                       t->dims == 3 ? t->pos3 : nullptr, t->dims == 3 ? t->seat3 : nullptr);
     YSMR_LAUNCH_CHECK();
     if (t->par) {      // the counters live in the parity-0 words from here on
         YSMR_HIP_CHECK(hipMemcpyAsync(t->d.n_tracks, t->d1.n_tracks, sizeof(int) * 2, hipMemcpyDeviceToDevice, st));
@@ -2457,8 +2505,12 @@ static int state_to_batch(ysmr_tracker *t, hipStream_t st)
 int ysmr_tracker_link_mode(ysmr_tracker *t, int mode)
 {
     if (!t) return ysmr::fail(YSMR_ERR_ARG, "tracker handle is NULL");
-    if (mode != 0 && mode != 1) return ysmr::fail(YSMR_ERR_ARG, "link mode must be 0 (the library's choice) or 1 (per-frame launches)");
+    if (mode < 0 || mode > 2)
+        return ysmr::fail(YSMR_ERR_ARG, "link mode must be 0 (the library's choice), 1 (per-frame launches) or 2 (as 0, and the batch "
+                                        "launch for a 3-D handle as well)");
     if (t->link_mode != mode) t->prepared[0] = t->prepared[1] = ysmr_tracker::Prepared();
+    if (mode == 2 && t->dims == 3)
+        if (int rc = setup_batch3(t)) return rc;
     t->link_mode = mode;       // (the state changes its layout at the next call that needs the other one)
     return YSMR_OK;
 }
@@ -2475,11 +2527,29 @@ int ysmr_tracker_prepare(ysmr_tracker *t, void *stream, const float *det_dev, co
     if (!t) return ysmr::fail(YSMR_ERR_ARG, "tracker handle is NULL");
     if (!det_dev || !det_count_dev || batch <= 0 || slot < 0 || slot > 1)
         return ysmr::fail(YSMR_ERR_ARG, "det_dev, det_count_dev must be set, batch > 0, slot 0 or 1");
-    if (!t->use_batch() || batch > BL_MAX_BATCH) return YSMR_OK;       // (nothing to prepare: ysmr_tracker_run does it all)
+    // (a 3-D handle: a no-op, as it has always been -- its binning takes the third coordinate, ysmr_tracker_prepare3)
+    if (t->dims != 2 || !t->use_batch() || batch > BL_MAX_BATCH) return YSMR_OK;       // (nothing to prepare: ysmr_tracker_run does it all)
     hipLaunchKernelGGL(k_bgrid, dim3(batch), dim3(BG_THREADS), t->bd.grid_stride, (hipStream_t)stream, det_dev, det_count_dev,
                        t->d.max_det, t->bd.grid + (size_t)slot * BL_MAX_BATCH * t->bd.grid_stride, t->bd.grid_stride);
     YSMR_LAUNCH_CHECK();
     t->prepared[slot].det = det_dev; t->prepared[slot].count = det_count_dev; t->prepared[slot].batch = batch;
+    return YSMR_OK;
+}
+
+int ysmr_tracker_prepare3(ysmr_tracker *t, void *stream, const float *det_dev, const double *third_dev, const int32_t *det_count_dev,
+                          int batch, int slot)
+{
+    if (!t) return ysmr::fail(YSMR_ERR_ARG, "tracker handle is NULL");
+    if (!det_dev || !third_dev || !det_count_dev || batch <= 0 || slot < 0 || slot > 1)
+        return ysmr::fail(YSMR_ERR_ARG, "det_dev, third_dev, det_count_dev must be set, batch > 0, slot 0 or 1");
+    if (t->dims != 3) return ysmr::fail(YSMR_ERR_STATE, "ysmr_tracker_prepare3 needs a 3-D handle (ysmr_tracker_dimensions)");
+    if (!t->use_batch() || batch > BL_MAX_BATCH) return YSMR_OK;       // (nothing to prepare: ysmr_tracker_run3 does it all)
+    hipLaunchKernelGGL(k_bgrid3, dim3(batch), dim3(BG_THREADS), 4 * (size_t)bl3_lds_dwords_max(t->d.max_det), (hipStream_t)stream, det_dev,
+                       third_dev, det_count_dev, t->d.max_det, (char *)t->grid3_block + (size_t)slot * BL_MAX_BATCH * t->grid3_stride,
+                       t->grid3_stride);
+    YSMR_LAUNCH_CHECK();
+    t->prepared[slot].det = det_dev; t->prepared[slot].third = third_dev; t->prepared[slot].count = det_count_dev;
+    t->prepared[slot].batch = batch;
     return YSMR_OK;
 }
 
@@ -2597,6 +2667,7 @@ int ysmr_tracker_update3(ysmr_tracker *t, void *stream, const void *det_dev, int
     if (m > t->d.max_det) return ysmr::fail(YSMR_ERR_CAPACITY, "m = %d exceeds max_det = %d", m, t->d.max_det);
     if ((!det_dev || !third_dev) && m != 0) return ysmr::fail(YSMR_ERR_ARG, "det_dev / third_dev is NULL");
     if (t->dims != 3) return ysmr::fail(YSMR_ERR_STATE, "ysmr_tracker_update3 needs a 3-D handle (ysmr_tracker_dimensions)");
+    if (int rc = state_to_std(t, (hipStream_t)stream)) return rc;     // (one frame at a time: the per-frame kernels)
     t->rowmin_for = nullptr;
     if (t->fused) { t->set_base = true; t->base_ptr = nullptr; }
     const DetGrid no_grid{nullptr, nullptr, nullptr, nullptr};
@@ -2616,6 +2687,40 @@ int ysmr_tracker_run3(ysmr_tracker *t, void *stream, const float *det_dev, const
     if (!det_dev || !third_dev || !det_count_dev || !rows_dev || !row_count_dev || batch <= 0)
         return ysmr::fail(YSMR_ERR_ARG, "det_dev, third_dev, det_count_dev, rows_dev, row_count_dev must be set and batch > 0");
     if (t->dims != 3) return ysmr::fail(YSMR_ERR_STATE, "ysmr_tracker_run3 needs a 3-D handle (ysmr_tracker_dimensions)");
+    if (t->use_batch()) {
+        // link mode 2 on a handle k_batch3 serves: one launch per BL_MAX_BATCH frames, as ysmr_tracker_run's batch path
+        t->linked = true;
+        if (int rc = state_to_batch(t, (hipStream_t)stream)) return rc;
+        const size_t md = (size_t)t->d.max_det;
+        for (int f0 = 0; f0 < batch; f0 += BL_MAX_BATCH) {
+            const int nb = batch - f0 < BL_MAX_BATCH ? batch - f0 : BL_MAX_BATCH;
+            const float *det = det_dev + (size_t)f0 * md * 5;
+            const double *third = third_dev + (size_t)f0 * md;
+            int block = 2;
+            for (int s = 0; s < 2; ++s)
+                if (f0 == 0 && batch <= BL_MAX_BATCH && t->prepared[s].det == (const void *)det_dev &&
+                    t->prepared[s].third == (const void *)third_dev && t->prepared[s].count == (const void *)det_count_dev &&
+                    t->prepared[s].batch == batch) {
+                    block = s;
+                    t->prepared[s] = ysmr_tracker::Prepared();       // (good for one call)
+                }
+            BlKernArgs3 ka;
+            ka.t = t->d; ka.bd = t->bd;
+            ka.bd.grid = (char *)t->grid3_block + (size_t)block * BL_MAX_BATCH * t->grid3_stride;
+            ka.bd.grid_stride = t->grid3_stride;
+            if (block == 2)
+                hipLaunchKernelGGL(k_bgrid3, dim3(nb), dim3(BG_THREADS), 4 * (size_t)bl3_lds_dwords_max(t->d.max_det), (hipStream_t)stream,
+                                   det, third, det_count_dev + f0, t->d.max_det, ka.bd.grid, ka.bd.grid_stride);
+            ka.det_all = det; ka.third_all = third; ka.det_count = det_count_dev + f0; ka.batch = nb;
+            ka.frame0 = first_frame_index + f0; ka.rows = rows_dev; ka.rows_capacity = (long long)rows_capacity;
+            ka.row_count = (long long *)row_count_dev; ka.seat3 = t->seat3;
+            if (BL_PAUSE_TICKS > 0) hipLaunchKernelGGL(k_pause, dim3(1), dim3(64), 0, (hipStream_t)stream, BL_PAUSE_TICKS);
+            hipLaunchKernelGGL(k_batch3, dim3(1), dim3(BL_THREADS), t->batch3_lds, (hipStream_t)stream, ka);
+            YSMR_LAUNCH_CHECK();
+        }
+        return YSMR_OK;
+    }
+    if (int rc = state_to_std(t, (hipStream_t)stream)) return rc;
     t->rowmin_for = nullptr;
     if (t->fused) { t->set_base = true; t->base_ptr = (const long long *)row_count_dev; }
     const DetGrid no_grid{nullptr, nullptr, nullptr, nullptr};
@@ -2654,9 +2759,13 @@ int ysmr_tracker_peek3(ysmr_tracker *t, void *stream, int32_t *ids_dev, double *
     if (!t) return ysmr::fail(YSMR_ERR_ARG, "tracker handle is NULL");
     if (t->dims != 3) return ysmr::fail(YSMR_ERR_STATE, "ysmr_tracker_peek3 needs a 3-D handle (ysmr_tracker_dimensions)");
     if (int rc = ysmr_tracker_peek(t, stream, ids_dev, xy_dev, disappeared_dev, n_dev)) return rc;
-    if (third_dev) {
-        hipLaunchKernelGGL(k_peek_third, dim3((t->d.capacity + 255) / 256), dim3(256), 0, (hipStream_t)stream, t->cur(), t->pos3,
-                           third_dev);
+    if (third_dev) {      // (from whichever layout holds the state)
+        if (t->in_batch)
+            hipLaunchKernelGGL(k_peek_third_batch, dim3((t->bd.seat_cap + 255) / 256), dim3(256), 0, (hipStream_t)stream, t->d, t->bd,
+                               t->seat3, third_dev);
+        else
+            hipLaunchKernelGGL(k_peek_third, dim3((t->d.capacity + 255) / 256), dim3(256), 0, (hipStream_t)stream, t->cur(), t->pos3,
+                               third_dev);
         YSMR_LAUNCH_CHECK();
     }
     return YSMR_OK;

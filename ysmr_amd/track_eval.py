@@ -12,8 +12,9 @@ The loop body (track_eval.py:156-366) is replaced by batched device work:
 Detection of batch b+1 is issued on a second HIP stream while batch b is being linked.
 
 'include luminosity in tracking calculation' (track_eval.py:290-300; with 'disable gsff' = True, the combination upstream
-runs): ``ysmr_luminosity_batch`` follows the detection on that stream and the link is ``ysmr_tracker_run3``, one launch
-per frame, with the mean gray value under each detection's box as a third coordinate.
+runs): ``ysmr_luminosity_batch`` follows the detection on that stream and the link is ``ysmr_tracker_run3`` in link mode
+2 -- one launch per batch (k_batch3) for the default shapes, one per frame otherwise -- with the mean gray value under each
+detection's box as a third coordinate.
 """
 from __future__ import annotations
 
@@ -112,15 +113,17 @@ class TrackingPipeline:
         # at 4K 14.8 k against 15.2 k).  Detection without a link has no neighbour and takes the matrix-pipe kernel.
         # 'include luminosity in tracking calculation' (track_eval.py:290-300): every detection's mean gray value / 100 is a
         # third tracking coordinate.  Upstream offers it with 'disable gsff' only (with the filter bank its tracker raises in
-        # the first update), so the tracker is built in three dimensions -- which links frame by frame, never with the batch
-        # launch -- and both detectors also run the luminosity kernel
+        # the first update), so the tracker is built in three dimensions, in link mode 2 -- a 3-D handle of a shape the 3-D
+        # batch launch serves (k_batch3: capacity <= 768, max_det about 2048) then links a batch with one launch like a 2-D
+        # one, every other 3-D handle frame by frame -- and both detectors also run the luminosity kernel
         self.luminosity = bool(settings.get("include luminosity in tracking calculation", False))
         if self.luminosity and not settings["disable gsff"]:
             raise ValueError("'include luminosity in tracking calculation' needs 'disable gsff' = True")
         self.trk = DeviceTracker(max_disappeared=fps, fps=fps, n_min=settings["minimum horizon size"],
                                  n_max=settings["maximum horizon size"], n_f=settings["number of LSFFs"],
                                  use_gsff=not settings["disable gsff"], capacity=capacity, max_det=max_det,
-                                 device=self.device, dimensions=3 if self.luminosity else 2)
+                                 device=self.device, dimensions=3 if self.luminosity else 2,
+                                 link_mode=2 if self.luminosity else 0)
         # (a handle that links a whole batch with ONE launch -- one workgroup on one compute unit -- is nobody's neighbour:
         # detection then takes the matrix-pipe kernel and its full resident grids; beside the per-frame kernels, one-launch
         # or split (4K), it keeps round 3's choice: 21.0 k against 22.3 k frames/s at 4K with the matrix-pipe kernel)
@@ -202,7 +205,7 @@ class TrackingPipeline:
                     e2.record(self.side)
                     chain_events.append((e1, e2, frames_dev.shape[0]))
             if self._link and self.trk.batched:      # the link's binning of these detections, off the link stream
-                self.trk.prepare(res.det, res.det_count, slot)
+                self.trk.prepare(res.det, res.det_count, slot, third=res.lum if self.luminosity else None)
             # (with luminosity on, the calls above have also issued ysmr_luminosity_batch behind the components call, here on
             # the side stream: it reads the batch's frames, which a frame feed frees on `ready`)
             ready = self._ev[slot]["ready"]

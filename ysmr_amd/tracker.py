@@ -35,7 +35,7 @@ class DeviceTracker:
     """Owns one ``ysmr_tracker`` handle (one video stream)."""
 
     def __init__(self, max_disappeared=50, fps=30, n_min=0, n_max=None, n_f=3, use_gsff=True,
-                 capacity=1024, max_det=2048, device="cuda:0", gains=None, dimensions=2):
+                 capacity=1024, max_det=2048, device="cuda:0", gains=None, dimensions=2, link_mode=0):
         if dimensions not in (2, 3):
             raise ValueError(f"a tracker links in 2 or 3 dimensions, got {dimensions}")
         if dimensions == 3 and use_gsff:
@@ -58,6 +58,8 @@ class DeviceTracker:
         _lib.check(rc, "ysmr_tracker_create")
         if self.dimensions == 3:
             _lib.check(_lib.lib().ysmr_tracker_dimensions(self._handle, 3), "ysmr_tracker_dimensions")
+        if link_mode:      # (before the object is returned: callers choose their kernels from ``batched``)
+            self.link_mode(link_mode)
 
     def close(self):
         if self._handle:
@@ -119,9 +121,22 @@ class DeviceTracker:
         _lib.check(rc, "ysmr_tracker_run")
 
     @_on_own_device
-    def prepare(self, det, det_count, slot):
+    def prepare(self, det, det_count, slot, third=None):
         """Bin a batch's detections for the ``run`` that follows, on the CURRENT stream (``ysmr_tracker_prepare``: takes
-        that launch off the link stream's chain when called on the detection stream).  No-op unless ``batched``."""
+        that launch off the link stream's chain when called on the detection stream).  No-op unless ``batched``.  A 3-D
+        handle takes ``third`` as ``run`` does (``ysmr_tracker_prepare3``); without it the call stays the no-op it has
+        always been on a 3-D handle, and ``run`` bins the batch itself."""
+        if self.dimensions == 3:
+            if third is None:
+                return
+            if third.dtype != torch.float64 or third.shape[1] != self.max_det or not third.is_contiguous():
+                raise ValueError("`third` of a 3-D tracker is a contiguous float64 device tensor [B, max_det]")
+            rc = _lib.lib().ysmr_tracker_prepare3(self._handle, _lib.stream_ptr(self.device), det.data_ptr(), third.data_ptr(),
+                                                  det_count.data_ptr(), det_count.numel(), int(slot))
+            _lib.check(rc, "ysmr_tracker_prepare3")
+            return
+        if third is not None:
+            raise ValueError("`third` needs a tracker made with dimensions=3")
         rc = _lib.lib().ysmr_tracker_prepare(self._handle, _lib.stream_ptr(self.device), det.data_ptr(), det_count.data_ptr(),
                                              det_count.numel(), int(slot))
         _lib.check(rc, "ysmr_tracker_prepare")
@@ -133,11 +148,13 @@ class DeviceTracker:
 
     @property
     def batched(self):
-        """True when ``run`` links a whole batch with one launch (``k_batch``: a track per lane of one workgroup)."""
+        """True when ``run`` links a whole batch with one launch (``k_batch``, or ``k_batch3`` for a 3-D handle in link
+        mode 2: a track per lane of one workgroup)."""
         return bool(_lib.lib().ysmr_tracker_batched(self._handle))
 
     def link_mode(self, mode):
-        """0: the library's choice; 1: one launch per frame even where a batch launch would serve (measurement, tests).
+        """0: the library's choice; 1: one launch per frame even where a batch launch would serve (measurement, tests);
+        2: as 0, and a 3-D handle that can also links a batch with one launch (the same table, bit for bit).
         The track table is carried over."""
         _lib.check(_lib.lib().ysmr_tracker_link_mode(self._handle, int(mode)), "ysmr_tracker_link_mode")
 
