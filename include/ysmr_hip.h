@@ -9,6 +9,7 @@
  *
  * Reference interfaces replaced (files under /root/reference):
  *   ysmr_unpack_dib_batch cv2.VideoCapture.read (uncompressed AVI frames)   ysmr/track_eval.py:159
+ *   ysmr_annotate_batch   cv2.putText + cv2.circle + cv2.VideoWriter.write   ysmr/track_eval.py:1423-1449
  *   ysmr_threshold_batch  cv2.cvtColor + cv2.GaussianBlur + 2 x cv2.adaptiveThreshold
  *                         ysmr/track_eval.py:180-208
  *   ysmr_mean_threshold_batch  cv2.cvtColor + cv2.GaussianBlur + cv2.meanStdDev + threshold_list
@@ -46,6 +47,9 @@ extern "C" {
 #define YSMR_ERR_CAPACITY  3   /* a fixed-capacity buffer would overflow (tracks, workspace) */
 #define YSMR_ERR_STATE     4   /* handle used in the wrong state */
 
+/* 15 still: ysmr_annotate_batch and its mark struct were ADDED under this number -- no existing entry point, struct or
+ * constant changed, so every caller written against 15 keeps working; only a caller of the new function needs a library
+ * that has it (the loader reports a missing symbol by name). */
 #define YSMR_ABI_VERSION   15
 
 /* per-frame detection status bits (status_dev) */
@@ -114,6 +118,30 @@ int ysmr_unpack_dib_batch(void *stream, const uint8_t *raw_dev, int n_frames, si
  * feed) by `threads` positional reads side by side (<= 0: 8).  What cap.read() does for an uncompressed file, a batch of
  * frames at a time (ysmr/track_eval.py:159). */
 int ysmr_file_read(int fd, void *dst, size_t n, long long offset, int threads);
+
+/* ---- annotated output video ------------------------------------------------------------- */
+
+/* One mark of the annotated video (ysmr/track_eval.py:1423-1447): a track's position in one frame, truncated to
+ * integers, its id, and how it is drawn -- style 0: (B, G, R) = (0, 255, 0); style 1 (not moving): (15, 165, 253);
+ * style 2 (turn point): (255, 255, 255) and a dot of radius 1 instead of a single pixel.  16 bytes. */
+typedef struct {
+    int32_t  x, y;
+    uint32_t track_id;
+    uint32_t style;
+} ysmr_mark;
+
+/* What cv2.putText + cv2.circle + cv2.VideoWriter.write (ysmr/track_eval.py:1435-1449) do to a batch of frames, for an
+ * uncompressed 24-bit stream.  frames_dev: u8 [n_frames][height][width][channels], channels 1 (gray: B = G = R) or 3
+ * (B, G, R).  The marks of frame i are marks_dev[first_dev[i] .. first_dev[i + 1]), in table order (first_dev: int64
+ * [n_frames + 1], non-decreasing; it may point into a longer array, first_dev[0] need not be 0); first_dev = NULL: no
+ * marks, the frames are only packed.  Every frame is painted as a sequential painter would: mark by mark, the id's
+ * decimal digits (5 x 7 pixels each, 6 apart, top-left corner at (x - 10, y - 16)) and then the dot at (x, y), later
+ * paint over earlier, pixels outside the frame dropped.  out_dev: n_frames stored DIB frames, out_frame_bytes apart
+ * (>= out_stride * height), rows out_stride bytes apart (a multiple of 4, >= 3 * width; the bytes behind a row's
+ * pixels are zeroed), the last row first if bottom_up.  out_dev 4-byte aligned. */
+int ysmr_annotate_batch(void *stream, const uint8_t *frames_dev, int n_frames, int height, int width, int channels,
+                        const ysmr_mark *marks_dev, const int64_t *first_dev,
+                        uint8_t *out_dev, int out_stride, size_t out_frame_bytes, int bottom_up);
 
 /* ---- detection: a1-a6 ------------------------------------------------------------------- */
 

@@ -1,0 +1,105 @@
+"""annotate_video end to end on a synthetic clip (default 1228 x 922 gray, 400 frames, 500 marks per frame), and the
+kernel / copy times of a traced run of the same.
+
+  python3 scripts/annotate_e2e.py                      # frames/s end to end (one warm-up on a tiny clip first)
+  rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d DIR -- python3 scripts/annotate_e2e.py
+  python3 scripts/annotate_e2e.py --parse DIR          # annotate kernels and device-to-host copies per batch, their ratio
+
+The output of the three, in that order, belongs in profiles/annotate_e2e.log."""
+import argparse
+import csv
+import glob
+import os
+import shutil
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def table(n_frames, tracks, height, width, seed=0):
+    import pandas as pd
+    rng = np.random.default_rng(seed)
+    x0, y0 = rng.uniform(0, width, tracks), rng.uniform(0, height, tracks)
+    vx, vy = rng.uniform(-1, 1, tracks), rng.uniform(-1, 1, tracks)
+    t = np.tile(np.arange(n_frames), tracks)
+    tid = np.repeat(np.arange(tracks), n_frames)
+    return pd.DataFrame({"TRACK_ID": tid.astype(np.int64), "POSITION_T": t.astype(np.int64),
+                         "POSITION_X": x0[tid] + vx[tid] * t, "POSITION_Y": y0[tid] + vy[tid] * t,
+                         "moving": (rng.random(len(t)) < 0.7).astype(np.int8),
+                         "turn_points": (rng.random(len(t)) < 0.1).astype(np.int8),
+                         "motility_phenotype": np.repeat(rng.integers(0, 3, tracks), n_frames).astype(np.int8)})
+
+
+def run(args):
+    import torch
+    from ysmr_amd import annotate_video
+    from ysmr_amd.helper_file import default_settings
+    work = tempfile.mkdtemp(prefix="annotate_e2e_", dir=args.tmp)
+    try:
+        s = default_settings(**{"log to file": False, "save video file extension": ".avi", "save video fourcc codec": "DIB ",
+                                "frames per second": 30.0})
+        rng = np.random.default_rng(1)
+        small = os.path.join(work, "warm.npy")
+        np.save(small, rng.integers(0, 255, (8, 64, 64), dtype=np.uint8))
+        assert annotate_video(small, table(8, 4, 64, 64), settings=s, result_folder=work) is not None
+        clip = os.path.join(work, "clip.npy")
+        frames = np.lib.format.open_memmap(clip, mode="w+", dtype=np.uint8, shape=(args.frames, args.height, args.width))
+        one = rng.integers(0, 255, (args.height, args.width), dtype=np.uint8)
+        for i in range(args.frames):
+            frames[i] = np.roll(one, i, axis=1)
+        frames.flush()
+        del frames
+        df = table(args.frames, args.tracks, args.height, args.width)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = annotate_video(clip, df, settings=s, result_folder=work)
+        dt = time.perf_counter() - t0
+        assert out is not None
+        size = os.path.getsize(out)
+        print("annotate_video: {} frames of {} x {}, {} marks per frame, {:.1f} MB written in {:.3f} s: {:.1f} frames/s, "
+              "{:.2f} GB/s to the file ({})".format(args.frames, args.width, args.height, args.tracks, size / 1e6, dt,
+                                                   args.frames / dt, size / dt / 1e9, work), flush=True)
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+
+
+def parse(directory):
+    def rows(pattern):
+        files = glob.glob(os.path.join(directory, "**", pattern), recursive=True)
+        if not files:
+            raise SystemExit("no {} under {}".format(pattern, directory))
+        return list(csv.DictReader(open(max(files, key=os.path.getmtime))))
+
+    kernels = [r for r in rows("*_kernel_trace.csv") if "k_pack_dib" in r["Kernel_Name"] or "k_paint_marks" in r["Kernel_Name"]]
+    dur = lambda r: (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3      # noqa: E731  (us)
+    pack = sorted(dur(r) for r in kernels if "k_pack_dib" in r["Kernel_Name"])
+    paint = sorted(dur(r) for r in kernels if "k_paint_marks" in r["Kernel_Name"])
+    batches = len(pack) - 1                                   # (the first launch is the warm-up clip's)
+    moved = rows("*_memory_copy_trace.csv")
+    direction = next(k for k in moved[0] if "irection" in k)
+    copies = sorted((dur(r) for r in moved if "DEVICE_TO_HOST" in r[direction].upper()), reverse=True)
+    copies = copies[:batches]                                 # the batches' copies are the long ones
+    pack, paint = pack[1:], paint[1:]
+    k_total, c_total = sum(pack) + sum(paint), sum(copies)
+    print("traced run: {} batches".format(batches))
+    print("  k_pack_dib     per batch: mean {:9.1f} us  (min {:.1f}, max {:.1f})".format(sum(pack) / batches, pack[0], pack[-1]))
+    print("  k_paint_marks  per batch: mean {:9.1f} us  (min {:.1f}, max {:.1f})".format(sum(paint) / batches, paint[0], paint[-1]))
+    print("  device-to-host per batch: mean {:9.1f} us  (min {:.1f}, max {:.1f})".format(c_total / batches, copies[-1], copies[0]))
+    print("  kernels / copy = {:.4f}  ({})".format(k_total / c_total, "the kernels hide behind the copy" if k_total < c_total
+                                                   else "THE KERNELS TAKE LONGER THAN THE COPY"))
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=400)
+    ap.add_argument("--tracks", type=int, default=500)
+    ap.add_argument("--height", type=int, default=922)
+    ap.add_argument("--width", type=int, default=1228)
+    ap.add_argument("--tmp", default=None, help="where the clip and the output go (removed afterwards)")
+    ap.add_argument("--parse", default=None, help="a rocprofv3 output directory: print the per-batch times")
+    a = ap.parse_args()
+    parse(a.parse) if a.parse else run(a)

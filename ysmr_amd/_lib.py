@@ -60,7 +60,10 @@ EXPORTS = ("ysmr_abi_version", "ysmr_last_error", "ysmr_detect_workspace_bytes",
            "ysmr_rows_format_csv", "ysmr_rows_write_csv", "ysmr_rows_write_csv_columns", "ysmr_rows_format_device_workspace_bytes", "ysmr_rows_format_device", "ysmr_rows_format_csv_devicelike", "ysmr_rows_stream_create", "ysmr_rows_stream_push", "ysmr_rows_stream_count", "ysmr_rows_stream_finish", "ysmr_rows_stream_destroy", "ysmr_rows_columns", "ysmr_select_workspace_bytes", "ysmr_select_tracks",
            "ysmr_evaluate_workspace_bytes", "ysmr_evaluate_tracks", "ysmr_unpack_dib_batch", "ysmr_file_read",
            "ysmr_luminosity_batch", "ysmr_luminosity_batch_host", "ysmr_tracker_dimensions", "ysmr_tracker_update3",
-           "ysmr_tracker_run3", "ysmr_tracker_peek3", "ysmr_tracker_prepare3")
+           "ysmr_tracker_run3", "ysmr_tracker_peek3", "ysmr_tracker_prepare3", "ysmr_annotate_batch")
+
+#: numpy view of ``ysmr_mark`` (16 bytes): one track position of one frame of the annotated video
+MARK_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("track_id", "<u4"), ("style", "<u4")])
 
 SELECT_OK, SELECT_TOO_SHORT, SELECT_TOO_SHORT_CLEANED, SELECT_NONE = 0, 1, 2, 3
 
@@ -186,6 +189,7 @@ def lib():
     L.ysmr_select_tracks.argtypes = [vp, ctypes.c_longlong, vp, vp, vp, vp, vp, vp, ctypes.POINTER(SelectParams), vp,
                                      ctypes.c_size_t, vp, vp, ctypes.POINTER(SelectSummary)]
     L.ysmr_unpack_dib_batch.argtypes = [vp, vp, ci, ctypes.c_size_t, ci, ci, ci, ci, ci, vp, vp]
+    L.ysmr_annotate_batch.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, ci, ctypes.c_size_t, ci]
     L.ysmr_evaluate_workspace_bytes.argtypes = [ctypes.c_longlong]
     L.ysmr_evaluate_workspace_bytes.restype = ctypes.c_size_t
     L.ysmr_evaluate_tracks.argtypes = [vp, ctypes.c_longlong, vp, vp, vp, vp, vp, vp, ctypes.POINTER(EvaluateParams), vp,

@@ -1,8 +1,9 @@
 """``ysmr()`` / ``analyse()`` entry points with the reference's signatures (ysmr/main.py:32, 175).
 
 ``analyse`` runs detect-and-link (``track_bacteria``), ``select_tracks`` and the statistics of
-``evaluate_tracks`` on the device; plots, ``annotate_video`` and the xlsx collation are presentation, not part
-of the HIP path, and are skipped with a log message.  It returns the last stage's result (``return_df=True``:
+``evaluate_tracks`` on the device, and with 'save video' set ``annotate_video`` writes the annotated video from the
+evaluated table; plots and the xlsx collation are presentation, not part of the HIP path, and are skipped with a log
+message.  It returns the last stage's result (``return_df=True``:
 a DataFrame, or evaluate_tracks' ``(df, df_stats)``) or ``True``; ``None`` signals an error, as upstream.
 
 Independent videos are embarrassingly parallel (the reference runs one process per path,
@@ -15,6 +16,7 @@ import logging
 import os
 from datetime import datetime
 
+from .annotate import annotate_video
 from .helper_file import create_results_folder, get_configs, get_loggers, metadata_file
 from .evaluate import evaluate_tracks
 from .select import select_tracks
@@ -83,8 +85,12 @@ def analyse(path, settings=None, result_folder=None, return_df=False, device="cu
         if plots_eval:     # statistics of the selected tracks (main.py:131-139); None after an error, as upstream
             value = evaluate_tracks(path_to_file=path, results_directory=result_folder, df=df, settings=settings,
                                     device=device, fps=meta.get("fps"))
-            if settings["save video"]:
-                logger.warning("'save video' is enabled: annotating videos is not part of the HIP path")
+            if settings["save video"] and value is not None and ".csv" not in path:    # (main.py:139-150)
+                annotate_video(video_path=path, df=value[0], settings=settings, result_folder=result_folder, device=device)
+            elif settings["save video"] and ".csv" in path:
+                logger.warning("'save video' setting is enabled but .csv file was provided. Video can only be annotated "
+                               "when ysmr() is given a video as an argument. Optionally use annotate_video() from "
+                               "ysmr_amd.track_eval directly.")
         elif "selected_data.csv" in path:
             logger.warning("No evaluation set to True in settings. Did not evaluate {}".format(path))
         return value

@@ -34,7 +34,7 @@ from .helper_file import (COLOR_BGR2GRAY, RowStream, create_results_folder, get_
                           rows_to_dataframe, save_list, wait_for_removals)
 from .tracker import DeviceTracker, rows_to_numpy, sort_rows
 
-__all__ = ["track_bacteria", "TrackingPipeline", "select_tracks", "evaluate_tracks"]
+__all__ = ["track_bacteria", "TrackingPipeline", "select_tracks", "evaluate_tracks", "annotate_video"]
 
 #: where the wall time of the last _device_pass went, in seconds since it began (diagnostics: scripts/e2e_profile.py)
 LAST_PASS_MARKS = {}
@@ -45,7 +45,10 @@ LAST_PIPELINE_FACTS = {}
 ROW_BUDGET_MAX = 32 << 20
 
 
-def __getattr__(name):   # select_tracks / evaluate_tracks live in track_eval upstream (track_eval.py:536, 846)
+def __getattr__(name):   # select_tracks / evaluate_tracks / annotate_video live in track_eval upstream (track_eval.py:536, 846, 1321)
+    if name == "annotate_video":
+        from .annotate import annotate_video
+        return annotate_video
     if name == "select_tracks":
         from .select import select_tracks
         return select_tracks
