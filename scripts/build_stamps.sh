@@ -7,3 +7,6 @@ for f in common detect thr_mfma meangray track rows select evaluate ingest lumin
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -fno-slp-vectorize -I$R/include -DYSMR_STAMPS $EXTRA -c $C/$f.hip -o $T/$f.o || exit 1
 done
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o $R/scripts/var_stamps.so $T/*.o && echo built scripts/var_stamps.so
+# k_batch's written-out scalar loads (batch_link.h): nothing may touch their registers before their wait, in THIS build too
+python3 $R/scripts/k_batch_census.py $R/scripts/var_stamps.so > $T/census.log; rc=$?; tail -1 $T/census.log
+[ $rc -eq 0 ] || { echo "scripts/var_stamps.so: a pending scalar load's registers are touched -- do not run it"; exit 1; }

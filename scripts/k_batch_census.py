@@ -40,6 +40,9 @@ again on their own), float64 (v_*_f64, compares included), v_cndmask, lane moves
 The last line, "filter bank, by hand", adds what the round-11 issue's hand count of the parent included beyond the steady
 path (the seeding block's tail behind its ring-store loop, the instructions an s_branch jumps over): 242 VALU there.
 `census()` returns the same as a dict for tests/test_kernel_hot_path.py.
+
+The round-trip report follows: for every `s_waitcnt lgkmcnt(N)` on the walked path, the youngest scalar load or LDS access
+the wave can be waiting for there and how many instructions lie between the two (tests/test_kernel_round_trips.py).
 """
 import os
 import re
@@ -138,12 +141,13 @@ def parse(text):
 
 
 def _loop_head(ins):
-    """The frame loop: the backward branch with the longest reach around the candidate list's ds_read_b128."""
-    mark = next(i for i, (op, _, _) in enumerate(ins) if op == "ds_read_b128")
+    """The frame loop: the backward branch with the longest reach around the candidate list's ds_read_b128 (the prologue may
+    hold a ds_read_b128 of its own -- the first frame's grid header -- with no loop around it)."""
     best = None
-    for i, (op, _, tgt) in enumerate(ins):
-        if tgt is not None and tgt <= mark < i and (best is None or i - tgt > best[1] - best[0]):
-            best = (tgt, i)
+    for mark in (i for i, (op, _, _) in enumerate(ins) if op == "ds_read_b128"):
+        for i, (op, _, tgt) in enumerate(ins):
+            if tgt is not None and tgt <= mark < i and (best is None or i - tgt > best[1] - best[0]):
+                best = (tgt, i)
     if best is None:
         raise SystemExit("no loop around ds_read_b128: is this k_batch?")
     return best
@@ -212,6 +216,85 @@ def classify(op):
     return out
 
 
+def _lgkm_kind(op):
+    """'smem' / 'lds' for what s_waitcnt lgkmcnt counts on this path, else None (flat accesses: none in this kernel)."""
+    if op.startswith(("s_load_", "s_buffer_load_", "s_memtime", "s_memrealtime")):
+        return "smem"
+    if op.startswith("ds_"):
+        return "lds"
+    return None
+
+
+def round_trips(lines):
+    """Every s_waitcnt lgkmcnt(N) of `lines` [(mnemonic, operands)] that can wait for something: the youngest scalar load /
+    LDS access it can be waiting for -- the (N + 1)-th youngest still on the books -- and the distance in instructions.
+    The books are the wave's own, in program order.  LDS accesses return in order, so a wait for N leaves at most the N
+    youngest of them open; scalar loads may return out of order, so a scalar load is credited to a wait for lgkmcnt(0) only
+    (which is why the compiler only ever waits for them that way)."""
+    out, open_ = [], []
+    for k, (op, args) in enumerate(lines):
+        if op == "s_waitcnt":
+            m = re.search(r"lgkmcnt\((\d+)\)", args)
+            if not m:
+                continue
+            n = int(m.group(1))
+            lds = [i for i in open_ if _lgkm_kind(lines[i][0]) == "lds"]
+            covered = list(open_) if n == 0 else lds[:max(0, len(lds) - n)]
+            if covered:
+                j = covered[-1]
+                out.append({"wait": k, "lgkmcnt": n, "issue": j, "distance": k - j, "op": lines[j][0], "args": lines[j][1],
+                            "kind": _lgkm_kind(lines[j][0]), "covers": len(covered),
+                            "covered": [(i, _lgkm_kind(lines[i][0])) for i in covered]})
+                open_ = [i for i in open_ if i not in covered]
+        elif _lgkm_kind(op):
+            open_.append(k)
+    return out
+
+
+def _sregs(args):
+    """Scalar registers named in an operand string: s7, s[4:5]."""
+    out = set()
+    for m in re.finditer(r"\bs\[(\d+):(\d+)\]|\bs(\d+)\b", args):
+        out |= set(range(int(m.group(1)), int(m.group(2)) + 1)) if m.group(1) else {int(m.group(3))}
+    return out
+
+
+def pending_load_hazards(text):
+    """The guard of the kernel's written-out scalar loads (batch_link.h, "Kernel arguments a phase ahead"): an s_load in
+    inline assembly hands the compiler registers it believes valid at once, and the matching s_waitcnt lgkmcnt(0) stands in
+    another asm statement many instructions later -- so nothing in between may read, copy, spill or overwrite them.
+    Checked for EVERY s_load of the kernel (the compiler's own satisfy it by construction), over the whole listing and
+    along every path: from the load, through both sides of every conditional branch, to the first s_waitcnt that waits
+    for lgkmcnt(0).  Returns [(load index, load text, offending index, offending text)]; empty: clean."""
+    ins = parse(text)
+    bad = []
+    for i, (op, args, _) in enumerate(ins):
+        if not op.startswith(("s_load_", "s_buffer_load_")):
+            continue
+        dst = _sregs(args.split(",")[0])
+        todo, seen = [i + 1], set()
+        while todo:
+            j = todo.pop()
+            if j in seen or j >= len(ins):
+                continue
+            seen.add(j)
+            o, a, tgt = ins[j]
+            if o == "s_waitcnt" and "lgkmcnt(0)" in a:
+                continue
+            if _sregs(a) & dst:
+                bad.append((i, f"{op} {args}", j, f"{o} {a}"))
+                continue
+            if o == "s_endpgm":
+                continue
+            if o == "s_branch":
+                todo.append(tgt if tgt is not None else j + 1)
+                continue
+            if o.startswith("s_cbranch") and tgt is not None:
+                todo.append(tgt)
+            todo.append(j + 1)
+    return bad
+
+
 def census(text):
     ins = parse(text)
     path, skipped = walk(ins)
@@ -278,7 +361,52 @@ def census(text):
     out["path"] = [ins[i][:2] for i in path]
     out["marks"] = {"claim": claim, "barrier A": bar_a, "row end": row_end, "filter bank": fb, "filter bank end": fb_end}
     out["kernel instructions"] = len(ins)
+    # the round trips of a steady pass: the path walked twice, so that a load issued in the loop's tail meets its wait in
+    # the next pass's search; positions are those of the second pass (an issue in the pass before: negative)
+    lines, n_path = out["path"], len(path)
+    trips = []
+    for t in round_trips(lines + lines):
+        if t["wait"] >= n_path:
+            t = dict(t, wait=t["wait"] - n_path, issue=t["issue"] - n_path, covered=[(i - n_path, k) for i, k in t["covered"]])
+            t["phase"] = next(name for name, a, b in zip(PHASES, bounds, bounds[1:]) if a <= t["wait"] < b) \
+                if t["wait"] < fb_end else PHASES[0]
+            trips.append(t)
+    out["round trips"] = trips
     return out
+
+
+def smem_waits(c):
+    """[(wait, issue, distance, text)] of every scalar load of the steady pass, with the wait that first covers it."""
+    path = c["path"]
+    return [(t["wait"], i, t["wait"] - i, " ".join(path[i])) for t in c["round trips"] for i, kind in t["covered"] if kind == "smem"]
+
+
+def lds_rounds_before_claim(c):
+    """Waits on LDS accesses between the loop head and the claim's atomic that start a round trip of their own: the
+    access waited for was issued behind the wait before (the partial waits lgkmcnt(7) .. (0) that take eight reads of ONE
+    round one by one count once)."""
+    rounds, last = [], -1
+    for t in c["round trips"]:
+        if 0 <= t["wait"] <= c["marks"]["claim"] and any(kind == "lds" and i > last for i, kind in t["covered"]):
+            rounds.append(t["wait"])
+            last = t["wait"]
+    return rounds
+
+
+def report_round_trips(c):
+    """One line per s_waitcnt lgkmcnt of the steady pass that can wait for something."""
+    marks = c["marks"]
+    lines = [f"round trips on the steady path (positions from the loop head; claim at {marks['claim']}, barrier A at "
+             f"{marks['barrier A']}, filter bank {marks['filter bank']} .. {marks['filter bank end']})",
+             f"{'wait at':>8s} {'lgkmcnt':>8s} {'issued':>7s} {'distance':>9s}  {'phase':18s} youngest access it can wait for"]
+    for t in c["round trips"]:
+        lines.append(f"{t['wait']:8d} {t['lgkmcnt']:8d} {t['issue']:7d} {t['distance']:9d}  {t['phase']:18s} {t['op']} {t['args']}"
+                     + (f"   (+{t['covers'] - 1} older)" if t["covers"] > 1 else ""))
+    smem = smem_waits(c)
+    rounds = lds_rounds_before_claim(c)
+    lines.append(f"scalar loads: {len(smem)}, waited for within 8 instructions: {sum(d <= 8 for _, _, d, _ in smem)}; "
+                 f"LDS round trips from the loop head to the claim: {len(rounds)} (waits at {rounds})")
+    return "\n".join(lines)
 
 
 def report(c):
@@ -301,7 +429,16 @@ def main():
     text = listing_of_library(src) if elf else open(src).read()
     if text is None:
         raise SystemExit("no gfx950 listing of k_batch: llvm-objcopy / llvm-objdump or the kernel are missing")
-    print(report(census(text)))
+    c = census(text)
+    print(report(c))
+    print()
+    print(report_round_trips(c))
+    bad = pending_load_hazards(text)
+    print(f"scalar loads whose registers are touched before their lgkmcnt(0) wait, whole kernel, every path: {len(bad)}")
+    for i, load, j, what in bad:
+        print(f"  {load} (instruction {i}): {what} (instruction {j})")
+    if bad:
+        raise SystemExit(1)
 
 
 if __name__ == "__main__":

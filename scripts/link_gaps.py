@@ -1,5 +1,7 @@
 """Where a batch's time goes on the link stream: rocprofv3 --kernel-trace csv of bench.py -> durations of k_batch, the
-gaps between consecutive k_batch launches, and the kernels that start inside those gaps.   usage: link_gaps.py <dir>"""
+gaps between consecutive k_batch launches, and the kernels that start inside those gaps; and the pipeline fill behind the
+trace's longest gap (bench.py: the synchronize in front of the timed steps), where a batch's detection runs with no link
+beside it.   usage: link_gaps.py <dir> [timed steps, to spread the fill over]"""
 import csv, glob, sys
 import numpy as np
 rows = []
@@ -34,3 +36,14 @@ print(f"detection kernels overlap {busy / 1e3 / max(1, len(kb)):.1f} us of a k_b
 big = np.argsort(gap)[-5:]
 for i in big:
     print(f"  gap {gap[i]:.1f} us after launch {i} (duration {dur[i]:.1f})")
+# The fill: behind the longest gap (the host synchronised, the pipeline is empty) the link waits for a whole batch's detection.
+# Set against the boundary between two launches inside the steady pipeline (the median gap: k_pause, the launch itself).
+i = int(np.argmax(gap))
+first_det = min((ds for ds, de in det if ds >= kb[i][1]), default=kb[i + 1][0])
+fill = (kb[i + 1][0] - first_det) / 1e3
+steps = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+pause = [e - s for s, e, n, _ in rows if "k_pause" in n]
+print(f"pipeline fill behind the longest gap (launch {i}): {fill:.1f} us from the first detection kernel to the next k_batch"
+      + (f" = {fill / steps:.1f} us per step over {steps} timed steps" if steps else ""))
+print(f"boundary between two launches in the steady pipeline: p50 {np.median(gap):.1f} us per launch"
+      + (f", of which k_pause {np.median(pause) / 1e3:.1f} us" if pause else ""))

@@ -581,17 +581,33 @@ struct BlGridView {
     __device__ __forceinline__ int item_at(int i) const { return reinterpret_cast<const unsigned short *>(bl_u32(items))[i]; }
     __device__ __forceinline__ float2 xy_at(int i) const { return reinterpret_cast<const float2 *>(bl_u32(xy))[i]; }
 };
-__device__ __forceinline__ BlGridView bl_grid_view(int buf, int m)     // buf: dword offset of the frame's block
+// (the block's header x0, y0, cell, 1 / cell: its first four words)
+__device__ __forceinline__ float4 bl_grid_header(int buf)
 {
-    const float *hdr = reinterpret_cast<const float *>(bl_u32(buf));
+    const float2 *h = reinterpret_cast<const float2 *>(bl_u32(buf));
+    const float2 a = h[0], b = h[1];
+    return make_float4(a.x, a.y, b.x, b.y);
+}
+__device__ __forceinline__ BlGridView bl_grid_view(int buf, int m, const float4 &hdr)     // buf: dword offset of the frame's block
+{
     BlGridView g;
     g.G = bl_grid_n(m);
     g.start = buf + 16;
     g.xy = buf + 16 + bl_start_dwords(g.G);
     g.items = buf + 16 + bl_start_dwords(g.G) + 2 * bl_mp(m);
     g.lists = bl_has_lists(m) ? buf + bl_list_off(m) : -1;
-    g.x0 = hdr[0]; g.y0 = hdr[1]; g.cell = hdr[2]; g.inv = hdr[3];
+    g.x0 = hdr.x; g.y0 = hdr.y; g.cell = hdr.z; g.inv = hdr.w;
     return g;
+}
+__device__ __forceinline__ BlGridView bl_grid_view(int buf, int m) { return bl_grid_view(buf, m, bl_grid_header(buf)); }
+// The winner's centre and its column: both addresses come from the winner's position, so both reads are issued in front of
+// ONE wait (left to itself the compiler issued the column's read behind the centre's wait: a second LDS round trip in
+// front of the claim).
+__device__ __forceinline__ void bl_winner(const BlGridView &g, int q, float2 &c, int &col)
+{
+    c = g.xy_at(q);
+    col = g.item_at(q);
+    asm volatile("" : "+v"(c.x), "+v"(c.y), "+v"(col));
 }
 __device__ __forceinline__ double bl_dist2(double px, double py, float2 c)
 {
@@ -687,11 +703,11 @@ __device__ __forceinline__ BlNear bl_search_block(const BlGridView &g, double px
         bound -= 1e-3f * g.cell;
         inside = bound >= big * 0.5f || (bound > 0.f && bound * bound > band);
     }
-    const float2 cw = g.xy_at(found ? bq : 0);
+    float2 cw;
     BlNear r;
+    bl_winner(g, found ? bq : 0, cw, r.col);
     r.s = bl_dist2(px, py, cw);
     r.zx = cw.x; r.zy = cw.y;
-    r.col = g.item_at(found ? bq : 0);
     r.done = found && inside && !(second <= band);     // (hi = 0xFFFFFFFF reads as a NaN: no second candidate)
     return r;
 }
@@ -729,10 +745,10 @@ __device__ __forceinline__ BlNear bl_search(const BlGridView &g, double px, doub
         const uint32_t slot = lo & 15u;
         const uint32_t wd = (slot & 4u) ? ((slot & 2u) ? l.w : l.z) : ((slot & 2u) ? l.y : l.x);
         const int bq = (int)((wd >> (16u * (slot & 1u))) & 0xFFFFu);
-        const float2 cw = g.xy_at(bq);
+        float2 cw;
+        bl_winner(g, bq, cw, r.col);
         r.s = bl_dist2(px, py, cw);
         r.zx = cw.x; r.zy = cw.y;
-        r.col = g.item_at(bq);
         r.done = !(second <= band);      // (a padding slot is 1e30 away: its distance is +inf, never within the band)
     } else {
         r = bl_search_block(g, px, py, m);
@@ -872,6 +888,10 @@ struct BlKernArgs {
     long long rows_capacity;
     long long *row_count;
     const BlGains *gains;
+    // horizons, the kernel's one source of them: the history length from which a filter's window is full, which is also the
+    // ring offset of its leaver -- n_i[0], and n_i[k] of every further filter the handle has; of one it does not have,
+    // INT_MAX (never full: one compare per filter gates its load, with no test of n_f)
+    alignas(16) int hz[4];
 };
 typedef const __attribute__((address_space(4))) BlKernArgs *BlKernArgsPtr;
 typedef const __attribute__((address_space(4))) BlGains *BlGainsPtr;     // (written once when the handle is made, before any launch)
@@ -887,6 +907,68 @@ __device__ __forceinline__ BlKernArgsPtr bl_kernargs()
 // outstanding, and the compiler waited for vmcnt(0) again after the row store -- a store's round trip in every frame.
 __device__ __forceinline__ void bl_wait_vmem() { __builtin_amdgcn_s_waitcnt(0x0F70); }     // vmcnt 0, expcnt 7, lgkmcnt 15
 
+// Kernel arguments a phase ahead.  A load through bl_kernargs() is issued where the compiler needs its result and waited
+// for a few instructions later: a scalar-cache round trip on the wave's serial chain, in every frame.  These issue the
+// s_load where the phase's inputs are known and wait for it where they are used, a barrier's worth of instructions
+// later.  The compiler's own wait insertion does not see a load in inline assembly, so the wait is written out, and the
+// values are used only as that wait hands them on.  Between the two the compiler believes the registers valid: were it to
+// copy, spill or reuse them there, a stale pointer would be used, or the load would land on something else -- and nothing
+// at compile time says so.  THE GUARD is scripts/k_batch_census.py: pending_load_hazards, which follows every s_load of
+// the kernel's listing along every path to its lgkmcnt(0) wait; tests/test_kernel_round_trips.py runs it on the built
+// library and on every variant build it finds, scripts/build_stamps.sh on the stamps build.  Hence also: every wait is
+// reached by every wave on every path from its load (none under a test of `alive`).  (An access the compiler does not know of only makes its own
+// lgkmcnt(N) waits stricter: LDS returns in order, so "at most N open" still covers every older LDS access.)
+typedef uint32_t bl_u32x4 __attribute__((ext_vector_type(4)));
+struct BlRowArgs { ysmr_row *rows; long long rows_capacity; };
+struct BlSearchArgs { const float *det_all; int hz[BL_NF]; };
+static_assert(__builtin_offsetof(BlKernArgs, rows_capacity) == __builtin_offsetof(BlKernArgs, rows) + 8, "one s_load_dwordx4: rows, rows_capacity");
+// rows, rows_capacity: what the row behind barrier A needs, in one load
+__device__ __forceinline__ bl_u32x4 bl_row_args_issue(BlKernArgsPtr kp)
+{
+    bl_u32x4 v;
+    asm volatile("s_load_dwordx4 %0, %1, %2" : "=&s"(v) : "s"(kp), "i"(__builtin_offsetof(BlKernArgs, rows)) : "memory");
+    return v;
+}
+__device__ __forceinline__ BlRowArgs bl_row_args_wait(bl_u32x4 v)
+{
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(v) :: "memory");
+    BlRowArgs a;
+    // (through the GLOBAL address space: a pointer made from an integer is generic, and the row would leave with flat_store)
+    a.rows = (ysmr_row *)(__attribute__((address_space(1))) ysmr_row *)(((unsigned long long)v[1] << 32) | v[0]);
+    a.rows_capacity = (long long)(((unsigned long long)v[3] << 32) | v[2]);
+    return a;
+}
+// the pointer to the gains: requested behind the row, taken in front of the filter bank (behind the frame's vmcnt(0))
+__device__ __forceinline__ unsigned long long bl_gains_issue(BlKernArgsPtr kp)
+{
+    unsigned long long g;
+    asm volatile("s_load_dwordx2 %0, %1, %2" : "=&s"(g) : "s"(kp), "i"(__builtin_offsetof(BlKernArgs, gains)) : "memory");
+    return g;
+}
+__device__ __forceinline__ BlGainsPtr bl_gains_wait(unsigned long long g)
+{
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(g) :: "memory");
+    return (BlGainsPtr)g;
+}
+// det_all and the horizons: what the loads behind the search need (the claimed box, the ring entries that leave the
+// windows).  Requested behind the search, a dozen instructions in front of the claim's atomic; the compiler waits for
+// lgkmcnt(0) in front of that atomic, so that is where they are waited for (the written-out wait behind it finds them in).
+static_assert(BL_NF <= 4, "one s_load_dwordx4: the horizons");
+__device__ __forceinline__ void bl_search_args_issue(BlKernArgsPtr kp, unsigned long long &det_all, bl_u32x4 &hz)
+{
+    asm volatile("s_load_dwordx2 %0, %2, %3\n\ts_load_dwordx4 %1, %2, %4" : "=&s"(det_all), "=&s"(hz)
+                 : "s"(kp), "i"(__builtin_offsetof(BlKernArgs, det_all)), "i"(__builtin_offsetof(BlKernArgs, hz)) : "memory");
+}
+__device__ __forceinline__ BlSearchArgs bl_search_args_wait(unsigned long long det_all, bl_u32x4 hz)
+{
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(det_all), "+s"(hz) :: "memory");
+    BlSearchArgs a;
+    a.det_all = (const float *)(const __attribute__((address_space(1))) float *)det_all;
+#pragma unroll
+    for (int k = 0; k < BL_NF; ++k) a.hz[k] = (int)hz[k];
+    return a;
+}
+
 __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
 {
     const TrackerDev &t = ka.t;
@@ -894,7 +976,6 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
     const int32_t *__restrict__ det_count = ka.det_count;
     const int batch = ka.batch, frame0 = ka.frame0;
     long long *row_count = ka.row_count;
-    const BlGains *gains = ka.gains;
     __shared__ BlShared sh;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned long long below = (1ull << lane) - 1ull;
@@ -912,9 +993,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
     const int nf = t.n_f;
     const int gone_max = (int)floor(t.max_gone);        // tracker.py:104, 208: disappeared > maxDisappeared, a float
     // (max_disappeared < 32000 for a one-launch handle, so the conversion is exact)
-    // horizons: the history length from which a window is full, and the ring offset of its leaver (a filter the handle does
-    // not have: never full -- one compare per filter then gates its load, with no test of nf beside it)
-    const int hn[BL_NF] = {t.n_i[0], nf > 1 ? t.n_i[1] : 0x7FFFFFFF, nf > 2 ? t.n_i[2] : 0x7FFFFFFF};
+    const int hn[BL_NF] = {ka.hz[0], ka.hz[1], ka.hz[2]};      // (the horizons, BlKernArgs::hz: here for the first frame's mode threshold)
 
     // ---- start of the batch: counters, this lane's track, the first frame's detections
     int n = *t.n_tracks, next_id = *t.next_id, head = *bd.head & (BL_HB - 1);
@@ -947,8 +1026,8 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
     int helpers_from = (sh.top + 63) >> 6;               // first wave without a track; BL_WAVES: none
     auto chore_first = [&]() { return helpers_from < BL_WAVES ? tid - 64 * helpers_from : tid; };
     auto chore_stride = [&]() { return helpers_from < BL_WAVES ? 64 * (BL_WAVES - helpers_from) : BL_THREADS; };
-    auto dma = [&](int f) {        // frame f's block -> s_buf[f & 1], whole 1-KiB pieces, a wave-instruction each
-        const int pieces = bl_grid_dwords(sh.cnt[f]) >> 8;
+    auto dma = [&](int f, int m_f) {        // frame f's block (m_f detections) -> s_buf[f & 1], whole 1-KiB pieces, a wave-instruction each
+        const int pieces = bl_grid_dwords(m_f) >> 8;
         const char *src = bd.grid + (size_t)bd.grid_stride * f;
         const int w0 = helpers_from < BL_WAVES ? helpers_from : 0, nw = BL_WAVES - w0;
         for (int c = wave - w0; c >= 0 && c < pieces; c += nw) {
@@ -959,7 +1038,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
     };
     // the first two frames' detections and key tables
 #pragma nounroll
-    for (int k = 0; k < 2 && k < batch; ++k) dma(k);
+    for (int k = 0; k < 2 && k < batch; ++k) dma(k, sh.cnt[k]);
     for (int c = tid; c < sh.cnt[0]; c += BL_THREADS) key_at(0)[c] = ~0ull;
     if (batch > 1)
         for (int c = tid; c < sh.cnt[1]; c += BL_THREADS) key_at(1)[c] = ~0ull;
@@ -1001,7 +1080,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
     double o0 = 0.0, o1 = 0.0;       // the filter bank's outputs: a frame's row leaves behind the next frame's barrier A
     // ranks, row and counts of frame `fr`, whose deaths were counted in sh.n_dead[slot] from `start` on; behind the barrier
     // that follows the frame's ageing.  Returns the running count.
-    auto settle = [&](int slot, int start, int fr, bool row) {
+    auto settle = [&](int slot, int start, int fr, bool row, const BlRowArgs &ra) {
         const int total = sh.n_dead[slot];
         const int n_dead = total - start;
 #ifdef YSMR_STAMPS
@@ -1011,9 +1090,8 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
             for (int k = 0; k < n_dead; ++k) S.rank -= sh.dead_id[slot][k] < S.id;
         n -= n_dead;
         if (row) {
-            const BlKernArgsPtr kr = bl_kernargs();
-            ysmr_row *rows = kr->rows;
-            const long long rows_capacity = kr->rows_capacity;
+            ysmr_row *rows = ra.rows;
+            const long long rows_capacity = ra.rows_capacity;
             if (S.alive && base + S.rank < rows_capacity) {      // track_eval.py:313-316
                 ysmr_row rr;
                 rr.frame = frame0 + fr;
@@ -1023,15 +1101,21 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
                 rr.disappeared = S.gone;
                 rows[base + S.rank] = rr;
             }
-            if (tid == 0 && base + n > rows_capacity) atomicOr(kr->t.err, ERR_ROWS_CAPACITY);
+            if (tid == 0 && base + n > rows_capacity) atomicOr(bl_kernargs()->t.err, ERR_ROWS_CAPACITY);
             base += n;
         }
         return total;
     };
+    // The frame's constants a frame ahead: the count and the grid header of frame f + 1 are fixed before the launch and in
+    // LDS before A(f) (the block of f + 1 landed in front of it), so they are read behind A(f), where every wave has just
+    // waited anyway, and the head of the next search starts from registers.  The count of frame f + 2 is read there for
+    // the LDS-DMA and the key clearing, and moves up a frame with each pass: ONE read of sh.cnt per frame.
+    int mv_cur = sh.cnt[0], mv_next = sh.cnt[batch > 1 ? 1 : 0];      // (uniform, kept in vector registers: scalar ones are short)
+    float4 hdr_cur = bl_grid_header(buf_off(0));
     for (int f = 0; f < batch; ++f) {
         const int par = f & 1;
         const int kn = kc == 2 ? 0 : kc + 1, ks = kc == 0 ? 2 : kc - 1;      // the tables of frame f + 1, and of f + 2 = f - 1
-        const int m = sh.cnt[f];
+        const int m = __builtin_amdgcn_readfirstlane(mv_cur);
         BLSTAMP(0);
 #ifdef YSMR_STAMPS
         if (f == 0 && lane == 0)
@@ -1042,12 +1126,16 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
             // (the lane's own ring stores of the frame before are complete, and nothing of the ring is left outstanding
             // in the compiler's books: it would otherwise wait for vmcnt(0) -- the row stores -- in the search of every frame)
             bl_wait_vmem();
-            bl_sums_from_ring(S, bd, tid, head, t.n_i[0], nf > 1 ? t.n_i[1] : 0, nf > 2 ? t.n_i[2] : 0);
+            // (the horizons from the argument segment, here where they are needed once in BL_REFRESH frames; a filter the
+            // handle does not have: 0)
+            const BlKernArgsPtr kh = bl_kernargs();
+            const int h1 = kh->hz[1], h2 = kh->hz[2];
+            bl_sums_from_ring(S, bd, tid, head, kh->hz[0], h1 == 0x7FFFFFFF ? 0 : h1, h2 == 0x7FFFFFFF ? 0 : h2);
             bl_wait_vmem();
         }
         // ---- each track proposes its nearest detection (tracker.py:151-163)
         const bool propose = S.alive && m > 0;
-        const BlGridView gv = bl_grid_view(buf_off(par), m);
+        const BlGridView gv = bl_grid_view(buf_off(par), m, hdr_cur);
         BlNear nr{0.0, 0.f, 0.f, 0, true};
         unsigned long long key = 0;
         if (propose) nr = bl_search(gv, S.px, S.py, m);
@@ -1085,27 +1173,9 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
                 if (lane == l) nr = w;
             }
         }
-        // the measurements that leave the filters' windows with this frame (used behind the claims): requested where the
-        // window is full, 0.0 elsewhere -- bl_gsff then uses them as they are (a track born in this frame has none: its
-        // seeding supplies them).  An entry a lane reads here it wrote itself, frames ago as a rule; in the frame before
-        // only when the track was born in it, and that frame waited for its ring stores (below, behind the filter bank).
-        // The box of the proposed detection, requested before the claim is settled (a proposer that loses its column has
-        // asked for nothing it uses) and taken in front of the filter bank: behind barrier A the load would be the
-        // youngest in flight where the filter bank waits for the leaving measurements, and the wait for those -- counted
-        // in order -- would wait for it as well, a round trip to HBM a few dozen instructions old.
-        float bx[3] = {0.f, 0.f, 0.f};
-        if (propose) {
-            const float *d = bl_kernargs()->det_all + ((size_t)f * md + nr.col) * 5;
-            bx[0] = d[2]; bx[1] = d[3]; bx[2] = d[4];
-        }
-        double2 leave[BL_NF];
-#pragma unroll
-        for (int k = 0; k < BL_NF; ++k) leave[k] = make_double2(0.0, 0.0);
-        if (S.alive && t.use_gsff) {
-#pragma unroll
-            for (int k = 0; k < BL_NF; ++k)
-                if (S.len >= hn[k]) leave[k] = bl_ring_load(bd, (head - hn[k]) & (BL_HB - 1), tid);
-        }
+        unsigned long long sa_det;       // (det_all and the horizons: requested here, used behind the claim's atomic)
+        bl_u32x4 sa_hz;
+        bl_search_args_issue(bl_kernargs(), sa_det, sa_hz);
         // ---- claims (tracker.py:151-189): a column goes to the proposer with the smallest (distance, id)
         // ONE key per proposal: the bits of the squared distance s without their ten lowest (a non-negative double orders
         // like its bits), and in their place the lane's table row -- below 768, unique among the live tracks, ascending
@@ -1124,6 +1194,29 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
             const unsigned long long before = atomicMin(&key_at(kc)[nr.col], key);
             if ((before >> 10) - (key >> 10) + 1ull <= 2ull) sh.tie[par] = f;     // (an empty column: 2^54 - 1, far from every s)
         }
+        // the measurements that leave the filters' windows with this frame (used behind the claims): requested where the
+        // window is full, 0.0 elsewhere -- bl_gsff then uses them as they are (a track born in this frame has none: its
+        // seeding supplies them).  An entry a lane reads here it wrote itself, frames ago as a rule; in the frame before
+        // only when the track was born in it, and that frame waited for its ring stores (below, behind the filter bank).
+        // The box of the proposed detection, requested before the claim is settled (a proposer that loses its column has
+        // asked for nothing it uses; behind the claim's atomic, in front of which det_all and the horizons have arrived) and taken in front of the filter bank: behind barrier A the load would be the
+        // youngest in flight where the filter bank waits for the leaving measurements, and the wait for those -- counted
+        // in order -- would wait for it as well, a round trip to HBM a few dozen instructions old.
+        const BlSearchArgs sa = bl_search_args_wait(sa_det, sa_hz);
+        float bx[3] = {0.f, 0.f, 0.f};
+        if (propose) {
+            // (frame and column in 32 bits -- batch x max_det detections are far below 2^32 -- then bytes in 64)
+            const float *d = sa.det_all + (size_t)((unsigned)f * (unsigned)md + (unsigned)nr.col) * 5;
+            bx[0] = d[2]; bx[1] = d[3]; bx[2] = d[4];
+        }
+        double2 leave[BL_NF];
+#pragma unroll
+        for (int k = 0; k < BL_NF; ++k) leave[k] = make_double2(0.0, 0.0);
+        if (S.alive && t.use_gsff) {
+#pragma unroll
+            for (int k = 0; k < BL_NF; ++k)
+                if (S.len >= sa.hz[k]) leave[k] = bl_ring_load(bd, (head - sa.hz[k]) & (BL_HB - 1), tid);
+        }
         BLSTAMP(1);
         // (the waves that requested a grid block behind the barrier before: it has landed.  Track waves beside helper
         // waves requested none and wait for no vector memory access here: their row and ring stores go on in flight)
@@ -1131,12 +1224,19 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         block_sync<true>();
         BLSTAMP(2);
         // ---- behind barrier A: every wave is past frame f - 1's ageing and registration, and past frame f's search
+        const bl_u32x4 ra_pending = bl_row_args_issue(bl_kernargs());      // (rows, rows_capacity: taken in front of the row)
         if (tid == BL_THREADS - 1) sh.used[par ^ 1] = 0;
-        if (f + 2 < batch) dma(f + 2);
-        // (both reads in one LDS round: every lane reads a key -- column 0 where it proposed nothing -- and the flag rides along)
+        // (frame f + 2's count; frame f + 1's header -- past the batch's end nobody uses either, and the read stays inside
+        // the kernel's own LDS)
+        const int c_ahead = sh.cnt[f + 2 < batch ? f + 2 : f];
+        const float4 hdr_next = bl_grid_header(buf_off(par ^ 1));
+        // (in the same LDS round: every lane reads a key -- column 0 where it proposed nothing -- and the flag rides along)
         const unsigned long long k_won = key_at(kc)[nr.col];
         const int exact = sh.tie[par] == f;
-        const int d_total = settle(par ^ 1, d_prev, f - 1, f > 0);
+        if (f + 2 < batch) dma(f + 2, __builtin_amdgcn_readfirstlane(c_ahead));
+        const BlRowArgs ra = bl_row_args_wait(ra_pending);
+        const int d_total = settle(par ^ 1, d_prev, f - 1, f > 0, ra);
+        const unsigned long long gains_pending = bl_gains_issue(bl_kernargs());
         BLSTAMP(3);
         bool mine = propose && k_won == key;
         if (exact) {
@@ -1265,10 +1365,8 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         }
         // The keys of frame f + 2 are cleared here, by the waves that would otherwise wait at barrier A: see above the loop
         // (behind the registration, whose scratch this table was)
-        {
-            const int m_ahead = f + 2 < batch ? sh.cnt[f + 2] : 0;
-            for (int c = chore_first(); c >= 0 && c < m_ahead; c += chore_stride()) key_at(ks)[c] = ~0ull;
-        }
+        if (f + 2 < batch)
+            for (int c = chore_first(); c >= 0 && c < c_ahead; c += chore_stride()) key_at(ks)[c] = ~0ull;
         // ---- the filter bank (tracker.py:219-227)
         BLSTAMP(6);
         // The one wait for vector memory of a track wave's frame: the leaving measurements and the box, requested in front
@@ -1276,6 +1374,9 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         // old.  For every lane, with or without a track: the compiler then knows that no load is in flight at the head of
         // the loop, and does not guard the search's registers with waits that would catch the ring store.
         bl_wait_vmem();
+        // (the gains' pointer, requested behind the row: taken here by EVERY wave, with or without a live track -- a load
+        // left in flight would land in registers the compiler has meanwhile given to something else)
+        const BlGainsPtr gq = bl_gains_wait(gains_pending);
         if (mine) { S.info[0] = bx[0]; S.info[1] = bx[1]; S.info[2] = bx[2]; }
         o0 = z0; o1 = z1;
 #ifdef YSMR_STAMPS
@@ -1290,9 +1391,6 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
                 // of the scalar cache, s_load_dwordx16 + s_load_dwordx8 and one wait; a plain pointer that went through the
                 // asm below came back generic, and the listing had six flat_load_dwordx4 per wave and frame with two
                 // vmcnt(0) lgkmcnt(0) waits in the middle of the float64 chain: tests/test_kernel_listing.py)
-                unsigned long long ga = (unsigned long long)gains;
-                asm volatile("" : "+s"(ga));
-                const BlGainsPtr gq = (BlGainsPtr)ga;
                 // (hist_cap, lik_min and the rare block's horizons likewise: read from the argument segment here, beside the
                 // gains, they hold no scalar register across the frame)
                 bl_gsff<true>(S, t, bl_kernargs()->t, bd, *gq, tid, head, leave, z0, z1, fresh, grow_at, o0, o1);
@@ -1312,10 +1410,11 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         d_prev = d_cur; d_cur = d_total;
         kc = kn;
         head = (head + 1) & (BL_HB - 1);
+        mv_cur = mv_next; mv_next = c_ahead; hdr_cur = hdr_next;
     }
     // ---- the last frame's ranks, row and counts, behind a barrier that every wave's ageing of it has reached
     block_sync<true>();
-    settle((batch - 1) & 1, d_prev, batch - 1, true);
+    settle((batch - 1) & 1, d_prev, batch - 1, true, bl_row_args_wait(bl_row_args_issue(bl_kernargs())));
     // ---- end of the batch: the small state goes back to HBM, seat by seat
     {
         const BlKernArgsPtr ke = bl_kernargs();
@@ -1324,7 +1423,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         be.grid = ke->bd.grid; be.grid_stride = ke->bd.grid_stride; be.seat_cap = ke->bd.seat_cap;
         if (tid < seats) {
             be.i32[5 * (size_t)be.seat_cap + tid] = S.alive ? 1 : 0;
-            S.mode = bl_mode_of(grow_at, nf, {ke->t.n_i[0], nf > 1 ? ke->t.n_i[1] : 0x7FFFFFFF, nf > 2 ? ke->t.n_i[2] : 0x7FFFFFFF});
+            S.mode = bl_mode_of(grow_at, ke->t.n_f, {ke->hz[0], ke->hz[1], ke->hz[2]});
             if (S.alive) bl_seat_store(S, be, tid);
         }
         if (tid == 0) { *ke->t.n_tracks = n; *ke->t.next_id = next_id; *ke->row_count = base; *be.head = head; }

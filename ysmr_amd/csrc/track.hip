@@ -2611,6 +2611,7 @@ int ysmr_tracker_run(ysmr_tracker *t, void *stream, const float *det_dev, const 
             ka.t = t->d; ka.bd = bd; ka.det_all = det; ka.det_count = det_count_dev + f0; ka.batch = nb;
             ka.frame0 = first_frame_index + f0; ka.rows = rows_dev; ka.rows_capacity = (long long)rows_capacity;
             ka.row_count = (long long *)row_count_dev; ka.gains = t->bgains_dev;
+            for (int k = 0; k < 4; ++k) ka.hz[k] = (k == 0 || k < t->d.n_f) && k < BL_NF ? t->d.n_i[k] : 0x7FFFFFFF;
             if (BL_PAUSE_TICKS > 0) hipLaunchKernelGGL(k_pause, dim3(1), dim3(64), 0, (hipStream_t)stream, BL_PAUSE_TICKS);
             hipLaunchKernelGGL(k_batch, dim3(1), dim3(BL_THREADS), t->batch_lds, (hipStream_t)stream, ka);
             YSMR_LAUNCH_CHECK();
