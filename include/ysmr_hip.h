@@ -28,6 +28,7 @@
  *   ysmr_rows_sort        sort_list (order by TRACK_ID, POSITION_T)  ysmr/helper_file.py:1538-1574
  *   ysmr_select_tracks    select_tracks + find_good_tracks   ysmr/track_eval.py:408-843
  *   ysmr_evaluate_tracks  evaluate_tracks (statistics, not the plots)  ysmr/track_eval.py:846-1318
+ *   ysmr_plot_*           large_xy_plot, rose_graph, angle_distribution_plot   ysmr/plot_functions.py:29-257
  *   ysmr_rows_columns,    save_list text + get_data (pandas.read_csv) + save_df_to_csv
  *   ysmr_rows_format_csv  ysmr/helper_file.py:1403-1478, 860-905, 1366-1400  (host functions)
  */
@@ -47,9 +48,9 @@ extern "C" {
 #define YSMR_ERR_CAPACITY  3   /* a fixed-capacity buffer would overflow (tracks, workspace) */
 #define YSMR_ERR_STATE     4   /* handle used in the wrong state */
 
-/* 15 still: ysmr_annotate_batch and its mark struct were ADDED under this number -- no existing entry point, struct or
- * constant changed, so every caller written against 15 keeps working; only a caller of the new function needs a library
- * that has it (the loader reports a missing symbol by name). */
+/* 15 still: ysmr_annotate_batch with its mark struct, and later the ysmr_plot_* functions, were ADDED under this number
+ * -- no existing entry point, struct or constant changed, so every caller written against 15 keeps working; only a caller
+ * of a new function needs a library that has it (the loader reports a missing symbol by name). */
 #define YSMR_ABI_VERSION   15
 
 /* per-frame detection status bits (status_dev) */
@@ -558,6 +559,70 @@ int ysmr_evaluate_tracks(void *stream, long long n_rows, const uint32_t *track_i
                          double *width_um_dev, double *height_um_dev, int32_t *angle_diff_dev, int8_t *moving_dev,
                          int8_t *turn_points_dev, double *tp_of_tracks_dev, double *travelled_dist_dev,
                          int8_t *motility_phenotype_dev, double *stats_dev, long long *n_tracks_out);
+
+/* ---- the track figures: large_xy_plot, rose_graph, angle_distribution_plot, ysmr/plot_functions.py:29-257 ---- */
+
+/* These entry points were ADDED under ABI 15 (see above).  Inputs are columns of the (TRACK_ID, POSITION_T)-ordered table
+ * in HBM: the rows of a track are one contiguous run of equal ids.  Every output is a caller-made DEVICE buffer; the calls
+ * only enqueue work on `stream`.  The image is this project's own rendering; its rules are DESIGN.md, "The figures". */
+
+/* HOST function: matplotlib's viridis_r as 256 x (R, G, B): out[3 k ..] = cm.viridis_r(k, bytes=True)[:3]. */
+int ysmr_plot_colormap(uint8_t *out);
+
+/* out_dev[4] = min u, max u, min v, max v over the rows where u and v are both finite (+inf, -inf, +inf, -inf when there is
+ * none).  mode 0 (overview): u = x / px, v = y / px.  mode 1 (rose): u = (x - x_first) / px, v = (y - y_first) / px with the
+ * first row of the row's track (upstream's x_norm, y_norm).  Exact: min and max do not depend on order. */
+int ysmr_plot_extent(void *stream, long long n_rows, const uint32_t *track_id_dev, const double *x_dev, const double *y_dev,
+                     int mode, double px, double *out_dev);
+
+typedef struct ysmr_plot_view {
+    double  px;                  /* pixels per micrometre: u = x / px */
+    double  u0, v0;              /* data coordinates of the axes' lower left corner */
+    double  units_per_pixel;     /* the same along u and v: equal aspect */
+    int32_t mode;                /* 0: overview (with start dots); 1: rose graph (every track from the origin) */
+    int32_t width, height;       /* the canvas */
+    int32_t ax_x, ax_y, ax_w, ax_h;   /* the axes rectangle (top-left pixel, size), inside the canvas */
+    int32_t r2_dot, r2_start;    /* squared radii of a row's dot and of a track's start dot, 0 .. 4096 */
+    int32_t n_grid_cols, n_grid_rows;
+    int32_t bar_x, bar_y, bar_w, bar_h;   /* the colour bar; bar_w = 0: none */
+    int32_t grid_cols[32];       /* canvas columns / rows of the grid lines (drawn inside the axes only) */
+    int32_t grid_rows[32];
+} ysmr_plot_view;
+
+/* ysmr_plot_tracks paints rgb_dev: u8 [height][width][3] (R, G, B), top-down, no padding.  A row lands on
+ * col = ax_x + floor((u - u0) / units_per_pixel), row = ax_y + ax_h - 1 - floor((v - v0) / units_per_pixel) (f64, unfused;
+ * rows with a non-finite u or v are skipped) and paints the pixels (col + dx, row + dy), dx^2 + dy^2 <= r2_dot, that lie
+ * inside the axes.  dist_dev[t * dist_stride], t < n_tracks: the track's 'Distance (um)' (column 1 of
+ * ysmr_evaluate_tracks' statistics, stride 12).  Colour value c_t = (dist_t - dmin) / (dmax - dmin), 0 for every track
+ * where that range is 0 or any distance is not finite; colour = viridis_r[min(255, (int)(c_t * 256))].  Where dots meet,
+ * the track of the larger rank wins: rank_t = number of tracks u with c_u > c_t, or c_u == c_t and u < t (the shortest
+ * path on top).  mode 0 puts a black dot (r2_start) under them at every track's first row.  Background white, grid
+ * (176, 176, 176), a one-pixel black frame just outside the axes and the bar; bar row j from the top has LUT index
+ * min(255, (bar_h - 1 - j) * 256 / bar_h).  Rows of tracks beyond n_tracks are not drawn.
+ * ysmr_plot_workspace_bytes(n_rows, n_tracks, width, height): the scratch of that call;
+ * ysmr_plot_workspace_bytes(n_rows, 0, 0, 0): the scratch of ysmr_plot_angle_histogram.  0: sizes out of range. */
+size_t ysmr_plot_workspace_bytes(long long n_rows, long long n_tracks, int width, int height);
+int ysmr_plot_tracks(void *stream, long long n_rows, const uint32_t *track_id_dev, const double *x_dev, const double *y_dev,
+                     long long n_tracks, const double *dist_dev, long long dist_stride, const ysmr_plot_view *view,
+                     void *workspace_dev, size_t workspace_bytes, uint8_t *rgb_dev);
+
+/* The histogram of angle_distribution_plot.  A track passes iff (rows with moving == 1) / rows > 0.7 (f64 division of the
+ * two counts); a row is selected iff its track passes and moving == 1; *n_points_dev = the selected rows.  A selected row
+ * i whose row i - lag belongs to the same track has the heading atan2(x_i - x_{i-lag}, y_i - y_{i-lag}) and counts in bin
+ * k with edges[k] <= heading < edges[k + 1] (the last bin closed on the right; found by binary search in edges_dev, n_bins
+ * + 1 ascending values); other rows land in no bin.  1 <= n_bins <= 1024; counts_dev: n_bins entries. */
+int ysmr_plot_angle_histogram(void *stream, long long n_rows, const uint32_t *track_id_dev, const double *x_dev,
+                              const double *y_dev, const int8_t *moving_dev, int lag, int n_bins, const double *edges_dev,
+                              void *workspace_dev, size_t workspace_bytes, long long *counts_dev, long long *n_points_dev);
+
+/* The polar bar chart (north up, clockwise) as a function of the pixel.  dirs_dev: the n_bins + 1 boundary directions as
+ * (east, north) pairs, each bar narrower than half a turn (3 <= n_bins <= 1024); the last should repeat the first bit for
+ * bit.  p = (col - cx, cy - row) lies in the wedge of the lowest k with d_k x p <= 0 and d_{k+1} x p > 0 (d x p = d_e * p_n -
+ * d_n * p_e in f64, unfused) and is filled iff 0 < |p|^2 <= r2_dev[k].  Filled pixels are (143, 187, 218), black where a
+ * 4-neighbour is not filled in the same wedge.  Under the bars a grey (176, 176, 176) ring: the pixels with |p|^2 <=
+ * ring_r2 that have a 4-neighbour beyond it.  Everything else white.  rgb_dev as above. */
+int ysmr_plot_wedges(void *stream, int width, int height, int cx, int cy, int n_bins, const double *dirs_dev,
+                     const long long *r2_dev, long long ring_r2, uint8_t *rgb_dev);
 
 #ifdef __cplusplus
 }

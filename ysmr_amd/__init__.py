@@ -2,7 +2,7 @@
 
 The public surface mirrors the reference package (``ysmr/__init__.py`` re-exports ``main``,
 ``plot_functions``, ``track_eval``): ``ysmr()``, ``analyse()``, ``track_bacteria()``,
-``select_tracks()``, ``evaluate_tracks()``, ``annotate_video()``, ``CentroidTracker``, ``GaussianSumFIR`` and the tracking.ini helpers.  Importing this package does
+``select_tracks()``, ``evaluate_tracks()``, ``annotate_video()``, the three figures of ``plot_functions``, ``CentroidTracker``, ``GaussianSumFIR`` and the tracking.ini helpers.  Importing this package does
 not touch the GPU; the HIP library (``csrc/libysmr_hip.so``) is loaded on first use and there is no
 CPU fallback.
 """
@@ -18,7 +18,7 @@ _os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 __version__ = "0.1.0"
 
 __all__ = ["ysmr", "analyse", "track_bacteria", "select_tracks", "evaluate_tracks", "annotate_video", "CentroidTracker", "GaussianSumFIR", "get_configs",
-           "create_configs", "default_settings"]
+           "create_configs", "default_settings", "large_xy_plot", "rose_graph", "angle_distribution_plot"]
 
 
 def __getattr__(name):   # lazy: keep `import ysmr_amd.synth` usable without torch
@@ -34,6 +34,9 @@ def __getattr__(name):   # lazy: keep `import ysmr_amd.synth` usable without tor
     if name == "evaluate_tracks":
         from .evaluate import evaluate_tracks
         return evaluate_tracks
+    if name in ("large_xy_plot", "rose_graph", "angle_distribution_plot"):
+        from . import plot_functions
+        return getattr(plot_functions, name)
     if name == "annotate_video":
         from .annotate import annotate_video
         return annotate_video

@@ -60,7 +60,8 @@ EXPORTS = ("ysmr_abi_version", "ysmr_last_error", "ysmr_detect_workspace_bytes",
            "ysmr_rows_format_csv", "ysmr_rows_write_csv", "ysmr_rows_write_csv_columns", "ysmr_rows_format_device_workspace_bytes", "ysmr_rows_format_device", "ysmr_rows_format_csv_devicelike", "ysmr_rows_stream_create", "ysmr_rows_stream_push", "ysmr_rows_stream_count", "ysmr_rows_stream_finish", "ysmr_rows_stream_destroy", "ysmr_rows_columns", "ysmr_select_workspace_bytes", "ysmr_select_tracks",
            "ysmr_evaluate_workspace_bytes", "ysmr_evaluate_tracks", "ysmr_unpack_dib_batch", "ysmr_file_read",
            "ysmr_luminosity_batch", "ysmr_luminosity_batch_host", "ysmr_tracker_dimensions", "ysmr_tracker_update3",
-           "ysmr_tracker_run3", "ysmr_tracker_peek3", "ysmr_tracker_prepare3", "ysmr_annotate_batch")
+           "ysmr_tracker_run3", "ysmr_tracker_peek3", "ysmr_tracker_prepare3", "ysmr_annotate_batch", "ysmr_plot_colormap",
+           "ysmr_plot_extent", "ysmr_plot_workspace_bytes", "ysmr_plot_tracks", "ysmr_plot_angle_histogram", "ysmr_plot_wedges")
 
 #: numpy view of ``ysmr_mark`` (16 bytes): one track position of one frame of the annotated video
 MARK_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("track_id", "<u4"), ("style", "<u4")])
@@ -92,6 +93,14 @@ class EvaluateParams(ctypes.Structure):
     _fields_ = [("pixel_per_micrometre", ctypes.c_double), ("fps", ctypes.c_double), ("min_turn_angle", ctypes.c_double),
                 ("angle_lag", ctypes.c_int32), ("reach_lag", ctypes.c_int32), ("median_kernel", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)]
+
+
+class PlotView(ctypes.Structure):
+    """``struct ysmr_plot_view``"""
+    _fields_ = [(k, ctypes.c_double) for k in ("px", "u0", "v0", "units_per_pixel")] + \
+               [(k, ctypes.c_int32) for k in ("mode", "width", "height", "ax_x", "ax_y", "ax_w", "ax_h", "r2_dot", "r2_start",
+                                              "n_grid_cols", "n_grid_rows", "bar_x", "bar_y", "bar_w", "bar_h")] + \
+               [("grid_cols", ctypes.c_int32 * 32), ("grid_rows", ctypes.c_int32 * 32)]
 
 
 class YsmrLibraryError(RuntimeError):
@@ -194,8 +203,16 @@ def lib():
     L.ysmr_evaluate_workspace_bytes.restype = ctypes.c_size_t
     L.ysmr_evaluate_tracks.argtypes = [vp, ctypes.c_longlong, vp, vp, vp, vp, vp, vp, ctypes.POINTER(EvaluateParams), vp,
                                        ctypes.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_longlong)]
+    ll = ctypes.c_longlong
+    L.ysmr_plot_colormap.argtypes = [vp]
+    L.ysmr_plot_extent.argtypes = [vp, ll, vp, vp, vp, ci, cd, vp]
+    L.ysmr_plot_workspace_bytes.argtypes = [ll, ll, ci, ci]
+    L.ysmr_plot_workspace_bytes.restype = ctypes.c_size_t
+    L.ysmr_plot_tracks.argtypes = [vp, ll, vp, vp, vp, ll, vp, ll, ctypes.POINTER(PlotView), vp, ctypes.c_size_t, vp]
+    L.ysmr_plot_angle_histogram.argtypes = [vp, ll, vp, vp, vp, vp, ci, ci, vp, vp, ctypes.c_size_t, vp, vp]
+    L.ysmr_plot_wedges.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, ll, vp]
     for name in EXPORTS:
-        if name not in ("ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
+        if name not in ("ysmr_plot_workspace_bytes", "ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
                         "ysmr_rows_sort_workspace_bytes", "ysmr_rows_csv_bound", "ysmr_rows_stream_count",
                         "ysmr_mean_threshold_state_bytes"):
             getattr(L, name).restype = ci

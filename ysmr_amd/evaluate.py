@@ -3,9 +3,9 @@
 Host mirror of the reference's function (ysmr/track_eval.py:846-1318): same signature, same argument checks and
 log lines, same result files (``<name>_statistics.csv``, ``<name>_analysed.csv``, written with the reference's own
 ``DataFrame.to_csv`` call) and the same return value ``(df, df_stats)``.  Everything numerical happens in
-``ysmr_evaluate_tracks`` (``csrc/evaluate.hip``).  The plots (matplotlib / seaborn figures: angle histogram, rose
-graph, overview, violin plots) are presentation, not part of the HIP path; settings that ask for them are noted
-in the log and skipped.
+``ysmr_evaluate_tracks`` (``csrc/evaluate.hip``).  The overview, the rose graph and the angle histogram are painted
+on the device (``plot_functions``, ``csrc/plots.hip``) under the reference's settings and file names; the violin
+plots (seaborn figures) are not part of the HIP path: settings that ask for them are noted in the log and skipped.
 """
 from __future__ import annotations
 
@@ -25,9 +25,51 @@ STATS_COLUMNS = ["Turn Points (TP/s)", "Distance (µm)", "Speed (µm/s)", "Time 
                  "Motility Phenotype", "TRACK_ID", "Median Speed"]
 ROW_COLUMNS = ["TRACK_ID", "POSITION_T", "POSITION_X", "POSITION_Y", "WIDTH", "HEIGHT", "DEGREES_ANGLE", "angle_diff",
                "moving", "turn_points", "tp_of_tracks", "travelled_dist", "motility_phenotype"]
-_PLOT_KEYS = ("save large plots", "save rose plot", "save time violin plot", "save acr violin plot",
-              "save length violin plot", "save turning point violin plot", "save speed violin plot",
-              "save angle distribution plot / bins", "save displacement violin plot", "save percent motile plot")
+#: figures this package does not draw
+_SKIPPED_PLOT_KEYS = ("save time violin plot", "save acr violin plot", "save length violin plot",
+                      "save turning point violin plot", "save speed violin plot", "save displacement violin plot",
+                      "save percent motile plot")
+
+
+def plot_title(file_name):
+    """The figures' title (track_eval.py:882-895): the file name with spaces for underscores, without a trailing
+    '_selected_data', and twelve leading digits read as a date (yymmddHHMMSS)."""
+    from time import strftime, strptime
+    title = file_name.replace("_", " ")
+    if "_selected_data" in file_name:
+        title = title[:-len("_selected_data")]
+    stamp = title[:12]
+    if len(stamp) == 12 and stamp.isdigit():
+        try:
+            title = "{} {}".format(strftime("%d. %m. '%y,", strptime(stamp, "%y%m%d%H%M%S")), title[12:])
+        except ValueError:
+            pass
+    return title
+
+
+def _figures(out, stats, settings, title, save_path, device, logger):
+    """The three figures where the reference draws them (track_eval.py:950-957, 1216-1236).  A figure that fails is an
+    error in the log; the tables and the csv files do not depend on it."""
+    from . import plot_functions as pf
+    px = settings["pixel per micrometre"]
+    jobs = []
+    if settings.get("save angle distribution plot / bins"):
+        jobs.append(("angle_histogram", lambda path: pf.angle_distribution_plot(
+            df=out, bins_number=settings["save angle distribution plot / bins"], plot_title_name=title, save_path=path,
+            compare_n_frames=settings["compare angle between n frames"], device=device)))
+    distances = np.ascontiguousarray(stats[:, 1])
+    span = dict(dist_min=float(distances.min()), dist_max=float(distances.max())) if len(distances) else {}
+    if settings.get("save large plots"):
+        jobs.append(("Bac_Run_Overview", lambda path: pf.large_xy_plot(
+            df=out, plot_title_name=title, save_path=path, px_to_micrometre=px, distances=distances, device=device, **span)))
+    if settings.get("save rose plot"):
+        jobs.append(("rose_graph", lambda path: pf.rose_graph(
+            df=out, plot_title_name=title, save_path=path, px_to_micrometre=px, distances=distances, device=device, **span)))
+    for name, job in jobs:
+        try:
+            job(save_path.format(name, ".png"))
+        except Exception as exc:   # noqa: BLE001 -- whatever went wrong in a figure, the results stand
+            logger.error("Figure {} failed: {}".format(save_path.format(name, ".png"), exc))
 
 
 def evaluate_params(settings, fps) -> _lib.EvaluateParams:
@@ -137,10 +179,12 @@ def evaluate_tracks(path_to_file, results_directory=None, df=None, settings=None
                        "could not be assigned, reverted to 'perc. motile'.")
         parameter = STATS_COLUMNS[5]
     df_stats["Categories ({})".format(parameter)] = "All"
-    asked = [k for k in _PLOT_KEYS if settings.get(k)]
+    asked = [k for k in _SKIPPED_PLOT_KEYS if settings.get(k)]
     if asked:
         logger.info("Plots are not part of the HIP path; skipped: {}".format(", ".join(asked)))
     if settings["store final analysed .csv file"]:
         save_df_to_csv(df=out, save_path=save_path.format("analysed", ".csv"))
+    if any(settings.get(k) for k in ("save large plots", "save rose plot", "save angle distribution plot / bins")):
+        _figures(out, stats, settings, plot_title(file_name), save_path, device, logger)
     logging.info("Done evaluating file {}".format(file_name))
     return out, df_stats

@@ -1,0 +1,363 @@
+"""The track figures of ``evaluate_tracks`` -- overview, rose graph, angle histogram -- painted on the device.
+
+Host mirror of the reference's module of this name (ysmr/plot_functions.py:29-257): the same three functions, the same
+file names and figure size.  The reference hands the table to matplotlib, one ``scatter`` call per track; here the
+columns go to HBM once, ``csrc/plots.hip`` paints the canvas, and the host stamps the lettering into the downloaded
+canvas and writes the PNG (NumPy and zlib only).  The image is this project's own rendering of the same data -- which
+pixel a row lands on, which track wins a pixel and what colour it has are fixed by rules ("The figures"),
+matplotlib's antialiased output is not reproduced; the lettering is a 5 x 7 bitmap font.  The violin plots are not
+part of this.
+"""
+from __future__ import annotations
+
+import ctypes
+import logging
+import math
+import struct
+import zlib
+
+import numpy as np
+
+from . import _lib
+
+__all__ = ["angle_distribution_plot", "large_xy_plot", "rose_graph"]
+
+FIG_INCHES = (11.6929133858, 8.2677165354)     # A4 landscape, as upstream: 3507 x 2480 at 300 dpi
+MAX_TICKS = 32
+
+
+# ---- PNG -------------------------------------------------------------------------------------------------------------
+
+def write_png(path, rgb, dpi=300):
+    """``rgb``: u8 [H, W, 3].  8-bit RGB, filter 0 on every row, zlib level 1, a pHYs chunk with ``dpi``."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+    if rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.shape[0] < 1 or rgb.shape[1] < 1:
+        raise ValueError("rgb must be [H, W, 3] with H, W >= 1, got {}".format(rgb.shape))
+    h, w = rgb.shape[:2]
+    raw = np.zeros((h, 1 + 3 * w), np.uint8)              # a filter byte (0: none) in front of every row
+    raw[:, 1:] = rgb.reshape(h, 3 * w)
+
+    def chunk(kind, body):
+        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xFFFFFFFF)
+
+    per_metre = int(round(dpi / 0.0254))
+    with open(path, "wb") as fh:
+        fh.write(b"\x89PNG\r\n\x1a\n")
+        fh.write(chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)))
+        fh.write(chunk(b"pHYs", struct.pack(">IIB", per_metre, per_metre, 1)))
+        fh.write(chunk(b"IDAT", zlib.compress(raw.tobytes(), 1)))
+        fh.write(chunk(b"IEND", b""))
+
+
+# ---- lettering -------------------------------------------------------------------------------------------------------
+
+# 5 x 7 glyphs of the printable ASCII characters, five column bytes each, bit 0 = top row (the classic LCD layout)
+_FONT_HEX = (
+    "0000000000" "00005f0000" "0007000700" "147f147f14" "242a7f2a12" "2313086462" "3649552250" "0005030000"
+    "001c224100" "0041221c00" "14083e0814" "08083e0808" "0050300000" "0808080808" "0060600000" "2010080402"
+    "3e5149453e" "00427f4000" "4261514946" "2141454b31" "1814127f10" "2745454539" "3c4a494930" "0171090503"
+    "3649494936" "064949291e" "0036360000" "0056360000" "0814224100" "1414141414" "0041221408" "0201510906"
+    "324979413e" "7e1111117e" "7f49494936" "3e41414122" "7f4141221c" "7f49494941" "7f09090901" "3e4149497a"
+    "7f0808087f" "00417f4100" "2040413f01" "7f08142241" "7f40404040" "7f020c027f" "7f0408107f" "3e4141413e"
+    "7f09090906" "3e4151215e" "7f09192946" "4649494931" "01017f0101" "3f4040403f" "1f2040201f" "3f4038403f"
+    "6314081463" "0708700807" "6151494543" "007f414100" "0204081020" "0041417f00" "0402010204" "4040404040"
+    "0001020400" "2054545478" "7f48444438" "3844444420" "384444487f" "3854545418" "087e090102" "0c5252523e"
+    "7f08040478" "00447d4000" "2040443d00" "7f10284400" "00417f4000" "7c04180478" "7c08040478" "3844444438"
+    "7c14141408" "081414187c" "7c08040408" "4854545420" "043f444020" "3c4040207c" "1c2040201c" "3c4030403c"
+    "4428102844" "0c5050503c" "4464544c44" "0008364100" "00007f0000" "0041360800" "0804081008")
+_MICRO = "7e2020103e"       # 'µ'
+GLYPH_W, GLYPH_H, GLYPH_STEP = 5, 7, 6
+
+
+def _glyph_table():
+    def bitmap(hex10):
+        cols = np.frombuffer(bytes.fromhex(hex10), np.uint8)
+        return ((cols[None, :] >> np.arange(GLYPH_H)[:, None]) & 1).astype(bool)       # [row, column]
+    table = {chr(32 + k): bitmap(_FONT_HEX[10 * k:10 * k + 10]) for k in range(95)}
+    table["µ"] = bitmap(_MICRO)
+    return table
+
+
+_GLYPHS = _glyph_table()
+
+
+def text_bitmap(text, scale=1):
+    """bool [7 scale, 6 scale len(text) - scale]: the text in the 5 x 7 font, a column of space between characters;
+    characters the font does not have become '?'."""
+    text = str(text)
+    out = np.zeros((GLYPH_H, max(GLYPH_STEP * len(text) - 1, 0)), bool)
+    for k, ch in enumerate(text):
+        out[:, GLYPH_STEP * k:GLYPH_STEP * k + GLYPH_W] = _GLYPHS.get(ch, _GLYPHS["?"])
+    scale = max(1, int(scale))
+    return np.repeat(np.repeat(out, scale, axis=0), scale, axis=1)
+
+
+def text_size(text, scale=1):
+    return max(GLYPH_STEP * len(str(text)) - 1, 0) * max(1, int(scale)), GLYPH_H * max(1, int(scale))
+
+
+def stamp_text(rgb, x, y, text, scale=1, colour=(0, 0, 0), anchor="left"):
+    """Stamp ``text`` into ``rgb`` with the top-left pixel of its box at (x, y) -- or the box centred on / ending at x
+    (anchor 'centre' / 'right').  Pixels outside the canvas are dropped."""
+    bm = text_bitmap(text, scale)
+    th, tw = bm.shape
+    x = int(x) - (tw // 2 if anchor == "centre" else tw if anchor == "right" else 0)
+    y = int(y)
+    H, W = rgb.shape[:2]
+    x0, y0, x1, y1 = max(x, 0), max(y, 0), min(x + tw, W), min(y + th, H)
+    if x0 >= x1 or y0 >= y1:
+        return
+    rgb[y0:y1, x0:x1][bm[y0 - y:y1 - y, x0 - x:x1 - x]] = colour
+
+
+# ---- ticks and the view ----------------------------------------------------------------------------------------------
+
+def nice_step(span, target=8):
+    """The smallest of 1, 2, 5 x 10^k that cuts ``span`` into at most ``target`` pieces."""
+    if not (span > 0) or not math.isfinite(span):
+        return 1.0
+    raw = span / target
+    mag = 10.0 ** math.floor(math.log10(raw))
+    for m in (1.0, 2.0, 5.0, 10.0):
+        if m * mag >= raw * (1 - 1e-12):
+            return m * mag
+    return 10.0 * mag
+
+
+def ticks_125(lo, hi, step):
+    """The multiples of ``step`` in [lo, hi], at most MAX_TICKS of them."""
+    if not (hi >= lo) or not (step > 0):
+        return np.zeros(0)
+    k0, k1 = math.ceil(lo / step - 1e-9), math.floor(hi / step + 1e-9)
+    k = np.arange(k0, k1 + 1, dtype=np.float64)[:MAX_TICKS]
+    digits = max(0, -int(math.floor(math.log10(step))) + 1)
+    return np.round(k * step, digits)
+
+
+def canvas_size(dpi):
+    return int(FIG_INCHES[0] * dpi), int(FIG_INCHES[1] * dpi)
+
+
+def figure_layout(W, H):
+    """(axes rectangle, colour bar rectangle) as (x, y, w, h): the inner area is upstream's GridSpec (5 % left and right,
+    matplotlib's 12 % above and 11 % below), the axes its left 98 / 100, the bar its right 2 / 100 less a gap."""
+    x0, x1, y0, y1 = int(round(0.05 * W)), int(round(0.95 * W)), int(round(0.12 * H)), int(round(0.89 * H))
+    inner_w, inner_h = max(x1 - x0, 8), max(y1 - y0, 2)
+    slot = inner_w * 98 // 100
+    gap = max(2, inner_w // 100)
+    bar_w = max(inner_w - slot - 1, 1)
+    return (x0, y0, max(slot - gap, 1), inner_h), (x0 + inner_w - bar_w, y0, bar_w, inner_h)
+
+
+def track_view(extent, mode, px, dpi=300, size=None):
+    """``ysmr_plot_view`` of a track figure for the data extent (min u, max u, min v, max v), and its tick values.
+    Equal aspect, 5 % margin around the extent; an empty or single-point extent gets a range of 1 around it."""
+    W, H = size or canvas_size(dpi)
+    (ax_x, ax_y, ax_w, ax_h), bar = figure_layout(W, H)
+    lo_u, hi_u, lo_v, hi_v = (float(e) for e in extent)
+    if not all(math.isfinite(e) for e in (lo_u, hi_u, lo_v, hi_v)) or hi_u < lo_u or hi_v < lo_v:
+        lo_u, hi_u, lo_v, hi_v = 0.0, 1.0, 0.0, 1.0
+    span_u, span_v = hi_u - lo_u, hi_v - lo_v
+    if span_u == 0 and span_v == 0:
+        span_u = span_v = 1.0
+    upp = max(1.1 * span_u / ax_w, 1.1 * span_v / ax_h)
+    if not (upp > 0) or not math.isfinite(upp):
+        upp = 1.0 / ax_w
+    u0 = 0.5 * (lo_u + hi_u) - 0.5 * upp * ax_w
+    v0 = 0.5 * (lo_v + hi_v) - 0.5 * upp * ax_h
+    scale = dpi / 300.0
+    view = _lib.PlotView()
+    view.px, view.u0, view.v0, view.units_per_pixel = float(px), u0, v0, upp
+    view.mode, view.width, view.height = int(mode), W, H
+    view.ax_x, view.ax_y, view.ax_w, view.ax_h = ax_x, ax_y, ax_w, ax_h
+    # upstream's s=1 markers at 300 dpi: a '.' of about three pixels, an 'o' of about five
+    view.r2_dot, view.r2_start = int(round(1 * scale * scale)), int(round(4 * scale * scale))
+    view.bar_x, view.bar_y, view.bar_w, view.bar_h = bar
+    step = nice_step(upp * ax_w)
+    ticks_u, ticks_v = ticks_125(u0, u0 + upp * ax_w, step), ticks_125(v0, v0 + upp * ax_h, step)
+    cols = [(t, ax_x + int(math.floor((t - u0) / upp))) for t in ticks_u]
+    rows = [(t, ax_y + ax_h - 1 - int(math.floor((t - v0) / upp))) for t in ticks_v]
+    cols = [(t, c) for t, c in cols if ax_x <= c < ax_x + ax_w]
+    rows = [(t, r) for t, r in rows if ax_y <= r < ax_y + ax_h]
+    view.n_grid_cols, view.n_grid_rows = len(cols), len(rows)
+    for k, (_, c) in enumerate(cols):
+        view.grid_cols[k] = c
+    for k, (_, r) in enumerate(rows):
+        view.grid_rows[k] = r
+    return view, cols, rows
+
+
+def _label(value):
+    return "{:g}".format(value + 0.0)          # (+ 0.0: no '-0')
+
+
+def decorate_track_figure(rgb, view, cols, rows, title, dist_min, dist_max, dpi=300):
+    """Title, tick labels, 'µm' and the colour bar's labels, stamped outside the axes rectangle."""
+    s = max(1, int(round(dpi / 100.0)))
+    gap = 2 * s
+    stamp_text(rgb, view.ax_x + view.ax_w // 2, view.ax_y - gap - GLYPH_H * (s + 1) - 1, title, s + 1, anchor="centre")
+    below = view.ax_y + view.ax_h + 1 + gap
+    for t, c in cols:
+        stamp_text(rgb, c, below, _label(t), s, anchor="centre")
+    stamp_text(rgb, view.ax_x + view.ax_w // 2, below + (GLYPH_H + 3) * s, "µm", s, anchor="centre")
+    widest = 0
+    for t, r in rows:
+        stamp_text(rgb, view.ax_x - 1 - gap, r - GLYPH_H * s // 2, _label(t), s, anchor="right")
+        widest = max(widest, text_size(_label(t), s)[0])
+    stamp_text(rgb, view.ax_x - 1 - 2 * gap - widest, view.ax_y + view.ax_h // 2 - GLYPH_H * s // 2, "µm", s, anchor="right")
+    if view.bar_w > 0:
+        right = view.bar_x + view.bar_w + 1 + gap
+        stamp_text(rgb, right, view.bar_y, "{:.4g}".format(dist_max), s)
+        stamp_text(rgb, right, view.bar_y + view.bar_h - GLYPH_H * s, "{:.4g}".format(dist_min), s)
+        stamp_text(rgb, right, view.bar_y + view.bar_h // 2 - GLYPH_H * s // 2, "µm", s)
+
+
+# ---- the device calls ------------------------------------------------------------------------------------------------
+
+def _upload(df, dev, moving=False):
+    import torch
+    ids = torch.from_numpy(np.ascontiguousarray(df["TRACK_ID"].to_numpy(), dtype=np.uint32).view(np.int32)).to(dev)
+    x = torch.from_numpy(np.ascontiguousarray(df["POSITION_X"].to_numpy(), dtype=np.float64)).to(dev)
+    y = torch.from_numpy(np.ascontiguousarray(df["POSITION_Y"].to_numpy(), dtype=np.float64)).to(dev)
+    if moving:
+        return ids, x, y, torch.from_numpy(np.ascontiguousarray(df["moving"].to_numpy(), dtype=np.int8)).to(dev)
+    return ids, x, y
+
+
+def device_extent(ids, x, y, mode, px, dev):
+    """``ysmr_plot_extent`` on device columns: (min u, max u, min v, max v) as a NumPy array."""
+    import torch
+    out = torch.empty(4, dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().ysmr_plot_extent(_lib.stream_ptr(dev), ids.numel(), ids.data_ptr(), x.data_ptr(), y.data_ptr(), int(mode),
+                                           float(px), out.data_ptr()), "ysmr_plot_extent")
+    return out.cpu().numpy()
+
+
+def device_tracks(ids, x, y, dist, view, dev, download=True):
+    """``ysmr_plot_tracks`` on device columns (``dist``: the tracks' distances, a NumPy array): the canvas as u8
+    [H, W, 3] on the host (``download=False``: the device tensor)."""
+    import torch
+    L = _lib.lib()
+    dist = torch.from_numpy(np.ascontiguousarray(dist, dtype=np.float64)).to(dev)
+    n, nt = ids.numel(), dist.numel()
+    ws = torch.empty(max(L.ysmr_plot_workspace_bytes(n, nt, view.width, view.height), 256), dtype=torch.uint8, device=dev)
+    rgb = torch.empty(view.height, view.width, 3, dtype=torch.uint8, device=dev)
+    _lib.check(L.ysmr_plot_tracks(_lib.stream_ptr(dev), n, ids.data_ptr(), x.data_ptr(), y.data_ptr(), nt, dist.data_ptr(), 1,
+                                  ctypes.byref(view), ws.data_ptr(), ws.numel(), rgb.data_ptr()), "ysmr_plot_tracks")
+    return rgb.cpu().numpy() if download else rgb
+
+
+def device_angle_histogram(ids, x, y, moving, lag, edges, dev):
+    """``ysmr_plot_angle_histogram``: (counts int64 [bins], number of selected rows)."""
+    import torch
+    L = _lib.lib()
+    n, n_bins = ids.numel(), len(edges) - 1
+    e = torch.from_numpy(np.ascontiguousarray(edges, dtype=np.float64)).to(dev)
+    ws = torch.empty(max(L.ysmr_plot_workspace_bytes(n, 0, 0, 0), 256), dtype=torch.uint8, device=dev)
+    out = torch.empty(max(n_bins, 1) + 1, dtype=torch.int64, device=dev)
+    _lib.check(L.ysmr_plot_angle_histogram(_lib.stream_ptr(dev), n, ids.data_ptr(), x.data_ptr(), y.data_ptr(), moving.data_ptr(),
+                                           int(lag), int(n_bins), e.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr() + 8,
+                                           out.data_ptr()), "ysmr_plot_angle_histogram")
+    host = out.cpu().numpy()
+    return host[1:1 + n_bins].copy(), int(host[0])
+
+
+def device_wedges(W, H, cx, cy, dirs, r2, ring_r2, dev, download=True):
+    """``ysmr_plot_wedges``: the canvas as u8 [H, W, 3] on the host (``download=False``: the device tensor)."""
+    import torch
+    d = torch.from_numpy(np.ascontiguousarray(dirs, dtype=np.float64)).to(dev)
+    r = torch.from_numpy(np.ascontiguousarray(r2, dtype=np.int64)).to(dev)
+    rgb = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib().ysmr_plot_wedges(_lib.stream_ptr(dev), W, H, int(cx), int(cy), len(r2), d.data_ptr(), r.data_ptr(),
+                                           int(ring_r2), rgb.data_ptr()), "ysmr_plot_wedges")
+    return rgb.cpu().numpy() if download else rgb
+
+
+def track_distances(df):
+    """A track's travelled distance, per track in table order: what upstream's ``distance_colour`` is made of."""
+    ids = df["TRACK_ID"].to_numpy()
+    start = np.ones(len(ids), bool)
+    start[1:] = ids[1:] != ids[:-1]
+    return np.add.reduceat(df["travelled_dist"].to_numpy(dtype=np.float64), np.flatnonzero(start)) if len(ids) else np.zeros(0)
+
+
+def _track_figure(df, mode, plot_title_name, save_path, px, dist_min, dist_max, dpi, device, distances):
+    import torch
+    logger = logging.getLogger("ysmr").getChild(__name__)
+    dev = torch.device(device)
+    dist = np.ascontiguousarray(track_distances(df) if distances is None else distances, dtype=np.float64)
+    if not dist_max:
+        dist_max = float(dist.max()) if len(dist) else 0.0
+    with _lib.on(dev):
+        ids, x, y = _upload(df, dev)
+        view, cols, rows = track_view(device_extent(ids, x, y, mode, px, dev), mode, px, dpi)
+        rgb = device_tracks(ids, x, y, dist, view, dev)
+    decorate_track_figure(rgb, view, cols, rows, plot_title_name, dist_min, dist_max, dpi)
+    write_png(save_path, rgb, dpi)
+    logger.debug("Saving figure {}".format(save_path))
+
+
+def large_xy_plot(df, plot_title_name, save_path, px_to_micrometre=1, dist_min=0, dist_max=None, dpi=300, device="cuda:0",
+                  distances=None):
+    """Every track's path on one plot, black dots where the tracks start (plot_functions.py:109-188).  ``distances``:
+    the tracks' 'Distance (µm)' in table order (default: the sums of the table's 'travelled_dist')."""
+    _track_figure(df, 0, plot_title_name, save_path, px_to_micrometre, dist_min, dist_max, dpi, device, distances)
+
+
+def rose_graph(df, plot_title_name, save_path, dist_min=0, dist_max=None, dpi=300, device="cuda:0", distances=None,
+               px_to_micrometre=1):
+    """Every track's path from a common origin (plot_functions.py:191-257).  Upstream reads its 'x_norm' / 'y_norm'
+    columns; here they are formed from POSITION_X / POSITION_Y and ``px_to_micrometre`` on the device."""
+    _track_figure(df, 1, plot_title_name, save_path, px_to_micrometre, dist_min, dist_max, dpi, device, distances)
+
+
+def wedge_plan(counts, W, H):
+    """Centre, ring and bar radii (squared, exact integers) of the polar chart: the longest bar reaches the ring."""
+    cx, cy = W // 2, int(round(0.53 * H))
+    ring = max(1, int(0.40 * min(W, H)))
+    top = int(max(counts)) if len(counts) else 0
+    r2 = [(ring * ring * int(c) * int(c)) // (top * top) if top else 0 for c in counts]
+    return cx, cy, ring * ring, r2
+
+
+def wedge_boundaries(edges):
+    """Boundary directions (east, north) for ``ysmr_plot_wedges`` and the bin of every wedge.  A bar must be narrower
+    than half a turn, so fewer than three bins are drawn with their bars cut in sectors."""
+    edges = np.asarray(edges, np.float64)
+    n_bins = len(edges) - 1
+    parts = 1 if n_bins >= 3 else 3 if n_bins == 1 else 2
+    fine = np.concatenate([np.linspace(edges[k], edges[k + 1], parts + 1)[:-1] for k in range(n_bins)] + [edges[-1:]])
+    dirs = np.stack([np.sin(fine), np.cos(fine)], axis=1)
+    dirs[-1] = dirs[0]                                      # one full turn: the seam is one direction, bit for bit
+    return np.ascontiguousarray(dirs), np.repeat(np.arange(n_bins), parts)
+
+
+def angle_distribution_plot(df, bins_number, plot_title_name, save_path, dpi=300, compare_n_frames=10, device="cuda:0"):
+    """Polar histogram of the headings of the moving rows of tracks that move more than 70 % of the time
+    (plot_functions.py:29-90).  The table evaluate_tracks returns holds the folded change of heading in degrees, not the
+    heading, so the heading is formed again from POSITION_X / POSITION_Y with the lag ``compare_n_frames``."""
+    import torch
+    logger = logging.getLogger("ysmr").getChild(__name__)
+    dev = torch.device(device)
+    bins_number = int(bins_number)
+    edges = np.linspace(-np.pi, np.pi, bins_number + 1)
+    W, H = canvas_size(dpi)
+    with _lib.on(dev):
+        ids, x, y, moving = _upload(df, dev, moving=True)
+        counts, n_points = device_angle_histogram(ids, x, y, moving, compare_n_frames, edges, dev)
+        if not n_points:
+            logger.warning("Cannot create angle distribution plot as there are no motile tracks.")
+            return
+        dirs, bin_of = wedge_boundaries(edges)
+        cx, cy, ring_r2, r2 = wedge_plan(counts[bin_of], W, H)
+        rgb = device_wedges(W, H, cx, cy, dirs, r2, ring_r2, dev)
+    s = max(1, int(round(dpi / 100.0)))
+    ring = math.isqrt(ring_r2)
+    stamp_text(rgb, W // 2, int(round(0.05 * H)), "{} Data points: {}".format(plot_title_name, n_points), s + 1, anchor="centre")
+    stamp_text(rgb, cx, cy - ring - (GLYPH_H + 2) * s, "0", s, anchor="centre")
+    stamp_text(rgb, cx + ring + 2 * s, cy - GLYPH_H * s // 2, "90", s)
+    stamp_text(rgb, cx, cy + ring + 2 * s, "180", s, anchor="centre")
+    stamp_text(rgb, cx - ring - 2 * s, cy - GLYPH_H * s // 2, "270", s, anchor="right")
+    stamp_text(rgb, cx + int(0.71 * ring) + 2 * s, cy - int(0.71 * ring) - (GLYPH_H + 2) * s, str(int(counts.max())), s)
+    write_png(save_path, rgb, dpi)
+    logger.debug("Saving figure {}".format(save_path))
