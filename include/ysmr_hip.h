@@ -10,6 +10,7 @@
  * Reference interfaces replaced (files under /root/reference):
  *   ysmr_unpack_dib_batch cv2.VideoCapture.read (uncompressed AVI frames)   ysmr/track_eval.py:159
  *   ysmr_annotate_batch   cv2.putText + cv2.circle + cv2.VideoWriter.write   ysmr/track_eval.py:1423-1449
+ *   ysmr_mjpeg_batch      cv2.VideoWriter.write with fourcc 'MJPG' ('save video fourcc codec')   ysmr/track_eval.py:1400-1449
  *   ysmr_threshold_batch  cv2.cvtColor + cv2.GaussianBlur + 2 x cv2.adaptiveThreshold
  *                         ysmr/track_eval.py:180-208
  *   ysmr_mean_threshold_batch  cv2.cvtColor + cv2.GaussianBlur + cv2.meanStdDev + threshold_list
@@ -48,7 +49,7 @@ extern "C" {
 #define YSMR_ERR_CAPACITY  3   /* a fixed-capacity buffer would overflow (tracks, workspace) */
 #define YSMR_ERR_STATE     4   /* handle used in the wrong state */
 
-/* 15 still: ysmr_annotate_batch with its mark struct, and later the ysmr_plot_* functions, were ADDED under this number
+/* 15 still: ysmr_annotate_batch with its mark struct, and later the ysmr_plot_* and ysmr_mjpeg_* functions, were ADDED under this number
  * -- no existing entry point, struct or constant changed, so every caller written against 15 keeps working; only a caller
  * of a new function needs a library that has it (the loader reports a missing symbol by name). */
 #define YSMR_ABI_VERSION   15
@@ -143,6 +144,35 @@ typedef struct {
 int ysmr_annotate_batch(void *stream, const uint8_t *frames_dev, int n_frames, int height, int width, int channels,
                         const ysmr_mark *marks_dev, const int64_t *first_dev,
                         uint8_t *out_dev, int out_stride, size_t out_frame_bytes, int bottom_up);
+
+/* ---- annotated output video as Motion-JPEG --------------------------------------------------- */
+
+/* bit of *status_dev of ysmr_mjpeg_batch */
+#define YSMR_MJPEG_OVERFLOW 1   /* offsets_dev[n_frames] > out_capacity: the chunks that end inside the capacity are complete */
+
+/* Bytes of scratch ysmr_mjpeg_batch needs for this geometry (about 16 per pixel of the padded frames: the quantised
+ * coefficients and a bit buffer with room for the worst case, 26 bits per coefficient).  0 for a geometry it refuses. */
+size_t ysmr_mjpeg_workspace_bytes(int n_frames, int height, int width);
+
+/* What cv2.VideoWriter.write does with fourcc 'MJPG', for a batch of frames as ysmr_annotate_batch leaves them.  dib_dev:
+ * n_frames stored 24-bit DIB frames, frame_bytes apart (>= stride * height), rows stride bytes apart (a multiple of 4,
+ * >= 3 * width), B, G, R per pixel, the last row first if bottom_up.  Every frame becomes one baseline sequential JPEG
+ * (SOF0, 8 bits, Y Cb Cr all sampled 1 x 1): SOI, APP0 'AVI1', one DQT with tables 0 and 1 (T.81 Annex K.1 scaled by
+ * quality 1 .. 100 as libjpeg does), SOF0, four DHT (the typical tables of Annex K.3), DRI = ceil(width / 8), SOS, data,
+ * EOI; one MCU row is one restart interval.  Integer arithmetic only from pixel to byte -- 16-bit fixed-point JFIF colour,
+ * the edges repeated up to a multiple of 8, a 16-bit matrix DCT, quantisation rounding half away from zero, AC clamped to
+ * +-1023 and DC to [-1024, 1023] -- so the bytes are exactly those of the model in tests/jpeg_model.py, and they do not
+ * depend on scheduling.
+ * out_dev receives finished AVI chunks back to back: '00dc', the JPEG's size (little-endian u32), the JPEG, one zero byte
+ * if that size is odd; chunk i begins at out_dev + offsets_dev[i] (offsets_dev: int64 [n_frames + 1], offsets_dev[0] = 0).
+ * offsets_dev is exact whether or not the batch fits: if offsets_dev[n_frames] > out_capacity, *status_dev =
+ * YSMR_MJPEG_OVERFLOW, no byte at or beyond out_capacity is written and the chunks that end inside it are complete (call
+ * again with a buffer of offsets_dev[n_frames] bytes); otherwise *status_dev = 0.  height, width <= 65535.
+ * workspace_dev: 256-byte aligned, workspace_bytes >= ysmr_mjpeg_workspace_bytes(...); no state is kept in it. */
+int ysmr_mjpeg_batch(void *stream, const uint8_t *dib_dev, int n_frames, int height, int width,
+                     int stride, size_t frame_bytes, int bottom_up, int quality,
+                     void *workspace_dev, size_t workspace_bytes,
+                     uint8_t *out_dev, size_t out_capacity, int64_t *offsets_dev, int32_t *status_dev);
 
 /* ---- detection: a1-a6 ------------------------------------------------------------------- */
 

@@ -2,10 +2,11 @@
 kernel / copy times of a traced run of the same.
 
   python3 scripts/annotate_e2e.py                      # frames/s end to end (one warm-up on a tiny clip first)
+  python3 scripts/annotate_e2e.py --codec MJPG --quality 90      # the same as Motion-JPEG (default: --codec 'DIB ')
   rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d DIR -- python3 scripts/annotate_e2e.py
   python3 scripts/annotate_e2e.py --parse DIR          # annotate kernels and device-to-host copies per batch, their ratio
 
-The output of the three, in that order, belongs in profiles/annotate_e2e.log."""
+The output of the three, in that order, belongs in profiles/annotate_e2e.log (profiles/mjpeg_e2e.log for Motion-JPEG)."""
 import argparse
 import csv
 import glob
@@ -34,21 +35,33 @@ def table(n_frames, tracks, height, width, seed=0):
                          "motility_phenotype": np.repeat(rng.integers(0, 3, tracks), n_frames).astype(np.int8)})
 
 
+def scene(rng, height, width):
+    """A frame like a microscope's: a noisy gray background and a few hundred bright blobs (noise alone is the worst case of
+    any codec and says nothing about a video's size)."""
+    frame = rng.normal(90.0, 6.0, (height, width))
+    yy, xx = np.mgrid[:height, :width]
+    for _ in range(300):
+        cy, cx, r = rng.uniform(0, height), rng.uniform(0, width), rng.uniform(2.0, 5.0)
+        y0, y1, x0, x1 = int(max(0, cy - 3 * r)), int(min(height, cy + 3 * r)), int(max(0, cx - 3 * r)), int(min(width, cx + 3 * r))
+        frame[y0:y1, x0:x1] += 120.0 * np.exp(-((yy[y0:y1, x0:x1] - cy) ** 2 + (xx[y0:y1, x0:x1] - cx) ** 2) / (2 * r * r))
+    return np.clip(frame, 0, 255).astype(np.uint8)
+
+
 def run(args):
     import torch
     from ysmr_amd import annotate_video
     from ysmr_amd.helper_file import default_settings
     work = tempfile.mkdtemp(prefix="annotate_e2e_", dir=args.tmp)
     try:
-        s = default_settings(**{"log to file": False, "save video file extension": ".avi", "save video fourcc codec": "DIB ",
-                                "frames per second": 30.0})
+        s = default_settings(**{"log to file": False, "save video file extension": ".avi", "save video fourcc codec": args.codec,
+                                "frames per second": 30.0, "hip video jpeg quality": args.quality})
         rng = np.random.default_rng(1)
         small = os.path.join(work, "warm.npy")
         np.save(small, rng.integers(0, 255, (8, 64, 64), dtype=np.uint8))
         assert annotate_video(small, table(8, 4, 64, 64), settings=s, result_folder=work) is not None
         clip = os.path.join(work, "clip.npy")
         frames = np.lib.format.open_memmap(clip, mode="w+", dtype=np.uint8, shape=(args.frames, args.height, args.width))
-        one = rng.integers(0, 255, (args.height, args.width), dtype=np.uint8)
+        one = scene(rng, args.height, args.width) if args.scene else rng.integers(0, 255, (args.height, args.width), dtype=np.uint8)
         for i in range(args.frames):
             frames[i] = np.roll(one, i, axis=1)
         frames.flush()
@@ -60,9 +73,11 @@ def run(args):
         dt = time.perf_counter() - t0
         assert out is not None
         size = os.path.getsize(out)
-        print("annotate_video: {} frames of {} x {}, {} marks per frame, {:.1f} MB written in {:.3f} s: {:.1f} frames/s, "
-              "{:.2f} GB/s to the file ({})".format(args.frames, args.width, args.height, args.tracks, size / 1e6, dt,
-                                                   args.frames / dt, size / dt / 1e9, work), flush=True)
+        print("annotate_video [{}{}]: {} frames of {} x {}, {} marks per frame, {:.1f} MB written in {:.3f} s: {:.1f} frames/s, "
+              "{:.2f} GB/s to the file, file size {} bytes ({})".format(
+                  args.codec.strip(), ", quality {}".format(args.quality) if args.codec.upper() in ("MJPG", "JPEG") else "",
+                  args.frames, args.width, args.height, args.tracks, size / 1e6, dt, args.frames / dt, size / dt / 1e9, size, work),
+              flush=True)
     finally:
         shutil.rmtree(work, ignore_errors=True)
 
@@ -74,7 +89,8 @@ def parse(directory):
             raise SystemExit("no {} under {}".format(pattern, directory))
         return list(csv.DictReader(open(max(files, key=os.path.getmtime))))
 
-    kernels = [r for r in rows("*_kernel_trace.csv") if "k_pack_dib" in r["Kernel_Name"] or "k_paint_marks" in r["Kernel_Name"]]
+    trace = rows("*_kernel_trace.csv")
+    kernels = [r for r in trace if "k_pack_dib" in r["Kernel_Name"] or "k_paint_marks" in r["Kernel_Name"]]
     dur = lambda r: (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3      # noqa: E731  (us)
     pack = sorted(dur(r) for r in kernels if "k_pack_dib" in r["Kernel_Name"])
     paint = sorted(dur(r) for r in kernels if "k_paint_marks" in r["Kernel_Name"])
@@ -89,6 +105,11 @@ def parse(directory):
     print("  k_pack_dib     per batch: mean {:9.1f} us  (min {:.1f}, max {:.1f})".format(sum(pack) / batches, pack[0], pack[-1]))
     print("  k_paint_marks  per batch: mean {:9.1f} us  (min {:.1f}, max {:.1f})".format(sum(paint) / batches, paint[0], paint[-1]))
     print("  device-to-host per batch: mean {:9.1f} us  (min {:.1f}, max {:.1f})".format(c_total / batches, copies[-1], copies[0]))
+    for name in ("k_mj_blocks", "k_mj_lengths", "k_mj_pack", "k_mj_count", "k_mj_layout", "k_mj_write"):
+        mine = sorted(dur(r) for r in trace if name in r["Kernel_Name"])[-batches:] if batches > 0 else []
+        if mine:                                                  # (the warm-up clip's launches are the short ones)
+            print("  {:<14} per batch: mean {:9.1f} us  (min {:.1f}, max {:.1f})".format(name, sum(mine) / len(mine), mine[0], mine[-1]))
+            k_total += sum(mine)
     print("  kernels / copy = {:.4f}  ({})".format(k_total / c_total, "the kernels hide behind the copy" if k_total < c_total
                                                    else "THE KERNELS TAKE LONGER THAN THE COPY"))
 
@@ -99,6 +120,9 @@ if __name__ == "__main__":
     ap.add_argument("--tracks", type=int, default=500)
     ap.add_argument("--height", type=int, default=922)
     ap.add_argument("--width", type=int, default=1228)
+    ap.add_argument("--codec", default="DIB ", help="'save video fourcc codec': 'DIB ' (uncompressed) or MJPG")
+    ap.add_argument("--quality", type=int, default=90, help="'hip video jpeg quality' (Motion-JPEG only)")
+    ap.add_argument("--scene", action="store_true", help="a microscope-like frame instead of noise")
     ap.add_argument("--tmp", default=None, help="where the clip and the output go (removed afterwards)")
     ap.add_argument("--parse", default=None, help="a rocprofv3 output directory: print the per-batch times")
     a = ap.parse_args()

@@ -2,14 +2,24 @@
 
 Upstream reads the video again, paints every track's id and centroid into each frame (``cv2.putText``, ``cv2.circle``)
 and hands the frames to ``cv2.VideoWriter``.  Here the frames come through ``DeviceFrameFeed``, ``ysmr_annotate_batch``
-(``csrc/annotate.hip``) paints the marks and lays the frames out as stored 24-bit DIB frames, a stream of its own copies
-them into one of two pinned buffers, and a writer thread appends those to an uncompressed AVI (``AviWriter``): the host
-moves bytes and touches no pixel.
+(``csrc/annotate.hip``) paints the marks and lays the frames out as stored 24-bit DIB frames, and then either
+
+* (uncompressed, the default) a stream of its own copies them into one of two pinned buffers, and a writer thread appends
+  those to an uncompressed AVI (``AviWriter``), or
+* (Motion-JPEG: 'save video file extension' ``.avi`` with 'save video fourcc codec' ``MJPG`` / ``JPEG``)
+  ``ysmr_mjpeg_batch`` (``csrc/mjpeg.hip``) turns them into finished ``00dc`` chunks, one baseline JPEG each, on the
+  device; the copy stream brings over their offsets and then only the bytes those name, and the writer thread appends
+  them to a Motion-JPEG AVI (``MjpegAviWriter``).
+
+Either way the host moves bytes and touches no pixel.
 
 Departures from upstream, all deliberate:
 
-* the file is always an uncompressed 24-bit ``.avi`` (no encoder is a dependency of this package); settings that ask for
-  another container or codec are answered with one warning that names what is written;
+* the file is always an ``.avi``, uncompressed 24-bit or Motion-JPEG (no encoder is a dependency of this package: the
+  JPEG encoder is the package's own kernels); settings that ask for another container or codec are answered with one
+  warning that names what is written;
+* Motion-JPEG is 4:4:4 with the typical Huffman tables of T.81 Annex K at the quality of the optional settings key
+  'hip video jpeg quality' (1 .. 100, default 90), one restart interval per MCU row (``output_format``);
 * the digits are a 5 x 7 bitmap font, not OpenCV's Hershey strokes (placement, size class, colours and dot sizes are
   upstream's);
 * ``select_subtype`` selects the rows whose ``motility_phenotype`` equals the subtype's code (0 immotile, 1 twitching,
@@ -33,13 +43,18 @@ from . import _lib
 from .frames import DeviceFrameFeed, open_video
 from .helper_file import create_results_folder, get_configs, get_data, get_loggers
 
-__all__ = ["annotate_video", "AviWriter", "build_marks", "subtype_code", "SUBTYPES"]
+__all__ = ["annotate_video", "AviWriter", "MjpegAviWriter", "output_format", "build_marks", "subtype_code", "SUBTYPES"]
 
 SUBTYPES = ("immotile", "twitching", "motile")
 #: one pinned output buffer (there are two) holds at most this many bytes
 PINNED_BYTES_MAX = 256 << 20
 #: what 'save video fourcc codec' may say without a warning: the names of an uncompressed stream
 _RAW_CODECS = ("", "DIB ", "DIB", "RGB ", "RGB", "RAW ", "RAW", "0")
+#: the names 'save video fourcc codec' has for Motion-JPEG (with 'save video file extension' = .avi)
+_JPEG_CODECS = ("MJPG", "JPEG")
+JPEG_QUALITY_DEFAULT = 90
+#: the encoder's workspace (about 16 bytes per pixel of a batch) is kept at or below this by the batch size
+MJPEG_WORKSPACE_MAX = 1 << 30
 
 
 class AviWriter:
@@ -96,7 +111,7 @@ class AviWriter:
         fh = self._fh
         movi_size = self._pos - (self._movi_list + 8)
         if self._first:
-            idx = b"".join(struct.pack("<4sIII", b"00db", 0x10, off, self.frame_bytes) for off in self._index)
+            idx = self._idx1()
             fh.write(b"idx1" + struct.pack("<I", len(idx)) + idx)
             self._pos += 8 + len(idx)
         fh.seek(self._movi_list + 4)
@@ -105,6 +120,14 @@ class AviWriter:
         fh.write(struct.pack("<I", self._pos - (self._seg_start + 8)))
         fh.seek(self._pos)
         self._first = False
+
+    def _idx1(self):
+        return b"".join(struct.pack("<4sIII", b"00db", 0x10, off, self.frame_bytes) for off in self._index)
+
+    def _stream_format(self):
+        """(strh handler, biCompression, biHeight, bytes of the largest frame, bytes per second)."""
+        size = self.frame_bytes
+        return b"DIB ", 0, self.height if self.bottom_up else -self.height, size, int(size * self.rate / self.scale)
 
     def _new_segment(self):
         self._end_segment()
@@ -153,13 +176,12 @@ class AviWriter:
             return
         fh = self._fh
         self._end_segment()
-        size = self.frame_bytes
-        avih = struct.pack("<14I", int(round(1e6 * self.scale / self.rate)), min(int(size * self.rate / self.scale), 0xFFFFFFFF), 0, 0x10,
+        handler, compression, bi_height, size, per_second = self._stream_format()
+        avih = struct.pack("<14I", int(round(1e6 * self.scale / self.rate)), min(per_second, 0xFFFFFFFF), 0, 0x10,
                            self._first_frames, 0, 1, size, self.width, self.height, 0, 0, 0, 0)
-        strh = struct.pack("<4s4sIHHIIIIIIiI4h", b"vids", b"DIB ", 0, 0, 0, 0, self.scale, self.rate, 0, self.frames, size,
+        strh = struct.pack("<4s4sIHHIIIIIIiI4h", b"vids", handler, 0, 0, 0, 0, self.scale, self.rate, 0, self.frames, size,
                            -1, 0, 0, 0, self.width, self.height)
-        strf = struct.pack("<IiiHHIIiiII", 40, self.width, self.height if self.bottom_up else -self.height, 1, 24, 0, size,
-                           0, 0, 0, 0)
+        strf = struct.pack("<IiiHHIIiiII", 40, self.width, bi_height, 1, 24, compression, size, 0, 0, 0, 0)
 
         def chunk(cid, body):
             return cid + struct.pack("<I", len(body)) + body
@@ -185,6 +207,96 @@ class AviWriter:
             os.remove(self.path)
         except OSError:
             pass
+
+
+class MjpegAviWriter(AviWriter):
+    """Motion-JPEG AVI: ``AviWriter``'s file with chunks of their own sizes.  ``strh`` handler and ``biCompression`` are
+    ``MJPG`` (24 bits, positive height), the chunks are ``00dc``, every ``idx1`` entry carries its chunk's size, and
+    ``biSizeImage`` / the suggested buffer size are the largest chunk's.  The segment rule (``RIFF AVIX``, ``riff_limit``),
+    the rate / scale fraction and ``dmlh`` are ``AviWriter``'s."""
+
+    def __init__(self, path, width, height, fps, riff_limit=1 << 30):
+        super().__init__(path, width, height, fps, riff_limit=riff_limit, bottom_up=True)
+        self._sizes = []                # payload sizes of the first segment's chunks, beside self._index
+        self.largest = 0                # the largest payload
+        self.payload_bytes = 0          # all payloads
+
+    def _idx1(self):
+        return b"".join(struct.pack("<4sIII", b"00dc", 0x10, off, size) for off, size in zip(self._index, self._sizes))
+
+    def _stream_format(self):
+        mean = self.payload_bytes / max(1, self.frames)
+        return b"MJPG", struct.unpack("<I", b"MJPG")[0], self.height, self.largest, int(mean * self.rate / self.scale)
+
+    def chunk_header(self):
+        raise NotImplementedError("a Motion-JPEG chunk carries its own size")
+
+    def write(self, frames):
+        raise NotImplementedError("MjpegAviWriter takes finished chunks: write_chunks(data, offsets)")
+
+    def write_chunks(self, data, offsets):
+        """Append finished chunks: ``data`` a C-contiguous uint8 array with the chunks back to back ('00dc', the payload
+        size, the payload, a zero byte if the size is odd), chunk i at ``data[offsets[i]:offsets[i + 1]]``.  A run of chunks
+        that stays inside one segment is one write."""
+        data = np.asarray(data)
+        offsets = [int(o) for o in offsets]
+        if data.dtype != np.uint8 or data.ndim != 1 or not data.flags["C_CONTIGUOUS"]:
+            raise ValueError("write_chunks needs a C-contiguous one-dimensional uint8 array")
+        if not offsets or offsets[-1] > len(data) or any(b - a < 8 for a, b in zip(offsets, offsets[1:])):
+            raise ValueError("offsets {} do not describe chunks of an array of {} bytes".format(offsets, len(data)))
+        sizes = []
+        for a, b in zip(offsets, offsets[1:]):
+            tag, size = struct.unpack_from("<4sI", data, a)
+            if tag != b"00dc" or 8 + size + (size & 1) != b - a:
+                raise ValueError("chunk at {}: tag {!r}, size {} in {} bytes".format(a, tag, size, b - a))
+            sizes.append(size)
+        done, n = 0, len(sizes)
+        while done < n:
+            run = done
+            while run < n:                       # how many more chunks the current segment takes
+                used = self._pos + (offsets[run] - offsets[done]) - self._seg_start
+                more = offsets[run + 1] - offsets[run] + (16 * (len(self._index) + run - done + 1) + 8 if self._first else 0)
+                empty = run == done and self._pos == self._movi_list + 12
+                if used + more > self.riff_limit and not empty:
+                    break
+                run += 1
+            if run == done:
+                self._new_segment()
+                continue
+            self._fh.write(memoryview(data[offsets[done]:offsets[run]]))
+            if self._first:
+                base = self._movi_list + 8
+                self._index.extend(self._pos - base + offsets[k] - offsets[done] for k in range(done, run))
+                self._sizes.extend(sizes[done:run])
+                self._first_frames += run - done
+            self.frames += run - done
+            self._pos += offsets[run] - offsets[done]
+            self.largest = max([self.largest] + sizes[done:run])
+            self.payload_bytes += sum(sizes[done:run])
+            done = run
+
+
+def output_format(settings):
+    """What 'save video file extension' / 'save video fourcc codec' / 'hip video jpeg quality' ask for:
+    ``(format, quality, warning)`` -- ``("mjpeg", 1 .. 100, None)`` exactly when the extension is ``.avi`` and the codec
+    ``MJPG`` or ``JPEG`` (any letter case; the quality defaults to 90; ValueError if it is not 1 .. 100), else
+    ``("raw", None, warning)`` with the warning (None for ``.avi`` and the name of an uncompressed stream) that the caller
+    completes with the file name."""
+    ext = str(settings.get("save video file extension") or "")
+    codec = str(settings.get("save video fourcc codec") or "")
+    if ext.lower() == ".avi" and codec.upper() in _JPEG_CODECS:
+        asked = settings.get("hip video jpeg quality")
+        try:
+            quality = JPEG_QUALITY_DEFAULT if asked is None or asked == "" else int(asked)
+        except (TypeError, ValueError):
+            quality = None
+        if quality is None or isinstance(asked, bool) or not 1 <= quality <= 100:
+            raise ValueError("'hip video jpeg quality' must be an integer from 1 to 100, got {!r}".format(asked))
+        return "mjpeg", quality, None
+    if ext.lower() != ".avi" or codec.upper() not in _RAW_CODECS:
+        return "raw", None, ("'save video file extension' = {!r} / 'save video fourcc codec' = {!r}: the HIP path has no encoder; "
+                             "writing an uncompressed 24-bit AVI instead".format(ext, codec))
+    return "raw", None, None
 
 
 def subtype_code(select_subtype):
@@ -244,13 +356,137 @@ def _csv_table(path, logger, settings):
     return get_data(path, dtype=dtype)
 
 
+def _mjpeg_frames(video, writer, marks, first, n_frames, quality, settings, result_folder, dev, logger):
+    """The loop of ``annotate_video`` in Motion-JPEG mode: ``ysmr_annotate_batch`` paints a batch into a device buffer of
+    stored DIB frames, ``ysmr_mjpeg_batch`` encodes that into finished chunks, the copy stream brings the offsets and the
+    status over and then only the bytes the offsets name, and the writer thread appends them.  Two output buffers on the
+    device and two pinned ones, as in the uncompressed mode; their default capacity is the batch's uncompressed size, and a
+    batch that does not fit is encoded once more into buffers of the size its offsets ask for.  Returns the number of frames
+    written, None (after a critical message) if the disk runs full; anything else is raised."""
+    import torch
+    height, width, channels = video.height, video.width, video.channels
+    stride, frame_bytes = writer.stride, writer.frame_bytes
+    L = _lib.lib()
+    batch = int(settings.get("hip frames per batch") or 0) or auto_batch(frame_bytes + 8, n_frames)
+    batch = max(1, min(batch, auto_batch(frame_bytes + 8, n_frames),
+                       MJPEG_WORKSPACE_MAX // max(1, L.ysmr_mjpeg_workspace_bytes(1, height, width))))
+    ws_bytes = L.ysmr_mjpeg_workspace_bytes(batch, height, width)
+    if not ws_bytes:
+        raise ValueError("a Motion-JPEG frame is at most 65535 x 65535, got {} x {}".format(width, height))
+    with _lib.on(dev):
+        marks_dev = torch.from_numpy(marks.view(np.uint8).reshape(-1)).to(dev) if len(marks) else \
+            torch.zeros(16, dtype=torch.uint8, device=dev)
+        first_dev = torch.from_numpy(first).to(dev)
+        dib_dev = torch.empty((batch, frame_bytes), dtype=torch.uint8, device=dev)       # (one: paint and encode are in order)
+        workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        capacity = [batch * frame_bytes] * 2
+        out_dev = [torch.empty(capacity[k], dtype=torch.uint8, device=dev) for k in range(2)]
+        pinned = [torch.empty(capacity[k], dtype=torch.uint8, pin_memory=True) for k in range(2)]
+        # offsets [batch + 1] and, in the last element, the status
+        meta_dev = [torch.zeros(batch + 2, dtype=torch.int64, device=dev) for _k in range(2)]
+        meta = [torch.zeros(batch + 2, dtype=torch.int64, pin_memory=True) for _k in range(2)]
+        copy_stream = torch.cuda.Stream(device=dev)
+        free_slots, jobs, failure = queue.Queue(), queue.Queue(), []
+        for k in range(2):
+            free_slots.put(k)
+
+        def write_loop():
+            while True:
+                job = jobs.get()
+                if job is None:
+                    return
+                k, offsets, copied = job
+                try:
+                    if not failure:
+                        copied.synchronize()
+                        writer.write_chunks(pinned[k].numpy()[:offsets[-1]], offsets)
+                except BaseException as exc:      # noqa: BLE001 -- handed to the caller's thread
+                    failure.append(exc)
+                free_slots.put(k)
+
+        def encode(stream, k, n):
+            """Encode the painted batch into slot k and bring offsets and status over: (offsets, status)."""
+            _lib.check(L.ysmr_mjpeg_batch(
+                stream.cuda_stream, dib_dev.data_ptr(), n, height, width, stride, frame_bytes, int(writer.bottom_up), quality,
+                workspace.data_ptr(), ws_bytes, out_dev[k].data_ptr(), capacity[k], meta_dev[k].data_ptr(),
+                meta_dev[k].data_ptr() + 8 * (batch + 1)), "ysmr_mjpeg_batch")
+            encoded = torch.cuda.Event()
+            encoded.record(stream)
+            with torch.cuda.stream(copy_stream):
+                copy_stream.wait_event(encoded)
+                meta[k].copy_(meta_dev[k], non_blocking=True)
+                known = torch.cuda.Event()
+                known.record(copy_stream)
+            known.synchronize()
+            values = meta[k].numpy()
+            return [int(v) for v in values[:n + 1]], int(values[batch + 1]) & 0xFFFFFFFF
+
+        thread = threading.Thread(target=write_loop, name="ysmr-annotate-writer", daemon=True)
+        thread.start()
+        done, shortfall, feed = 0, None, None
+        try:
+            feed = DeviceFrameFeed(video, batch, dev, depth=2)
+            for frames_dev, f0, n, slot in feed:
+                n = min(n, n_frames - f0)
+                if n <= 0:
+                    feed.release(slot, True)
+                    break
+                k = free_slots.get()              # its last copy has been written: both buffers of slot k are free
+                if failure:
+                    raise failure[0]
+                stream = torch.cuda.current_stream(dev)
+                _lib.check(L.ysmr_annotate_batch(
+                    stream.cuda_stream, frames_dev.data_ptr(), n, height, width, channels, marks_dev.data_ptr(),
+                    first_dev.data_ptr() + 8 * f0, dib_dev.data_ptr(), stride, frame_bytes, int(writer.bottom_up)),
+                    "ysmr_annotate_batch")
+                painted = torch.cuda.Event()
+                painted.record(stream)
+                feed.release(slot, painted)
+                offsets, status = encode(stream, k, n)
+                if status & 1:
+                    logger.debug("Motion-JPEG: frames {} .. {} take {} bytes, the buffer has {}: encoding them again".format(
+                        f0, f0 + n - 1, offsets[-1], capacity[k]))
+                    capacity[k] = offsets[-1]
+                    out_dev[k] = torch.empty(capacity[k], dtype=torch.uint8, device=dev)
+                    pinned[k] = torch.empty(capacity[k], dtype=torch.uint8, pin_memory=True)
+                    offsets, status = encode(stream, k, n)
+                if status:
+                    raise RuntimeError("ysmr_mjpeg_batch: status {} for frames {} .. {} ({} bytes into {})".format(
+                        status, f0, f0 + n - 1, offsets[-1], capacity[k]))
+                need, free = offsets[-1] + 24 * n + 4096, shutil.disk_usage(result_folder).free
+                if free < need:
+                    shortfall = (need, free)
+                    break
+                with torch.cuda.stream(copy_stream):
+                    pinned[k][:offsets[-1]].copy_(out_dev[k][:offsets[-1]], non_blocking=True)
+                    copied = torch.cuda.Event()
+                    copied.record(copy_stream)
+                jobs.put((k, offsets, copied))
+                done = f0 + n
+        finally:
+            jobs.put(None)
+            thread.join()
+            torch.cuda.synchronize(dev)
+            if feed is not None:
+                feed.close()
+        if failure:
+            raise failure[0]
+        if shortfall:
+            logger.critical("Not enough free space in {} for the annotated video: {} bytes needed, {} free".format(
+                result_folder, shortfall[0], shortfall[1]))
+            return None
+    return done
+
+
 def annotate_video(video_path, df, output_save=True, settings=None, result_folder=None, select_subtype=None,
                    device="cuda:0", **_):
     """Write ``<name>_annotated_output.avi`` (``<subtype>_subtype_<name>_annotated_output.avi`` with ``select_subtype``)
     into ``result_folder``: the video with every track's id and centroid painted into the frames of the table ``df`` (the
     first element of ``evaluate_tracks``' result, or the path of an ``*_analysed.csv``) -- green, orange where the track is
     not moving, white with a larger dot at turn points.  Returns the path of the file, None after any failure (logged on
-    'ysmr', never raised).  Optional settings key 'hip frames per batch' overrides the batch size."""
+    'ysmr', never raised).  Optional settings keys: 'hip frames per batch' overrides the batch size; 'hip video jpeg
+    quality' (1 .. 100, default 90) is the quality of a Motion-JPEG file (``output_format`` says when one is written;
+    the free space is then checked batch by batch, against the bytes about to be written)."""
     import pandas as pd
     import torch
     logger = logging.getLogger("ysmr").getChild(__name__)
@@ -292,17 +528,38 @@ def annotate_video(video_path, df, output_save=True, settings=None, result_folde
             select_subtype = subtype_code(select_subtype)
             name = "{}_subtype_{}_annotated_output.avi".format(SUBTYPES[select_subtype], filename)
         output_video_name = os.path.join(result_folder, name)
-        asked_ext = str(settings.get("save video file extension") or "")
-        asked_codec = str(settings.get("save video fourcc codec") or "")
-        if asked_ext.lower() != ".avi" or asked_codec.upper() not in _RAW_CODECS:
-            logger.warning("'save video file extension' = {!r} / 'save video fourcc codec' = {!r}: the HIP path has no encoder; "
-                           "writing an uncompressed 24-bit AVI instead: {}".format(asked_ext, asked_codec, output_video_name))
+        try:
+            fmt, quality, warning = output_format(settings)
+        except ValueError as exc:
+            logger.critical(str(exc))
+            return None
+        if warning:
+            logger.warning("{}: {}".format(warning, output_video_name))
         held = getattr(video, "frames_available", video.frame_count)
         n_frames = int(held if held < (1 << 60) else video.frame_count)
         if n_frames <= 0:
             logger.critical("Error during cap.read() with file {}".format(video_path))
             return None
         height, width, channels = video.height, video.width, video.channels
+        if fmt == "mjpeg":
+            marks, first = build_marks(df, n_frames, select_subtype)
+            writer = MjpegAviWriter(output_video_name, width, height, fps_of_file)
+            logger.info("Annotated video {}: {} frames of {} x {}, Motion-JPEG, quality {}".format(
+                output_video_name, n_frames, width, height, quality))
+            done = _mjpeg_frames(video, writer, marks, first, n_frames, quality, settings, result_folder, torch.device(device), logger)
+            if done is None:
+                return None
+            frame_count = video.frame_count
+            if done not in (frame_count, frame_count - 1):
+                logger.critical("Error during cap.read() with file {}".format(video_path))
+            else:
+                logger.debug("Frames from file {} read.".format(os.path.basename(video_path)))
+            writer.close()
+            writer = None
+            written, raw = os.path.getsize(output_video_name), AviWriter.file_bytes(width, height, done)
+            logger.info("Output video file: {}: {:.1f} MiB written, {:.3f} of the {:.1f} MiB of the uncompressed AVI".format(
+                output_video_name, written / 2 ** 20, written / raw, raw / 2 ** 20))
+            return output_video_name
         expected = AviWriter.file_bytes(width, height, n_frames)
         logger.info("Annotated video {}: {} frames of {} x {}, {:.1f} MiB uncompressed".format(
             output_video_name, n_frames, width, height, expected / 2 ** 20))
