@@ -370,7 +370,9 @@ int ysmr_tracker_update3(ysmr_tracker *t, void *stream, const void *det_dev, int
                          int32_t *claim_col_dev, int32_t *n_before_dev, int32_t *new_cols_dev, int32_t *n_new_dev);
 
 /* The frame loop of track_bacteria for `batch` consecutive frames whose detections are already
- * on the device: det_dev f32 [batch][max_det][5], det_count_dev i32 [batch].  Rows are appended
+ * on the device: det_dev f32 [batch][max_det][5], det_count_dev i32 [batch] -- the WHOLE array, batch x max_det x 5 floats
+ * whatever the counts are: the batch link reads the box of a frame's slot 0 for lanes that claim nothing, also where the
+ * frame's count is 0, and uses nothing of it.  Rows are appended
  * to rows_dev (capacity rows_capacity) starting at *row_count_dev, which is advanced; rows of a
  * frame are contiguous and in ascending id order.  Overflow sets *row_count_dev past capacity
  * (rows beyond capacity are dropped); the host checks after synchronising. */

@@ -35,7 +35,7 @@
 //                after them.  The sums are recomputed from the ring, exactly, in every frame whose NUMBER is a multiple of
 //                BL_REFRESH = 64 (not at the start of a launch: the rows must not depend on how the frames were batched),
 //                so rounding drift is bounded by 64 updates: ~1e-11 px, the size of a from-scratch sum's own rounding.
-//   rows         one 40-byte ysmr_row per live lane at rows[base + rank], fire and forget.
+//   rows         one 40-byte ysmr_row per live lane at rows[base + rank] (k_batch: rowp[rank]), fire and forget.
 //
 // One workgroup barrier per frame, behind the atomic round of the claims: the ranks, the row and the counts of a frame --
 // all that needs every wave to be past the frame's ageing -- are settled behind the NEXT frame's barrier, and a wave goes
@@ -303,7 +303,7 @@ struct BlSeat {
     bool alive;
 };
 // rest format, seat-major: f64 [BL_SF64][seat_cap] = w, xa, xb, px, py, the twelve window sums; f32 [3][seat_cap];
-// i32 [6][seat_cap] = id, gone, history length, mode, rank, alive; ring double2 [BL_HB][seat_cap]
+// i32 [6][seat_cap] = id, gone, history length, mode, rank, alive; ring double2 [BL_HB + 1][seat_cap] (the last line: zeros, never stored to)
 
 __device__ __forceinline__ void bl_seat_blank(BlSeat &S)
 {
@@ -358,6 +358,15 @@ __device__ __forceinline__ void bl_seat_store(const BlSeat &S, const BatchDev &b
 __device__ __forceinline__ double2 bl_ring_load(const BatchDev &bd, int pos, int seat)
 {
     const double *p = reinterpret_cast<const double *>(bd.ring + (size_t)pos * bd.seat_cap + seat);
+    double2 v;
+    v.x = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    v.y = __hip_atomic_load(p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return v;
+}
+// (the same by its byte offset in the ring, 32 bits: a uniform base and a lane's offset, one address computation)
+__device__ __forceinline__ double2 bl_ring_load_bytes(const BatchDev &bd, unsigned at)
+{
+    const double *p = reinterpret_cast<const double *>(reinterpret_cast<const char *>(bd.ring) + at);
     double2 v;
     v.x = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     v.y = __hip_atomic_load(p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -471,10 +480,11 @@ __device__ __forceinline__ void bl_gsff(BlSeat &S, const TrackerDev &t, const Ar
             }
             for (int a = 0; a < n0; ++a) bl_ring_store(bd, (head - 1 - a) & (BL_HB - 1), seat, z0, z1);
             len = n0;
-            if (GATED) {     // what leaves a window that these copies fill is a copy
+            if (GATED) {     // what leaves a window that these copies fill is a copy; nothing leaves the others (the caller
+                             // requested nothing for a lane that held no track then: leave[] is unset on entry)
 #pragma unroll
                 for (int f = 0; f < BL_NF; ++f)
-                    if (len >= n_i[f]) leave[f] = make_double2(z0, z1);
+                    leave[f] = len >= n_i[f] ? make_double2(z0, z1) : make_double2(0.0, 0.0);
             }
         }
         bool grew = false;   // gsff.py:283-289: while len(history) >= n_i[mode]: mode += 1
@@ -862,6 +872,8 @@ struct BlShared {      // static part of the LDS
     int wave_cnt[2][BL_WAVES];       // registration: per-wave counts of the two ranked lists
     int set_state[2];
     int top;                         // one past the highest seat ever taken
+    long long rows_then;             // k_batch: the row count at the start of the launch plus the room it found (thread 0's,
+                                     // for the end of the launch; in the padding of the 16-byte rounding: bl_lds_total is what it was)
 };
 
 __host__ __device__ inline int bl_md_padded(int max_det) { return (max_det + 3) / 4 * 4; }
@@ -919,24 +931,15 @@ __device__ __forceinline__ void bl_wait_vmem() { __builtin_amdgcn_s_waitcnt(0x0F
 // reached by every wave on every path from its load (none under a test of `alive`).  (An access the compiler does not know of only makes its own
 // lgkmcnt(N) waits stricter: LDS returns in order, so "at most N open" still covers every older LDS access.)
 typedef uint32_t bl_u32x4 __attribute__((ext_vector_type(4)));
-struct BlRowArgs { ysmr_row *rows; long long rows_capacity; };
 struct BlSearchArgs { const float *det_all; int hz[BL_NF]; };
-static_assert(__builtin_offsetof(BlKernArgs, rows_capacity) == __builtin_offsetof(BlKernArgs, rows) + 8, "one s_load_dwordx4: rows, rows_capacity");
-// rows, rows_capacity: what the row behind barrier A needs, in one load
-__device__ __forceinline__ bl_u32x4 bl_row_args_issue(BlKernArgsPtr kp)
+// The rows a buffer of `capacity` still takes behind `base`, in 32 bits.  A launch writes fewer than 2^20 rows (BL_MAX_BATCH
+// frames of at most BL_THREADS), so the clamps are never reached by counting down: above INT_MAX everything fits, and a
+// buffer that is already overrun (base > capacity: the count goes on past the capacity) takes nothing -- -1, not 0: an
+// empty frame fits a full buffer, and does not fit an overrun one (base + 0 > capacity).
+__device__ __forceinline__ int bl_room(long long capacity, long long base)
 {
-    bl_u32x4 v;
-    asm volatile("s_load_dwordx4 %0, %1, %2" : "=&s"(v) : "s"(kp), "i"(__builtin_offsetof(BlKernArgs, rows)) : "memory");
-    return v;
-}
-__device__ __forceinline__ BlRowArgs bl_row_args_wait(bl_u32x4 v)
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(v) :: "memory");
-    BlRowArgs a;
-    // (through the GLOBAL address space: a pointer made from an integer is generic, and the row would leave with flat_store)
-    a.rows = (ysmr_row *)(__attribute__((address_space(1))) ysmr_row *)(((unsigned long long)v[1] << 32) | v[0]);
-    a.rows_capacity = (long long)(((unsigned long long)v[3] << 32) | v[2]);
-    return a;
+    const long long left = capacity - base;
+    return left > 0x7FFFFFFFll ? 0x7FFFFFFF : (left < 0 ? -1 : (int)left);
 }
 // the pointer to the gains: requested behind the row, taken in front of the filter bank (behind the frame's vmcnt(0))
 __device__ __forceinline__ unsigned long long bl_gains_issue(BlKernArgsPtr kp)
@@ -997,13 +1000,21 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
 
     // ---- start of the batch: counters, this lane's track, the first frame's detections
     int n = *t.n_tracks, next_id = *t.next_id, head = *bd.head & (BL_HB - 1);
-    long long base = *row_count;
+    // The rows of the launch: `rowp`, where the next frame's row of rank 0 goes, and `room`, the rows the buffer still
+    // takes, in 32 bits (bl_room) -- a frame's capacity decision is then ONE scalar compare, and a row's address one
+    // multiply-add on a scalar base.  The row count goes back to HBM as what it was plus what `room` lost (sh.rows_then).
+    ysmr_row *rowp = ka.rows + *row_count;
+    int room = bl_room(ka.rows_capacity, *row_count);
+    if (tid == 0) sh.rows_then = *row_count + room;
     for (int f = tid; f < batch; f += BL_THREADS) {
         int m = det_count[f];
         if (m > md) { m = md; atomicOr(t.err, ERR_DET_CLAMPED); }
         sh.cnt[f] = m < 0 ? 0 : m;
     }
     if (tid < 2) { sh.used[tid] = 0; sh.n_dead[tid] = 0; sh.tie[tid] = -1; }
+    // (column 0 of every key table holds a key or all ones from the first frame on, also in frames without detections,
+    // whose tables nobody clears: a lane that proposes nothing reads it and compares it with a key no table holds)
+    if (tid < 3) key_at(tid)[0] = ~0ull;
     if (tid == 0) sh.top = 0;
     BlSeat S;
     bl_seat_blank(S);
@@ -1080,7 +1091,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
     double o0 = 0.0, o1 = 0.0;       // the filter bank's outputs: a frame's row leaves behind the next frame's barrier A
     // ranks, row and counts of frame `fr`, whose deaths were counted in sh.n_dead[slot] from `start` on; behind the barrier
     // that follows the frame's ageing.  Returns the running count.
-    auto settle = [&](int slot, int start, int fr, bool row, const BlRowArgs &ra) {
+    auto settle = [&](int slot, int start, int fr, bool row) {
         const int total = sh.n_dead[slot];
         const int n_dead = total - start;
 #ifdef YSMR_STAMPS
@@ -1090,19 +1101,23 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
             for (int k = 0; k < n_dead; ++k) S.rank -= sh.dead_id[slot][k] < S.id;
         n -= n_dead;
         if (row) {
-            ysmr_row *rows = ra.rows;
-            const long long rows_capacity = ra.rows_capacity;
-            if (S.alive && base + S.rank < rows_capacity) {      // track_eval.py:313-316
+            // Every live lane has rank < n, so a frame whose n rows fit decides nothing per lane; the frame that does not
+            // fit is the one that raises ERR_ROWS_CAPACITY, and only it compares ranks (rank < room: base + rank < capacity).
+            bool fits = S.alive;
+            if (n > room) {
+                fits = S.alive && S.rank < room;
+                if (tid == 0) atomicOr(bl_kernargs()->t.err, ERR_ROWS_CAPACITY);
+            }
+            if (fits) {      // track_eval.py:313-316
                 ysmr_row rr;
                 rr.frame = frame0 + fr;
                 rr.track_id = S.id;
                 rr.x = o0; rr.y = o1;
                 rr.w = S.info[0]; rr.h = S.info[1]; rr.angle = S.info[2];
                 rr.disappeared = S.gone;
-                rows[base + S.rank] = rr;
+                rowp[S.rank] = rr;
             }
-            if (tid == 0 && base + n > rows_capacity) atomicOr(bl_kernargs()->t.err, ERR_ROWS_CAPACITY);
-            base += n;
+            rowp += n; room -= n;
         }
         return total;
     };
@@ -1114,7 +1129,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
     float4 hdr_cur = bl_grid_header(buf_off(0));
     for (int f = 0; f < batch; ++f) {
         const int par = f & 1;
-        const int kn = kc == 2 ? 0 : kc + 1, ks = kc == 0 ? 2 : kc - 1;      // the tables of frame f + 1, and of f + 2 = f - 1
+        const int kn = kc == 2 ? 0 : kc + 1, ks = 3 - kc - kn;      // the tables of frame f + 1, and of f + 2 = f - 1 (the third of 0, 1, 2)
         const int m = __builtin_amdgcn_readfirstlane(mv_cur);
         BLSTAMP(0);
 #ifdef YSMR_STAMPS
@@ -1137,7 +1152,9 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         const bool propose = S.alive && m > 0;
         const BlGridView gv = bl_grid_view(buf_off(par), m, hdr_cur);
         BlNear nr{0.0, 0.f, 0.f, 0, true};
-        unsigned long long key = 0;
+        // (a lane that proposes nothing: a key no column can hold -- a squared distance has no sign bit, an empty column is
+        // all ones -- so that `the column's winner is my key` needs no `and I proposed`)
+        unsigned long long key = 1ull << 63;
         if (propose) nr = bl_search(gv, S.px, S.py, m);
 #ifdef YSMR_STAMPS
         {   // (bl_search's test for the candidate list, repeated)
@@ -1203,19 +1220,25 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         // youngest in flight where the filter bank waits for the leaving measurements, and the wait for those -- counted
         // in order -- would wait for it as well, a round trip to HBM a few dozen instructions old.
         const BlSearchArgs sa = bl_search_args_wait(sa_det, sa_hz);
-        float bx[3] = {0.f, 0.f, 0.f};
-        if (propose) {
+        // (every lane asks: a lane that proposed nothing has column 0, whose five floats lie inside frame f's block of
+        // det_all whatever the frame holds, and uses nothing of it -- `mine` implies `propose`.  No exec region, no zeros.)
+        float bx[3];
+        {
             // (frame and column in 32 bits -- batch x max_det detections are far below 2^32 -- then bytes in 64)
             const float *d = sa.det_all + (size_t)((unsigned)f * (unsigned)md + (unsigned)nr.col) * 5;
             bx[0] = d[2]; bx[1] = d[3]; bx[2] = d[4];
         }
+        // ONE exec region for the three filters: where a window is not full (a filter the handle lacks: hz = INT_MAX) the
+        // lane reads the ring's line of zeros, position BL_HB, which nothing ever stores to -- a select of the position,
+        // not of the value: an entry that was never written may hold anything, and bl_gsff<true> needs exactly 0.0, 0.0.
         double2 leave[BL_NF];
-#pragma unroll
-        for (int k = 0; k < BL_NF; ++k) leave[k] = make_double2(0.0, 0.0);
         if (S.alive && t.use_gsff) {
+            const unsigned line = (unsigned)bd.seat_cap * (unsigned)sizeof(double2), seat_b = (unsigned)tid * (unsigned)sizeof(double2);
 #pragma unroll
-            for (int k = 0; k < BL_NF; ++k)
-                if (S.len >= sa.hz[k]) leave[k] = bl_ring_load(bd, (head - sa.hz[k]) & (BL_HB - 1), tid);
+            for (int k = 0; k < BL_NF; ++k) {
+                const unsigned pos = S.len >= sa.hz[k] ? (unsigned)((head - sa.hz[k]) & (BL_HB - 1)) : (unsigned)BL_HB;
+                leave[k] = bl_ring_load_bytes(bd, __umul24(pos, line) + seat_b);      // (33 lines of 768 seats: 24 bits hold a line)
+            }
         }
         BLSTAMP(1);
         // (the waves that requested a grid block behind the barrier before: it has landed.  Track waves beside helper
@@ -1224,7 +1247,6 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         block_sync<true>();
         BLSTAMP(2);
         // ---- behind barrier A: every wave is past frame f - 1's ageing and registration, and past frame f's search
-        const bl_u32x4 ra_pending = bl_row_args_issue(bl_kernargs());      // (rows, rows_capacity: taken in front of the row)
         if (tid == BL_THREADS - 1) sh.used[par ^ 1] = 0;
         // (frame f + 2's count; frame f + 1's header -- past the batch's end nobody uses either, and the read stays inside
         // the kernel's own LDS)
@@ -1234,11 +1256,10 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         const unsigned long long k_won = key_at(kc)[nr.col];
         const int exact = sh.tie[par] == f;
         if (f + 2 < batch) dma(f + 2, __builtin_amdgcn_readfirstlane(c_ahead));
-        const BlRowArgs ra = bl_row_args_wait(ra_pending);
-        const int d_total = settle(par ^ 1, d_prev, f - 1, f > 0, ra);
+        const int d_total = settle(par ^ 1, d_prev, f - 1, f > 0);
         const unsigned long long gains_pending = bl_gains_issue(bl_kernargs());
         BLSTAMP(3);
-        bool mine = propose && k_won == key;
+        unsigned long long won = k_won;      // (`mine` is ONE compare behind the rare block: a vote on it is that compare's mask)
         if (exact) {
             // The exact rule, for every column of the frame (uniform: the flag was set before barrier A and stands until
             // frame f + 2 sets it again, behind A(f + 1)): the smallest s in full, then the proposers at the column's
@@ -1265,11 +1286,16 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
                 if (tie) atomicMin(&cid_at()[nr.col], (uint32_t)S.id);
             }
             block_sync<true>();
-            mine = propose && cid_at()[nr.col] == (uint32_t)S.id;
+            won = propose && cid_at()[nr.col] == (uint32_t)S.id ? key : ~key;
         }
+        const bool mine = won == key;
+        const unsigned long long bm = __ballot(mine);      // (here, beside the compare: its mask IS the vote)
         BLSTAMP(4);
         // ---- ageing and deregistration (tracker.py:95-107, 198-211)
-        const bool age = (m == 0) || (n > 0 && n >= m);
+        // (tracker.py ages when there are no detections, or when n > 0 and n >= m, and registers when m > 0 and n == 0 or
+        // n < m.  Counts are never negative, so the two are `n >= m` and `n < m`: one scalar compare, each the other's
+        // complement.)
+        const bool births = n < m, age = !births;
         double z0 = S.px, z1 = S.py;
         bool fresh = false, died = false;
         if (mine) {
@@ -1281,7 +1307,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
             if (S.gone > gone_max) { S.alive = false; died = true; }
         }
         {
-            const unsigned long long bm = __ballot(mine), bx = __ballot(died);
+            const unsigned long long bx = __ballot(died);
             if (lane == 0 && bm) atomicAdd(&sh.used[par], (int)__popcll(bm));
             if (bx) {      // the ids of the deregistered tracks: every younger track moves up one table row (settle)
                 int at = 0;
@@ -1292,7 +1318,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         }
         BLSTAMP(5);
         // ---- registration (tracker.py:135-137, 212-217): unclaimed columns become tracks, in CPython set order
-        const bool births = m > 0 && (n == 0 || n < m);        // (uniform; nobody was aged in such a frame)
+        // (`births`, above: uniform; nobody was aged in such a frame)
 #ifdef YSMR_STAMPS
         BLCOUNT(4, births);
 #endif
@@ -1414,7 +1440,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
     }
     // ---- the last frame's ranks, row and counts, behind a barrier that every wave's ageing of it has reached
     block_sync<true>();
-    settle((batch - 1) & 1, d_prev, batch - 1, true, bl_row_args_wait(bl_row_args_issue(bl_kernargs())));
+    settle((batch - 1) & 1, d_prev, batch - 1, true);
     // ---- end of the batch: the small state goes back to HBM, seat by seat
     {
         const BlKernArgsPtr ke = bl_kernargs();
@@ -1426,7 +1452,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
             S.mode = bl_mode_of(grow_at, ke->t.n_f, {ke->hz[0], ke->hz[1], ke->hz[2]});
             if (S.alive) bl_seat_store(S, be, tid);
         }
-        if (tid == 0) { *ke->t.n_tracks = n; *ke->t.next_id = next_id; *ke->row_count = base; *be.head = head; }
+        if (tid == 0) { *ke->t.n_tracks = n; *ke->t.next_id = next_id; *ke->row_count = sh.rows_then - room; *be.head = head; }
     }
 }
 

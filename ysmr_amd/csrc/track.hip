@@ -94,7 +94,9 @@ constexpr int BL_SF64 = 3 * BL_NF + 2 + 4 * BL_NF;   // w, xa, xb, px, py, the w
 constexpr int BL_REFRESH = 64;        // frames between two exact recomputations of the window sums (a power of two)
 
 struct BatchDev {
-    double2 *ring;      // [BL_HB][seat_cap]  the measurements of the last BL_HB frames, seat by seat
+    double2 *ring;      // [BL_HB + 1][seat_cap]  the measurements of the last BL_HB frames, seat by seat; position BL_HB is
+                        // a line of zeros, cleared when the handle is made and never stored to (k_batch: what leaves a window
+                        // that is not full)
     double *f64;        // [BL_SF64][seat_cap]
     float *f32;         // [3][seat_cap]      box of the last claimed detection (0 while lost)
     int *i32;           // [6][seat_cap]      id, gone, history length, mode, table row, seat taken
@@ -2256,7 +2258,8 @@ int ysmr_tracker_create(double max_disappeared, double fps, int n_min, double n_
     const size_t o_rmin1 = take(sizeof(double) * cap), o_rarg1 = take(sizeof(int) * cap);
     // the batch link's rest format (seat-major) and its gain table
     const size_t seat_cap = capacity > BL_THREADS ? (size_t)capacity : (size_t)BL_THREADS;     // (k_batch: 768 seats; k_track_lanes: a seat per slot)
-    const size_t o_ring = take(sizeof(double2) * BL_HB * seat_cap);
+    // (BL_HB positions and the line of zeros behind them: cleared with the block below; every store indexes 0 .. BL_HB - 1)
+    const size_t o_ring = take(sizeof(double2) * (BL_HB + 1) * seat_cap);
     const size_t o_b64 = take(sizeof(double) * BL_SF64 * seat_cap), o_b32 = take(sizeof(float) * 3 * seat_cap);
     const size_t o_bi = take(sizeof(int) * 6 * seat_cap);
     t->block_bytes = off;
@@ -2521,6 +2524,35 @@ int ysmr_debug_read_bcounts(unsigned long long *out) { return (int)hipMemcpyFrom
 #endif
 
 int ysmr_tracker_batched(ysmr_tracker *t) { return t && t->use_batch() ? 1 : 0; }
+
+// Test hooks for the ring (tests/test_gpu_batch_bookkeeping.py; not part of the ABI the host code binds).  _poison: every
+// entry of positions 0 .. BL_HB - 1 becomes a NaN bit pattern (all ones) -- refused once the handle has registered a track: whatever a
+// filter bank then sums that its own frames did not store shows in the rows.  _zero_line: the non-zero 64-bit words of
+// position BL_HB, the line of zeros (read-only).  Both wait for the device before and after.
+int ysmr_debug_ring_poison(ysmr_tracker *t)
+{
+    if (!t) return ysmr::fail(YSMR_ERR_ARG, "tracker handle is NULL");
+    hipError_t e = hipDeviceSynchronize();
+    int seen[2] = {0, 0};      // (live tracks, next id: a handle that has registered a track keeps its ring)
+    if (e == hipSuccess) e = hipMemcpy(seen, t->cur().n_tracks, sizeof(seen), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && (seen[0] != 0 || seen[1] != 0))
+        return ysmr::fail(YSMR_ERR_ARG, "ysmr_debug_ring_poison is for a handle that has held no track yet");
+    if (e == hipSuccess) e = hipMemset(t->bd.ring, 0xFF, sizeof(double2) * BL_HB * (size_t)t->bd.seat_cap);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    return e == hipSuccess ? YSMR_OK : ysmr::fail(YSMR_ERR_HIP, "ring poison failed: %s", hipGetErrorString(e));
+}
+int ysmr_debug_ring_zero_line(ysmr_tracker *t, long long *nonzero)
+{
+    if (!t || !nonzero) return ysmr::fail(YSMR_ERR_ARG, "tracker handle and nonzero must be set");
+    std::vector<unsigned long long> line(2 * (size_t)t->bd.seat_cap);
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess)
+        e = hipMemcpy(line.data(), t->bd.ring + (size_t)BL_HB * t->bd.seat_cap, sizeof(double2) * (size_t)t->bd.seat_cap, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return ysmr::fail(YSMR_ERR_HIP, "ring read failed: %s", hipGetErrorString(e));
+    *nonzero = 0;
+    for (unsigned long long w : line) *nonzero += w != 0;
+    return YSMR_OK;
+}
 
 int ysmr_tracker_prepare(ysmr_tracker *t, void *stream, const float *det_dev, const int32_t *det_count_dev, int batch, int slot)
 {
