@@ -30,6 +30,8 @@
  *   ysmr_select_tracks    select_tracks + find_good_tracks   ysmr/track_eval.py:408-843
  *   ysmr_evaluate_tracks  evaluate_tracks (statistics, not the plots)  ysmr/track_eval.py:846-1318
  *   ysmr_plot_*           large_xy_plot, rose_graph, angle_distribution_plot   ysmr/plot_functions.py:29-257
+ *   ysmr_violin_*,        violin_plot and the categories of evaluate_tracks    ysmr/plot_functions.py:260-370,
+ *   ysmr_plot_violins                                                          ysmr/track_eval.py:1151-1303
  *   ysmr_rows_columns,    save_list text + get_data (pandas.read_csv) + save_df_to_csv
  *   ysmr_rows_format_csv  ysmr/helper_file.py:1403-1478, 860-905, 1366-1400  (host functions)
  */
@@ -49,7 +51,7 @@ extern "C" {
 #define YSMR_ERR_CAPACITY  3   /* a fixed-capacity buffer would overflow (tracks, workspace) */
 #define YSMR_ERR_STATE     4   /* handle used in the wrong state */
 
-/* 15 still: ysmr_annotate_batch with its mark struct, and later the ysmr_plot_* and ysmr_mjpeg_* functions, were ADDED under this number
+/* 15 still: ysmr_annotate_batch with its mark struct, and later the ysmr_plot_*, ysmr_mjpeg_* and ysmr_violin_* functions, were ADDED under this number
  * -- no existing entry point, struct or constant changed, so every caller written against 15 keeps working; only a caller
  * of a new function needs a library that has it (the loader reports a missing symbol by name). */
 #define YSMR_ABI_VERSION   15
@@ -655,6 +657,70 @@ int ysmr_plot_angle_histogram(void *stream, long long n_rows, const uint32_t *tr
  * ring_r2 that have a 4-neighbour beyond it.  Everything else white.  rgb_dev as above. */
 int ysmr_plot_wedges(void *stream, int width, int height, int cx, int cy, int n_bins, const double *dirs_dev,
                      const long long *r2_dev, long long ring_r2, uint8_t *rgb_dev);
+
+/* ---- the violin plots of evaluate_tracks: violin_plot, ysmr/plot_functions.py:260-370, track_eval.py:1151-1303 ---- */
+
+/* ADDED under ABI 15 as well.  A figure shows one value column of the per-track statistics, split by a cut column:
+ * violin 0 is 'All', violin k + 1 the half-open interval [lo[k], hi[k]) of the cut column.  A track belongs to violin 0
+ * and to at most one other: the LAST k with lo[k] <= c and c < hi[k] in f64 (upstream's loop overwrites); a NaN c
+ * belongs to none.  Seaborn's violinplot(cut=0, bw=.2, gridsize=100, scale='count', width=.95) is what is computed. */
+#define YSMR_VIOLIN_GRID      100   /* density points per violin */
+#define YSMR_VIOLIN_MAX_CUTS  254   /* intervals of one call of the statistics */
+#define YSMR_VIOLIN_MAX_SLOTS 64    /* violins of one painted figure */
+
+typedef struct ysmr_violin_summary {
+    long long members;           /* tracks in the category */
+    long long values;            /* ... whose value is finite: only these count below.  0: every field below is 0 */
+    double    vmin, vmax;
+    double    q25, q50, q75;     /* NumPy's linear rule: pos = q (n - 1), lo = floor(pos), t = pos - lo, a = x[lo], b = x[lo + 1]:
+                                    a + (b - a) t when t < 0.5, else b - (b - a) (1 - t) */
+    double    whisker_lo, whisker_hi;   /* the smallest value >= q25 - 1.5 (q75 - q25), the largest <= q75 + 1.5 (q75 - q25) */
+    double    mean;              /* sum / n, the sum in a fixed order (lanes striding by 256, then a tree) */
+    double    h;                 /* 0.2 * sqrt(sum (x - mean)^2 / (n - 1)); 0 when n < 2 */
+} ysmr_violin_summary;
+
+/* The scratch of either call below (0: sizes out of range); ax_h may be 0 for the statistics alone. */
+size_t ysmr_violin_workspace_bytes(long long n_tracks, int n_violins, int ax_h);
+
+/* cut_dev[t * cut_stride], value_dev[t * value_stride], t < n_tracks (columns of the [tracks][12] statistics: stride 12);
+ * lo_dev, hi_dev: n_cuts doubles.  Writes summaries_dev[n_cuts + 1] and density_dev[n_cuts + 1][YSMR_VIOLIN_GRID]:
+ *   d_j = (1 / (n h sqrt(2 pi))) * sum_i exp(-0.5 ((g_j - x_i) / h)^2),  g_j = vmin + j (vmax - vmin) / 99, g_99 = vmax
+ * (the difference before the division; one workgroup per (violin, j), the sum in the fixed order of the mean over the
+ * SORTED values).  A violin with values < 2 or h == 0 has no density: zeros.  No floating-point atomics: two calls
+ * give the same bytes.  0 <= n_tracks <= 2^30, 0 <= n_cuts <= YSMR_VIOLIN_MAX_CUTS. */
+int ysmr_violin_stats(void *stream, long long n_tracks, const double *cut_dev, long long cut_stride, const double *value_dev,
+                      long long value_stride, int n_cuts, const double *lo_dev, const double *hi_dev, void *workspace_dev,
+                      size_t workspace_bytes, ysmr_violin_summary *summaries_dev, double *density_dev);
+
+typedef struct ysmr_violin_view {
+    double  y0;                  /* data value at the lower edge of the axes */
+    double  units_per_pixel;
+    int32_t width, height;       /* the canvas */
+    int32_t ax_x, ax_y, ax_w, ax_h;   /* the axes rectangle (top-left pixel, size), inside the canvas */
+    int32_t n_violins;           /* 1 .. YSMR_VIOLIN_MAX_SLOTS: entries of the arrays below and of summaries / density */
+    int32_t n_grid_rows;
+    int32_t line_half;           /* half widths (pixels) of the whisker line and of a degenerate violin's line */
+    int32_t box_half;            /* ... of the quartile box */
+    int32_t dot_r2;              /* squared radius of the median dot */
+    int32_t reserved;
+    int32_t grid_rows[32];       /* canvas rows of the grid lines (drawn inside the axes only) */
+    int32_t slot_x[64];          /* canvas column of the slot's left edge */
+    int32_t slot_w[64];          /* its width; 0: the violin is not drawn.  Slots lie inside the axes and do not overlap */
+    int32_t slot_colour[64];     /* position of the violin in the figure: entry (position mod 10) of the fill table */
+} ysmr_violin_view;
+
+/* Paints rgb_dev: u8 [height][width][3].  Two steps ("The figures"):
+ * profile -- axes row r (0 on top) has the data value y = y0 + ((ax_h - 1 - r) + 0.5) units_per_pixel; inside [vmin, vmax] the
+ *   density is interpolated between its grid neighbours, d = d_j + (d_{j+1} - d_j) t (f64, unfused), and
+ *   half = floor(d / peak * values / max_values * 0.95 * slot_w / 2), peak = max_j d_j, max_values the largest `values` of the
+ *   drawn violins; -1 outside [vmin, vmax].  A value v lies on axes row ax_h - 1 - floor((v - y0) / units_per_pixel);
+ * paint -- integers only, every pixel a function of (x, y); layers from the bottom: white, grid rows (176, 176, 176), the
+ *   fill |x - cx| <= half (cx = slot_x + slot_w / 2), its outline (fill pixels with a 4-neighbour that is not fill; (76, 76, 76)),
+ *   the whisker line, the quartile box (both (76, 76, 76)), the white median dot, and black left and bottom spines just
+ *   outside the axes.  A violin with values == 1 or h == 0 is a horizontal line of half length slot_w * 95 / 200 at its value;
+ *   one with values == 0 is not drawn.  A violin paints inside its slot and inside the axes only. */
+int ysmr_plot_violins(void *stream, int n_violins, const ysmr_violin_summary *summaries_dev, const double *density_dev,
+                      const ysmr_violin_view *view, void *workspace_dev, size_t workspace_bytes, uint8_t *rgb_dev);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,7 @@
 
 The public surface mirrors the reference package (``ysmr/__init__.py`` re-exports ``main``,
 ``plot_functions``, ``track_eval``): ``ysmr()``, ``analyse()``, ``track_bacteria()``,
-``select_tracks()``, ``evaluate_tracks()``, ``annotate_video()``, the three figures of ``plot_functions``, ``CentroidTracker``, ``GaussianSumFIR`` and the tracking.ini helpers.  Importing this package does
+``select_tracks()``, ``evaluate_tracks()``, ``annotate_video()``, the figures of ``plot_functions`` (``violin_plot`` as ``ysmr_amd.plot_functions.violin_plot``), ``CentroidTracker``, ``GaussianSumFIR`` and the tracking.ini helpers.  Importing this package does
 not touch the GPU; the HIP library (``csrc/libysmr_hip.so``) is loaded on first use and there is no
 CPU fallback.
 """

@@ -62,7 +62,7 @@ EXPORTS = ("ysmr_abi_version", "ysmr_last_error", "ysmr_detect_workspace_bytes",
            "ysmr_luminosity_batch", "ysmr_luminosity_batch_host", "ysmr_tracker_dimensions", "ysmr_tracker_update3",
            "ysmr_tracker_run3", "ysmr_tracker_peek3", "ysmr_tracker_prepare3", "ysmr_annotate_batch", "ysmr_plot_colormap",
            "ysmr_plot_extent", "ysmr_plot_workspace_bytes", "ysmr_plot_tracks", "ysmr_plot_angle_histogram", "ysmr_plot_wedges",
-           "ysmr_mjpeg_workspace_bytes", "ysmr_mjpeg_batch")
+           "ysmr_mjpeg_workspace_bytes", "ysmr_mjpeg_batch", "ysmr_violin_workspace_bytes", "ysmr_violin_stats", "ysmr_plot_violins")
 
 #: numpy view of ``ysmr_mark`` (16 bytes): one track position of one frame of the annotated video
 MARK_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("track_id", "<u4"), ("style", "<u4")])
@@ -102,6 +102,22 @@ class PlotView(ctypes.Structure):
                [(k, ctypes.c_int32) for k in ("mode", "width", "height", "ax_x", "ax_y", "ax_w", "ax_h", "r2_dot", "r2_start",
                                               "n_grid_cols", "n_grid_rows", "bar_x", "bar_y", "bar_w", "bar_h")] + \
                [("grid_cols", ctypes.c_int32 * 32), ("grid_rows", ctypes.c_int32 * 32)]
+
+
+VIOLIN_GRID, VIOLIN_MAX_CUTS, VIOLIN_MAX_SLOTS = 100, 254, 64
+
+#: numpy view of ``struct ysmr_violin_summary`` (88 bytes)
+VIOLIN_SUMMARY_DTYPE = np.dtype([("members", "<i8"), ("values", "<i8")] + [(k, "<f8") for k in (
+    "vmin", "vmax", "q25", "q50", "q75", "whisker_lo", "whisker_hi", "mean", "h")])
+
+
+class ViolinView(ctypes.Structure):
+    """``struct ysmr_violin_view``"""
+    _fields_ = [("y0", ctypes.c_double), ("units_per_pixel", ctypes.c_double)] + \
+               [(k, ctypes.c_int32) for k in ("width", "height", "ax_x", "ax_y", "ax_w", "ax_h", "n_violins", "n_grid_rows",
+                                              "line_half", "box_half", "dot_r2", "reserved")] + \
+               [("grid_rows", ctypes.c_int32 * 32), ("slot_x", ctypes.c_int32 * 64), ("slot_w", ctypes.c_int32 * 64),
+                ("slot_colour", ctypes.c_int32 * 64)]
 
 
 class YsmrLibraryError(RuntimeError):
@@ -215,8 +231,12 @@ def lib():
     L.ysmr_mjpeg_workspace_bytes.argtypes = [ci, ci, ci]
     L.ysmr_mjpeg_workspace_bytes.restype = ctypes.c_size_t
     L.ysmr_mjpeg_batch.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.c_size_t, ci, ci, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp]
+    L.ysmr_violin_workspace_bytes.argtypes = [ll, ci, ci]
+    L.ysmr_violin_workspace_bytes.restype = ctypes.c_size_t
+    L.ysmr_violin_stats.argtypes = [vp, ll, vp, ll, vp, ll, ci, vp, vp, vp, ctypes.c_size_t, vp, vp]
+    L.ysmr_plot_violins.argtypes = [vp, ci, vp, vp, ctypes.POINTER(ViolinView), vp, ctypes.c_size_t, vp]
     for name in EXPORTS:
-        if name not in ("ysmr_mjpeg_workspace_bytes", "ysmr_plot_workspace_bytes", "ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
+        if name not in ("ysmr_violin_workspace_bytes", "ysmr_mjpeg_workspace_bytes", "ysmr_plot_workspace_bytes", "ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
                         "ysmr_rows_sort_workspace_bytes", "ysmr_rows_csv_bound", "ysmr_rows_stream_count",
                         "ysmr_mean_threshold_state_bytes"):
             getattr(L, name).restype = ci

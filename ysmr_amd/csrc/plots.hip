@@ -34,19 +34,11 @@ __device__ __forceinline__ long long gtid() { return (long long)blockIdx.x * blo
 __device__ __forceinline__ long long gstride() { return (long long)gridDim.x * blockDim.x; }
 inline unsigned pl_grid(long long items) { return (unsigned)std::max(1ll, std::min<long long>((items + 255) / 256, PL_BLOCKS)); }
 
-// doubles as u64 keys of the same order (-inf < ... < -0 < +0 < ... < +inf): min and max become integer atomics
-__device__ __forceinline__ unsigned long long key_of(double v)
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : b | 0x8000000000000000ull;
-}
-__device__ __forceinline__ double value_of(unsigned long long k)
-{
-    return __longlong_as_double((long long)((k >> 63) ? k & 0x7FFFFFFFFFFFFFFFull : ~k));
-}
+using ysmr::prim::key_of;      // doubles as u64 keys of the same order: min and max become integer atomics
+using ysmr::prim::value_of;
+using ysmr::prim::finite64;
 constexpr unsigned long long KEY_POS_INF = 0xFFF0000000000000ull;   // key_of(+inf)
 constexpr unsigned long long KEY_NEG_INF = 0x000FFFFFFFFFFFFFull;   // key_of(-inf)
-__device__ __forceinline__ bool finite64(double v) { return (__double_as_longlong(v) & 0x7FF0000000000000ll) != 0x7FF0000000000000ll; }
 
 // first / last row of the run of equal ids that holds row i (binary search: "same id" is monotone on either side)
 __device__ __forceinline__ long long run_first(const uint32_t *__restrict__ id, long long i)

@@ -22,6 +22,20 @@
 namespace ysmr {
 namespace prim {
 
+// ---- doubles as ordered integers ------------------------------------------------------------------------
+// u64 keys of the same order as the doubles (-inf < ... < -0 < +0 < ... < +inf; NaNs beyond the infinities): min and max
+// become integer atomics (plots.hip), a sort by value a radix sort (violin.hip)
+__device__ __forceinline__ unsigned long long key_of(double v)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b >> 63) ? ~b : b | 0x8000000000000000ull;
+}
+__device__ __forceinline__ double value_of(unsigned long long k)
+{
+    return __longlong_as_double((long long)((k >> 63) ? k & 0x7FFFFFFFFFFFFFFFull : ~k));
+}
+__device__ __forceinline__ bool finite64(double v) { return (__double_as_longlong(v) & 0x7FF0000000000000ll) != 0x7FF0000000000000ll; }
+
 constexpr int SCAN_ITEMS = 8;                       // per thread
 constexpr int SCAN_TILE = 256 * SCAN_ITEMS;
 constexpr int RADIX_ROUNDS = 8;                     // keys per thread

@@ -4,8 +4,9 @@ Host mirror of the reference's function (ysmr/track_eval.py:846-1318): same sign
 log lines, same result files (``<name>_statistics.csv``, ``<name>_analysed.csv``, written with the reference's own
 ``DataFrame.to_csv`` call) and the same return value ``(df, df_stats)``.  Everything numerical happens in
 ``ysmr_evaluate_tracks`` (``csrc/evaluate.hip``).  The overview, the rose graph and the angle histogram are painted
-on the device (``plot_functions``, ``csrc/plots.hip``) under the reference's settings and file names; the violin
-plots (seaborn figures) are not part of the HIP path: settings that ask for them are noted in the log and skipped.
+on the device (``plot_functions``, ``csrc/plots.hip``) under the reference's settings and file names.  The violin
+plots (seaborn figures upstream) are drawn by ``plot_functions.violin_plot`` (``csrc/violin.hip``) when the settings
+hold a true 'hip violin plots'; without that key the settings that ask for them are noted in the log and skipped.
 """
 from __future__ import annotations
 
@@ -25,10 +26,32 @@ STATS_COLUMNS = ["Turn Points (TP/s)", "Distance (µm)", "Speed (µm/s)", "Time 
                  "Motility Phenotype", "TRACK_ID", "Median Speed"]
 ROW_COLUMNS = ["TRACK_ID", "POSITION_T", "POSITION_X", "POSITION_Y", "WIDTH", "HEIGHT", "DEGREES_ANGLE", "angle_diff",
                "moving", "turn_points", "tp_of_tracks", "travelled_dist", "motility_phenotype"]
-#: figures this package does not draw
+#: figures drawn only under 'hip violin plots'
 _SKIPPED_PLOT_KEYS = ("save time violin plot", "save acr violin plot", "save length violin plot",
                       "save turning point violin plot", "save speed violin plot", "save displacement violin plot",
                       "save percent motile plot")
+
+
+#: upstream's violin figures in its order (track_eval.py:1237-1290): settings key, column, file name, keys of the y limits
+VIOLIN_FIGURES = (("save turning point violin plot", 0, "turning_points", "turning point violin plot"),
+                  ("save length violin plot", 1, "distance", "length violin plot"),
+                  ("save speed violin plot", 2, "speed", "speed violin plot"),
+                  ("save time violin plot", 3, "time_plot", "time violin plot"),
+                  ("save displacement violin plot", 4, "displacement", "displacement violin plot"),
+                  ("save percent motile plot", 5, "perc_motile", "percent motile plot"),
+                  ("save acr violin plot", 6, "arc-chord_ratio", "acr violin plot"))
+
+
+def violin_cut_list(parameter, splits):
+    """The (low, high, name) triples of the violins (track_eval.py:1164-1179): 'All' in front, then the consecutive pairs
+    of 'split violin plots on' -- or the three phenotypes when the tracks are split by 'Motility Phenotype'."""
+    if parameter == STATS_COLUMNS[5]:
+        cuts = [(a, b, "{:.1f}% - {:.1f}%".format(a, b)) for a, b in zip(splits[:-1], splits[1:])]
+    elif parameter == STATS_COLUMNS[9]:
+        cuts = [(0, 0.001, "Immotile"), (1, 1.001, "Twitching"), (2, 2.001, "Motile")]
+    else:
+        cuts = [(a, b, "{:.2f} - {:.2f}".format(a, b)) for a, b in zip(splits[:-1], splits[1:])]
+    return [(-np.inf, np.inf, "All")] + cuts
 
 
 def plot_title(file_name):
@@ -47,8 +70,8 @@ def plot_title(file_name):
     return title
 
 
-def _figures(out, stats, settings, title, save_path, device, logger):
-    """The three figures where the reference draws them (track_eval.py:950-957, 1216-1236).  A figure that fails is an
+def _figures(out, stats, settings, title, save_path, device, logger, df_stats=None, parameter=None):
+    """The figures where the reference draws them (track_eval.py:950-957, 1216-1303).  A figure that fails is an
     error in the log; the tables and the csv files do not depend on it."""
     from . import plot_functions as pf
     px = settings["pixel per micrometre"]
@@ -65,6 +88,15 @@ def _figures(out, stats, settings, title, save_path, device, logger):
     if settings.get("save rose plot"):
         jobs.append(("rose_graph", lambda path: pf.rose_graph(
             df=out, plot_title_name=title, save_path=path, px_to_micrometre=px, distances=distances, device=device, **span)))
+    if settings.get("hip violin plots") and df_stats is not None:
+        cut_list = violin_cut_list(parameter, settings["split violin plots on"])
+        chosen = [(STATS_COLUMNS[col], name, settings.get(limits + " min"), settings.get(limits + " max"))
+                  for key, col, name, limits in VIOLIN_FIGURES if settings.get(key)]
+        chosen.append((STATS_COLUMNS[11], "Median_speed", None, None))
+        for column, name, y_min, y_max in chosen:
+            jobs.append((name, lambda path, column=column, y_min=y_min, y_max=y_max: pf.violin_plot(
+                df=df_stats, save_path=path, category=column, cut_off_category="Categories ({})".format(parameter),
+                cut_off_list=cut_list, plot_title_name=title, y_min=y_min, y_max=y_max, device=device)))
     for name, job in jobs:
         try:
             job(save_path.format(name, ".png"))
@@ -179,12 +211,13 @@ def evaluate_tracks(path_to_file, results_directory=None, df=None, settings=None
                        "could not be assigned, reverted to 'perc. motile'.")
         parameter = STATS_COLUMNS[5]
     df_stats["Categories ({})".format(parameter)] = "All"
+    violins = bool(settings.get("hip violin plots"))
     asked = [k for k in _SKIPPED_PLOT_KEYS if settings.get(k)]
-    if asked:
+    if asked and not violins:
         logger.info("Plots are not part of the HIP path; skipped: {}".format(", ".join(asked)))
     if settings["store final analysed .csv file"]:
         save_df_to_csv(df=out, save_path=save_path.format("analysed", ".csv"))
-    if any(settings.get(k) for k in ("save large plots", "save rose plot", "save angle distribution plot / bins")):
-        _figures(out, stats, settings, plot_title(file_name), save_path, device, logger)
+    if violins or any(settings.get(k) for k in ("save large plots", "save rose plot", "save angle distribution plot / bins")):
+        _figures(out, stats, settings, plot_title(file_name), save_path, device, logger, df_stats, parameter)
     logging.info("Done evaluating file {}".format(file_name))
     return out, df_stats

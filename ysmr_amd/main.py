@@ -2,8 +2,8 @@
 
 ``analyse`` runs detect-and-link (``track_bacteria``), ``select_tracks`` and the statistics of
 ``evaluate_tracks`` on the device, and with 'save video' set ``annotate_video`` writes the annotated video from the
-evaluated table; plots and the xlsx collation are presentation, not part of the HIP path, and are skipped with a log
-message.  It returns the last stage's result (``return_df=True``:
+evaluated table; the track figures are painted on the device, the violin plots too under 'hip violin plots' (without
+that key they are skipped with a log message, like the xlsx collation).  It returns the last stage's result (``return_df=True``:
 a DataFrame, or evaluate_tracks' ``(df, df_stats)``) or ``True``; ``None`` signals an error, as upstream.
 
 Independent videos are embarrassingly parallel (the reference runs one process per path,

@@ -1,12 +1,14 @@
-"""The track figures of ``evaluate_tracks`` -- overview, rose graph, angle histogram -- painted on the device.
+"""The figures of ``evaluate_tracks`` -- overview, rose graph, angle histogram, violin plots -- painted on the device.
 
 Host mirror of the reference's module of this name (ysmr/plot_functions.py:29-257): the same three functions, the same
 file names and figure size.  The reference hands the table to matplotlib, one ``scatter`` call per track; here the
 columns go to HBM once, ``csrc/plots.hip`` paints the canvas, and the host stamps the lettering into the downloaded
 canvas and writes the PNG (NumPy and zlib only).  The image is this project's own rendering of the same data -- which
 pixel a row lands on, which track wins a pixel and what colour it has are fixed by rules ("The figures"),
-matplotlib's antialiased output is not reproduced; the lettering is a 5 x 7 bitmap font.  The violin plots are not
-part of this.
+matplotlib's antialiased output is not reproduced; the lettering is a 5 x 7 bitmap font.  ``violin_plot`` is upstream's
+function of that name (plot_functions.py:260-370) without seaborn: the categories, order statistics, moments and the
+Gaussian kernel density estimate come from ``csrc/violin.hip``, which paints the canvas as well; ``evaluate_tracks``
+calls it when the settings hold a true 'hip violin plots'.
 """
 from __future__ import annotations
 
@@ -359,5 +361,186 @@ def angle_distribution_plot(df, bins_number, plot_title_name, save_path, dpi=300
     stamp_text(rgb, cx, cy + ring + 2 * s, "180", s, anchor="centre")
     stamp_text(rgb, cx - ring - 2 * s, cy - GLYPH_H * s // 2, "270", s, anchor="right")
     stamp_text(rgb, cx + int(0.71 * ring) + 2 * s, cy - int(0.71 * ring) - (GLYPH_H + 2) * s, str(int(counts.max())), s)
+    write_png(save_path, rgb, dpi)
+    logger.debug("Saving figure {}".format(save_path))
+
+
+# ---- the violin plots ------------------------------------------------------------------------------------------------
+
+VIOLIN_INCHES = (11.6929133858 / 2, 8.2677165354 / 2)     # half A4 landscape, as upstream: 1753 x 1240 at 300 dpi
+
+
+def violin_canvas_size(dpi):
+    return int(VIOLIN_INCHES[0] * dpi), int(VIOLIN_INCHES[1] * dpi)
+
+
+def violin_layout(W, H):
+    """The axes rectangle (x, y, w, h): room for the tick labels and the column's name on the left, for the title and the
+    three lines of the text boxes above, for the category names below."""
+    x0, x1, y0, y1 = int(round(0.11 * W)), int(round(0.97 * W)), int(round(0.17 * H)), int(round(0.90 * H))
+    return x0, y0, max(x1 - x0, 1), max(y1 - y0, 1)
+
+
+def device_violin_stats(cut, value, lo, hi, dev):
+    """``ysmr_violin_stats``: (summaries as a NumPy record array [len(lo) + 1] of ``_lib.VIOLIN_SUMMARY_DTYPE``,
+    densities f64 [len(lo) + 1, 100]); violin 0 is 'All'."""
+    import torch
+    L = _lib.lib()
+    cut = torch.from_numpy(np.ascontiguousarray(cut, dtype=np.float64)).to(dev)
+    value = torch.from_numpy(np.ascontiguousarray(value, dtype=np.float64)).to(dev)
+    n, n_cuts = cut.numel(), len(lo)
+    if value.numel() != n or len(hi) != n_cuts:
+        raise ValueError("cut and value, lo and hi must have the same lengths")
+    if n_cuts > _lib.VIOLIN_MAX_CUTS:
+        raise ValueError("at most {} intervals, got {}".format(_lib.VIOLIN_MAX_CUTS, n_cuts))
+    bounds = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(lo, np.float64), np.asarray(hi, np.float64)]))).to(dev)
+    ws = torch.empty(max(L.ysmr_violin_workspace_bytes(n, n_cuts + 1, 0), 256), dtype=torch.uint8, device=dev)
+    size = _lib.VIOLIN_SUMMARY_DTYPE.itemsize
+    sums = torch.empty((n_cuts + 1) * size, dtype=torch.uint8, device=dev)
+    dens = torch.empty(n_cuts + 1, _lib.VIOLIN_GRID, dtype=torch.float64, device=dev)
+    _lib.check(L.ysmr_violin_stats(_lib.stream_ptr(dev), n, cut.data_ptr(), 1, value.data_ptr(), 1, n_cuts, bounds.data_ptr(),
+                                   bounds.data_ptr() + 8 * n_cuts, ws.data_ptr(), ws.numel(), sums.data_ptr(), dens.data_ptr()),
+               "ysmr_violin_stats")
+    return sums.cpu().numpy().view(_lib.VIOLIN_SUMMARY_DTYPE).copy(), dens.cpu().numpy()
+
+
+def device_violins(sums, dens, view, dev, download=True):
+    """``ysmr_plot_violins`` on summaries and densities given as NumPy arrays: the canvas as u8 [H, W, 3] on the host
+    (``download=False``: the device tensor)."""
+    import torch
+    L = _lib.lib()
+    n = int(view.n_violins)
+    sums = np.ascontiguousarray(sums, dtype=_lib.VIOLIN_SUMMARY_DTYPE)
+    dens = np.ascontiguousarray(dens, dtype=np.float64)
+    if len(sums) != n or dens.shape != (n, _lib.VIOLIN_GRID):
+        raise ValueError("the view has {} violins, the summaries {}, the densities {}".format(n, len(sums), dens.shape))
+    s = torch.from_numpy(sums.view(np.uint8).copy()).to(dev)
+    d = torch.from_numpy(dens).to(dev)
+    ws = torch.empty(max(L.ysmr_violin_workspace_bytes(0, n, view.ax_h), 256), dtype=torch.uint8, device=dev)
+    rgb = torch.empty(view.height, view.width, 3, dtype=torch.uint8, device=dev)
+    _lib.check(L.ysmr_plot_violins(_lib.stream_ptr(dev), n, s.data_ptr(), d.data_ptr(), ctypes.byref(view), ws.data_ptr(), ws.numel(),
+                                   rgb.data_ptr()), "ysmr_plot_violins")
+    return rgb.cpu().numpy() if download else rgb
+
+
+def violin_view(sums, y_min=None, y_max=None, dpi=300, size=None):
+    """``ysmr_violin_view`` for the summaries of one figure and its y ticks as (value, canvas row) pairs.  A limit that is
+    None or False is automatic: the 'All' violin's minimum / maximum with a margin of 5 % of its range.  The violins that
+    exist (values > 0) share the axes' width in order, as seaborn's categorical axis does."""
+    W, H = size or violin_canvas_size(dpi)
+    ax_x, ax_y, ax_w, ax_h = violin_layout(W, H)
+    n = len(sums)
+    if not 1 <= n <= _lib.VIOLIN_MAX_SLOTS:
+        raise ValueError("a figure holds 1..{} violins, got {}".format(_lib.VIOLIN_MAX_SLOTS, n))
+    vmin, vmax = (float(sums[0]["vmin"]), float(sums[0]["vmax"])) if sums[0]["values"] > 0 else (0.0, 1.0)
+    margin = 0.05 * (vmax - vmin) if vmax > vmin else 0.5
+    lo = vmin - margin if y_min is None or y_min is False else float(y_min)
+    hi = vmax + margin if y_max is None or y_max is False else float(y_max)
+    if not (math.isfinite(lo) and math.isfinite(hi)) or not hi > lo:
+        hi = lo + 1.0 if math.isfinite(lo) else 1.0
+        lo = lo if math.isfinite(lo) else 0.0
+    view = _lib.ViolinView()
+    view.y0, view.units_per_pixel = lo, (hi - lo) / ax_h
+    view.width, view.height, view.ax_x, view.ax_y, view.ax_w, view.ax_h = W, H, ax_x, ax_y, ax_w, ax_h
+    view.n_violins = n
+    # upstream's linewidth 1 and seaborn's inner box at 300 dpi: a line of 3 pixels, a box of 13, a dot of radius 4
+    s = max(1, int(round(dpi / 100.0)))
+    view.line_half, view.box_half, view.dot_r2 = s // 2, 2 * s, (s + 1) * (s + 1)
+    drawn = [v for v in range(n) if sums[v]["values"] > 0]
+    for pos, v in enumerate(drawn):
+        left, right = ax_x + pos * ax_w // len(drawn), ax_x + (pos + 1) * ax_w // len(drawn)
+        view.slot_x[v], view.slot_w[v], view.slot_colour[v] = left, right - left, pos
+    ticks = ticks_125(lo, hi, nice_step(hi - lo))
+    rows = [(t, ax_y + ax_h - 1 - int(math.floor((t - lo) / view.units_per_pixel))) for t in ticks]
+    rows = [(t, r) for t, r in rows if ax_y <= r < ax_y + ax_h]
+    view.n_grid_rows = len(rows)
+    for k, (_, r) in enumerate(rows):
+        view.grid_rows[k] = r
+    return view, rows
+
+
+def violin_text_boxes(sums, labels):
+    """Upstream's text box of every violin that exists: (violin, text) in cut-list order."""
+    total = int(sums[0]["members"])
+    boxes = []
+    for v, label in enumerate(labels):
+        if not sums[v]["values"] > 0:
+            continue
+        share = "{:.1%}".format(int(sums[v]["members"]) / total) if total > 0 else "error"
+        boxes.append((v, "{}: {} ({})\nMedian: {:.2f}\nAverage:  {:.2f}".format(label, int(sums[v]["members"]), share,
+                                                                               float(sums[v]["q50"]), float(sums[v]["mean"]))))
+    return boxes
+
+
+def _fitting_scale(texts, room, largest):
+    """The largest lettering scale <= ``largest`` at which every text is at most ``room`` pixels wide (1 if none is)."""
+    for s in range(max(1, largest), 1, -1):
+        if all(text_size(t, s)[0] <= room for t in texts):
+            return s
+    return 1
+
+
+def stamp_text_vertical(rgb, x, y, text, scale=1, colour=(0, 0, 0)):
+    """``text`` reading upwards, its box centred on row ``y`` with its left edge at column ``x``; clipped like stamp_text."""
+    bm = np.rot90(text_bitmap(text, scale))
+    th, tw = bm.shape
+    x, y = int(x), int(y) - th // 2
+    H, W = rgb.shape[:2]
+    x0, y0, x1, y1 = max(x, 0), max(y, 0), min(x + tw, W), min(y + th, H)
+    if x0 >= x1 or y0 >= y1:
+        return
+    rgb[y0:y1, x0:x1][bm[y0 - y:y1 - y, x0 - x:x1 - x]] = colour
+
+
+def decorate_violin_figure(rgb, view, rows, title, column, labels, boxes, dpi=300):
+    """Title, tick labels, the column's name along y, the category names under the violins and the text boxes above them,
+    all stamped outside the axes rectangle."""
+    s = max(1, int(round(dpi / 150.0)))
+    gap = 2 * s
+    ax_x, ax_y, ax_w, ax_h = view.ax_x, view.ax_y, view.ax_w, view.ax_h
+    stamp_text(rgb, ax_x + ax_w // 2, max(gap, int(round(0.015 * view.height))), title, s + 1, anchor="centre")
+    widest = 0
+    for t, r in rows:
+        stamp_text(rgb, ax_x - 1 - gap, r - GLYPH_H * s // 2, _label(t), s, anchor="right")
+        widest = max(widest, text_size(_label(t), s)[0])
+    stamp_text_vertical(rgb, max(gap, ax_x - 1 - 3 * gap - widest - GLYPH_H * s), ax_y + ax_h // 2, column, s)
+    if boxes:
+        room = ax_w // len(boxes) - int(0.02 * ax_w)
+        sb = _fitting_scale([line for _, text in boxes for line in text.split("\n")], room, s)
+        line_h = (GLYPH_H + 2) * sb
+        for idx, (v, text) in enumerate(boxes):
+            lines = text.split("\n")
+            for k, line in enumerate(lines):
+                stamp_text(rgb, ax_x + idx * ax_w // len(boxes) + int(0.015 * ax_w), ax_y - gap - line_h * (len(lines) - k), line, sb)
+        sl = _fitting_scale([labels[v] for v, _ in boxes], room, s)
+        for v, _ in boxes:
+            stamp_text(rgb, view.slot_x[v] + view.slot_w[v] // 2, ax_y + ax_h + 1 + 2 * gap, labels[v], sl, anchor="centre")
+
+
+def _cut_column(df, cut_off_category):
+    name = str(cut_off_category)
+    if name.startswith("Categories (") and name.endswith(")") and name[len("Categories ("):-1] in df.columns:
+        return name[len("Categories ("):-1]
+    raise ValueError("cannot tell the column the categories are cut on from {!r}".format(cut_off_category))
+
+
+def violin_plot(df, save_path, category, cut_off_category, cut_off_list, plot_title_name="\n\n", y_min=None, y_max=None, dpi=300,
+                device="cuda:0"):
+    """One violin per entry of ``cut_off_list`` -- (low, high, name) triples, 'All' in front -- of the column
+    ``category`` of the per-track table ``df`` (plot_functions.py:260-370).  Upstream receives the table with a label
+    column made on the host; here ``cut_off_category`` ('Categories (<column>)') names the column the intervals cut,
+    and the device tells the tracks apart."""
+    import torch
+    logger = logging.getLogger("ysmr").getChild(__name__)
+    dev = torch.device(device)
+    cut = df[_cut_column(df, cut_off_category)].to_numpy(dtype=np.float64)
+    value = df[category].to_numpy(dtype=np.float64)
+    labels = [str(name) for _, _, name in cut_off_list]
+    lo, hi = [float(a) for a, _, _ in cut_off_list[1:]], [float(b) for _, b, _ in cut_off_list[1:]]
+    with _lib.on(dev):
+        sums, dens = device_violin_stats(cut, value, lo, hi, dev)
+        view, rows = violin_view(sums, y_min, y_max, dpi)
+        rgb = device_violins(sums, dens, view, dev)
+    decorate_violin_figure(rgb, view, rows, str(plot_title_name).strip(), category, labels, violin_text_boxes(sums, labels), dpi)
     write_png(save_path, rgb, dpi)
     logger.debug("Saving figure {}".format(save_path))
