@@ -11,7 +11,8 @@
 //                brings the block of frame f+2 into LDS by LDS-DMA while it works on frames f and f+1.
 //   row minimum  tracker.py:151-163 reads only D.min(1) and D.argmin(1): a lane reads the candidate list k_bgrid left for
 //                its prediction's cell (every detection that can be nearest to a point of the cell, <= 8), in float, and
-//                evaluates the winner once in float64 (bl_search); outside the grid, in a cell with more candidates, or
+//                evaluates the winner once in float64 (bl_search; a cell with more candidates is served by the lists of
+//                its four quadrants); outside the grid, in a cell with a quadrant that still holds more, or
 //                in frames of more than 600 detections (no lists) it looks at the 3 x 3 cells around the prediction
 //                (bl_search_block); what float cannot decide -- a candidate a hair from the best, a nearer detection
 //                possibly outside the block -- the wave settles exactly over all detections (bl_search_wave:
@@ -58,11 +59,21 @@
 //   [.., + MP / 2)     their column numbers as u16
 //   [.., + 4 G G)      G <= 32 only: per cell BL_LIST u16 positions in the cell-ordered centres -- every detection that can
 //                      be nearest to, or within the float tie band of the nearest to, a point of the cell (k_bgrid, below),
-//                      ascending, padded with m; 0xFFFF first: more than BL_LIST, the cell's lanes search the 3 x 3 block
+//                      ascending, padded with m; 0xFFFF first: more than BL_LIST, the cell's lanes search the 3 x 3 block;
+//                      BL_SPLIT first: the cell's four quadrants have lists of their own, in overflow entry <second u16>
+//                      (of a slot that starts with 0xFFFF or BL_SPLIT the rest is unspecified: what the first pass left)
+//   [.., + 16 BL_OVF)  G <= 32 only, the overflow area: BL_OVF entries of 4 x BL_LIST u16 -- the lists of the quadrants
+//                      (x half + 2 * y half) of a cell whose own list came out too long, built like a cell's list on the
+//                      quadrant's rectangle.  Entries go to the crowded cells in cell order; a cell beyond the BL_OVF-th,
+//                      or one with a quadrant that still overflows, keeps 0xFFFF.  Unused entries are zero.
 // (cells per side so that a cell holds ~0.45 detections: the three cells of a row of the 3 x 3 block around a prediction
 // then hold more than five candidates once in 200 rows, and the block reaches one cell -- ~1.7 mean nearest-neighbour
 // distances -- beyond the prediction's own cell)
 constexpr int BL_LIST = 8;        // candidates per cell: one ds_read_b128 per lane
+constexpr int BL_OVF = 8;         // overflow entries per frame (512 bytes; DESIGN.md section 4, round 16, has the distribution:
+                                  // the bench clip's frames hold 0 .. 5 crowded cells, and a frame of ~530 detections still
+                                  // takes 24 LDS-DMA pieces with them)
+constexpr unsigned BL_FLAG = 0xFFFFu, BL_SPLIT = 0xFFFEu;      // first u16 of a cell's slot (positions are <= 600)
 __host__ __device__ inline int bl_grid_n(int m) { return m <= 128 ? 16 : (m <= 600 ? 32 : (m <= 1300 ? 48 : 64)); }
 // (the lists of 48 x 48 cells would take 36 KB per block: two of them beside the tables of max_det = 2048 do not fit a
 // compute unit's 160 KB; those frames keep the 3 x 3 search)
@@ -74,10 +85,13 @@ __host__ __device__ inline int bl_list_off(int m)      // dword offset of the li
 {
     return 16 + bl_start_dwords(bl_grid_n(m)) + 2 * bl_mp(m) + bl_mp(m) / 2;
 }
+__host__ __device__ inline int bl_ovf_off(int m)       // dword offset of the overflow area (frames with lists)
+{
+    return bl_list_off(m) + bl_grid_n(m) * bl_grid_n(m) * BL_LIST / 2;
+}
 __host__ __device__ inline int bl_grid_dwords(int m)   // rounded up to whole 1-KiB pieces (one LDS-DMA wave-instruction)
 {
-    const int G = bl_grid_n(m);
-    const int raw = bl_list_off(m) + (bl_has_lists(m) ? G * G * BL_LIST / 2 : 0);
+    const int raw = bl_has_lists(m) ? bl_ovf_off(m) + BL_OVF * 4 * BL_LIST / 2 : bl_list_off(m);
     return (raw + 255) / 256 * 256;
 }
 __host__ __device__ inline int bl_grid_dwords_max(int max_det)
@@ -95,6 +109,7 @@ __host__ __device__ inline int bl_grid_dwords_max(int max_det)
 // the first version (35 us per batch beside the next batch's detection kernels).
 constexpr int BG_THREADS = 256, BG_PER = 10;      // 2560 >= the 2456 detections a one-launch link serves
 constexpr int BG_CAND = 32;                       // candidates of a cell before the pruning (more: the cell is flagged)
+static_assert(BG_THREADS == 4 * 64 && BL_OVF <= 64, "k_bgrid's second pass: quadrant w of overflow entry `lane` on wave w");
 
 // The candidate list of cell c (G <= 32).  R = the cell's rectangle grown by e on every side: a prediction that bl_search
 // places in cell c lies in R (below).  Every point p of R has a detection within U = min over d of maxdist(d, R) -- found by
@@ -111,14 +126,22 @@ constexpr int BG_CAND = 32;                       // candidates of a cell before
 // circle), and at most a few detections per cell survive: uniform frames of 500 detections keep <= BL_LIST in 99.7 % of cells.
 // e: a prediction's cell is floor((fx - x0) * inv) in float, fx = (float)px: off by |fx - px| <= 2.4e-4 px, plus 2.4e-4 px
 // for fx - x0 and ~1e-5 cells for the product -- e = 4e-3 px + 2e-4 cells covers that and the corners' own rounding here.
-__device__ __forceinline__ void bl_cell_list(int c, int G, int m, float x0, float y0, float cell, float inv, const unsigned short *start16,
-                                             const float2 *xy, unsigned short *list16, unsigned short *cand)
+// A QUADRANT of a cell (split lists, below): bl_search decides it from the same float product, frac = u - floor(u) >= 0.5
+// with u = (fx - x0) * inv.  The subtraction is exact (u and floor(u) are less than one apart), so the decision is
+// u >= cx + 0.5 for the float u, and u is off from the prediction's true place by what sets e above: |fx - px| <= 2.4e-4 px,
+// 2.4e-4 px for fx - x0, ~1e-5 cells for the product.  The midline itself, x0 + (cx + 0.5) * cell, is rounded here like a
+// cell's side (cx + 0.5 is exact).  The same e = 4e-3 px + 2e-4 cells therefore covers a quadrant's rectangle, on its
+// inner sides as on its outer ones -- which are the cell's own, bit for bit (cx + 0.5 + 0.5 = cx + 1).
+// The walk for U and the gathering stay centred on the quadrant's CELL: U only has to be an upper bound (any detection's
+// maxdist is one), and the gathering's rho carries two cells of slack where the rectangle needs none beyond its cell.
+__device__ __forceinline__ void bl_rect_list(int cx, int cy, float ax, float bx, float ay, float by, float e, int G, int m, float cell,
+                                             float inv, const unsigned short *start16, const float2 *xy, unsigned short *list8,
+                                             unsigned short *cand)
 {
-    const int cx = c % G, cy = c / G;
-    const float e = 4e-3f + 2e-4f * cell;
-    const float ax = x0 + (float)cx * cell - e, bx = x0 + (float)(cx + 1) * cell + e;
-    const float ay = y0 + (float)cy * cell - e, by = y0 + (float)(cy + 1) * cell + e;
-    // U^2: rings 0, 1, 2, ... (a detection of ring r + 1 is at least (r + 1) cells from the rectangle's far side)
+    // U^2: rings 0, 1, 2, ... (a detection of ring r + 1 is at least (r + 1) cells from the rectangle's far side -- of a
+    // CELL's rectangle.  From a quadrant's far side it is only (r + 0.5) cells, so for a quadrant the walk may stop a ring
+    // before the true minimum: U stays an upper bound, T comes out a little larger, a few more candidates are gathered and
+    // pruned again.  Kept so that a quadrant's list is the cell's procedure verbatim.)
     float u2 = 3.0e38f;
     int ju = 0;                 // the detection that sets U: tried first as the nearer one in the pruning
     auto far2 = [&](int a, int b) {
@@ -172,20 +195,48 @@ __device__ __forceinline__ void bl_cell_list(int c, int G, int m, float x0, floa
             const float xa = ax - di.x, xb = bx - di.x, ya = ay - di.y, yb = by - di.y;
             const float s0 = xa * xa + ya * ya, s1 = xb * xb + ya * ya, s2 = xa * xa + yb * yb, s3 = xb * xb + yb * yb;
             bool beaten = ji != ju && s0 > u0 && s1 > u1 && s2 > u2c && s3 > u3;
-            for (int k = 0; k < n && !beaten; ++k) {
-                const float2 dk = xy[cand[k * BG_THREADS]];
-                const float ka = ax - dk.x, kb = bx - dk.x, la = ay - dk.y, lb = by - dk.y;
-                beaten = k != i && s0 > (ka * ka + la * la) * eps + beta && s1 > (kb * kb + la * la) * eps + beta &&
-                         s2 > (ka * ka + lb * lb) * eps + beta && s3 > (kb * kb + lb * lb) * eps + beta;
+            // (four rivals per pass, their reads in flight together: a rival costs two dependent LDS reads, and a crowded
+            // rectangle tries ~150 of them -- one after the other that was the slowest thread's tail, and the second pass
+            // of the split lists would have added a tail of its own; `beaten` is an OR over the rivals, so the order is free)
+            for (int k = 0; k < n && !beaten; k += 4) {
+                float2 dk[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) dk[u] = xy[cand[min(k + u, n - 1) * BG_THREADS]];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const float ka = ax - dk[u].x, kb = bx - dk[u].x, la = ay - dk[u].y, lb = by - dk[u].y;
+                    beaten = beaten || (k + u < n && k + u != i && s0 > (ka * ka + la * la) * eps + beta && s1 > (kb * kb + la * la) * eps + beta &&
+                                        s2 > (ka * ka + lb * lb) * eps + beta && s3 > (kb * kb + lb * lb) * eps + beta);
+                }
             }
             if (!beaten) {
-                if (kept < BL_LIST) list16[c * BL_LIST + kept] = (unsigned short)ji;
+                if (kept < BL_LIST) list8[kept] = (unsigned short)ji;
                 ++kept;
             }
         }
-    if (n > BG_CAND || kept > BL_LIST) list16[c * BL_LIST] = 0xFFFFu;
+    if (n > BG_CAND || kept > BL_LIST) list8[0] = (unsigned short)BL_FLAG;
     else
-        for (int k = kept; k < BL_LIST; ++k) list16[c * BL_LIST + k] = (unsigned short)m;
+        for (int k = kept; k < BL_LIST; ++k) list8[k] = (unsigned short)m;
+}
+__device__ __forceinline__ void bl_cell_list(int c, int G, int m, float x0, float y0, float cell, float inv, const unsigned short *start16,
+                                             const float2 *xy, unsigned short *list16, unsigned short *cand)
+{
+    const int cx = c % G, cy = c / G;
+    const float e = 4e-3f + 2e-4f * cell;
+    const float ax = x0 + (float)cx * cell - e, bx = x0 + (float)(cx + 1) * cell + e;
+    const float ay = y0 + (float)cy * cell - e, by = y0 + (float)(cy + 1) * cell + e;
+    bl_rect_list(cx, cy, ax, bx, ay, by, e, G, m, cell, inv, start16, xy, list16 + c * BL_LIST, cand);
+}
+// quadrant q = (x half) + 2 * (y half) of cell c, into list8
+__device__ __forceinline__ void bl_quad_list(int c, int q, int G, int m, float x0, float y0, float cell, float inv, const unsigned short *start16,
+                                             const float2 *xy, unsigned short *list8, unsigned short *cand)
+{
+    const int cx = c % G, cy = c / G;
+    const float e = 4e-3f + 2e-4f * cell;
+    const float hx = (float)cx + 0.5f * (float)(q & 1), hy = (float)cy + 0.5f * (float)(q >> 1);
+    const float ax = x0 + hx * cell - e, bx = x0 + (hx + 0.5f) * cell + e;
+    const float ay = y0 + hy * cell - e, by = y0 + (hy + 0.5f) * cell + e;
+    bl_rect_list(cx, cy, ax, bx, ay, by, e, G, m, cell, inv, start16, xy, list8, cand);
 }
 
 __global__ __launch_bounds__(BG_THREADS) void k_bgrid(const float *__restrict__ det_all, const int32_t *__restrict__ det_count,
@@ -197,6 +248,9 @@ __global__ __launch_bounds__(BG_THREADS) void k_bgrid(const float *__restrict__ 
     __shared__ int s_wave_sum[4];
     const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     __shared__ unsigned short s_cand[BG_CAND][BG_THREADS];      // a cell's candidates, per thread
+    __shared__ unsigned short s_crowded[BL_OVF];                // the cells that get an overflow entry, ascending
+    __shared__ int s_crowded_n;                                 // how many of them (at most BL_OVF)
+    __shared__ int s_any_crowded;                               // flag: the first pass flagged a cell
     const float *det = det_all + (size_t)f * max_det * 5;
     int m = det_count[f];
     m = m < 0 ? 0 : (m > max_det ? max_det : m);
@@ -283,9 +337,55 @@ __global__ __launch_bounds__(BG_THREADS) void k_bgrid(const float *__restrict__ 
             xy[at] = make_float2(x[k], y[k]);
         }
     }
+    unsigned short *ovf16 = reinterpret_cast<unsigned short *>(s_out + bl_ovf_off(m));      // (frames with lists only)
+    if (bl_has_lists(m)) {      // (the overflow area starts as zeros; "no crowded cell yet")
+        for (int i = tid; i < BL_OVF * 4 * BL_LIST / 2; i += BG_THREADS) s_out[bl_ovf_off(m) + i] = 0;
+        if (tid == 0) s_any_crowded = 0;
+    }
     __syncthreads();
     if (bl_has_lists(m) && m > 0) {
-        for (int c = tid; c < cells; c += BG_THREADS) bl_cell_list(c, G, m, x0, y0, cell, inv, start16, xy, list16, &s_cand[0][tid]);
+        for (int c = tid; c < cells; c += BG_THREADS) {
+            bl_cell_list(c, G, m, x0, y0, cell, inv, start16, xy, list16, &s_cand[0][tid]);
+            if (list16[c * BL_LIST] == BL_FLAG) s_any_crowded = 1;     // (the second pass runs)
+        }
+        __syncthreads();
+    }
+    if (bl_has_lists(m) && m > 0 && s_any_crowded) {         // (uniform: read behind the barrier)
+        // Split lists.  The crowded cells (flagged above) are compacted in cell order -- K consecutive cells per thread, the
+        // scan of the counts again -- and the first BL_OVF of them get an overflow entry each; the (entry, quadrant) items
+        // then go out over the workgroup, one per thread: the thread that owned a crowded cell was the slowest of the first
+        // pass already, and four more lists in a row behind it would be the kernel's tail.
+        int mine = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (k < K) mine += list16[(tid * K + k) * BL_LIST] == BL_FLAG;
+        int inc2 = mine;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(inc2, d); if (lane >= d) inc2 += o; }
+        if (lane == 63) s_wave_sum[w] = inc2;      // (its readers of the first scan are barriers back)
+        __syncthreads();
+        int at = inc2 - mine;
+        for (int k = 0; k < w; ++k) at += s_wave_sum[k];
+        if (mine)
+            for (int k = 0; k < K; ++k)
+                if (list16[(tid * K + k) * BL_LIST] == BL_FLAG) {
+                    if (at < BL_OVF) s_crowded[at] = (unsigned short)(tid * K + k);
+                    ++at;
+                }
+        if (tid == BG_THREADS - 1) s_crowded_n = min(at, BL_OVF);
+        __syncthreads();
+        const int entries = s_crowded_n;
+        // (quadrant w of entry `lane` on wave w: a wave's lanes run their lists in lockstep, every lane through every other
+        // lane's loops, so the items are spread over the four waves rather than packed into the first)
+        if (lane < entries)
+            bl_quad_list(s_crowded[lane], w, G, m, x0, y0, cell, inv, start16, xy, ovf16 + (4 * lane + w) * BL_LIST, &s_cand[0][tid]);
+        __syncthreads();
+        if (tid < entries) {
+            bool fits = true;
+            for (int q = 0; q < 4; ++q) fits = fits && ovf16[(4 * tid + q) * BL_LIST] != BL_FLAG;
+            // (the slot's first dword: the marker and the entry; a cell with a quadrant that still overflows keeps its flag)
+            if (fits) reinterpret_cast<uint32_t *>(list16)[s_crowded[tid] * (BL_LIST / 2)] = BL_SPLIT | ((uint32_t)tid << 16);
+        }
         __syncthreads();
     }
     uint4 *out = reinterpret_cast<uint4 *>(grid + (size_t)grid_stride * f);
@@ -726,16 +826,25 @@ __device__ __forceinline__ BlNear bl_search_block(const BlGridView &g, double px
 // round for the list, one for the centres, eight keys as above -- the slot is the list position -- and no bounds, masks or
 // outside test: the list holds the float64 argmin of every point of the cell and every detection within the float band of
 // it (k_bgrid: bl_cell_list), so what it leaves open is what the 3 x 3 block would (the band), and that goes to the wave.
-// A lane outside the grid or in a flagged cell takes bl_search_block; the wave runs it only when some lane needs it.
+// A cell whose list came out too long is served the same way from the list of the prediction's QUADRANT (bl_quad_list).
+// A lane outside the grid or in a cell still flagged takes bl_search_block; the wave runs it only when some lane needs it.
 __device__ __forceinline__ BlNear bl_search(const BlGridView &g, double px, double py, int m)
 {
     const int G = g.G;
     const float fx = (float)px, fy = (float)py;
-    const int cx = (int)floorf((fx - g.x0) * g.inv), cy = (int)floorf((fy - g.y0) * g.inv);
+    const float ux = (fx - g.x0) * g.inv, uy = (fy - g.y0) * g.inv;
+    const float wx = floorf(ux), wy = floorf(uy);
+    const int cx = (int)wx, cy = (int)wy;
     bool listed = g.lists >= 0 && cx >= 0 && cx < G && cy >= 0 && cy < G;
     uint4 l = make_uint4(0u, 0u, 0u, 0u);
     if (listed) l = reinterpret_cast<const uint4 *>(bl_u32(g.lists))[cy * G + cx];
-    listed = listed && (l.x & 0xFFFFu) != 0xFFFFu;
+    // a split cell (k_bgrid: its own list came out too long): the list of the prediction's quadrant, from the overflow
+    // area behind the lists -- one more dependent read for these lanes, then the same eight candidates as everyone
+    if (listed && (l.x & 0xFFFFu) == BL_SPLIT) {
+        const int q = (int)(ux - wx >= 0.5f) + 2 * (int)(uy - wy >= 0.5f);
+        l = reinterpret_cast<const uint4 *>(bl_u32(g.lists))[G * G + (int)(l.x >> 16) * 4 + q];
+    }
+    listed = listed && (l.x & 0xFFFFu) != BL_FLAG;
     BlNear r;
     if (listed) {
         const uint32_t w[4] = {l.x, l.y, l.z, l.w};

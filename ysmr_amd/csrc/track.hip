@@ -2554,6 +2554,21 @@ int ysmr_debug_ring_zero_line(ysmr_tracker *t, long long *nonzero)
     return YSMR_OK;
 }
 
+// Test hook for the grid blocks (tests/test_gpu_cell_lists_split.py): the block k_bgrid left for frame `frame` of the batch
+// last prepared into `slot` (ysmr_tracker_prepare), the first `bytes` of it (at most the handle's bytes per frame: header,
+// cell starts, centres, columns, lists, overflow area -- batch_link.h).  Waits for the device first.
+int ysmr_debug_read_grid_block(ysmr_tracker *t, int slot, int frame, void *out, size_t bytes)
+{
+    if (!t || !out) return ysmr::fail(YSMR_ERR_ARG, "tracker handle and out must be set");
+    if (t->dims != 2 || !t->use_batch()) return ysmr::fail(YSMR_ERR_STATE, "the handle has no batch link: no grid blocks");
+    if (slot < 0 || slot > 1 || t->prepared[slot].batch <= 0 || frame < 0 || frame >= t->prepared[slot].batch || bytes > t->bd.grid_stride)
+        return ysmr::fail(YSMR_ERR_ARG, "slot 0 or 1 with a prepared batch, a frame of that batch, at most %u bytes", t->bd.grid_stride);
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess)
+        e = hipMemcpy(out, t->bd.grid + ((size_t)slot * BL_MAX_BATCH + (size_t)frame) * t->bd.grid_stride, bytes, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? YSMR_OK : ysmr::fail(YSMR_ERR_HIP, "grid block read failed: %s", hipGetErrorString(e));
+}
+
 int ysmr_tracker_prepare(ysmr_tracker *t, void *stream, const float *det_dev, const int32_t *det_count_dev, int batch, int slot)
 {
     if (!t) return ysmr::fail(YSMR_ERR_ARG, "tracker handle is NULL");
