@@ -9,6 +9,7 @@
  *
  * Reference interfaces replaced (files under /root/reference):
  *   ysmr_unpack_dib_batch cv2.VideoCapture.read (uncompressed AVI frames)   ysmr/track_eval.py:159
+ *   ysmr_mjpeg_decode_batch cv2.VideoCapture.read (Motion-JPEG AVI frames)  ysmr/track_eval.py:159
  *   ysmr_annotate_batch   cv2.putText + cv2.circle + cv2.VideoWriter.write   ysmr/track_eval.py:1423-1449
  *   ysmr_mjpeg_batch      cv2.VideoWriter.write with fourcc 'MJPG' ('save video fourcc codec')   ysmr/track_eval.py:1400-1449
  *   ysmr_threshold_batch  cv2.cvtColor + cv2.GaussianBlur + 2 x cv2.adaptiveThreshold
@@ -51,7 +52,7 @@ extern "C" {
 #define YSMR_ERR_CAPACITY  3   /* a fixed-capacity buffer would overflow (tracks, workspace) */
 #define YSMR_ERR_STATE     4   /* handle used in the wrong state */
 
-/* 15 still: ysmr_annotate_batch with its mark struct, and later the ysmr_plot_*, ysmr_mjpeg_* and ysmr_violin_* functions, were ADDED under this number
+/* 15 still: ysmr_annotate_batch with its mark struct, and later the ysmr_plot_*, ysmr_mjpeg_*, ysmr_violin_* and ysmr_mjpeg_decode_* functions, were ADDED under this number
  * -- no existing entry point, struct or constant changed, so every caller written against 15 keeps working; only a caller
  * of a new function needs a library that has it (the loader reports a missing symbol by name). */
 #define YSMR_ABI_VERSION   15
@@ -146,6 +147,31 @@ typedef struct {
 int ysmr_annotate_batch(void *stream, const uint8_t *frames_dev, int n_frames, int height, int width, int channels,
                         const ysmr_mark *marks_dev, const int64_t *first_dev,
                         uint8_t *out_dev, int out_stride, size_t out_frame_bytes, int bottom_up);
+
+/* ---- frame ingest: Motion-JPEG ------------------------------------------------------------------ */
+
+/* ADDED under ABI 15 (see above).  bits of status_dev[i] of ysmr_mjpeg_decode_batch */
+#define YSMR_MJPEGD_UNSUPPORTED 1  /* not baseline SOF0 / 8 bit / one interleaved scan of all components, sampling other than
+                                      the call's, geometry other than the call's, APP14 present, > 1 SOS, arithmetic coding */
+#define YSMR_MJPEGD_CORRUPT     2  /* a code that no table holds, a coefficient index past 63, an entropy segment that ends
+                                      before its MCUs, a missing or out-of-sequence RSTn, no SOS / SOF / DQT the scan needs */
+
+/* Bytes of scratch ysmr_mjpeg_decode_batch needs (mostly the quantised coefficients, 2 bytes per sample of the padded
+ * planes, and for three components the decoded planes, 1 byte per sample).  0 for arguments it refuses. */
+size_t ysmr_mjpeg_decode_workspace_bytes(int n_frames, int height, int width, int channels, int sampling);
+
+/* What cv2.VideoCapture.read does with a Motion-JPEG AVI, for a batch of '00dc' chunk bodies as they are in the file, back
+ * to back: JPEG i is chunks_dev[offsets_dev[i] .. offsets_dev[i + 1]); bytes behind its EOI are ignored.  sampling: 0 = one
+ * component (channels 1), 1 = 4:4:4, 2 = 4:2:2 (2 x 1), 3 = 4:2:0 (2 x 2) (channels 3: B, G, R).  frames_dev: u8
+ * [n_frames][height][width][channels], the layout ysmr_threshold_batch reads, byte for byte what libjpeg-turbo's default
+ * decode (accurate integer IDCT, fancy upsampling) delivers.  status_dev[i] = 0, or YSMR_MJPEGD_* bits for a frame outside
+ * the supported subset or damaged: such a frame's pixels are undefined, inside its own height * width * channels bytes
+ * and nowhere else, and no read leaves its own chunk.  Asynchronous on `stream`.  workspace_dev: 256-byte aligned,
+ * workspace_bytes >= ysmr_mjpeg_decode_workspace_bytes(...); no state is kept in it and nothing found in it is used. */
+int    ysmr_mjpeg_decode_batch(void *stream, const uint8_t *chunks_dev, const int64_t *offsets_dev, int n_frames,
+                               int height, int width, int channels, int sampling,
+                               void *workspace_dev, size_t workspace_bytes,
+                               uint8_t *frames_dev, int32_t *status_dev /* [n_frames] */);
 
 /* ---- annotated output video as Motion-JPEG --------------------------------------------------- */
 

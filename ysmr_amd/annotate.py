@@ -40,7 +40,7 @@ from fractions import Fraction
 import numpy as np
 
 from . import _lib
-from .frames import DeviceFrameFeed, open_video
+from .frames import DeviceFrameFeed, decode_mjpeg_setting, open_video
 from .helper_file import create_results_folder, get_configs, get_data, get_loggers
 
 __all__ = ["annotate_video", "AviWriter", "MjpegAviWriter", "output_format", "build_marks", "subtype_code", "SUBTYPES"]
@@ -425,7 +425,7 @@ def _mjpeg_frames(video, writer, marks, first, n_frames, quality, settings, resu
         thread.start()
         done, shortfall, feed = 0, None, None
         try:
-            feed = DeviceFrameFeed(video, batch, dev, depth=2)
+            feed = DeviceFrameFeed(video, batch, dev, depth=2, decode_on_device=decode_mjpeg_setting(settings))
             for frames_dev, f0, n, slot in feed:
                 n = min(n, n_frames - f0)
                 if n <= 0:
@@ -486,7 +486,8 @@ def annotate_video(video_path, df, output_save=True, settings=None, result_folde
     not moving, white with a larger dot at turn points.  Returns the path of the file, None after any failure (logged on
     'ysmr', never raised).  Optional settings keys: 'hip frames per batch' overrides the batch size; 'hip video jpeg
     quality' (1 .. 100, default 90) is the quality of a Motion-JPEG file (``output_format`` says when one is written;
-    the free space is then checked batch by batch, against the bytes about to be written)."""
+    the free space is then checked batch by batch, against the bytes about to be written); 'hip decode mjpeg' (True /
+    'always' / False) says whether a Motion-JPEG INPUT is decoded on the device, as in ``track_bacteria``."""
     import pandas as pd
     import torch
     logger = logging.getLogger("ysmr").getChild(__name__)
@@ -611,7 +612,7 @@ def annotate_video(video_path, df, output_save=True, settings=None, result_folde
             thread.start()
             done = 0
             try:
-                feed = DeviceFrameFeed(video, batch, dev, depth=2)
+                feed = DeviceFrameFeed(video, batch, dev, depth=2, decode_on_device=decode_mjpeg_setting(settings))
                 for frames_dev, f0, n, slot in feed:
                     n = min(n, n_frames - f0)
                     if n <= 0:

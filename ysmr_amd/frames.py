@@ -9,8 +9,10 @@ it happens to be importable:
 * ``.y4m``  -- YUV4MPEG2; the luma plane is used as the gray frame
 * ``.avi``  -- uncompressed AVI (what many microscope cameras write): 8-bit gray or 24-bit BGR DIB frames,
                bottom-up or top-down, OpenDML ``AVIX`` extensions included -- ``DeviceFrameFeed`` uploads the stored
-               frames as they are and unpacks them on the device (``ysmr_unpack_dib_batch``); Motion-JPEG AVI if
-               Pillow can be imported (frames decoded on the reader threads); other compressed streams go to cv2
+               frames as they are and unpacks them on the device (``ysmr_unpack_dib_batch``); Motion-JPEG AVI: baseline
+               frames (gray, 4:4:4, 4:2:2, 4:2:0) are uploaded as they are and decoded on the device
+               (``ysmr_mjpeg_decode_batch``), anything else by Pillow on the reader threads, if it can be imported; other
+               compressed streams go to cv2
 * anything else -- ``cv2.VideoCapture`` if cv2 can be imported, otherwise an error
 
 Every source exposes ``frame_count`` (what the container reports: cv2's CAP_PROP_FRAME_COUNT), optionally
@@ -143,7 +145,7 @@ class Y4mVideo:
 
 class AviVideo:
     """AVI (RIFF) without OpenCV: stream 0 must be video with BI_RGB 8- or 24-bit frames (or the raw
-    gray fourccs Y800 / GREY / Y8), or Motion-JPEG (decoded with Pillow, if installed).  8-bit frames whose palette is the gray ramp are delivered as gray
+    gray fourccs Y800 / GREY / Y8), or Motion-JPEG (``jpeg_layout``: decoded on the device; else with Pillow, if installed).  8-bit frames whose palette is the gray ramp are delivered as gray
     [H, W] -- what ``cv2.VideoCapture`` + ``COLOR_BGR2GRAY`` make of them --, other palettes are
     expanded to BGR; 24-bit frames are BGR as stored.  Raises ValueError for compressed streams."""
 
@@ -226,16 +228,22 @@ class AviVideo:
         if self._jpeg:
             try:
                 from PIL import Image
+                self._Image, self._no_pillow = Image, None
             except ImportError as exc:
-                raise ValueError(f"{path}: Motion-JPEG AVI needs Pillow ({exc})") from exc
-            self._Image = Image
+                self._Image, self._no_pillow = None, str(exc)
             self.width, self.height = int(width), abs(int(height))
             self.frames_available = len(self._frames)
             self.frame_count = declared[0] or self.frames_available
             if not self.frames_available:
                 raise ValueError(f"{path}: no frames")
-            with Image.open(self._chunk(0)) as first:
-                self.channels = 1 if first.mode == "L" else 3
+            # the first frame's SOF / SOS say what the file holds: Pillow is needed only for frames the device does not decode
+            components, self._jpeg_sampling, self._jpeg_dri = self._jpeg_first(self._chunk(0).getvalue())
+            if self.jpeg_layout_for(1) is None and self._Image is None:
+                raise ValueError(f"{path}: Motion-JPEG AVI needs Pillow ({self._no_pillow})")
+            if components is None:
+                with self._Image.open(self._chunk(0)) as first:
+                    components = 1 if first.mode == "L" else 3
+            self.channels = 1 if components == 1 else 3
             return
         if not (compression == 0 or (fourcc in self._RAW_GRAY and bits == 8)) or bits not in (8, 24):
             raise ValueError(f"{path}: only uncompressed 8/24-bit or Motion-JPEG AVI is read natively "
@@ -275,7 +283,68 @@ class AviVideo:
         self._fh.seek(off)
         return io.BytesIO(self._fh.read(size))
 
+    def _jpeg_first(self, data):
+        """(components or None, sampling or None, has DRI) of a frame.  ``sampling`` is the argument of
+        ``ysmr_mjpeg_decode_batch`` -- 0 one component, 1 4:4:4, 2 4:2:2, 3 4:2:0 -- if the frame's headers up to SOS pass the
+        rules by which that function would not flag it (tests/jpeg_decode_model.py, ``_headers``): SOF0 of this file's size,
+        8 bit, the supported sampling factors and component ids, 8-bit DQT, no APP14, no other or second SOF, one scan of all
+        components in their order with Ss, Se, Ah / Al = 0, 63, 0, every segment inside the chunk; else None."""
+        n, pos = len(data), 2
+        components, factors, ids, dri, ok = None, None, None, False, True
+        if n < 4 or data[:2] != b"\xff\xd8":
+            return None, None, False
+        while True:
+            if pos >= n or data[pos] != 0xFF:
+                return components, None, dri
+            while pos < n and data[pos] == 0xFF:                  # fill bytes
+                pos += 1
+            if pos >= n:
+                return components, None, dri
+            marker = data[pos]
+            pos += 1
+            if marker == 0x01 or 0xD0 <= marker <= 0xD8:
+                continue
+            if marker in (0xD9, 0x00) or pos + 2 > n:
+                return components, None, dri
+            size = int.from_bytes(data[pos:pos + 2], "big")
+            if size < 2 or pos + size > n:
+                return components, None, dri
+            body = data[pos + 2:pos + size]
+            if marker == 0xDB:
+                for at in range(0, len(body), 65):
+                    if body[at] >> 4 or (body[at] & 15) > 3 or at + 65 > len(body):
+                        ok = False                                   # (16-bit table; or damaged)
+            elif marker == 0xC0 and components is None and len(body) >= 6 and len(body) == 6 + 3 * body[5]:
+                components = body[5]
+                ids, factors = [body[6 + 3 * c] for c in range(components)], [body[7 + 3 * c] for c in range(components)]
+                if body[0] != 8 or int.from_bytes(body[1:3], "big") != self.height or int.from_bytes(body[3:5], "big") != self.width or \
+                        any(body[8 + 3 * c] > 3 for c in range(components)):
+                    ok = False
+            elif marker == 0xDD:
+                dri = len(body) == 2 and int.from_bytes(body, "big") > 0
+                ok = ok and len(body) == 2
+            elif marker == 0xEE or (0xC0 <= marker <= 0xCF and marker not in (0xC4, 0xC8)):
+                if components is None and 0xC0 <= marker <= 0xCF and marker != 0xCC and len(body) >= 6:
+                    components = body[5]                             # (another kind of frame: Pillow's, with this many components)
+                ok = False
+            elif marker == 0xDA:
+                if not ok or components is None or len(body) < 1 or body[0] != components or len(body) != 4 + 2 * components:
+                    return components, None, dri
+                if [body[1 + 2 * c] for c in range(components)] != ids or any((body[2 + 2 * c] >> 4) > 3 or (body[2 + 2 * c] & 15) > 3
+                                                                              for c in range(components)):
+                    return components, None, dri
+                if tuple(body[1 + 2 * components:]) != (0, 63, 0):
+                    return components, None, dri
+                if factors == [0x11]:
+                    return components, 0, dri
+                if ids == [1, 2, 3] and factors[1:] == [0x11, 0x11] and factors[0] in (0x11, 0x21, 0x22):
+                    return components, {0x11: 1, 0x21: 2, 0x22: 3}[factors[0]], dri
+                return components, None, dri
+            pos += size
+
     def _decode_jpeg(self, blob, dst):
+        if self._Image is None:
+            raise ValueError(f"{self.path}: Motion-JPEG AVI needs Pillow ({self._no_pillow})")
         with self._Image.open(blob) as im:
             if self.channels == 1:
                 dst[...] = np.asarray(im.convert("L"))
@@ -329,6 +398,59 @@ class AviVideo:
             got, view = 0, memoryview(out[i]).cast("B")[:need]
             while got < need:                                   # (a read may return short of a large request)
                 k = os.preadv(fd, [view[got:]], self._frames[start + i][0] + got)
+                if k <= 0:
+                    raise ValueError(f"{self.path}: frame {start + i} is truncated")
+                got += k
+
+        if pool is None or n < 2:
+            for i in range(n):
+                one(i)
+        else:
+            for job in [pool.submit(one, i) for i in range(n)]:
+                job.result()
+        return n
+
+    # ---- Motion-JPEG chunks as they are in the file, for decoding on the device (DeviceFrameFeed, ysmr_mjpeg_decode_batch)
+    #: the batch size ``jpeg_layout`` sizes its third number for (a feed asks ``jpeg_layout_for`` with its own)
+    jpeg_batch = 248
+    def jpeg_layout_for(self, batch, needs_restart=True):
+        """None, or what a caller of ``ysmr_mjpeg_decode_batch`` needs to know before it reads this file: (sampling, bytes of
+        the largest chunk, most bytes of any ``batch`` consecutive chunks).  None for files that are not Motion-JPEG and for
+        those whose first frame is outside the subset the device decodes (``raw_layout`` is None for every JPEG file).
+        ``needs_restart``: None also when the first frame has no restart interval (DRI).  One lane decodes a restart interval,
+        so a frame without restart markers is one lane's work, and the host path is the faster one for such a file
+        (profiles/mjpeg_decode_e2e.log); False gives the layout of every supported file."""
+        if not getattr(self, "_jpeg", False) or self._jpeg_sampling is None or (needs_restart and not self._jpeg_dri):
+            return None
+        sizes = np.array([f[1] for f in self._frames], np.int64)
+        total = np.concatenate([[0], np.cumsum(sizes)])
+        k = max(1, min(int(batch), len(sizes)))
+        return self._jpeg_sampling, int(sizes.max()), int((total[k:] - total[:-k]).max())
+
+    @property
+    def jpeg_layout(self):
+        return self.jpeg_layout_for(self.jpeg_batch)
+
+    def read_jpeg_into(self, start, count, out, offsets, pool=None):
+        """Chunk bodies of frames [start, start + count) back to back into ``out`` (u8 [bytes], e.g. pinned memory; the
+        RIFF pad byte of an odd-sized chunk is not part of it) and where each begins into ``offsets[:n + 1]`` (int64): file
+        reads only (``os.preadv``, spread over the threads of ``pool`` if one is given), nothing is parsed."""
+        n = max(0, min(count, self.frames_available - start))
+        fd = self._fh.fileno()
+        at = 0
+        for i in range(n):
+            offsets[i] = at
+            at += self._frames[start + i][1]
+        offsets[n] = at
+        if at > out.size:
+            raise ValueError(f"{self.path}: frames {start} .. {start + n - 1} hold {at} bytes, the buffer {out.size}")
+        flat = memoryview(out).cast("B")
+
+        def one(i):
+            where, need = self._frames[start + i]
+            got, view = 0, flat[int(offsets[i]):int(offsets[i]) + need]
+            while got < need:
+                k = os.preadv(fd, [view[got:]], where + got)
                 if k <= 0:
                     raise ValueError(f"{self.path}: frame {start + i} is truncated")
                 got += k
@@ -435,9 +557,16 @@ class DeviceFrameFeed:
     ``near_gpu``: the staging buffers are allocated, and the producer and its readers run, on the CPUs of the GPU's own NUMA node
     (the caller's threads are left where they are).  On a two-socket host the copy into pinned memory and the DMA out of it
     otherwise cross the sockets' link half of the time: reads 50-60 GB/s and uploads 35-45 while both run, against 85-90 and
-    56 (`scripts/feed_copy_timeline.py`)."""
+    56 (`scripts/feed_copy_timeline.py`).
 
-    def __init__(self, video, batch, device, depth=3, readers=16, pieces=4, near_gpu=True):
+    ``decode_on_device`` (the settings key 'hip decode mjpeg'): True -- a Motion-JPEG AVI whose ``jpeg_layout`` is not None (a
+    supported first frame WITH a restart interval) -- or "always" -- also one without restart markers, for which the host path
+    is the faster one -- is uploaded as chunk bodies and decoded by
+    ``ysmr_mjpeg_decode_batch`` on the copy stream; the per-frame status comes back once per batch, and a frame it flags
+    (outside the supported subset, or damaged) is decoded again by the host path and copied into its place -- with whatever
+    that path raises.  False: every frame takes the host path."""
+
+    def __init__(self, video, batch, device, depth=3, readers=16, pieces=4, near_gpu=True, decode_on_device=True):
         import queue
         import threading
         from concurrent.futures import ThreadPoolExecutor
@@ -449,6 +578,11 @@ class DeviceFrameFeed:
         # uncompressed AVI: the stored frames (bottom-up, padded rows, palette indices) go to the device as they are
         # and are unpacked there; every other source delivers finished frames
         self._raw = getattr(video, "raw_layout", None)
+        # Motion-JPEG AVI: the chunk bodies go to the device as they are and are decoded there
+        if decode_on_device not in (True, False, "always"):
+            raise ValueError("decode_on_device must be True, False or 'always', got {!r}".format(decode_on_device))
+        self._jpeg = video.jpeg_layout_for(self.B, needs_restart=decode_on_device != "always") \
+            if decode_on_device and hasattr(video, "jpeg_layout_for") else None
         self._cpus = cpus_near_gpu(self.device) if near_gpu else None
         with _ThreadOn(self._cpus):      # (pinned pages are the calling thread's node's)
             self._allocate(shape)
@@ -466,7 +600,22 @@ class DeviceFrameFeed:
 
     def _allocate(self, shape):
         import torch
-        if self._raw is not None:
+        if self._jpeg is not None:
+            from . import _lib
+            sampling, _, batch_bytes = self._jpeg
+            # [offsets int64 [B + 1]] [chunk bodies]: one copy per batch, of the bytes used
+            self._jpeg_head = 8 * (self.B + 1)
+            size = self._jpeg_head + batch_bytes
+            self._pinned = [torch.empty(size, dtype=torch.uint8, pin_memory=True) for _ in range(self.depth)]
+            self._jpeg_dev = [torch.empty(size, dtype=torch.uint8, device=self.device) for _ in range(self.depth)]
+            self._status_dev = [torch.empty(self.B, dtype=torch.int32, device=self.device) for _ in range(self.depth)]
+            self._status = [torch.empty(self.B, dtype=torch.int32, pin_memory=True) for _ in range(self.depth)]
+            self._frame_host = torch.empty(shape[1:], dtype=torch.uint8, pin_memory=True)       # for a frame the host decodes
+            ws = _lib.lib().ysmr_mjpeg_decode_workspace_bytes(self.B, shape[1], shape[2], self.video.channels, sampling)
+            if ws == 0:
+                raise ValueError("ysmr_mjpeg_decode_workspace_bytes refuses {} frames of {} x {}".format(self.B, shape[2], shape[1]))
+            self._jpeg_ws = torch.empty(ws, dtype=torch.uint8, device=self.device)             # (the slots' decodes are serial)
+        elif self._raw is not None:
             raw_bytes, _, _, _, palette = self._raw
             self._pinned = [torch.empty((self.B, raw_bytes), dtype=torch.uint8, pin_memory=True) for _ in range(self.depth)]
             self._raw_dev = [torch.empty((self.B, raw_bytes), dtype=torch.uint8, device=self.device) for _ in range(self.depth)]
@@ -490,6 +639,10 @@ class DeviceFrameFeed:
             for f0 in range(0, getattr(self.video, "frames_available", self.video.frame_count), self.B):
                 slot = i % self.depth
                 with self._cv:
+                    busy = self._released[slot] is None
+                if busy:
+                    self._finish_jpeg()      # (the consumer frees this slot only after it has been given what is pending)
+                with self._cv:
                     while self._released[slot] is None and not self._stop:
                         self._cv.wait(0.05)
                     if self._stop:
@@ -498,6 +651,12 @@ class DeviceFrameFeed:
                 if self._uploaded[slot] is not None:
                     self._uploaded[slot].synchronize()          # staging buffer free again
                 host = self._pinned[slot].numpy()
+                if self._jpeg is not None:
+                    n = self._produce_jpeg(f0, slot, released, host)
+                    if n == 0:
+                        break
+                    i += 1
+                    continue
                 # A batch is read and uploaded in `pieces` parts: the upload of a part starts when the part has been read, not
                 # when the batch has (the first batch of a 1228 x 922 file is 280 MB: 5 ms of reading before the first byte
                 # crossed the bus, 4 of the 73 ms a 1920-frame file takes)
@@ -539,9 +698,59 @@ class DeviceFrameFeed:
                 self._uploaded[slot] = ev
                 self._q.put((slot, f0, n, ev))
                 i += 1
+            self._finish_jpeg()
             self._q.put(None)
         except BaseException as exc:   # hand the failure to the consumer
             self._q.put(exc)
+
+    _jpeg_pending = None
+
+    def _produce_jpeg(self, f0, slot, released, host):
+        """Batch ``f0`` as chunk bodies: read, upload, decode on the copy stream.  The batch is handed on when its status has
+        come back, which is waited for only after the NEXT batch has been read and issued (``_finish_jpeg``)."""
+        import torch
+        from . import _lib
+        video, head = self.video, self._jpeg_head
+        offsets = host[:head].view(np.int64)
+        n = video.read_jpeg_into(f0, self.B, host[head:], offsets, self._pool)
+        if n == 0:
+            return 0
+        used = head + int(offsets[n])
+        with torch.cuda.stream(self._copy_stream):
+            if released is not True:
+                self._copy_stream.wait_event(released)          # the kernels that read this device buffer are done
+            self._jpeg_dev[slot][:used].copy_(self._pinned[slot][:used], non_blocking=True)
+            _lib.check(_lib.lib().ysmr_mjpeg_decode_batch(
+                self._copy_stream.cuda_stream, self._jpeg_dev[slot].data_ptr() + head, self._jpeg_dev[slot].data_ptr(), n,
+                video.height, video.width, video.channels, self._jpeg[0], self._jpeg_ws.data_ptr(), self._jpeg_ws.numel(),
+                self._dev[slot].data_ptr(), self._status_dev[slot].data_ptr()), "ysmr_mjpeg_decode_batch")
+            self._status[slot][:n].copy_(self._status_dev[slot][:n], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self._copy_stream)
+        self._uploaded[slot] = ev
+        self._finish_jpeg()
+        self._jpeg_pending = (slot, f0, n, ev)
+        return n
+
+    def _finish_jpeg(self):
+        """Hand the pending Motion-JPEG batch to the consumer: its status is here once its event has passed; the frames the
+        device flagged are decoded by the host path (which raises what it raises today) and copied into their places."""
+        import torch
+        if self._jpeg_pending is None:
+            return
+        (slot, f0, n, ev), self._jpeg_pending = self._jpeg_pending, None
+        ev.synchronize()
+        flagged = np.flatnonzero(self._status[slot][:n].numpy())
+        if len(flagged):
+            with torch.cuda.stream(self._copy_stream):
+                for k in flagged:
+                    self.video._decode_jpeg(self.video._chunk(f0 + int(k)), self._frame_host.numpy())
+                    self._dev[slot][int(k)].copy_(self._frame_host, non_blocking=True)
+                    self._copy_stream.synchronize()             # (the one staging frame is free again)
+                ev = torch.cuda.Event()
+                ev.record(self._copy_stream)
+            self._uploaded[slot] = ev
+        self._q.put((slot, f0, n, ev))
 
     def __iter__(self):
         import torch
@@ -572,6 +781,19 @@ class DeviceFrameFeed:
         self._thread.join(timeout=5.0)
         if self._pool is not None:
             self._pool.shutdown(wait=False)
+
+
+def decode_mjpeg_setting(settings):
+    """The ``decode_on_device`` argument of ``DeviceFrameFeed`` from the optional settings key 'hip decode mjpeg': true
+    (default: Motion-JPEG files with restart markers are decoded on the device), false (every frame by the host path) or
+    'always' (files without restart markers too)."""
+    value = settings.get("hip decode mjpeg", True)
+    if isinstance(value, str):
+        word = value.strip().lower()
+        if word == "always":
+            return "always"
+        return word not in ("false", "0", "no", "off", "")
+    return bool(value)
 
 
 def open_video(path, default_fps=30.0):

@@ -29,7 +29,7 @@ import torch
 
 from . import _lib
 from .detect import Detector, MeanGrayState, mean_gray_params, threshold_params
-from .frames import DeviceFrameFeed, open_video
+from .frames import DeviceFrameFeed, decode_mjpeg_setting, open_video
 from .helper_file import (COLOR_BGR2GRAY, RowStream, create_results_folder, get_configs, get_loggers, rows_to_csv_bytes, rows_to_csv_file, rows_to_csv_file_and_dataframe, rows_device_to_csv_file_and_dataframe,
                           rows_to_dataframe, save_list, wait_for_removals)
 from .tracker import DeviceTracker, rows_to_numpy, sort_rows
@@ -335,6 +335,9 @@ def track_bacteria(video_path, settings=None, result_folder=None, batch=None, ma
     Optional settings key 'hip print rows on device' (default True): the ordered rows' csv text and DataFrame columns are worked
     out on the device (``ysmr_rows_format_device``); False: on the host's threads (``ysmr_rows_write_csv_columns``) -- the same
     bytes and bits either way.  'hip stream rows' (default False): the host's threads print the rows while the video runs.
+    'hip decode mjpeg' (default True): a Motion-JPEG AVI of baseline frames with restart markers is decoded on the device
+    (``ysmr_mjpeg_decode_batch``); 'always': one without restart markers too; False: by Pillow on the reader threads
+    (``frames.decode_mjpeg_setting``).
     """
     logger = logging.getLogger("ysmr").getChild(__name__)
     settings = get_configs(settings)
@@ -589,7 +592,7 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
         rows_upper = 0     # host-side bound on the rows in the device buffer (no sync per batch)
         LAST_PASS_MARKS.clear()
         LAST_PASS_MARKS["pipeline built"] = time.perf_counter() - t_start
-        feed = DeviceFrameFeed(video, pipe.B, pipe.device)
+        feed = DeviceFrameFeed(video, pipe.B, pipe.device, decode_on_device=decode_mjpeg_setting(settings))
         LAST_PASS_MARKS["feed built"] = time.perf_counter() - t_start
         # (rows leave for the host and are printed batch by batch, while later batches run -- unless they are to be appended
         # to the list file in the order they were tracked, 'hip persist rows', which is the older, serial path)
