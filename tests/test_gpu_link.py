@@ -323,3 +323,108 @@ def test_split_link_lane_per_track_over_ring_wraps_and_refreshes(torch_cuda, ora
         got = rows_to_numpy(rows, int(count.item()))
         assert trk.info()[2] == 0
         compare_rows(got, ref_rows)
+
+
+def _clip(seed, n_blobs, n_frames, pitch, vel_sigma, p_drop, n_absent, absent, period=None, spurious_every=None):
+    """Blobs on a jittered lattice of `pitch` px that drift slowly, measured with 0.2 px of noise: no two detections are
+    equidistant from a track within float error.  Random dropouts (lost tracks); the first `n_absent` blobs are missing in
+    frames `absent` = (first, end), again every `period` frames if given (deaths, and births when they return); two
+    spurious detections every `spurious_every`-th frame if given (births)."""
+    rng = np.random.default_rng(seed)
+    side = int(np.ceil(np.sqrt(n_blobs)))
+    base = np.array([(i % side, i // side) for i in range(n_blobs)], float) * pitch + 50 + rng.uniform(-0.2, 0.2, (n_blobs, 2)) * pitch
+    vel = rng.normal(0, vel_sigma, base.shape)
+    frames = []
+    for f in range(n_frames):
+        keep = rng.random(n_blobs) > p_drop
+        if absent[0] <= (f % period if period else f) < absent[1]:
+            keep[:n_absent] = False
+        xy = base[keep] + rng.normal(0, 0.2, (int(keep.sum()), 2))
+        if spurious_every and f % spurious_every == 3:
+            xy = np.vstack([xy, rng.uniform(3000, 3500, (2, 2))])
+        whd = np.column_stack([rng.uniform(1, 9, len(xy)), rng.uniform(1, 9, len(xy)), rng.uniform(0, 90, len(xy))])
+        frames.append(np.column_stack([xy, whd]).astype(np.float32))
+        base += vel
+    return frames
+
+
+def _oracle_rows(oracle, frames, **kw):
+    """The oracle's rows for a clip, and (ids issued, tracks dropped, rows of lost tracks)."""
+    ot = oracle.OracleTracker(shadows=2, **kw)
+    ref, lost = [], 0
+    for f, d in enumerate(frames):
+        ids, xy, info, _ = ot.update(oracle.det_to_rects(d))
+        ref += [(f, tid, float(xy[i][0]), float(xy[i][1]), *map(float, info[i]), float(ot.last_sens[i])) for i, tid in enumerate(ids)]
+        lost += len(ids) - len(d) if len(ids) > len(d) else 0
+    return ref, (ot.next_id, ot.next_id - len(ot.tracks), lost)
+
+
+def test_row_base_is_handed_over_between_run_and_update_calls(torch_cuda, oracle):
+    """One launch per frame (``link_mode(1)``: k_rowmin + k_frame): ``run`` calls of 5 frames append to ONE row buffer
+    through ONE row counter that is never reset, a single-frame ``update`` (rows from 0 in a buffer of its own) after
+    every second of them.  The first k_rowmin of a call takes the first output row from the caller's counter (run) or
+    from 0 (update), every later frame from what the frame before left in the state."""
+    torch = torch_cuda
+    from ysmr_amd import _lib
+    from ysmr_amd.tracker import DeviceTracker, rows_to_numpy
+    kw = dict(max_disappeared=3.0, fps=30.0, n_min=0, n_max=30, n_f=3)
+    frames = _clip(21, 40, 30, 60.0, 0.8, 0.07, n_absent=5, absent=(8, 15), spurious_every=7)
+    ref, (issued, dropped, lost) = _oracle_rows(oracle, frames, **kw)
+    assert issued > 40 + 5 and dropped > 5 and lost > 20          # births, deaths, lost tracks
+    cap, md = 128, 64
+    trk = DeviceTracker(capacity=cap, max_det=md, **kw)
+    trk.link_mode(1)
+    assert trk.fused and not trk.batched
+    rows = torch.empty((len(ref) + 8) * _lib.ROW_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    one = torch.empty(cap * _lib.ROW_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    count = torch.zeros(1, dtype=torch.int64, device="cuda")
+    n_one = torch.zeros(1, dtype=torch.int32, device="cuda")
+    det_all = np.zeros((len(frames), md, 5), np.float32)
+    for f, d in enumerate(frames):
+        det_all[f, :len(d)] = d
+    det_all = torch.from_numpy(det_all).cuda()
+    cnt_all = torch.tensor([len(d) for d in frames], dtype=torch.int32, device="cuda")
+    singles, f, calls = [], 0, 0
+    while f < len(frames):
+        nb = min(5, len(frames) - f)
+        trk.run(det_all[f:f + nb], cnt_all[f:f + nb], f, rows, count)
+        f, calls = f + nb, calls + 1
+        if calls % 2 == 0 and f < len(frames):
+            trk.update(det_all[f, :len(frames[f])].contiguous(), m=len(frames[f]), frame=f, rows=one, n_rows=n_one)
+            singles.append(rows_to_numpy(one, int(n_one.item())).copy())
+            f += 1
+    assert len(singles) == 2
+    from_run = rows_to_numpy(rows, int(count.item()))
+    assert int(count.item()) == len(ref) - sum(len(s) for s in singles)
+    got = np.concatenate([from_run] + singles)
+    got = got[np.argsort(got["frame"], kind="stable")]
+    assert trk.info()[2] == 0
+    compare_rows(got, ref)
+
+
+@pytest.mark.parametrize("n_f", [3, 5])
+def test_split_link_cuts_a_call_longer_than_the_grid_block(torch_cuda, oracle, n_f):
+    """max_det = 2500 is beyond the one-launch link (k_rowmin over the detection grid, k_link, then k_track_lanes for three
+    filters or k_track with a wave per track for five).  One ``run`` call of 260 frames is longer than the 256 frames the
+    grid block holds: it is linked in two pieces, each with its own grid build and first row minima."""
+    torch = torch_cuda
+    from ysmr_amd import _lib
+    from ysmr_amd.tracker import DeviceTracker, rows_to_numpy
+    kw = dict(max_disappeared=3.0, fps=30.0, n_min=0, n_max=30, n_f=n_f)
+    frames = [d[np.sort(np.random.default_rng(f).permutation(len(d))[:8 + f % 5])] for f, d in
+              enumerate(_clip(22, 12, 260, 100.0, 0.15, 0.0, n_absent=3, absent=(40, 50), period=60))]
+    assert {len(d) for d in frames} == {8, 9, 10, 11, 12}
+    ref, (issued, dropped, lost) = _oracle_rows(oracle, frames, **kw)
+    assert issued > 12 + 5 and dropped > 5 and lost > 100         # births, deaths, lost tracks
+    cap, md = 64, 2500
+    trk = DeviceTracker(capacity=cap, max_det=md, **kw)
+    assert not trk.fused and not trk.batched
+    det = np.zeros((len(frames), md, 5), np.float32)
+    for f, d in enumerate(frames):
+        det[f, :len(d)] = d
+    rows = torch.empty((len(ref) + 8) * _lib.ROW_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    count = torch.zeros(1, dtype=torch.int64, device="cuda")
+    trk.run(torch.from_numpy(det).cuda(), torch.tensor([len(d) for d in frames], dtype=torch.int32, device="cuda"), 0, rows, count)
+    got = rows_to_numpy(rows, int(count.item()))
+    assert trk.info()[2] == 0
+    compare_rows(got, ref)

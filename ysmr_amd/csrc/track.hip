@@ -128,10 +128,6 @@ struct ysmr_tracker {
     void *block;       // the single device allocation
     size_t block_bytes;
     std::vector<double> gains_host;
-    bool set_base;                 // fused path: the next k_rowmin also sets row_base from base_ptr
-    const long long *base_ptr;
-    const void *rowmin_for = nullptr;   // fused path: the frame (its detections' address) whose row minima the last launch of
-                                        // the previous ysmr_tracker_run_chained call has already left in the state
     void *grid_block = nullptr;    // split path: DetGrid arrays for grid_frames frames; batch link: k_bgrid's blocks
     int grid_frames = 0;           //   (allocated by ysmr_tracker_create: no allocation on the call path)
     // batch link (batch_link.h): the handle can link a whole batch per launch; where the state rests right now
@@ -201,7 +197,6 @@ extern "C" int ysmr_debug_read_stamps(unsigned long long *out) { return (int)hip
 // when every wave of a frame's k_track finished (plain stores, one slot per wave; the host takes the maximum)
 __device__ unsigned long long g_wave_end[64 * 8192];
 #define TRACK_END() do { if ((threadIdx.x & 63) == 0 && i < 8192) { unsigned long long t_; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); g_wave_end[(frame & 63) * 8192 + i] = t_; } } while (0)
-#define TRACK_END_TO_RING() do {} while (0)
 extern "C" int ysmr_debug_read_wave_end(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_end), sizeof(unsigned long long) * 64 * 8192); }
 #else
 #define GSTAMP(k) do {} while (0)
@@ -209,7 +204,6 @@ extern "C" int ysmr_debug_read_wave_end(unsigned long long *out) { return (int)h
 #define RING(tag) do {} while (0)
 #define LRING(k) do {} while (0)
 #define TRACK_END() do {} while (0)
-#define TRACK_END_TO_RING() do {} while (0)
 #endif
 
 namespace {
@@ -925,7 +919,7 @@ __device__ __forceinline__ void gsff_wave(const TrackerDev &t, const double *gai
 template <typename DetT, int NF, bool D3 = false>
 __global__ __launch_bounds__(256) void k_track(TrackerDev t, int frame, ysmr_row *rows, long long rows_capacity,
                                                const DetT *__restrict__ det, const DetT *__restrict__ next_det,
-                                               int next_m_host, const int32_t *next_m_dev, DetGrid next_grid, Third3<D3> th)
+                                               const int32_t *next_m_dev, DetGrid next_grid, Third3<D3> th)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) RING((4ull << 40) | (unsigned)frame);   // k_track entry
     BSTAMP(0);
@@ -945,7 +939,7 @@ __global__ __launch_bounds__(256) void k_track(TrackerDev t, int frame, ysmr_row
     if (i >= n_live) return;
     const int lane = threadIdx.x & 63;
     // the next frame's detections do not depend on this frame's state: fetch them first
-    const int m_next = next_det ? det_count(next_m_host, next_m_dev, t.max_det, nullptr) : 0;
+    const int m_next = next_det ? det_count(-1, next_m_dev, t.max_det, nullptr) : 0;
     DetChunk<DetT> first;
     if (m_next > 0 && !next_grid.start) load_chunk(first, next_det, m_next, 0, lane);
     const int slot = __builtin_amdgcn_readfirstlane(slot_spec);
@@ -1231,7 +1225,6 @@ __global__ __launch_bounds__(LINK_THREADS) void k_link(TrackerDev t, const DetT 
     const int tid = threadIdx.x;
     const int cap = t.capacity;
     if (tid == 0) RING((9ull << 40) | (unsigned)frame);    // entry (before the first load)
-    TRACK_END_TO_RING();
     const int n = *t.n_tracks, nfree0 = *t.n_free;
     int nfree_now = nfree0;        // (the register-resident path keeps the height of the free stack here)
     const int m = det_count(m_host, m_dev, t.max_det, t.err);
@@ -1688,7 +1681,7 @@ __global__ __launch_bounds__(FRAME_THREADS) void k_frame(TrackerDev a, TrackerDe
                                                          int32_t *n_rows_out, int32_t *claim_out, int32_t *n_before_out,
                                                          int32_t *new_cols_out, int32_t *n_new_out,
                                                          const DetT *__restrict__ next_det, const int32_t *next_m_dev,
-                                                         int base_from_ext, Third3<D3> th)
+                                                         Third3<D3> th)
 {
     extern __shared__ unsigned long long s_raw[];
     __shared__ int s_n_used, s_n_dead, s_set_state[2];
@@ -1715,9 +1708,7 @@ __global__ __launch_bounds__(FRAME_THREADS) void k_frame(TrackerDev a, TrackerDe
     const int32_t *mn_ptr = next_det ? next_m_dev : a.n_tracks;
     const int n_raw = *a.n_tracks, nfree_raw = *a.n_free, id0_raw = *a.next_id;
     const int m_raw = *m_ptr, mn_raw = *mn_ptr;
-    // (first frame of a run whose k_rowmin -- which also takes the caller's row count as the base -- was not needed)
-    const long long *base_ptr = (base_from_ext && row_count_ext) ? row_count_ext : a.row_base;
-    const long long row_base_raw = *base_ptr;
+    const long long row_base = *a.row_base;     // (the previous frame's launch left it, or the call's k_rowmin)
     constexpr int SPEC_ROWS = 3;       // table rows tid + 256k, k < 3, are fetched before n is known
     const int i = blockIdx.x * 4 + wave;
     int so[SPEC_ROWS], sg[SPEC_ROWS], sa[SPEC_ROWS];
@@ -1739,7 +1730,6 @@ __global__ __launch_bounds__(FRAME_THREADS) void k_frame(TrackerDev a, TrackerDe
     // of the [max_det][5] frame slice are stale; rowmin_wave masks them; without a next frame this frame's are read)
     DetChunk<DetT> first;
     load_chunk(first, next_det ? next_det : det, md, 0, lane);
-    const long long row_base = (base_from_ext && !row_count_ext) ? 0ll : row_base_raw;
     const int n = __builtin_amdgcn_readfirstlane(n_raw);
     const int nfree = __builtin_amdgcn_readfirstlane(nfree_raw), id0 = __builtin_amdgcn_readfirstlane(id0_raw);
     int m = __builtin_amdgcn_readfirstlane(m_host < 0 ? m_raw : m_host);
@@ -2045,94 +2035,79 @@ void closed_form_gain(int N, double *g)
     }
 }
 
-template <typename DetT>
-int launch_update_t(ysmr_tracker *t, hipStream_t st, const DetT *det, int m, const int32_t *m_dev, int frame,
-                    ysmr_row *rows, long long rows_capacity, long long *row_count, int32_t *n_rows, int32_t *claim,
-                    int32_t *n_before, int32_t *new_cols, int32_t *n_new, bool rowmin_done, const DetT *next_det,
-                    const int32_t *next_m_dev, DetGrid grid = DetGrid{nullptr, nullptr, nullptr, nullptr},
-                    DetGrid next_grid = DetGrid{nullptr, nullptr, nullptr, nullptr}, bool base_from_ext = false,
-                    const double *third = nullptr, const double *next_third = nullptr)
+// One frame through the per-frame kernels.  `det` is [m][5] float (double with `f64`); the count is `m`, or *m_dev when m < 0.
+struct FrameArgs {
+    const void *det = nullptr;
+    bool f64 = false;
+    int m = -1;
+    const int32_t *m_dev = nullptr;
+    int frame = 0;
+    ysmr_row *rows = nullptr;
+    long long rows_capacity = 0;
+    long long *row_count = nullptr;      // the caller's running row count (NULL: a call of its own, rows from 0)
+    int32_t *n_rows = nullptr, *claim = nullptr, *n_before = nullptr, *new_cols = nullptr, *n_new = nullptr;
+    const void *next_det = nullptr;      // the frame whose row minima this launch leaves behind (NULL: none)
+    const int32_t *next_m_dev = nullptr;
+    DetGrid grid{}, next_grid{};         // split path, 2-D: the grids over `det` and `next_det`
+    const double *third = nullptr, *next_third = nullptr;    // 3-D handle: the third coordinate of `det` and `next_det`
+    bool rowmin_done = false;            // the previous frame's launch left this frame's row minima (false: the first frame of
+                                         // a call, or of a split-path chunk -- k_rowmin goes first)
+};
+
+template <typename DetT, bool D3>
+int launch_frame_t(ysmr_tracker *t, hipStream_t st, const FrameArgs &a)
 {
-    const DetGrid no_grid{nullptr, nullptr, nullptr, nullptr};
+    const DetT *det = (const DetT *)a.det, *next_det = (const DetT *)a.next_det;
     const dim3 wgrid((t->d.capacity + 3) / 4);
+    Third3<D3> th{};
+    if constexpr (D3) th = {t->pos3, a.third, next_det ? a.next_third : nullptr};
+    // the filter bank is unrolled at compile time: 3 covers tracking.ini's default (and 1, 2), 8 the rest (a 3-D handle has none)
+    const bool wide = !D3 && t->d.n_f > 3;
     t->linked = true;
-    if (t->dims == 3) {
-        // the same launches with the third coordinate: all-pairs row minima (no grids), no filter bank (n_f = 1), k_track
-        // with a wave per track
-        const Third3<true> th{t->pos3, third, next_det ? next_third : nullptr};
-        if (t->fused) {
-            const TrackerDev &a = t->cur(), &b = t->nxt();
-            if (!rowmin_done) {
-                hipLaunchKernelGGL((k_rowmin<DetT, true>), wgrid, dim3(256), 0, st, a, det, m, m_dev, t->set_base ? 1 : 0, t->base_ptr,
-                                   no_grid, th);
-                t->set_base = false;
-            }
-            hipLaunchKernelGGL((k_frame<DetT, 3, true>), wgrid, dim3(FRAME_THREADS), t->frame_lds, st, a, b, det, m, m_dev, frame,
-                               rows, rows_capacity, row_count, n_rows, claim, n_before, new_cols, n_new, next_det, next_m_dev,
-                               base_from_ext ? 1 : 0, th);
-            t->par ^= 1;
-        } else {
-            const TrackerDev &d = t->d;
-            if (!rowmin_done)
-                hipLaunchKernelGGL((k_rowmin<DetT, true>), wgrid, dim3(256), 0, st, d, det, m, m_dev, 0, nullptr, no_grid, th);
-            const size_t link_lds = 12 * (size_t)d.max_det;
-            if (link_lds <= 140 * 1024)
-                hipLaunchKernelGGL((k_link<DetT, true, true>), dim3(1), dim3(LINK_THREADS), link_lds, st, d, det, m, m_dev, frame,
-                                   rows, rows_capacity, row_count, n_rows, claim, n_before, new_cols, n_new, th);
-            else
-                hipLaunchKernelGGL((k_link<DetT, false, true>), dim3(1), dim3(LINK_THREADS), 0, st, d, det, m, m_dev, frame, rows,
-                                   rows_capacity, row_count, n_rows, claim, n_before, new_cols, n_new, th);
-            hipLaunchKernelGGL((k_track<DetT, 3, true>), wgrid, dim3(256), 0, st, d, frame, rows, rows_capacity, det, next_det, -1,
-                               next_m_dev, no_grid, th);
-        }
-        YSMR_LAUNCH_CHECK();
-        return YSMR_OK;
-    }
-    const Third3<false> th{};
     if (t->fused) {
-        const TrackerDev &a = t->cur(), &b = t->nxt();
-        if (!rowmin_done) {
-            hipLaunchKernelGGL(k_rowmin<DetT>, wgrid, dim3(256), 0, st, a, det, m, m_dev, t->set_base ? 1 : 0, t->base_ptr, no_grid, th);
-            t->set_base = false;
-        }
-        // the filter bank is unrolled at compile time: 3 covers tracking.ini's default (and 1, 2), 8 the rest
-        if (a.n_f <= 3)
-            hipLaunchKernelGGL((k_frame<DetT, 3>), wgrid, dim3(FRAME_THREADS), t->frame_lds, st, a, b, det, m, m_dev, frame,
-                               rows, rows_capacity, row_count, n_rows, claim, n_before, new_cols, n_new, next_det, next_m_dev,
-                               base_from_ext ? 1 : 0, th);
-        else
-            hipLaunchKernelGGL((k_frame<DetT, YSMR_MAX_FILTERS>), wgrid, dim3(FRAME_THREADS), t->frame_lds, st, a, b, det, m,
-                               m_dev, frame, rows, rows_capacity, row_count, n_rows, claim, n_before, new_cols, n_new,
-                               next_det, next_m_dev, base_from_ext ? 1 : 0, th);
+        const TrackerDev &c = t->cur(), &n = t->nxt();
+        // (a call's first frame: k_rowmin also sets the first output row -- *a.row_count in a run, 0 when it is NULL, an update)
+        if (!a.rowmin_done)
+            hipLaunchKernelGGL((k_rowmin<DetT, D3>), wgrid, dim3(256), 0, st, c, det, a.m, a.m_dev, 1, a.row_count, DetGrid{}, th);
+        auto frame = k_frame<DetT, 3, D3>;
+        if constexpr (!D3) if (wide) frame = k_frame<DetT, YSMR_MAX_FILTERS>;
+        hipLaunchKernelGGL(frame, wgrid, dim3(FRAME_THREADS), t->frame_lds, st, c, n, det, a.m, a.m_dev, a.frame, a.rows,
+                           a.rows_capacity, a.row_count, a.n_rows, a.claim, a.n_before, a.new_cols, a.n_new, next_det, a.next_m_dev, th);
         t->par ^= 1;
     } else {
         const TrackerDev &d = t->d;
-        if (!rowmin_done) hipLaunchKernelGGL(k_rowmin<DetT>, wgrid, dim3(256), 0, st, d, det, m, m_dev, 0, nullptr, grid, th);
+        if (!a.rowmin_done)
+            hipLaunchKernelGGL((k_rowmin<DetT, D3>), wgrid, dim3(256), 0, st, d, det, a.m, a.m_dev, 0, nullptr, a.grid, th);
         const size_t link_lds = 12 * (size_t)d.max_det;
 #ifdef YSMR_TUNING
         static const bool hbm_tables = getenv("YSMR_LINK_TABLES") && !strcmp(getenv("YSMR_LINK_TABLES"), "hbm");
 #else
         const bool hbm_tables = false;
 #endif
-        if (link_lds <= 140 * 1024 && !hbm_tables)
-            hipLaunchKernelGGL((k_link<DetT, true>), dim3(1), dim3(LINK_THREADS), link_lds, st, d, det, m, m_dev, frame, rows,
-                               rows_capacity, row_count, n_rows, claim, n_before, new_cols, n_new, th);
-        else
-            hipLaunchKernelGGL((k_link<DetT, false>), dim3(1), dim3(LINK_THREADS), 0, st, d, det, m, m_dev, frame, rows,
-                               rows_capacity, row_count, n_rows, claim, n_before, new_cols, n_new, th);
+        const bool lds_tables = link_lds <= 140 * 1024 && (D3 || !hbm_tables);     // (the tuning hook is 2-D only)
+        auto link = k_link<DetT, true, D3>;
+        if (!lds_tables) link = k_link<DetT, false, D3>;
+        hipLaunchKernelGGL(link, dim3(1), dim3(LINK_THREADS), lds_tables ? link_lds : 0, st, d, det, a.m, a.m_dev, a.frame, a.rows,
+                           a.rows_capacity, a.row_count, a.n_rows, a.claim, a.n_before, a.new_cols, a.n_new, th);
         if (t->lanes) {
             hipLaunchKernelGGL(k_track_lanes<DetT>, dim3((d.capacity + TL_THREADS - 1) / TL_THREADS), dim3(TL_THREADS), 0, st, d, t->bd,
-                               t->bgains_dev, t->lanes_head, frame, rows, rows_capacity, det, next_det, next_m_dev, next_grid);
+                               t->bgains_dev, t->lanes_head, a.frame, a.rows, a.rows_capacity, det, next_det, a.next_m_dev, a.next_grid);
             t->lanes_head = (t->lanes_head + 1) & (BL_HB - 1);
-        } else if (d.n_f <= 3)
-            hipLaunchKernelGGL((k_track<DetT, 3>), wgrid, dim3(256), 0, st, d, frame, rows, rows_capacity, det, next_det, -1,
-                               next_m_dev, next_grid, th);
-        else
-            hipLaunchKernelGGL((k_track<DetT, YSMR_MAX_FILTERS>), wgrid, dim3(256), 0, st, d, frame, rows, rows_capacity, det,
-                               next_det, -1, next_m_dev, next_grid, th);
+        } else {
+            auto track = k_track<DetT, 3, D3>;
+            if constexpr (!D3) if (wide) track = k_track<DetT, YSMR_MAX_FILTERS>;
+            hipLaunchKernelGGL(track, wgrid, dim3(256), 0, st, d, a.frame, a.rows, a.rows_capacity, det, next_det, a.next_m_dev,
+                               a.next_grid, th);
+        }
     }
     YSMR_LAUNCH_CHECK();
     return YSMR_OK;
+}
+
+int launch_frame(ysmr_tracker *t, hipStream_t st, const FrameArgs &a)
+{
+    if (t->dims == 3) return a.f64 ? launch_frame_t<double, true>(t, st, a) : launch_frame_t<float, true>(t, st, a);
+    return a.f64 ? launch_frame_t<double, false>(t, st, a) : launch_frame_t<float, false>(t, st, a);
 }
 
 __global__ void k_peek(TrackerDev t, int32_t *ids, double *xy, int32_t *gone, int32_t *n_out)
@@ -2300,8 +2275,6 @@ int ysmr_tracker_create(double max_disappeared, double fps, int n_min, double n_
         q.row_min = (double *)(b + o_rmin1); q.row_arg = (int *)(b + o_rarg1);
     }
     t->par = 0;
-    t->set_base = false;
-    t->base_ptr = nullptr;
     t->frame_lds = frame_lds_bytes(capacity, max_det, (int)gain_doubles);
 #ifdef YSMR_TUNING
     const char *mode_env = getenv("YSMR_LINK_MODE");   // "split" forces the two-kernel path (tuning builds only)
@@ -2450,7 +2423,6 @@ int ysmr_tracker_reset(ysmr_tracker *t, void *stream)
     if (!t) return ysmr::fail(YSMR_ERR_ARG, "tracker handle is NULL");
     int n = t->d.capacity > t->d.max_det ? t->d.capacity : t->d.max_det;
     t->par = 0;
-    t->rowmin_for = nullptr;
     t->prepared[0] = t->prepared[1] = ysmr_tracker::Prepared();
     if (t->lanes) {                    // (ids start over: a slot's old filter state must not pass for the new track 0's)
         YSMR_HIP_CHECK(hipMemsetAsync(t->bd.i32, 0xFF, sizeof(int) * (size_t)t->bd.seat_cap, (hipStream_t)stream));
@@ -2487,7 +2459,6 @@ static int state_to_std(ysmr_tracker *t, hipStream_t st)
     YSMR_LAUNCH_CHECK();
     t->in_batch = false;
     t->par = 0;
-    t->rowmin_for = nullptr;
     return YSMR_OK;
 }
 static int state_to_batch(ysmr_tracker *t, hipStream_t st)
@@ -2501,7 +2472,6 @@ static int state_to_batch(ysmr_tracker *t, hipStream_t st)
     }
     t->in_batch = true;
     t->par = 0;
-    t->rowmin_for = nullptr;
     return YSMR_OK;
 }
 
@@ -2569,18 +2539,44 @@ int ysmr_debug_read_grid_block(ysmr_tracker *t, int slot, int frame, void *out, 
     return e == hipSuccess ? YSMR_OK : ysmr::fail(YSMR_ERR_HIP, "grid block read failed: %s", hipGetErrorString(e));
 }
 
+// The handle's batch-link arrays with grid block `block` of its dimension: 0, 1 are ysmr_tracker_prepare's callers', 2 is run's own.
+static BatchDev batch_dev(const ysmr_tracker *t, int block)
+{
+    BatchDev bd = t->bd;
+    if (t->dims == 3) { bd.grid = (char *)t->grid3_block; bd.grid_stride = t->grid3_stride; }
+    bd.grid += (size_t)block * BL_MAX_BATCH * bd.grid_stride;
+    return bd;
+}
+
+// `batch` frames of detections binned frame by frame into a grid block (`third` is NULL for a 2-D handle)
+static void bin_batch(const ysmr_tracker *t, hipStream_t st, const float *det, const double *third, const int32_t *count, int batch,
+                      const BatchDev &bd)
+{
+    if (t->dims == 3)
+        hipLaunchKernelGGL(k_bgrid3, dim3(batch), dim3(BG_THREADS), 4 * (size_t)bl3_lds_dwords_max(t->d.max_det), st, det, third, count,
+                           t->d.max_det, bd.grid, bd.grid_stride);
+    else
+        hipLaunchKernelGGL(k_bgrid, dim3(batch), dim3(BG_THREADS), bd.grid_stride, st, det, count, t->d.max_det, bd.grid, bd.grid_stride);
+}
+
+static int tracker_prepare(ysmr_tracker *t, hipStream_t st, const float *det_dev, const double *third_dev, const int32_t *det_count_dev,
+                           int batch, int slot)
+{
+    if (!t->use_batch() || batch > BL_MAX_BATCH) return YSMR_OK;       // (nothing to prepare: the run call does it all)
+    bin_batch(t, st, det_dev, third_dev, det_count_dev, batch, batch_dev(t, slot));
+    YSMR_LAUNCH_CHECK();
+    t->prepared[slot] = ysmr_tracker::Prepared{det_dev, det_count_dev, third_dev, batch};
+    return YSMR_OK;
+}
+
 int ysmr_tracker_prepare(ysmr_tracker *t, void *stream, const float *det_dev, const int32_t *det_count_dev, int batch, int slot)
 {
     if (!t) return ysmr::fail(YSMR_ERR_ARG, "tracker handle is NULL");
     if (!det_dev || !det_count_dev || batch <= 0 || slot < 0 || slot > 1)
         return ysmr::fail(YSMR_ERR_ARG, "det_dev, det_count_dev must be set, batch > 0, slot 0 or 1");
     // (a 3-D handle: a no-op, as it has always been -- its binning takes the third coordinate, ysmr_tracker_prepare3)
-    if (t->dims != 2 || !t->use_batch() || batch > BL_MAX_BATCH) return YSMR_OK;       // (nothing to prepare: ysmr_tracker_run does it all)
-    hipLaunchKernelGGL(k_bgrid, dim3(batch), dim3(BG_THREADS), t->bd.grid_stride, (hipStream_t)stream, det_dev, det_count_dev,
-                       t->d.max_det, t->bd.grid + (size_t)slot * BL_MAX_BATCH * t->bd.grid_stride, t->bd.grid_stride);
-    YSMR_LAUNCH_CHECK();
-    t->prepared[slot].det = det_dev; t->prepared[slot].count = det_count_dev; t->prepared[slot].batch = batch;
-    return YSMR_OK;
+    if (t->dims != 2) return YSMR_OK;
+    return tracker_prepare(t, (hipStream_t)stream, det_dev, nullptr, det_count_dev, batch, slot);
 }
 
 int ysmr_tracker_prepare3(ysmr_tracker *t, void *stream, const float *det_dev, const double *third_dev, const int32_t *det_count_dev,
@@ -2590,14 +2586,21 @@ int ysmr_tracker_prepare3(ysmr_tracker *t, void *stream, const float *det_dev, c
     if (!det_dev || !third_dev || !det_count_dev || batch <= 0 || slot < 0 || slot > 1)
         return ysmr::fail(YSMR_ERR_ARG, "det_dev, third_dev, det_count_dev must be set, batch > 0, slot 0 or 1");
     if (t->dims != 3) return ysmr::fail(YSMR_ERR_STATE, "ysmr_tracker_prepare3 needs a 3-D handle (ysmr_tracker_dimensions)");
-    if (!t->use_batch() || batch > BL_MAX_BATCH) return YSMR_OK;       // (nothing to prepare: ysmr_tracker_run3 does it all)
-    hipLaunchKernelGGL(k_bgrid3, dim3(batch), dim3(BG_THREADS), 4 * (size_t)bl3_lds_dwords_max(t->d.max_det), (hipStream_t)stream, det_dev,
-                       third_dev, det_count_dev, t->d.max_det, (char *)t->grid3_block + (size_t)slot * BL_MAX_BATCH * t->grid3_stride,
-                       t->grid3_stride);
-    YSMR_LAUNCH_CHECK();
-    t->prepared[slot].det = det_dev; t->prepared[slot].third = third_dev; t->prepared[slot].count = det_count_dev;
-    t->prepared[slot].batch = batch;
-    return YSMR_OK;
+    return tracker_prepare(t, (hipStream_t)stream, det_dev, third_dev, det_count_dev, batch, slot);
+}
+
+// one frame at a time: the per-frame kernels, rows from 0 (`third` is NULL for a 2-D handle)
+static int tracker_update(ysmr_tracker *t, hipStream_t st, const void *det_dev, int det_is_f64, const double *third_dev, int m,
+                          const int32_t *m_dev, int32_t frame_index, ysmr_row *rows_dev, int32_t *n_rows_dev, int32_t *claim_col_dev,
+                          int32_t *n_before_dev, int32_t *new_cols_dev, int32_t *n_new_dev)
+{
+    if (int rc = state_to_std(t, st)) return rc;
+    FrameArgs a;
+    a.det = det_dev; a.f64 = det_is_f64 != 0; a.third = third_dev;
+    a.m = m; a.m_dev = m_dev; a.frame = frame_index;
+    a.rows = rows_dev; a.rows_capacity = t->d.capacity;
+    a.n_rows = n_rows_dev; a.claim = claim_col_dev; a.n_before = n_before_dev; a.new_cols = new_cols_dev; a.n_new = n_new_dev;
+    return launch_frame(t, st, a);
 }
 
 int ysmr_tracker_update(ysmr_tracker *t, void *stream, const void *det_dev, int det_is_f64, int m,
@@ -2609,101 +2612,8 @@ int ysmr_tracker_update(ysmr_tracker *t, void *stream, const void *det_dev, int 
     if (m > t->d.max_det) return ysmr::fail(YSMR_ERR_CAPACITY, "m = %d exceeds max_det = %d", m, t->d.max_det);
     if (!det_dev && m != 0) return ysmr::fail(YSMR_ERR_ARG, "det_dev is NULL");
     if (t->dims != 2) return ysmr::fail(YSMR_ERR_STATE, "a 3-D handle is updated with ysmr_tracker_update3");
-    if (int rc = state_to_std(t, (hipStream_t)stream)) return rc;     // (one frame at a time: the per-frame kernels)
-    t->rowmin_for = nullptr;
-    if (t->fused) { t->set_base = true; t->base_ptr = nullptr; }
-    if (det_is_f64)
-        return launch_update_t<double>(t, (hipStream_t)stream, (const double *)det_dev, m, m_dev, frame_index, rows_dev,
-                                       t->d.capacity, nullptr, n_rows_dev, claim_col_dev, n_before_dev, new_cols_dev,
-                                       n_new_dev, false, nullptr, nullptr);
-    return launch_update_t<float>(t, (hipStream_t)stream, (const float *)det_dev, m, m_dev, frame_index, rows_dev,
-                                  t->d.capacity, nullptr, n_rows_dev, claim_col_dev, n_before_dev, new_cols_dev,
-                                  n_new_dev, false, nullptr, nullptr);
-}
-
-int ysmr_tracker_run(ysmr_tracker *t, void *stream, const float *det_dev, const int32_t *det_count_dev, int batch,
-                     int32_t first_frame_index, ysmr_row *rows_dev, int64_t rows_capacity, int64_t *row_count_dev)
-{
-    if (!t) return ysmr::fail(YSMR_ERR_ARG, "tracker handle is NULL");
-    if (!det_dev || !det_count_dev || !rows_dev || !row_count_dev || batch <= 0)
-        return ysmr::fail(YSMR_ERR_ARG, "det_dev, det_count_dev, rows_dev, row_count_dev must be set and batch > 0");
-    if (t->dims != 2) return ysmr::fail(YSMR_ERR_STATE, "a 3-D handle is run with ysmr_tracker_run3");
-    t->linked = true;
-    // (ysmr_tracker_run_chained, which also took the NEXT call's first frame, left the ABI with version 12: its look-ahead
-    // had been ignored since version 10 -- a launch that had the next call's first row minima ready had to take its first
-    // output row from *row_count_dev, the word its own first workgroup advances, ADVICE r03 -- and a batch-link handle
-    // links a batch with ONE launch, so there is nothing to chain.)
-    const float *after_det_dev = nullptr;
-    const int32_t *after_count_dev = nullptr;
-    if (t->use_batch()) {
-        // one launch links the batch (cut to the BL_MAX_BATCH frames the grid block holds); `after` has nothing to save here
-        if (int rc = state_to_batch(t, (hipStream_t)stream)) return rc;
-        for (int f0 = 0; f0 < batch; f0 += BL_MAX_BATCH) {
-            const int nb = batch - f0 < BL_MAX_BATCH ? batch - f0 : BL_MAX_BATCH;
-            const float *det = det_dev + (size_t)f0 * t->d.max_det * 5;
-            // the batch's detections binned frame by frame: by ysmr_tracker_prepare ahead of this call, or here
-            int block = 2;
-            for (int s = 0; s < 2; ++s)
-                if (f0 == 0 && batch <= BL_MAX_BATCH && t->prepared[s].det == (const void *)det_dev &&
-                    t->prepared[s].count == (const void *)det_count_dev && t->prepared[s].batch == batch) {
-                    block = s;
-                    t->prepared[s] = ysmr_tracker::Prepared();       // (good for one call)
-                }
-            BatchDev bd = t->bd;
-            bd.grid = t->bd.grid + (size_t)block * BL_MAX_BATCH * t->bd.grid_stride;
-            if (block == 2)
-                hipLaunchKernelGGL(k_bgrid, dim3(nb), dim3(BG_THREADS), t->bd.grid_stride, (hipStream_t)stream, det,
-                                   det_count_dev + f0, t->d.max_det, bd.grid, bd.grid_stride);
-            BlKernArgs ka;
-            ka.t = t->d; ka.bd = bd; ka.det_all = det; ka.det_count = det_count_dev + f0; ka.batch = nb;
-            ka.frame0 = first_frame_index + f0; ka.rows = rows_dev; ka.rows_capacity = (long long)rows_capacity;
-            ka.row_count = (long long *)row_count_dev; ka.gains = t->bgains_dev;
-            for (int k = 0; k < 4; ++k) ka.hz[k] = (k == 0 || k < t->d.n_f) && k < BL_NF ? t->d.n_i[k] : 0x7FFFFFFF;
-            if (BL_PAUSE_TICKS > 0) hipLaunchKernelGGL(k_pause, dim3(1), dim3(64), 0, (hipStream_t)stream, BL_PAUSE_TICKS);
-            hipLaunchKernelGGL(k_batch, dim3(1), dim3(BL_THREADS), t->batch_lds, (hipStream_t)stream, ka);
-            YSMR_LAUNCH_CHECK();
-        }
-        return YSMR_OK;
-    }
-    if (int rc = state_to_std(t, (hipStream_t)stream)) return rc;
-    // the previous call may have left this call's first row minima behind (it was told this frame comes next)
-    const bool have_rowmin = t->fused && t->rowmin_for != nullptr && t->rowmin_for == (const void *)det_dev;
-    t->rowmin_for = nullptr;
-    if (t->fused) { t->set_base = !have_rowmin; t->base_ptr = (const long long *)row_count_dev; }
-    const DetGrid no_grid{nullptr, nullptr, nullptr, nullptr};
-    bool grids = false;
-    if (!t->fused) {
-        // large tables: a uniform grid over every frame's detections, built for the whole batch in one launch
-        // (the detections of a batch are all there before the first frame is linked)
-        const size_t per = ysmr_tracker::grid_bytes_per_frame(t->d.max_det);
-        if (batch > t->grid_frames) {      // (the grid block was sized by ysmr_tracker_create: longer batches go in pieces)
-            for (int f0 = 0; f0 < batch; f0 += t->grid_frames) {
-                const int nb = batch - f0 < t->grid_frames ? batch - f0 : t->grid_frames;
-                if (int rc = ysmr_tracker_run(t, stream, det_dev + (size_t)f0 * t->d.max_det * 5, det_count_dev + f0, nb,
-                                              first_frame_index + f0, rows_dev, rows_capacity, row_count_dev))
-                    return rc;
-            }
-            return YSMR_OK;
-        }
-        hipLaunchKernelGGL(k_grid_build<float>, dim3(batch), dim3(1024), 0, (hipStream_t)stream, det_dev, det_count_dev,
-                           t->d.max_det, (char *)t->grid_block, per);
-        YSMR_LAUNCH_CHECK();
-        grids = true;
-    }
-    for (int f = 0; f < batch; ++f) {
-        const bool inside = f + 1 < batch, has_next = inside || after_det_dev != nullptr;
-        const float *next_det = inside ? det_dev + (size_t)(f + 1) * t->d.max_det * 5 : after_det_dev;
-        const int32_t *next_m = inside ? det_count_dev + f + 1 : after_count_dev;
-        int rc = launch_update_t<float>(t, (hipStream_t)stream, det_dev + (size_t)f * t->d.max_det * 5, -1,
-                                        det_count_dev + f, first_frame_index + f, rows_dev, (long long)rows_capacity,
-                                        (long long *)row_count_dev, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                        f > 0 || have_rowmin, has_next ? next_det : nullptr, has_next ? next_m : nullptr,
-                                        grids ? t->grid(f) : no_grid, grids && inside ? t->grid(f + 1) : no_grid,
-                                        f == 0 && have_rowmin);
-        if (rc) return rc;
-    }
-    if (after_det_dev) t->rowmin_for = (const void *)after_det_dev;
-    return YSMR_OK;
+    return tracker_update(t, (hipStream_t)stream, det_dev, det_is_f64, nullptr, m, m_dev, frame_index, rows_dev, n_rows_dev,
+                          claim_col_dev, n_before_dev, new_cols_dev, n_new_dev);
 }
 
 int ysmr_tracker_update3(ysmr_tracker *t, void *stream, const void *det_dev, int det_is_f64, const double *third_dev, int m,
@@ -2715,17 +2625,96 @@ int ysmr_tracker_update3(ysmr_tracker *t, void *stream, const void *det_dev, int
     if (m > t->d.max_det) return ysmr::fail(YSMR_ERR_CAPACITY, "m = %d exceeds max_det = %d", m, t->d.max_det);
     if ((!det_dev || !third_dev) && m != 0) return ysmr::fail(YSMR_ERR_ARG, "det_dev / third_dev is NULL");
     if (t->dims != 3) return ysmr::fail(YSMR_ERR_STATE, "ysmr_tracker_update3 needs a 3-D handle (ysmr_tracker_dimensions)");
-    if (int rc = state_to_std(t, (hipStream_t)stream)) return rc;     // (one frame at a time: the per-frame kernels)
-    t->rowmin_for = nullptr;
-    if (t->fused) { t->set_base = true; t->base_ptr = nullptr; }
-    const DetGrid no_grid{nullptr, nullptr, nullptr, nullptr};
-    if (det_is_f64)
-        return launch_update_t<double>(t, (hipStream_t)stream, (const double *)det_dev, m, m_dev, frame_index, rows_dev,
-                                       t->d.capacity, nullptr, n_rows_dev, claim_col_dev, n_before_dev, new_cols_dev,
-                                       n_new_dev, false, nullptr, nullptr, no_grid, no_grid, false, third_dev, nullptr);
-    return launch_update_t<float>(t, (hipStream_t)stream, (const float *)det_dev, m, m_dev, frame_index, rows_dev,
-                                  t->d.capacity, nullptr, n_rows_dev, claim_col_dev, n_before_dev, new_cols_dev,
-                                  n_new_dev, false, nullptr, nullptr, no_grid, no_grid, false, third_dev, nullptr);
+    return tracker_update(t, (hipStream_t)stream, det_dev, det_is_f64, third_dev, m, m_dev, frame_index, rows_dev, n_rows_dev,
+                          claim_col_dev, n_before_dev, new_cols_dev, n_new_dev);
+}
+
+// a batch of frames on one row buffer and the caller's running row count (`third_dev` is NULL for a 2-D handle)
+static int tracker_run(ysmr_tracker *t, hipStream_t st, const float *det_dev, const double *third_dev, const int32_t *det_count_dev,
+                       int batch, int32_t first_frame_index, ysmr_row *rows_dev, long long rows_capacity, long long *row_count_dev)
+{
+    const bool d3 = t->dims == 3;
+    const size_t md = (size_t)t->d.max_det;
+    t->linked = true;
+    if (t->use_batch()) {
+        // one launch links the batch, cut to the BL_MAX_BATCH frames a grid block holds (3-D: link mode 2 on a handle k_batch3 serves)
+        if (int rc = state_to_batch(t, st)) return rc;
+        for (int f0 = 0; f0 < batch; f0 += BL_MAX_BATCH) {
+            const int nb = std::min(batch - f0, BL_MAX_BATCH);
+            const float *det = det_dev + (size_t)f0 * md * 5;
+            const double *third = d3 ? third_dev + (size_t)f0 * md : nullptr;
+            // the batch's detections binned frame by frame: by ysmr_tracker_prepare ahead of this call, or here
+            int block = 2;
+            for (int s = 0; s < 2; ++s) {
+                const ysmr_tracker::Prepared &p = t->prepared[s];
+                if (f0 == 0 && batch <= BL_MAX_BATCH && p.det == (const void *)det_dev && p.third == (const void *)third_dev &&
+                    p.count == (const void *)det_count_dev && p.batch == batch) {
+                    block = s;
+                    t->prepared[s] = ysmr_tracker::Prepared();       // (good for one call)
+                }
+            }
+            const BatchDev bd = batch_dev(t, block);
+            if (block == 2) bin_batch(t, st, det, third, det_count_dev + f0, nb, bd);
+            if (BL_PAUSE_TICKS > 0) hipLaunchKernelGGL(k_pause, dim3(1), dim3(64), 0, st, BL_PAUSE_TICKS);
+            if (d3) {
+                BlKernArgs3 ka;
+                ka.t = t->d; ka.bd = bd; ka.det_all = det; ka.third_all = third; ka.det_count = det_count_dev + f0; ka.batch = nb;
+                ka.frame0 = first_frame_index + f0; ka.rows = rows_dev; ka.rows_capacity = rows_capacity;
+                ka.row_count = row_count_dev; ka.seat3 = t->seat3;
+                hipLaunchKernelGGL(k_batch3, dim3(1), dim3(BL_THREADS), t->batch3_lds, st, ka);
+            } else {
+                BlKernArgs ka;
+                ka.t = t->d; ka.bd = bd; ka.det_all = det; ka.det_count = det_count_dev + f0; ka.batch = nb;
+                ka.frame0 = first_frame_index + f0; ka.rows = rows_dev; ka.rows_capacity = rows_capacity;
+                ka.row_count = row_count_dev; ka.gains = t->bgains_dev;
+                for (int k = 0; k < 4; ++k) ka.hz[k] = (k == 0 || k < t->d.n_f) && k < BL_NF ? t->d.n_i[k] : 0x7FFFFFFF;
+                hipLaunchKernelGGL(k_batch, dim3(1), dim3(BL_THREADS), t->batch_lds, st, ka);
+            }
+            YSMR_LAUNCH_CHECK();
+        }
+        return YSMR_OK;
+    }
+    if (int rc = state_to_std(t, st)) return rc;
+    // One launch per frame (or two); a frame's launch leaves the next frame's row minima.  Large 2-D tables (the split path)
+    // look for them in a uniform grid over each frame's detections, built a grid block of frames at a time: the look-ahead
+    // stays inside such a chunk, whose first frame gets its own k_rowmin.
+    const bool grids = !t->fused && !d3;
+    const int chunk = grids ? t->grid_frames : batch;
+    for (int f0 = 0; f0 < batch; f0 += chunk) {
+        const int nb = std::min(batch - f0, chunk);
+        if (grids) {
+            hipLaunchKernelGGL(k_grid_build<float>, dim3(nb), dim3(1024), 0, st, det_dev + (size_t)f0 * md * 5, det_count_dev + f0,
+                               t->d.max_det, (char *)t->grid_block, ysmr_tracker::grid_bytes_per_frame(t->d.max_det));
+            YSMR_LAUNCH_CHECK();
+        }
+        for (int f = 0; f < nb; ++f) {
+            const size_t g = (size_t)f0 + f;
+            FrameArgs a;
+            a.det = det_dev + g * md * 5; a.m_dev = det_count_dev + g; a.frame = first_frame_index + (int)g;
+            a.rows = rows_dev; a.rows_capacity = rows_capacity; a.row_count = row_count_dev;
+            a.rowmin_done = f > 0;
+            if (d3) a.third = third_dev + g * md;
+            if (grids) a.grid = t->grid(f);
+            if (f + 1 < nb) {
+                a.next_det = det_dev + (g + 1) * md * 5; a.next_m_dev = det_count_dev + g + 1;
+                if (d3) a.next_third = third_dev + (g + 1) * md;
+                if (grids) a.next_grid = t->grid(f + 1);
+            }
+            if (int rc = launch_frame(t, st, a)) return rc;
+        }
+    }
+    return YSMR_OK;
+}
+
+int ysmr_tracker_run(ysmr_tracker *t, void *stream, const float *det_dev, const int32_t *det_count_dev, int batch,
+                     int32_t first_frame_index, ysmr_row *rows_dev, int64_t rows_capacity, int64_t *row_count_dev)
+{
+    if (!t) return ysmr::fail(YSMR_ERR_ARG, "tracker handle is NULL");
+    if (!det_dev || !det_count_dev || !rows_dev || !row_count_dev || batch <= 0)
+        return ysmr::fail(YSMR_ERR_ARG, "det_dev, det_count_dev, rows_dev, row_count_dev must be set and batch > 0");
+    if (t->dims != 2) return ysmr::fail(YSMR_ERR_STATE, "a 3-D handle is run with ysmr_tracker_run3");
+    return tracker_run(t, (hipStream_t)stream, det_dev, nullptr, det_count_dev, batch, first_frame_index, rows_dev,
+                       (long long)rows_capacity, (long long *)row_count_dev);
 }
 
 int ysmr_tracker_run3(ysmr_tracker *t, void *stream, const float *det_dev, const double *third_dev, const int32_t *det_count_dev,
@@ -2735,54 +2724,8 @@ int ysmr_tracker_run3(ysmr_tracker *t, void *stream, const float *det_dev, const
     if (!det_dev || !third_dev || !det_count_dev || !rows_dev || !row_count_dev || batch <= 0)
         return ysmr::fail(YSMR_ERR_ARG, "det_dev, third_dev, det_count_dev, rows_dev, row_count_dev must be set and batch > 0");
     if (t->dims != 3) return ysmr::fail(YSMR_ERR_STATE, "ysmr_tracker_run3 needs a 3-D handle (ysmr_tracker_dimensions)");
-    if (t->use_batch()) {
-        // link mode 2 on a handle k_batch3 serves: one launch per BL_MAX_BATCH frames, as ysmr_tracker_run's batch path
-        t->linked = true;
-        if (int rc = state_to_batch(t, (hipStream_t)stream)) return rc;
-        const size_t md = (size_t)t->d.max_det;
-        for (int f0 = 0; f0 < batch; f0 += BL_MAX_BATCH) {
-            const int nb = batch - f0 < BL_MAX_BATCH ? batch - f0 : BL_MAX_BATCH;
-            const float *det = det_dev + (size_t)f0 * md * 5;
-            const double *third = third_dev + (size_t)f0 * md;
-            int block = 2;
-            for (int s = 0; s < 2; ++s)
-                if (f0 == 0 && batch <= BL_MAX_BATCH && t->prepared[s].det == (const void *)det_dev &&
-                    t->prepared[s].third == (const void *)third_dev && t->prepared[s].count == (const void *)det_count_dev &&
-                    t->prepared[s].batch == batch) {
-                    block = s;
-                    t->prepared[s] = ysmr_tracker::Prepared();       // (good for one call)
-                }
-            BlKernArgs3 ka;
-            ka.t = t->d; ka.bd = t->bd;
-            ka.bd.grid = (char *)t->grid3_block + (size_t)block * BL_MAX_BATCH * t->grid3_stride;
-            ka.bd.grid_stride = t->grid3_stride;
-            if (block == 2)
-                hipLaunchKernelGGL(k_bgrid3, dim3(nb), dim3(BG_THREADS), 4 * (size_t)bl3_lds_dwords_max(t->d.max_det), (hipStream_t)stream,
-                                   det, third, det_count_dev + f0, t->d.max_det, ka.bd.grid, ka.bd.grid_stride);
-            ka.det_all = det; ka.third_all = third; ka.det_count = det_count_dev + f0; ka.batch = nb;
-            ka.frame0 = first_frame_index + f0; ka.rows = rows_dev; ka.rows_capacity = (long long)rows_capacity;
-            ka.row_count = (long long *)row_count_dev; ka.seat3 = t->seat3;
-            if (BL_PAUSE_TICKS > 0) hipLaunchKernelGGL(k_pause, dim3(1), dim3(64), 0, (hipStream_t)stream, BL_PAUSE_TICKS);
-            hipLaunchKernelGGL(k_batch3, dim3(1), dim3(BL_THREADS), t->batch3_lds, (hipStream_t)stream, ka);
-            YSMR_LAUNCH_CHECK();
-        }
-        return YSMR_OK;
-    }
-    if (int rc = state_to_std(t, (hipStream_t)stream)) return rc;
-    t->rowmin_for = nullptr;
-    if (t->fused) { t->set_base = true; t->base_ptr = (const long long *)row_count_dev; }
-    const DetGrid no_grid{nullptr, nullptr, nullptr, nullptr};
-    const size_t md = (size_t)t->d.max_det;
-    for (int f = 0; f < batch; ++f) {       // one launch per frame (or two); a frame's launch leaves the next frame's row minima
-        const bool inside = f + 1 < batch;
-        int rc = launch_update_t<float>(t, (hipStream_t)stream, det_dev + (size_t)f * md * 5, -1, det_count_dev + f,
-                                        first_frame_index + f, rows_dev, (long long)rows_capacity, (long long *)row_count_dev,
-                                        nullptr, nullptr, nullptr, nullptr, nullptr, f > 0,
-                                        inside ? det_dev + (size_t)(f + 1) * md * 5 : nullptr, inside ? det_count_dev + f + 1 : nullptr,
-                                        no_grid, no_grid, false, third_dev + (size_t)f * md, inside ? third_dev + (size_t)(f + 1) * md : nullptr);
-        if (rc) return rc;
-    }
-    return YSMR_OK;
+    return tracker_run(t, (hipStream_t)stream, det_dev, third_dev, det_count_dev, batch, first_frame_index, rows_dev,
+                       (long long)rows_capacity, (long long *)row_count_dev);
 }
 
 int ysmr_tracker_fused(ysmr_tracker *t) { return t && t->fused && !t->use_batch() ? 1 : 0; }
