@@ -61,3 +61,20 @@ def select_settings(**kw):
                             "limit track length to x seconds": 3.0, "store processed .csv file": False})
     s.update(kw)
     return s
+
+
+#: track lengths that start a track on the last row of a 2048-row scan tile (csrc/prim.h: SCAN_TILE), on the first row of the next
+#: tile and on the first row of the third: rows 2047, 2079, 4096 and rows 2048, 4096
+TILE_EDGE_LENGTHS = ((2047, 32, 2017, 40), (2048, 2048, 40))
+
+
+def walk_table(lengths, seed=9):
+    """Random-walk tracks of the given lengths, one after the other, every frame present."""
+    rng = np.random.default_rng(seed)
+    parts = []
+    for tid, n in enumerate(lengths):
+        xy = np.cumsum(rng.normal(0, 1.5, (n, 2)), axis=0) + 300
+        parts.append(pd.DataFrame({"TRACK_ID": np.full(n, tid, np.uint32), "POSITION_T": np.arange(n, dtype=np.uint32),
+                                   "POSITION_X": xy[:, 0], "POSITION_Y": xy[:, 1], "WIDTH": rng.uniform(4, 8, n),
+                                   "HEIGHT": rng.uniform(1, 3, n), "DEGREES_ANGLE": rng.uniform(0, 90, n)}))
+    return pd.concat(parts, ignore_index=True)

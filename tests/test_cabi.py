@@ -43,6 +43,26 @@ def test_workspace_size_and_bad_arguments(lib):
     assert rc == 1 and b"channels" in lib.ysmr_last_error()
 
 
+TABLE_WORKSPACES = {
+    # the stages that post-process the finished table carve their workspaces by one rule (csrc/table.h: Arena); the sizes are
+    # part of what callers see (they allocate them), and the buffers' order decides where each entry point finds its own
+    "ysmr_select_workspace_bytes": {(0, 0): 270848, (1, 0): 270848, (1, 950): 15639040, (2049, 950): 16005888,
+                                    (100000, 20000): 152133376, (-1, 0): 0, (2 ** 31, 0): 0},
+    "ysmr_evaluate_workspace_bytes": {(0,): 3584, (1,): 3584, (2048,): 139520, (2049,): 143104, (100000,): 6801664, (-1,): 0,
+                                      (2 ** 31,): 0},
+    "ysmr_plot_workspace_bytes": {(0, 0, 0, 0): 2304, (0, 0, 64, 48): 14336, (1, 1, 64, 48): 14336, (2049, 300, 640, 480): 1252096,
+                                  (100000, 3000, 1600, 1200): 8532224, (5, 0, 0, 0): 2304, (1, 1, 32769, 1): 0},
+    "ysmr_violin_workspace_bytes": {(0, 1, 0): 4864, (0, 4, 300): 9472, (1, 1, 0): 5888, (1025, 4, 0): 56064,
+                                    (100000, 255, 0): 4912384, (0, 64, 32768): 8395008, (0, 0, 0): 0, (0, 256, 0): 0},
+}
+
+
+@pytest.mark.parametrize("name", sorted(TABLE_WORKSPACES))
+def test_table_stage_workspace_sizes(lib, name):
+    for args, expect in TABLE_WORKSPACES[name].items():
+        assert getattr(lib, name)(*args) == expect, (name, args)
+
+
 def test_gsff_gains_closed_form_matches_reference_formula(lib):
     from oracle.ysmr_oracle import horizon_sizes, lsf_gain
     for fps, n_min, n_max, n_f in [(30.0, 0, 30.0, 3), (29.97, 0, -1.0, 3), (25.0, 4, 24.0, 4)]:

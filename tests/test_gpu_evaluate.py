@@ -79,6 +79,19 @@ def test_statistics_on_awkward_tables(oracle):
     _compare(oracle, zig, s, 30.0)
 
 
+@pytest.mark.parametrize("lengths", ["2047-32-2017-40", "2048-2048-40"])
+def test_statistics_with_tracks_starting_at_scan_tile_edges(oracle, lengths):
+    """Tracks that start on the last row of a scan tile, on the first row of the next and of the third: the track number and
+    the first / last row of every track come from an inclusive scan in tiles of 2048 rows (csrc/table.h: index_runs)."""
+    from select_tables import TILE_EDGE_LENGTHS, select_settings, walk_table
+    lengths = tuple(int(n) for n in lengths.split("-"))
+    assert lengths in TILE_EDGE_LENGTHS and min(lengths) >= 32
+    df = walk_table(lengths)
+    assert len(_long_enough(df, 32)) == len(df) == 4136
+    _, ref_stats = _compare(oracle, df, select_settings(), 30.0)
+    assert len(ref_stats) == len(lengths)
+
+
 def test_evaluate_tracks_entry_point_and_files(tmp_path, oracle):
     """evaluate_tracks() as the reference exposes it: (df, df_stats), the two csv files written by the reference's
     own to_csv call, analyse() running it after the selection."""

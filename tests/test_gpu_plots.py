@@ -130,7 +130,9 @@ def test_tracks_with_equal_distances_one_row_and_no_row(canvas):
 
 
 def test_tracks_grid_stride_loop():
-    """200 000 rows in 300 tracks on 640 x 480: more rows than the resident grid has threads."""
+    """200 000 rows in 300 tracks on 640 x 480: more rows than the resident grid has threads.  The rows' track numbers and
+    first rows come from csrc/table.h's k_run_flags and k_run_index: this is their stride loop, which the selection and
+    the statistics run as well."""
     rng = np.random.default_rng(11)
     lengths = rng.multinomial(200_000 - 300, np.ones(300) / 300) + 1
     ids = np.repeat(np.arange(300, dtype=np.uint32) * 7, lengths)
@@ -148,6 +150,43 @@ def test_tracks_grid_stride_loop():
     assert np.array_equal(got, want), f"{(got != want).any(axis=2).sum()} pixels differ"
     view = dict(view, mode=1, u0=-300.0, v0=-240.0)
     assert np.array_equal(_paint(ids, xy[:, 0], xy[:, 1], dist, view), pm.paint_tracks(ids, xy[:, 0], xy[:, 1], dist, view))
+
+
+def _walk_columns(lengths):
+    from select_tables import walk_table
+    df = walk_table(lengths)
+    ids = df["TRACK_ID"].to_numpy() * 3 + 2
+    dist = np.random.default_rng(len(lengths)).uniform(0, 300, len(lengths))
+    return ids, df["POSITION_X"].to_numpy(), df["POSITION_Y"].to_numpy(), dist
+
+
+WALK_VIEWS = {0: pm.make_view(0, 640, 480, (40, 20, 540, 430), -20.0, -30.0, 1.1, px=1.0, r2_dot=1, r2_start=4, grid_cols=[100, 300],
+                              grid_rows=[200], bar=(600, 20, 20, 430))}
+WALK_VIEWS[1] = dict(WALK_VIEWS[0], mode=1, u0=-300.0, v0=-240.0)
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("lengths", ["2047-32-2017-40", "2048-2048-40"])
+def test_tracks_starting_at_scan_tile_edges(lengths, mode):
+    """Tracks that start on the last row of a scan tile, on the first row of the next and of the third (csrc/table.h:
+    index_runs scans in tiles of 2048 rows); with two distances only, the tracks from the third on are not drawn."""
+    from select_tables import TILE_EDGE_LENGTHS
+    lengths = tuple(int(n) for n in lengths.split("-"))
+    assert lengths in TILE_EDGE_LENGTHS
+    ids, x, y, dist = _walk_columns(lengths)
+    view = WALK_VIEWS[mode]
+    want = pm.paint_tracks(ids, x, y, dist, view)
+    assert np.array_equal(_paint(ids, x, y, dist, view), want)
+    capped = pm.paint_tracks(ids, x, y, dist[:2], view)
+    assert np.array_equal(_paint(ids, x, y, dist[:2], view), capped) and not np.array_equal(capped, want)
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_tracks_of_one_row_each(mode):
+    """2049 tracks of one row: first[] is used to its full length, past a scan tile."""
+    ids, x, y, dist = _walk_columns((1,) * 2049)
+    want = pm.paint_tracks(ids, x, y, dist, WALK_VIEWS[mode])
+    assert np.array_equal(_paint(ids, x, y, dist, WALK_VIEWS[mode]), want)
 
 
 # ---- the angle histogram ---------------------------------------------------------------------------------------------

@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from select_tables import make_table, select_settings
+from select_tables import TILE_EDGE_LENGTHS, make_table, select_settings, walk_table
 
 pytestmark = pytest.mark.gpu
 
@@ -66,6 +66,28 @@ def test_select_long_tracks_use_the_pairwise_tree(oracle):
                            "percent of screen edges to exclude": 0.0})
     ref, info = _compare(oracle, df, s, h=2000, w=2000)
     assert info["good_tracks"] >= 5
+
+
+@pytest.mark.parametrize("lengths", TILE_EDGE_LENGTHS, ids=lambda l: "-".join(map(str, l)))
+def test_select_with_tracks_starting_at_scan_tile_edges(oracle, lengths):
+    """Tracks that start on the last row of a scan tile, on the first row of the next and of the third (csrc/table.h:
+    k_run_index after a scan in tiles of 2048 rows).  The clean-up drops the rows of large area, the tracks stay: the
+    second run index, over the cleaned table, has all of them; without that rule the cleaned table is the table, tile
+    edges included, and the tracks pass."""
+    df = walk_table(lengths)
+    s = select_settings(**{"limit track length to x seconds": 0.0, "try to omit motility outliers": False,
+                           "percent of screen edges to exclude": 0.0})
+    _, info = _compare(oracle, df, s, h=2000, w=2000)
+    assert info["tracks_before"] == info["tracks_after"] == len(lengths) and 0 < info["rows_after"] < len(df)
+    _, info = _compare(oracle, df, dict(s, **{"exclude measurement when above x times average area": 0.0}), h=2000, w=2000)
+    assert info["rows_after"] == len(df) and info["good_tracks"] == len(lengths)
+
+
+def test_select_every_row_its_own_track(oracle):
+    """2049 tracks of one row: first[] and last[] are used to their full length, past a scan tile; every track is too short."""
+    df = walk_table((1,) * 2049)
+    _, info = _compare(oracle, df, select_settings())
+    assert info["status"] == 2
 
 
 def test_select_statuses(oracle):

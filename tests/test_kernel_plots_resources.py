@@ -1,4 +1,4 @@
-"""Resources of the figure kernels (csrc/plots.hip), read from the built library's gfx950 code objects (no GPU needed):
+"""Resources of the figure kernels (csrc/plots.hip, and those of csrc/table.h and csrc/prim.h that it launches), read from the built library's gfx950 code objects (no GPU needed):
 none of them may need scratch memory -- a spilled register or a stack array in a per-pixel loop would go unnoticed
 otherwise."""
 import re
@@ -8,8 +8,11 @@ import pytest
 
 from test_kernel_resources import LIB, _gfx950_code_objects, _tool
 
-KERNELS = ("k_extent_init", "k_extent", "k_extent_finish", "k_pl_flags", "k_pl_first", "k_pl_range", "k_pl_colour", "k_pl_rank",
+KERNELS = ("k_extent_init", "k_extent", "k_extent_finish", "k_run_flags", "k_run_index", "k_pl_range", "k_pl_colour", "k_pl_rank",
            "k_pl_paint", "k_pl_compose", "k_hist_moving", "k_hist", "k_wedges")
+# plots.hip's own kernels are in its anonymous namespace (_ZN12_GLOBAL__N_1<len><name>E...), the shared ones in ysmr::table
+# (_ZN4ysmr5tableL<len><name>E...; L: static, so every code object that uses them has a copy, and every copy is checked)
+NAMESPACES = ("_ZN12_GLOBAL__N_1", "_ZN4ysmr5tableL")
 
 
 def _blocks(tmp_path):
@@ -30,16 +33,16 @@ def _blocks(tmp_path):
             m = re.search(r"^\s*\.?name:\s+(\S+)\s*$", block, re.M)
             if not m:
                 continue
-            for kernel in KERNELS:      # (anonymous namespace: _ZN12_GLOBAL__N_1<len><name>E...)
-                if re.match(r"_ZN12_GLOBAL__N_1" + str(len(kernel)) + kernel + "E", m.group(1)):
-                    found[kernel] = block
+            for kernel in KERNELS:
+                if any(m.group(1).startswith(ns + str(len(kernel)) + kernel + "E") for ns in NAMESPACES):
+                    found.setdefault(kernel, []).append(block)
     return found
 
 
 def test_figure_kernels_need_no_scratch(tmp_path):
     found = _blocks(tmp_path)
     assert sorted(found) == sorted(KERNELS), "kernels missing from the gfx950 code objects: {}".format(sorted(set(KERNELS) - set(found)))
-    for kernel, block in found.items():
+    for kernel, block in ((kernel, block) for kernel, blocks in found.items() for block in blocks):
         for field in ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count"):
             m = re.search(r"\.?" + field + r":\s+(\d+)", block)
             assert m, f"{field} missing from the metadata of {kernel}"

@@ -26,12 +26,12 @@
 
 #include "common.h"
 #include "prim.h"
+#include "table.h"
 
 namespace {
 
 constexpr int EV_BLOCKS = 512;
-__device__ __forceinline__ long long gtid() { return (long long)blockIdx.x * blockDim.x + threadIdx.x; }
-__device__ __forceinline__ long long gstride() { return (long long)gridDim.x * blockDim.x; }
+using namespace ysmr::table;
 __device__ __forceinline__ double nan64() { return __longlong_as_double(0x7FF8000000000000ll); }
 
 struct Kahan {   // pandas group_sum
@@ -57,31 +57,10 @@ struct EvRows {        // per row, n entries each
     double *w_um, *h_um, *travelled, *heading, *tp_of_tracks, *tp_dist, *blen;   // blen: float16 bac_length as double
     int32_t *angle, *cand;
     int8_t *moving, *tp, *phenotype;
-    uint32_t *first, *last;                          // per track
+    uint32_t *first, *last;                          // per track (table.h: index_runs)
     uint32_t *run_pos;                               // per stretch: its first row
     double *bins;                                    // scratch of the per-second sums (one slot per row)
 };
-
-__global__ __launch_bounds__(256) void k_ev_flags(EvRows r, long long n)
-{
-    for (long long i = gtid(); i < n; i += gstride()) r.flag[i] = (i == 0 || r.id[i] != r.id[i - 1]) ? 1u : 0u;
-}
-
-// seg = inclusive scan of flag - 1; first / last row of every track
-__global__ __launch_bounds__(256) void k_ev_segments(EvRows r, long long n)
-{
-    for (long long i = gtid(); i < n; i += gstride()) {
-        const uint32_t s = r.seg[i] - 1u;
-        r.seg[i] = s;
-    }
-}
-__global__ __launch_bounds__(256) void k_ev_bounds(EvRows r, long long n)
-{
-    for (long long i = gtid(); i < n; i += gstride()) {
-        if (r.flag[i]) r.first[r.seg[i]] = (uint32_t)i;
-        if (i == n - 1 || r.flag[i + 1]) r.last[r.seg[i]] = (uint32_t)i;
-    }
-}
 
 // steps, lengths in micrometres, float16 body length, path per row, "moving" before the median filters
 __global__ __launch_bounds__(256) void k_ev_steps(EvRows r, long long n, EvParams p)
@@ -178,32 +157,9 @@ __global__ __launch_bounds__(256) void k_ev_stretches(EvRows r, long long n, uin
     }
 }
 
-__device__ __forceinline__ double block_max(double v, double *s_red)
-{
-    // NaN-skipping maximum of the block (all NaN -> NaN)
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const double o = __shfl_xor(v, d);
-        v = (v != v) ? o : ((o != o) ? v : (o > v ? o : v));
-    }
-    __syncthreads();
-    if (lane == 0) s_red[w] = v;
-    __syncthreads();
-    double m = s_red[0];
-    for (int k = 1; k < 4; ++k) { const double o = s_red[k]; m = (m != m) ? o : ((o != o) ? m : (o > m ? o : m)); }
-    return m;
-}
-__device__ __forceinline__ long long block_sum(long long v, long long *s_red)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    __syncthreads();
-    if (lane == 0) s_red[w] = v;
-    __syncthreads();
-    return s_red[0] + s_red[1] + s_red[2] + s_red[3];
-}
+struct NanSkipMax {   // NaN-skipping maximum (all NaN -> NaN)
+    __device__ double operator()(double v, double o) const { return (v != v) ? o : ((o != o) ? v : (o > v ? o : v)); }
+};
 
 // numpy's float floor_divide (npy_divmod): the bin of row i in df.index // fps
 __device__ __forceinline__ double np_floor_divide(double a, double b)
@@ -222,8 +178,8 @@ __device__ __forceinline__ double np_floor_divide(double a, double b)
 // One block per track: everything the statistics table holds (track_eval.py:990-1090).
 __global__ __launch_bounds__(256) void k_ev_tracks(EvRows r, long long n, uint32_t n_tracks, EvParams p, double *stats)
 {
-    __shared__ double s_redd[4];
-    __shared__ long long s_redl[4];
+    __shared__ double s_redd[256];
+    __shared__ long long s_redl[256];
     __shared__ double s_body, s_path, s_median;
     for (uint32_t k = blockIdx.x; k < n_tracks; k += gridDim.x) {
         const long long a = r.first[k], b = r.last[k], len = b - a + 1;
@@ -276,9 +232,9 @@ __global__ __launch_bounds__(256) void k_ev_tracks(EvRows r, long long n, uint32
             if (td == td) stretch = (stretch != stretch || td > stretch) ? td : stretch;
             moving_rows += r.moving[i];
         }
-        reach = block_max(reach, s_redd) / body;
-        stretch = block_max(stretch, s_redd) / body;
-        moving_rows = block_sum(moving_rows, s_redl);
+        reach = block_reduce(reach, s_redd, NanSkipMax()) / body;
+        stretch = block_reduce(stretch, s_redd, NanSkipMax()) / body;
+        moving_rows = block_reduce(moving_rows, s_redl, Sum());
         const int phen = (reach > 1.5 && stretch > 5.0) ? 2 : ((reach > 1.5 && stretch <= 5.0) ? 1 : 0);
         // turning points of immotile tracks are dropped (the track start stays one)
         long long turns = 0;
@@ -288,7 +244,7 @@ __global__ __launch_bounds__(256) void k_ev_tracks(EvRows r, long long n, uint32
             r.tp[i] = tp;
             turns += tp;
         }
-        turns = block_sum(turns, s_redl);
+        turns = block_reduce(turns, s_redl, Sum());
         // largest distance between any two positions of the track
         double widest2 = -1.0;
         for (long long i = a + threadIdx.x; i <= b; i += 256) {
@@ -299,7 +255,7 @@ __global__ __launch_bounds__(256) void k_ev_tracks(EvRows r, long long n, uint32
                 widest2 = s > widest2 ? s : widest2;
             }
         }
-        widest2 = block_max(widest2, s_redd);
+        widest2 = block_reduce(widest2, s_redd, NanSkipMax());
         if (threadIdx.x == 0) {
             const double widest = sqrt(widest2);                          // (len >= 2: selected tracks are long)
             const double frames = (double)((long long)r.t[b] - (long long)r.t[a]) + 1.0;
@@ -324,23 +280,16 @@ __global__ __launch_bounds__(256) void k_ev_tracks(EvRows r, long long n, uint32
     }
 }
 
-struct EvLayout {
-    size_t flag, seg, u32a, u32b, run_incl, heading, tp_dist, blen, cand, first, last, run_pos, bins, temp, total;
-};
-EvLayout ev_layout(long long n)
+// the workspace part of r (the table's columns and the outputs are the caller's); returns the scans' scratch
+uint32_t *ev_carve(Arena &a, long long n, EvRows &r)
 {
-    EvLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = ysmr::align_up(off + bytes, 256); return o; };
     const size_t N = (size_t)(n > 0 ? n : 1);
-    L.flag = take(4 * N); L.seg = take(4 * N); L.u32a = take(4 * N); L.u32b = take(4 * N); L.run_incl = take(4 * N);
-    L.heading = take(8 * N); L.tp_dist = take(8 * N); L.blen = take(8 * N); L.cand = take(4 * N);
-    L.first = take(4 * N); L.last = take(4 * N); L.run_pos = take(4 * N); L.bins = take(8 * N);
-    L.temp = take(sizeof(uint32_t) * ysmr::prim::scan_temp_words(N));
-    L.total = off;
-    return L;
+    r.flag = a.take<uint32_t>(N); r.seg = a.take<uint32_t>(N); r.u32a = a.take<uint32_t>(N); r.u32b = a.take<uint32_t>(N);
+    r.run_incl = a.take<uint32_t>(N);
+    r.heading = a.take<double>(N); r.tp_dist = a.take<double>(N); r.blen = a.take<double>(N); r.cand = a.take<int32_t>(N);
+    r.first = a.take<uint32_t>(N); r.last = a.take<uint32_t>(N); r.run_pos = a.take<uint32_t>(N); r.bins = a.take<double>(N);
+    return a.take<uint32_t>(ysmr::prim::scan_temp_words(N));
 }
-unsigned ev_grid(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, EV_BLOCKS)); }
 
 }  // namespace
 
@@ -349,7 +298,10 @@ extern "C" {
 size_t ysmr_evaluate_workspace_bytes(long long n_rows)
 {
     if (n_rows < 0 || n_rows > 0x7FFFFFFFll) return 0;
-    return ev_layout(n_rows).total;
+    Arena sizing(nullptr);
+    EvRows r{};
+    ev_carve(sizing, n_rows, r);
+    return sizing.bytes();
 }
 
 int ysmr_evaluate_tracks(void *stream, long long n_rows, const uint32_t *track_id_dev, const uint32_t *t_dev,
@@ -370,32 +322,22 @@ int ysmr_evaluate_tracks(void *stream, long long n_rows, const uint32_t *track_i
         !angle_diff_dev || !moving_dev || !turn_points_dev || !tp_of_tracks_dev || !travelled_dist_dev || !motility_phenotype_dev ||
         !stats_dev)
         return ysmr::fail(YSMR_ERR_ARG, "a required device pointer is NULL");
-    const EvLayout L = ev_layout(n_rows);
-    if (workspace_bytes < L.total)
-        return ysmr::fail(YSMR_ERR_CAPACITY, "evaluate workspace too small: %zu < %zu bytes", workspace_bytes, L.total);
-    hipStream_t st = (hipStream_t)stream;
-    char *w = (char *)workspace_dev;
-    const long long n = n_rows;
+    Arena arena(workspace_dev);
     EvRows r{};
+    uint32_t *temp = ev_carve(arena, n_rows, r);
+    if (workspace_bytes < arena.bytes())
+        return ysmr::fail(YSMR_ERR_CAPACITY, "evaluate workspace too small: %zu < %zu bytes", workspace_bytes, arena.bytes());
+    hipStream_t st = (hipStream_t)stream;
+    const long long n = n_rows;
     r.id = track_id_dev; r.t = t_dev; r.x = x_dev; r.y = y_dev; r.w = w_dev; r.h = h_dev;
-    r.flag = (uint32_t *)(w + L.flag); r.seg = (uint32_t *)(w + L.seg); r.u32a = (uint32_t *)(w + L.u32a);
-    r.u32b = (uint32_t *)(w + L.u32b); r.run_incl = (uint32_t *)(w + L.run_incl);
-    r.w_um = width_um_dev; r.h_um = height_um_dev; r.travelled = travelled_dist_dev; r.heading = (double *)(w + L.heading);
-    r.tp_of_tracks = tp_of_tracks_dev; r.tp_dist = (double *)(w + L.tp_dist); r.blen = (double *)(w + L.blen);
-    r.angle = angle_diff_dev; r.cand = (int32_t *)(w + L.cand);
-    r.moving = moving_dev; r.tp = turn_points_dev; r.phenotype = motility_phenotype_dev;
-    r.first = (uint32_t *)(w + L.first); r.last = (uint32_t *)(w + L.last); r.run_pos = (uint32_t *)(w + L.run_pos);
-    r.bins = (double *)(w + L.bins);
-    uint32_t *temp = (uint32_t *)(w + L.temp);
+    r.w_um = width_um_dev; r.h_um = height_um_dev; r.travelled = travelled_dist_dev; r.tp_of_tracks = tp_of_tracks_dev;
+    r.angle = angle_diff_dev; r.moving = moving_dev; r.tp = turn_points_dev; r.phenotype = motility_phenotype_dev;
     EvParams p{prm->pixel_per_micrometre, prm->fps, prm->min_turn_angle, prm->angle_lag, prm->reach_lag, 1, (prm->median_kernel - 1) / 2};
-    const dim3 g(ev_grid(n)), tb(256);
+    const dim3 g(resident_grid(n, EV_BLOCKS)), tb(256);
 
-    hipLaunchKernelGGL(k_ev_flags, g, tb, 0, st, r, n);
-    ysmr::prim::inclusive_scan_u32(st, r.flag, r.seg, (size_t)n, temp);
-    uint32_t n_tracks = 0;
-    YSMR_HIP_CHECK(hipMemcpyAsync(&n_tracks, r.seg + (n - 1), 4, hipMemcpyDeviceToHost, st));
-    hipLaunchKernelGGL(k_ev_segments, g, tb, 0, st, r, n);
-    hipLaunchKernelGGL(k_ev_bounds, g, tb, 0, st, r, n);
+    index_runs(st, g.x, r.id, n, r.flag, r.seg, r.first, r.last, UINT32_MAX, temp);
+    uint32_t last_track = 0;   // the last row's track number
+    YSMR_HIP_CHECK(hipMemcpyAsync(&last_track, r.seg + (n - 1), 4, hipMemcpyDeviceToHost, st));
     hipLaunchKernelGGL(k_ev_steps, g, tb, 0, st, r, n, p);
     // moving: two median filters (3 rows, then about a second)
     ysmr::prim::inclusive_scan_u32(st, r.u32a, r.u32b, (size_t)n, temp);
@@ -411,7 +353,8 @@ int ysmr_evaluate_tracks(void *stream, long long n_rows, const uint32_t *track_i
     YSMR_HIP_CHECK(hipMemcpyAsync(&n_runs, r.run_incl + (n - 1), 4, hipMemcpyDeviceToHost, st));
     hipLaunchKernelGGL(k_ev_numbers, g, tb, 0, st, r, n);
     YSMR_HIP_CHECK(hipStreamSynchronize(st));
-    hipLaunchKernelGGL(k_ev_stretches, dim3(ev_grid(n_runs)), tb, 0, st, r, n, n_runs);
+    const uint32_t n_tracks = last_track + 1u;
+    hipLaunchKernelGGL(k_ev_stretches, dim3(resident_grid(n_runs, EV_BLOCKS)), tb, 0, st, r, n, n_runs);
     hipLaunchKernelGGL(k_ev_tracks, dim3(std::max(1u, std::min(n_tracks, 1024u))), tb, 0, st, r, n, n_tracks, p, stats_dev);
     YSMR_LAUNCH_CHECK();
     YSMR_HIP_CHECK(hipStreamSynchronize(st));

@@ -20,6 +20,7 @@
 #include "common.h"
 #include "plot_lut.h"
 #include "prim.h"
+#include "table.h"
 
 namespace {
 
@@ -30,9 +31,7 @@ constexpr int PL_MAX_BINS = 1024;
 __constant__ uint8_t c_lut[768] = {YSMR_VIRIDIS_R_U8};
 const uint8_t h_lut[768] = {YSMR_VIRIDIS_R_U8};
 
-__device__ __forceinline__ long long gtid() { return (long long)blockIdx.x * blockDim.x + threadIdx.x; }
-__device__ __forceinline__ long long gstride() { return (long long)gridDim.x * blockDim.x; }
-inline unsigned pl_grid(long long items) { return (unsigned)std::max(1ll, std::min<long long>((items + 255) / 256, PL_BLOCKS)); }
+using namespace ysmr::table;
 
 using ysmr::prim::key_of;      // doubles as u64 keys of the same order: min and max become integer atomics
 using ysmr::prim::value_of;
@@ -62,31 +61,6 @@ __device__ __forceinline__ long long run_last(const uint32_t *__restrict__ id, l
     return lo;
 }
 
-__device__ __forceinline__ unsigned long long block_min_key(unsigned long long v, unsigned long long *s)
-{
-    s[threadIdx.x] = v;
-    __syncthreads();
-    for (int d = 128; d > 0; d >>= 1) {
-        if ((int)threadIdx.x < d) s[threadIdx.x] = std::min(s[threadIdx.x], s[threadIdx.x + d]);
-        __syncthreads();
-    }
-    const unsigned long long r = s[0];
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ unsigned long long block_max_key(unsigned long long v, unsigned long long *s)
-{
-    s[threadIdx.x] = v;
-    __syncthreads();
-    for (int d = 128; d > 0; d >>= 1) {
-        if ((int)threadIdx.x < d) s[threadIdx.x] = std::max(s[threadIdx.x], s[threadIdx.x + d]);
-        __syncthreads();
-    }
-    const unsigned long long r = s[0];
-    __syncthreads();
-    return r;
-}
-
 // ---- extent -----------------------------------------------------------------------------------------------------------
 
 __global__ void k_extent_init(unsigned long long *keys)
@@ -113,8 +87,8 @@ __global__ __launch_bounds__(256) void k_extent(long long n, const uint32_t *__r
         u_lo = std::min(u_lo, ku); u_hi = std::max(u_hi, ku);
         v_lo = std::min(v_lo, kv); v_hi = std::max(v_hi, kv);
     }
-    u_lo = block_min_key(u_lo, s_red); u_hi = block_max_key(u_hi, s_red);
-    v_lo = block_min_key(v_lo, s_red); v_hi = block_max_key(v_hi, s_red);
+    u_lo = block_reduce(u_lo, s_red, Min()); u_hi = block_reduce(u_hi, s_red, Max());
+    v_lo = block_reduce(v_lo, s_red, Min()); v_hi = block_reduce(v_hi, s_red, Max());
     if (threadIdx.x == 0) {
         atomicMin(&keys[0], u_lo); atomicMax(&keys[1], u_hi);
         atomicMin(&keys[2], v_lo); atomicMax(&keys[3], v_hi);
@@ -135,26 +109,10 @@ struct PlTracks {
     const uint32_t *id;
     const double *x, *y, *dist;
     long long dist_stride;
-    uint32_t *flag, *seg, *first, *rank, *canvas;
+    uint32_t *flag, *seg, *first, *rank, *canvas;   // seg: the row's track number; first[t]: track t's first row (t < n_tracks)
     double *c, *scal;                    // scal: dmin, dmax - dmin, 1.0 when the colour values are all 0
     uint8_t *lut_of_rank;
 };
-
-__global__ __launch_bounds__(256) void k_pl_flags(PlTracks r, long long n)
-{
-    for (long long i = gtid(); i < n; i += gstride()) r.flag[i] = (i == 0 || r.id[i] != r.id[i - 1]) ? 1u : 0u;
-}
-
-// seg becomes the row's track number (it holds the inclusive scan of flag); first[t] the track's first row.  Rows of
-// tracks beyond n_tracks are left out of first[] here and of the canvas later.
-__global__ __launch_bounds__(256) void k_pl_first(PlTracks r, long long n, uint32_t n_tracks)
-{
-    for (long long i = gtid(); i < n; i += gstride()) {
-        const uint32_t t = r.seg[i] - 1u;
-        r.seg[i] = t;
-        if (r.flag[i] && t < n_tracks) r.first[t] = (uint32_t)i;
-    }
-}
 
 // one block: the range of the distances
 __global__ __launch_bounds__(256) void k_pl_range(PlTracks r, uint32_t n_tracks)
@@ -167,9 +125,9 @@ __global__ __launch_bounds__(256) void k_pl_range(PlTracks r, uint32_t n_tracks)
         const unsigned long long k = key_of(d);
         lo = std::min(lo, k); hi = std::max(hi, k);
     }
-    lo = block_min_key(lo, s_red);
-    hi = block_max_key(hi, s_red);
-    bad = block_max_key(bad, s_red);
+    lo = block_reduce(lo, s_red, Min());
+    hi = block_reduce(hi, s_red, Max());
+    bad = block_reduce(bad, s_red, Max());
     if (threadIdx.x == 0) {
         const double dmin = value_of(lo), span = value_of(hi) - dmin;
         const bool flat = bad || n_tracks == 0 || !(span > 0.0) || !finite64(span);
@@ -299,24 +257,19 @@ __global__ __launch_bounds__(256) void k_pl_compose(const uint32_t *__restrict__
     }
 }
 
-struct PlLayout { size_t flag, seg, temp, first, rank, c, scal, lut, canvas, total; };
-
-PlLayout pl_layout(long long n, long long n_tracks, long long pixels)
+// the workspace part of r; returns the scan's scratch.  (The angle histogram carves (n, 0, 0) and uses flag and seg alone.)
+uint32_t *pl_carve(Arena &a, long long n, long long n_tracks, long long pixels, PlTracks &r)
 {
-    PlLayout L{};
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t here = at; at += ysmr::align_up(std::max<size_t>(bytes, 1), 256); return here; };
-    L.flag = take(4 * (size_t)n);
-    L.seg = take(4 * (size_t)n);
-    L.temp = take(4 * ysmr::prim::scan_temp_words((size_t)n));
-    L.first = take(4 * (size_t)n_tracks);
-    L.rank = take(4 * (size_t)n_tracks);
-    L.c = take(8 * (size_t)n_tracks);
-    L.scal = take(8 * 4);
-    L.lut = take((size_t)n_tracks);
-    L.canvas = take(4 * (size_t)pixels);
-    L.total = at;
-    return L;
+    r.flag = a.take<uint32_t>((size_t)n);
+    r.seg = a.take<uint32_t>((size_t)n);
+    uint32_t *scan_temp = a.take<uint32_t>(ysmr::prim::scan_temp_words((size_t)n));
+    r.first = a.take<uint32_t>((size_t)n_tracks);
+    r.rank = a.take<uint32_t>((size_t)n_tracks);
+    r.c = a.take<double>((size_t)n_tracks);
+    r.scal = a.take<double>(4);
+    r.lut_of_rank = a.take<uint8_t>((size_t)n_tracks);
+    r.canvas = a.take<uint32_t>((size_t)pixels);
+    return scan_temp;
 }
 
 bool sizes_ok(long long n, long long n_tracks, int W, int H)
@@ -439,7 +392,7 @@ int ysmr_plot_extent(void *stream, long long n_rows, const uint32_t *track_id_de
     unsigned long long *keys = (unsigned long long *)out_dev;
     hipLaunchKernelGGL(k_extent_init, dim3(1), dim3(64), 0, st, keys);
     if (n_rows > 0)
-        hipLaunchKernelGGL(k_extent, dim3(pl_grid(n_rows)), dim3(256), 0, st, n_rows, track_id_dev, x_dev, y_dev, mode, px, keys);
+        hipLaunchKernelGGL(k_extent, dim3(resident_grid(n_rows, PL_BLOCKS)), dim3(256), 0, st, n_rows, track_id_dev, x_dev, y_dev, mode, px, keys);
     hipLaunchKernelGGL(k_extent_finish, dim3(1), dim3(64), 0, st, keys);
     YSMR_LAUNCH_CHECK();
     return YSMR_OK;
@@ -448,7 +401,10 @@ int ysmr_plot_extent(void *stream, long long n_rows, const uint32_t *track_id_de
 size_t ysmr_plot_workspace_bytes(long long n_rows, long long n_tracks, int width, int height)
 {
     if (!sizes_ok(n_rows, n_tracks, width, height)) return 0;
-    return pl_layout(n_rows, n_tracks, (long long)width * height).total;
+    Arena sizing(nullptr);
+    PlTracks r{};
+    pl_carve(sizing, n_rows, n_tracks, (long long)width * height, r);
+    return sizing.bytes();
 }
 
 int ysmr_plot_tracks(void *stream, long long n_rows, const uint32_t *track_id_dev, const double *x_dev, const double *y_dev,
@@ -481,16 +437,13 @@ int ysmr_plot_tracks(void *stream, long long n_rows, const uint32_t *track_id_de
     if (n_tracks > 0 && (!dist_dev || dist_stride < 1)) return ysmr::fail(YSMR_ERR_ARG, "dist_dev must not be NULL and dist_stride >= 1");
     if (((uintptr_t)workspace_dev & 7)) return ysmr::fail(YSMR_ERR_ARG, "workspace_dev must be 8-byte aligned");
     const long long pixels = (long long)view->width * view->height;
-    const PlLayout L = pl_layout(n_rows, n_tracks, pixels);
-    if (workspace_bytes < L.total)
-        return ysmr::fail(YSMR_ERR_CAPACITY, "plot workspace too small: %zu < %zu bytes", workspace_bytes, L.total);
-    hipStream_t st = (hipStream_t)stream;
-    char *w = (char *)workspace_dev;
+    Arena arena(workspace_dev);
     PlTracks r{};
+    uint32_t *scan_temp = pl_carve(arena, n_rows, n_tracks, pixels, r);
+    if (workspace_bytes < arena.bytes())
+        return ysmr::fail(YSMR_ERR_CAPACITY, "plot workspace too small: %zu < %zu bytes", workspace_bytes, arena.bytes());
+    hipStream_t st = (hipStream_t)stream;
     r.id = track_id_dev; r.x = x_dev; r.y = y_dev; r.dist = dist_dev; r.dist_stride = dist_stride;
-    r.flag = (uint32_t *)(w + L.flag); r.seg = (uint32_t *)(w + L.seg); r.first = (uint32_t *)(w + L.first);
-    r.rank = (uint32_t *)(w + L.rank); r.canvas = (uint32_t *)(w + L.canvas); r.c = (double *)(w + L.c);
-    r.scal = (double *)(w + L.scal); r.lut_of_rank = (uint8_t *)(w + L.lut);
     PlView v{};
     v.mode = view->mode; v.W = view->width; v.H = view->height; v.ax_x = view->ax_x; v.ax_y = view->ax_y; v.ax_w = view->ax_w;
     v.ax_h = view->ax_h; v.r2_dot = view->r2_dot; v.r2_start = view->r2_start; v.n_cols = view->n_grid_cols; v.n_rows = view->n_grid_rows;
@@ -502,17 +455,16 @@ int ysmr_plot_tracks(void *stream, long long n_rows, const uint32_t *track_id_de
 
     YSMR_HIP_CHECK(hipMemsetAsync(r.canvas, 0, 4 * (size_t)pixels, st));
     if (n_rows > 0 && nt > 0) {
-        const dim3 g(pl_grid(n_rows)), gt(pl_grid(nt)), tb(256);
-        // (a table with fewer tracks than n_tracks leaves the tail of first[] unused: no row refers to it)
-        hipLaunchKernelGGL(k_pl_flags, g, tb, 0, st, r, n_rows);
-        ysmr::prim::inclusive_scan_u32(st, r.flag, r.seg, (size_t)n_rows, (uint32_t *)(w + L.temp));
-        hipLaunchKernelGGL(k_pl_first, g, tb, 0, st, r, n_rows, nt);
+        const dim3 g(resident_grid(n_rows, PL_BLOCKS)), gt(resident_grid(nt, PL_BLOCKS)), tb(256);
+        // (a table with fewer tracks than n_tracks leaves the tail of first[] unused: no row refers to it; rows of tracks
+        // beyond n_tracks are left out of first[] here and of the canvas later)
+        index_runs(st, g.x, r.id, n_rows, r.flag, r.seg, r.first, nullptr, nt, scan_temp);
         hipLaunchKernelGGL(k_pl_range, dim3(1), tb, 0, st, r, nt);
         hipLaunchKernelGGL(k_pl_colour, gt, tb, 0, st, r, nt);
         hipLaunchKernelGGL(k_pl_rank, gt, tb, 0, st, r, nt);
         hipLaunchKernelGGL(k_pl_paint, g, tb, 0, st, r, n_rows, nt, v);
     }
-    hipLaunchKernelGGL(k_pl_compose, dim3(pl_grid(pixels)), dim3(256), 0, st, (const uint32_t *)r.canvas,
+    hipLaunchKernelGGL(k_pl_compose, dim3(resident_grid(pixels, PL_BLOCKS)), dim3(256), 0, st, (const uint32_t *)r.canvas,
                        (const uint8_t *)r.lut_of_rank, v, rgb_dev);
     YSMR_LAUNCH_CHECK();
     return YSMR_OK;
@@ -530,18 +482,19 @@ int ysmr_plot_angle_histogram(void *stream, long long n_rows, const uint32_t *tr
     if (n_rows > 0 && (!track_id_dev || !x_dev || !y_dev || !moving_dev)) return ysmr::fail(YSMR_ERR_ARG, "a required device pointer is NULL");
     if (((uintptr_t)counts_dev & 7) || ((uintptr_t)n_points_dev & 7) || ((uintptr_t)workspace_dev & 7))
         return ysmr::fail(YSMR_ERR_ARG, "workspace_dev, counts_dev and n_points_dev must be 8-byte aligned");
-    const PlLayout L = pl_layout(n_rows, 0, 0);
-    if (workspace_bytes < L.total)
-        return ysmr::fail(YSMR_ERR_CAPACITY, "plot workspace too small: %zu < %zu bytes", workspace_bytes, L.total);
+    Arena arena(workspace_dev);
+    PlTracks r{};
+    uint32_t *scan_temp = pl_carve(arena, n_rows, 0, 0, r);
+    if (workspace_bytes < arena.bytes())
+        return ysmr::fail(YSMR_ERR_CAPACITY, "plot workspace too small: %zu < %zu bytes", workspace_bytes, arena.bytes());
     hipStream_t st = (hipStream_t)stream;
-    char *w = (char *)workspace_dev;
-    uint32_t *mv = (uint32_t *)(w + L.flag), *incl = (uint32_t *)(w + L.seg);
+    uint32_t *mv = r.flag, *incl = r.seg;
     YSMR_HIP_CHECK(hipMemsetAsync(counts_dev, 0, 8 * (size_t)n_bins, st));
     YSMR_HIP_CHECK(hipMemsetAsync(n_points_dev, 0, 8, st));
     if (n_rows > 0) {
-        const dim3 g(pl_grid(n_rows)), tb(256);
+        const dim3 g(resident_grid(n_rows, PL_BLOCKS)), tb(256);
         hipLaunchKernelGGL(k_hist_moving, g, tb, 0, st, moving_dev, mv, n_rows);
-        ysmr::prim::inclusive_scan_u32(st, mv, incl, (size_t)n_rows, (uint32_t *)(w + L.temp));
+        ysmr::prim::inclusive_scan_u32(st, mv, incl, (size_t)n_rows, scan_temp);
         hipLaunchKernelGGL(k_hist, g, tb, 0, st, n_rows, track_id_dev, x_dev, y_dev, moving_dev, (const uint32_t *)incl, (long long)lag,
                            n_bins, edges_dev, (unsigned long long *)counts_dev, (unsigned long long *)n_points_dev);
     }
@@ -560,7 +513,7 @@ int ysmr_plot_wedges(void *stream, int width, int height, int cx, int cy, int n_
     if (ring_r2 < 0) return ysmr::fail(YSMR_ERR_ARG, "ring_r2 must not be negative");
     if (!dirs_dev || !r2_dev || !rgb_dev) return ysmr::fail(YSMR_ERR_ARG, "dirs_dev, r2_dev and rgb_dev must not be NULL");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_wedges, dim3(pl_grid((long long)width * height)), dim3(256), 0, st, width, height, cx, cy, n_bins, dirs_dev,
+    hipLaunchKernelGGL(k_wedges, dim3(resident_grid((long long)width * height, PL_BLOCKS)), dim3(256), 0, st, width, height, cx, cy, n_bins, dirs_dev,
                        r2_dev, ring_r2, rgb_dev);
     YSMR_LAUNCH_CHECK();
     return YSMR_OK;

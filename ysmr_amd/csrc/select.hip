@@ -25,14 +25,14 @@
 
 #include "common.h"
 #include "prim.h"
+#include "table.h"
 
 namespace {
 
 constexpr int SEL_BLOCKS = 1024;
 constexpr int TRACK_BLOCKS = 256;           // k_sel_tracks: 4 waves per block, one track per wave at a time
 
-__device__ __forceinline__ long long gtid() { return (long long)blockIdx.x * 256 + threadIdx.x; }
-__device__ __forceinline__ long long gstride() { return (long long)gridDim.x * 256; }
+using namespace ysmr::table;
 
 // ---- clean-up ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_sel_area(const uint32_t *__restrict__ id, const double *__restrict__ w,
@@ -41,20 +41,7 @@ __global__ __launch_bounds__(256) void k_sel_area(const uint32_t *__restrict__ i
 {
     for (long long i = gtid(); i < n; i += gstride()) {
         area[i] = w[i] * h[i];
-        start[i] = (i == 0 || id[i] != id[i - 1]) ? 1u : 0u;
-    }
-}
-
-// seg[i] = index of row i's track; first/last row of every track
-__global__ __launch_bounds__(256) void k_sel_segments(const uint32_t *__restrict__ start, const uint32_t *__restrict__ incl,
-                                                      long long n, uint32_t *__restrict__ seg, uint32_t *__restrict__ first,
-                                                      uint32_t *__restrict__ last)
-{
-    for (long long i = gtid(); i < n; i += gstride()) {
-        const uint32_t s = incl[i] - 1u;
-        seg[i] = s;
-        if (start[i]) first[s] = (uint32_t)i;
-        if (i == n - 1 || start[i + 1]) last[s] = (uint32_t)i;
+        start[i] = is_run_start(id, i) ? 1u : 0u;
     }
 }
 
@@ -124,7 +111,7 @@ __global__ __launch_bounds__(256) void k_sel_compact(const uint32_t *__restrict_
 __global__ __launch_bounds__(256) void k_sel_dist(Table c, long long n, uint32_t *__restrict__ start)
 {
     for (long long i = gtid(); i < n; i += gstride()) {
-        const bool st = i == 0 || c.id[i] != c.id[i - 1];
+        const bool st = is_run_start(c.id, i);
         start[i] = st ? 1u : 0u;
         double d = 0.0;
         if (!st) {
@@ -431,44 +418,45 @@ __global__ __launch_bounds__(256) void k_sel_emit(const uint8_t *__restrict__ go
 }
 
 // ---- workspace ------------------------------------------------------------------------------------
-struct SelLayout {
-    size_t area, start, incl, seg, first, last, bits_a, bits_b, val_a, val_b, key32_a, key32_b, median, keep, pos;
-    size_t c_id, c_t, c_orig, c_x, c_y, c_area, c_ratio, c_dist, flag, good, bounds, counters, leaf, leaf_sum, stack, temp;
-    size_t temp_bytes, total;
-    long long leaf_slots;
+struct SelWork {
+    double *area, *median;
+    uint32_t *start, *incl, *seg, *first, *last, *keep, *pos, *key32_a, *key32_b;
+    unsigned long long *bits_a, *bits_b, *val_a, *val_b;   // (val: values of pass 2 / distance keys)
+    Table c;
+    uint8_t *flag, *good;
+    Bounds *bounds;
+    unsigned long long *counters;   // [0..8] kick reasons, [9] good tracks, [10] error (int)
+    TrackScratch sc;
     int stack_cap;
+    void *temp;                     // of the scans and the radix sorts
 };
 
-SelLayout sel_layout(long long n, int max_recursion)
+SelWork sel_carve(Arena &a, long long n, int max_recursion)
 {
-    SelLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = ysmr::align_up(off + bytes, 256); return o; };
+    SelWork k{};
     const size_t N = (size_t)(n > 0 ? n : 1);
-    L.area = take(8 * N); L.start = take(4 * N); L.incl = take(4 * N); L.seg = take(4 * N);
-    L.first = take(4 * N); L.last = take(4 * N);
-    L.bits_a = take(8 * N); L.bits_b = take(8 * N); L.val_a = take(8 * N); L.val_b = take(8 * N);
-    L.key32_a = take(4 * N); L.key32_b = take(4 * N);
-    L.median = take(8 * N); L.keep = take(4 * N); L.pos = take(4 * N);
-    L.c_id = take(4 * N); L.c_t = take(4 * N); L.c_orig = take(4 * N);
-    L.c_x = take(8 * N); L.c_y = take(8 * N); L.c_area = take(8 * N); L.c_ratio = take(8 * N); L.c_dist = take(8 * N);
-    L.flag = take(N); L.good = take(N);
-    L.bounds = take(sizeof(Bounds)); L.counters = take(16 * 8);
-    L.leaf_slots = (long long)(N / 64 + N + 2);   // (tracks <= rows)
-    L.leaf = take(sizeof(int2) * (size_t)L.leaf_slots);
-    L.leaf_sum = take(sizeof(double) * 4 * (size_t)L.leaf_slots);
+    k.area = a.take<double>(N); k.start = a.take<uint32_t>(N); k.incl = a.take<uint32_t>(N); k.seg = a.take<uint32_t>(N);
+    k.first = a.take<uint32_t>(N); k.last = a.take<uint32_t>(N);
+    k.bits_a = a.take<unsigned long long>(N); k.bits_b = a.take<unsigned long long>(N);
+    k.val_a = a.take<unsigned long long>(N); k.val_b = a.take<unsigned long long>(N);
+    k.key32_a = a.take<uint32_t>(N); k.key32_b = a.take<uint32_t>(N);
+    k.median = a.take<double>(N); k.keep = a.take<uint32_t>(N); k.pos = a.take<uint32_t>(N);
+    k.c.id = a.take<uint32_t>(N); k.c.t = a.take<uint32_t>(N); k.c.orig = a.take<uint32_t>(N);
+    k.c.x = a.take<double>(N); k.c.y = a.take<double>(N); k.c.area = a.take<double>(N); k.c.ratio = a.take<double>(N);
+    k.c.dist = a.take<double>(N);
+    k.flag = a.take<uint8_t>(N); k.good = a.take<uint8_t>(N);
+    k.bounds = a.take<Bounds>(1); k.counters = a.take<unsigned long long>(16);
+    k.sc.leaf_slots = (long long)(N / 64 + N + 2);   // (tracks <= rows)
+    k.sc.leaf = a.take<int2>((size_t)k.sc.leaf_slots);
+    k.sc.leaf_sum = a.take<double>(4 * (size_t)k.sc.leaf_slots);
     long long cap = (long long)max_recursion + 4;
     if (cap < 16) cap = 16;
     if (cap > 8192) cap = 8192;   // (16 B x 1024 waves per entry; a deeper walk is reported as YSMR_ERR_CAPACITY)
-    L.stack_cap = (int)cap;
-    L.stack = take(sizeof(int4) * (size_t)L.stack_cap * TRACK_BLOCKS * 4);
-    L.temp_bytes = std::max(ysmr::prim::radix_temp_bytes(N), sizeof(uint32_t) * ysmr::prim::scan_temp_words(N));
-    L.temp = take(L.temp_bytes);
-    L.total = off;
-    return L;
+    k.stack_cap = (int)cap;
+    k.sc.stack = a.take<int4>((size_t)k.stack_cap * TRACK_BLOCKS * 4);
+    k.temp = a.take<char>(std::max(ysmr::prim::radix_temp_bytes(N), sizeof(uint32_t) * ysmr::prim::scan_temp_words(N)));
+    return k;
 }
-
-unsigned grid_for(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, SEL_BLOCKS)); }
 
 }  // namespace
 
@@ -477,7 +465,9 @@ extern "C" {
 size_t ysmr_select_workspace_bytes(long long n_rows, int max_recursion)
 {
     if (n_rows < 0 || n_rows > 0x7FFFFFFFll) return 0;
-    return sel_layout(n_rows, max_recursion).total;
+    Arena sizing(nullptr);
+    sel_carve(sizing, n_rows, max_recursion);
+    return sizing.bytes();
 }
 
 int ysmr_select_tracks(void *stream, long long n_rows, const uint32_t *track_id_dev, const uint32_t *t_dev,
@@ -495,26 +485,23 @@ int ysmr_select_tracks(void *stream, long long n_rows, const uint32_t *track_id_
     if (n_rows < prm->min_length_frames || n_rows == 0) { summary->status = YSMR_SELECT_TOO_SHORT; return YSMR_OK; }
     if (!track_id_dev || !t_dev || !x_dev || !y_dev || !w_dev || !h_dev || !workspace_dev || !sel_row_dev || !sel_index_dev)
         return ysmr::fail(YSMR_ERR_ARG, "a required device pointer is NULL");
-    const SelLayout L = sel_layout(n_rows, prm->max_recursion);
-    if (workspace_bytes < L.total)
-        return ysmr::fail(YSMR_ERR_CAPACITY, "select workspace too small: %zu < %zu bytes", workspace_bytes, L.total);
+    Arena arena(workspace_dev);
+    const SelWork k = sel_carve(arena, n_rows, prm->max_recursion);
+    if (workspace_bytes < arena.bytes())
+        return ysmr::fail(YSMR_ERR_CAPACITY, "select workspace too small: %zu < %zu bytes", workspace_bytes, arena.bytes());
     hipStream_t st = (hipStream_t)stream;
-    char *w = (char *)workspace_dev;
-    auto P = [&](size_t off) { return (void *)(w + off); };
-    double *area = (double *)P(L.area), *median = (double *)P(L.median);
-    uint32_t *start = (uint32_t *)P(L.start), *incl = (uint32_t *)P(L.incl), *seg = (uint32_t *)P(L.seg);
-    uint32_t *first = (uint32_t *)P(L.first), *last = (uint32_t *)P(L.last), *keep = (uint32_t *)P(L.keep), *pos = (uint32_t *)P(L.pos);
-    auto *bits_a = (unsigned long long *)P(L.bits_a), *bits_b = (unsigned long long *)P(L.bits_b);
-    auto *val_a = (unsigned long long *)P(L.val_a), *val_b = (unsigned long long *)P(L.val_b);   // (values of pass 2 / distance keys)
-    uint32_t *key32_a = (uint32_t *)P(L.key32_a), *key32_b = (uint32_t *)P(L.key32_b);
-    void *temp = P(L.temp);
+    double *area = k.area, *median = k.median;
+    uint32_t *start = k.start, *incl = k.incl, *seg = k.seg, *first = k.first, *last = k.last, *keep = k.keep, *pos = k.pos;
+    unsigned long long *bits_a = k.bits_a, *bits_b = k.bits_b, *val_a = k.val_a, *val_b = k.val_b;
+    uint32_t *key32_a = k.key32_a, *key32_b = k.key32_b;
+    void *temp = k.temp;
     const long long n = n_rows;
-    const unsigned g = grid_for(n);
+    const unsigned g = resident_grid(n, SEL_BLOCKS);
 
     // ---- clean-up
     hipLaunchKernelGGL(k_sel_area, dim3(g), dim3(256), 0, st, track_id_dev, w_dev, h_dev, n, area, start);
     ysmr::prim::inclusive_scan_u32(st, start, incl, (size_t)n, (uint32_t *)temp);
-    hipLaunchKernelGGL(k_sel_segments, dim3(g), dim3(256), 0, st, start, incl, n, seg, first, last);
+    hipLaunchKernelGGL(k_run_index, dim3(g), dim3(256), 0, st, (const uint32_t *)start, (const uint32_t *)incl, n, seg, first, last, UINT32_MAX);
     uint32_t n_tracks = 0;
     YSMR_HIP_CHECK(hipMemcpyAsync(&n_tracks, incl + (n - 1), 4, hipMemcpyDeviceToHost, st));
     YSMR_HIP_CHECK(hipStreamSynchronize(st));
@@ -530,14 +517,13 @@ int ysmr_select_tracks(void *stream, long long n_rows, const uint32_t *track_id_
     uint32_t *seg_sorted = at ? key32_b : key32_a, *seg_other = at ? key32_a : key32_b;
     at = ysmr::prim::radix_sort(st, seg_sorted, seg_other, area_sorted, area_other, (size_t)n, track_bits, temp);
     const unsigned long long *area_by_track = at ? area_other : area_sorted;
-    hipLaunchKernelGGL(k_sel_median, dim3(grid_for(n_tracks)), dim3(256), 0, st, area_by_track, first, last, n_tracks, median);
+    hipLaunchKernelGGL(k_sel_median, dim3(resident_grid(n_tracks, SEL_BLOCKS)), dim3(256), 0, st, area_by_track, first, last, n_tracks, median);
     CleanParams cp{prm->area_lo, prm->area_hi, prm->area_factor, prm->area_factor != 0.0 ? 1 : 0, (uint32_t)prm->min_length_frames};
     hipLaunchKernelGGL(k_sel_keep, dim3(g), dim3(256), 0, st, area, seg, median, first, last, t_dev, n, cp, keep);
     ysmr::prim::inclusive_scan_u32(st, keep, pos, (size_t)n, (uint32_t *)temp);
     uint32_t n_kept = 0;
     YSMR_HIP_CHECK(hipMemcpyAsync(&n_kept, pos + (n - 1), 4, hipMemcpyDeviceToHost, st));
-    Table c{(uint32_t *)P(L.c_id), (uint32_t *)P(L.c_t), (uint32_t *)P(L.c_orig), (double *)P(L.c_x), (double *)P(L.c_y),
-            (double *)P(L.c_area), (double *)P(L.c_ratio), (double *)P(L.c_dist)};
+    const Table c = k.c;
     hipLaunchKernelGGL(k_sel_compact, dim3(g), dim3(256), 0, st, keep, pos, track_id_dev, t_dev, x_dev, y_dev, w_dev, h_dev, area, n, c);
     YSMR_HIP_CHECK(hipStreamSynchronize(st));
     summary->rows_after = n_kept;
@@ -546,10 +532,10 @@ int ysmr_select_tracks(void *stream, long long n_rows, const uint32_t *track_id_
 
     // ---- the cleaned table: tracks, distances, bounds
     const long long m = n_kept;
-    const unsigned gm = grid_for(m);
+    const unsigned gm = resident_grid(m, SEL_BLOCKS);
     hipLaunchKernelGGL(k_sel_dist, dim3(gm), dim3(256), 0, st, c, m, start);
     ysmr::prim::inclusive_scan_u32(st, start, incl, (size_t)m, (uint32_t *)temp);
-    hipLaunchKernelGGL(k_sel_segments, dim3(gm), dim3(256), 0, st, start, incl, m, seg, first, last);
+    hipLaunchKernelGGL(k_run_index, dim3(gm), dim3(256), 0, st, (const uint32_t *)start, (const uint32_t *)incl, m, seg, first, last, UINT32_MAX);
     uint32_t n_tracks2 = 0;
     YSMR_HIP_CHECK(hipMemcpyAsync(&n_tracks2, incl + (m - 1), 4, hipMemcpyDeviceToHost, st));
     const int use_area = prm->q_area > 0.0 ? 1 : 0, use_dist = prm->omit_motility ? 1 : 0;
@@ -563,14 +549,14 @@ int ysmr_select_tracks(void *stream, long long n_rows, const uint32_t *track_id_
         hipLaunchKernelGGL(k_sel_bits, dim3(gm), dim3(256), 0, st, c.dist, m, val_a);
         dists_ordered = ysmr::prim::radix_sort(st, val_a, val_b, none, none, (size_t)m, 64, temp) ? val_b : val_a;
     }
-    Bounds *bounds = (Bounds *)P(L.bounds);
+    Bounds *bounds = k.bounds;
     // pandas hands numpy q * 100 and numpy divides by 100 again
     const double q_lo = prm->q_area * 100.0 / 100.0, q_hi = (1.0 - prm->q_area) * 100.0 / 100.0;
     hipLaunchKernelGGL(k_sel_bounds, dim3(1), dim3(1), 0, st, areas_ordered, dists_ordered, m, q_lo, q_hi, use_area, use_dist, bounds);
-    uint8_t *flag = (uint8_t *)P(L.flag), *good = (uint8_t *)P(L.good);
+    uint8_t *flag = k.flag, *good = k.good;
     YSMR_HIP_CHECK(hipMemsetAsync(flag, 0, (size_t)m, st));
     YSMR_HIP_CHECK(hipMemsetAsync(good, 0, (size_t)m, st));
-    unsigned long long *counters = (unsigned long long *)P(L.counters);   // [0..8] kick reasons, [9] good tracks, [10] error (int)
+    unsigned long long *counters = k.counters;
     YSMR_HIP_CHECK(hipMemsetAsync(counters, 0, 16 * 8, st));
     if (use_dist) {
         hipLaunchKernelGGL(k_sel_flags, dim3(gm), dim3(256), 0, st, c.dist, m, bounds, flag);
@@ -592,11 +578,10 @@ int ysmr_select_tracks(void *stream, long long n_rows, const uint32_t *track_id_
     tp.max_recursion = prm->max_recursion;
     tp.limit_frames = (uint32_t)prm->limit_frames;
     tp.limit_exact = prm->limit_exact;
-    tp.stack_cap = L.stack_cap;
-    TrackScratch sc{(int4 *)P(L.stack), (int2 *)P(L.leaf), (double *)P(L.leaf_sum), L.leaf_slots};
+    tp.stack_cap = k.stack_cap;
     TrackOut to{good, counters, counters + 9, (int *)(counters + 10)};
     const unsigned tblocks = (unsigned)std::max<long long>(1, std::min<long long>(((long long)n_tracks2 + 3) / 4, TRACK_BLOCKS));
-    hipLaunchKernelGGL(k_sel_tracks, dim3(tblocks), dim3(256), 0, st, c, flag, first, last, n_tracks2, tp, bounds, sc, to);
+    hipLaunchKernelGGL(k_sel_tracks, dim3(tblocks), dim3(256), 0, st, c, flag, first, last, n_tracks2, tp, bounds, k.sc, to);
     YSMR_LAUNCH_CHECK();
 
     // ---- output
@@ -611,7 +596,7 @@ int ysmr_select_tracks(void *stream, long long n_rows, const uint32_t *track_id_
     YSMR_HIP_CHECK(hipMemcpyAsync(&hb, bounds, sizeof(hb), hipMemcpyDeviceToHost, st));
     YSMR_HIP_CHECK(hipStreamSynchronize(st));
     if ((int)(h_counters[10] & 0xFFFFFFFFull) != 0)
-        return ysmr::fail(YSMR_ERR_CAPACITY, "select_tracks: recursion stack of %d entries exhausted", L.stack_cap);
+        return ysmr::fail(YSMR_ERR_CAPACITY, "select_tracks: recursion stack of %d entries exhausted", k.stack_cap);
     summary->area_lo = hb.area_lo; summary->area_hi = hb.area_hi;
     summary->q1_dist = hb.q1_dist; summary->q3_dist = hb.q3_dist; summary->dist_fence = hb.fence;
     summary->dist_outliers = (long long)hb.outliers;

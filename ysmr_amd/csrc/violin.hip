@@ -20,6 +20,7 @@
 #include "common.h"
 #include "plot_lut.h"
 #include "prim.h"
+#include "table.h"
 
 namespace {
 
@@ -32,27 +33,11 @@ constexpr double VI_ROW_CLAMP = 1048576.0;   // rows are kept within 2^20 of the
 
 __constant__ uint8_t c_fill[30] = {YSMR_VIOLIN_FILL_U8};
 
-__device__ __forceinline__ long long gtid() { return (long long)blockIdx.x * blockDim.x + threadIdx.x; }
-__device__ __forceinline__ long long gstride() { return (long long)gridDim.x * blockDim.x; }
-inline unsigned vi_grid(long long items) { return (unsigned)std::max(1ll, std::min<long long>((items + 255) / 256, VI_BLOCKS)); }
+using namespace ysmr::table;   // (block_reduce with Sum: the 256 lanes' values in a fixed order, a tree over LDS)
 
 using ysmr::prim::key_of;      // doubles as u64 keys of the same order: the radix sort's keys
 using ysmr::prim::value_of;
 using ysmr::prim::finite64;
-
-// the sum of the 256 lanes' values in a fixed order (a tree over LDS)
-__device__ __forceinline__ double block_sum(double v, double *s)
-{
-    s[threadIdx.x] = v;
-    __syncthreads();
-    for (int d = 128; d > 0; d >>= 1) {
-        if ((int)threadIdx.x < d) s[threadIdx.x] = s[threadIdx.x] + s[threadIdx.x + d];
-        __syncthreads();
-    }
-    const double r = s[0];
-    __syncthreads();
-    return r;
-}
 
 // ---- categories --------------------------------------------------------------------------------------------------------
 
@@ -107,14 +92,14 @@ __global__ __launch_bounds__(256) void k_vi_summary(const unsigned long long *__
 
     double acc = 0.0;
     for (uint32_t i = threadIdx.x; i < n; i += 256) acc = acc + value_of(x[i]);
-    const double total = block_sum(acc, s_red);
+    const double total = block_reduce(acc, s_red, Sum());
     const double mean = n ? total / (double)n : 0.0;
     acc = 0.0;
     for (uint32_t i = threadIdx.x; i < n; i += 256) {
         const double d = value_of(x[i]) - mean;
         acc = acc + d * d;
     }
-    const double ss = block_sum(acc, s_red);
+    const double ss = block_reduce(acc, s_red, Sum());
     if (threadIdx.x != 0) return;
 
     ysmr_violin_summary s;
@@ -177,7 +162,7 @@ __global__ __launch_bounds__(256) void k_vi_density(const unsigned long long *__
         const double z = (g - value_of(x[i])) / s.h;
         acc = acc + exp(-0.5 * z * z);
     }
-    const double total = block_sum(acc, s_red);
+    const double total = block_reduce(acc, s_red, Sum());
     if (threadIdx.x == 0) {
         const double norm = 1.0 / ((double)n * s.h * VI_SQRT_2PI);
         density[(size_t)v * VI_GRID + j] = norm * total;
@@ -304,25 +289,29 @@ __global__ __launch_bounds__(256) void k_vi_paint(const int *__restrict__ prof, 
     }
 }
 
-struct ViLayout { size_t keys_a, keys_b, ids_a, ids_b, counts, start, temp, prof, marks, total; };
+struct ViWork {
+    unsigned long long *keys_a, *keys_b;
+    uint32_t *ids_a, *ids_b, *counts, *start;
+    void *temp;                 // of the radix sorts
+    int *prof, *marks;
+};
 
-ViLayout vi_layout(long long n_tracks, int n_violins, int ax_h)
+// ysmr_violin_stats carves (n_tracks, n_violins, 0) and uses the buffers in front of prof, ysmr_plot_violins carves
+// (0, n_violins, ax_h) and uses prof and marks
+ViWork vi_carve(Arena &a, long long n_tracks, int n_violins, int ax_h)
 {
-    ViLayout L{};
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t here = at; at += ysmr::align_up(std::max<size_t>(bytes, 1), 256); return here; };
+    ViWork k{};
     const size_t entries = 2 * (size_t)n_tracks;
-    L.keys_a = take(8 * entries);
-    L.keys_b = take(8 * entries);
-    L.ids_a = take(4 * entries);
-    L.ids_b = take(4 * entries);
-    L.counts = take(4 * 512);
-    L.start = take(4 * 256);
-    L.temp = take(ysmr::prim::radix_temp_bytes(entries));
-    L.prof = take(4 * (size_t)n_violins * (size_t)ax_h);
-    L.marks = take(4 * (size_t)n_violins * VI_MARKS);
-    L.total = at;
-    return L;
+    k.keys_a = a.take<unsigned long long>(entries);
+    k.keys_b = a.take<unsigned long long>(entries);
+    k.ids_a = a.take<uint32_t>(entries);
+    k.ids_b = a.take<uint32_t>(entries);
+    k.counts = a.take<uint32_t>(512);
+    k.start = a.take<uint32_t>(256);
+    k.temp = a.take<char>(ysmr::prim::radix_temp_bytes(entries));
+    k.prof = a.take<int>((size_t)n_violins * (size_t)ax_h);
+    k.marks = a.take<int>((size_t)n_violins * VI_MARKS);
+    return k;
 }
 
 bool vi_sizes_ok(long long n_tracks, int n_violins, int ax_h)
@@ -337,7 +326,9 @@ extern "C" {
 size_t ysmr_violin_workspace_bytes(long long n_tracks, int n_violins, int ax_h)
 {
     if (!vi_sizes_ok(n_tracks, n_violins, ax_h)) return 0;
-    return vi_layout(n_tracks, n_violins, ax_h).total;
+    Arena sizing(nullptr);
+    vi_carve(sizing, n_tracks, n_violins, ax_h);
+    return sizing.bytes();
 }
 
 int ysmr_violin_stats(void *stream, long long n_tracks, const double *cut_dev, long long cut_stride, const double *value_dev,
@@ -353,26 +344,25 @@ int ysmr_violin_stats(void *stream, long long n_tracks, const double *cut_dev, l
     if (((uintptr_t)workspace_dev & 7) || ((uintptr_t)summaries_dev & 7) || ((uintptr_t)density_dev & 7))
         return ysmr::fail(YSMR_ERR_ARG, "workspace_dev, summaries_dev and density_dev must be 8-byte aligned");
     const int n_violins = n_cuts + 1;
-    const ViLayout L = vi_layout(n_tracks, n_violins, 0);
-    if (workspace_bytes < L.total)
-        return ysmr::fail(YSMR_ERR_CAPACITY, "violin workspace too small: %zu < %zu bytes", workspace_bytes, L.total);
+    Arena arena(workspace_dev);
+    const ViWork k = vi_carve(arena, n_tracks, n_violins, 0);
+    if (workspace_bytes < arena.bytes())
+        return ysmr::fail(YSMR_ERR_CAPACITY, "violin workspace too small: %zu < %zu bytes", workspace_bytes, arena.bytes());
     hipStream_t st = (hipStream_t)stream;
-    char *w = (char *)workspace_dev;
-    unsigned long long *keys_a = (unsigned long long *)(w + L.keys_a), *keys_b = (unsigned long long *)(w + L.keys_b);
-    uint32_t *ids_a = (uint32_t *)(w + L.ids_a), *ids_b = (uint32_t *)(w + L.ids_b);
-    uint32_t *counts = (uint32_t *)(w + L.counts), *start = (uint32_t *)(w + L.start);
+    unsigned long long *keys_a = k.keys_a, *keys_b = k.keys_b;
+    uint32_t *ids_a = k.ids_a, *ids_b = k.ids_b, *counts = k.counts, *start = k.start;
     const size_t entries = 2 * (size_t)n_tracks;
 
     YSMR_HIP_CHECK(hipMemsetAsync(counts, 0, 4 * 512, st));
     const unsigned long long *sorted = keys_a;
     if (n_tracks > 0) {
-        hipLaunchKernelGGL(k_vi_keys, dim3(vi_grid(n_tracks)), dim3(256), 0, st, n_tracks, cut_dev, cut_stride, value_dev, value_stride,
+        hipLaunchKernelGGL(k_vi_keys, dim3(resident_grid(n_tracks, VI_BLOCKS)), dim3(256), 0, st, n_tracks, cut_dev, cut_stride, value_dev, value_stride,
                            n_cuts, lo_dev, hi_dev, keys_a, ids_a, counts);
         // by value (eight passes: back in the a buffers), then by violin (one pass, stable: into the b buffers)
-        const int where = ysmr::prim::radix_sort<unsigned long long, uint32_t>(st, keys_a, keys_b, ids_a, ids_b, entries, 64, w + L.temp);
+        const int where = ysmr::prim::radix_sort<unsigned long long, uint32_t>(st, keys_a, keys_b, ids_a, ids_b, entries, 64, k.temp);
         unsigned long long *k_in = where ? keys_b : keys_a, *k_out = where ? keys_a : keys_b;
         uint32_t *i_in = where ? ids_b : ids_a, *i_out = where ? ids_a : ids_b;
-        const int there = ysmr::prim::radix_sort<uint32_t, unsigned long long>(st, i_in, i_out, k_in, k_out, entries, 8, w + L.temp);
+        const int there = ysmr::prim::radix_sort<uint32_t, unsigned long long>(st, i_in, i_out, k_in, k_out, entries, 8, k.temp);
         sorted = there ? k_out : k_in;
     }
     hipLaunchKernelGGL(k_vi_summary, dim3(n_violins), dim3(256), 0, st, sorted, (const uint32_t *)counts, start, summaries_dev);
@@ -411,9 +401,10 @@ int ysmr_plot_violins(void *stream, int n_violins, const ysmr_violin_summary *su
         return ysmr::fail(YSMR_ERR_ARG, "summaries_dev, density_dev, workspace_dev and rgb_dev must not be NULL");
     if (((uintptr_t)workspace_dev & 7) || ((uintptr_t)summaries_dev & 7) || ((uintptr_t)density_dev & 7))
         return ysmr::fail(YSMR_ERR_ARG, "workspace_dev, summaries_dev and density_dev must be 8-byte aligned");
-    const ViLayout L = vi_layout(0, n_violins, view->ax_h);
-    if (workspace_bytes < L.total)
-        return ysmr::fail(YSMR_ERR_CAPACITY, "violin workspace too small: %zu < %zu bytes", workspace_bytes, L.total);
+    Arena arena(workspace_dev);
+    const ViWork k = vi_carve(arena, 0, n_violins, view->ax_h);
+    if (workspace_bytes < arena.bytes())
+        return ysmr::fail(YSMR_ERR_CAPACITY, "violin workspace too small: %zu < %zu bytes", workspace_bytes, arena.bytes());
     ViView v{};
     v.y0 = view->y0; v.upp = view->units_per_pixel; v.W = view->width; v.H = view->height; v.ax_x = view->ax_x; v.ax_y = view->ax_y;
     v.ax_w = view->ax_w; v.ax_h = view->ax_h; v.n = n_violins; v.n_rows = view->n_grid_rows; v.line_half = view->line_half;
@@ -423,10 +414,9 @@ int ysmr_plot_violins(void *stream, int n_violins, const ysmr_violin_summary *su
     memcpy(v.slot_w, view->slot_w, sizeof v.slot_w);
     memcpy(v.slot_colour, view->slot_colour, sizeof v.slot_colour);
     hipStream_t st = (hipStream_t)stream;
-    char *w = (char *)workspace_dev;
-    int *prof = (int *)(w + L.prof), *marks = (int *)(w + L.marks);
+    int *prof = k.prof, *marks = k.marks;
     hipLaunchKernelGGL(k_vi_profile, dim3(n_violins), dim3(256), 0, st, summaries_dev, density_dev, v, prof, marks);
-    hipLaunchKernelGGL(k_vi_paint, dim3(vi_grid((long long)v.W * v.H)), dim3(256), 0, st, (const int *)prof, (const int *)marks, v, rgb_dev);
+    hipLaunchKernelGGL(k_vi_paint, dim3(resident_grid((long long)v.W * v.H, VI_BLOCKS)), dim3(256), 0, st, (const int *)prof, (const int *)marks, v, rgb_dev);
     YSMR_LAUNCH_CHECK();
     return YSMR_OK;
 }
