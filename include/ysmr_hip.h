@@ -173,6 +173,26 @@ int    ysmr_mjpeg_decode_batch(void *stream, const uint8_t *chunks_dev, const in
                                void *workspace_dev, size_t workspace_bytes,
                                uint8_t *frames_dev, int32_t *status_dev /* [n_frames] */);
 
+/* ADDED under ABI 15 (see above).  ysmr_mjpeg_decode_batch for files WITHOUT restart markers -- what cameras, ffmpeg, OpenCV and
+ * Pillow write.  ysmr_mjpeg_decode_batch gives a lane to each restart interval, so such a frame is one lane's work there; here
+ * its entropy data is cut into subsequences of fixed size that are decoded side by side, every one from an assumed state first
+ * and again from its predecessor's exit state until no entry state changes, which makes the result EXACT for every stream (a
+ * decoder started at a wrong bit falls into step with the code after a few symbols; one that never does costs time only).  A
+ * frame WITH a restart interval is decoded as ysmr_mjpeg_decode_batch decodes it.  Same supported subset, same status bits, same
+ * bytes in frames_dev, same rules for the workspace and for what is read and written.
+ * max_chunk_bytes: an upper bound of offsets_dev[i + 1] - offsets_dev[i] over the call, 1 .. 2^27 - 1 (the host knows the chunk
+ * sizes, the offsets live on the device); it sizes the workspace, and a frame with a longer chunk is flagged
+ * YSMR_MJPEGD_CORRUPT. */
+size_t ysmr_mjpeg_decode_sync_workspace_bytes(int n_frames, int height, int width, int channels, int sampling,
+                                              int max_chunk_bytes);   /* 0 for arguments the call refuses */
+int    ysmr_mjpeg_decode_batch_sync(void *stream, const uint8_t *chunks_dev, const int64_t *offsets_dev, int n_frames,
+                                    int height, int width, int channels, int sampling, int max_chunk_bytes,
+                                    void *workspace_dev, size_t workspace_bytes,
+                                    uint8_t *frames_dev, int32_t *status_dev /* [n_frames] */);
+/* The two compile-time constants of it: bytes of a subsequence, subsequences a workgroup takes at a time (tests build streams
+ * that cross these boundaries).  Either pointer may be NULL. */
+void   ysmr_mjpeg_decode_sync_geometry(int *subsequence_bytes, int *subsequences_per_pass);
+
 /* ---- annotated output video as Motion-JPEG --------------------------------------------------- */
 
 /* bit of *status_dev of ysmr_mjpeg_batch */

@@ -6,6 +6,8 @@
                                                     # restart markers -- the serial worst case (skipped where Pillow is missing)
   python3 scripts/mjpeg_decode_e2e.py run FILE      # False and True alternate, three warm runs each: frames/s, medians
   python3 scripts/mjpeg_decode_e2e.py batch FILE    # the first batches of FILE through ysmr_mjpeg_decode_batch alone, timed by events;
+  python3 scripts/mjpeg_decode_e2e.py batch FILE sync      # ... through ysmr_mjpeg_decode_batch_sync (frames without restart markers
+                                                    # are many lanes' work there), where the library has it;
                                                     # under `rocprofv3 --kernel-trace --stats --output-format csv -d OUT --` for ...
   python3 scripts/mjpeg_decode_e2e.py kernels OUT   # ... the k_mjd_* kernels' time per batch
   python3 scripts/mjpeg_decode_e2e.py run FILE device      # the device path alone, one warm run and one more; under
@@ -17,7 +19,8 @@
   python3 scripts/mjpeg_decode_e2e.py               # all of it in a temporary directory: every step a child process under its own
                                                     # time limit, and a step that fails ends the run
 
-The output of the last form belongs in profiles/mjpeg_decode_e2e.log."""
+The output of the last form belongs in profiles/mjpeg_decode_e2e.log (profiles/mjpeg_decode_sync_e2e.log: the run with --libs and the
+parent commit's library, after ysmr_mjpeg_decode_batch_sync was added)."""
 import csv
 import glob
 import os
@@ -107,19 +110,42 @@ def run(path, reps=3, modes=(False, True)):
     assert len(set(rows.values())) == 1, "the two paths tracked different tables"
 
 
-def batch(path, repeats=5):
-    """ysmr_mjpeg_decode_batch alone on the first batch of the file: milliseconds per batch by events."""
+def batch(path, repeats=5, sync=False):
+    """ysmr_mjpeg_decode_batch (``sync``: ysmr_mjpeg_decode_batch_sync) alone on the first batch of the file: milliseconds per
+    batch by events.  A library built before the second entry existed says so and is passed over."""
     import torch
     from ysmr_amd import _lib
     from ysmr_amd.frames import AviVideo
     video = AviVideo(path)
-    sampling, _, most = video.jpeg_layout_for(BATCH, needs_restart=False)
+    sampling, largest, most = video.jpeg_layout_for(BATCH, needs_restart=False)
     n = min(BATCH, video.frames_available)
     host, offsets = np.empty(most, np.uint8), np.zeros(n + 1, np.int64)
     assert video.read_jpeg_into(0, n, host, offsets) == n
-    L = _lib.lib()
+    # (the library is bound here, entry by entry: a build from before ysmr_mjpeg_decode_batch_sync, given with --libs, still
+    # serves the older entry, and _lib.lib() rightly refuses a library that lacks a function it binds)
+    import ctypes
+    L = ctypes.CDLL(_lib.LIB_PATH)
+    name = "ysmr_mjpeg_decode_batch_sync" if sync else "ysmr_mjpeg_decode_batch"
+    if not hasattr(L, name):
+        print("{}: {}: not in {}".format(os.path.basename(path), name, _lib.LIB_PATH))
+        return
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    L.ysmr_last_error.restype = ctypes.c_char_p
+    L.ysmr_mjpeg_decode_workspace_bytes.argtypes, L.ysmr_mjpeg_decode_workspace_bytes.restype = [ci] * 5, ctypes.c_size_t
+    L.ysmr_mjpeg_decode_batch.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, ctypes.c_size_t, vp, vp]
+    if sync:
+        L.ysmr_mjpeg_decode_sync_workspace_bytes.argtypes, L.ysmr_mjpeg_decode_sync_workspace_bytes.restype = [ci] * 6, ctypes.c_size_t
+        L.ysmr_mjpeg_decode_batch_sync.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, ctypes.c_size_t, vp, vp]
+
+    def check(rc):
+        if rc:
+            raise RuntimeError("{} failed (code {}): {}".format(name, rc, L.ysmr_last_error().decode("utf-8", "replace")))
+
     chunks, offsets_dev = torch.from_numpy(host).cuda(), torch.from_numpy(offsets).cuda()
-    ws_bytes = L.ysmr_mjpeg_decode_workspace_bytes(n, video.height, video.width, video.channels, sampling)
+    if sync:
+        ws_bytes = L.ysmr_mjpeg_decode_sync_workspace_bytes(n, video.height, video.width, video.channels, sampling, largest)
+    else:
+        ws_bytes = L.ysmr_mjpeg_decode_workspace_bytes(n, video.height, video.width, video.channels, sampling)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
     out = torch.empty((n, video.height, video.width, video.channels), dtype=torch.uint8, device="cuda")
     status = torch.empty(n, dtype=torch.int32, device="cuda")
@@ -127,14 +153,19 @@ def batch(path, repeats=5):
     for _ in range(repeats + 1):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        _lib.check(L.ysmr_mjpeg_decode_batch(None, chunks.data_ptr(), offsets_dev.data_ptr(), n, video.height, video.width, video.channels,
-                                             sampling, ws.data_ptr(), ws_bytes, out.data_ptr(), status.data_ptr()), "ysmr_mjpeg_decode_batch")
+        if sync:
+            check(L.ysmr_mjpeg_decode_batch_sync(None, chunks.data_ptr(), offsets_dev.data_ptr(), n, video.height, video.width,
+                                                 video.channels, sampling, largest, ws.data_ptr(), ws_bytes, out.data_ptr(),
+                                                 status.data_ptr()))
+        else:
+            check(L.ysmr_mjpeg_decode_batch(None, chunks.data_ptr(), offsets_dev.data_ptr(), n, video.height, video.width, video.channels,
+                                            sampling, ws.data_ptr(), ws_bytes, out.data_ptr(), status.data_ptr()))
         b.record()
         torch.cuda.synchronize()
         times.append(a.elapsed_time(b))
     assert not status.any().item(), "a frame was flagged"
-    print("{}: ysmr_mjpeg_decode_batch, {} frames, {:.1f} MB of chunks, workspace {:.0f} MB: {} ms, median {:.2f} ms = {:.0f} frames/s".format(
-        os.path.basename(path), n, offsets[n] / 1e6, ws_bytes / 1e6, " ".join("{:.2f}".format(t) for t in times[1:]),
+    print("{}: {}, {} frames, {:.1f} MB of chunks, workspace {:.0f} MB: {} ms, median {:.2f} ms = {:.0f} frames/s".format(
+        os.path.basename(path), name, n, offsets[n] / 1e6, ws_bytes / 1e6, " ".join("{:.2f}".format(t) for t in times[1:]),
         statistics.median(times[1:]), n / statistics.median(times[1:]) * 1e3))
     video.close()
 
@@ -172,8 +203,14 @@ def everything(libs=()):
             steps.append((["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(work, "trace_" + name),
                            "--"] + me + ["batch", path], 300))
             steps.append((me + ["kernels", os.path.join(work, "trace_" + name)], 60))
+            # the entry that decodes a frame without restart markers with many lanes: the same batch, then its kernels
+            steps.append((me + ["batch", path, "sync"], 300))
+            steps.append((["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(work, "sync_" + name),
+                           "--"] + me + ["batch", path, "sync"], 300))
+            steps.append((me + ["kernels", os.path.join(work, "sync_" + name)], 60))
             for lib in libs:                                           # the same batch through other builds, on the same box
                 steps.append((me + ["batch", path], 300, lib))
+                steps.append((me + ["batch", path, "sync"], 300, lib))
             steps.append((["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", os.path.join(work, "pipe_" + name), "--"] + me +
                           ["run", path, "device"], 300))
             steps.append((me + ["cotenancy", os.path.join(work, "pipe_" + name)], 60))
@@ -206,7 +243,7 @@ if __name__ == "__main__":
         else:
             run(sys.argv[2])
     elif sys.argv[1] == "batch":
-        batch(sys.argv[2])
+        batch(sys.argv[2], sync=len(sys.argv) > 3 and sys.argv[3] == "sync")
     elif sys.argv[1] == "kernels":
         kernels(sys.argv[2])
     elif sys.argv[1] == "cotenancy":

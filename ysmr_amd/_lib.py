@@ -63,7 +63,8 @@ EXPORTS = ("ysmr_abi_version", "ysmr_last_error", "ysmr_detect_workspace_bytes",
            "ysmr_tracker_run3", "ysmr_tracker_peek3", "ysmr_tracker_prepare3", "ysmr_annotate_batch", "ysmr_plot_colormap",
            "ysmr_plot_extent", "ysmr_plot_workspace_bytes", "ysmr_plot_tracks", "ysmr_plot_angle_histogram", "ysmr_plot_wedges",
            "ysmr_mjpeg_workspace_bytes", "ysmr_mjpeg_batch", "ysmr_violin_workspace_bytes", "ysmr_violin_stats", "ysmr_plot_violins",
-           "ysmr_mjpeg_decode_workspace_bytes", "ysmr_mjpeg_decode_batch")
+           "ysmr_mjpeg_decode_workspace_bytes", "ysmr_mjpeg_decode_batch",
+           "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_batch_sync", "ysmr_mjpeg_decode_sync_geometry")
 
 #: numpy view of ``ysmr_mark`` (16 bytes): one track position of one frame of the annotated video
 MARK_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("track_id", "<u4"), ("style", "<u4")])
@@ -234,13 +235,18 @@ def lib():
     L.ysmr_mjpeg_decode_workspace_bytes.argtypes = [ci, ci, ci, ci, ci]
     L.ysmr_mjpeg_decode_workspace_bytes.restype = ctypes.c_size_t
     L.ysmr_mjpeg_decode_batch.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, ctypes.c_size_t, vp, vp]
+    L.ysmr_mjpeg_decode_sync_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, ci]
+    L.ysmr_mjpeg_decode_sync_workspace_bytes.restype = ctypes.c_size_t
+    L.ysmr_mjpeg_decode_batch_sync.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, ctypes.c_size_t, vp, vp]
+    L.ysmr_mjpeg_decode_sync_geometry.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    L.ysmr_mjpeg_decode_sync_geometry.restype = None
     L.ysmr_mjpeg_batch.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.c_size_t, ci, ci, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp]
     L.ysmr_violin_workspace_bytes.argtypes = [ll, ci, ci]
     L.ysmr_violin_workspace_bytes.restype = ctypes.c_size_t
     L.ysmr_violin_stats.argtypes = [vp, ll, vp, ll, vp, ll, ci, vp, vp, vp, ctypes.c_size_t, vp, vp]
     L.ysmr_plot_violins.argtypes = [vp, ci, vp, vp, ctypes.POINTER(ViolinView), vp, ctypes.c_size_t, vp]
     for name in EXPORTS:
-        if name not in ("ysmr_mjpeg_decode_workspace_bytes", "ysmr_violin_workspace_bytes", "ysmr_mjpeg_workspace_bytes", "ysmr_plot_workspace_bytes", "ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
+        if name not in ("ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_sync_geometry", "ysmr_mjpeg_decode_workspace_bytes", "ysmr_violin_workspace_bytes", "ysmr_mjpeg_workspace_bytes", "ysmr_plot_workspace_bytes", "ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
                         "ysmr_rows_sort_workspace_bytes", "ysmr_rows_csv_bound", "ysmr_rows_stream_count",
                         "ysmr_mean_threshold_state_bytes"):
             getattr(L, name).restype = ci

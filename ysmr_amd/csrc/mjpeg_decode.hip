@@ -14,9 +14,13 @@
 //                  index is checked before its store -> int16 coef[frame][block][64], natural order, zeroed by the memset
 //   k_mjd_idct     eight threads per block: dequantise, columns, rows (through LDS), clamp -> sample planes (gray: the frame)
 //   k_mjd_colour   a thread per pixel: fancy upsampling of the chrominance planes, 16-bit fixed-point colour -> B, G, R
+// ysmr_mjpeg_decode_batch_sync is the same call for files WITHOUT restart markers (what cameras, ffmpeg, OpenCV and Pillow write): a
+// frame with a restart interval takes k_mjd_entropy as above, one without takes k_mjd_destuff, k_mjd_sync and k_mjd_dc (below,
+// "entropy decode of a frame WITHOUT restart markers"), which decode it with a lane per 64 bytes instead of one per frame.
 // No kernel writes outside the workspace, status_dev and the frame's own H * W * channels bytes; every read of chunks_dev lies
 // inside the frame's own [offsets[i], offsets[i + 1]).
 #include "common.h"
+#include "mjpeg_decode_plan.h"
 #include <algorithm>
 
 namespace {
@@ -55,61 +59,16 @@ __constant__ uint8_t c_zigzag[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 1
                                      7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31,
                                      39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
-// ---- the geometry of a call (host and device) --------------------------------------------------------------------------------
-struct Geo {
-    int H, W, sampling, nc;
-    int lh, lv;                       // sampling factors of the luminance
-    int mx, my, mcus;                 // MCUs per row, MCU rows, MCUs per frame = the most restart intervals a frame can have
-    int ycols, yrows, ccols, crows;   // blocks per plane
-    int blocks_y, blocks_c, blocks;   // blocks per frame
-    int ypitch, cpitch;               // bytes per row of the sample planes (whole blocks)
-    size_t plane_y, plane_c, planes;  // bytes of the sample planes of a frame (0 for one component: the frame is the plane)
-};
+// the geometry of a call, what k_mjd_headers leaves per frame and the workspace's layout: mjpeg_decode_plan.h (host-only code)
+using mjd::FrameInfo;
+using mjd::Geo;
+using mjd::geometry_of;
+using mjd::HuffRaw;
+using mjd::Plan;
+using mjd::plan_of;
 
-// the part of it the serial kernels need (a kernel's arguments live in scalar registers, and these kernels have few to spare)
+// the part of the geometry the serial kernels need (a kernel's arguments live in scalar registers, and these kernels have few to spare)
 struct SmallGeo { int H, W, nc, lh, lv, mx, mcus, ycols, ccols, blocks_y, blocks_c, blocks; };
-
-// what k_mjd_headers leaves per frame
-struct FrameInfo {
-    int32_t ent_start, ent_end;       // the entropy data [start, end) inside the frame's bytes
-    int32_t ri, nseg;                 // restart interval in MCUs (0: none), restart intervals of the frame
-    uint32_t tq, td, ta;              // per component, a byte each: quantisation table, DC and AC Huffman slot
-    uint32_t defined;                 // bit 4 * class + slot: the frame's Huffman table is in the workspace
-};
-struct HuffRaw { uint8_t bits[16]; uint8_t vals[256]; };
-
-struct Plan {
-    size_t info, quant, huff, seg_start, coef, planes, total;
-};
-
-Plan plan_of(int n, const Geo &g)
-{
-    Plan p;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t here = at; at += ysmr::align_up(bytes, 256); return here; };
-    p.info = take((size_t)n * sizeof(FrameInfo));
-    p.quant = take((size_t)n * 4 * 64 * sizeof(uint16_t));
-    p.huff = take((size_t)n * 8 * sizeof(HuffRaw));
-    p.seg_start = take((size_t)n * g.mcus * sizeof(int32_t));
-    p.coef = take((size_t)n * g.blocks * 64 * sizeof(int16_t));
-    p.planes = take((size_t)n * g.planes);
-    p.total = at;
-    return p;
-}
-
-bool geometry_of(int n, int H, int W, int channels, int sampling, Geo &g)
-{
-    if (n <= 0 || H <= 0 || W <= 0 || H > 65535 || W > 65535 || sampling < 0 || sampling > 3) return false;
-    if (channels != (sampling == 0 ? 1 : 3)) return false;
-    g.H = H; g.W = W; g.sampling = sampling; g.nc = channels;
-    g.lh = sampling >= 2 ? 2 : 1; g.lv = sampling == 3 ? 2 : 1;
-    g.mx = (W + 8 * g.lh - 1) / (8 * g.lh); g.my = (H + 8 * g.lv - 1) / (8 * g.lv); g.mcus = g.mx * g.my;
-    g.ycols = g.mx * g.lh; g.yrows = g.my * g.lv; g.ccols = g.mx; g.crows = g.my;
-    g.blocks_y = g.ycols * g.yrows; g.blocks_c = g.nc == 3 ? g.ccols * g.crows : 0; g.blocks = g.blocks_y + 2 * g.blocks_c;
-    g.ypitch = 8 * g.ycols; g.cpitch = 8 * g.ccols;
-    g.plane_y = g.nc == 3 ? (size_t)64 * g.blocks_y : 0; g.plane_c = (size_t)64 * g.blocks_c; g.planes = g.plane_y + 2 * g.plane_c;
-    return true;
-}
 
 // ---- headers -----------------------------------------------------------------------------------------------------------------
 // A LANE walks the markers of one frame; `at(p)` never reads outside the frame.  The checks come in the order of the model's, so
@@ -395,16 +354,9 @@ __device__ __forceinline__ int next_symbol(BitReader &r, const Tables &tb, int t
 
 __device__ __forceinline__ int extend(uint32_t v, int size) { return v < (1u << (size - 1)) ? (int)v - (1 << size) + 1 : (int)v; }
 
-__global__ __launch_bounds__(64) void k_mjd_entropy(const uint8_t *__restrict__ chunks, const long long *__restrict__ offsets, SmallGeo g,
-                                                    const FrameInfo *__restrict__ info, const HuffRaw *__restrict__ huff,
-                                                    const int32_t *__restrict__ seg_start, int16_t *__restrict__ coef, int *__restrict__ status)
+// (every thread of a workgroup of `threads` calls it; the tables are complete behind it)
+__device__ __forceinline__ void build_tables(Tables &tb, const FrameInfo &fi, const HuffRaw *__restrict__ hf, int tid, int threads)
 {
-    __shared__ Tables tb;
-    const int f = blockIdx.y, tid = threadIdx.x;
-    if (status[f] != 0) return;
-    const FrameInfo fi = info[f];
-    if ((int)blockIdx.x * 64 >= fi.nseg) return;
-    const HuffRaw *hf = huff + (size_t)f * 8;
     if (tid < 8) {
         int code = 0, k = 0;
         tb.maxcode[tid][0] = -1; tb.valoff[tid][0] = 0;
@@ -416,10 +368,10 @@ __global__ __launch_bounds__(64) void k_mjd_entropy(const uint8_t *__restrict__ 
             k += b;
         }
     }
-    for (int i = tid; i < 8 * 256; i += 64) tb.vals[i >> 8][i & 255] = ((fi.defined >> (i >> 8)) & 1) ? hf[i >> 8].vals[i & 255] : 0;
-    tb.zigzag[tid] = c_zigzag[tid];
+    for (int i = tid; i < 8 * 256; i += threads) tb.vals[i >> 8][i & 255] = ((fi.defined >> (i >> 8)) & 1) ? hf[i >> 8].vals[i & 255] : 0;
+    if (tid < 64) tb.zigzag[tid] = c_zigzag[tid];
     __syncthreads();
-    for (int i = tid; i < 8 << LUT_BITS; i += 64) {
+    for (int i = tid; i < 8 << LUT_BITS; i += threads) {
         const int t = i >> LUT_BITS, idx = i & ((1 << LUT_BITS) - 1);
         uint32_t e = 0;
         for (int l = 1; l <= LUT_BITS; ++l) {
@@ -429,6 +381,19 @@ __global__ __launch_bounds__(64) void k_mjd_entropy(const uint8_t *__restrict__ 
         tb.lut[t][idx] = (uint16_t)e;
     }
     __syncthreads();
+}
+
+__global__ __launch_bounds__(64) void k_mjd_entropy(const uint8_t *__restrict__ chunks, const long long *__restrict__ offsets, SmallGeo g,
+                                                    const FrameInfo *__restrict__ info, const HuffRaw *__restrict__ huff,
+                                                    const int32_t *__restrict__ seg_start, int16_t *__restrict__ coef, int *__restrict__ status)
+{
+    __shared__ Tables tb;
+    const int f = blockIdx.y, tid = threadIdx.x;
+    if (status[f] != 0) return;
+    const FrameInfo fi = info[f];
+    if ((int)blockIdx.x * 64 >= fi.nseg) return;
+    const HuffRaw *hf = huff + (size_t)f * 8;
+    build_tables(tb, fi, hf, tid, 64);
 
     const uint8_t *base = chunks + offsets[f];
     const int32_t *seg = seg_start + (size_t)f * g.mcus;
@@ -479,6 +444,301 @@ __global__ __launch_bounds__(64) void k_mjd_entropy(const uint8_t *__restrict__ 
         if (r.overran()) corrupt = true;
     }
     if (corrupt) atomicOr(&status[f], YSMR_MJPEGD_CORRUPT);
+}
+
+// ---- entropy decode of a frame WITHOUT restart markers (ysmr_mjpeg_decode_batch_sync) ------------------------------------------
+// Huffman-coded data has no marks a decoder could start from, but a decoder started at a wrong bit falls into step with the
+// code after a few symbols.  So the frame's data is cut into subsequences of SYNC_SUB_BYTES, a lane each, and
+//   k_mjd_destuff  takes the stuffing out first: the reader's rules -- 0x00 behind a 0xFF (after any number of fill 0xFF) is no
+//                  data, a marker ends it -- applied once, by a compaction; behind it a position is a plain bit number and a
+//                  decoder can start at any of them
+//   k_mjd_sync     a workgroup per frame, SYNC_PASS subsequences per pass: every lane decodes the symbols that START in its
+//                  subsequence from an assumed state (its first bit, a DC symbol of block 0), storing nothing, and hands its
+//                  exit state to its successor, which decodes again from that -- until no lane's entry state changed; then the
+//                  blocks are counted by a scan and every lane decodes once more, from its TRUE state, and stores.  DC values
+//                  are stored as differences
+//   k_mjd_dc       the prefix sums of those differences per component, over the blocks in scan order
+// tests/jpeg_sync_model.py is the same in Python, with the rounds of every pass.
+
+// STATE of a decoder between two symbols: the bit position in the destuffed data and (k | i << 8 | error << 16): block k of the
+// MCU, zigzag index i inside it; `error`: it met a code no table holds, a DC category above 11 or an index past 63 on the way --
+// for an assumed state an exit like any other, which flags nothing and which the successor does not take over.
+constexpr int SYNC_ERROR = 1 << 16;
+
+// 32 bits at any bit position of data[0, bytes): bytes behind the end read as zeros.  The window holds eight bytes and is loaded
+// anew when the position has left its first 32 bits.  The data lies in the workspace with eight bytes to spare behind it
+// (SyncPlan::data_pitch), so that is ONE load and a mask that clears what lies behind the end -- whatever the workspace held
+// there is not used.
+struct BitWindow {
+    const uint8_t *data;
+    int bytes;
+    uint64_t w;
+    int first;                        // bit number of the window's first bit; far away: nothing loaded
+    __device__ __forceinline__ void start(const uint8_t *d, int n) { data = d; bytes = n; w = 0; first = -(1 << 30); }
+    __device__ __forceinline__ uint32_t peek(int pos)                       // 0 <= pos < 8 * bytes
+    {
+        uint32_t off = (uint32_t)(pos - first);
+        if (off > 32u) {
+            const int at = pos >> 3, valid = bytes - at;                     // valid >= 1
+            uint64_t raw;
+            __builtin_memcpy(&raw, data + at, 8);
+            if (valid < 8) raw &= ~0ull >> (64 - 8 * valid);
+            first = pos & ~7;
+            w = __builtin_bswap64(raw);
+            off = (uint32_t)(pos & 7);
+        }
+        return (uint32_t)((w << off) >> 32);
+    }
+};
+
+struct SyncFrame {                    // what the symbol loop needs of the frame and the call, in registers
+    uint32_t td, ta;
+    int luma, per_mcu;
+};
+
+// The symbols that start before bit `stop`, from state (pos, ki) on; `done` counts the blocks completed.  `store` (the same in
+// every lane): `block0` is the frame's number of blocks completed before, the coefficients go to fcoef (DC as the difference),
+// and decoding ends with the frame's last block; the return value then tells whether the frame is damaged.  ONE copy of this
+// loop serves the rounds and the write pass: two of them cost more scalar registers than there are.
+__device__ __forceinline__ bool sync_decode(BitWindow &r, const Tables &tb, const SyncFrame &sf, int &pos, int &ki, int stop, int &done,
+                                            const SmallGeo &g, bool store, int block0, int total_bits, int16_t *__restrict__ fcoef)
+{
+    int k = ki & 255, i = (ki >> 8) & 255;
+    bool error = (ki & SYNC_ERROR) != 0, ended = store && block0 >= g.blocks;
+    int16_t *out = nullptr;
+    done = 0;
+    while (pos < stop && !error && !ended) {
+        const int c = k < sf.luma ? 0 : k - sf.luma + 1;
+        if (store && (i == 0 || !out)) {
+            // where the block lies (a lane may enter in the middle of one): MCU (mrow, mcol) of the scan, block k inside it
+            const int mcu = (block0 + done) / sf.per_mcu, mrow = mcu / g.mx, mcol = mcu - mrow * g.mx;
+            const int sy = g.lh == 2 ? k >> 1 : k, sx = g.lh == 2 ? k & 1 : 0;
+            const int block = c == 0 ? (mrow * g.lv + sy) * g.ycols + mcol * g.lh + sx : g.blocks_y + (c - 1) * g.blocks_c + mrow * g.ccols + mcol;
+            if ((unsigned)block >= (unsigned)g.blocks) { error = true; break; }      // (the block index is checked before the store)
+            out = fcoef + (size_t)block * 64;
+        }
+        const int t = i == 0 ? (int)((sf.td >> (8 * c)) & 3) : 4 + (int)((sf.ta >> (8 * c)) & 3);
+        const uint32_t w = r.peek(pos);
+        uint32_t e = tb.lut[t][w >> (32 - LUT_BITS)];
+        if (!e) {
+            #pragma nounroll
+            for (int l = LUT_BITS + 1; l <= 16; ++l) {
+                const int code = (int)(w >> (32 - l));
+                if (code <= tb.maxcode[t][l]) { e = ((uint32_t)l << 8) | tb.vals[t][(tb.valoff[t][l] + code) & 255]; break; }
+            }
+        }
+        const int len = (int)(e >> 8), sym = (int)(e & 255);
+        if (!e || (i == 0 && sym > 11)) { error = true; break; }
+        const int size = sym & 15, run = i == 0 ? 0 : sym >> 4;
+        bool complete;
+        if (i > 0 && size == 0) {                                            // end of block, or sixteen zeros
+            pos += len;
+            i += 16;
+            complete = run != 15 || i > 63;
+        } else {
+            i += run;
+            if (i > 63) { error = true; break; }                             // (the index is checked before the store)
+            if (store) out[tb.zigzag[i]] = (int16_t)(size ? extend((w << len) >> (32 - size), size) : 0);
+            pos += len + size;
+            complete = ++i == 64;
+        }
+        if (complete) {
+            i = 0;
+            if (++k == sf.per_mcu) k = 0;
+            ++done;
+            if (store && block0 + done == g.blocks) ended = true;            // what follows the last block is not looked at
+        }
+    }
+    ki = k | (i << 8) | (error ? SYNC_ERROR : 0);
+    // damaged: a symbol of the frame's blocks that no table holds, or bits of them beyond the data's end
+    return store && block0 < g.blocks && (error || (ended && pos > total_bits));
+}
+
+// A WORKGROUP compacts one frame's entropy data, 16 bytes per thread and step (the loop of k_mjd_markers).  Inside [ent_start,
+// ent_end) of a frame that k_mjd_markers passed there is no marker: a 0xFF is followed by 0x00, by another 0xFF or by the end.
+// Of a run of 0xFF the first is data and the others fill bytes, the 0x00 behind it is stuffing; a run the data ends with is
+// the beginning of the marker that ended it.  The frames of this call that HAVE a restart interval are k_mjd_entropy's, and
+// those that have none are taken from it here: no restart interval of theirs is left (nseg = 0).
+__global__ __launch_bounds__(256) void k_mjd_destuff(const uint8_t *__restrict__ chunks, const long long *__restrict__ offsets, int max_chunk,
+                                                     FrameInfo *__restrict__ info, uint8_t *__restrict__ data, size_t pitch,
+                                                     int32_t *__restrict__ data_bytes, int *__restrict__ status)
+{
+    __shared__ int s_go, s_count, s_wave[4];
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) {
+        int st = status[f];
+        if (st == 0 && offsets[f + 1] - offsets[f] > (long long)max_chunk) status[f] = st = YSMR_MJPEGD_CORRUPT;
+        s_go = st == 0 && info[f].ri == 0;
+        if (s_go) info[f].nseg = 0;
+        s_count = 0;
+    }
+    __syncthreads();
+    if (!s_go) return;
+    const uint8_t *base = chunks + offsets[f];
+    const int start = info[f].ent_start, len = info[f].ent_end;
+    uint8_t *out = data + (size_t)f * pitch;
+    for (long long step0 = start; step0 < len; step0 += 256 * 16) {
+        const long long p0 = step0 + tid * 16;
+        uint32_t keep = 0;
+        uint64_t w0 = 0, w1 = 0;
+        if (p0 < len) {
+            w0 = load8(base + p0, base + len); w1 = load8(base + p0 + 8, base + len);
+            uint32_t prev = p0 > start ? base[p0 - 1] : 0u;
+            for (int j = 0; j < 16 && p0 + j < len; ++j) {
+                const uint32_t b = (uint32_t)((j < 8 ? w0 >> (8 * j) : w1 >> (8 * j - 64)) & 255);
+                if (!(prev == 0xFF && (b == 0x00 || b == 0xFF))) keep |= 1u << j;
+                prev = b;
+            }
+        }
+        int incl = __popc(keep);
+        const int mine = incl;
+        for (int d = 1; d < 64; d <<= 1) {
+            const int o = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += o;
+        }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        int k = s_count + incl - mine;
+        for (int v = 0; v < wave; ++v) k += s_wave[v];
+        for (int j = 0; j < 16; ++j)
+            if ((keep >> j) & 1) {
+                if ((size_t)k < pitch) out[k] = (uint8_t)((j < 8 ? w0 >> (8 * j) : w1 >> (8 * j - 64)) & 255);
+                ++k;
+            }
+        __syncthreads();
+        if (tid == 0) s_count += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+        __syncthreads();
+    }
+    if (tid == 0) data_bytes[f] = s_count - (len > start && base[len - 1] == 0xFF ? 1 : 0);
+}
+
+__global__ __launch_bounds__(mjd::SYNC_PASS) void k_mjd_sync(SmallGeo g0, const FrameInfo *__restrict__ info, const HuffRaw *__restrict__ huff,
+                                                             const uint8_t *__restrict__ data, size_t pitch,
+                                                             const int32_t *__restrict__ data_bytes, int16_t *__restrict__ coef,
+                                                             int *__restrict__ status)
+{
+    constexpr int PASS = mjd::SYNC_PASS, SUB_BITS = 8 * mjd::SYNC_SUB_BYTES, WAVES = PASS / 64;
+    __shared__ Tables tb;
+    __shared__ int s_pos[PASS], s_ki[PASS], s_wave[WAVES];
+    __shared__ SmallGeo s_geo;        // the geometry is read from here: once per block, and scalar registers are the scarce ones
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (status[f] != 0) return;
+    const FrameInfo fi = info[f];
+    if (fi.ri != 0) return;
+    if (tid == 0) s_geo = g0;
+    build_tables(tb, fi, huff + (size_t)f * 8, tid, PASS);
+    const SmallGeo &g = s_geo;
+
+    // (what is the same in every lane is told to be: loops whose conditions are scalar cost no saved execution masks)
+    const int bytes = __builtin_amdgcn_readfirstlane(data_bytes[f]), total_bits = 8 * bytes;
+    const int blocks = __builtin_amdgcn_readfirstlane(g.blocks);
+    const int nsub = (bytes + mjd::SYNC_SUB_BYTES - 1) / mjd::SYNC_SUB_BYTES;
+    int16_t *fcoef = coef + (size_t)f * g.blocks * 64;
+    SyncFrame sf;
+    sf.td = fi.td; sf.ta = fi.ta;
+    sf.luma = g.lh * g.lv; sf.per_mcu = g.nc == 1 ? 1 : sf.luma + 2;
+    BitWindow r;
+    r.start(data + (size_t)f * pitch, bytes);
+    int true_pos = 0, true_ki = 0, blocks_done = 0;                         // the state behind the passes so far (the same in every lane)
+    bool corrupt = false;
+    for (int s0 = 0; s0 < nsub && blocks_done < blocks && !(true_ki & SYNC_ERROR); s0 += PASS) {
+        const int s = s0 + tid;
+        const bool active = s < nsub;
+        const int stop = (int)std::min<long long>((long long)(s + 1) * SUB_BITS, total_bits);
+        // lane 0 starts from the TRUE state, every other lane at its first bit, expecting the DC symbol of block 0
+        const int first_bit = active ? s * SUB_BITS : 0;
+        int in_pos = tid == 0 ? true_pos : first_bit, in_ki = tid == 0 ? true_ki : 0;
+        int was_pos = -1, was_ki = -1, done = 0, before = 0, all = 0;
+        // After round r the first r lanes hold true states and decode no more, so there are PASS rounds at most; the rounds
+        // end when NO lane's entry state changed, and then every entry state is the true one: the blocks completed before
+        // each lane are counted, and the loop's last turn is the write pass.
+        for (bool store = false;;) {
+            const bool go = active && (store || in_pos != was_pos || in_ki != was_ki);
+            if (go) {
+                int pos = in_pos, ki = in_ki, n;
+                const bool damaged = sync_decode(r, tb, sf, pos, ki, stop, n, g, store, before, total_bits, fcoef);
+                if (store) {
+                    corrupt = corrupt || damaged;
+                } else {
+                    s_pos[tid] = pos; s_ki[tid] = ki; done = n;
+                    was_pos = in_pos; was_ki = in_ki;
+                }
+            }
+            if (store) break;
+            if (__builtin_amdgcn_readfirstlane(__syncthreads_or(go))) {
+                if (active && tid > 0) {
+                    in_pos = s_pos[tid - 1]; in_ki = s_ki[tid - 1];
+                    // a predecessor that met an error has nothing to hand on: this lane keeps to its assumed state (the error
+                    // of one wrong guess must not silence every lane behind it until the true state arrives)
+                    if (in_ki & SYNC_ERROR) { in_pos = first_bit; in_ki = 0; }
+                }
+                __syncthreads();
+                continue;
+            }
+            // blocks completed before this lane's subsequence: an exclusive scan.  (The lanes are chosen by arithmetic, x >> 31 =
+            // -1 for x < 0: comparisons that do not change from round to round are kept in scalar register pairs, ten of them)
+            int incl = done;
+            for (int d = 1; d < 64; d <<= 1) incl += __builtin_amdgcn_ds_bpermute((lane - d) << 2, incl) & ((d - 1 - lane) >> 31);
+            if (lane == 63) s_wave[wave] = incl;
+            __syncthreads();
+            before = blocks_done + incl - done;
+            #pragma nounroll
+            for (int v = 0; v < WAVES; ++v) {
+                if (v < wave) before += s_wave[v];                           // (`wave` is a scalar)
+                all += s_wave[v];
+            }
+            all = __builtin_amdgcn_readfirstlane(all);
+            store = true;
+        }
+        const int last = std::min(PASS, nsub - s0) - 1;
+        true_pos = __builtin_amdgcn_readfirstlane(s_pos[last]); true_ki = __builtin_amdgcn_readfirstlane(s_ki[last]);
+        blocks_done += all;
+        // (a barrier in any case: s_pos, s_ki and s_wave are written again; behind a damaged pass nothing is worth decoding)
+        if (__builtin_amdgcn_readfirstlane(__syncthreads_or(corrupt))) break;
+    }
+    // the data ended before the frame's last block (a decoder that read on would read the zeros behind it)
+    if (blocks_done < blocks) corrupt = true;
+    if (corrupt) atomicOr(&status[f], YSMR_MJPEGD_CORRUPT);
+}
+
+// DC: the prefix sums of the differences, per component over its blocks in SCAN order (the luminance blocks of an MCU follow
+// each other in the scan, not in the plane), 32 bits wide and stored as the serial decoder's (int16_t) v -- truncation commutes
+// with the sum.  A thread sums a run of consecutive blocks, the runs are scanned, the thread walks its run again.
+__global__ __launch_bounds__(256) void k_mjd_dc(SmallGeo g, const FrameInfo *__restrict__ info, const int *__restrict__ status,
+                                                int16_t *__restrict__ coef)
+{
+    __shared__ int s_wave[4];
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (status[f] != 0 || info[f].ri != 0) return;
+    int16_t *fcoef = coef + (size_t)f * g.blocks * 64;
+    const int luma = g.lh * g.lv;
+    for (int c = 0; c < g.nc; ++c) {
+        const int count = c == 0 ? g.blocks_y : g.blocks_c, per = (count + 255) / 256;
+        const int j0 = std::min(count, tid * per), j1 = std::min(count, j0 + per);
+        auto block_of = [&](int j) {
+            if (c > 0) return g.blocks_y + (c - 1) * g.blocks_c + j;
+            const int mcu = j / luma, k = j - mcu * luma, mrow = mcu / g.mx, mcol = mcu - mrow * g.mx;
+            const int sy = g.lh == 2 ? k >> 1 : k, sx = g.lh == 2 ? k & 1 : 0;
+            return (mrow * g.lv + sy) * g.ycols + mcol * g.lh + sx;
+        };
+        uint32_t sum = 0;                                                    // (unsigned: the sums wrap by definition)
+        for (int j = j0; j < j1; ++j) sum += (uint32_t)(int)fcoef[(size_t)block_of(j) * 64];
+        uint32_t incl = sum;
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t o = (uint32_t)__shfl_up((int)incl, d, 64);
+            if (lane >= d) incl += o;
+        }
+        if (lane == 63) s_wave[wave] = (int)incl;
+        __syncthreads();
+        uint32_t v = incl - sum;
+        for (int u = 0; u < wave; ++u) v += (uint32_t)s_wave[u];
+        for (int j = j0; j < j1; ++j) {
+            int16_t *dc = fcoef + (size_t)block_of(j) * 64;
+            v += (uint32_t)(int)*dc;
+            *dc = (int16_t)v;
+        }
+        __syncthreads();
+    }
 }
 
 // ---- dequantise + IDCT ---------------------------------------------------------------------------------------------------------
@@ -659,6 +919,80 @@ extern "C" int ysmr_mjpeg_decode_batch(void *stream, const uint8_t *chunks_dev, 
     const unsigned ex = (unsigned)std::min(ENTROPY_GRID_X, (g.mcus + 63) / 64);
     hipLaunchKernelGGL(k_mjd_entropy, dim3(ex, n_frames), dim3(64), 0, st, chunks_dev, offsets, sg, info, huff, seg_start, coef,
                        (int *)status_dev);
+    YSMR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_mjd_idct, dim3(grid_of((long long)n_frames * g.blocks, 32)), dim3(256), 0, st, coef, quant, info,
+                       (const int *)status_dev, n_frames, g, planes, frames_dev);
+    YSMR_LAUNCH_CHECK();
+    if (g.nc == 3) {
+        hipLaunchKernelGGL(k_mjd_colour, dim3(grid_of((long long)n_frames * height * width, 256)), dim3(256), 0, st, planes,
+                           (const int *)status_dev, n_frames, g, frames_dev);
+        YSMR_LAUNCH_CHECK();
+    }
+    return YSMR_OK;
+}
+
+extern "C" void ysmr_mjpeg_decode_sync_geometry(int *subsequence_bytes, int *subsequences_per_pass)
+{
+    if (subsequence_bytes) *subsequence_bytes = mjd::SYNC_SUB_BYTES;
+    if (subsequences_per_pass) *subsequences_per_pass = mjd::SYNC_PASS;
+}
+
+extern "C" size_t ysmr_mjpeg_decode_sync_workspace_bytes(int n_frames, int height, int width, int channels, int sampling, int max_chunk_bytes)
+{
+    Geo g;
+    mjd::SyncPlan p;
+    if (!mjd::sync_plan_of(n_frames, height, width, channels, sampling, max_chunk_bytes, g, p)) return 0;
+    return p.total;
+}
+
+extern "C" int ysmr_mjpeg_decode_batch_sync(void *stream, const uint8_t *chunks_dev, const int64_t *offsets_dev, int n_frames, int height,
+                                            int width, int channels, int sampling, int max_chunk_bytes, void *workspace_dev,
+                                            size_t workspace_bytes, uint8_t *frames_dev, int32_t *status_dev)
+{
+    Geo g;
+    mjd::SyncPlan sp;
+    if (!mjd::sync_plan_of(n_frames, height, width, channels, sampling, max_chunk_bytes, g, sp))
+        return ysmr::fail(YSMR_ERR_ARG, "n_frames must be positive, height and width 1 .. 65535, sampling 0 .. 3 with 1 channel for 0 and 3 "
+                          "otherwise, max_chunk_bytes 1 .. %d (got %d, %d, %d, sampling %d, %d channels, max_chunk_bytes %d), and the "
+                          "workspace's size must fit a size_t", mjd::SYNC_MAX_CHUNK, n_frames, height, width, sampling, channels, max_chunk_bytes);
+    if (!chunks_dev || !offsets_dev || !workspace_dev || !frames_dev || !status_dev)
+        return ysmr::fail(YSMR_ERR_ARG, "chunks_dev, offsets_dev, workspace_dev, frames_dev and status_dev must not be NULL");
+    if (workspace_bytes < sp.total)
+        return ysmr::fail(YSMR_ERR_ARG, "workspace of %zu bytes, %zu needed (ysmr_mjpeg_decode_sync_workspace_bytes)", workspace_bytes, sp.total);
+    if (((uintptr_t)workspace_dev & 255) || ((uintptr_t)offsets_dev & 7) || ((uintptr_t)status_dev & 3))
+        return ysmr::fail(YSMR_ERR_ARG, "workspace_dev must be 256-byte aligned, offsets_dev 8-byte, status_dev 4-byte");
+
+    hipStream_t st = (hipStream_t)stream;
+    const Plan &p = sp.base;
+    uint8_t *ws = (uint8_t *)workspace_dev;
+    FrameInfo *info = (FrameInfo *)(ws + p.info);
+    uint16_t *quant = (uint16_t *)(ws + p.quant);
+    HuffRaw *huff = (HuffRaw *)(ws + p.huff);
+    int32_t *seg_start = (int32_t *)(ws + p.seg_start);
+    int16_t *coef = (int16_t *)(ws + p.coef);
+    uint8_t *planes = ws + p.planes, *data = ws + sp.data;
+    int32_t *data_bytes = (int32_t *)(ws + sp.data_bytes);
+    const long long *offsets = (const long long *)offsets_dev;
+    const SmallGeo sg = {g.H, g.W, g.nc, g.lh, g.lv, g.mx, g.mcus, g.ycols, g.ccols, g.blocks_y, g.blocks_c, g.blocks};
+    hipLaunchKernelGGL(k_mjd_headers, dim3((n_frames + 63) / 64), dim3(64), 0, st, chunks_dev, offsets, n_frames, sg, info, quant, huff,
+                       (int *)status_dev);
+    YSMR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_mjd_markers, dim3(n_frames), dim3(256), 0, st, chunks_dev, offsets, g.mcus, info, seg_start, (int *)status_dev);
+    YSMR_LAUNCH_CHECK();
+    YSMR_HIP_CHECK(hipMemsetAsync(coef, 0, (size_t)n_frames * g.blocks * 64 * sizeof(int16_t), st));
+    // the frames part here: those without a restart interval leave k_mjd_entropy none to decode (k_mjd_destuff) and are
+    // k_mjd_sync's and k_mjd_dc's, which pass over the others
+    hipLaunchKernelGGL(k_mjd_destuff, dim3(n_frames), dim3(256), 0, st, chunks_dev, offsets, max_chunk_bytes, info, data, sp.data_pitch,
+                       data_bytes, (int *)status_dev);
+    YSMR_LAUNCH_CHECK();
+    const unsigned ex = (unsigned)std::min(ENTROPY_GRID_X, (g.mcus + 63) / 64);
+    hipLaunchKernelGGL(k_mjd_entropy, dim3(ex, n_frames), dim3(64), 0, st, chunks_dev, offsets, sg, info, huff, seg_start, coef,
+                       (int *)status_dev);
+    YSMR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_mjd_sync, dim3(n_frames), dim3(mjd::SYNC_PASS), 0, st, sg, info, huff, data, sp.data_pitch, data_bytes, coef,
+                       (int *)status_dev);
+    YSMR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_mjd_dc, dim3(n_frames), dim3(256), 0, st, sg, info, (const int *)status_dev, coef);
     YSMR_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_mjd_idct, dim3(grid_of((long long)n_frames * g.blocks, 32)), dim3(256), 0, st, coef, quant, info,
                        (const int *)status_dev, n_frames, g, planes, frames_dev);

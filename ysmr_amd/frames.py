@@ -560,9 +560,10 @@ class DeviceFrameFeed:
     56 (`scripts/feed_copy_timeline.py`).
 
     ``decode_on_device`` (the settings key 'hip decode mjpeg'): True -- a Motion-JPEG AVI whose ``jpeg_layout`` is not None (a
-    supported first frame WITH a restart interval) -- or "always" -- also one without restart markers, for which the host path
-    is the faster one -- is uploaded as chunk bodies and decoded by
-    ``ysmr_mjpeg_decode_batch`` on the copy stream; the per-frame status comes back once per batch, and a frame it flags
+    supported first frame WITH a restart interval) -- or "always" -- also one without restart markers -- is uploaded as chunk
+    bodies and decoded on the copy stream: by ``ysmr_mjpeg_decode_batch``, a lane per restart interval, or under "always" by
+    ``ysmr_mjpeg_decode_batch_sync``, which decodes a frame without restart markers with a lane per 64 bytes of its entropy data
+    (and one with them as the other call does); the per-frame status comes back once per batch, and a frame it flags
     (outside the supported subset, or damaged) is decoded again by the host path and copied into its place -- with whatever
     that path raises.  False: every frame takes the host path."""
 
@@ -581,6 +582,7 @@ class DeviceFrameFeed:
         # Motion-JPEG AVI: the chunk bodies go to the device as they are and are decoded there
         if decode_on_device not in (True, False, "always"):
             raise ValueError("decode_on_device must be True, False or 'always', got {!r}".format(decode_on_device))
+        self._decode_on_device = decode_on_device
         self._jpeg = video.jpeg_layout_for(self.B, needs_restart=decode_on_device != "always") \
             if decode_on_device and hasattr(video, "jpeg_layout_for") else None
         self._cpus = cpus_near_gpu(self.device) if near_gpu else None
@@ -611,9 +613,17 @@ class DeviceFrameFeed:
             self._status_dev = [torch.empty(self.B, dtype=torch.int32, device=self.device) for _ in range(self.depth)]
             self._status = [torch.empty(self.B, dtype=torch.int32, pin_memory=True) for _ in range(self.depth)]
             self._frame_host = torch.empty(shape[1:], dtype=torch.uint8, pin_memory=True)       # for a frame the host decodes
-            ws = _lib.lib().ysmr_mjpeg_decode_workspace_bytes(self.B, shape[1], shape[2], self.video.channels, sampling)
+            # 'always': the entry that also decodes a frame without restart markers with many lanes; it sizes its workspace
+            # by the file's largest chunk
+            self._jpeg_sync = self._decode_on_device == "always"
+            if self._jpeg_sync:
+                ws = _lib.lib().ysmr_mjpeg_decode_sync_workspace_bytes(self.B, shape[1], shape[2], self.video.channels, sampling,
+                                                                       self._jpeg[1])
+            else:
+                ws = _lib.lib().ysmr_mjpeg_decode_workspace_bytes(self.B, shape[1], shape[2], self.video.channels, sampling)
             if ws == 0:
-                raise ValueError("ysmr_mjpeg_decode_workspace_bytes refuses {} frames of {} x {}".format(self.B, shape[2], shape[1]))
+                raise ValueError("ysmr_mjpeg_decode_{}workspace_bytes refuses {} frames of {} x {} (largest chunk {} bytes)".format(
+                    "sync_" if self._jpeg_sync else "", self.B, shape[2], shape[1], self._jpeg[1]))
             self._jpeg_ws = torch.empty(ws, dtype=torch.uint8, device=self.device)             # (the slots' decodes are serial)
         elif self._raw is not None:
             raw_bytes, _, _, _, palette = self._raw
@@ -720,10 +730,16 @@ class DeviceFrameFeed:
             if released is not True:
                 self._copy_stream.wait_event(released)          # the kernels that read this device buffer are done
             self._jpeg_dev[slot][:used].copy_(self._pinned[slot][:used], non_blocking=True)
-            _lib.check(_lib.lib().ysmr_mjpeg_decode_batch(
-                self._copy_stream.cuda_stream, self._jpeg_dev[slot].data_ptr() + head, self._jpeg_dev[slot].data_ptr(), n,
-                video.height, video.width, video.channels, self._jpeg[0], self._jpeg_ws.data_ptr(), self._jpeg_ws.numel(),
-                self._dev[slot].data_ptr(), self._status_dev[slot].data_ptr()), "ysmr_mjpeg_decode_batch")
+            if self._jpeg_sync:
+                _lib.check(_lib.lib().ysmr_mjpeg_decode_batch_sync(
+                    self._copy_stream.cuda_stream, self._jpeg_dev[slot].data_ptr() + head, self._jpeg_dev[slot].data_ptr(), n,
+                    video.height, video.width, video.channels, self._jpeg[0], self._jpeg[1], self._jpeg_ws.data_ptr(),
+                    self._jpeg_ws.numel(), self._dev[slot].data_ptr(), self._status_dev[slot].data_ptr()), "ysmr_mjpeg_decode_batch_sync")
+            else:
+                _lib.check(_lib.lib().ysmr_mjpeg_decode_batch(
+                    self._copy_stream.cuda_stream, self._jpeg_dev[slot].data_ptr() + head, self._jpeg_dev[slot].data_ptr(), n,
+                    video.height, video.width, video.channels, self._jpeg[0], self._jpeg_ws.data_ptr(), self._jpeg_ws.numel(),
+                    self._dev[slot].data_ptr(), self._status_dev[slot].data_ptr()), "ysmr_mjpeg_decode_batch")
             self._status[slot][:n].copy_(self._status_dev[slot][:n], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self._copy_stream)
@@ -786,7 +802,8 @@ class DeviceFrameFeed:
 def decode_mjpeg_setting(settings):
     """The ``decode_on_device`` argument of ``DeviceFrameFeed`` from the optional settings key 'hip decode mjpeg': true
     (default: Motion-JPEG files with restart markers are decoded on the device), false (every frame by the host path) or
-    'always' (files without restart markers too)."""
+    'always' (files without restart markers too, by ``ysmr_mjpeg_decode_batch_sync``: what cameras, ffmpeg, OpenCV and Pillow
+    write; profiles/mjpeg_decode_sync_e2e.log has the rates)."""
     value = settings.get("hip decode mjpeg", True)
     if isinstance(value, str):
         word = value.strip().lower()

@@ -336,8 +336,9 @@ def track_bacteria(video_path, settings=None, result_folder=None, batch=None, ma
     out on the device (``ysmr_rows_format_device``); False: on the host's threads (``ysmr_rows_write_csv_columns``) -- the same
     bytes and bits either way.  'hip stream rows' (default False): the host's threads print the rows while the video runs.
     'hip decode mjpeg' (default True): a Motion-JPEG AVI of baseline frames with restart markers is decoded on the device
-    (``ysmr_mjpeg_decode_batch``); 'always': one without restart markers too; False: by Pillow on the reader threads
-    (``frames.decode_mjpeg_setting``).
+    (``ysmr_mjpeg_decode_batch``); 'always': one without restart markers too -- what cameras, ffmpeg, OpenCV and Pillow write
+    -- by ``ysmr_mjpeg_decode_batch_sync``, which gives such a frame a lane per 64 bytes of its entropy data instead of one in
+    all; False: by Pillow on the reader threads (``frames.decode_mjpeg_setting``).
     """
     logger = logging.getLogger("ysmr").getChild(__name__)
     settings = get_configs(settings)
