@@ -494,7 +494,11 @@ int ysmr_tracker_info(ysmr_tracker *t, void *stream, int32_t *n_tracks, int32_t 
 
 /* Order rows by (TRACK_ID, POSITION_T): what sort_list does to the csv after tracking
  * (helper_file.py:1538-1574, called at track_eval.py:393).  rows_dev and sorted_dev are distinct
- * device arrays of n_rows rows; (track_id, frame) pairs are unique, so the order is total. */
+ * device arrays of n_rows rows; (track_id, frame) pairs are unique, so the order is total.
+ * On return the first uint32 of the workspace reports which ordering ran: 0, the table had the tracker's shape (ids
+ * below n_rows, every track with one row in every frame from its first to its last) and each row was put at
+ * offset[id] + frame - first_frame[id] without a sort, sorted_dev is complete; 1, any other table, ordered by the stable
+ * radix sort of (track_id << 32 | frame) (equal pairs keep their input order), which may still be running on `stream`. */
 size_t ysmr_rows_sort_workspace_bytes(long long n_rows);
 int    ysmr_rows_sort(void *stream, const ysmr_row *rows_dev, long long n_rows, void *workspace_dev,
                       size_t workspace_bytes, ysmr_row *sorted_dev);

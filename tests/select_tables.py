@@ -1,5 +1,7 @@
 """Synthetic (TRACK_ID, POSITION_T)-ordered tables for the select_tracks tests: tracks with holes,
-jumps, lost ('disappeared') rows, odd shapes and sizes, positions near and beyond the frame."""
+jumps, lost ('disappeared') rows, odd shapes and sizes, positions near and beyond the frame -- and the builders of the
+tables at the sizes of a real video (tests/test_gpu_tables_at_scale.py): dust tracks by the million, spans beyond uint16,
+rows in the tracker's emission order, rows of mixed values for the formatter."""
 import numpy as np
 import pandas as pd
 
@@ -52,6 +54,81 @@ def make_table(seed, n_tracks=60, height=400, width=600, max_len=260):
                                    "POSITION_X": xy[:, 0], "POSITION_Y": xy[:, 1], "WIDTH": w, "HEIGHT": h,
                                    "DEGREES_ANGLE": deg}))
     return pd.concat(parts, ignore_index=True)
+
+
+_COLUMNS = ("TRACK_ID", "POSITION_T", "POSITION_X", "POSITION_Y", "WIDTH", "HEIGHT", "DEGREES_ANGLE")
+
+
+def dust_table(real, n_rows_total, seed, height=400, width=600):
+    """`real` (a make_table result) with equal blocks of 2-row 'dust' tracks in front of each of its tracks: block, real
+    track, block, real track, ...; the table ends with a real track.  Dust tracks have frames 0 and 1, positions anywhere
+    in the frame, WIDTH in 4..8 and HEIGHT in 1..3 (an area median like any track's: they fall to the length rule of
+    the clean-up, after their medians were worked out).  Ids ascend through the whole table -- a real track's becomes
+    (its rank + 1) * (block + 1) - 1 -- and the block is the smallest that gives at least `n_rows_total` rows."""
+    rng = np.random.default_rng(seed)
+    rank = np.unique(real["TRACK_ID"].to_numpy(), return_inverse=True)[1].astype(np.int64)
+    n_real = int(rank.max()) + 1
+    block = max(0, -(-(int(n_rows_total) - len(real)) // (2 * n_real)))
+    n_dust = block * n_real
+    dust_id = np.arange(n_dust, dtype=np.int64)
+    dust_id += dust_id // max(block, 1)                               # one id left free behind every block
+    ids = np.concatenate([np.repeat(dust_id, 2), (rank + 1) * (block + 1) - 1])
+    order = np.argsort(ids, kind="stable")
+    dust = {"POSITION_T": np.tile(np.array([0, 1], np.uint32), n_dust),
+            "POSITION_X": rng.uniform(0.0, width, 2 * n_dust), "POSITION_Y": rng.uniform(0.0, height, 2 * n_dust),
+            "WIDTH": rng.uniform(4.0, 8.0, 2 * n_dust), "HEIGHT": rng.uniform(1.0, 3.0, 2 * n_dust),
+            "DEGREES_ANGLE": rng.uniform(-90.0, 0.0, 2 * n_dust)}
+    out = {"TRACK_ID": ids[order].astype(np.uint32)}
+    for name in _COLUMNS[1:]:
+        out[name] = np.concatenate([dust[name], real[name].to_numpy()])[order]
+    return pd.DataFrame(out)
+
+
+def with_wrapping_spans(real, spans=(65566, 65546)):
+    """`real` behind one 2-row track per entry of `spans`, frames (0, span - 1); the real tracks' ids move up.  A span of
+    65,536 frames or more does not fit the uint16 the reference keeps it in (track_eval.py:655-659): 65,566 counts as
+    30 frames, 65,546 as 10."""
+    k = len(spans)
+    rng = np.random.default_rng(1)
+    head = pd.DataFrame({"TRACK_ID": np.repeat(np.arange(k, dtype=np.uint32), 2),
+                         "POSITION_T": np.array([f for s in spans for f in (0, s - 1)], np.uint32),
+                         "POSITION_X": rng.uniform(100, 500, 2 * k), "POSITION_Y": rng.uniform(100, 300, 2 * k),
+                         "WIDTH": rng.uniform(4, 8, 2 * k), "HEIGHT": rng.uniform(1, 3, 2 * k),
+                         "DEGREES_ANGLE": rng.uniform(-90, 0, 2 * k)})
+    tail = real.copy()
+    tail["TRACK_ID"] = (tail["TRACK_ID"] + k).astype(np.uint32)
+    return pd.concat([head, tail], ignore_index=True)
+
+
+def tracker_shaped(n, n_tracks, seed):
+    """(track_id, frame) of `n` rows as the link emits them: ids 0 .. n_tracks - 1, every track with a row in every frame
+    from its first to its last, rows frame by frame and ids ascending within a frame."""
+    rng = np.random.default_rng(seed)
+    cuts = np.sort(rng.choice(np.arange(1, n), n_tracks - 1, replace=False)) if n_tracks > 1 else np.zeros(0, np.int64)
+    lengths = np.diff(np.r_[0, cuts, n])
+    first = rng.integers(0, 25, n_tracks)
+    ids = np.repeat(np.arange(n_tracks), lengths)
+    frames = np.concatenate([f + np.arange(m) for f, m in zip(first, lengths)])
+    order = np.lexsort((ids, frames))
+    return ids[order].astype(np.int64), frames[order].astype(np.int64)
+
+
+def value_mix_rows(n, seed=33):
+    """`n` ordered rows (200 per track) of mixed values for the device formatter's tests: uniform and float32-widened
+    doubles, ties, halves, negative values, zeros, the neighbours of powers of two.  Their lines have many lengths."""
+    from ysmr_amd import _lib
+    rng = np.random.default_rng(seed)
+    rows = np.zeros(n, _lib.ROW_DTYPE)
+    rows["track_id"] = np.arange(n) // 200
+    rows["frame"] = np.arange(n) % 200
+    powers = np.ldexp(1.0, np.arange(-20, 24))
+    edge = np.concatenate([powers, np.nextafter(powers, 0)[1:], np.nextafter(powers, np.inf), [0.0, -0.0, 0.1, 0.5, 1e-5, 123456.789]])
+    rows["x"] = np.where(rng.random(n) < 0.5, rng.uniform(-5, 1300, n), rng.uniform(0, 4000, n).astype(np.float32).astype(np.float64))
+    rows["x"][:len(edge)] = edge
+    rows["y"] = rng.integers(0, 4000, n) + rng.choice([0, 0.5, 0.25, 0.125, 0.1, 0.3], n)
+    rows["w"], rows["h"] = rng.uniform(0, 40, n).astype(np.float32), rng.uniform(0, 40, n).astype(np.float32)
+    rows["angle"] = rng.uniform(-90, 90, n).astype(np.float32)
+    return rows
 
 
 def select_settings(**kw):

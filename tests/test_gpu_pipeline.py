@@ -815,20 +815,10 @@ def test_device_formatter_against_the_host_formatter_on_a_large_table(tmp_path):
     neighbours of powers of two) against ``ysmr_rows_write_csv_columns``: file and columns identical; a table with a NaN is
     declined (``None``: the caller takes the host path), an empty table is its header."""
     import torch
-    from ysmr_amd import _lib
+    from select_tables import value_mix_rows
     from ysmr_amd.helper_file import rows_device_to_csv_file_and_dataframe, rows_to_csv_file_and_dataframe
-    rng = np.random.default_rng(33)
     n = 400000
-    rows = np.zeros(n, _lib.ROW_DTYPE)
-    rows["track_id"] = np.arange(n) // 200
-    rows["frame"] = np.arange(n) % 200
-    powers = np.ldexp(1.0, np.arange(-20, 24))
-    edge = np.concatenate([powers, np.nextafter(powers, 0)[1:], np.nextafter(powers, np.inf), [0.0, -0.0, 0.1, 0.5, 1e-5, 123456.789]])
-    rows["x"] = np.where(rng.random(n) < 0.5, rng.uniform(-5, 1300, n), rng.uniform(0, 4000, n).astype(np.float32).astype(np.float64))
-    rows["x"][:len(edge)] = edge
-    rows["y"] = rng.integers(0, 4000, n) + rng.choice([0, 0.5, 0.25, 0.125, 0.1, 0.3], n)
-    rows["w"], rows["h"] = rng.uniform(0, 40, n).astype(np.float32), rng.uniform(0, 40, n).astype(np.float32)
-    rows["angle"] = rng.uniform(-90, 90, n).astype(np.float32)
+    rows = value_mix_rows(n, seed=33)
     dev = torch.from_numpy(rows.view(np.uint8).copy()).cuda()
     for via in (True, False):
         a, b = tmp_path / "host.csv", tmp_path / "device.csv"
