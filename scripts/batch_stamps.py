@@ -62,6 +62,14 @@ for rep in range(12 if beside else 6):
         cn = np.array(cnt[:], dtype=np.int64).reshape(NW, len(count_names))
         for k, what in enumerate(count_names):
             print(f"   {what:58s}", cn[:, k].tolist())
+    if hasattr(L, "ysmr_debug_read_bwaves"):
+        hist = (ctypes.c_ulonglong * 17)()
+        L.ysmr_debug_read_bwaves(hist)
+        print("   frames run on k track waves:", {k: int(v) for k, v in enumerate(hist[:]) if v})
+    if hasattr(L, "ysmr_debug_read_bseats"):
+        seats = (ctypes.c_ulonglong * 2)()
+        L.ysmr_debug_read_bseats(seats)
+        print(f"   frames that gave up track waves: {int(seats[0])}, tracks moved in them: {int(seats[1])}")
     print(f"rep {rep}: launch pair {t0.elapsed_time(t1) * 1e3:.1f} us for {B} frames; frame (wave 0) {a[0, LAST] - a[0, 0]} cycles")
 a = np.mean(np.array(acc), axis=0) if beside else np.median(np.array(acc), axis=0)
 d = np.diff(a, axis=1)

@@ -9,7 +9,8 @@ wrote, or the compiler's own -S output.  The walk starts at the head of the fram
   * it falls through, and follows unconditional branches;
   * a FORWARD conditional branch (s_cbranch_execz / vccz / vccnz / scc0 / scc1) jumps over a guarded block.  The block is
     skipped -- it is a rare path: the 3 x 3 search, the quadrant list of a split cell, the wave search, the exact claims, the
-    registration, the seeding of a new track, a filter bank that grows -- unless it holds one of the landmarks below (the blocks under `propose`, `alive` and
+    registration, the seeding of a new track, a filter bank that grows, the block that gives up a track wave (its landmark:
+    three or more s_barrier around a 16-byte load and a 16-byte store, the ring copy) -- unless it holds one of the landmarks below (the blocks under `propose`, `alive` and
     the row's bounds check ARE the steady frame) or vector-memory loads without a barrier or a loop (the ring entries that
     leave the windows, the claimed detection's box);
   * of an if / else (s_andn2_saveexec / s_or_saveexec between the halves) whose first half was skipped, the second half
@@ -153,6 +154,12 @@ def _loop_head(ins):
     return best
 
 
+def _seat_block(ops):
+    """The block at the head of the frame loop that gives up a track wave (batch_link.h): barriers of its own around the
+    ring copy, whole entries loaded and stored."""
+    return ops.count("s_barrier") >= 3 and "global_load_dwordx4" in ops and "global_store_dwordx4" in ops
+
+
 def walk(ins):
     """Indices of the steady frame's instructions, and the skipped blocks as (first, one past last)."""
     head, close = _loop_head(ins)
@@ -193,7 +200,7 @@ def walk(ins):
             marks = {o for o in block if o in STEADY_MARKS}
             if marks == {"ds_read_b128"} and any(ins[j][0] == "ds_read_b128" for j in path):
                 marks = set()
-            if not marks and not row and not loads:
+            if _seat_block(block) or (not marks and not row and not loads):
                 skipped.append((i + 1, tgt))
                 i = tgt
                 continue
@@ -365,6 +372,30 @@ def census(text):
     total["instructions"] = len(path)
     out["frame"] = total
     out["skipped blocks"] = len(skipped)
+    out_path = [ins[i][:2] for i in path]
+    # the block that gives up a track wave, and what its trigger costs the steady frame: the scalar arithmetic, the compare
+    # and the branch between the loop head and the block (everything else there is the frame's own)
+    seats = [(a, b) for a, b in skipped if _seat_block([o for o, _, _ in ins[a:b]]) and a - 1 in pos]
+    if len(seats) > 1:
+        raise SystemExit(f"{len(seats)} skipped blocks have the seat block's landmark: the landmark no longer names one block")
+    if seats:
+        # the trigger: the scalar chain that ends in the block's branch -- from the branch back, the compare that sets scc
+        # and the instructions that write a register the chain reads (the round-up add, the shift); anything else in front
+        # of the branch is the frame's own
+        seat = seats[0]
+        at = pos[seat[0] - 1]
+        trig, need = [ops[at]], set()
+        for k in range(at - 1, -1, -1):
+            op, args = out_path[k]
+            if op.startswith("s_cmp_") and len(trig) == 1:
+                trig.append(op); need |= _sregs(args)
+            elif len(trig) > 1 and op.startswith("s_") and not op.startswith(("s_waitcnt", "s_nop", "s_cmp_")):
+                dst, _, src = args.partition(",")
+                if _sregs(dst) & need:
+                    trig.append(op); need = (need - _sregs(dst)) | _sregs(src)
+        if len(trig) < 2:
+            raise SystemExit("no scalar compare in front of the seat block's branch: is this its trigger?")
+        out["seat block"] = {"instructions": seat[1] - seat[0], "branch at": at, "trigger": trig[::-1]}
     out["barriers"] = sum(o == "s_barrier" for o in ops)
     out["path"] = [ins[i][:2] for i in path]
     out["marks"] = {"claim": claim, "barrier A": bar_a, "row end": row_end, "filter bank": fb, "filter bank end": fb_end}
@@ -426,6 +457,11 @@ def report(c):
         lead = f"{name:18s}" if len(name) <= 18 else f"{name}\n{'':18s}"
         lines.append(lead + f"{r['instructions']:9d}" + "".join(f"{r[k]:9d}" for k in COLUMNS))
     lines.append(f"s_barrier on the walked path: {c['barriers']}")
+    if "seat block" in c:
+        sb = c["seat block"]
+        lines.append(f"the block that gives up a track wave: {sb['instructions']} instructions, skipped; its trigger adds "
+                     f"{len(sb['trigger'])} instructions to \"chores + search\" ({' '.join(sb['trigger'])}), the branch is "
+                     f"instruction {sb['branch at']} of the pass")
     return "\n".join(lines)
 
 

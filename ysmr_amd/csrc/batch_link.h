@@ -472,6 +472,16 @@ __device__ __forceinline__ double2 bl_ring_load_bytes(const BatchDev &bd, unsign
     v.y = __hip_atomic_load(p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return v;
 }
+// (a whole entry with ONE instruction, for the seats' ring copy: 16 bytes are more than an atomic load takes, so the load
+// and its wait are written out -- sc1, as the compiler writes an agent-scope load; the compiler's own books know nothing
+// of it and need not: it is complete where the statement ends)
+typedef uint32_t bl_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ bl_u32x4 bl_ring_load16(const double2 *p)
+{
+    bl_u32x4 v;
+    asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(v) : "v"(p) : "memory");
+    return v;
+}
 __device__ __forceinline__ void bl_ring_store(const BatchDev &bd, int pos, int seat, double x, double y)
 {
     bd.ring[(size_t)pos * bd.seat_cap + seat] = make_double2(x, y);
@@ -481,12 +491,21 @@ __device__ __forceinline__ void bl_ring_store(const BatchDev &bd, int pos, int s
 // head - 1 - a; a filter's window holds the newest min(N, len) of them.  Done for every track at the frames whose index
 // is a multiple of BL_REFRESH (a schedule in FRAME numbers: the rows of a video must not depend on how its frames were cut
 // into batches), and by k_to_batch.
+// (WHOLE: an entry with one 16-byte load, bl_ring_load16 -- k_batch, whose loop waits for every entry before it asks for
+// the next either way)
+template <bool WHOLE = false>
 __device__ __forceinline__ void bl_sums_from_ring(BlSeat &S, const BatchDev &bd, int seat, int head, int n0, int n1, int n2)
 {
     const int lim[BL_NF] = {min(n0, S.len), min(n1, S.len), min(n2, S.len)};
     double s0x = 0.0, s1x = 0.0, s0y = 0.0, s1y = 0.0;
     for (int a = 0; a < BL_HB - 1; ++a) {
-        const double2 e = bl_ring_load(bd, (head - 1 - a) & (BL_HB - 1), seat);
+        double2 e;
+        if constexpr (WHOLE) {
+            const bl_u32x4 w = bl_ring_load16(bd.ring + (size_t)((head - 1 - a) & (BL_HB - 1)) * bd.seat_cap + seat);
+            e.x = __hiloint2double((int)w.y, (int)w.x); e.y = __hiloint2double((int)w.w, (int)w.z);
+        } else {
+            e = bl_ring_load(bd, (head - 1 - a) & (BL_HB - 1), seat);
+        }
         if (a < S.len) {
             s0x = s0x + e.x;
             s0y = s0y + e.y;
@@ -956,6 +975,8 @@ __device__ __forceinline__ BlNear bl_search_wave(const BlGridView &g, double px,
 
 // ---- the kernel ----------------------------------------------------------------------------------------------------
 constexpr int BL_COUNTS = 9;
+constexpr int BL_SEAT_SLACK_WAVES = 0;      // a track wave is given up when the live tracks fit in this many fewer than hold one, + 1
+constexpr int BL_MOVE_WORDS = 7 * BL_NF + 4 + 4;      // a track on the move, 64-bit words: the filter state, px, py, o0, o1; eight 32-bit fields
 #ifdef YSMR_STAMPS
 __device__ unsigned long long g_bstamps[BL_WAVES][16];
 #ifndef YSMR_BL_FRAME
@@ -967,6 +988,9 @@ __device__ unsigned long long g_bstamps[BL_WAVES][16];
 // 4 frames with registration, 5 wave-frames refreshing the window sums from the ring, 6 frames with deaths, 7 deaths,
 // 8 frames on the exact claim path
 __device__ unsigned long long g_bcounts[BL_WAVES][BL_COUNTS];
+// (the seats' two counts and the histogram in arrays of their own: tests/test_gpu_batch_claims.py reads g_bcounts as it is)
+__device__ unsigned long long g_bseats[2];                 // the launch's frames that gave up track waves, tracks moved in them
+__device__ unsigned long long g_bwaves[BL_WAVES + 1];      // the launch's frames by the track waves they ran on (0 .. BL_WAVES)
 #define BLCOUNT(k, cond) do { const unsigned long long b_ = __ballot(cond); if (lane == 0 && b_) g_bcounts[wave][k] += 1; } while (0)
 #else
 #define BLSTAMP(k) do {} while (0)
@@ -1039,7 +1063,6 @@ __device__ __forceinline__ void bl_wait_vmem() { __builtin_amdgcn_s_waitcnt(0x0F
 // library and on every variant build it finds, scripts/build_stamps.sh on the stamps build.  Hence also: every wait is
 // reached by every wave on every path from its load (none under a test of `alive`).  (An access the compiler does not know of only makes its own
 // lgkmcnt(N) waits stricter: LDS returns in order, so "at most N open" still covers every older LDS access.)
-typedef uint32_t bl_u32x4 __attribute__((ext_vector_type(4)));
 struct BlSearchArgs { const float *det_all; int hz[BL_NF]; };
 // The rows a buffer of `capacity` still takes behind `base`, in 32 bits.  A launch writes fewer than 2^20 rows (BL_MAX_BATCH
 // frames of at most BL_THREADS), so the clamps are never reached by counting down: above INT_MAX everything fits, and a
@@ -1125,6 +1148,8 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
     // whose tables nobody clears: a lane that proposes nothing reads it and compares it with a key no table holds)
     if (tid < 3) key_at(tid)[0] = ~0ull;
     if (tid == 0) sh.top = 0;
+    // (the launch's seat events, tracks moved and track waves at its end, behind the ring's head: ysmr_debug_seat_events)
+    if (tid == 0) { bd.head[1] = 0; bd.head[2] = 0; bd.head[3] = 0; }
     BlSeat S;
     bl_seat_blank(S);
     if (n > 0 && tid < seats && bd.i32[5 * (size_t)bd.seat_cap + tid]) {     // (an empty table: whatever the flags say)
@@ -1189,6 +1214,17 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
     //                subtracts it.  dead_id likewise: rewritten behind A(f + 2).
     //   sh.used      as before: parity par ^ 1 is reset behind A(f); it was last read by frame f - 1's registration, in
     //                front of A(f), and is next added to behind A(f + 1).
+    //   seat block   (rare: a track wave is given up, at the head of frame f, four barriers of its own; every wave takes it
+    //                or none.)  Its opening barrier stands behind every wave's frame f - 1: the key table of frame f - 1
+    //                and the table of winning ids are dead, and every lane's ring store of frame f - 1 has landed (each
+    //                wave waits for its vector memory in front of it -- a helper's grid pieces with it).  The state and
+    //                the seat lists are written in front of the second barrier and read behind it; the waves' `alive`
+    //                votes in front of the third, sh.top and the ring copy behind it; the closing barrier stands behind
+    //                every thread's wait for its copies, and sh.top is read behind it.  helpers_from only falls here, so a
+    //                wave that requested grid pieces as a helper is still one where it waits for them.  The table is
+    //                cleared for frame f + 2 behind A(f), behind the registration, whose scratch it is next; its column 0
+    //                is not touched.  n_dead / dead_id of frame f - 1 are not touched either: the moved tracks' stale ranks
+    //                are settled behind A(f), in their new lanes.
     // The claim key carries S.rank as it stood BEFORE frame f - 1's deaths were taken off (they are, behind A(f)).  It is
     // still a valid tie-breaker: for two live tracks a < b (by id) the stale ranks are the true ranks plus the number of
     // frame f - 1's dead with a smaller id, which is no smaller for b than for a -- so stale ranks stay unique among the
@@ -1201,7 +1237,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
     // ranks, row and counts of frame `fr`, whose deaths were counted in sh.n_dead[slot] from `start` on; behind the barrier
     // that follows the frame's ageing.  Returns the running count.
     auto settle = [&](int slot, int start, int fr, bool row) {
-        const int total = sh.n_dead[slot];
+        const int total = __builtin_amdgcn_readfirstlane(sh.n_dead[slot]);      // (uniform: one lane move serves the count and the return)
         const int n_dead = total - start;
 #ifdef YSMR_STAMPS
         if (lane == 0 && n_dead) { g_bcounts[wave][6] += 1; g_bcounts[wave][7] += n_dead; }
@@ -1218,13 +1254,15 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
                 if (tid == 0) atomicOr(bl_kernargs()->t.err, ERR_ROWS_CAPACITY);
             }
             if (fits) {      // track_eval.py:313-316
-                ysmr_row rr;
-                rr.frame = frame0 + fr;
-                rr.track_id = S.id;
-                rr.x = o0; rr.y = o1;
-                rr.w = S.info[0]; rr.h = S.info[1]; rr.angle = S.info[2];
-                rr.disappeared = S.gone;
-                rowp[S.rank] = rr;
+                // (the box and `gone` first: their four registers are put together for the store, the position's are not --
+                // the same 40 bytes as one struct assignment, which can come back if a later compiler's allocation keeps
+                // tests/test_kernel_bookkeeping.py's limit on ranks + row without this order)
+                ysmr_row *rp = rowp + S.rank;
+                rp->w = S.info[0]; rp->h = S.info[1]; rp->angle = S.info[2];
+                rp->disappeared = S.gone;
+                rp->frame = frame0 + fr;
+                rp->track_id = S.id;
+                rp->x = o0; rp->y = o1;
             }
             rowp += n; room -= n;
         }
@@ -1244,7 +1282,123 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
 #ifdef YSMR_STAMPS
         if (f == 0 && lane == 0)
             for (int k = 0; k < BL_COUNTS; ++k) g_bcounts[wave][k] = 0;
+        if (f == 0 && tid == 0) {      // (in front of the seat block, which counts into them)
+            g_bseats[0] = g_bseats[1] = 0;
+            for (int k = 0; k <= BL_WAVES; ++k) g_bwaves[k] = 0;
+        }
         BLCOUNT(5, ((frame0 + f) & (BL_REFRESH - 1)) == 0 && S.alive && t.use_gsff);
+#endif
+        // ---- a track wave is given up (rare): the live tracks fit in fewer waves than hold one.  `n` is stale by the
+        // deaths of the frame before (they come off behind barrier A), which only makes the test conservative.
+        if (((n + 63) >> 6) + BL_SEAT_SLACK_WAVES < helpers_from) {
+            // (the thread, its wave and lane as values of this frame, as in the registration)
+            // (and the table's number: held from here it would take a scalar register through the search of every frame)
+            int tl = tid, wv = wave, ln = lane, mp = mdp, kd = kc;
+            asm volatile("" : "+v"(tl), "+s"(wv), "+v"(ln), "+s"(mp), "+s"(kd));
+            kd = 3 - kd - (kd == 2 ? 0 : kd + 1);
+            const int keep = (n + 63) >> 6;                  // the waves that stay track waves
+            // The live lanes at and above wave `keep` move into the free lanes below it, highest wave first, mover k into
+            // the k-th free lane.  The state passes through the key table of frame f - 1 (dead behind the opening barrier,
+            // cleared for frame f + 2 behind barrier A; column 0 stays as it is, see the prologue), the seat numbers through
+            // the table of winning ids.  What the table does not hold stays seated and moves in the next frame.
+            // (what the block keeps across its barriers, in vector registers: scalar ones are short)
+            int room_for = (mp - 1) / BL_MOVE_WORDS;
+            unsigned long long *box = bl_lds + kd * mp + 1;
+            uint32_t *seat_of = bl_u32(6 * mp);
+            int role = S.alive ? (tl >= 64 * keep ? 1 : 0) : (tl < min(64 * keep, seats) ? 2 : 0);      // 1: mover, 2: target
+            int mr, tr;
+            {
+                const unsigned long long b_mv = __ballot(role == 1), b_tg = __ballot(role == 2);
+                if (ln == 0) { sh.wave_cnt[0][wv] = (int)__popcll(b_mv); sh.wave_cnt[1][wv] = (int)__popcll(b_tg); }
+                mr = (int)__popcll(b_mv & below); tr = (int)__popcll(b_tg & below);
+            }
+            asm volatile("" : "+v"(role), "+v"(room_for), "+v"(mr), "+v"(tr));
+            // (this lane's ring store of the frame before has landed: another thread copies it below)
+            bl_wait_vmem();
+            __syncthreads();
+            int movers = 0;
+#pragma unroll
+            for (int k = 0; k < BL_WAVES; ++k) {
+                const int v = sh.wave_cnt[0][k];
+                mr += k > wv ? v : 0; movers += v;
+                tr += k < wv ? sh.wave_cnt[1][k] : 0;
+            }
+            int n_mov = min(movers, room_for);
+            asm volatile("" : "+v"(n_mov));
+            if (role == 1 && mr >= n_mov) role = 0;      // (does not fit the table: stays seated)
+            if (role == 2 && tr >= n_mov) role = 0;
+            asm volatile("" : "+v"(role));
+            if (role == 1) {
+                unsigned long long *p = box + mr;
+                int j = 0;
+                auto put = [&](double v) { p[room_for * j++] = (unsigned long long)__double_as_longlong(v); };
+                auto put2 = [&](uint32_t lo, uint32_t hi) { p[room_for * j++] = (unsigned long long)lo | ((unsigned long long)hi << 32); };
+#pragma unroll
+                for (int k = 0; k < BL_NF; ++k) {
+                    put(S.s0x[k]); put(S.s1x[k]); put(S.s0y[k]); put(S.s1y[k]); put(S.w[k]); put(S.xa[k]); put(S.xb[k]);
+                }
+                put(S.px); put(S.py); put(o0); put(o1);
+                put2(__float_as_uint(S.info[0]), __float_as_uint(S.info[1]));
+                put2(__float_as_uint(S.info[2]), (uint32_t)S.id);
+                put2((uint32_t)S.gone, (uint32_t)S.len);
+                put2((uint32_t)S.rank, (uint32_t)grow_at);
+                seat_of[mr] = (uint32_t)tl;
+            }
+            if (role == 2) seat_of[room_for + tr] = (uint32_t)tl;
+            __syncthreads();
+            if (role == 1) {
+                bl_seat_blank(S);
+                grow_at = 0; o0 = o1 = 0.0;
+            }
+            if (role == 2) {
+                const unsigned long long *p = box + tr;
+                int j = 0;
+                auto get = [&]() { return __longlong_as_double((long long)p[room_for * j++]); };
+                auto get2 = [&](uint32_t &lo, uint32_t &hi) { const unsigned long long v = p[room_for * j++]; lo = (uint32_t)v; hi = (uint32_t)(v >> 32); };
+#pragma unroll
+                for (int k = 0; k < BL_NF; ++k) {
+                    S.s0x[k] = get(); S.s1x[k] = get(); S.s0y[k] = get(); S.s1y[k] = get(); S.w[k] = get(); S.xa[k] = get(); S.xb[k] = get();
+                }
+                S.px = get(); S.py = get(); o0 = get(); o1 = get();
+                uint32_t a, b;
+                get2(a, b); S.info[0] = __uint_as_float(a); S.info[1] = __uint_as_float(b);
+                get2(a, b); S.info[2] = __uint_as_float(a); S.id = (int)b;
+                get2(a, b); S.gone = (int)a; S.len = (int)b;
+                get2(a, b); S.rank = (int)a; grow_at = (int)b;
+                S.alive = true;
+            }
+            {
+                const unsigned long long b_live = __ballot(S.alive);
+                if (ln == 0) sh.wave_cnt[0][wv] = b_live != 0ull;
+            }
+            __syncthreads();
+            if (tl == 0) {      // one past the highest seat in use, set, not raised: between two barriers
+                int top = 0;
+#pragma unroll
+                for (int k = 0; k < BL_WAVES; ++k) top = sh.wave_cnt[0][k] ? 64 * (k + 1) : top;
+                sh.top = top;
+                int *seen = bl_kernargs()->bd.head;      // (ysmr_debug_seat_events: events and tracks moved of this launch)
+                atomicAdd(seen + 1, 1); atomicAdd(seen + 2, n_mov);
+#ifdef YSMR_STAMPS
+                g_bseats[0] += 1; g_bseats[1] += n_mov;
+#endif
+            }
+            // The ring goes with the seat: the 32 entries of every mover (not the line of zeros), one entry of one mover per
+            // thread and pass, past this unit's L1 as every ring load.  The copies have landed before the closing barrier.
+            {
+                double2 *ring = bl_kernargs()->bd.ring;
+                const size_t sc = (size_t)bl_kernargs()->bd.seat_cap;
+                for (int i = tl; i < n_mov * BL_HB; i += BL_THREADS) {
+                    const int k = i / BL_HB, e = i & (BL_HB - 1);
+                    *reinterpret_cast<bl_u32x4 *>(ring + e * sc + seat_of[room_for + k]) = bl_ring_load16(ring + e * sc + seat_of[k]);
+                }
+            }
+            bl_wait_vmem();
+            __syncthreads();
+            helpers_from = (sh.top + 63) >> 6;
+        }
+#ifdef YSMR_STAMPS
+        if (tid == 0) atomicAdd(&g_bwaves[helpers_from], 1ull);      // (no return value: nothing in the frame waits for a load)
 #endif
         if (((frame0 + f) & (BL_REFRESH - 1)) == 0 && S.alive && t.use_gsff) {     // (uniform but for `alive`: see bl_sums_from_ring)
             // (the lane's own ring stores of the frame before are complete, and nothing of the ring is left outstanding
@@ -1254,7 +1408,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
             // handle does not have: 0)
             const BlKernArgsPtr kh = bl_kernargs();
             const int h1 = kh->hz[1], h2 = kh->hz[2];
-            bl_sums_from_ring(S, bd, tid, head, kh->hz[0], h1 == 0x7FFFFFFF ? 0 : h1, h2 == 0x7FFFFFFF ? 0 : h2);
+            bl_sums_from_ring<true>(S, bd, tid, head, kh->hz[0], h1 == 0x7FFFFFFF ? 0 : h1, h2 == 0x7FFFFFFF ? 0 : h2);
             bl_wait_vmem();
         }
         // ---- each track proposes its nearest detection (tracker.py:151-163)
@@ -1279,7 +1433,8 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         }
 #endif
         BLSTAMP(11);
-        {   // the lanes the 5 x 5 cells did not settle, one after the other, by the whole wave
+        {   // the lanes bl_search did not settle (a second candidate within its float band, or a block that does not settle
+            // the lane), one after the other, by the whole wave
             unsigned long long todo = __ballot(propose && !nr.done);
 #ifdef YSMR_STAMPS
             if (f == YSMR_BL_FRAME && lane == 0) g_bstamps[wave][12] = __popcll(todo);
@@ -1297,6 +1452,9 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
                 todo &= todo - 1ull;
                 const BlNear w = bl_search_wave(gv, lane_value(S.px, l), lane_value(S.py, l), m, lane);
                 if (lane == l) nr = w;
+                // (nothing of the wave search is left in flight where the steady path goes on: the compiler would wait for
+                // it at the first register it shares with the claim, which may be right behind the scalar loads below)
+                __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt 0 (vmcnt 63, expcnt 7)
             }
         }
         unsigned long long sa_det;       // (det_all and the horizons: requested here, used behind the claim's atomic)
@@ -1317,8 +1475,14 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         // that lane raises the frame's flag.  Keys farther above M need no flag.
         if (propose) {
             key = ((unsigned long long)__double_as_longlong(nr.s) & ~0x3FFull) | (unsigned long long)S.rank;
+            // (the key's half of the band test in front of the atomic: behind it, on the wave's serial chain, the test is a
+            // shift, an add and a compare.  The same arithmetic modulo 2^64 as (before >> 10) - (key >> 10) + 1; written
+            // this way for tests/test_kernel_bookkeeping.py's limit on the claims -- it can go back to the one expression
+            // if a later compiler's allocation makes room)
+            unsigned long long band = 1ull - (key >> 10);
+            asm volatile("" : "+v"(band));
             const unsigned long long before = atomicMin(&key_at(kc)[nr.col], key);
-            if ((before >> 10) - (key >> 10) + 1ull <= 2ull) sh.tie[par] = f;     // (an empty column: 2^54 - 1, far from every s)
+            if ((before >> 10) + band <= 2ull) sh.tie[par] = f;     // (an empty column: 2^54 - 1, far from every s)
         }
         // the measurements that leave the filters' windows with this frame (used behind the claims): requested where the
         // window is full, 0.0 elsewhere -- bl_gsff then uses them as they are (a track born in this frame has none: its
@@ -1562,6 +1726,10 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
             if (S.alive) bl_seat_store(S, be, tid);
         }
         if (tid == 0) { *ke->t.n_tracks = n; *ke->t.next_id = next_id; *ke->row_count = sh.rows_then - room; *be.head = head; }
+        {   // (the highest wave that ends the launch with a track, + 1: ysmr_debug_track_waves)
+            const unsigned long long b_live = __ballot(S.alive);
+            if (lane == 0 && b_live) atomicMax(be.head + 3, wave + 1);
+        }
     }
 }
 

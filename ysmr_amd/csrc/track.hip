@@ -2491,13 +2491,19 @@ int ysmr_tracker_link_mode(ysmr_tracker *t, int mode)
 #ifdef YSMR_STAMPS
 int ysmr_debug_read_bstamps(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bstamps), sizeof(unsigned long long) * BL_WAVES * 16); }
 int ysmr_debug_read_bcounts(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bcounts), sizeof(unsigned long long) * BL_WAVES * BL_COUNTS); }
+int ysmr_debug_read_bwaves(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bwaves), sizeof(unsigned long long) * (BL_WAVES + 1)); }
+int ysmr_debug_read_bseats(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bseats), sizeof(unsigned long long) * 2); }
 #endif
 
 int ysmr_tracker_batched(ysmr_tracker *t) { return t && t->use_batch() ? 1 : 0; }
 
 // Test hooks for the ring (tests/test_gpu_batch_bookkeeping.py; not part of the ABI the host code binds).  _poison: every
 // entry of positions 0 .. BL_HB - 1 becomes a NaN bit pattern (all ones) -- refused once the handle has registered a track: whatever a
-// filter bank then sums that its own frames did not store shows in the rows.  _zero_line: the non-zero 64-bit words of
+// filter bank then sums that its own frames did not store shows in the rows.  For handles that STAY in the batch layout:
+// k_to_std copies whole ring columns into the per-frame history, whose FIR (fir_wave_all) multiplies the entries beyond a
+// young track's history by gains of zero -- zeros in a fresh handle, NaN x 0 in a poisoned one; the first update() behind a
+// poisoned batch launch ended in an illegal memory access on the device (how the NaN position becomes an address out of
+// bounds in the per-frame kernels was not traced, and the parent was not run that way).  _zero_line: the non-zero 64-bit words of
 // position BL_HB, the line of zeros (read-only).  Both wait for the device before and after.
 int ysmr_debug_ring_poison(ysmr_tracker *t)
 {
@@ -2510,6 +2516,32 @@ int ysmr_debug_ring_poison(ysmr_tracker *t)
     if (e == hipSuccess) e = hipMemset(t->bd.ring, 0xFF, sizeof(double2) * BL_HB * (size_t)t->bd.seat_cap);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     return e == hipSuccess ? YSMR_OK : ysmr::fail(YSMR_ERR_HIP, "ring poison failed: %s", hipGetErrorString(e));
+}
+// Test hooks for the seats (tests/test_gpu_seat_compaction.py; not part of the ABI either).  The last k_batch launch's
+// frames that gave up track waves and the tracks they moved; the highest wave that held a track when it ended, + 1.  Three
+// words behind the ring's head, which the launch writes.  Both wait for the device first.
+static int seat_words(ysmr_tracker *t, int (&w)[3])
+{
+    if (!t) return ysmr::fail(YSMR_ERR_ARG, "tracker handle is NULL");
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(w, t->bd.head + 1, sizeof(w), hipMemcpyDeviceToHost);
+    return e == hipSuccess ? YSMR_OK : ysmr::fail(YSMR_ERR_HIP, "seat words read failed: %s", hipGetErrorString(e));
+}
+int ysmr_debug_seat_events(ysmr_tracker *t, int *events_out, int *moved_out)
+{
+    int w[3];
+    if (!events_out || !moved_out) return ysmr::fail(YSMR_ERR_ARG, "events_out and moved_out must be set");
+    if (int rc = seat_words(t, w)) return rc;
+    *events_out = w[0]; *moved_out = w[1];
+    return YSMR_OK;
+}
+int ysmr_debug_track_waves(ysmr_tracker *t, int *out)
+{
+    int w[3];
+    if (!out) return ysmr::fail(YSMR_ERR_ARG, "out must be set");
+    if (int rc = seat_words(t, w)) return rc;
+    *out = w[2];
+    return YSMR_OK;
 }
 int ysmr_debug_ring_zero_line(ysmr_tracker *t, long long *nonzero)
 {
