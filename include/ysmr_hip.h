@@ -772,6 +772,42 @@ typedef struct ysmr_violin_view {
 int ysmr_plot_violins(void *stream, int n_violins, const ysmr_violin_summary *summaries_dev, const double *density_dev,
                       const ysmr_violin_view *view, void *workspace_dev, size_t workspace_bytes, uint8_t *rgb_dev);
 
+/* ---- the figures' PNG files: lettering and deflate on the device (csrc/png.hip) ---- */
+
+/* ADDED under ABI 15 as well.  With these a figure leaves the device as a finished zlib stream: the canvas is never
+ * downloaded.  Which text goes where stays the host's decision (plot_functions.py). */
+
+typedef struct ysmr_stamp {
+    int32_t  x, y;               /* canvas position of the bitmap's top-left pixel; may lie outside the canvas */
+    int32_t  w, h;               /* the bitmap's size; a record with w < 1 or h < 1 paints nothing */
+    uint32_t bit_offset;         /* of the bitmap's first bit in `bits`: pixel (col, row) is bit bit_offset + row * w + col,
+                                    bit k being (bits[k / 8] >> (k % 8)) & 1 */
+    uint32_t colour;             /* R | G << 8 | B << 16 */
+} ysmr_stamp;
+
+/* Paints the set bits of every record into rgb_dev: u8 [height][width][3]; pixels outside the canvas are dropped (the
+ * clipping of stamp_text / stamp_text_vertical).  Where records overlap the LATER record wins, whatever the scheduling: a
+ * pixel is stored only by the last record with a set bit on it.  records_dev and bits_dev are device buffers; a record
+ * whose bits do not lie inside bits_bytes paints nothing.  0 <= n_records <= 4096, bits_bytes <= 2^28. */
+int ysmr_plot_stamp(void *stream, uint8_t *rgb_dev, int width, int height, const ysmr_stamp *records_dev, int n_records,
+                    const uint8_t *bits_dev, size_t bits_bytes);
+
+/* The zlib stream of a canvas' PNG scanlines: height rows of S = 1 + 3 width bytes, a filter byte 0 in front of every row.
+ * The stream is 78 01, ONE deflate block (BFINAL = 1, BTYPE = 01: the fixed Huffman code of RFC 1951, 3.2.6), the end-of-block
+ * code, padding to a byte and the Adler-32 of the scanline bytes, big-endian.  Every row is cut into pieces of 1024 bytes (the
+ * last one shorter) and a piece is parsed on its own, greedily: at byte i, with L3 and LS the match lengths at the distances 3
+ * and S (LS = 0 when S > 32768), each capped at 258 and at the piece's end -- (L3, 3) if L3 >= LS and L3 >= 3, else (LS, S) if
+ * LS >= 4, else the literal.  A match's source may lie anywhere before it.  Integers only and no atomics on a sum: two calls
+ * give the same bytes (tests/png_deflate_model.py restates the stream).
+ * ysmr_png_stream_bytes_max: ceil((3 + 9 H S + 7) / 8) + 6 -- no code spends more than 9 bits on a byte -- rounded up to a
+ * word, plus a word for the packer; out_dev must hold that much and is overwritten up to it.  *out_len_dev: the stream's
+ * bytes.  1 <= width, height <= 16384 (the size calls return 0 outside); workspace_dev and out_len_dev 8-byte aligned, out_dev
+ * 4-byte aligned.  The calls only enqueue work on `stream`. */
+size_t ysmr_png_workspace_bytes(int width, int height);
+size_t ysmr_png_stream_bytes_max(int width, int height);
+int ysmr_png_deflate(void *stream, const uint8_t *rgb_dev, int width, int height, void *workspace_dev, size_t workspace_bytes,
+                     uint8_t *out_dev, size_t out_bytes, unsigned long long *out_len_dev);
+
 #ifdef __cplusplus
 }
 #endif

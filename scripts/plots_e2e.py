@@ -1,9 +1,12 @@
 """The three track figures end to end on the selected table of the bench clip (1228 x 922, 500 blobs, 1920 frames):
 per figure the device time (upload of the small arrays, kernels), the canvas download, the lettering + PNG encoding and
 the wall time of the public function; the matplotlib scatter loop of the reference's overview on the same table where
-matplotlib is importable; evaluate_tracks with the three keys on and off.
+matplotlib is importable; evaluate_tracks with the three keys on and off.  ``--png device`` runs the public functions and
+evaluate_tracks with 'hip png on device'; ``--png-ab`` runs only the comparison of the two PNG paths: per figure the wall
+time of the public function on either path, alternating, the file sizes, and zlib level 1 on the same scanlines.
 
-  python3 scripts/plots_e2e.py [--frames 1920] [--tmp DIR] > profiles/plots_e2e.log
+  python3 scripts/plots_e2e.py [--frames 1920] [--tmp DIR] [--png host|device] > profiles/plots_e2e.log
+  python3 scripts/plots_e2e.py --png-ab >> profiles/png_e2e.log
 """
 import argparse
 import os
@@ -86,18 +89,89 @@ def figure_phases(out, stats, settings, work, reps):
                 rep, "angle_histogram", t_hist, points, t_paint, t_down, t_png))
 
 
-def public_functions(out, stats, settings, work, reps):
+def public_functions(out, stats, settings, work, reps, on_device=False):
     from ysmr_amd import plot_functions as pf
     dist = np.ascontiguousarray(stats["Distance (µm)"].to_numpy())
     px = settings["pixel per micrometre"]
     for rep in range(reps):
         _, a = timed(lambda: pf.large_xy_plot(out, "bench clip", os.path.join(work, "overview.png"), px_to_micrometre=px, distances=dist,
-                                              dist_min=float(dist.min()), dist_max=float(dist.max())))
+                                              dist_min=float(dist.min()), dist_max=float(dist.max()), png_on_device=on_device))
         _, b = timed(lambda: pf.rose_graph(out, "bench clip", os.path.join(work, "rose.png"), px_to_micrometre=px, distances=dist,
-                                           dist_min=float(dist.min()), dist_max=float(dist.max())))
+                                           dist_min=float(dist.min()), dist_max=float(dist.max()), png_on_device=on_device))
         _, c = timed(lambda: pf.angle_distribution_plot(out, 36, "bench clip", os.path.join(work, "angle.png"),
-                                                        compare_n_frames=settings["compare angle between n frames"]))
-        print("rep {}: wall time large_xy_plot {:.1f} ms, rose_graph {:.1f} ms, angle_distribution_plot {:.1f} ms".format(rep, a, b, c))
+                                                        compare_n_frames=settings["compare angle between n frames"], png_on_device=on_device))
+        print("rep {} (png on the {}): wall time large_xy_plot {:.1f} ms, rose_graph {:.1f} ms, angle_distribution_plot {:.1f} ms".format(
+            rep, "device" if on_device else "host", a, b, c))
+
+
+def read_scanlines(path):
+    """(IHDR body, the inflated IDAT) of a PNG written by write_png / write_png_device."""
+    import struct
+    import zlib
+    raw = open(path, "rb").read()
+    at, head, idat = 8, None, b""
+    while at < len(raw):
+        (size,) = struct.unpack(">I", raw[at:at + 4])
+        kind, body = raw[at + 4:at + 8], raw[at + 8:at + 8 + size]
+        head = body if kind == b"IHDR" else head
+        idat += body if kind == b"IDAT" else b""
+        at += 12 + size
+    return head, zlib.decompress(idat)
+
+
+def png_ab(figures, work, reps):
+    """``figures``: (name, draw(path, png_on_device)).  Per figure and repetition the wall time of ``draw`` on the host path
+    and on the device path, one after the other; then the two files' sizes, zlib level 1 on the same scanlines (what the
+    host path's IDAT is) and whether the two files hold the same pixels."""
+    import zlib
+    for name, draw in figures:
+        host, device = os.path.join(work, name + "_host.png"), os.path.join(work, name + "_device.png")
+        draw(host, False), draw(device, True)                                          # warm-up of either path
+        for rep in range(reps):
+            _, t_host = timed(lambda: draw(host, False))
+            _, t_dev = timed(lambda: draw(device, True))
+            print("rep {}: {:17s} wall time, png on the host {:7.1f} ms, on the device {:7.1f} ms".format(rep, name, t_host, t_dev), flush=True)
+        (head_h, raw_h), (head_d, raw_d) = read_scanlines(host), read_scanlines(device)
+        t0 = time.perf_counter()
+        level1 = len(zlib.compress(raw_h, 1))
+        t_zlib = (time.perf_counter() - t0) * 1e3
+        print("       {:17s} files: host {} bytes, device {} bytes (ratio {:.3f}); zlib level 1 on the {:.1f} MB of scanlines: {} bytes in {:.1f} ms "
+              "on this host's CPU; same header and pixels: {}".format(name, os.path.getsize(host), os.path.getsize(device),
+                                                                      os.path.getsize(device) / os.path.getsize(host), len(raw_h) / 1e6, level1,
+                                                                      t_zlib, head_h == head_d and raw_h == raw_d), flush=True)
+
+
+def track_figures(out, stats, settings):
+    from ysmr_amd import plot_functions as pf
+    dist = np.ascontiguousarray(stats["Distance (µm)"].to_numpy())
+    px, span = settings["pixel per micrometre"], dict(dist_min=float(dist.min()), dist_max=float(dist.max()))
+    return [("Bac_Run_Overview", lambda path, dev: pf.large_xy_plot(out, "bench clip", path, px_to_micrometre=px, distances=dist,
+                                                                    png_on_device=dev, **span)),
+            ("rose_graph", lambda path, dev: pf.rose_graph(out, "bench clip", path, px_to_micrometre=px, distances=dist, png_on_device=dev,
+                                                           **span)),
+            ("angle_histogram", lambda path, dev: pf.angle_distribution_plot(
+                out, 36, "bench clip", path, compare_n_frames=settings["compare angle between n frames"], png_on_device=dev))]
+
+
+def device_png_phases(out, stats, settings, reps):
+    """The device path's own steps on the overview's canvas: lettering (upload + kernel), deflate (kernels + the two downloads)."""
+    import torch
+    from ysmr_amd import _lib, plot_functions as pf
+    dev = torch.device("cuda:0")
+    px = settings["pixel per micrometre"]
+    dist = np.ascontiguousarray(stats["Distance (µm)"].to_numpy())
+    with _lib.on(dev):
+        ids, x, y = pf._upload(out, dev)
+        view, cols, rows = pf.track_view(pf.device_extent(ids, x, y, 0, px, dev), 0, px)
+        rgb = pf.device_tracks(ids, x, y, dist, view, dev, download=False)
+        stamps = pf.StampList(rgb.shape[0], rgb.shape[1])
+        pf.decorate_track_figure(stamps, view, cols, rows, "bench clip", float(dist.min()), float(dist.max()))
+        for rep in range(reps + 1):
+            _, t_stamp = timed(lambda: pf.device_stamp(rgb, stamps))
+            stream, t_deflate = timed(lambda: pf.device_deflate(rgb))
+            if rep:
+                print("rep {}: overview canvas: ysmr_plot_stamp of {} records {:.2f} ms, ysmr_png_deflate with its downloads {:.2f} ms "
+                      "({} bytes)".format(rep - 1, len(stamps.records), t_stamp, t_deflate, len(stream)), flush=True)
 
 
 def matplotlib_loop(out, stats, settings, work):
@@ -137,13 +211,27 @@ def run(args):
         table, fps = selected_table(args, work, base)
         name = os.path.join(work, "clip_selected_data.csv")
         evaluate_tracks(name, work, df=table, settings=off, fps=fps)                    # warm-up: library, allocator
+        if args.png_ab:
+            on_dev = dict(base, **{"hip png on device": True})
+            res_on = evaluate_tracks(name, work, df=table, settings=on_dev, fps=fps)
+            for rep in range(args.reps):
+                _, t_host = timed(lambda: evaluate_tracks(name, work, df=table, settings=base, fps=fps))
+                _, t_dev = timed(lambda: evaluate_tracks(name, work, df=table, settings=on_dev, fps=fps))
+                _, t_off = timed(lambda: evaluate_tracks(name, work, df=table, settings=off, fps=fps))
+                print("rep {}: evaluate_tracks with the three figures, png on the host {:.1f} ms, on the device {:.1f} ms, without figures "
+                      "{:.1f} ms".format(rep, t_host, t_dev, t_off), flush=True)
+            png_ab(track_figures(*res_on, base), work, args.reps)
+            device_png_phases(*res_on, base, args.reps)
+            return
+        if args.png == "device":
+            base = dict(base, **{"hip png on device": True})
         for rep in range(args.reps):
             (res_on), t_on = timed(lambda: evaluate_tracks(name, work, df=table, settings=base, fps=fps))
             (res_off), t_off = timed(lambda: evaluate_tracks(name, work, df=table, settings=off, fps=fps))
             print("rep {}: evaluate_tracks with the three figures {:.1f} ms, without {:.1f} ms".format(rep, t_on, t_off), flush=True)
         out, stats = res_on
         figure_phases(out, stats, base, work, args.reps)
-        public_functions(out, stats, base, work, args.reps)
+        public_functions(out, stats, base, work, args.reps, on_device=args.png == "device")
         matplotlib_loop(out, stats, base, work)
     finally:
         shutil.rmtree(work, ignore_errors=True)
@@ -157,4 +245,6 @@ if __name__ == "__main__":
     ap.add_argument("--blobs", type=int, default=500)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--tmp", default=None, help="where the clip and the figures go (removed afterwards)")
+    ap.add_argument("--png", choices=("host", "device"), default="host", help="where the PNG files are made ('hip png on device')")
+    ap.add_argument("--png-ab", action="store_true", help="only compare the two PNG paths: times, file sizes, zlib level 1")
     run(ap.parse_args())

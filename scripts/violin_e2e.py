@@ -3,7 +3,8 @@ off (the eight figures must be there), then one figure's phases -- statistics an
 paint with the canvas download, lettering, PNG -- for per-track tables of 500 and 20 000 tracks.  Not compared with
 upstream: seaborn is needed for that.
 
-  python3 scripts/violin_e2e.py [--frames 600] [--tmp DIR] > profiles/violin_e2e.log
+  python3 scripts/violin_e2e.py [--frames 600] [--tmp DIR] [--png host|device] > profiles/violin_e2e.log
+  python3 scripts/violin_e2e.py --png-ab >> profiles/png_e2e.log     (only the two PNG paths, alternating: times and sizes)
 """
 import argparse
 import os
@@ -33,7 +34,7 @@ def statistics_table(n_tracks, seed=0):
     return pd.DataFrame(cols)
 
 
-def figure_phases(n_tracks, work, reps):
+def figure_phases(n_tracks, work, reps, on_device=False):
     import torch
     from plots_e2e import timed
     from ysmr_amd import _lib, plot_functions as pf
@@ -57,10 +58,21 @@ def figure_phases(n_tracks, work, reps):
         t0 = time.perf_counter()
         pf.write_png(path, rgb)
         t_png = (time.perf_counter() - t0) * 1e3
-        _, t_all = timed(lambda: pf.violin_plot(table, path, "Speed (µm/s)", "Categories (Perc. Motile)", cut_list, "bench clip", 0.0, False))
+        _, t_all = timed(lambda: pf.violin_plot(table, path, "Speed (µm/s)", "Categories (Perc. Motile)", cut_list, "bench clip", 0.0, False,
+                                                png_on_device=on_device))
         print("rep {}: {:6d} tracks: statistics and densities (upload, sort, kernels, download) {:6.2f} ms, profile and paint {:5.2f} ms, "
-              "download {:5.2f} ms, lettering {:5.2f} ms, png {:5.1f} ms ({:.2f} MB); violin_plot {:6.1f} ms".format(
-                  rep, n_tracks, t_stats, t_paint, t_down, t_text, t_png, os.path.getsize(path) / 1e6, t_all), flush=True)
+              "download {:5.2f} ms, lettering {:5.2f} ms, png {:5.1f} ms; violin_plot (png on the {}) {:6.1f} ms ({:.2f} MB)".format(
+                  rep, n_tracks, t_stats, t_paint, t_down, t_text, t_png, "device" if on_device else "host", t_all,
+                  os.path.getsize(path) / 1e6), flush=True)
+
+
+def violin_figures(n_tracks):
+    from ysmr_amd import plot_functions as pf
+    from ysmr_amd.evaluate import violin_cut_list
+    table = statistics_table(n_tracks)
+    cut_list = violin_cut_list("Perc. Motile", [0.0, 20.0, 40.0, 60.0, 80.0, 100.01])
+    return [("violin_{}".format(n_tracks), lambda path, dev: pf.violin_plot(table, path, "Speed (µm/s)", "Categories (Perc. Motile)", cut_list,
+                                                                            "bench clip", 0.0, False, png_on_device=dev))]
 
 
 def run(args):
@@ -72,6 +84,13 @@ def run(args):
         base = default_settings(**{"user input": False, "select files": False, "display video analysis": False, "log to file": False,
                                    "save large plots": False, "save rose plot": False, "save angle distribution plot / bins": 0})
         on = dict(base, **{"hip violin plots": True})
+        if args.png_ab:
+            from plots_e2e import png_ab
+            for n_tracks in (500, 20000):
+                png_ab(violin_figures(n_tracks), work, args.reps)
+            return 0
+        if args.png == "device":
+            on["hip png on device"] = True
         table, fps = selected_table(args, work, base)
         name = os.path.join(work, "clip_selected_data.csv")
         evaluate_tracks(name, work, df=table, settings=base, fps=fps)                   # warm-up: library, allocator
@@ -82,7 +101,7 @@ def run(args):
         missing = [f for f in FIGURES if not os.path.exists(os.path.join(work, "clip_selected_data_{}.png".format(f)))]
         print("figures written: {} of {}{}".format(len(FIGURES) - len(missing), len(FIGURES), ", missing: {}".format(missing) if missing else ""))
         for n_tracks in (500, 20000):
-            figure_phases(n_tracks, work, args.reps)
+            figure_phases(n_tracks, work, args.reps, on_device=args.png == "device")
         print("not compared with upstream: seaborn is not installed here")
         return 1 if missing else 0
     finally:
@@ -97,4 +116,6 @@ if __name__ == "__main__":
     ap.add_argument("--blobs", type=int, default=500)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--tmp", default=None, help="where the clip and the figures go (removed afterwards)")
+    ap.add_argument("--png", choices=("host", "device"), default="host", help="where the PNG files are made ('hip png on device')")
+    ap.add_argument("--png-ab", action="store_true", help="only compare the two PNG paths: times, file sizes, zlib level 1")
     sys.exit(run(ap.parse_args()))

@@ -64,7 +64,8 @@ EXPORTS = ("ysmr_abi_version", "ysmr_last_error", "ysmr_detect_workspace_bytes",
            "ysmr_plot_extent", "ysmr_plot_workspace_bytes", "ysmr_plot_tracks", "ysmr_plot_angle_histogram", "ysmr_plot_wedges",
            "ysmr_mjpeg_workspace_bytes", "ysmr_mjpeg_batch", "ysmr_violin_workspace_bytes", "ysmr_violin_stats", "ysmr_plot_violins",
            "ysmr_mjpeg_decode_workspace_bytes", "ysmr_mjpeg_decode_batch",
-           "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_batch_sync", "ysmr_mjpeg_decode_sync_geometry")
+           "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_batch_sync", "ysmr_mjpeg_decode_sync_geometry",
+           "ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_png_deflate", "ysmr_plot_stamp")
 
 #: numpy view of ``ysmr_mark`` (16 bytes): one track position of one frame of the annotated video
 MARK_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("track_id", "<u4"), ("style", "<u4")])
@@ -120,6 +121,10 @@ class ViolinView(ctypes.Structure):
                                               "line_half", "box_half", "dot_r2", "reserved")] + \
                [("grid_rows", ctypes.c_int32 * 32), ("slot_x", ctypes.c_int32 * 64), ("slot_w", ctypes.c_int32 * 64),
                 ("slot_colour", ctypes.c_int32 * 64)]
+
+
+#: numpy view of ``ysmr_stamp`` (24 bytes): one bitmap of a figure's lettering
+STAMP_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"), ("bit_offset", "<u4"), ("colour", "<u4")])
 
 
 class YsmrLibraryError(RuntimeError):
@@ -245,8 +250,14 @@ def lib():
     L.ysmr_violin_workspace_bytes.restype = ctypes.c_size_t
     L.ysmr_violin_stats.argtypes = [vp, ll, vp, ll, vp, ll, ci, vp, vp, vp, ctypes.c_size_t, vp, vp]
     L.ysmr_plot_violins.argtypes = [vp, ci, vp, vp, ctypes.POINTER(ViolinView), vp, ctypes.c_size_t, vp]
+    L.ysmr_png_workspace_bytes.argtypes = [ci, ci]
+    L.ysmr_png_workspace_bytes.restype = ctypes.c_size_t
+    L.ysmr_png_stream_bytes_max.argtypes = [ci, ci]
+    L.ysmr_png_stream_bytes_max.restype = ctypes.c_size_t
+    L.ysmr_png_deflate.argtypes = [vp, vp, ci, ci, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]
+    L.ysmr_plot_stamp.argtypes = [vp, vp, ci, ci, vp, ci, vp, ctypes.c_size_t]
     for name in EXPORTS:
-        if name not in ("ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_sync_geometry", "ysmr_mjpeg_decode_workspace_bytes", "ysmr_violin_workspace_bytes", "ysmr_mjpeg_workspace_bytes", "ysmr_plot_workspace_bytes", "ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
+        if name not in ("ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_sync_geometry", "ysmr_mjpeg_decode_workspace_bytes", "ysmr_violin_workspace_bytes", "ysmr_mjpeg_workspace_bytes", "ysmr_plot_workspace_bytes", "ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
                         "ysmr_rows_sort_workspace_bytes", "ysmr_rows_csv_bound", "ysmr_rows_stream_count",
                         "ysmr_mean_threshold_state_bytes"):
             getattr(L, name).restype = ci

@@ -75,19 +75,20 @@ def _figures(out, stats, settings, title, save_path, device, logger, df_stats=No
     error in the log; the tables and the csv files do not depend on it."""
     from . import plot_functions as pf
     px = settings["pixel per micrometre"]
+    on_device = bool(settings.get("hip png on device"))      # lettering and deflate in csrc/png.hip; absent: the host path
     jobs = []
     if settings.get("save angle distribution plot / bins"):
         jobs.append(("angle_histogram", lambda path: pf.angle_distribution_plot(
             df=out, bins_number=settings["save angle distribution plot / bins"], plot_title_name=title, save_path=path,
-            compare_n_frames=settings["compare angle between n frames"], device=device)))
+            compare_n_frames=settings["compare angle between n frames"], device=device, png_on_device=on_device)))
     distances = np.ascontiguousarray(stats[:, 1])
     span = dict(dist_min=float(distances.min()), dist_max=float(distances.max())) if len(distances) else {}
     if settings.get("save large plots"):
         jobs.append(("Bac_Run_Overview", lambda path: pf.large_xy_plot(
-            df=out, plot_title_name=title, save_path=path, px_to_micrometre=px, distances=distances, device=device, **span)))
+            df=out, plot_title_name=title, save_path=path, px_to_micrometre=px, distances=distances, device=device, png_on_device=on_device, **span)))
     if settings.get("save rose plot"):
         jobs.append(("rose_graph", lambda path: pf.rose_graph(
-            df=out, plot_title_name=title, save_path=path, px_to_micrometre=px, distances=distances, device=device, **span)))
+            df=out, plot_title_name=title, save_path=path, px_to_micrometre=px, distances=distances, device=device, png_on_device=on_device, **span)))
     if settings.get("hip violin plots") and df_stats is not None:
         cut_list = violin_cut_list(parameter, settings["split violin plots on"])
         chosen = [(STATS_COLUMNS[col], name, settings.get(limits + " min"), settings.get(limits + " max"))
@@ -96,7 +97,7 @@ def _figures(out, stats, settings, title, save_path, device, logger, df_stats=No
         for column, name, y_min, y_max in chosen:
             jobs.append((name, lambda path, column=column, y_min=y_min, y_max=y_max: pf.violin_plot(
                 df=df_stats, save_path=path, category=column, cut_off_category="Categories ({})".format(parameter),
-                cut_off_list=cut_list, plot_title_name=title, y_min=y_min, y_max=y_max, device=device)))
+                cut_off_list=cut_list, plot_title_name=title, y_min=y_min, y_max=y_max, device=device, png_on_device=on_device)))
     for name, job in jobs:
         try:
             job(save_path.format(name, ".png"))

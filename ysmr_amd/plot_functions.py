@@ -3,8 +3,9 @@
 Host mirror of the reference's module of this name (ysmr/plot_functions.py:29-257): the same three functions, the same
 file names and figure size.  The reference hands the table to matplotlib, one ``scatter`` call per track; here the
 columns go to HBM once, ``csrc/plots.hip`` paints the canvas, and the host stamps the lettering into the downloaded
-canvas and writes the PNG (NumPy and zlib only).  The image is this project's own rendering of the same data -- which
-pixel a row lands on, which track wins a pixel and what colour it has are fixed by rules ("The figures"),
+canvas and writes the PNG (NumPy and zlib only); with ``png_on_device`` the canvas stays in HBM, ``csrc/png.hip`` stamps
+the lettering and deflates the scanlines, and only the finished zlib stream is downloaded.  The image is this
+project's own rendering of the same data -- which pixel a row lands on, which track wins a pixel and what colour it has are fixed by rules ("The figures"),
 matplotlib's antialiased output is not reproduced; the lettering is a 5 x 7 bitmap font.  ``violin_plot`` is upstream's
 function of that name (plot_functions.py:260-370) without seaborn: the categories, order statistics, moments and the
 Gaussian kernel density estimate come from ``csrc/violin.hip``, which paints the canvas as well; ``evaluate_tracks``
@@ -48,6 +49,43 @@ def write_png(path, rgb, dpi=300):
         fh.write(chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)))
         fh.write(chunk(b"pHYs", struct.pack(">IIB", per_metre, per_metre, 1)))
         fh.write(chunk(b"IDAT", zlib.compress(raw.tobytes(), 1)))
+        fh.write(chunk(b"IEND", b""))
+
+
+def device_deflate(rgb_device):
+    """``ysmr_png_deflate`` of a u8 [H, W, 3] device tensor: the zlib stream of its PNG scanlines as bytes.  One launch
+    chain; the 8-byte length is downloaded, then the stream."""
+    import torch
+    if rgb_device.dtype != torch.uint8 or rgb_device.dim() != 3 or rgb_device.shape[2] != 3 or not rgb_device.is_contiguous():
+        raise ValueError("rgb_device must be a contiguous u8 [H, W, 3] tensor, got {} {}".format(rgb_device.dtype, tuple(rgb_device.shape)))
+    L = _lib.lib()
+    dev = rgb_device.device
+    h, w = int(rgb_device.shape[0]), int(rgb_device.shape[1])
+    with _lib.on(dev):
+        ws = torch.empty(max(L.ysmr_png_workspace_bytes(w, h), 256), dtype=torch.uint8, device=dev)
+        out = torch.empty(max(L.ysmr_png_stream_bytes_max(w, h), 256), dtype=torch.uint8, device=dev)
+        length = torch.empty(1, dtype=torch.int64, device=dev)
+        _lib.check(L.ysmr_png_deflate(_lib.stream_ptr(dev), rgb_device.data_ptr(), w, h, ws.data_ptr(), ws.numel(), out.data_ptr(),
+                                      out.numel(), length.data_ptr()), "ysmr_png_deflate")
+        n = int(length.item())
+        return out[:n].cpu().numpy().tobytes()
+
+
+def write_png_device(path, rgb_device, dpi=300):
+    """``write_png`` for a canvas in HBM (u8 [H, W, 3] device tensor): the same chunks in the same layout, the IDAT body
+    deflated on the device (fixed Huffman code, ``csrc/png.hip``) -- the file decodes to the same pixels, its bytes differ."""
+    idat = device_deflate(rgb_device)
+    h, w = int(rgb_device.shape[0]), int(rgb_device.shape[1])
+
+    def chunk(kind, body):
+        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xFFFFFFFF)
+
+    per_metre = int(round(dpi / 0.0254))
+    with open(path, "wb") as fh:
+        fh.write(b"\x89PNG\r\n\x1a\n")
+        fh.write(chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)))
+        fh.write(chunk(b"pHYs", struct.pack(">IIB", per_metre, per_metre, 1)))
+        fh.write(chunk(b"IDAT", idat))
         fh.write(chunk(b"IEND", b""))
 
 
@@ -98,18 +136,74 @@ def text_size(text, scale=1):
     return max(GLYPH_STEP * len(str(text)) - 1, 0) * max(1, int(scale)), GLYPH_H * max(1, int(scale))
 
 
-def stamp_text(rgb, x, y, text, scale=1, colour=(0, 0, 0), anchor="left"):
-    """Stamp ``text`` into ``rgb`` with the top-left pixel of its box at (x, y) -- or the box centred on / ending at x
-    (anchor 'centre' / 'right').  Pixels outside the canvas are dropped."""
-    bm = text_bitmap(text, scale)
+class StampList:
+    """Stands in for the canvas in ``stamp_text`` / ``stamp_text_vertical`` and the ``decorate_*`` functions: the bitmaps
+    are recorded instead of painted, for ``ysmr_plot_stamp`` to paint them into the canvas in HBM.  ``shape`` is the
+    canvas' [H, W, 3]."""
+
+    def __init__(self, height, width):
+        self.shape = (int(height), int(width), 3)
+        self.records = []          # (x, y, w, h, bit offset, colour)
+        self._bits = []
+        self._n_bits = 0
+
+    def add(self, x, y, bm, colour):
+        th, tw = bm.shape
+        if th < 1 or tw < 1:
+            return
+        r, g, b = (int(c) & 255 for c in colour)
+        self.records.append((int(x), int(y), tw, th, self._n_bits, r | g << 8 | b << 16))
+        packed = np.packbits(np.ascontiguousarray(bm, dtype=bool).reshape(-1), bitorder="little")
+        self._bits.append(packed)
+        self._n_bits += 8 * len(packed)        # every bitmap starts on a byte
+
+    def arrays(self):
+        """(records as ``_lib.STAMP_DTYPE``, packed bits u8)"""
+        rec = np.array(self.records, dtype=np.int64).reshape(-1, 6)
+        out = np.zeros(len(rec), _lib.STAMP_DTYPE)
+        for k, name in enumerate(_lib.STAMP_DTYPE.names):
+            out[name] = rec[:, k]
+        return out, np.concatenate(self._bits) if self._bits else np.zeros(0, np.uint8)
+
+
+def _paint(rgb, x, y, bm, colour):
+    """The set pixels of ``bm``, its top-left pixel at (x, y), in ``colour``; pixels outside the canvas are dropped."""
+    if isinstance(rgb, StampList):
+        rgb.add(x, y, bm, colour)
+        return
     th, tw = bm.shape
-    x = int(x) - (tw // 2 if anchor == "centre" else tw if anchor == "right" else 0)
-    y = int(y)
     H, W = rgb.shape[:2]
     x0, y0, x1, y1 = max(x, 0), max(y, 0), min(x + tw, W), min(y + th, H)
     if x0 >= x1 or y0 >= y1:
         return
     rgb[y0:y1, x0:x1][bm[y0 - y:y1 - y, x0 - x:x1 - x]] = colour
+
+
+def stamp_text(rgb, x, y, text, scale=1, colour=(0, 0, 0), anchor="left"):
+    """Stamp ``text`` into ``rgb`` with the top-left pixel of its box at (x, y) -- or the box centred on / ending at x
+    (anchor 'centre' / 'right').  Pixels outside the canvas are dropped.  ``rgb`` may be a ``StampList``."""
+    bm = text_bitmap(text, scale)
+    tw = bm.shape[1]
+    x = int(x) - (tw // 2 if anchor == "centre" else tw if anchor == "right" else 0)
+    _paint(rgb, x, int(y), bm, colour)
+
+
+def device_stamp(rgb_device, stamps):
+    """``ysmr_plot_stamp``: paints the records of a ``StampList`` into the canvas in HBM.  One upload carries the records
+    and the bits."""
+    import torch
+    rec, bits = stamps.arrays()
+    if not len(rec):
+        return
+    if tuple(rgb_device.shape) != tuple(stamps.shape) or rgb_device.dtype != torch.uint8 or not rgb_device.is_contiguous():
+        raise ValueError("the canvas must be a contiguous u8 {} tensor, got {} {}".format(stamps.shape, rgb_device.dtype,
+                                                                                        tuple(rgb_device.shape)))
+    dev = rgb_device.device
+    head = rec.view(np.uint8).reshape(-1)
+    both = torch.from_numpy(np.concatenate([head, bits])).to(dev)
+    with _lib.on(dev):
+        _lib.check(_lib.lib().ysmr_plot_stamp(_lib.stream_ptr(dev), rgb_device.data_ptr(), stamps.shape[1], stamps.shape[0],
+                                              both.data_ptr(), len(rec), both.data_ptr() + len(head), len(bits)), "ysmr_plot_stamp")
 
 
 # ---- ticks and the view ----------------------------------------------------------------------------------------------
@@ -283,7 +377,20 @@ def track_distances(df):
     return np.add.reduceat(df["travelled_dist"].to_numpy(dtype=np.float64), np.flatnonzero(start)) if len(ids) else np.zeros(0)
 
 
-def _track_figure(df, mode, plot_title_name, save_path, px, dist_min, dist_max, dpi, device, distances):
+def _finish_figure(rgb, decorate, save_path, dpi, png_on_device):
+    """Lettering and file.  ``decorate(canvas)`` stamps into a NumPy canvas -- or, with ``png_on_device`` (``rgb`` is the
+    device tensor then), into a ``StampList`` that the device paints before it deflates the canvas."""
+    if png_on_device:
+        stamps = StampList(rgb.shape[0], rgb.shape[1])
+        decorate(stamps)
+        device_stamp(rgb, stamps)
+        write_png_device(save_path, rgb, dpi)
+    else:
+        decorate(rgb)
+        write_png(save_path, rgb, dpi)
+
+
+def _track_figure(df, mode, plot_title_name, save_path, px, dist_min, dist_max, dpi, device, distances, png_on_device=False):
     import torch
     logger = logging.getLogger("ysmr").getChild(__name__)
     dev = torch.device(device)
@@ -293,24 +400,25 @@ def _track_figure(df, mode, plot_title_name, save_path, px, dist_min, dist_max, 
     with _lib.on(dev):
         ids, x, y = _upload(df, dev)
         view, cols, rows = track_view(device_extent(ids, x, y, mode, px, dev), mode, px, dpi)
-        rgb = device_tracks(ids, x, y, dist, view, dev)
-    decorate_track_figure(rgb, view, cols, rows, plot_title_name, dist_min, dist_max, dpi)
-    write_png(save_path, rgb, dpi)
+        rgb = device_tracks(ids, x, y, dist, view, dev, download=False) if png_on_device else device_tracks(ids, x, y, dist, view, dev)
+    _finish_figure(rgb, lambda canvas: decorate_track_figure(canvas, view, cols, rows, plot_title_name, dist_min, dist_max, dpi),
+                   save_path, dpi, png_on_device)
     logger.debug("Saving figure {}".format(save_path))
 
 
 def large_xy_plot(df, plot_title_name, save_path, px_to_micrometre=1, dist_min=0, dist_max=None, dpi=300, device="cuda:0",
-                  distances=None):
+                  distances=None, png_on_device=False):
     """Every track's path on one plot, black dots where the tracks start (plot_functions.py:109-188).  ``distances``:
-    the tracks' 'Distance (µm)' in table order (default: the sums of the table's 'travelled_dist')."""
-    _track_figure(df, 0, plot_title_name, save_path, px_to_micrometre, dist_min, dist_max, dpi, device, distances)
+    the tracks' 'Distance (µm)' in table order (default: the sums of the table's 'travelled_dist').  ``png_on_device``:
+    lettering and deflate on the device, the canvas is not downloaded."""
+    _track_figure(df, 0, plot_title_name, save_path, px_to_micrometre, dist_min, dist_max, dpi, device, distances, png_on_device)
 
 
 def rose_graph(df, plot_title_name, save_path, dist_min=0, dist_max=None, dpi=300, device="cuda:0", distances=None,
-               px_to_micrometre=1):
+               px_to_micrometre=1, png_on_device=False):
     """Every track's path from a common origin (plot_functions.py:191-257).  Upstream reads its 'x_norm' / 'y_norm'
     columns; here they are formed from POSITION_X / POSITION_Y and ``px_to_micrometre`` on the device."""
-    _track_figure(df, 1, plot_title_name, save_path, px_to_micrometre, dist_min, dist_max, dpi, device, distances)
+    _track_figure(df, 1, plot_title_name, save_path, px_to_micrometre, dist_min, dist_max, dpi, device, distances, png_on_device)
 
 
 def wedge_plan(counts, W, H):
@@ -334,7 +442,20 @@ def wedge_boundaries(edges):
     return np.ascontiguousarray(dirs), np.repeat(np.arange(n_bins), parts)
 
 
-def angle_distribution_plot(df, bins_number, plot_title_name, save_path, dpi=300, compare_n_frames=10, device="cuda:0"):
+def decorate_angle_figure(rgb, W, H, cx, cy, ring_r2, title, n_points, top, dpi=300):
+    """Title with the number of points, the four compass labels and the longest bar's count at the ring."""
+    s = max(1, int(round(dpi / 100.0)))
+    ring = math.isqrt(ring_r2)
+    stamp_text(rgb, W // 2, int(round(0.05 * H)), "{} Data points: {}".format(title, n_points), s + 1, anchor="centre")
+    stamp_text(rgb, cx, cy - ring - (GLYPH_H + 2) * s, "0", s, anchor="centre")
+    stamp_text(rgb, cx + ring + 2 * s, cy - GLYPH_H * s // 2, "90", s)
+    stamp_text(rgb, cx, cy + ring + 2 * s, "180", s, anchor="centre")
+    stamp_text(rgb, cx - ring - 2 * s, cy - GLYPH_H * s // 2, "270", s, anchor="right")
+    stamp_text(rgb, cx + int(0.71 * ring) + 2 * s, cy - int(0.71 * ring) - (GLYPH_H + 2) * s, str(int(top)), s)
+
+
+def angle_distribution_plot(df, bins_number, plot_title_name, save_path, dpi=300, compare_n_frames=10, device="cuda:0",
+                            png_on_device=False):
     """Polar histogram of the headings of the moving rows of tracks that move more than 70 % of the time
     (plot_functions.py:29-90).  The table evaluate_tracks returns holds the folded change of heading in degrees, not the
     heading, so the heading is formed again from POSITION_X / POSITION_Y with the lag ``compare_n_frames``."""
@@ -352,16 +473,9 @@ def angle_distribution_plot(df, bins_number, plot_title_name, save_path, dpi=300
             return
         dirs, bin_of = wedge_boundaries(edges)
         cx, cy, ring_r2, r2 = wedge_plan(counts[bin_of], W, H)
-        rgb = device_wedges(W, H, cx, cy, dirs, r2, ring_r2, dev)
-    s = max(1, int(round(dpi / 100.0)))
-    ring = math.isqrt(ring_r2)
-    stamp_text(rgb, W // 2, int(round(0.05 * H)), "{} Data points: {}".format(plot_title_name, n_points), s + 1, anchor="centre")
-    stamp_text(rgb, cx, cy - ring - (GLYPH_H + 2) * s, "0", s, anchor="centre")
-    stamp_text(rgb, cx + ring + 2 * s, cy - GLYPH_H * s // 2, "90", s)
-    stamp_text(rgb, cx, cy + ring + 2 * s, "180", s, anchor="centre")
-    stamp_text(rgb, cx - ring - 2 * s, cy - GLYPH_H * s // 2, "270", s, anchor="right")
-    stamp_text(rgb, cx + int(0.71 * ring) + 2 * s, cy - int(0.71 * ring) - (GLYPH_H + 2) * s, str(int(counts.max())), s)
-    write_png(save_path, rgb, dpi)
+        rgb = device_wedges(W, H, cx, cy, dirs, r2, ring_r2, dev, download=False) if png_on_device else device_wedges(W, H, cx, cy, dirs, r2, ring_r2, dev)
+    _finish_figure(rgb, lambda canvas: decorate_angle_figure(canvas, W, H, cx, cy, ring_r2, plot_title_name, n_points, counts.max(), dpi),
+                   save_path, dpi, png_on_device)
     logger.debug("Saving figure {}".format(save_path))
 
 
@@ -483,13 +597,7 @@ def _fitting_scale(texts, room, largest):
 def stamp_text_vertical(rgb, x, y, text, scale=1, colour=(0, 0, 0)):
     """``text`` reading upwards, its box centred on row ``y`` with its left edge at column ``x``; clipped like stamp_text."""
     bm = np.rot90(text_bitmap(text, scale))
-    th, tw = bm.shape
-    x, y = int(x), int(y) - th // 2
-    H, W = rgb.shape[:2]
-    x0, y0, x1, y1 = max(x, 0), max(y, 0), min(x + tw, W), min(y + th, H)
-    if x0 >= x1 or y0 >= y1:
-        return
-    rgb[y0:y1, x0:x1][bm[y0 - y:y1 - y, x0 - x:x1 - x]] = colour
+    _paint(rgb, int(x), int(y) - bm.shape[0] // 2, bm, colour)
 
 
 def decorate_violin_figure(rgb, view, rows, title, column, labels, boxes, dpi=300):
@@ -525,7 +633,7 @@ def _cut_column(df, cut_off_category):
 
 
 def violin_plot(df, save_path, category, cut_off_category, cut_off_list, plot_title_name="\n\n", y_min=None, y_max=None, dpi=300,
-                device="cuda:0"):
+                device="cuda:0", png_on_device=False):
     """One violin per entry of ``cut_off_list`` -- (low, high, name) triples, 'All' in front -- of the column
     ``category`` of the per-track table ``df`` (plot_functions.py:260-370).  Upstream receives the table with a label
     column made on the host; here ``cut_off_category`` ('Categories (<column>)') names the column the intervals cut,
@@ -540,7 +648,8 @@ def violin_plot(df, save_path, category, cut_off_category, cut_off_list, plot_ti
     with _lib.on(dev):
         sums, dens = device_violin_stats(cut, value, lo, hi, dev)
         view, rows = violin_view(sums, y_min, y_max, dpi)
-        rgb = device_violins(sums, dens, view, dev)
-    decorate_violin_figure(rgb, view, rows, str(plot_title_name).strip(), category, labels, violin_text_boxes(sums, labels), dpi)
-    write_png(save_path, rgb, dpi)
+        rgb = device_violins(sums, dens, view, dev, download=False) if png_on_device else device_violins(sums, dens, view, dev)
+    boxes = violin_text_boxes(sums, labels)
+    _finish_figure(rgb, lambda canvas: decorate_violin_figure(canvas, view, rows, str(plot_title_name).strip(), category, labels, boxes, dpi),
+                   save_path, dpi, png_on_device)
     logger.debug("Saving figure {}".format(save_path))
