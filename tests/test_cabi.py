@@ -88,42 +88,47 @@ def test_threshold_params_match_oracle(oracle):
         assert (p.inv, p.t_low, p.t_high, p.use_high) == oracle.threshold_params(*args)
 
 
-def _model_unused_order(m, used):
-    """Python model of the device code's CPython-set emulation (csrc/track.hip)."""
-    unused = [c for c in range(m) if c not in used]
-    if (m >> 2) > len(used):
-        return unused
-    def insert(table, mask, key):
-        perturb, i = key, key & mask
-        while True:
-            probes = 9 if i + 9 <= mask else 0
-            for j in range(probes + 1):
-                if table[i + j] < 0:
-                    table[i + j] = key
-                    return
-            perturb >>= 5
-            i = (i * 5 + 1 + perturb) & mask
-    table, mask, fill = [-1] * 8, 7, 0
-    for c in unused:
-        insert(table, mask, c)
-        fill += 1
-        if fill * 5 >= mask * 3:
-            minused = fill * 2 if fill > 50000 else fill * 4
-            size = 8
-            while size <= minused:
-                size <<= 1
-            new = [-1] * size
-            for k in table:
-                if k >= 0:
-                    insert(new, size - 1, k)
-            table, mask = new, size - 1
-    return [k for k in table if k >= 0]
+def _set_order_program(tmp_path, cases):
+    """The serial set model of the device code (csrc/set_order.h, what cpython_unused_order runs), compiled for the host as
+    tests/set_order_check.cc and run on `cases` = [(m, used columns, table_cap)]: per case the model's return value and order."""
+    import shutil
+    import subprocess
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not found")
+    exe = str(tmp_path / "set_order_check")
+    built = subprocess.run([hipcc, "-x", "c++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-Xarch_host", "-fsanitize=address,undefined",
+                            "-Xarch_host", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "ysmr_amd", "csrc"),
+                            os.path.join(ROOT, "tests", "set_order_check.cc"), "-o", exe], capture_output=True, text=True)
+    assert built.returncode == 0, built.stdout + built.stderr
+    text = "".join(f"{m} {cap} {len(used)} {' '.join(map(str, sorted(used)))}\n" for m, used, cap in cases)
+    done = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=300)
+    assert done.returncode == 0 and not done.stderr.strip(), done.stderr
+    rows = [[int(v) for v in line.split()] for line in done.stdout.splitlines()]
+    assert len(rows) == len(cases)
+    return [(r[0], r[1:]) for r in rows]
 
 
-def test_cpython_set_model_matches_this_interpreter():
+def test_cpython_set_model_matches_this_interpreter(tmp_path):
     rng = np.random.default_rng(0)
+    cases = []
     for _ in range(3000):
         m = int(rng.integers(1, 700))
         k = int(rng.integers(0, m + 1))
-        used = set(int(v) for v in rng.choice(m, size=k, replace=False))
-        assert _model_unused_order(m, used) == list(set(range(0, m)).difference(used)), (m, sorted(used))
+        cases.append((m, set(int(v) for v in rng.choice(m, size=k, replace=False)), 4096))
+    # the unclaimed columns of tests/test_gpu_link.py::test_set_order_when_the_unclaimed_columns_collide, and whole residue
+    # classes of the small tables: multiples of 8, 64 and 512
+    total = 900
+    patterns = [np.arange(0, total, 128), np.arange(0, total, 32), np.arange(7, total, 8)[:90], np.arange(100, 190),
+                np.r_[np.arange(0, total, 64), np.arange(300, 345), np.arange(513, 530)],
+                np.r_[np.arange(3, total, 16), np.arange(640, 700)], np.arange(total - 70, total),
+                np.arange(0, total, 8), np.arange(0, total, 64), np.arange(0, total, 512)]
+    for cols in patterns:
+        cases.append((total, set(range(total)) - set(int(c) for c in cols), 4096))
+    got = _set_order_program(tmp_path, cases)
+    for (m, used, _), (n, order) in zip(cases, got):
+        expect = list(set(range(0, m)).difference(used))
+        assert n == len(expect) and order == expect, (m, sorted(used))
+    # a table beyond its capacity: 200 unclaimed columns of 400 grow the table to 512 entries
+    (n, order), (n_fits, _) = _set_order_program(tmp_path, [(400, set(range(200, 400)), 256), (400, set(range(200, 400)), 512)])
+    assert (n, order) == (-1, []) and n_fits == 200

@@ -132,3 +132,13 @@ def test_split_clip_holds_what_its_gpu_test_is_about(G):
     e = float(M.grow(g))
     ux = (probes[:, 0] - float(g.x0)) / float(g.cell) % 1.0 - 0.5
     assert (np.abs(ux) * float(g.cell) <= e).sum() >= 4 and (ux == 0).sum() >= 1
+
+
+def test_block_layout_is_the_librarys(tmp_path):
+    """grid_n, list_off, ovf_off and grid_dwords here against csrc/tracker_plan.h's bl_grid_n, bl_list_off, bl_ovf_off and
+    bl_grid_dwords, for every detection count k_bgrid serves (tests/tracker_plan_check.cc prints them; no GPU needed)."""
+    from test_tracker_plan_sanitized import run_plan_check
+    rows = [tuple(int(v) for v in line.split()[1:]) for line in run_plan_check(tmp_path) if line.startswith("grid ")]
+    assert [r[0] for r in rows] == list(range(2561))
+    for m, n, list_off, ovf_off, dwords in rows:
+        assert (M.grid_n(m), M.list_off(m), M.ovf_off(m), M.grid_dwords(m)) == (n, list_off, ovf_off, dwords), m

@@ -428,3 +428,20 @@ def test_split_link_cuts_a_call_longer_than_the_grid_block(torch_cuda, oracle, n
     got = rows_to_numpy(rows, int(count.item()))
     assert trk.info()[2] == 0
     compare_rows(got, ref)
+
+
+def test_every_shape_of_the_plan_table_links_as_recorded(torch_cuda):
+    """tests/tracker_plan_cases.py, the shapes of capacity <= 8192: a handle per case, made with the case's dimensions and
+    link mode, answers ``fused`` and ``batched`` as the library did before the link path had one place (no frame is run)."""
+    import tracker_plan_cases as tc
+    from ysmr_amd._lib import YsmrLibraryError
+    for name, changes, path, caps, fused, batched, sizes in tc.CASES:
+        if tc.arguments(changes)["capacity"] > 8192:
+            continue
+        if path.startswith("error:"):
+            with pytest.raises(YsmrLibraryError):
+                tc.device_tracker(changes)
+            continue
+        trk = tc.device_tracker(changes)
+        assert (trk.fused, trk.batched) == (fused, batched), name
+        trk.close()

@@ -49,67 +49,19 @@
 // k_link + k_track (ysmr_tracker_update, tables beyond this kernel's 768 seats).
 #pragma once
 
-// (BL_* constants and struct BatchDev: track.hip, next to TrackerDev -- the host handle holds one)
+// (BL_* constants, struct BatchDev, BlShared, and the layout and size of a frame's block and of the LDS: tracker_plan.h)
+#include "tracker_plan.h"
 
-// ---- a frame's detections as this kernel wants them: one block of dwords per frame ------------------------------
-//   [0, 16)            header: x0, y0, cell, 1 / cell (f32), cells per side G, m, candidates per cell (0: no lists) (i32)
-//   [16, 16 + SW)      start[G * G + 1] as u16: first item of each cell (row-major), the last entry = m
-//   [.., + 2 * MP)     centres (x, y) f32 of the detections in cell order;  MP = m + 1 rounded up to 8 (entry m and the
-//                      rest: 1e30, far from everything -- the sentinel the candidate lists are padded with)
-//   [.., + MP / 2)     their column numbers as u16
-//   [.., + 4 G G)      G <= 32 only: per cell BL_LIST u16 positions in the cell-ordered centres -- every detection that can
-//                      be nearest to, or within the float tie band of the nearest to, a point of the cell (k_bgrid, below),
-//                      ascending, padded with m; 0xFFFF first: more than BL_LIST, the cell's lanes search the 3 x 3 block;
-//                      BL_SPLIT first: the cell's four quadrants have lists of their own, in overflow entry <second u16>
-//                      (of a slot that starts with 0xFFFF or BL_SPLIT the rest is unspecified: what the first pass left)
-//   [.., + 16 BL_OVF)  G <= 32 only, the overflow area: BL_OVF entries of 4 x BL_LIST u16 -- the lists of the quadrants
-//                      (x half + 2 * y half) of a cell whose own list came out too long, built like a cell's list on the
-//                      quadrant's rectangle.  Entries go to the crowded cells in cell order; a cell beyond the BL_OVF-th,
-//                      or one with a quadrant that still overflows, keeps 0xFFFF.  Unused entries are zero.
-// (cells per side so that a cell holds ~0.45 detections: the three cells of a row of the 3 x 3 block around a prediction
-// then hold more than five candidates once in 200 rows, and the block reaches one cell -- ~1.7 mean nearest-neighbour
-// distances -- beyond the prediction's own cell)
-constexpr int BL_LIST = 8;        // candidates per cell: one ds_read_b128 per lane
-constexpr int BL_OVF = 8;         // overflow entries per frame (512 bytes; DESIGN.md section 4, round 16, has the distribution:
-                                  // the bench clip's frames hold 0 .. 5 crowded cells, and a frame of ~530 detections still
-                                  // takes 24 LDS-DMA pieces with them)
 constexpr unsigned BL_FLAG = 0xFFFFu, BL_SPLIT = 0xFFFEu;      // first u16 of a cell's slot (positions are <= 600)
-__host__ __device__ inline int bl_grid_n(int m) { return m <= 128 ? 16 : (m <= 600 ? 32 : (m <= 1300 ? 48 : 64)); }
-// (the lists of 48 x 48 cells would take 36 KB per block: two of them beside the tables of max_det = 2048 do not fit a
-// compute unit's 160 KB; those frames keep the 3 x 3 search)
-__host__ __device__ inline bool bl_has_lists(int m) { return bl_grid_n(m) <= 32; }
-__host__ __device__ inline int bl_start_dwords(int G) { return ((G * G + 2) / 2 + 3) / 4 * 4; }
-__host__ __device__ inline int bl_pad8(int m) { return (m + 7) / 8 * 8; }
-__host__ __device__ inline int bl_mp(int m) { return bl_pad8(m + 1); }
-__host__ __device__ inline int bl_list_off(int m)      // dword offset of the lists in the block (a multiple of 4)
-{
-    return 16 + bl_start_dwords(bl_grid_n(m)) + 2 * bl_mp(m) + bl_mp(m) / 2;
-}
-__host__ __device__ inline int bl_ovf_off(int m)       // dword offset of the overflow area (frames with lists)
-{
-    return bl_list_off(m) + bl_grid_n(m) * bl_grid_n(m) * BL_LIST / 2;
-}
-__host__ __device__ inline int bl_grid_dwords(int m)   // rounded up to whole 1-KiB pieces (one LDS-DMA wave-instruction)
-{
-    const int raw = bl_has_lists(m) ? bl_ovf_off(m) + BL_OVF * 4 * BL_LIST / 2 : bl_list_off(m);
-    return (raw + 255) / 256 * 256;
-}
-__host__ __device__ inline int bl_grid_dwords_max(int max_det)
-{
-    int most = bl_grid_dwords(max_det);
-    const int steps[4] = {128, 600, 1300, max_det};      // (the size is monotone in m between two changes of the grid)
-    for (int k = 0; k < 4; ++k)
-        if (steps[k] <= max_det && bl_grid_dwords(steps[k]) > most) most = bl_grid_dwords(steps[k]);
-    return most;
-}
 
 // One workgroup per frame: bounding box of the centres, G x G cells over it with one cell of margin, counting sort.  The
 // detections are read ONCE (up to BG_PER per thread, kept in registers through the three passes), the block is assembled
 // in LDS and leaves with 16-byte stores: one round of loads and one of stores instead of the five dependent round trips of
 // the first version (35 us per batch beside the next batch's detection kernels).
-constexpr int BG_THREADS = 256, BG_PER = 10;      // 2560 >= the 2456 detections a one-launch link serves
+constexpr int BG_THREADS = 256, BG_PER = 10;      // 2560 >= FUSED_MAX_DET, the detections a one-launch link serves
 constexpr int BG_CAND = 32;                       // candidates of a cell before the pruning (more: the cell is flagged)
 static_assert(BG_THREADS == 4 * 64 && BL_OVF <= 64, "k_bgrid's second pass: quadrant w of overflow entry `lane` on wave w");
+static_assert(BG_THREADS * BG_PER >= FUSED_MAX_DET, "k_bgrid keeps a frame's detections in registers, BG_PER per thread");
 
 // The candidate list of cell c (G <= 32).  R = the cell's rectangle grown by e on every side: a prediction that bl_search
 // places in cell c lies in R (below).  Every point p of R has a detection within U = min over d of maxdist(d, R) -- found by
@@ -995,29 +947,6 @@ __device__ unsigned long long g_bwaves[BL_WAVES + 1];      // the launch's frame
 #else
 #define BLSTAMP(k) do {} while (0)
 #endif
-struct BlShared {      // static part of the LDS
-    int cnt[BL_MAX_BATCH];           // detections per frame (clamped)
-    int used[2];                     // per frame parity: claims made
-    int n_dead[2];                   // per frame parity: tracks deregistered, as a RUNNING count over the launch (k_batch)
-    int tie[2];                      // per frame parity: the last frame in which some column's proposals were too close
-                                     // for the short key (a frame NUMBER: never reset)
-    int dead_id[2][BL_THREADS];      // ids of the tracks deregistered in the frame
-    int wave_cnt[2][BL_WAVES];       // registration: per-wave counts of the two ranked lists
-    int set_state[2];
-    int top;                         // one past the highest seat ever taken
-    long long rows_then;             // k_batch: the row count at the start of the launch plus the room it found (thread 0's,
-                                     // for the end of the launch; in the padding of the 16-byte rounding: bl_lds_total is what it was)
-};
-
-__host__ __device__ inline int bl_md_padded(int max_det) { return (max_det + 3) / 4 * 4; }
-// dynamic part: three key tables (u64 per column), one table of winning ids (u32), two grid blocks, the set model's table
-__host__ __device__ inline size_t bl_lds_bytes(int max_det)
-{
-    return 2 * 4 * (size_t)bl_grid_dwords_max(max_det) + (3 * 8 + 4) * (size_t)bl_md_padded(max_det) + 4 * BL_TABLE + 64;
-}
-// all of it: what one workgroup of k_batch takes of a compute unit's 160 KiB (the static part is BlShared and nothing else)
-__host__ __device__ inline size_t bl_lds_total(int max_det) { return bl_lds_bytes(max_det) + (sizeof(BlShared) + 15) / 16 * 16; }
-constexpr size_t BL_LDS_LIMIT = 160 * 1024;
 
 // The kernel's arguments as ONE structure: the kernel argument segment then IS this structure, and an argument that one
 // phase of a frame needs (the row buffer, the detections' boxes, the error word, the state arrays at the end) is read
@@ -2063,18 +1992,6 @@ __global__ void k_peek_third_batch(TrackerDev t, BatchDev bd, const double *seat
 // max_det = 2048; an f64 plane in both buffers would add 33 KB, the f32 plane adds 16 (157 KB with the static part, of 160).
 // A lane's float-stage winner costs one 8-byte load from the tail before its claim key is built; the exact wave search
 // reads the tail coalesced, in cell order like the centres.
-__host__ __device__ inline int bl3_lds_dwords(int m) { return (bl_list_off(m) + bl_mp(m) + 255) / 256 * 256; }
-// (without candidate lists the size only grows with m -- bl_grid_n and bl_mp do -- so the largest block is max_det's)
-__host__ __device__ inline int bl3_lds_dwords_max(int max_det) { return bl3_lds_dwords(max_det); }
-__host__ __device__ inline size_t bl3_grid_stride(int max_det)      // bytes per frame: the LDS part and the f64 tail, whole KiB
-{
-    return 4 * (size_t)bl3_lds_dwords_max(max_det) + (8 * (size_t)bl_mp(max_det) + 1023) / 1024 * 1024;
-}
-__host__ __device__ inline size_t bl3_lds_bytes(int max_det)
-{
-    return 2 * 4 * (size_t)bl3_lds_dwords_max(max_det) + (3 * 8 + 4) * (size_t)bl_md_padded(max_det) + 4 * BL_TABLE + 64;
-}
-__host__ __device__ inline size_t bl3_lds_total(int max_det) { return bl3_lds_bytes(max_det) + (sizeof(BlShared) + 15) / 16 * 16; }
 
 // One workgroup per frame, as k_bgrid: the same cells and the same counting sort (a frame's centres come out in the same
 // order), without the candidate lists.  The bounding box, the cells' size, the cell of a detection, the scan of the counts

@@ -16,6 +16,7 @@
 // Compiled with -ffp-contract=off: every fused multiply-add below is an explicit fmaf().
 #include "common.h"
 #include "thr_mfma.h"
+#include "tracker_plan.h"      // FUSED_MAX_DET
 #include <hip/hip_ext.h>
 #include <atomic>
 #include <cfloat>
@@ -2643,9 +2644,9 @@ int ysmr_components_batch(void *stream, int batch, int height, int width, void *
     uint32_t *labels = reinterpret_cast<uint32_t *>(labels_dev);
 
     const Knobs &kn = knobs();
-    // (the LDS reserve matters to k_frame, the one-launch link, which tables of more than 2456 detections do not use
+    // (the LDS reserve matters to k_frame, the one-launch link, which tables of more than FUSED_MAX_DET detections do not use
     // and which the caller announces with YSMR_BESIDE_LINK)
-    const bool small_tables = max_det <= 2456 && (cv_flavour & YSMR_BESIDE_LINK);
+    const bool small_tables = max_det <= FUSED_MAX_DET && (cv_flavour & YSMR_BESIDE_LINK);
     // k_windows' grid.  Beside the per-frame link kernels (one-launch or split) it stays a RESIDENT grid that leaves them their LDS
     // and wave slots.  Beside the batch link -- one workgroup that has long been seated -- or with no link at all, a wave per work item
     // and the dispatcher hands the workgroups out as units become free: the work items differ (a core with twenty islands, a core

@@ -6,11 +6,8 @@
 // `in_range`).  No tables, no division: a digit is at most nine subtractions.
 #pragma once
 #include <stdint.h>
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define YSMR_FMT_HD __host__ __device__ __forceinline__
-#else
-#define YSMR_FMT_HD inline
-#endif
+#include "hd.h"
+#define YSMR_FMT_HD YSMR_HD_FORCE
 
 namespace ysmr_fmt {
 

@@ -8,9 +8,15 @@
 // correct + predict, the frame's output row, and the nearest detection of the NEXT frame -- the fused
 // row-min / arg-min of the N x M float64 distance matrix, which is never stored (tracker.py:151-163
 // only ever reads D.min(1), D.argmin(1)).  k_rowmin does that last step stand-alone for the first
-// frame of a batch.  Configurations beyond the LDS budget of k_frame (max_det > 2456, very large
-// capacity) run the same device functions as two launches: k_link (one workgroup) + k_track (one
-// wave per track).
+// frame of a batch.  Configurations beyond the LDS budget of k_frame (max_det > FUSED_MAX_DET, very
+// large capacity) run the same device functions as two launches: k_link (one workgroup) + k_track
+// (one wave per track).
+//
+// Which of the five link paths a handle takes -- k_frame | k_link + k_track | k_link + k_track_lanes |
+// k_batch | k_batch3 (batch_link.h) -- is decided in tracker_plan.h, host-only and tested without a
+// device: qualifies() says what a configuration can run, link_of(caps, dims, link_mode) which one
+// links.  Here the device may only clear a capability (a refused LDS size); every reader asks
+// ysmr_tracker::link() / frame_link().  The state block's carving and every size are there too.
 //
 // Claim rule (tracker.py:158-189): proposals are visited in ascending (row minimum, row); a
 // proposal is accepted iff its column is still free.  Each row occurs once, so the winner of a
@@ -19,98 +25,14 @@
 //
 // All arithmetic is float64 like the reference; -ffp-contract=off keeps mul/add unfused.
 #include "common.h"
+#include "set_order.h"
+#include "tracker_plan.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
-#define YSMR_MAX_FILTERS 8
-
-struct TrackerDev {
-    // what the link kernels' first round of loads is addressed with, together at the head of the structure: one scalar
-    // load of the kernel's arguments fetches them all
-    int *n_tracks, *next_id, *err, *n_free;
-    int *order, *gone;
-    int *row_arg;                 // [cap]
-    double *row_min;              // [cap]
-    long long *row_base;          // first output row of the current frame (k_link -> k_gsff)
-    int capacity, max_det, n_f, use_gsff, hist_cap, table_cap, gain_total, gone_by_row;
-    int gains_decoupled;             // x-hat reads only x columns, y-hat only y columns (every closed-form gain)
-    double max_gone, lik_min;
-    int n_i[YSMR_MAX_FILTERS];
-    int gain_off[YSMR_MAX_FILTERS];  // filter i: row0 at gains[gain_off[i]], row1 at +2*n_i[i]
-    const double *gains;
-    // persistent state
-    int *free_slots;
-    int *id;
-    double *pos;      // [2][cap]
-    float *info;      // [3][cap]
-    double *hist;     // [cap][hist_cap][2]  (one contiguous ring per track slot)
-    // the filter bank's scalars of a slot as ONE record of rec_stride doubles: [0] history length | head << 32,
-    // [1] mode, [2 + f] weight, [2 + n_f + f] / [2 + 2 n_f + f] x-hat of filter f (the likelihoods are recomputed in
-    // every step and not kept).  A wave fetches and stores it with one instruction, lane = field: 15 VGPRs fewer than
-    // separately addressed scalars in k_frame and 10 in k_track (more of its 5000 waves resident at 4K: +2.5 %)
-    double *rec;      // [cap][rec_stride]
-    int rec_stride;
-    // per-frame scratch
-    int *unused;                  // [max_det] unclaimed detection columns, ascending
-    int *row_gone;                // [cap] split path: `gone` of the track in a row, written with the row minimum (k_link then
-                                  // has everything a row's claim and ageing need from ONE round of loads by row)
-    int *dead;                    // [cap]
-    int *new_cols;                // [max_det]
-    int *set_table;               // [2][table_cap] CPython set model
-    // split path (tables too large for LDS): k_link's per-column winners and per-row claims
-    unsigned long long *link_key; // [max_det]
-    int *link_row;                // [max_det]
-    int *link_claim;              // [capacity]
-    // split path: the detection column the track in a slot claimed in the current frame (-1: none).  k_link only decides;
-    // the winner's detection is fetched, and position / box are stored, by the track's own wave in k_track (5000 waves
-    // instead of one workgroup's two rounds of dependent gathers: 5 us of k_link's 12.6 at 4K)
-    int *claim_slot;              // [capacity]
-    // ... and by ROW of the table k_track sees (after compaction and registration), valid when n_tracks[4] != 0 (k_link's
-    // register-resident path, the 4K configuration): the wave then knows its detection one round of loads earlier -- with
-    // its slot instead of after it
-    int *claim_row;               // [capacity]
-};
-
-// ---- the batch link (batch_link.h): one workgroup links a whole batch of frames per launch, a track per lane
-#ifndef YSMR_BL_THREADS
-#define YSMR_BL_THREADS 768
-#endif
-constexpr int BL_THREADS = YSMR_BL_THREADS;      // seats: one track per lane
-constexpr int BL_WAVES = BL_THREADS / 64;
-constexpr int BL_HB = 32;             // ring of measurements per seat (hist_cap <= 32; a power of two)
-constexpr int BL_NF = 3;              // filters (n_f <= 3)
-#ifndef YSMR_BL_MAX_BATCH
-#define YSMR_BL_MAX_BATCH 256
-#endif
-constexpr int BL_MAX_BATCH = YSMR_BL_MAX_BATCH;      // frames per launch (the grid block is sized for it; longer batches are cut).
-                                                    // 256 since the end of round 4: a launch's fixed costs (state in and out, the gap to the next
-                                                    // launch) and the detection kernels' per-item costs are paid per BATCH (bench.py: 161.5 k frames/s
-                                                    // at 64 frames per batch, 163.5 k at 128, 165 k at 256)
-constexpr int BL_TABLE = 4096;        // CPython set model table, 32-bit slots (as FRAME_TABLE)
-constexpr int BL_SF64 = 3 * BL_NF + 2 + 4 * BL_NF;   // w, xa, xb, px, py, the window sums
-constexpr int BL_REFRESH = 64;        // frames between two exact recomputations of the window sums (a power of two)
-
-struct BatchDev {
-    double2 *ring;      // [BL_HB + 1][seat_cap]  the measurements of the last BL_HB frames, seat by seat; position BL_HB is
-                        // a line of zeros, cleared when the handle is made and never stored to (k_batch: what leaves a window
-                        // that is not full)
-    double *f64;        // [BL_SF64][seat_cap]
-    float *f32;         // [3][seat_cap]      box of the last claimed detection (0 while lost)
-    int *i32;           // [6][seat_cap]      id, gone, history length, mode, table row, seat taken
-    int *head;          // ring position of the next frame's measurements
-    char *grid;         // [BL_MAX_BATCH][grid_stride] bytes, written by k_bgrid
-    unsigned grid_stride;   // bytes per frame (a multiple of 1024)
-    int seat_cap;
-};
-
-struct BlGains { double alpha[BL_NF][2], beta[BL_NF][2]; };    // [filter][x / y row]; batch_link.h: bl_fir
-// Uniform grid over one frame's detections (split path): the nearest detection of a track is looked for in the
-// cells around it instead of among all of them (25 M distances per frame at 5000 x 5000).
-constexpr int GRID_N = 128;                         // cells per side
-constexpr int GRID_CELLS = GRID_N * GRID_N;
 struct DetGrid {
     const int *start;     // [GRID_CELLS + 1] first item of each cell (cells row-major: cy * GRID_N + cx)
     const int *items;     // [max_det] detection columns, cell by cell (any order inside a cell)
@@ -119,49 +41,39 @@ struct DetGrid {
                           // of loads instead of column numbers first and the detections they name after them
 };
 
+namespace plan = tracker_plan;
+
 struct ysmr_tracker {
     TrackerDev d;      // view of parity 0
-    TrackerDev d1;     // view of parity 1 (fused path: small per-frame arrays are double-buffered)
-    int par;           // parity of the current state
-    bool fused;        // one k_frame launch per frame instead of k_link + k_track
-    size_t frame_lds;
-    void *block;       // the single device allocation
-    size_t block_bytes;
-    std::vector<double> gains_host;
-    void *grid_block = nullptr;    // split path: DetGrid arrays for grid_frames frames; batch link: k_bgrid's blocks
-    int grid_frames = 0;           //   (allocated by ysmr_tracker_create: no allocation on the call path)
-    // batch link (batch_link.h): the handle can link a whole batch per launch; where the state rests right now
-    BatchDev bd;
-    bool batchable = false;        // configuration served by k_batch (three filters of <= 31 frames, <= 1024 tracks, ...)
+    TrackerDev d1;     // view of parity 1 (k_frame: small per-frame arrays are double-buffered)
+    int par = 0;       // parity of the current state
+    // tracker_plan.h: what the arguments of ysmr_tracker_create come to, and which link paths the handle can take (the
+    // device may have cleared one: a refused LDS size).  link() says which one it takes
+    plan::Config cfg;
+    plan::Caps caps;
+    int dims = 2;                  // ysmr_tracker_dimensions: 2 (x, y) or 3 (x, y, luminosity)
+    int link_mode = 0;             // ysmr_tracker_link_mode
     bool in_batch = false;         // the state rests in the seat-major arrays of `bd` (else: the per-slot layout)
-    int link_mode = 0;             // ysmr_tracker_link_mode: 0 = the library's choice, 1 = one (or two) launches per frame,
-                                   // 2 = as 0, and a 3-D handle that can also links a batch with one launch (k_batch3)
-    size_t batch_lds = 0;
-    BlGains bgains;
-    const BlGains *bgains_dev = nullptr;     // the same in device memory (behind the grid blocks): k_batch reads it frame by frame
+    bool linked = false;           // a frame has been linked since creation / the last reset: the dimension is fixed
+    void *block = nullptr;         // the single device allocation
+    size_t block_bytes = 0;
+    std::vector<double> gains_host;
+    void *grid_block = nullptr;    // two-launch paths: DetGrid arrays for grid_frames frames; batch link: k_bgrid's blocks
+    int grid_frames = 0;           //   (allocated by ysmr_tracker_create: no allocation on the call path)
+    BatchDev bd;                   // batch link (batch_link.h), and the filter state of k_track_lanes: seat-major by slot from the start
+    const BlGains *bgains_dev = nullptr;     // cfg.bgains in device memory (behind the grid blocks): k_batch reads it frame by frame
     // ysmr_tracker_prepare: which batch each of the two caller-named grid blocks was binned for (block 2 is run's own)
     struct Prepared { const void *det = nullptr; const void *count = nullptr; const void *third = nullptr; int batch = 0; } prepared[2];
-    // split link with a track per lane (batch_link.h: k_track_lanes): the filter state of a non-fused handle lives seat-major by
-    // slot in `bd` from the start; the ring's head is kept here (every live track appends one measurement per frame)
-    bool lanes = false;
-    int lanes_head = 0;
-    // ysmr_tracker_dimensions: 2 (x, y) or 3 (x, y, luminosity).  A 3-D handle links frame by frame with all-pairs row minima
-    // (the grid searches and the batch link are two-dimensional): `batchable` and `lanes` are false while it is one, and what
-    // they were for the 2-D handle is kept beside them.
-    int dims = 2;
-    bool batchable_2d = false, lanes_2d = false;
-    bool linked = false;           // a frame has been linked since creation / the last reset: the dimension is fixed
+    int lanes_head = 0;            // k_track_lanes: the ring's head (every live track appends one measurement per frame)
     double *pos3 = nullptr;        // [capacity] third coordinate of the track in a slot
     // the batch link of a 3-D handle (batch_link.h: k_bgrid3 + k_batch3), on request only (link mode 2): its grid blocks -- a
     // larger stride than the 2-D ones, for the third coordinate's two planes -- and the seat-major third coordinate are
     // allocated when the mode is first selected on a 3-D handle, so a 2-D handle's footprint is what it was
-    bool batchable3 = false;       // set up and served by k_batch3
-    bool tried3 = false;           // ... or found not to be (asked once)
     void *grid3_block = nullptr;   // [3][BL_MAX_BATCH][grid3_stride] bytes, then seat3 f64 [seat_cap]
     unsigned grid3_stride = 0;
     double *seat3 = nullptr;
-    size_t batch3_lds = 0;
-    bool use_batch() const { return dims == 3 ? (batchable3 && link_mode == 2) : (batchable && link_mode != 1); }
+    plan::Link link() const { return plan::link_of(caps, dims, link_mode); }      // how a `run` call is linked
+    plan::Link frame_link() const { return plan::link_of(caps, dims, 1); }        // ... and a single frame (update; link mode 1)
     DetGrid grid(int f) const
     {
         char *b = (char *)grid_block;
@@ -170,13 +82,10 @@ struct ysmr_tracker {
         return DetGrid{(const int *)(b + per * f), (const int *)(b + per * f + o_items), (const float *)(b + per * f + o_hdr),
                        (const float2 *)(b + per * f + o_hdr + 64)};
     }
-    static size_t grid_bytes_per_frame(int max_det)
-    {
-        return ysmr::align_up(sizeof(int) * (GRID_CELLS + 64) + sizeof(int) * (size_t)max_det + 64 + sizeof(float2) * (size_t)max_det, 256);
-    }
     const TrackerDev &cur() const { return par ? d1 : d; }
     const TrackerDev &nxt() const { return par ? d : d1; }
 };
+
 
 #ifdef YSMR_STAMPS
 __device__ unsigned long long g_stamps[32];
@@ -1004,54 +913,13 @@ __global__ __launch_bounds__(256) void k_track(TrackerDev t, int frame, ysmr_row
 
 // ------------------------------------------------------------------------------------------
 // CPython set model: iteration order of set(range(m)).difference(used_cols) (tracker.py:193,216).
-// Ints hash to themselves; table sizes, linear probing (LINEAR_PROBES = 9) and perturbation
-// (PERTURB_SHIFT = 5) as in Objects/setobject.c of CPython 3.7-3.12.
-// The insertions are order-dependent and run on one thread; the number of unused columns per frame
-// is small (k_frame does everything else of the model with the whole block).
+// set_order.h has its rules and the serial form, which runs here on one thread over tables in HBM;
+// the number of unused columns per frame is small (k_frame does everything else of the model with
+// the whole block).
 // ------------------------------------------------------------------------------------------
-__device__ void set_insert_clean(int *table, unsigned mask, int key)
-{
-    unsigned long long perturb = (unsigned long long)key;
-    unsigned i = (unsigned)key & mask;
-    while (true) {
-        int probes = (i + 9u <= mask) ? 9 : 0;
-        for (int j = 0; j <= probes; ++j)
-            if (table[i + j] < 0) { table[i + j] = key; return; }
-        perturb >>= 5;
-        i = (unsigned)(((unsigned long long)i * 5ull + 1ull + perturb) & mask);
-    }
-}
-
 __device__ int cpython_unused_order(const TrackerDev &t, int m, int n_used, int n_unused, int *out)
 {
-    const int *unused = t.unused;  // ascending
-    if ((m >> 2) > n_used) {       // set_copy_and_difference: a copy of set(range(m)) iterates ascending
-        for (int k = 0; k < n_unused; ++k) out[k] = unused[k];
-        return n_unused;
-    }
-    int *table = t.set_table, *other = t.set_table + t.table_cap;
-    unsigned mask = 7;
-    int fill = 0;
-    for (int i = 0; i < 8; ++i) table[i] = -1;
-    for (int k = 0; k < n_unused; ++k) {
-        set_insert_clean(table, mask, unused[k]);  // no equal keys, no dummies: add == insert_clean
-        ++fill;
-        if ((unsigned long long)fill * 5ull >= (unsigned long long)mask * 3ull) {
-            unsigned minused = fill > 50000 ? (unsigned)fill * 2u : (unsigned)fill * 4u;
-            unsigned newsize = 8;
-            while (newsize <= minused) newsize <<= 1;
-            if ((int)newsize > t.table_cap) return -1;
-            for (unsigned i = 0; i < newsize; ++i) other[i] = -1;
-            for (unsigned i = 0; i <= mask; ++i)
-                if (table[i] >= 0) set_insert_clean(other, newsize - 1, table[i]);
-            int *tmp = table; table = other; other = tmp;
-            mask = newsize - 1;
-        }
-    }
-    int count = 0;
-    for (unsigned i = 0; i <= mask; ++i)
-        if (table[i] >= 0) out[count++] = table[i];
-    return count;
+    return set_unused_order(t.unused, m, n_used, n_unused, out, t.set_table, t.set_table + t.table_cap, t.table_cap);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1111,11 +979,7 @@ __device__ __forceinline__ void set_insert_batch(uint32_t *table, unsigned mask,
     int j = 0;                       // offset inside the linear run that starts at i
     unsigned at = 0;
     bool need = active;              // has to propose its next candidate
-    auto advance = [&]() {           // setobject.c set_insert_clean: i .. i + 9, then the perturbed jump
-        const int probes = (i + 9u <= mask) ? 9 : 0;
-        if (j < probes) ++j;
-        else { perturb >>= 5; i = (unsigned)(((unsigned long long)i * 5ull + 1ull + perturb) & mask); j = 0; }
-    };
+    const SetProbeStep advance{i, mask, j, perturb};
     while (true) {
         if (need) {
             at = i + (unsigned)j;
@@ -1138,7 +1002,7 @@ __device__ int cpython_order_block(const int *unused, int n_unused, int m, int n
                                    int cap_table, uint32_t *list, unsigned short *stage, int *s_scan, int *s_state)
 {
     const int tid = threadIdx.x, lane = tid & 63;
-    if ((m >> 2) > n_used) {       // set_copy_and_difference: a copy of set(range(m)) iterates ascending
+    if (set_order_is_ascending(m, n_used)) {
         for (int k = tid; k < n_unused; k += LINK_THREADS) out[k] = unused[k];
         return n_unused;
     }
@@ -1162,7 +1026,7 @@ __device__ int cpython_order_block(const int *unused, int n_unused, int m, int n
     };
     while (true) {
         // wave 0: keys go in until the table wants to grow (setobject.c: fill*5 >= mask*3 after an add)
-        const int thresh = (int)((3u * mask + 4u) / 5u);
+        const int thresh = set_growth_fill(mask);
         const int upto = min(n_unused, k + (thresh - fill));
         if (tid < 64) {
             for (int k0 = k; k0 < upto; k0 += 64) {
@@ -1173,9 +1037,7 @@ __device__ int cpython_order_block(const int *unused, int n_unused, int m, int n
         seq += (unsigned)(upto - k); fill += upto - k; k = upto;
         __syncthreads();
         if (fill < thresh) break;
-        const unsigned minused = (unsigned)fill > 50000u ? (unsigned)fill * 2u : (unsigned)fill * 4u;
-        unsigned newsize = 8;
-        while (newsize <= minused) newsize <<= 1;
+        const unsigned newsize = set_grown_size(fill);
         if ((int)newsize > cap_table) return -1;                      // (uniform)
         const int cnt = collect(list);
         __syncthreads();
@@ -1558,8 +1420,6 @@ __global__ __launch_bounds__(LINK_THREADS) void k_link(TrackerDev t, const DetT 
 // write while another still reads them (order, gone, row_min/row_arg, the counters) are
 // double-buffered by frame parity: `a` is the state before this frame, `b` the state after it.
 // ------------------------------------------------------------------------------------------
-constexpr int FRAME_THREADS = 256;
-constexpr int FRAME_TABLE = 4096;   // CPython set model table (entries) in LDS: up to 2457 unused columns
 
 // LDS of k_frame.  Kept small on purpose (59 KB at capacity = max_det = 2048): a block that wants
 // most of a CU's 160 KB cannot be placed while kernels of another stream hold LDS there, and the
@@ -1576,10 +1436,6 @@ struct FrameLds {
     short *table;                  // 4 * FRAME_TABLE bytes: the set model's table of 32-bit slots
 };
 
-__host__ __device__ inline size_t frame_lds_bytes(int cap, int max_det, int gain_total)
-{
-    return 8 * ((size_t)gain_total + max_det) + 4 * ((size_t)max_det + 2 * (size_t)cap + 16) + 2 * 2 * FRAME_TABLE + 64;
-}
 
 // Exclusive rank of this thread's flag among the block's flags (thread order) and their count:
 // a ballot per wave, four wave counts through LDS, ONE barrier.  Consecutive calls must alternate
@@ -1611,7 +1467,7 @@ __device__ int cpython_order_lds(const int *unused, int n_unused, int m, int n_u
     // out of the loop and held in scalar registers for the whole launch)
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));
-    if ((m >> 2) > n_used) {
+    if (set_order_is_ascending(m, n_used)) {
         for (int k = tid; k < n_unused; k += THREADS) out[k] = unused[k];
         __syncthreads();
         return n_unused;
@@ -1623,16 +1479,14 @@ __device__ int cpython_order_lds(const int *unused, int n_unused, int m, int n_u
         if (lane < 8) table[lane] = SET_EMPTY32;
         while (true) {
             // keys go in until the table wants to grow (setobject.c: fill*5 >= mask*3 after an add)
-            const int thresh = (int)((3u * mask + 4u) / 5u);
+            const int thresh = set_growth_fill(mask);
             while (k < n_unused && fill < thresh) {
                 const int b = min(64, min(n_unused - k, thresh - fill));
                 set_insert_batch(table, mask, lane < b, lane < b ? (unsigned)unused[k + lane] : 0u, seq + lane);
                 k += b; fill += b; seq += b;
             }
             if (fill < thresh) break;
-            const unsigned minused = (unsigned)fill > 50000u ? (unsigned)fill * 2u : (unsigned)fill * 4u;
-            unsigned newsize = 8;
-            while (newsize <= minused) newsize <<= 1;
+            const unsigned newsize = set_grown_size(fill);
             if ((int)newsize > TABLE) { result = -1; break; }
             int cnt = 0;
             for (unsigned i0 = 0; i0 <= mask; i0 += 64) {   // the old table in slot order -> list
@@ -2004,35 +1858,19 @@ __global__ void k_tracker_reset(TrackerDev t)
     if (i == 0) { *t.n_tracks = 0; *t.next_id = 0; *t.err = 0; *t.n_free = t.capacity; }
 }
 
-int horizons(double fps, int n_min, double n_max, int n_f, int *n_i)
+// what tracker_plan.h found wrong with the arguments, as the library reports it
+int plan_fail(const plan::Status &s)
 {
-    // generate_n_i (gsff.py:87-109); CentroidTracker passes n_max = fps when it is None (tracker.py:58-59)
-    if (n_f < 1 || n_f > YSMR_MAX_FILTERS)
-        return ysmr::fail(YSMR_ERR_ARG, "number of LSFFs must be in 1..%d, got %d", YSMR_MAX_FILTERS, n_f);
-    if (!(fps > 0)) return ysmr::fail(YSMR_ERR_ARG, "fps must be positive");
-    double top = n_max > 0 ? n_max : fps;
-    double p = (top - n_min) / n_f;
-    for (int i = 1; i <= n_f; ++i) n_i[i - 1] = (int)(n_min + p * i);
-    for (int i = 0; i < n_f; ++i)
-        if (n_i[i] < 1 || (i && n_i[i] <= n_i[i - 1]))
-            return ysmr::fail(YSMR_ERR_ARG, "filter horizons must be >= 1 and strictly increasing (n_min=%d n_max=%g n_f=%d)",
-                              n_min, top, n_f);
-    return YSMR_OK;
-}
-
-void closed_form_gain(int N, double *g)
-{
-    // rows 0/1 of (L^T L)^-1 L^T for the constant-velocity model: the one-step-ahead
-    // least-squares line fit, c_j = 1/N + t_j * ((N+1)/2) / sum(t^2), t_j = j - (N-1)/2
-    double st2 = 0.0;
-    for (int j = 0; j < N; ++j) { double tj = j - (N - 1) / 2.0; st2 += tj * tj; }
-    std::memset(g, 0, sizeof(double) * 4 * N);
-    for (int j = 0; j < N; ++j) {
-        double tj = j - (N - 1) / 2.0;
-        double c = 1.0 / N + (st2 > 0 ? tj * ((N + 1) / 2.0) / st2 : 0.0);
-        g[2 * j] = c;              // row 0, x columns
-        g[2 * N + 2 * j + 1] = c;  // row 1, y columns
+    switch (s.what) {
+    case plan::Bad::size: return ysmr::fail(YSMR_ERR_ARG, "capacity/max_det out of range: need 1 .. %d, got %d/%d", TRACKER_MAX_SIZE, s.a, s.b);
+    case plan::Bad::filters: return ysmr::fail(YSMR_ERR_ARG, "number of LSFFs must be in 1..%d, got %d", s.a, s.b);
+    case plan::Bad::fps: return ysmr::fail(YSMR_ERR_ARG, "fps must be positive");
+    case plan::Bad::horizons:
+        return ysmr::fail(YSMR_ERR_ARG, "filter horizons must be >= 1 and strictly increasing (n_min=%d n_max=%g n_f=%d)", s.a, s.x, s.b);
+    case plan::Bad::horizon_max: return ysmr::fail(YSMR_ERR_ARG, "maximum horizon size %d exceeds the supported 63", s.a);
+    case plan::Bad::none: break;
     }
+    return YSMR_OK;
 }
 
 // One frame through the per-frame kernels.  `det` is [m][5] float (double with `f64`); the count is `m`, or *m_dev when m < 0.
@@ -2064,32 +1902,33 @@ int launch_frame_t(ysmr_tracker *t, hipStream_t st, const FrameArgs &a)
     // the filter bank is unrolled at compile time: 3 covers tracking.ini's default (and 1, 2), 8 the rest (a 3-D handle has none)
     const bool wide = !D3 && t->d.n_f > 3;
     t->linked = true;
-    if (t->fused) {
+    const plan::Link path = t->frame_link();
+    if (path == plan::Link::frame) {
         const TrackerDev &c = t->cur(), &n = t->nxt();
         // (a call's first frame: k_rowmin also sets the first output row -- *a.row_count in a run, 0 when it is NULL, an update)
         if (!a.rowmin_done)
             hipLaunchKernelGGL((k_rowmin<DetT, D3>), wgrid, dim3(256), 0, st, c, det, a.m, a.m_dev, 1, a.row_count, DetGrid{}, th);
         auto frame = k_frame<DetT, 3, D3>;
         if constexpr (!D3) if (wide) frame = k_frame<DetT, YSMR_MAX_FILTERS>;
-        hipLaunchKernelGGL(frame, wgrid, dim3(FRAME_THREADS), t->frame_lds, st, c, n, det, a.m, a.m_dev, a.frame, a.rows,
+        hipLaunchKernelGGL(frame, wgrid, dim3(FRAME_THREADS), t->caps.frame_lds, st, c, n, det, a.m, a.m_dev, a.frame, a.rows,
                            a.rows_capacity, a.row_count, a.n_rows, a.claim, a.n_before, a.new_cols, a.n_new, next_det, a.next_m_dev, th);
         t->par ^= 1;
     } else {
         const TrackerDev &d = t->d;
         if (!a.rowmin_done)
             hipLaunchKernelGGL((k_rowmin<DetT, D3>), wgrid, dim3(256), 0, st, d, det, a.m, a.m_dev, 0, nullptr, a.grid, th);
-        const size_t link_lds = 12 * (size_t)d.max_det;
+        const size_t link_lds = t->caps.link_lds_bytes;
 #ifdef YSMR_TUNING
         static const bool hbm_tables = getenv("YSMR_LINK_TABLES") && !strcmp(getenv("YSMR_LINK_TABLES"), "hbm");
 #else
         const bool hbm_tables = false;
 #endif
-        const bool lds_tables = link_lds <= 140 * 1024 && (D3 || !hbm_tables);     // (the tuning hook is 2-D only)
+        const bool lds_tables = t->caps.link_lds && (D3 || !hbm_tables);     // (the tuning hook is 2-D only)
         auto link = k_link<DetT, true, D3>;
         if (!lds_tables) link = k_link<DetT, false, D3>;
         hipLaunchKernelGGL(link, dim3(1), dim3(LINK_THREADS), lds_tables ? link_lds : 0, st, d, det, a.m, a.m_dev, a.frame, a.rows,
                            a.rows_capacity, a.row_count, a.n_rows, a.claim, a.n_before, a.new_cols, a.n_new, th);
-        if (t->lanes) {
+        if (path == plan::Link::lanes) {
             hipLaunchKernelGGL(k_track_lanes<DetT>, dim3((d.capacity + TL_THREADS - 1) / TL_THREADS), dim3(TL_THREADS), 0, st, d, t->bd,
                                t->bgains_dev, t->lanes_head, a.frame, a.rows, a.rows_capacity, det, next_det, a.next_m_dev, a.next_grid);
             t->lanes_head = (t->lanes_head + 1) & (BL_HB - 1);
@@ -2158,227 +1997,107 @@ extern "C" {
 int ysmr_gsff_gains(double fps, int n_min, double n_max, int n_f, int32_t *n_i_out, double *gains_out)
 {
     int n_i[YSMR_MAX_FILTERS];
-    if (int rc = horizons(fps, n_min, n_max, n_f, n_i)) return rc;
+    if (plan::Status s = plan::horizons(fps, n_min, n_max, n_f, n_i)) return plan_fail(s);
     if (!n_i_out) return ysmr::fail(YSMR_ERR_ARG, "n_i_out must not be NULL");
     size_t off = 0;
     for (int i = 0; i < n_f; ++i) {
         n_i_out[i] = n_i[i];
-        if (gains_out) closed_form_gain(n_i[i], gains_out + off);
+        if (gains_out) plan::closed_form_gain(n_i[i], gains_out + off);
         off += 4 * (size_t)n_i[i];
     }
     return YSMR_OK;
 }
 
+// What only the build and the device can say about a handle's capabilities: each may clear one, none sets one.
+static void clear_refused(plan::Caps &q)
+{
+#ifdef YSMR_TUNING
+    // YSMR_LINK_MODE (tuning builds only): "split" forces the two-launch path, "waves" keeps k_track (a wave per track) in it
+    // for A/B runs, and anything but "batch" keeps the link per frame
+    if (const char *mode_env = getenv("YSMR_LINK_MODE")) {
+        if (!strcmp(mode_env, "split")) q.frame = false;
+        if (strcmp(mode_env, "batch")) q.batch = false;
+        if (!strcmp(mode_env, "waves")) q.lanes = false;
+    }
+#endif
+    if (q.frame) {
+        const void *variants[4] = {(const void *)k_frame<float, 3>, (const void *)k_frame<double, 3>,
+                                   (const void *)k_frame<float, YSMR_MAX_FILTERS>, (const void *)k_frame<double, YSMR_MAX_FILTERS>};
+        for (const void *fn : variants)
+            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.frame_lds) != hipSuccess) q.frame = false;
+    }
+    if (q.frame && q.batch &&
+        hipFuncSetAttribute((const void *)k_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.batch_lds) != hipSuccess)
+        q.batch = false;
+}
+
+static int destroy_failed(ysmr_tracker *t, int rc)      // (rc: ysmr::fail's, its message already written)
+{
+    if (t->block) (void)hipFree(t->block);
+    if (t->grid_block) (void)hipFree(t->grid_block);
+    delete t;
+    return rc;
+}
+
+// check, plan (tracker_plan.h), allocate, bind, upload
 int ysmr_tracker_create(double max_disappeared, double fps, int n_min, double n_max, int n_f, int use_gsff,
                         int capacity, int max_det, const double *gains_host, ysmr_tracker **out)
 {
     if (!out) return ysmr::fail(YSMR_ERR_ARG, "out must not be NULL");
     *out = nullptr;
-    // (the tables of the two-launch path live in HBM; the bound only keeps 32-bit indices and the state block sane)
-    if (capacity <= 0 || max_det <= 0 || capacity > 65536 || max_det > 65536)
-        return ysmr::fail(YSMR_ERR_ARG, "capacity/max_det out of range: need 1 .. 65536, got %d/%d", capacity, max_det);
     ysmr_tracker *t = new ysmr_tracker();
-    TrackerDev &d = t->d;
-    std::memset(&d, 0, sizeof(d));
-    d.capacity = capacity;
-    d.max_det = max_det;
-    d.use_gsff = use_gsff ? 1 : 0;
-    d.max_gone = max_disappeared;
-    d.lik_min = 1e-20;  // tracker.py:67
-    d.n_f = use_gsff ? n_f : 1;
-    size_t gain_doubles = 0;
-    if (use_gsff) {
-        if (int rc = horizons(fps, n_min, n_max, n_f, d.n_i)) { delete t; return rc; }
-        for (int i = 0; i < n_f; ++i) { d.gain_off[i] = (int)gain_doubles; gain_doubles += 4 * (size_t)d.n_i[i]; }
-        t->gains_host.resize(gain_doubles);
-        if (gains_host) std::memcpy(t->gains_host.data(), gains_host, sizeof(double) * gain_doubles);
-        else for (int i = 0; i < n_f; ++i) closed_form_gain(d.n_i[i], t->gains_host.data() + d.gain_off[i]);
-        d.gains_decoupled = 1;   // row 0 must vanish on the y columns, row 1 on the x columns
-        for (int i = 0; i < n_f && d.gains_decoupled; ++i) {
-            const double *g = t->gains_host.data() + d.gain_off[i];
-            for (int j = 0; j < d.n_i[i]; ++j)
-                if (g[2 * j + 1] != 0.0 || g[2 * d.n_i[i] + 2 * j] != 0.0) { d.gains_decoupled = 0; break; }
-        }
-        d.hist_cap = d.n_i[n_f - 1] + 1;
-        if (d.hist_cap > 64) { delete t; return ysmr::fail(YSMR_ERR_ARG, "maximum horizon size %d exceeds the supported 63", d.n_i[n_f - 1]); }
-    } else {
-        d.n_i[0] = 1;
-        d.hist_cap = 1;
-    }
-    unsigned tc = 8;
-    while (tc <= (unsigned)max_det * 4u) tc <<= 1;
-    d.table_cap = (int)tc;
-    d.gain_total = (int)gain_doubles;
-
-    const size_t cap = capacity, nf = d.n_f;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = ysmr::align_up(off + bytes, 256); return o; };
-    const size_t o_scal = take(sizeof(int) * 16);
-    const size_t o_order = take(sizeof(int) * cap), o_free = take(sizeof(int) * cap);
-    const size_t o_id = take(sizeof(int) * cap), o_gone = take(sizeof(int) * cap);
-    const size_t o_pos = take(sizeof(double) * 2 * cap), o_info = take(sizeof(float) * 3 * cap);
-    const size_t o_pos3 = take(sizeof(double) * cap);      // (a 3-D handle's third coordinate: ysmr_tracker_dimensions)
-    const size_t o_hist = take(sizeof(double) * 2 * cap * d.hist_cap);
-    d.rec_stride = (2 + 3 * nf + 7) / 8 * 8;
-    const size_t o_rec = take(sizeof(double) * (size_t)d.rec_stride * cap);
-    const size_t o_gain = take(sizeof(double) * (gain_doubles ? gain_doubles : 1));
-    const size_t o_unused = take(sizeof(int) * max_det);
-    const size_t o_rmin = take(sizeof(double) * cap), o_rarg = take(sizeof(int) * cap), o_rgone = take(sizeof(int) * cap);
-    const size_t o_dead = take(sizeof(int) * cap);
-    const size_t o_new = take(sizeof(int) * max_det), o_table = take(sizeof(int) * 2 * (size_t)d.table_cap);
-    const size_t o_lkey = take(sizeof(unsigned long long) * max_det), o_lrow = take(sizeof(int) * max_det);
-    const size_t o_lclaim = take(sizeof(int) * cap), o_cslot = take(sizeof(int) * cap), o_crow = take(sizeof(int) * cap);
-    // parity-1 copies of the arrays k_frame double-buffers
-    const size_t o_scal1 = take(sizeof(int) * 16), o_order1 = take(sizeof(int) * cap), o_gone1 = take(sizeof(int) * cap);
-    const size_t o_rmin1 = take(sizeof(double) * cap), o_rarg1 = take(sizeof(int) * cap);
-    // the batch link's rest format (seat-major) and its gain table
-    const size_t seat_cap = capacity > BL_THREADS ? (size_t)capacity : (size_t)BL_THREADS;     // (k_batch: 768 seats; k_track_lanes: a seat per slot)
-    // (BL_HB positions and the line of zeros behind them: cleared with the block below; every store indexes 0 .. BL_HB - 1)
-    const size_t o_ring = take(sizeof(double2) * (BL_HB + 1) * seat_cap);
-    const size_t o_b64 = take(sizeof(double) * BL_SF64 * seat_cap), o_b32 = take(sizeof(float) * 3 * seat_cap);
-    const size_t o_bi = take(sizeof(int) * 6 * seat_cap);
-    t->block_bytes = off;
-    hipError_t e = hipMalloc(&t->block, off);
+    const plan::Config &c = t->cfg;
+    if (plan::Status s = plan::configure(max_disappeared, fps, n_min, n_max, n_f, use_gsff, capacity, max_det, gains_host, t->cfg,
+                                         t->gains_host))
+        return destroy_failed(t, plan_fail(s));
+    plan::Caps &q = t->caps = plan::qualifies(c);
+    t->block_bytes = plan::carve_state(nullptr, c, t->d, t->d1, t->bd, t->pos3);
+    hipError_t e = hipMalloc(&t->block, t->block_bytes);
     if (e != hipSuccess) {
-        delete t;
-        return ysmr::fail(YSMR_ERR_HIP, "hipMalloc(%zu) failed: %s", off, hipGetErrorString(e));
+        t->block = nullptr;
+        return destroy_failed(t, ysmr::fail(YSMR_ERR_HIP, "hipMalloc(%zu) failed: %s", t->block_bytes, hipGetErrorString(e)));
     }
-    char *b = (char *)t->block;
-    int *scal = (int *)(b + o_scal);
-    d.n_tracks = scal; d.next_id = scal + 1; d.err = scal + 2; d.n_free = scal + 3;
-    d.row_base = (long long *)(scal + 8);
-    d.order = (int *)(b + o_order); d.free_slots = (int *)(b + o_free);
-    d.id = (int *)(b + o_id); d.gone = (int *)(b + o_gone);
-    d.pos = (double *)(b + o_pos); d.info = (float *)(b + o_info); d.hist = (double *)(b + o_hist);
-    t->pos3 = (double *)(b + o_pos3);
-    d.rec = (double *)(b + o_rec);
-    d.gains = (const double *)(b + o_gain);
-    d.unused = (int *)(b + o_unused);
-    d.row_min = (double *)(b + o_rmin); d.row_arg = (int *)(b + o_rarg); d.row_gone = (int *)(b + o_rgone);
-    d.dead = (int *)(b + o_dead);
-    d.new_cols = (int *)(b + o_new); d.set_table = (int *)(b + o_table);
-    d.link_key = (unsigned long long *)(b + o_lkey); d.link_row = (int *)(b + o_lrow); d.link_claim = (int *)(b + o_lclaim);
-    d.claim_slot = (int *)(b + o_cslot);
-    d.claim_row = (int *)(b + o_crow);
-    t->bd.ring = (double2 *)(b + o_ring);
-    t->bd.f64 = (double *)(b + o_b64); t->bd.f32 = (float *)(b + o_b32); t->bd.i32 = (int *)(b + o_bi);
-    t->bd.head = scal + 12;
-    t->bd.seat_cap = (int)seat_cap;
-    t->bd.grid = nullptr; t->bd.grid_stride = 0;
-    t->d1 = d;
-    {
-        TrackerDev &q = t->d1;
-        int *scal1 = (int *)(b + o_scal1);
-        q.n_tracks = scal1; q.next_id = scal1 + 1; q.n_free = scal1 + 3;   // err stays shared (sticky)
-        q.row_base = (long long *)(scal1 + 8);
-        q.order = (int *)(b + o_order1); q.gone = (int *)(b + o_gone1);
-        q.row_min = (double *)(b + o_rmin1); q.row_arg = (int *)(b + o_rarg1);
-    }
-    t->par = 0;
-    t->frame_lds = frame_lds_bytes(capacity, max_det, (int)gain_doubles);
-#ifdef YSMR_TUNING
-    const char *mode_env = getenv("YSMR_LINK_MODE");   // "split" forces the two-kernel path (tuning builds only)
-#else
-    const char *mode_env = nullptr;
-#endif
-    // (max_det <= 2456: the LDS set model holds that many unregistered columns; the split path keeps its
-    // tables in HBM and has no such limit)
-    // (and a `gone` counter that fits the 15 bits k_frame packs it into)
-    t->fused = t->frame_lds <= 150 * 1024 && max_det <= 2456 && max_disappeared < 32000.0 &&
-               !(mode_env && !strcmp(mode_env, "split"));
-    if (t->fused) {
-        const void *variants[4] = {(const void *)k_frame<float, 3>, (const void *)k_frame<double, 3>,
-                                   (const void *)k_frame<float, YSMR_MAX_FILTERS>, (const void *)k_frame<double, YSMR_MAX_FILTERS>};
-        for (const void *fn : variants)
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->frame_lds) != hipSuccess) t->fused = false;
-    }
-    t->d.gone_by_row = t->d1.gone_by_row = t->fused ? 1 : 0;
-    // The batch link serves what tracking.ini's defaults ask for: up to three filters with horizons of at most 31 frames
-    // (hist_cap <= 32 ring entries), gains affine in a measurement's age, tables of at most 1024 tracks -- a track per lane of ONE
-    // workgroup -- and detection counts whose tables fit its LDS.  Everything else links with one (or two) launches per
-    // frame as before.
-    t->batch_lds = bl_lds_bytes(max_det);
-    t->batchable = t->fused && d.n_f <= BL_NF && d.hist_cap <= BL_HB && (!use_gsff || d.gains_decoupled) &&
-                   capacity <= BL_THREADS && bl_lds_total(max_det) <= BL_LDS_LIMIT && !(mode_env && strcmp(mode_env, "batch"));
-    if (t->batchable &&
-        hipFuncSetAttribute((const void *)k_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->batch_lds) != hipSuccess)
-        t->batchable = false;
-    // ... and the two-launch link of larger tables runs its per-track half with a track per LANE (k_track_lanes) under the same
-    // conditions on the filter bank (tuning builds: YSMR_LINK_MODE=waves keeps k_track, a wave per track, for A/B runs)
-    t->lanes = !t->fused && d.n_f <= BL_NF && d.hist_cap <= BL_HB && (!use_gsff || d.gains_decoupled) &&
-               !(mode_env && !strcmp(mode_env, "waves"));
-    // the gains as the batch kernel takes them: affine in the age of a measurement (batch_link.h: bl_fir)
-    std::memset(&t->bgains, 0, sizeof(t->bgains));
-    if (use_gsff && (t->batchable || t->lanes)) {
-        bool affine = true;
-        for (int f = 0; f < d.n_f && affine; ++f) {
-            const int N = d.n_i[f];
-            const double *g = t->gains_host.data() + d.gain_off[f];
-            for (int c = 0; c < 2 && affine; ++c) {
-                auto gain = [&](int a) { return c ? g[2 * N + 2 * (N - 1 - a) + 1] : g[2 * (N - 1 - a)]; };   // age a, row c
-                const double alpha = gain(0), beta = N > 1 ? gain(0) - gain(1) : 0.0;
-                for (int a = 0; a < N; ++a)
-                    if (std::fabs(gain(a) - (alpha - beta * a)) > 1e-14 * std::fabs(alpha)) affine = false;
-                t->bgains.alpha[f][c] = alpha;
-                t->bgains.beta[f][c] = beta;
-            }
+    clear_refused(q);
+    plan::carve_state(t->block, c, t->d, t->d1, t->bd, t->pos3);
+    t->d.gone_by_row = t->d1.gone_by_row = q.frame ? 1 : 0;
+    // the per-frame grids of a batch: sized here, once, for BL_MAX_BATCH frames (longer batches are cut to that); behind them the
+    // affine gains of the lane kernels.  (A handle is created 2-D, in link mode 0.)
+    const plan::Link own = t->link();
+    const bool lane_bank = own == plan::Link::batch || own == plan::Link::lanes;
+    const plan::GridBlocks g = plan::grid_blocks(q, max_det);
+    if (g.blocks) {
+        const size_t bytes = g.per_frame * BL_MAX_BATCH * g.blocks;
+        e = hipMalloc(&t->grid_block, bytes + 256);
+        if (e != hipSuccess) t->grid_block = nullptr;
+        if (e == hipSuccess && lane_bank) {
+            t->bgains_dev = reinterpret_cast<const BlGains *>((char *)t->grid_block + bytes);
+            e = hipMemcpy((void *)t->bgains_dev, &c.bgains, sizeof(BlGains), hipMemcpyHostToDevice);
         }
-        if (!affine) t->batchable = t->lanes = false;
+        if (e != hipSuccess) return destroy_failed(t, ysmr::fail(YSMR_ERR_HIP, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e)));
+        t->grid_frames = BL_MAX_BATCH;
+        t->bd.grid = (char *)t->grid_block;
+        t->bd.grid_stride = (unsigned)g.per_frame;
     }
-    // the per-frame grids of a batch: sized here, once, for BL_MAX_BATCH frames (longer batches are cut to that)
-    {
-        const size_t per = t->batchable ? (size_t)bl_grid_dwords_max(max_det) * 4 : ysmr_tracker::grid_bytes_per_frame(max_det);
-        const size_t blocks = t->batchable ? 3 : 1;      // (two for ysmr_tracker_prepare's callers, one for ysmr_tracker_run itself)
-        if (t->batchable || !t->fused) {
-            e = hipMalloc(&t->grid_block, per * BL_MAX_BATCH * blocks + 256);
-            if (e == hipSuccess && (t->batchable || t->lanes)) {
-                t->bgains_dev = reinterpret_cast<const BlGains *>((char *)t->grid_block + per * BL_MAX_BATCH * blocks);
-                e = hipMemcpy((void *)t->bgains_dev, &t->bgains, sizeof(BlGains), hipMemcpyHostToDevice);
-            }
-            if (e != hipSuccess) {
-                (void)hipFree(t->block);
-                delete t;
-                return ysmr::fail(YSMR_ERR_HIP, "hipMalloc(%zu) failed: %s", per * BL_MAX_BATCH * blocks, hipGetErrorString(e));
-            }
-            t->grid_frames = BL_MAX_BATCH;
-            t->bd.grid = (char *)t->grid_block;
-            t->bd.grid_stride = (unsigned)per;
-        }
-    }
-    e = hipMemset(t->block, 0, off);
-    if (e == hipSuccess && t->lanes) e = hipMemset(t->bd.i32, 0xFF, sizeof(int) * seat_cap);     // no slot's filter state belongs to a track yet
-    if (e == hipSuccess && gain_doubles)
-        e = hipMemcpy(b + o_gain, t->gains_host.data(), sizeof(double) * gain_doubles, hipMemcpyHostToDevice);
-
-    if (e != hipSuccess) {
-        (void)hipFree(t->block);
-        if (t->grid_block) (void)hipFree(t->grid_block);
-        delete t;
-        return ysmr::fail(YSMR_ERR_HIP, "tracker state initialisation failed: %s", hipGetErrorString(e));
-    }
-    t->batchable_2d = t->batchable;
-    t->lanes_2d = t->lanes;
+    e = hipMemset(t->block, 0, t->block_bytes);
+    if (e == hipSuccess && own == plan::Link::lanes)      // no slot's filter state belongs to a track yet
+        e = hipMemset(t->bd.i32, 0xFF, sizeof(int) * (size_t)t->bd.seat_cap);
+    if (e == hipSuccess && c.gain_total)
+        e = hipMemcpy((void *)t->d.gains, t->gains_host.data(), sizeof(double) * c.gain_total, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return destroy_failed(t, ysmr::fail(YSMR_ERR_HIP, "tracker state initialisation failed: %s", hipGetErrorString(e)));
     *out = t;
     return ysmr_tracker_reset(t, nullptr);
 }
 
-// The 3-D batch link of a handle, set up the first time link mode 2 meets three dimensions: "batchable in 3-D" is fused,
-// at most BL_THREADS tracks, and k_batch3's LDS within a compute unit's for the handle's max_det (capacity 768 with
-// max_det 2048, the pipeline's shape, is).  A handle that is not keeps the per-frame link, silently, as 2-D handles do.
+// The 3-D batch link of a handle, set up the first time link mode 2 meets three dimensions, for a handle that qualifies
+// (caps.batch3: capacity 768 with max_det 2048, the pipeline's shape, does).  One that does not, or whose LDS the device
+// refuses, keeps the per-frame link, silently, as 2-D handles do; after a failed allocation the next call tries again.
 static int setup_batch3(ysmr_tracker *t)
 {
-    if (t->tried3) return YSMR_OK;
-    // (tried3 is set on a definite answer only -- the shape does not qualify, the device refuses the LDS, or everything is
-    // in place: after a failed allocation the next call tries again)
+    if (!(t->caps.frame && t->caps.batch3) || t->grid3_block) return YSMR_OK;
     const int max_det = t->d.max_det;
-    if (!t->fused || t->d.use_gsff || t->d.capacity > BL_THREADS || bl3_lds_total(max_det) > BL_LDS_LIMIT) {
-        t->tried3 = true;
-        return YSMR_OK;
-    }
-    t->batch3_lds = bl3_lds_bytes(max_det);
-    if (hipFuncSetAttribute((const void *)k_batch3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->batch3_lds) != hipSuccess) {
+    if (hipFuncSetAttribute((const void *)k_batch3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->caps.batch3_lds) != hipSuccess) {
         (void)hipGetLastError();
-        t->tried3 = true;
+        t->caps.batch3 = false;
         return YSMR_OK;
     }
     const size_t per = bl3_grid_stride(max_det), grids = per * BL_MAX_BATCH * 3;
@@ -2388,10 +2107,8 @@ static int setup_batch3(ysmr_tracker *t)
         (void)hipGetLastError();
         return ysmr::fail(YSMR_ERR_HIP, "hipMalloc(%zu) failed: %s", grids, hipGetErrorString(e));
     }
-    t->tried3 = true;
     t->grid3_stride = (unsigned)per;
     t->seat3 = reinterpret_cast<double *>((char *)t->grid3_block + grids);
-    t->batchable3 = true;
     return YSMR_OK;
 }
 
@@ -2404,16 +2121,15 @@ int ysmr_tracker_dimensions(ysmr_tracker *t, int dimensions)
                                         "(x, y) only: its CentroidTracker raises on a third coordinate, ysmr/tracker.py:68-69, 222)");
     if (t->linked)
         return ysmr::fail(YSMR_ERR_STATE, "the dimension of a tracker is fixed with its first frame (ysmr_tracker_reset frees it)");
-    if (dimensions == 3 && t->fused) {
+    if (dimensions == 3 && t->caps.frame) {
         const void *variants[2] = {(const void *)k_frame<float, 3, true>, (const void *)k_frame<double, 3, true>};
-        for (const void *fn : variants) YSMR_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->frame_lds));
+        for (const void *fn : variants)
+            YSMR_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->caps.frame_lds));
     }
     if (dimensions == 3 && t->link_mode == 2)      // (in front of every change to the handle: a failure leaves it as it was)
         if (int rc = setup_batch3(t)) return rc;
     t->dims = dimensions;
-    t->batchable = dimensions == 2 && t->batchable_2d;
-    t->lanes = dimensions == 2 && t->lanes_2d;
-    t->in_batch = t->use_batch();      // (the table is empty: the same in both layouts)
+    t->in_batch = plan::is_batch(t->link());      // (the table is empty: the same in both layouts)
     t->prepared[0] = t->prepared[1] = ysmr_tracker::Prepared();
     return YSMR_OK;
 }
@@ -2424,11 +2140,11 @@ int ysmr_tracker_reset(ysmr_tracker *t, void *stream)
     int n = t->d.capacity > t->d.max_det ? t->d.capacity : t->d.max_det;
     t->par = 0;
     t->prepared[0] = t->prepared[1] = ysmr_tracker::Prepared();
-    if (t->lanes) {                    // (ids start over: a slot's old filter state must not pass for the new track 0's)
+    if (t->frame_link() == plan::Link::lanes) {      // (ids start over: a slot's old filter state must not pass for the new track 0's)
         YSMR_HIP_CHECK(hipMemsetAsync(t->bd.i32, 0xFF, sizeof(int) * (size_t)t->bd.seat_cap, (hipStream_t)stream));
         t->lanes_head = 0;
     }
-    t->in_batch = t->use_batch();      // (an empty table is the same in both layouts)
+    t->in_batch = plan::is_batch(t->link());      // (an empty table is the same in both layouts)
     t->linked = false;
     hipLaunchKernelGGL(k_tracker_reset, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, t->d);
     YSMR_LAUNCH_CHECK();
@@ -2495,7 +2211,7 @@ int ysmr_debug_read_bwaves(unsigned long long *out) { return (int)hipMemcpyFromS
 int ysmr_debug_read_bseats(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bseats), sizeof(unsigned long long) * 2); }
 #endif
 
-int ysmr_tracker_batched(ysmr_tracker *t) { return t && t->use_batch() ? 1 : 0; }
+int ysmr_tracker_batched(ysmr_tracker *t) { return t && plan::is_batch(t->link()) ? 1 : 0; }
 
 // Test hooks for the ring (tests/test_gpu_batch_bookkeeping.py; not part of the ABI the host code binds).  _poison: every
 // entry of positions 0 .. BL_HB - 1 becomes a NaN bit pattern (all ones) -- refused once the handle has registered a track: whatever a
@@ -2562,7 +2278,7 @@ int ysmr_debug_ring_zero_line(ysmr_tracker *t, long long *nonzero)
 int ysmr_debug_read_grid_block(ysmr_tracker *t, int slot, int frame, void *out, size_t bytes)
 {
     if (!t || !out) return ysmr::fail(YSMR_ERR_ARG, "tracker handle and out must be set");
-    if (t->dims != 2 || !t->use_batch()) return ysmr::fail(YSMR_ERR_STATE, "the handle has no batch link: no grid blocks");
+    if (t->link() != plan::Link::batch) return ysmr::fail(YSMR_ERR_STATE, "the handle has no batch link: no grid blocks");
     if (slot < 0 || slot > 1 || t->prepared[slot].batch <= 0 || frame < 0 || frame >= t->prepared[slot].batch || bytes > t->bd.grid_stride)
         return ysmr::fail(YSMR_ERR_ARG, "slot 0 or 1 with a prepared batch, a frame of that batch, at most %u bytes", t->bd.grid_stride);
     hipError_t e = hipDeviceSynchronize();
@@ -2594,7 +2310,7 @@ static void bin_batch(const ysmr_tracker *t, hipStream_t st, const float *det, c
 static int tracker_prepare(ysmr_tracker *t, hipStream_t st, const float *det_dev, const double *third_dev, const int32_t *det_count_dev,
                            int batch, int slot)
 {
-    if (!t->use_batch() || batch > BL_MAX_BATCH) return YSMR_OK;       // (nothing to prepare: the run call does it all)
+    if (!plan::is_batch(t->link()) || batch > BL_MAX_BATCH) return YSMR_OK;       // (nothing to prepare: the run call does it all)
     bin_batch(t, st, det_dev, third_dev, det_count_dev, batch, batch_dev(t, slot));
     YSMR_LAUNCH_CHECK();
     t->prepared[slot] = ysmr_tracker::Prepared{det_dev, det_count_dev, third_dev, batch};
@@ -2668,7 +2384,7 @@ static int tracker_run(ysmr_tracker *t, hipStream_t st, const float *det_dev, co
     const bool d3 = t->dims == 3;
     const size_t md = (size_t)t->d.max_det;
     t->linked = true;
-    if (t->use_batch()) {
+    if (plan::is_batch(t->link())) {
         // one launch links the batch, cut to the BL_MAX_BATCH frames a grid block holds (3-D: link mode 2 on a handle k_batch3 serves)
         if (int rc = state_to_batch(t, st)) return rc;
         for (int f0 = 0; f0 < batch; f0 += BL_MAX_BATCH) {
@@ -2693,14 +2409,14 @@ static int tracker_run(ysmr_tracker *t, hipStream_t st, const float *det_dev, co
                 ka.t = t->d; ka.bd = bd; ka.det_all = det; ka.third_all = third; ka.det_count = det_count_dev + f0; ka.batch = nb;
                 ka.frame0 = first_frame_index + f0; ka.rows = rows_dev; ka.rows_capacity = rows_capacity;
                 ka.row_count = row_count_dev; ka.seat3 = t->seat3;
-                hipLaunchKernelGGL(k_batch3, dim3(1), dim3(BL_THREADS), t->batch3_lds, st, ka);
+                hipLaunchKernelGGL(k_batch3, dim3(1), dim3(BL_THREADS), t->caps.batch3_lds, st, ka);
             } else {
                 BlKernArgs ka;
                 ka.t = t->d; ka.bd = bd; ka.det_all = det; ka.det_count = det_count_dev + f0; ka.batch = nb;
                 ka.frame0 = first_frame_index + f0; ka.rows = rows_dev; ka.rows_capacity = rows_capacity;
                 ka.row_count = row_count_dev; ka.gains = t->bgains_dev;
                 for (int k = 0; k < 4; ++k) ka.hz[k] = (k == 0 || k < t->d.n_f) && k < BL_NF ? t->d.n_i[k] : 0x7FFFFFFF;
-                hipLaunchKernelGGL(k_batch, dim3(1), dim3(BL_THREADS), t->batch_lds, st, ka);
+                hipLaunchKernelGGL(k_batch, dim3(1), dim3(BL_THREADS), t->caps.batch_lds, st, ka);
             }
             YSMR_LAUNCH_CHECK();
         }
@@ -2710,13 +2426,13 @@ static int tracker_run(ysmr_tracker *t, hipStream_t st, const float *det_dev, co
     // One launch per frame (or two); a frame's launch leaves the next frame's row minima.  Large 2-D tables (the split path)
     // look for them in a uniform grid over each frame's detections, built a grid block of frames at a time: the look-ahead
     // stays inside such a chunk, whose first frame gets its own k_rowmin.
-    const bool grids = !t->fused && !d3;
+    const bool grids = plan::uses_det_grids(t->link(), t->dims);
     const int chunk = grids ? t->grid_frames : batch;
     for (int f0 = 0; f0 < batch; f0 += chunk) {
         const int nb = std::min(batch - f0, chunk);
         if (grids) {
             hipLaunchKernelGGL(k_grid_build<float>, dim3(nb), dim3(1024), 0, st, det_dev + (size_t)f0 * md * 5, det_count_dev + f0,
-                               t->d.max_det, (char *)t->grid_block, ysmr_tracker::grid_bytes_per_frame(t->d.max_det));
+                               t->d.max_det, (char *)t->grid_block, grid_bytes_per_frame(t->d.max_det));
             YSMR_LAUNCH_CHECK();
         }
         for (int f = 0; f < nb; ++f) {
@@ -2760,7 +2476,7 @@ int ysmr_tracker_run3(ysmr_tracker *t, void *stream, const float *det_dev, const
                        (long long)rows_capacity, (long long *)row_count_dev);
 }
 
-int ysmr_tracker_fused(ysmr_tracker *t) { return t && t->fused && !t->use_batch() ? 1 : 0; }
+int ysmr_tracker_fused(ysmr_tracker *t) { return t && t->link() == plan::Link::frame ? 1 : 0; }
 
 int ysmr_tracker_peek(ysmr_tracker *t, void *stream, int32_t *ids_dev, double *xy_dev, int32_t *disappeared_dev,
                       int32_t *n_dev)
