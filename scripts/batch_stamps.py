@@ -1,5 +1,7 @@
 """In-kernel phases of the batch link (k_batch), one frame of a batch, per wave: s_memtime stamps of a stamps build
-(scripts/build_stamps.sh; YSMR_HIP_LIB=scripts/var_stamps.so).  usage: batch_stamps.py [blobs] [capacity] [max_det]"""
+(scripts/build_stamps.sh; YSMR_HIP_LIB=scripts/var_stamps.so).  usage: batch_stamps.py [blobs] [capacity] [max_det]
+The stamped launch is frames 64 .. 127: a build with EXTRA=-DYSMR_BL_FRAME=0 stamps frame 64, which refreshes the window sums
+from the ring; its block has a stamp pair of its own and is printed beside that frame and launch frame 40, a steady one."""
 import ctypes, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -29,6 +31,7 @@ count_names = ["wave-frames with a lane on the 3 x 3 block search", "lanes on th
                "frames with registration", "wave-frames refreshing the sums from the ring", "frames with deaths", "deaths",
                "frames on the exact claim path (row of wave 0)"]
 acc = []
+acc_r = []      # per rep and wave: the refresh block, the stamped frame, launch frame 40 (cycles)
 # BESIDE=1: the stamped launch runs while another stream loops over the matrix-pipe threshold kernel on 248 workgroups, as
 # in the pipeline (which phase of a frame the memory system's load stretches)
 beside = os.environ.get("BESIDE") == "1"
@@ -70,6 +73,14 @@ for rep in range(12 if beside else 6):
         seats = (ctypes.c_ulonglong * 2)()
         L.ysmr_debug_read_bseats(seats)
         print(f"   frames that gave up track waves: {int(seats[0])}, tracks moved in them: {int(seats[1])}")
+    if hasattr(L, "ysmr_debug_read_brefresh"):
+        # (a build with -DYSMR_BL_FRAME=0 stamps the stamped launch's first frame, frame 64: the one that refreshes)
+        rf = (ctypes.c_ulonglong * (NW * 4))()
+        L.ysmr_debug_read_brefresh(rf)
+        r = np.array(rf[:], dtype=np.int64).reshape(NW, 4)
+        acc_r.append(np.stack([r[:, 1] - r[:, 0], a[:, LAST] - a[:, 0], r[:, 3] - r[:, 2]], axis=1))
+        print("   refresh block per wave:", acc_r[-1][:, 0].tolist(), " its frame:", acc_r[-1][:, 1].tolist(),
+              " steady frame 40:", acc_r[-1][:, 2].tolist())
     print(f"rep {rep}: launch pair {t0.elapsed_time(t1) * 1e3:.1f} us for {B} frames; frame (wave 0) {a[0, LAST] - a[0, 0]} cycles")
 a = np.mean(np.array(acc), axis=0) if beside else np.median(np.array(acc), axis=0)
 d = np.diff(a, axis=1)
@@ -77,4 +88,13 @@ print("%-44s" % "phase (cycles of s_memtime, 100 MHz? no: shader clock)", " ".jo
 for k, n in enumerate(names):
     print("%-44s" % n, " ".join(f"{d[w, k]:<7.0f}" for w in range(NW)))
 print("%-44s" % "frame", " ".join(f"{a[w, LAST] - a[w, 0]:<7.0f}" for w in range(NW)))
+if acc_r:
+    rr = np.array(acc_r)
+    for how, fn in (("median", np.median), ("mean", np.mean), ("max", np.max)):
+        v = fn(rr, axis=0)
+        for k, n in enumerate(["refresh block", "stamped frame (the refresh's)", "steady frame (launch frame 40)"]):
+            print("%-44s" % f"{n}, {how}", " ".join(f"{v[w, k]:<7.0f}" for w in range(NW)))
+    # the frame ends for the workgroup where its slowest wave does: what a refresh adds to a frame's critical path
+    print("slowest wave per rep: refresh block", rr[:, :, 0].max(axis=1).tolist(), " refresh frame", rr[:, :, 1].max(axis=1).tolist(),
+          " steady frame", rr[:, :, 2].max(axis=1).tolist())
 print(pipe.trk.info())

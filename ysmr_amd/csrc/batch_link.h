@@ -434,6 +434,22 @@ __device__ __forceinline__ bl_u32x4 bl_ring_load16(const double2 *p)
     asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(v) : "v"(p) : "memory");
     return v;
 }
+// (BL_RING_GROUP whole entries, requested together and all of them there where the
+// statement ends: the refresh of the window sums, whose entries do not depend on each other -- one round trip past L1 for
+// the group instead of one per entry.  The wait stands in the statement of the loads and the outputs are early-clobber, as
+// above: the compiler takes an asm output for written where the statement ends, and must not hand a destination register
+// to a later load's address.  The caller has nothing else in flight (vmcnt(0) would wait for it too).  Three, not four:
+// tests/test_kernel_listing.py allows k_batch 46 vector-memory loads, and it had 44 with one entry per statement.)
+constexpr int BL_RING_GROUP = 3;
+__device__ __forceinline__ void bl_ring_load16_group(const double2 *const (&at)[BL_RING_GROUP], bl_u32x4 (&v)[BL_RING_GROUP])
+{
+    static_assert(BL_RING_GROUP == 3, "one load per entry is written out below");
+    asm volatile("global_load_dwordx4 %0, %3, off sc1\n\t"
+                 "global_load_dwordx4 %1, %4, off sc1\n\t"
+                 "global_load_dwordx4 %2, %5, off sc1\n\t"
+                 "s_waitcnt vmcnt(0)"
+                 : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]) : "v"(at[0]), "v"(at[1]), "v"(at[2]) : "memory");
+}
 __device__ __forceinline__ void bl_ring_store(const BatchDev &bd, int pos, int seat, double x, double y)
 {
     bd.ring[(size_t)pos * bd.seat_cap + seat] = make_double2(x, y);
@@ -443,21 +459,52 @@ __device__ __forceinline__ void bl_ring_store(const BatchDev &bd, int pos, int s
 // head - 1 - a; a filter's window holds the newest min(N, len) of them.  Done for every track at the frames whose index
 // is a multiple of BL_REFRESH (a schedule in FRAME numbers: the rows of a video must not depend on how its frames were cut
 // into batches), and by k_to_batch.
-// (WHOLE: an entry with one 16-byte load, bl_ring_load16 -- k_batch, whose loop waits for every entry before it asks for
-// the next either way)
+// (WHOLE: k_batch, where every live track does this in the same frame, on the frame's critical path -- whole entries,
+// BL_RING_GROUP of them per round trip, and no further than the handle's largest horizon)
 template <bool WHOLE = false>
 __device__ __forceinline__ void bl_sums_from_ring(BlSeat &S, const BatchDev &bd, int seat, int head, int n0, int n1, int n2)
 {
     const int lim[BL_NF] = {min(n0, S.len), min(n1, S.len), min(n2, S.len)};
     double s0x = 0.0, s1x = 0.0, s0y = 0.0, s1y = 0.0;
-    for (int a = 0; a < BL_HB - 1; ++a) {
-        double2 e;
-        if constexpr (WHOLE) {
-            const bl_u32x4 w = bl_ring_load16(bd.ring + (size_t)((head - 1 - a) & (BL_HB - 1)) * bd.seat_cap + seat);
-            e.x = __hiloint2double((int)w.y, (int)w.x); e.y = __hiloint2double((int)w.w, (int)w.z);
-        } else {
-            e = bl_ring_load(bd, (head - 1 - a) & (BL_HB - 1), seat);
+    if constexpr (WHOLE) {
+        // BL_RING_GROUP entries per round trip, summed in the order of their ages with the operations of the loop below, as
+        // far as the handle's largest horizon: behind it no filter records anything.  The bound is the handle's, not the lane's: the loop is the
+        // wave's.  A lane asks for entries beyond its own history, and the last group for ages at and beyond the bound --
+        // every position lies in the ring, whatever it holds -- and records nothing of them.
+        // (the bound and the count are said to be uniform, readfirstlane: the compiler took both through vector registers
+        // -- the count is converted to float64 below -- and made the loop an exec region of its own, scalar pairs that the
+        // steady frame then spilled; the conversion gets a copy of the count)
+        const int end = __builtin_amdgcn_readfirstlane(min(max(n0, max(n1, n2)), BL_HB - 1));
+        // (a window longer than the ring holds is never recorded, as below: the last group's ages may reach it)
+        const int rec[BL_NF] = {lim[0] > end ? -1 : lim[0], lim[1] > end ? -1 : lim[1], lim[2] > end ? -1 : lim[2]};
+        for (int a0 = 0; a0 < end; a0 = __builtin_amdgcn_readfirstlane(a0 + BL_RING_GROUP)) {
+            int a0v = a0;
+            asm volatile("" : "+v"(a0v));
+            const double2 *at[BL_RING_GROUP];
+            bl_u32x4 w[BL_RING_GROUP];
+#pragma unroll
+            for (int k = 0; k < BL_RING_GROUP; ++k)
+                at[k] = bd.ring + (size_t)((head - 1 - a0 - k) & (BL_HB - 1)) * bd.seat_cap + seat;
+            bl_ring_load16_group(at, w);
+#pragma unroll
+            for (int k = 0; k < BL_RING_GROUP; ++k) {
+                const int a = a0 + k;
+                const double ex = __hiloint2double((int)w[k].y, (int)w[k].x), ey = __hiloint2double((int)w[k].w, (int)w[k].z);
+                if (a < S.len) {      // (at and beyond the bound as well: nothing records those sums)
+                    s0x = s0x + ex;
+                    s0y = s0y + ey;
+                    s1x = __builtin_fma((double)(a0v + k), ex, s1x);
+                    s1y = __builtin_fma((double)(a0v + k), ey, s1y);
+                }
+#pragma unroll
+                for (int f = 0; f < BL_NF; ++f)
+                    if (a + 1 == rec[f]) { S.s0x[f] = s0x; S.s1x[f] = s1x; S.s0y[f] = s0y; S.s1y[f] = s1y; }
+            }
         }
+        return;
+    }
+    for (int a = 0; a < BL_HB - 1; ++a) {
+        const double2 e = bl_ring_load(bd, (head - 1 - a) & (BL_HB - 1), seat);
         if (a < S.len) {
             s0x = s0x + e.x;
             s0y = s0y + e.y;
@@ -944,8 +991,18 @@ __device__ unsigned long long g_bcounts[BL_WAVES][BL_COUNTS];
 __device__ unsigned long long g_bseats[2];                 // the launch's frames that gave up track waves, tracks moved in them
 __device__ unsigned long long g_bwaves[BL_WAVES + 1];      // the launch's frames by the track waves they ran on (0 .. BL_WAVES)
 #define BLCOUNT(k, cond) do { const unsigned long long b_ = __ballot(cond); if (lane == 0 && b_) g_bcounts[wave][k] += 1; } while (0)
+// (the refresh of the window sums, an array of its own as well: per wave 0, 1 the block's first and last instruction in the
+// stamped frame, taken around the block by every wave of a refresh frame -- a wave without a live track passes it at once;
+// 2, 3 the head and the end of launch frame YSMR_BL_STEADY, a steady frame of the same launch to set the refresh frame
+// against)
+__device__ unsigned long long g_brefresh[BL_WAVES][4];
+#ifndef YSMR_BL_STEADY
+#define YSMR_BL_STEADY 40
+#endif
+#define BLSTAMP_AT(cond, k) do { if ((cond) && lane == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); g_brefresh[wave][k] = t_; } } while (0)
 #else
 #define BLSTAMP(k) do {} while (0)
+#define BLSTAMP_AT(cond, k) do {} while (0)
 #endif
 
 // The kernel's arguments as ONE structure: the kernel argument segment then IS this structure, and an argument that one
@@ -1208,6 +1265,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         const int kn = kc == 2 ? 0 : kc + 1, ks = 3 - kc - kn;      // the tables of frame f + 1, and of f + 2 = f - 1 (the third of 0, 1, 2)
         const int m = __builtin_amdgcn_readfirstlane(mv_cur);
         BLSTAMP(0);
+        BLSTAMP_AT(f == YSMR_BL_STEADY, 2);
 #ifdef YSMR_STAMPS
         if (f == 0 && lane == 0)
             for (int k = 0; k < BL_COUNTS; ++k) g_bcounts[wave][k] = 0;
@@ -1329,6 +1387,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
 #ifdef YSMR_STAMPS
         if (tid == 0) atomicAdd(&g_bwaves[helpers_from], 1ull);      // (no return value: nothing in the frame waits for a load)
 #endif
+        BLSTAMP_AT(f == YSMR_BL_FRAME && ((frame0 + f) & (BL_REFRESH - 1)) == 0, 0);
         if (((frame0 + f) & (BL_REFRESH - 1)) == 0 && S.alive && t.use_gsff) {     // (uniform but for `alive`: see bl_sums_from_ring)
             // (the lane's own ring stores of the frame before are complete, and nothing of the ring is left outstanding
             // in the compiler's books: it would otherwise wait for vmcnt(0) -- the row stores -- in the search of every frame)
@@ -1340,6 +1399,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
             bl_sums_from_ring<true>(S, bd, tid, head, kh->hz[0], h1 == 0x7FFFFFFF ? 0 : h1, h2 == 0x7FFFFFFF ? 0 : h2);
             bl_wait_vmem();
         }
+        BLSTAMP_AT(f == YSMR_BL_FRAME && ((frame0 + f) & (BL_REFRESH - 1)) == 0, 1);
         // ---- each track proposes its nearest detection (tracker.py:151-163)
         const bool propose = S.alive && m > 0;
         const BlGridView gv = bl_grid_view(buf_off(par), m, hdr_cur);
@@ -1635,6 +1695,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         // scripts/k_batch_census.py ends the filter bank's phase at its last float64 instruction / the ring store)
         __builtin_amdgcn_sched_barrier(0);
         BLSTAMP(7);
+        BLSTAMP_AT(f == YSMR_BL_STEADY, 3);
         d_prev = d_cur; d_cur = d_total;
         kc = kn;
         head = (head + 1) & (BL_HB - 1);
