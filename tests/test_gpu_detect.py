@@ -128,6 +128,37 @@ def test_threshold_matrix_pipe_distance(torch_cuda, oracle):
             assert np.array_equal(got, ref), f"{args} variant {variant}: " + _mismatch_report(got, ref)
 
 
+@pytest.mark.parametrize("name", [
+    "thr_h17_w64", "thr_h18_w64", "thr_h18_w60", "thr_h2_w16", "thr_h1_w16", "thr_h5_w12", "thr_h5_w16", "thr_gap_0", "thr_gap_1",
+    "thr_gap_127", "thr_gap_128", "thr_gap_127_v1", "thr_gap_128_v1", "thr_gap_128_mfma", "thr_mfma_b8_h18_w64", "thr_mfma_b8_h32_w64",
+    "thr_mfma_b8_h48_w1236", "thr_strip_b8_small", "thr_strip_b8_h128_w16"])
+def test_threshold_on_both_sides_of_every_kernel_choice(torch_cuda, oracle, name):
+    """The rows of tests/detect_plan_cases.py that sit beside a rule of csrc/detect_plan.h's threshold_plan and that no other
+    test here runs: the matrix-pipe kernel's smallest frame (18 x 64) against 17 rows and 60 columns, the strip kernel's
+    (2 x 16) against one row and twelve columns, two levels that are equal, one, 127 and 128 apart, and -- with 8 frames --
+    workgroups that are and are not dealt to the XCDs.  Every byte of every frame against the oracle, both polarities."""
+    import detect_plan_cases as dc
+    torch = torch_cuda
+    from ysmr_amd import _lib
+    (batch, h, w, channels, t_low, t_high, use_high, flavour, variant, thr_blocks, seg_h, _lds), = [a for k, n, a in dc.ROWS if n == name]
+    assert channels == 1 and thr_blocks == 0 and seg_h == 0 and batch in (3, 8)
+    rng = np.random.default_rng(batch * 1000003 + h * 10007 + w)
+    frames = rng.integers(0, 256, (batch, h, w), dtype=np.uint8)
+    frames[1] = (rng.normal(40, 2, (h, w))).round().clip(0, 255).astype(np.uint8)
+    frames[1, ::3, ::5] = 200
+    dev = torch.from_numpy(frames).cuda()
+    cls = torch.empty((batch, h, w), dtype=torch.uint8, device="cuda")
+    for inv in (1, 0):
+        cls.fill_(0xEE)
+        rc = _lib.lib().ysmr_threshold_batch_variant(_lib.stream_ptr(dev.device), dev.data_ptr(), batch, h, w, 1, inv, t_low, t_high, use_high,
+                                                     cls.data_ptr(), flavour, variant)
+        _lib.check(rc, "ysmr_threshold_batch_variant")
+        torch.cuda.synchronize()
+        got = cls.cpu().numpy()
+        ref = np.stack([oracle.classify(b, oracle.adaptive_mean(b), inv, t_low, t_high, use_high) for b in map(oracle.blur3, frames)])
+        assert np.array_equal(got, ref), f"{name} inv {inv}: " + _mismatch_report(got, ref)
+
+
 def _detect_all(torch, det, dev):
     r = det.detect(dev)
     torch.cuda.synchronize()

@@ -1,6 +1,7 @@
 // Shared helpers for libysmr_hip.so (host side).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdint>
@@ -21,6 +22,21 @@ int fail(int code, const char *fmt, ...);
     } while (0)
 
 #define YSMR_LAUNCH_CHECK() YSMR_HIP_CHECK(hipGetLastError())
+
+// batch, height, width and max_det positive, 1 or 3 channels, the limits of 32-bit pixel indices (detect_plan.h:
+// check_geometry): YSMR_OK, or YSMR_ERR_ARG with the message set (the mean-gray branch's does not name max_det)
+int check_geometry(int batch, int H, int W, int channels, int max_det, bool names_max_det = true);
+// the largest detection table the one-launch link takes (tracker_plan.h: FUSED_MAX_DET; track.hip)
+int fused_max_det();
+
+// One kernel launch; with an event given, the dispatch itself updates the two (hipExtLaunchKernelGGL).
+template <class... Params, class... Args>
+inline void launch(void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, hipEvent_t ev_start,
+                   hipEvent_t ev_stop, const Args &...args)
+{
+    if (ev_start || ev_stop) hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, stream, ev_start, ev_stop, 0u, args...);
+    else hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+}
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

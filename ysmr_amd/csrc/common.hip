@@ -1,5 +1,6 @@
 // Error reporting shared by the C ABI entry points.
 #include "common.h"
+#include "detect_plan.h"
 #include <cstring>
 
 namespace ysmr {
@@ -17,6 +18,20 @@ int fail(int code, const char *fmt, ...)
     vsnprintf(error_buffer(), 512, fmt, ap);
     va_end(ap);
     return code;
+}
+
+int check_geometry(int batch, int H, int W, int channels, int max_det, bool names_max_det)
+{
+    switch (detect_plan::check_geometry(batch, H, W, channels, max_det)) {
+    case detect_plan::Bad::none: break;
+    case detect_plan::Bad::positive:
+        if (!names_max_det) return fail(YSMR_ERR_ARG, "batch, height, width must be positive (got %d, %d, %d)", batch, H, W);
+        return fail(YSMR_ERR_ARG, "batch, height, width, max_det must be positive (got %d, %d, %d, %d)", batch, H, W, max_det);
+    case detect_plan::Bad::channels: return fail(YSMR_ERR_ARG, "channels must be 1 (gray) or 3 (BGR), got %d", channels);
+    case detect_plan::Bad::too_large:
+        return fail(YSMR_ERR_ARG, "batch too large (height and width are limited to 16384, batch*height*width to 2^32 - 1)");
+    }
+    return YSMR_OK;
 }
 
 }  // namespace ysmr

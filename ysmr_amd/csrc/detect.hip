@@ -15,9 +15,8 @@
 //
 // Compiled with -ffp-contract=off: every fused multiply-add below is an explicit fmaf().
 #include "common.h"
+#include "detect_plan.h"
 #include "thr_mfma.h"
-#include "tracker_plan.h"      // FUSED_MAX_DET
-#include <hip/hip_ext.h>
 #include <atomic>
 #include <cfloat>
 #include <cmath>
@@ -36,10 +35,11 @@ extern "C" int ysmr_debug_read_det_ring(unsigned long long *out, unsigned int *n
 
 namespace {
 
+using namespace detect_plan;      // the constants host and kernels share; the host's decisions (the end of this file)
+
 // ------------------------------------------------------------------------------------------
-// k_threshold: a1-a3
+// k_threshold: a1-a3 (TW x TH: the output tile per 256-thread block)
 // ------------------------------------------------------------------------------------------
-constexpr int TW = 64, TH = 32;            // output tile per 256-thread block
 constexpr int GW = TW + 12, GH = TH + 12;  // gray halo   (blur 1 + gaussian 5 on each side)
 constexpr int BW = TW + 10, BH = TH + 10;  // blurred halo
 
@@ -139,9 +139,6 @@ __global__ __launch_bounds__(256) void k_threshold(const uint8_t *__restrict__ f
 //   -> symmetric column filter, round-half-even, SWAR compare, 4 class bytes = one dword store.
 // Nothing but the input frame and the class map touches HBM: 1 B/px read + 1 B/px written.
 // ------------------------------------------------------------------------------------------
-constexpr int STRIP_HALO_LANES = 3;
-constexpr int STRIP_MAX_OUT_LANES = 64 - 2 * STRIP_HALO_LANES;   // 58 lanes = 232 columns
-
 struct StripParams {
     int H, W, batch;
     int out_lanes;     // output lanes per strip (<= 58), strips_x * out_lanes * 4 >= W
@@ -612,7 +609,6 @@ __global__ __launch_bounds__(256, 4) void k_threshold_strip(const uint8_t *__res
 // The smaller raster index always becomes the root, so a component's root is its first pixel.
 // ------------------------------------------------------------------------------------------
 constexpr uint32_t DEAD = 0xFFFFFFFFu;
-constexpr int NR_STRIDE = 32;   // ints between per-frame counters
 
 __device__ __forceinline__ uint32_t ld_node(const uint32_t *L, uint32_t i)
 {
@@ -723,8 +719,6 @@ struct PixelList {
     uint32_t cap;      // entries the list can hold
 };
 
-constexpr int SPARSE_BLOCKS = 768;  // resident grid of the list-driven passes (grid-stride over the list)
-
 // The passes are bound by chains of dependent L2 round trips (union-find), so they want many
 // short threads: one lane per pixel, grid-stride.
 // (nb: the number of blocks that take part, see k_residue)
@@ -770,7 +764,6 @@ struct CompTables {
 // (The status words are zeroed here.  The per-call counters are left at zero by k_compact, the last kernel of a
 // call, which also keeps the component counts for this kernel (prev_n) and vouches for the buffers; k_windows,
 // the next launch, marks the header invalid until then, so a chain that was cut short is followed by a full clear.)
-constexpr int CLEAR_BLOCKS = 512;
 // k_windows also CLEARS (round 5, last hours): the previous call's label map and mask are zeroed by the wave that works on a core
 // -- the pixels that call may have written (one word per core and row, left in the workspace by k_windows itself) and this one
 // will not -- instead of by k_clear beforehand (which dirtied the same ~1.45 M lines k_windows dirties again, and had them
@@ -895,24 +888,8 @@ __global__ __launch_bounds__(256) void k_clear(PixelList pl, CompTables t, uint8
 // The class bytes of a macro-tile of 4 x 4 cores are turned into row masks once, in LDS (v_dot4_u32_u8 gathers
 // the class bit of four pixels), and read by the 16 windows of the tile.
 // ------------------------------------------------------------------------------------------
-constexpr int WIN_CORE = 32, WIN_MARGIN = 16;
-#ifndef WIN_GROUP_N
-#define WIN_GROUP_N 8
-#endif
-constexpr int WIN_GROUP = WIN_GROUP_N;                           // cores per work item, side by side (4, or 8: round 5)
+constexpr int WIN_MARGIN = 16;                                   // (WIN_CORE, WIN_GROUP: detect_plan.h)
 constexpr int WIN_HALVES = 2 * (WIN_GROUP + 1);                  // 16-pixel half-words per staged row (5 dwords, odd: lanes = rows hit 32 banks)
-// Resident grid: 4 blocks per CU.  The kernel's own time hardly depends on it (1536 .. 2560 blocks: 62 .. 66 us), but
-// every block holds 10 KB of LDS, and with 8 per CU only one of k_frame's 59 KB blocks fits next to them
-// (scripts/sweep_e2e_blocks.sh: end to end 83.7 k frames/s with 2048 blocks here and 1536 in k_geometry, 85.7 k
-// with 1024 and 512).
-#ifndef WINDOW_BLOCKS_N
-#define WINDOW_BLOCKS_N 1024
-#endif
-constexpr int WINDOW_BLOCKS = WINDOW_BLOCKS_N;
-#ifndef WINDOW_BLOCKS_FREE_N
-#define WINDOW_BLOCKS_FREE_N 8192
-#endif
-constexpr int WINDOW_BLOCKS_FREE = WINDOW_BLOCKS_FREE_N;   // k_windows' grid where no per-frame link kernel runs beside it (components_batch)
 
 __device__ __forceinline__ uint64_t row_above(uint64_t v)   // lane r: the mask of lane r-1 (0 into lane 0)
 {
@@ -1208,9 +1185,10 @@ __global__ __launch_bounds__(256) void k_windows(uint8_t *__restrict__ cls, uint
     __shared__ __attribute__((aligned(8))) uint16_t s_bits[4][2][CHUNKS];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int H = g.H, W = g.W;
-    constexpr int SPAN = WIN_GROUP * WIN_CORE;   // 128
-    const int groups_x = (W + SPAN - 1) / SPAN, rows_y = (H + WIN_CORE - 1) / WIN_CORE;
-    const long long per_frame = (long long)groups_x * rows_y, items = per_frame * batch;
+    constexpr int SPAN = WIN_GROUP * WIN_CORE;   // 256
+    const WinItems wi = win_items(batch, H, W);
+    const int groups_x = wi.groups_x;
+    const long long per_frame = wi.per_frame, items = wi.items;
     uint16_t *st = s_bits[wave][0], *sm = s_bits[wave][1];
     // Workgroups b and b + 8 run on the same XCD (as in k_threshold_strip): every XCD works through whole frames
     // -- the frames it thresholded, if the batch is a multiple of 8 -- or else through one contiguous eighth of the
@@ -1485,10 +1463,8 @@ __device__ __forceinline__ void pass_flatten(const uint8_t *__restrict__ cls, ui
 // lanes share a root and split the comparisons.  A component takes its box and Euler number along to its rank
 // (k_windows / pass_bbox_euler filed them under the slot the root was appended at), gets its root's label back
 // (pass_tag_roots), and is queued for nested_component if it has holes.
-constexpr int RANK_THREADS = 1024;
 constexpr int RANK_BANDS = 2048;      // bands of image rows (LDS histogram)
 constexpr int RANK_BUCKET = 8192;     // roots of a frame the banded ranking holds in LDS
-constexpr int HOLED_CAP = 4096;
 
 __global__ __launch_bounds__(RANK_THREADS) void k_rank(CompTables t, uint32_t *labels, uint32_t HW, int W, int H, int32_t *status,
                                                        WsHeader *hdr, int32_t *n_holed, int2 *holed)
@@ -1689,7 +1665,6 @@ __device__ __forceinline__ void pass_bbox_euler(const uint8_t *__restrict__ cls,
 // The union-find passes over the residue as ONE launch: usually there is no residue (every block returns at
 // once; five near-empty launches cost 25 us per batch), otherwise the passes are separated by a software grid
 // barrier (all RESIDUE_BLOCKS blocks are resident: 128 x 256 threads, no LDS to speak of).
-constexpr int RESIDUE_BLOCKS = 128;
 
 __device__ __forceinline__ bool grid_barrier(uint32_t *counter, uint32_t target, uint32_t spin_limit = 20000000u)
 {
@@ -1784,10 +1759,7 @@ __global__ __launch_bounds__(256) void k_residue(uint8_t *cls, uint32_t *labels,
 // Five grid barriers among 128 blocks were 13 of k_residue's 16 us on the bench batch.  A frame with more entries than
 // the LDS list holds reads the whole list in every pass and keeps its own; an overflowed list (dense) walks the frame.
 // Batches of fewer than eight frames keep k_residue (few workgroups would serve whole frames; from a batch of 16 4K frames on this form wins: 342 -> 310 us of labelling chain, 22.5 -> 23.2 k frames/s).
-#ifndef RESF_MIN_BATCH_N
-#define RESF_MIN_BATCH_N 8
-#endif
-constexpr int RESF_THREADS = 1024, RESF_CAP = 8192, RESF_MIN_BATCH = RESF_MIN_BATCH_N;
+constexpr int RESF_THREADS = 1024, RESF_CAP = 8192;      // (RESF_MIN_BATCH: detect_plan.h)
 __global__ __launch_bounds__(RESF_THREADS) void k_residue_frames(uint8_t *cls, uint32_t *labels, uint8_t *mask, Geo g, int batch,
                                                                  PixelList pl, CompTables t, int32_t *status)
 {
@@ -1945,7 +1917,6 @@ __device__ void nested_component(const uint32_t *__restrict__ labels, const Geo 
 // The queued components (usually a handful) are worked on by the first NEST_BLOCKS workgroups of k_geometry's launch (round 5:
 // nothing in k_geometry depends on the outcome -- k_compact drops the nested components -- and as a launch of its own,
 // between k_rank and k_geometry, this was 10-16 us of the labelling chain for a handful of dependent loads).
-constexpr int NEST_BLOCKS = 128;
 
 // ------------------------------------------------------------------------------------------
 // k_geometry: a6, a 16-lane group per component (column scan), then its lane 0 (hull, calipers)
@@ -2300,7 +2271,6 @@ __device__ void geometry_group(const uint32_t *__restrict__ labels, const Geo &g
 // loop stops at the largest component count of the batch (t.max_roots, from k_rank).  2 blocks per CU: a block
 // holds 27 KB of LDS, and six of them per CU left no room for a k_frame block (see WINDOW_BLOCKS); the benchmark
 // batch takes two rounds this way (detection alone 229 k instead of 243 k frames/s, end to end +2 %).
-constexpr int GEO_BLOCKS = 512;
 __global__ __launch_bounds__(GEO_THREADS) void k_geometry(const uint32_t *__restrict__ labels, Geo g, CompTables t,
                                                           int batch, float *det_tmp, float *arena,
                                                           uint32_t arena_floats, uint32_t *arena_used, int32_t *status,
@@ -2402,90 +2372,47 @@ __global__ __launch_bounds__(COMPACT_THREADS) void k_compact(CompTables t, const
     if (threadIdx.x == 0) det_count[f] = base;
 }
 
-Gauss11 make_gauss11()
-{
-    Gauss11 g;
-    const double sigma = 0.3 * ((11 - 1) * 0.5 - 1.0) + 0.8;
-    const double scale2x = -0.5 / (sigma * sigma);
-    double t[11], sum = 0.0;
-    for (int i = 0; i < 11; ++i) {
-        double x = i - 5.0;
-        t[i] = std::exp(scale2x * x * x);
-        sum += t[i];
-    }
-    sum = 1.0 / sum;
-    for (int i = 0; i < 11; ++i) g.k[i] = (float)(t[i] * sum);
-    return g;
-}
-
 struct Workspace {
     int32_t *nroots, *roots, *order, *bbox, *euler4, *nested, *n_holed, *max_roots, *prev_n, *bbox_tmp, *euler_tmp;
     int2 *holed;
     PixelList pixels;
-    uint32_t *arena_used, *oldbits;
+    uint32_t *arena_used, *barrier, *oldbits;
     float *det_tmp, *arena;
     uint32_t arena_floats;
-    size_t bytes;
 };
 
-Workspace carve(void *base, int batch, int H, int W, int max_det)
+// the workspace's regions (detect_plan.h: layout) on the caller's block
+Workspace carve(void *base, const Layout &l)
 {
+    auto at = [&](size_t off) { return (char *)base + off; };
     Workspace w{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = ysmr::align_up(off + bytes, 256); return (char *)base + o; };
-    size_t bm = (size_t)batch * max_det;
-    w.pixels.hdr = (WsHeader *)take(256);   // persists across calls (ysmr_detect_workspace_init zeroes it)
-    // counters first: k_clear zeroes nroots, n_holed, arena_used, max_roots in one go
-    w.nroots = (int32_t *)take(sizeof(int32_t) * ((size_t)batch * NR_STRIDE + 8));
-    w.n_holed = w.nroots + (size_t)batch * NR_STRIDE;
-    w.arena_used = (uint32_t *)(w.n_holed + 1);
-    w.max_roots = w.n_holed + 3;
-    w.prev_n = (int32_t *)take(sizeof(int32_t) * (size_t)batch);
-    w.pixels.cap = (uint32_t)(((size_t)batch * H * W + 7) / 8);
-    w.pixels.idx[0] = (uint32_t *)take(sizeof(uint32_t) * w.pixels.cap);
+    w.pixels.hdr = (WsHeader *)at(l.hdr);
+    w.nroots = (int32_t *)at(l.counters);
+    w.n_holed = w.nroots + l.n_holed;
+    w.arena_used = (uint32_t *)(w.nroots + l.arena_used);
+    w.barrier = (uint32_t *)(w.nroots + l.barrier);
+    w.max_roots = w.nroots + l.max_roots;
+    w.prev_n = (int32_t *)at(l.prev_n);
+    w.pixels.cap = l.pixel_cap;
+    w.pixels.idx[0] = (uint32_t *)at(l.pixels);
     w.pixels.idx[1] = nullptr;
-    w.holed = (int2 *)take(sizeof(int2) * HOLED_CAP);
-    w.roots = (int32_t *)take(sizeof(int32_t) * bm);
-    w.order = (int32_t *)take(sizeof(int32_t) * bm);
-    w.bbox = (int32_t *)take(sizeof(int32_t) * bm * 4);
-    w.euler4 = (int32_t *)take(sizeof(int32_t) * bm);
-    w.nested = (int32_t *)take(sizeof(int32_t) * bm);
-    w.bbox_tmp = (int32_t *)take(sizeof(int32_t) * bm * 4);
-    w.euler_tmp = (int32_t *)take(sizeof(int32_t) * bm);
-    w.det_tmp = (float *)take(sizeof(float) * bm * 5);
-    // scratch arena shared by k_geometry (hulls wider than the LDS fast path) and its nesting workgroups (windows
-    // larger than LDS): room for 16 full-width hulls per frame, and at least one full-frame window
-    size_t arena_floats = (size_t)batch * std::max<size_t>(16 * 5 * (2 * (size_t)W + 3), ((size_t)(H + 2) * (W + 2) + 3) / 4);
-    if (arena_floats > 0x7FFFFFFFull) arena_floats = 0x7FFFFFFFull;
-    w.arena_floats = (uint32_t)arena_floats;
-    w.arena = (float *)take(sizeof(float) * arena_floats);
-    // k_windows' words for the next call's clearing: per work item (WIN_GROUP cores side by side) 32 rows x WIN_GROUP words
-    {
-        constexpr int SPAN = WIN_GROUP * WIN_CORE;
-        const size_t items = (size_t)batch * ((H + WIN_CORE - 1) / WIN_CORE) * ((W + SPAN - 1) / SPAN);
-        w.oldbits = (uint32_t *)take(sizeof(uint32_t) * items * WIN_CORE * WIN_GROUP);
-    }
-    w.bytes = off;
+    w.holed = (int2 *)at(l.holed);
+    w.roots = (int32_t *)at(l.roots);
+    w.order = (int32_t *)at(l.order);
+    w.bbox = (int32_t *)at(l.bbox);
+    w.euler4 = (int32_t *)at(l.euler4);
+    w.nested = (int32_t *)at(l.nested);
+    w.bbox_tmp = (int32_t *)at(l.bbox_tmp);
+    w.euler_tmp = (int32_t *)at(l.euler_tmp);
+    w.det_tmp = (float *)at(l.det_tmp);
+    w.arena_floats = l.arena_floats;
+    w.arena = (float *)at(l.arena);
+    w.oldbits = (uint32_t *)at(l.oldbits);
     return w;
 }
 
-int check_geometry(int batch, int H, int W, int channels, int max_det)
-{
-    if (batch <= 0 || H <= 0 || W <= 0 || max_det <= 0)
-        return ysmr::fail(YSMR_ERR_ARG, "batch, height, width, max_det must be positive (got %d, %d, %d, %d)", batch, H, W, max_det);
-    if (channels != 1 && channels != 3)
-        return ysmr::fail(YSMR_ERR_ARG, "channels must be 1 (gray) or 3 (BGR), got %d", channels);
-    if (H > 16384 || W > 16384 || (size_t)batch * H * W > (1ull << 32) - 64)
-        return ysmr::fail(YSMR_ERR_ARG, "batch too large (height and width are limited to 16384, batch*height*width to 2^32 - 1)");
-    return YSMR_OK;
-}
-
-// Tuning knobs: resident grid sizes of the detection kernels and the strip kernel's segment height; values
-// <= 0 keep the defaults.  The shipped library has none (a drop-in library does not read its caller's
+// The knobs' values (detect_plan.h: Knobs).  The shipped library has none (a drop-in library does not read its caller's
 // environment); a build with EXTRA=-DYSMR_TUNING reads them once per process for the sweeps in scripts/.
-struct Knobs {
-    int seg_h, thr_blocks, collect_blocks, sparse_blocks, clear_blocks, geo_blocks;
-};
 const Knobs &knobs()
 {
 #ifdef YSMR_TUNING
@@ -2500,75 +2427,33 @@ const Knobs &knobs()
     return k;
 }
 
-// workgroups of the matrix-pipe threshold kernel under the caller's hints (0: one per compute unit, thr_mfma's own choice)
-static int threshold_workgroups(int cv_flavour)
-{
-    return (cv_flavour & YSMR_BESIDE_BATCH_LINK) ? 248 : ((cv_flavour & YSMR_BESIDE_SPLIT_LINK) ? 160 : 0);
-}
-
-
 thread_local hipEvent_t t_thr_events[2] = {nullptr, nullptr};   // ysmr_threshold_timing -> the next launch_threshold of this thread
 
-// variant: 0 = the shipped choice of kernel; 1 = strip / tile kernels only (bit-exact float32 chain for every pixel);
-// 2, 3 = the matrix-pipe kernel's diagnostic builds (thr_mfma.h)
+// the kernel detect_plan::threshold_plan chose for the launch, with the shape and grid it gave
 int launch_threshold(hipStream_t st, const uint8_t *frames, int batch, int H, int W, int channels, int inv, int t_low,
-                     int t_high, int use_high, uint8_t *cls, int cv_flavour, int variant = 0)
+                     int t_high, int use_high, uint8_t *cls, int cv_flavour, int variant)
 {
-    Gauss11 gk = make_gauss11();
+    Gauss11 gk;
+    gauss11(gk.k);
     const ysmr::GrayCoef gc = ysmr::gray_coef(cv_flavour);
     // (ysmr_threshold_timing: this call's kernel dispatch updates the caller's two events)
     const hipEvent_t ev0 = t_thr_events[0], ev1 = t_thr_events[1];
     t_thr_events[0] = t_thr_events[1] = nullptr;
-    const bool timed = ev0 || ev1;
-    if (variant != 1 && ysmr_thr::supported(H, W, channels, t_low, t_high, use_high))
-        return ysmr_thr::launch(st, frames, cls, batch, H, W, inv, t_low, t_high, use_high, gk.k,
-                                knobs().thr_blocks > 0 ? knobs().thr_blocks : threshold_workgroups(cv_flavour),
-                                variant >= 2 ? variant - 1 : 0, ev0, ev1);
-    if (variant >= 2) return ysmr::fail(YSMR_ERR_ARG, "the matrix-pipe threshold kernel does not serve this geometry");
-    const int t_gap = use_high ? (t_high > t_low ? t_high - t_low : t_low - t_high) : 0;
-    if ((W & 3) == 0 && W >= 16 && H >= 2 && t_low > -100000 && t_low < 100000 && t_high > -100000 && t_high < 100000 && t_gap <= 127) {
-        StripParams P;
-        P.H = H; P.W = W; P.batch = batch;
-        const int quads = (W + 3) / 4;
-        P.strips_x = (quads + STRIP_MAX_OUT_LANES - 1) / STRIP_MAX_OUT_LANES;
-        P.out_lanes = (quads + P.strips_x - 1) / P.strips_x;
-        int resident = 768;   // 3 blocks per CU (105 / 111 VGPRs, allocated as 112): a wave slot and 176 VGPRs per
-                              // SIMD stay free for the link kernel's waves
-        if (knobs().thr_blocks > 0) resident = knobs().thr_blocks;
-        // rows per work item: every item re-reads and re-filters 10 halo rows, so items are as tall as they can
-        // be while there is still one for every resident wave (1228x922, 64 frames: 384 strip columns x 8
-        // segments of 116 rows = 3072 items = 768 blocks x 4 waves; it was 45 rows, 2.6 items per wave); never
-        // shorter than 32 rows
-        {
-            const long long columns = (long long)batch * P.strips_x;
-            const long long segs = std::max<long long>(1, (long long)resident * 4 / columns);
-            P.seg_h = (int)std::max<long long>(32, (H + segs - 1) / segs);
-        }
-        if (knobs().seg_h > 0) P.seg_h = knobs().seg_h;
-        P.segs_y = (H + P.seg_h - 1) / P.seg_h;
-        P.inv = inv; P.t_low = t_low; P.t_high = use_high ? t_high : t_low; P.gc = gc;
-        const long long waves = (long long)batch * P.strips_x * P.segs_y;
-        long long blocks = (waves + 3) / 4;
-        if (resident > 0 && blocks > resident) blocks = resident;
-        P.by_xcd = (batch % 8 == 0 && blocks % 8 == 0) ? 1 : 0;
-        if (P.by_xcd && blocks / 8 * 4 > (long long)(batch / 8) * P.strips_x * P.segs_y)    // (no more waves than an XCD has items)
-            blocks = (((long long)(batch / 8) * P.strips_x * P.segs_y + 3) / 4) * 8;
-        if (timed) {
-            if (channels == 1) hipExtLaunchKernelGGL(k_threshold_strip<1>, dim3((unsigned)blocks), dim3(256), 0u, st, ev0, ev1, 0u, frames, cls, P, gk);
-            else hipExtLaunchKernelGGL(k_threshold_strip<3>, dim3((unsigned)blocks), dim3(256), 0u, st, ev0, ev1, 0u, frames, cls, P, gk);
-        } else if (channels == 1) hipLaunchKernelGGL(k_threshold_strip<1>, dim3((unsigned)blocks), dim3(256), 0, st, frames, cls, P, gk);
-        else hipLaunchKernelGGL(k_threshold_strip<3>, dim3((unsigned)blocks), dim3(256), 0, st, frames, cls, P, gk);
-    } else {
-        dim3 grid((W + TW - 1) / TW, (H + TH - 1) / TH, batch);
-        if (timed) {
-            if (channels == 1)
-                hipExtLaunchKernelGGL(k_threshold<1>, grid, dim3(256), 0u, st, ev0, ev1, 0u, frames, cls, H, W, gk, inv, t_low, t_high, use_high, gc);
-            else
-                hipExtLaunchKernelGGL(k_threshold<3>, grid, dim3(256), 0u, st, ev0, ev1, 0u, frames, cls, H, W, gk, inv, t_low, t_high, use_high, gc);
-        } else if (channels == 1)
-            hipLaunchKernelGGL(k_threshold<1>, grid, dim3(256), 0, st, frames, cls, H, W, gk, inv, t_low, t_high, use_high, gc);
-        else
-            hipLaunchKernelGGL(k_threshold<3>, grid, dim3(256), 0, st, frames, cls, H, W, gk, inv, t_low, t_high, use_high, gc);
+    const ThresholdPlan p = threshold_plan(batch, H, W, channels, t_low, t_high, use_high, cv_flavour, variant, knobs(), ysmr_thr::lds_bytes());
+    switch (p.kernel) {
+    case Kernel::refused: return ysmr::fail(YSMR_ERR_ARG, "the matrix-pipe threshold kernel does not serve this geometry");
+    case Kernel::mfma:
+        return ysmr_thr::launch(st, frames, cls, batch, H, W, inv, t_low, t_high, use_high, gk.k, p.mfma, p.mfma_variant, ev0, ev1);
+    case Kernel::strip: {
+        const StripShape &s = p.strip;
+        const StripParams P{H, W, batch, s.out_lanes, s.strips_x, s.seg_h, s.segs_y, inv, t_low, use_high ? t_high : t_low, s.by_xcd, gc};
+        ysmr::launch(channels == 1 ? k_threshold_strip<1> : k_threshold_strip<3>, dim3(s.blocks), dim3(256), 0, st, ev0, ev1, frames, cls, P, gk);
+        break;
+    }
+    case Kernel::tile:
+        ysmr::launch(channels == 1 ? k_threshold<1> : k_threshold<3>, dim3(p.tile_grid[0], p.tile_grid[1], p.tile_grid[2]), dim3(256), 0, st,
+                     ev0, ev1, frames, cls, H, W, gk, inv, t_low, t_high, use_high, gc);
+        break;
     }
     YSMR_LAUNCH_CHECK();
     return YSMR_OK;
@@ -2581,7 +2466,7 @@ extern "C" {
 size_t ysmr_detect_workspace_bytes(int batch, int height, int width, int max_det)
 {
     if (batch <= 0 || height <= 0 || width <= 0 || max_det <= 0) return 0;
-    return carve(nullptr, batch, height, width, max_det).bytes;
+    return layout(batch, height, width, max_det).total;
 }
 
 int ysmr_detect_workspace_init(void *stream, void *workspace_dev, size_t workspace_bytes)
@@ -2594,11 +2479,8 @@ int ysmr_detect_workspace_init(void *stream, void *workspace_dev, size_t workspa
 int ysmr_threshold_batch(void *stream, const uint8_t *frames_dev, int batch, int height, int width, int channels,
                          int inv, int t_low, int t_high, int use_high, uint8_t *cls_dev, int cv_flavour)
 {
-    if (int rc = check_geometry(batch, height, width, channels, 1)) return rc;
-    if (!frames_dev || !cls_dev) return ysmr::fail(YSMR_ERR_ARG, "frames_dev and cls_dev must not be NULL");
-    if (cv_flavour & ~YSMR_CV_FLAVOUR_MASK) return ysmr::fail(YSMR_ERR_ARG, "unknown cv_flavour bits 0x%x", cv_flavour);
-    return launch_threshold((hipStream_t)stream, frames_dev, batch, height, width, channels, inv, t_low, t_high,
-                            use_high, cls_dev, cv_flavour, (cv_flavour & YSMR_BESIDE_LINK) ? 1 : 0);
+    return ysmr_threshold_batch_variant(stream, frames_dev, batch, height, width, channels, inv, t_low, t_high, use_high, cls_dev,
+                                        cv_flavour, 0);
 }
 
 int ysmr_threshold_timing(void *start_event, void *stop_event)
@@ -2608,20 +2490,15 @@ int ysmr_threshold_timing(void *start_event, void *stop_event)
     return YSMR_OK;
 }
 
-int ysmr_threshold_workgroups(int cv_flavour)
-{
-    const int n = threshold_workgroups(cv_flavour);
-    return n > 0 ? n : 256;
-}
+int ysmr_threshold_workgroups(int cv_flavour) { return threshold_workgroups(cv_flavour); }
 
 int ysmr_threshold_batch_variant(void *stream, const uint8_t *frames_dev, int batch, int height, int width, int channels,
                                  int inv, int t_low, int t_high, int use_high, uint8_t *cls_dev, int cv_flavour, int variant)
 {
-    if (int rc = check_geometry(batch, height, width, channels, 1)) return rc;
+    if (int rc = ysmr::check_geometry(batch, height, width, channels, 1)) return rc;
     if (!frames_dev || !cls_dev) return ysmr::fail(YSMR_ERR_ARG, "frames_dev and cls_dev must not be NULL");
     if (cv_flavour & ~YSMR_CV_FLAVOUR_MASK) return ysmr::fail(YSMR_ERR_ARG, "unknown cv_flavour bits 0x%x", cv_flavour);
     if (variant < 0 || variant > 3) return ysmr::fail(YSMR_ERR_ARG, "variant must be 0..3, got %d", variant);
-    if (variant == 0 && (cv_flavour & YSMR_BESIDE_LINK)) variant = 1;
     return launch_threshold((hipStream_t)stream, frames_dev, batch, height, width, channels, inv, t_low, t_high,
                             use_high, cls_dev, cv_flavour, variant);
 }
@@ -2630,57 +2507,36 @@ int ysmr_components_batch(void *stream, int batch, int height, int width, void *
                           uint8_t *cls_dev, uint8_t *mask_dev, int32_t *labels_dev, int32_t *det_count_dev,
                           float *det_dev, int32_t *anchors_dev, int max_det, int32_t *status_dev, int cv_flavour)
 {
-    if (int rc = check_geometry(batch, height, width, 1, max_det)) return rc;
+    if (int rc = ysmr::check_geometry(batch, height, width, 1, max_det)) return rc;
     if (cv_flavour & ~YSMR_CV_FLAVOUR_MASK) return ysmr::fail(YSMR_ERR_ARG, "unknown cv_flavour bits 0x%x", cv_flavour);
     if (!cls_dev || !labels_dev || !det_count_dev || !det_dev || !status_dev || !workspace_dev)
         return ysmr::fail(YSMR_ERR_ARG, "a required device pointer is NULL");
     if (((uintptr_t)cls_dev & 15) || ((uintptr_t)labels_dev & 15) || (mask_dev && ((uintptr_t)mask_dev & 15)))
         return ysmr::fail(YSMR_ERR_ARG, "cls_dev, labels_dev and mask_dev must be 16-byte aligned");
-    Workspace w = carve(workspace_dev, batch, height, width, max_det);
-    if (workspace_bytes < w.bytes)
-        return ysmr::fail(YSMR_ERR_CAPACITY, "workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
+    const Layout l = layout(batch, height, width, max_det);
+    if (workspace_bytes < l.total)
+        return ysmr::fail(YSMR_ERR_CAPACITY, "workspace too small: %zu < %zu bytes", workspace_bytes, l.total);
+    const Workspace w = carve(workspace_dev, l);
+    const ChainPlan c = chain_plan(batch, height, width, max_det, cv_flavour, knobs(), ysmr::fused_max_det());
     hipStream_t st = (hipStream_t)stream;
     Geo g{height, width, (uint32_t)((size_t)height * width), (size_t)batch * height * width};
     uint32_t *labels = reinterpret_cast<uint32_t *>(labels_dev);
+    const dim3 tb(256);
 
-    const Knobs &kn = knobs();
-    // (the LDS reserve matters to k_frame, the one-launch link, which tables of more than FUSED_MAX_DET detections do not use
-    // and which the caller announces with YSMR_BESIDE_LINK)
-    const bool small_tables = max_det <= FUSED_MAX_DET && (cv_flavour & YSMR_BESIDE_LINK);
-    // k_windows' grid.  Beside the per-frame link kernels (one-launch or split) it stays a RESIDENT grid that leaves them their LDS
-    // and wave slots.  Beside the batch link -- one workgroup that has long been seated -- or with no link at all, a wave per work item
-    // and the dispatcher hands the workgroups out as units become free: the work items differ (a core with twenty islands, a core
-    // with none), and 2048 resident workgroups with 4.4 items per wave ended as late as the unluckiest of them (round 5, last hours:
-    // 293 -> 267-270 us of labelling chain per 256 frames with 7168-8192 workgroups, scripts/sweep_window_blocks.sh; the link's
-    // time does not change)
-    const bool per_frame_link = (cv_flavour & (YSMR_BESIDE_LINK | YSMR_BESIDE_SPLIT_LINK)) != 0;
-    const unsigned window_blocks = kn.collect_blocks > 0 ? (unsigned)kn.collect_blocks
-                                   : (unsigned)(small_tables ? WINDOW_BLOCKS : (per_frame_link ? 2 * WINDOW_BLOCKS : WINDOW_BLOCKS_FREE));
-    const unsigned sparse_blocks = kn.sparse_blocks > 0 ? (unsigned)kn.sparse_blocks : (unsigned)SPARSE_BLOCKS;
-    const unsigned clear_blocks = kn.clear_blocks > 0 ? (unsigned)kn.clear_blocks : (unsigned)CLEAR_BLOCKS;
-    const unsigned geo_blocks = kn.geo_blocks > 0 ? (unsigned)kn.geo_blocks : (unsigned)(small_tables ? GEO_BLOCKS : 3 * GEO_BLOCKS);
     CompTables t{w.nroots, w.roots, w.order, w.bbox, w.euler4, w.nested, w.max_roots, w.prev_n, w.bbox_tmp, w.euler_tmp, max_det};
-    hipLaunchKernelGGL(k_clear, dim3(clear_blocks), dim3(256), 0, st, w.pixels, t, reinterpret_cast<uint8_t *>(labels), mask_dev,
-                       g.total, batch * NR_STRIDE + 8, status_dev, batch, height, width);
-    const dim3 sg(sparse_blocks), tb(256);
-    {
-        constexpr int SPAN = WIN_GROUP * WIN_CORE;
-        const long long items = (long long)batch * ((height + WIN_CORE - 1) / WIN_CORE) * ((width + SPAN - 1) / SPAN);
-        long long wblocks = std::min<long long>((items + 3) / 4, window_blocks);
-        if (wblocks >= 8) wblocks &= ~7ll;   // (a multiple of 8: the kernel deals its items to the XCDs)
-        hipLaunchKernelGGL(k_windows, dim3((unsigned)wblocks), tb, 0, st, cls_dev, labels, mask_dev, g,
-                           batch, w.pixels, t, w.oldbits);
-    }
-    if (batch >= RESF_MIN_BATCH)
-        hipLaunchKernelGGL(k_residue_frames, dim3(batch), dim3(RESF_THREADS), 0, st, cls_dev, labels, mask_dev, g, batch, w.pixels, t,
+    hipLaunchKernelGGL(k_clear, dim3(c.clear), tb, 0, st, w.pixels, t, reinterpret_cast<uint8_t *>(labels), mask_dev,
+                       g.total, l.n_counters, status_dev, batch, height, width);
+    hipLaunchKernelGGL(k_windows, dim3(c.windows), tb, 0, st, cls_dev, labels, mask_dev, g, batch, w.pixels, t, w.oldbits);
+    if (c.residue_frames)
+        hipLaunchKernelGGL(k_residue_frames, dim3(c.residue), dim3(RESF_THREADS), 0, st, cls_dev, labels, mask_dev, g, batch, w.pixels, t,
                            status_dev);
     else
-        hipLaunchKernelGGL(k_residue, dim3(RESIDUE_BLOCKS), tb, 0, st, cls_dev, labels, mask_dev, g, batch, w.pixels, t, w.arena_used + 1,
+        hipLaunchKernelGGL(k_residue, dim3(c.residue), tb, 0, st, cls_dev, labels, mask_dev, g, batch, w.pixels, t, w.barrier,
                            status_dev);
     YSMR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_rank, dim3(batch, (max_det + RANK_THREADS / 4 - 1) / (RANK_THREADS / 4) < 32 ? (max_det + RANK_THREADS / 4 - 1) / (RANK_THREADS / 4) : 32), dim3(RANK_THREADS), 0, st, t, labels, g.HW,
+    hipLaunchKernelGGL(k_rank, dim3(c.rank_x, c.rank_y), dim3(RANK_THREADS), 0, st, t, labels, g.HW,
                        width, height, status_dev, w.pixels.hdr, w.n_holed, w.holed);
-    hipLaunchKernelGGL(k_geometry, dim3(geo_blocks + NEST_BLOCKS), dim3(GEO_THREADS), 0, st,
+    hipLaunchKernelGGL(k_geometry, dim3(c.geometry), dim3(GEO_THREADS), 0, st,
                        labels, g, t, batch, w.det_tmp, w.arena, w.arena_floats, w.arena_used, status_dev, w.n_holed, w.holed);
     hipLaunchKernelGGL(k_compact, dim3(batch), dim3(COMPACT_THREADS), 0, st, t, w.det_tmp, det_dev, det_count_dev, anchors_dev, w.pixels,
                        reinterpret_cast<const uint8_t *>(labels), mask_dev, g.total, batch, height, width,

@@ -11,12 +11,12 @@
 // keeps every component, as the reference does in this branch (no binary_propagation).
 // All grids are resident-sized and stride over their work (see detect.hip on why).
 #include "common.h"
+#include "detect_plan.h"
 #include <cmath>
 
 namespace {
 
-constexpr int MG_BLOCKS = 1024;
-constexpr int LEVEL_SEG = 32;      // output rows per thread item of k_level_threshold
+using detect_plan::LEVEL_SEG;      // output rows per thread item of k_level_threshold
 constexpr int LEVEL_PF = 4;        // rows in flight per thread
 
 __device__ __forceinline__ int reflect101(int i, int n)
@@ -305,7 +305,6 @@ __global__ __launch_bounds__(256) void k_level_threshold(const uint8_t *__restri
 // (k_level_threshold above issues three loads per 4 pixels and is bound by the texture path.)
 // ------------------------------------------------------------------------------------------
 constexpr int LSTRIP_PF = 8;   // rows in flight per lane: the kernel is a stream, it needs ~6 MB in flight to cover the HBM latency
-constexpr int LSTRIP_OUT_LANES = 62;
 
 struct LevelStrip {
     int H, W, batch, out_lanes, strips_x, seg_h, segs_y, inv;
@@ -435,11 +434,7 @@ int ysmr_mean_threshold_batch(void *stream, const uint8_t *frames_dev, int batch
 {
     if (cv_flavour & ~YSMR_CV_FLAVOUR_MASK) return ysmr::fail(YSMR_ERR_ARG, "unknown cv_flavour bits 0x%x", cv_flavour);
     const ysmr::GrayCoef gc = ysmr::gray_coef(cv_flavour);
-    if (batch <= 0 || height <= 0 || width <= 0)
-        return ysmr::fail(YSMR_ERR_ARG, "batch, height, width must be positive (got %d, %d, %d)", batch, height, width);
-    if (channels != 1 && channels != 3) return ysmr::fail(YSMR_ERR_ARG, "channels must be 1 (gray) or 3 (BGR), got %d", channels);
-    if (height > 16384 || width > 16384 || (size_t)batch * height * width > (1ull << 32) - 64)
-        return ysmr::fail(YSMR_ERR_ARG, "batch too large (height and width are limited to 16384, batch*height*width to 2^32 - 1)");
+    if (int rc = ysmr::check_geometry(batch, height, width, channels, 1, false)) return rc;
     if (window < 1) return ysmr::fail(YSMR_ERR_ARG, "window must be >= 1 (got %d)", window);
     if (!frames_dev || !state_dev || !stats_dev || !levels_dev || !cls_dev)
         return ysmr::fail(YSMR_ERR_ARG, "a required device pointer is NULL");
@@ -448,47 +443,20 @@ int ysmr_mean_threshold_batch(void *stream, const uint8_t *frames_dev, int batch
     hipStream_t st = (hipStream_t)stream;
     const uint32_t HW = (uint32_t)height * (uint32_t)width;
     YSMR_HIP_CHECK(hipMemsetAsync(stats_dev, 0, sizeof(double) * 4 * (size_t)batch, st));
-    // k_gray_sums: enough parts per frame to fill the resident grid, each at least 4096 pixels
-    int parts = (MG_BLOCKS + batch - 1) / batch;
-    const int max_parts = (int)((HW + 4095u) / 4096u);
-    parts = parts < 1 ? 1 : (parts > max_parts ? max_parts : parts);
-    const long long sum_items = (long long)batch * parts;
-    const unsigned sum_blocks = (unsigned)(sum_items < MG_BLOCKS ? sum_items : MG_BLOCKS);
+    const detect_plan::MeanPlan m = detect_plan::mean_plan(batch, height, width, (((uintptr_t)cls_dev | (uintptr_t)frames_dev) & 3) == 0);
     unsigned long long *sums = reinterpret_cast<unsigned long long *>(stats_dev);
-    if (channels == 1) hipLaunchKernelGGL(k_gray_sums<1>, dim3(sum_blocks), dim3(256), 0, st, frames_dev, HW, batch, parts, sums, 4, gc);
-    else hipLaunchKernelGGL(k_gray_sums<3>, dim3(sum_blocks), dim3(256), 0, st, frames_dev, HW, batch, parts, sums, 4, gc);
+    hipLaunchKernelGGL(channels == 1 ? k_gray_sums<1> : k_gray_sums<3>, dim3(m.sum_blocks), dim3(256), 0, st, frames_dev, HW, batch, m.parts,
+                       sums, 4, gc);
     LevelState ls{reinterpret_cast<double *>(state_dev), reinterpret_cast<long long *>(reinterpret_cast<double *>(state_dev) + window)};
     hipLaunchKernelGGL(k_mean_levels, dim3(1), dim3(256), 0, st, stats_dev, batch, (double)HW, inv, offset, window, ls, levels_dev);
-    if ((width & 3) == 0 && width >= 8 && (((uintptr_t)cls_dev | (uintptr_t)frames_dev) & 3) == 0) {
-        LevelStrip P;
-        P.H = height; P.W = width; P.batch = batch; P.inv = inv;
-        const int quads = width / 4;
-        P.strips_x = (quads + LSTRIP_OUT_LANES - 1) / LSTRIP_OUT_LANES;
-        P.out_lanes = (quads + P.strips_x - 1) / P.strips_x;
-        // rows per item: the tallest segment <= 64 rows for which the items fill the resident waves a whole
-        // number of times (a last, nearly empty round costs as much as a full one)
-        const int resident = 768;            // 3 blocks per CU, as k_threshold_strip
-        const long long columns = (long long)batch * P.strips_x;
-        P.seg_h = 32;
-        for (int k = 1; k <= 16; ++k) {
-            const long long segs = (long long)k * resident * 4 / columns;
-            if (segs < 1) continue;
-            const int h = (int)((height + segs - 1) / segs);
-            if (h <= 64) { P.seg_h = h < 8 ? 8 : h; break; }
-        }
-        P.segs_y = (height + P.seg_h - 1) / P.seg_h;
-        const long long waves = columns * P.segs_y;
-        const long long want = (waves + 3) / 4;
-        const unsigned blocks = (unsigned)(want < resident ? want : resident);
-        if (channels == 1) hipLaunchKernelGGL(k_level_strip<1>, dim3(blocks), dim3(256), 0, st, frames_dev, cls_dev, P, levels_dev, gc);
-        else hipLaunchKernelGGL(k_level_strip<3>, dim3(blocks), dim3(256), 0, st, frames_dev, cls_dev, P, levels_dev, gc);
+    if (m.strip) {
+        const LevelStrip P{height, width, batch, m.level.out_lanes, m.level.strips_x, m.level.seg_h, m.level.segs_y, inv};
+        hipLaunchKernelGGL(channels == 1 ? k_level_strip<1> : k_level_strip<3>, dim3(m.level.blocks), dim3(256), 0, st, frames_dev, cls_dev, P,
+                           levels_dev, gc);
     } else {
-        LevelGeo G{height, width, batch, (width + 3) / 4, (height + LEVEL_SEG - 1) / LEVEL_SEG, inv};
-        const long long thr_items = (long long)G.groups_x * G.segs_y * batch;
-        const long long want = (thr_items + 255) / 256;
-        const unsigned thr_blocks = (unsigned)(want < MG_BLOCKS ? want : MG_BLOCKS);
-        if (channels == 1) hipLaunchKernelGGL(k_level_threshold<1>, dim3(thr_blocks), dim3(256), 0, st, frames_dev, cls_dev, G, levels_dev, gc);
-        else hipLaunchKernelGGL(k_level_threshold<3>, dim3(thr_blocks), dim3(256), 0, st, frames_dev, cls_dev, G, levels_dev, gc);
+        const LevelGeo G{height, width, batch, m.groups_x, m.segs_y, inv};
+        hipLaunchKernelGGL(channels == 1 ? k_level_threshold<1> : k_level_threshold<3>, dim3(m.thr_blocks), dim3(256), 0, st, frames_dev,
+                           cls_dev, G, levels_dev, gc);
     }
     YSMR_LAUNCH_CHECK();
     return YSMR_OK;

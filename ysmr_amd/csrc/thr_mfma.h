@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "detect_plan.h"
 
 namespace ysmr_thr {
 
@@ -18,14 +19,15 @@ struct Params {
     float kw[6];           // the Gaussian's distinct weights k[0..5] (k[i] == k[10 - i]), cv2's float32 values
 };
 
-// geometry / arguments the kernel serves (everything else stays on k_threshold_strip / k_threshold)
-bool supported(int H, int W, int channels, int t_low, int t_high, int use_high);
+// the kernel's LDS, of which detect_plan::threshold_plan makes the workgroups per compute unit
+size_t lds_bytes();
 
+// shape: detect_plan::threshold_plan's, for a geometry the kernel serves (detect_plan::mfma_supported)
 // variant: 0 = shipped (EPS = 1.875 / S for the largest admissible scale S: 0.048 gray levels with cv2's taps), 1 = half that
 // scale (diagnostic: twice the EPS, twice the list of undecided pixels), 2 = every pixel through the exact path (diagnostic)
 // ev_start / ev_stop (either may be null): events the dispatch itself updates (hipExtLaunchKernel)
 int launch(hipStream_t st, const uint8_t *frames, uint8_t *cls, int batch, int H, int W, int inv, int t_low, int t_high,
-           int use_high, const float *gauss11, int blocks_wanted, int variant, hipEvent_t ev_start = nullptr,
+           int use_high, const float *gauss11, const detect_plan::MfmaShape &shape, int variant, hipEvent_t ev_start = nullptr,
            hipEvent_t ev_stop = nullptr);
 
 }  // namespace ysmr_thr

@@ -6,7 +6,7 @@
 //         column pass = symmetric form), REPLICATE border
 //   m   = round-half-even(acc);  thresh = (b - m > t_low), markers = (b - m > t_high)   [INV: <=]
 // The two class bits only depend on where acc lies relative to b - t - 0.5.  This kernel evaluates
-//   v = mean - b   with |v - (acc - b)| < EPS   (a bound worked out on the host: choose_scales / walk_bound below)
+//   v = mean - b   with |v - (acc - b)| < EPS   (a bound worked out on the host: detect_plan.h, choose_scales / walk_bound)
 // on the matrix pipe and decides every pixel whose v is farther than EPS from both levels; the others (a few dozen per frame)
 // are listed and recomputed with cv2's exact float32 chain at the end of the workgroup, from the frame in global memory.
 // Results are bit for bit those of k_threshold / k_threshold_strip (detect.hip), which remain the path for BGR input and odd
@@ -46,16 +46,13 @@
 // The tile (blurred pixels - 128 as f16, a ring of two 16-row blocks) lies in LDS as four planes, one per octet of its 32 rows:
 // TM_PLANES below.
 //
-// Error bound: the comment at walk_bound() (bottom of this file): 0.0423 gray levels for cv2's sigma-2 taps with any image,
+// Error bound: the comment at walk_bound() (detect_plan.h): 0.0423 gray levels for cv2's sigma-2 taps with any image,
 // of which 0.031 is the f16 rounding of the intermediate (half an ulp at |v1| < 128); EPS = 1.875 / 39.375 = 0.0476.
 // MEASURED: tests/test_gpu_detect.py (48 cases, every geometry class, noise and synthetic video, the bench's and the 4K launch
 // shapes) byte for byte against the oracle; scripts/sim/thr_single_f16.py models the same arithmetic in numpy: worst
 // |model - real| 0.037 on the bench clip, ~35 undecided pixels per 1.13-Mpx frame (4 at round 4's EPS = 1/256).
 #include "common.h"
 #include "thr_mfma.h"
-#include <hip/hip_ext.h>
-#include <algorithm>
-#include <cmath>
 #include <cstring>
 #include <mutex>
 #include <type_traits>
@@ -83,16 +80,9 @@ constexpr bool TM_MEM_WAVE = TM_MEM_WAVE_N != 0;
 #ifndef TM_WAVES_N
 #define TM_WAVES_N 16
 #endif
-#ifndef TM_MAX_PANEL_N
-#define TM_MAX_PANEL_N 1232
-#endif
 constexpr int TM_WAVES = TM_WAVES_N, TM_THREADS = 64 * TM_WAVES;
-#ifndef TM_START_ROWS_N
-#define TM_START_ROWS_N 48
-#endif
-constexpr int TM_START_ROWS = TM_START_ROWS_N;               // what an item's start costs, in rows of the walk (swept: profiles/r04_thr_start_rows.log)
 constexpr int TM_ROWS = 16;                                  // rows per step (one MFMA tile row block)
-constexpr int TM_MAX_PANEL = TM_MAX_PANEL_N;                 // columns per panel, a multiple of 16 (1232: 77 tiles of 16)
+using detect_plan::TM_MAX_PANEL;                             // columns per panel, a multiple of 16 (detect_plan.h)
 constexpr int TM_MAX_TILES = TM_MAX_PANEL / 16;              // output tiles t: columns 16t .. 16t + 15 of the panel
 constexpr int TM_MAX_BLOCKS = TM_MAX_TILES + 1;              // tile column blocks u: columns 16u - 8 .. 16u + 7
 // blocks (and tiles) per wave: 5 -- with the memory wave, which has none: fifteen waves of five and one more for the three that share
@@ -372,7 +362,7 @@ __global__ __launch_bounds__(TM_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
     uint32_t tv[4];                   // (variant 1 is variant 0 with its register pairs exchanged: built where it is used)
     // Gaussian columns, B [k][n]: k = window row (0..15 the older tile block, 16..31 the newer), output row n is window
     // row n + 8: tap k - n - 3.  ONE f16 per tap (round 5): the taps are scaled by P.col_scale, chosen on the host so that the
-    // eleven scaled weights lie close to f16 values (the bound: launch()).
+    // eleven scaled weights lie close to f16 values (the bound: detect_plan.h).
     uint32_t tbh[4];
     // Gaussian rows, B [k][n]: the A operand is two column blocks' accumulators kept in place, halves j = 0..3 / 4..7 =
     // positions 4q + (j & 3) of one block each; variant v: the RIGHT block (u = t + 1) sits in half v.  Position i of block u
@@ -1207,141 +1197,42 @@ __global__ __launch_bounds__(TM_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
 extern "C" int ysmr_debug_read_thr_stamps(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tm_stamps), sizeof(g_tm_stamps)); }
 #endif
 
-namespace {
-
-// ---- the scales of the walk's arithmetic and its error bound (host) ------------------------------------------------
-// The walk evaluates  x = X (mean - b - theta_1), X = +-S,  with ONE f16 per tap and ONE f16 for the column-filtered value:
-//   tile          b - 128, exact integers in [-128, 127]
-//   column pass   v1 = sum_j f16(s w_j) (b_j - 128)            float32 accumulation of exact products
-//   intermediate  h = f16(v1), round to nearest                 |h - v1| <= 2^-5 while |v1| < 128
-//   row pass      x = sum_i f16(X / s  w_i) h_i + [-X theta_1 - X (b - 128)]
-// against the real number  X (sum_ij w_i w_j b_ij - b - theta_1).  In gray levels (divide by S):
-//   column taps   |sum_j (f16(s w_j) / s - w_j) (b_j - 128)|            <= 128 dc,   dc = sum_j |f16(s w_j) / s - w_j|
-//   intermediate  (1 / s) sum_i w_i |h_i - v1_i|                        <= 2^-5 / s  (needs s 128 (1 + dc) sum w < 128)
-//   row taps      |sum_i (f16(S / s w_i) / S - w_i / s) h_i|, |h_i| <= 128   <= 128 dr / s,   dr = sum_i |f16(S / s w_i) s / S - w_i|
-//   accumulation  one float32 rounding per product, all lined up: 32 x 2^-18 (column pass, partial sums below 128) plus
-//                 64 half-ulps at S x 384 (the two products of the row pass), over S
-//   cv2 itself    its float32 chain is within 22 x 2^-24 x 255 of the real mean; its taps sum to 1 within 1e-8
-// s and S are free: s is searched so that the eleven scaled weights lie close to f16 values (dc = 3.1e-5 at s = 0.9945 for
-// cv2's sigma-2 kernel, against 2.1e-4 at s = 1), S -- an f16 value itself, it is a tap of the accumulator's preset --
-// likewise, the largest whose 1.875 / S (where the bf8 conversion of x sets its exponent's top bit) covers 1.1 x the bound:
-// S = 39.375, bound 0.0423, EPS = 1.875 / S = 0.0476 gray levels
-// (scripts/sim/thr_single_f16.py is the same arithmetic in numpy, with the counts of undecided pixels it leaves).
-struct Scales { double s, S, bound; };
-
-double host_f16(double x)      // round to nearest even at 11 significant bits (normal range only: checked by walk_bound)
-{
-    if (x == 0.0) return 0.0;
-    int e;
-    const double m = std::frexp(x, &e);
-    return std::ldexp(std::nearbyint(std::ldexp(m, 11)), e - 11);
-}
-
-double taps_error(const double *w11, double scale)
-{
-    double d = 0.0;
-    for (int i = 0; i < 11; ++i) d += std::fabs(host_f16(w11[i] * scale) / scale - w11[i]);
-    return d;
-}
-
-double walk_bound(const double *w11, double s, double S)
-{
-    double sum = 0.0;
-    for (int i = 0; i < 11; ++i) sum += w11[i];
-    const double dc = taps_error(w11, s), dr = taps_error(w11, S / s);
-    if (!(s * 128.0 * (1.0 + dc) * sum < 128.0 * (1.0 - 1e-6))) return 1e30;        // the intermediate must stay below 128
-    if (S / s * w11[5] > 60000.0 || s * w11[0] < 6.2e-5 || S / s * w11[0] < 6.2e-5) return 1e30;   // taps in f16's normal range
-    const double acc = 32.0 * std::ldexp(1.0, -18) + 64.0 * std::ldexp(1.0, (int)std::floor(std::log2(S * 384.0)) - 24) / S;
-    const double cv2 = 22.0 * std::ldexp(1.0, -24) * 255.0 + std::fabs(sum - 1.0) * 255.0;
-    return 128.0 * dc + std::ldexp(1.0, -5) / s + 128.0 * dr / s + acc + cv2;
-}
-
-Scales choose_scales(const float *gauss6)
-{
-    static std::mutex mu;
-    static float key[6] = {0, 0, 0, 0, 0, 0};
-    static Scales cached{0.0, 0.0, 0.0};
-    std::lock_guard<std::mutex> lk(mu);
-    if (cached.S > 0.0 && !std::memcmp(key, gauss6, sizeof(key))) return cached;
-    double w[11];
-    for (int i = 0; i < 11; ++i) w[i] = (double)gauss6[i <= 5 ? i : 10 - i];
-    Scales best{0.0, 0.0, 0.0};
-    double best_score = 1e30;
-    for (int k = 0; k < 2000; ++k) {
-        const double s = 0.9 + 5e-5 * k;
-        if (walk_bound(w, s, 1024.0) > 1e29) continue;
-        const double score = 128.0 * taps_error(w, s) + std::ldexp(1.0, -5) / s;
-        if (score < best_score) { best_score = score; best.s = s; }
-    }
-    if (best.s > 0.0)
-        for (int k = 64 * 16; k >= 4 * 16; --k) {    // multiples of 1/16 below 64: f16 values, and so are their halves (the diagnostic variant)
-            const double S = k / 16.0, E = walk_bound(w, best.s, S);
-            if (1.1 * E <= 1.875 / S) { best.S = S; best.bound = E; break; }
-        }
-    std::memcpy(key, gauss6, sizeof(key));
-    cached = best;
-    return best;
-}
-
-}  // namespace
-
 namespace ysmr_thr {
 
-bool supported(int H, int W, int channels, int t_low, int t_high, int use_high)
-{
-    const int gap = use_high ? (t_high > t_low ? t_high - t_low : t_low - t_high) : 1;
-    return channels == 1 && (W & 3) == 0 && W >= 64 && W <= 16384 && H >= 18 && H <= 16383 && gap >= 1 &&
-           t_low > -1000 && t_low < 1000 && t_high > -1000 && t_high < 1000;
-}
+size_t lds_bytes() { return sizeof(Lds); }
 
 int launch(hipStream_t st, const uint8_t *frames, uint8_t *cls, int batch, int H, int W, int inv, int t_low, int t_high,
-           int use_high, const float *gauss11, int blocks_wanted, int variant, hipEvent_t ev_start, hipEvent_t ev_stop)
+           int use_high, const float *gauss11, const detect_plan::MfmaShape &shape, int variant, hipEvent_t ev_start, hipEvent_t ev_stop)
 {
+    // (a -DTM_MAX_PANEL_N build of this file alone: the plan was made for wider panels than this kernel's LDS holds)
+    if (shape.panel_w > TM_MAX_PANEL)
+        return ysmr::fail(YSMR_ERR_ARG, "panels of %d columns, the matrix-pipe threshold kernel was built for %d", shape.panel_w, TM_MAX_PANEL);
+    // the scale search (detect_plan.h: choose_scales) once per set of taps
+    static std::mutex mu;
+    static float key[6] = {0, 0, 0, 0, 0, 0};
+    static detect_plan::Scales cached{0.0, 0.0, 0.0};
+    detect_plan::Scales sc;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!(cached.S > 0.0 && !std::memcmp(key, gauss11, sizeof(key)))) {
+            cached = detect_plan::choose_scales(gauss11);
+            std::memcpy(key, gauss11, sizeof(key));
+        }
+        sc = cached;
+    }
+    if (!(sc.S > 0.0)) return ysmr::fail(YSMR_ERR_ARG, "the matrix-pipe threshold kernel found no admissible scale for these taps");
+    const detect_plan::LevelConsts c = detect_plan::level_consts(sc, inv, t_low, t_high, use_high, variant);
     Params P{};
     P.H = H; P.W = W; P.batch = batch;
-    P.panels = (W + TM_MAX_PANEL - 1) / TM_MAX_PANEL;
-    P.panel_w = ((W + P.panels - 1) / P.panels + 15) & ~15;
-    P.panels = (W + P.panel_w - 1) / P.panel_w;
-    // every CU full; a build whose workgroups are small enough for several per compute unit (TM_WAVES_N = 8 with narrow panels: an
-    // experiment of round 5) takes the caller's figure as compute units
-    const int per_cu = (int)((160 * 1024) / sizeof(Lds));
-    const int blocks = (blocks_wanted > 0 ? blocks_wanted : 256) * per_cu;
+    P.panels = shape.panels; P.panel_w = shape.panel_w; P.by_xcd = shape.by_xcd; P.start_rows = shape.start_rows;
     P.inv = inv; P.use_high = use_high; P.t_low = t_low; P.t_high = use_high ? t_high : t_low;
     for (int i = 0; i < 6; ++i) P.kw[i] = gauss11[i];
-    // v = mean - b.  BINARY: bit = (b - m > t) <=> v < theta = -t - 0.5;  INV: bit = (b - m <= t) <=> v > theta (ties: exact path).
-    // x = X (v - theta) with X = +S (BINARY) / -S (INV) is negative exactly where the bit is set, and |x| >= 1.875 -- where its
-    // bf8 conversion has the exponent's top bit set -- exactly when v is 1.875 / S or more away from theta: S is the largest scale
-    // whose 1.875 / S still covers the error bound of the walk's arithmetic with a tenth to spare (choose_scales: S = 39.375,
-    // EPS = 0.0476 gray levels for cv2's sigma-2 taps; variant 1, diagnostic: half that scale, twice the list).
-    // The FIRST level is the one whose clear, decided bit implies the other's: the larger theta for BINARY, the smaller for INV;
-    // a tile in which it fires nowhere is class 0 throughout and never evaluates the second.  One level: the second = the first.
-    const Scales sc = choose_scales(gauss11);
-    if (!(sc.S > 0.0)) return ysmr::fail(YSMR_ERR_ARG, "the matrix-pipe threshold kernel found no admissible scale for these taps");
-    const double S = variant == 1 ? sc.S / 2 : sc.S, X = inv ? -S : S;
-    const double th_lo = -(double)t_low - 0.5, th_hi = use_high ? -(double)t_high - 0.5 : th_lo;
-    const bool lo_first = inv ? th_lo <= th_hi : th_lo >= th_hi;
-    const double th1 = lo_first ? th_lo : th_hi, th2 = lo_first ? th_hi : th_lo;
-    P.col_scale = (float)sc.s;
-    P.row_scale = (float)(X / sc.s);
-    P.neg_x_mul = (float)-X;
-    P.k_first = (float)(-X * th1);
-    P.d2 = (float)(X * (th1 - th2));
-    P.sh1 = lo_first ? 7 : 6; P.k1 = lo_first ? 0x01010101u : 0x02020202u;
-    P.sh2 = lo_first ? 6 : 7; P.k2 = lo_first ? 0x02020202u : 0x01010101u;
-    // (no workgroup with fewer than 32 rows: an item re-filters 16 halo rows)
-    long long grid = std::max<long long>(1, std::min<long long>((long long)batch * P.panels * H / 32, blocks));
-    P.by_xcd = (batch % 8 == 0 && grid % 8 == 0) ? 1 : 0;
-    {
-        const long long groups = P.by_xcd ? 8 : 1, cols = (long long)(batch / groups) * P.panels, nb = grid / groups;
-        P.start_rows = nb % cols == 0 ? 0 : TM_START_ROWS;
-    }
-    const size_t lds = sizeof(Lds);
+    P.col_scale = c.col_scale; P.row_scale = c.row_scale;
+    P.neg_x_mul = c.neg_x_mul; P.k_first = c.k_first; P.d2 = c.d2;
+    P.sh1 = c.sh1; P.k1 = c.k1; P.sh2 = c.sh2; P.k2 = c.k2;
     auto kern = variant == 2 ? k_threshold_mfma<2> : k_threshold_mfma<0>;
-    YSMR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (ev_start || ev_stop)
-        hipExtLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(TM_THREADS), (uint32_t)lds, st, ev_start, ev_stop, 0u, frames, cls, P);
-    else
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(TM_THREADS), lds, st, frames, cls, P);
+    YSMR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Lds)));
+    ysmr::launch(kern, dim3(shape.grid), dim3(TM_THREADS), sizeof(Lds), st, ev_start, ev_stop, frames, cls, P);
     YSMR_LAUNCH_CHECK();
     return YSMR_OK;
 }

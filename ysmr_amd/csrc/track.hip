@@ -1970,6 +1970,8 @@ __global__ void k_peek_third(TrackerDev t, const double *pos3, double *third)
 
 }  // namespace
 
+int ysmr::fused_max_det() { return FUSED_MAX_DET; }      // for detection's grids beside the one-launch link (detect_plan.h: chain_plan)
+
 // One wave that waits `ticks` x 10 ns (the 100 MHz realtime counter), in front of every launch of the batch link.  In the pipeline the
 // event behind a link launch releases two things at the same instant: the NEXT link launch (same stream) and the detection of the
 // batch whose buffers that launch was reading -- the threshold kernel's 248 workgroups, one per free compute unit, 31 per XCD.  A link
