@@ -23,7 +23,9 @@ buf = (ctypes.c_ulonglong * (NW * 16))()
 # rest of the frame; one barrier)
 names = ["search + key atomic", "wait (grid block) + barrier A", "dma issue + key read + ranks, row of the frame before",
          "exact claim path", "ageing / deregistration", "registration + clear keys two frames ahead",
-         "wait vmcnt(0) + filter bank"]
+         "wait vmcnt(0)", "filter bank"]
+# (the stamps in the order a pass meets them: stamp 8 stands behind the frame's wait for vector memory, stamp 7 at the frame's end)
+ORDER = [0, 1, 2, 3, 4, 5, 6, 8, 7]
 LAST = len(names)
 # per wave over the launch's frames (g_bcounts): how often each rarely taken path ran
 count_names = ["wave-frames with a lane on the 3 x 3 block search", "lanes on the 3 x 3 block search",
@@ -31,6 +33,7 @@ count_names = ["wave-frames with a lane on the 3 x 3 block search", "lanes on th
                "frames with registration", "wave-frames refreshing the sums from the ring", "frames with deaths", "deaths",
                "frames on the exact claim path (row of wave 0)"]
 acc = []
+acc_s = []      # the same stamps of launch frame YSMR_BL_STEADY (g_bsteady)
 acc_r = []      # per rep and wave: the refresh block, the stamped frame, launch frame 40 (cycles)
 # BESIDE=1: the stamped launch runs while another stream loops over the matrix-pipe threshold kernel on 248 workgroups, as
 # in the pipeline (which phase of a frame the memory system's load stretches)
@@ -50,10 +53,17 @@ for rep in range(12 if beside else 6):
     t0 = torch.cuda.Event(enable_timing=True); t1 = torch.cuda.Event(enable_timing=True)
     t0.record(); pipe.trk.run(res1.det, res1.det_count, B, pipe.rows, pipe.row_count); t1.record()
     torch.cuda.synchronize()
+    if not hasattr(L, "ysmr_debug_read_bstamps"):      # (a plain library: the launch's time without the stamps' own cycles)
+        print(f"rep {rep}: launch pair {t0.elapsed_time(t1) * 1e3:.1f} us for {B} frames (no stamps in this library)")
+        continue
     L.ysmr_debug_read_bstamps(buf)
     full = np.array(buf[:], dtype=np.int64).reshape(NW, 16)
-    a = full[:, :LAST + 1]
+    a = full[:, ORDER]
     acc.append(a)
+    if hasattr(L, "ysmr_debug_read_bsteady"):
+        sbuf = (ctypes.c_ulonglong * (NW * 16))()
+        L.ysmr_debug_read_bsteady(sbuf)
+        acc_s.append(np.array(sbuf[:], dtype=np.int64).reshape(NW, 16)[:, ORDER])
     print("   fast path per wave:", (full[:, 11] - full[:, 0]).tolist(), " lanes left to the wave search:", full[:, 12].tolist())
     print("   over the launch's frames: lanes left to the wave search per wave", full[:, 13].tolist(), "= %.2f per frame; frames in which a wave ran it:" % (full[:, 13].sum() / B), full[:, 14].tolist())
     rt0, rt1, mt0, mt1 = int(full[0, 15]), int(full[1, 15]), int(full[2, 15]), int(full[3, 15])
@@ -82,12 +92,19 @@ for rep in range(12 if beside else 6):
         print("   refresh block per wave:", acc_r[-1][:, 0].tolist(), " its frame:", acc_r[-1][:, 1].tolist(),
               " steady frame 40:", acc_r[-1][:, 2].tolist())
     print(f"rep {rep}: launch pair {t0.elapsed_time(t1) * 1e3:.1f} us for {B} frames; frame (wave 0) {a[0, LAST] - a[0, 0]} cycles")
-a = np.mean(np.array(acc), axis=0) if beside else np.median(np.array(acc), axis=0)
-d = np.diff(a, axis=1)
-print("%-44s" % "phase (cycles of s_memtime, 100 MHz? no: shader clock)", " ".join(f"w{w:<6d}" for w in range(NW)))
-for k, n in enumerate(names):
-    print("%-44s" % n, " ".join(f"{d[w, k]:<7.0f}" for w in range(NW)))
-print("%-44s" % "frame", " ".join(f"{a[w, LAST] - a[w, 0]:<7.0f}" for w in range(NW)))
+for title, stamps in (("the stamped frame (YSMR_BL_FRAME)", acc), ("the steady frame (YSMR_BL_STEADY)", acc_s)):
+    if not stamps:
+        continue
+    a = np.mean(np.array(stamps), axis=0) if beside else np.median(np.array(stamps), axis=0)
+    d = np.diff(a, axis=1)
+    print(title)
+    print("%-44s" % "phase (cycles of s_memtime, 100 MHz? no: shader clock)", " ".join(f"w{w:<6d}" for w in range(NW)))
+    for k, n in enumerate(names):
+        print("%-44s" % n, " ".join(f"{d[w, k]:<7.0f}" for w in range(NW)))
+    print("%-44s" % "frame", " ".join(f"{a[w, LAST] - a[w, 0]:<7.0f}" for w in range(NW)))
+    # the exposed wait of the track waves (a wave without a track passes it at once), every rep: the range
+    ws = np.array(stamps)[:, :, 7] - np.array(stamps)[:, :, 6]
+    print("%-44s" % "wait vmcnt(0), min .. max over the reps", " ".join(f"{ws[:, w].min()}..{ws[:, w].max()}" for w in range(NW)))
 if acc_r:
     rr = np.array(acc_r)
     for how, fn in (("median", np.median), ("mean", np.mean), ("max", np.max)):

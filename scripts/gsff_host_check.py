@@ -39,6 +39,9 @@ struct BatchDev { double2 *ring; int seat_cap; };
 struct BlGains { double alpha[BL_NF][2], beta[BL_NF][2]; };
 static inline void bl_ring_store(const BatchDev &bd, int pos, int seat, double x, double y) { bd.ring[(size_t)pos * bd.seat_cap + seat] = make_double2(x, y); }
 static inline double2 bl_ring_load(const BatchDev &bd, int pos, int seat) { return bd.ring[(size_t)pos * bd.seat_cap + seat]; }
+// (a ring entry as bl_gsff takes it: here the two doubles; k_batch hands it the four registers of a 16-byte load)
+static inline double2 bl_entry(const double2 &e) { return e; }
+static inline void bl_entry_set(double2 &e, double x, double y) { e = make_double2(x, y); }
 '''
 
 DRIVER = r'''

@@ -274,6 +274,14 @@ def _sregs(args):
     return out
 
 
+def _vregs(args):
+    """Vector registers named in an operand string: v7, v[4:7]."""
+    out = set()
+    for m in re.finditer(r"\bv\[(\d+):(\d+)\]|\bv(\d+)\b", args):
+        out |= set(range(int(m.group(1)), int(m.group(2)) + 1)) if m.group(1) else {int(m.group(3))}
+    return out
+
+
 def pending_load_hazards(text):
     """The guard of the kernel's written-out scalar loads (batch_link.h, "Kernel arguments a phase ahead"): an s_load in
     inline assembly hands the compiler registers it believes valid at once, and the matching s_waitcnt lgkmcnt(0) stands in
@@ -284,9 +292,13 @@ def pending_load_hazards(text):
     ins = parse(text)
     bad = []
     for i, (op, args, _) in enumerate(ins):
-        if not op.startswith(("s_load_", "s_buffer_load_")):
+        # (the written-out vector loads likewise -- bl_ring_issue16, the ring entries that leave the windows: a 16-byte
+        # sc1 load is one the compiler never writes itself; its registers are nobody's up to the first vmcnt(0) wait)
+        vector = op == "global_load_dwordx4" and re.search(r"\bsc1\b", args) is not None
+        if not vector and not op.startswith(("s_load_", "s_buffer_load_")):
             continue
-        dst = _sregs(args.split(",")[0])
+        regs, done = (_vregs, r"\bvmcnt\(0\)") if vector else (_sregs, r"\blgkmcnt\(0\)")
+        dst = regs(args.split(",")[0])
         todo, seen = [i + 1], set()
         while todo:
             j = todo.pop()
@@ -294,9 +306,9 @@ def pending_load_hazards(text):
                 continue
             seen.add(j)
             o, a, tgt = ins[j]
-            if o == "s_waitcnt" and "lgkmcnt(0)" in a:
+            if o == "s_waitcnt" and re.search(done, a):
                 continue
-            if _sregs(a) & dst:
+            if regs(a) & dst:
                 bad.append((i, f"{op} {args}", j, f"{o} {a}"))
                 continue
             if o == "s_endpgm":
@@ -478,7 +490,7 @@ def main():
     print()
     print(report_round_trips(c))
     bad = pending_load_hazards(text)
-    print(f"scalar loads whose registers are touched before their lgkmcnt(0) wait, whole kernel, every path: {len(bad)}")
+    print(f"scalar loads and written-out 16-byte ring loads whose registers are touched before their wait, whole kernel, every path: {len(bad)}")
     for i, load, j, what in bad:
         print(f"  {load} (instruction {i}): {what} (instruction {j})")
     if bad:

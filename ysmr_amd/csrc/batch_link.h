@@ -450,6 +450,40 @@ __device__ __forceinline__ void bl_ring_load16_group(const double2 *const (&at)[
                  "s_waitcnt vmcnt(0)"
                  : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]) : "v"(at[0]), "v"(at[1]), "v"(at[2]) : "memory");
 }
+// (a whole entry with ONE instruction and NO wait of its own: the measurements that leave the windows in k_batch's steady
+// frame, requested in front of barrier A and taken behind the frame's one bl_wait_vmem() in front of the filter bank, by
+// bl_ring_taken16.  Between the two the compiler believes the destination registers written: were it to read, copy or
+// spill them there, it would move what the load has not delivered yet -- early-clobber, as above, keeps them off the
+// statement's own address, and THE GUARD for the stretch up to the wait is scripts/k_batch_census.py:
+// pending_load_hazards, which follows every written-out `global_load_dwordx4 ... sc1` of the listing along every path
+// to its vmcnt(0) wait, as it follows the written-out scalar loads.  The address is the seat's own entry of line 0 --
+// what the frame's ring store is addressed from, a register pair the lane holds anyway -- plus the line's bytes: with the
+// ring's base taken alone the compiler fetched it from the argument segment right in front of the first load.)
+__device__ __forceinline__ void bl_ring_issue16(const BatchDev &bd, int seat, unsigned line_at, bl_u32x4 &v)
+{
+    const char *p = reinterpret_cast<const char *>(bd.ring + seat) + line_at;
+    asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=&v"(v) : "v"(p) : "memory");
+}
+// (behind the wait: the entries are handed on as that wait left them, and nothing that reads them is scheduled above it)
+__device__ __forceinline__ void bl_ring_taken16(bl_u32x4 (&v)[BL_NF])
+{
+    static_assert(BL_NF == 3, "one operand per entry is written out below");
+    asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]));
+}
+// A ring entry as bl_gsff takes it: the two doubles, or the four registers a 16-byte load left (k_batch: the entry stays
+// in them up to the operations that use it, and the seeding of a new track writes its copies into the same four -- as
+// separate doubles the two sources met in six register moves per frame).
+__device__ __forceinline__ double2 bl_entry(const double2 &e) { return e; }
+__device__ __forceinline__ double2 bl_entry(const bl_u32x4 &v)
+{
+    return make_double2(__hiloint2double((int)v.y, (int)v.x), __hiloint2double((int)v.w, (int)v.z));
+}
+__device__ __forceinline__ void bl_entry_set(double2 &e, double x, double y) { e = make_double2(x, y); }
+__device__ __forceinline__ void bl_entry_set(bl_u32x4 &v, double x, double y)
+{
+    v.x = (uint32_t)__double2loint(x); v.y = (uint32_t)__double2hiint(x);
+    v.z = (uint32_t)__double2loint(y); v.w = (uint32_t)__double2hiint(y);
+}
 __device__ __forceinline__ void bl_ring_store(const BatchDev &bd, int pos, int seat, double x, double y)
 {
     bd.ring[(size_t)pos * bd.seat_cap + seat] = make_double2(x, y);
@@ -576,9 +610,10 @@ __device__ __forceinline__ int bl_mode_of(int grow_at, int nf, const int (&n_i)[
 // ring held, fresh says that the seat's state is not this track's, grow_at is unused.
 // tr: the tracker's arguments again, for what only the rare block and the tail need (horizons, hist_cap, lik_min) -- k_batch
 // passes the argument segment itself, so that they come with scalar loads where they are used.
-template <bool GATED, typename Args, typename Gains>
+// Entry: double2, or the registers of a 16-byte load (bl_entry, above: k_batch).
+template <bool GATED, typename Args, typename Gains, typename Entry>
 __device__ __forceinline__ void bl_gsff(BlSeat &S, const TrackerDev &t, const Args &tr, const BatchDev &bd, const Gains &g, int seat, int head,
-                                        double2 (&leave)[BL_NF], double z0, double z1, bool fresh, int &grow_at, double &o0, double &o1)
+                                        Entry (&leave)[BL_NF], double z0, double z1, bool fresh, int &grow_at, double &o0, double &o1)
 {
     const int nf = t.n_f, L = tr.hist_cap;
     const double lik_min = tr.lik_min;
@@ -601,8 +636,10 @@ __device__ __forceinline__ void bl_gsff(BlSeat &S, const TrackerDev &t, const Ar
             if (GATED) {     // what leaves a window that these copies fill is a copy; nothing leaves the others (the caller
                              // requested nothing for a lane that held no track then: leave[] is unset on entry)
 #pragma unroll
-                for (int f = 0; f < BL_NF; ++f)
-                    leave[f] = len >= n_i[f] ? make_double2(z0, z1) : make_double2(0.0, 0.0);
+                for (int f = 0; f < BL_NF; ++f) {
+                    const bool copy = len >= n_i[f];
+                    bl_entry_set(leave[f], copy ? z0 : 0.0, copy ? z1 : 0.0);
+                }
             }
         }
         bool grew = false;   // gsff.py:283-289: while len(history) >= n_i[mode]: mode += 1
@@ -626,7 +663,8 @@ __device__ __forceinline__ void bl_gsff(BlSeat &S, const TrackerDev &t, const Ar
     // append the measurement: every entry one frame older, the entry of age N - 1 leaves a full window
 #pragma unroll
     for (int f = 0; f < BL_NF; ++f) {
-        double lx = leave[f].x, ly = leave[f].y;
+        const double2 lv = bl_entry(leave[f]);
+        double lx = lv.x, ly = lv.y;
         if (!GATED) {
             const bool full = f < nf && len >= t.n_i[f];
             // (a track born in this frame: its history is copies of z, written above -- after `leave` was requested)
@@ -981,7 +1019,19 @@ __device__ unsigned long long g_bstamps[BL_WAVES][16];
 #ifndef YSMR_BL_FRAME
 #define YSMR_BL_FRAME 40
 #endif
-#define BLSTAMP(k) do { if (f == YSMR_BL_FRAME && lane == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); g_bstamps[wave][k] = t_; } } while (0)
+// (stamp 8 stands directly behind the frame's wait for vector memory, in front of the filter bank: 6 -> 8 is the exposed
+// wait, 8 -> 7 the filter bank.  g_bsteady: the same stamps of launch frame YSMR_BL_STEADY, so that a build whose stamped
+// frame is the refresh frame has a steady frame's phases of the same launch beside it.)
+__device__ unsigned long long g_bsteady[BL_WAVES][16];
+#ifndef YSMR_BL_STEADY
+#define YSMR_BL_STEADY 40
+#endif
+#define BLSTAMP(k) BLSTAMP_IN(f, k)
+// (stamp 8: the frame number through an empty asm statement, so that its test is not the test of stamp 6 -- the compiler
+// merged the two and took the wait between them into both halves of ONE branch, `lane 0 of a stamped frame` and the rest;
+// every wave still waited, but scripts/k_batch_census.py's walk saw a way round the wait in either half)
+#define BLSTAMP_OWN_TEST(k) do { int f_ = f; asm volatile("" : "+s"(f_)); BLSTAMP_IN(f_, k); } while (0)
+#define BLSTAMP_IN(f, k) do { if ((f == YSMR_BL_FRAME || f == YSMR_BL_STEADY) && lane == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); if (f == YSMR_BL_FRAME) g_bstamps[wave][k] = t_; if (f == YSMR_BL_STEADY) g_bsteady[wave][k] = t_; } } while (0)
 // per wave, over the launch's frames, how often a rarely taken path ran: 0 wave-frames with a lane on the 3 x 3 block search,
 // 1 such lanes, 2 wave-frames with a lane seeding a new track's filter bank, 3 with a lane whose filter bank grew (not new),
 // 4 frames with registration, 5 wave-frames refreshing the window sums from the ring, 6 frames with deaths, 7 deaths,
@@ -1002,6 +1052,7 @@ __device__ unsigned long long g_brefresh[BL_WAVES][4];
 #define BLSTAMP_AT(cond, k) do { if ((cond) && lane == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); g_brefresh[wave][k] = t_; } } while (0)
 #else
 #define BLSTAMP(k) do {} while (0)
+#define BLSTAMP_OWN_TEST(k) do {} while (0)
 #define BLSTAMP_AT(cond, k) do {} while (0)
 #endif
 
@@ -1493,13 +1544,15 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         // ONE exec region for the three filters: where a window is not full (a filter the handle lacks: hz = INT_MAX) the
         // lane reads the ring's line of zeros, position BL_HB, which nothing ever stores to -- a select of the position,
         // not of the value: an entry that was never written may hold anything, and bl_gsff<true> needs exactly 0.0, 0.0.
-        double2 leave[BL_NF];
+        // (whole entries, one 16-byte load each, outside the compiler's books: bl_ring_issue16; taken behind the frame's
+        // wait for vector memory, in front of the filter bank)
+        bl_u32x4 leaving[BL_NF];
         if (S.alive && t.use_gsff) {
-            const unsigned line = (unsigned)bd.seat_cap * (unsigned)sizeof(double2), seat_b = (unsigned)tid * (unsigned)sizeof(double2);
+            const unsigned line = (unsigned)bd.seat_cap * (unsigned)sizeof(double2);
 #pragma unroll
             for (int k = 0; k < BL_NF; ++k) {
                 const unsigned pos = S.len >= sa.hz[k] ? (unsigned)((head - sa.hz[k]) & (BL_HB - 1)) : (unsigned)BL_HB;
-                leave[k] = bl_ring_load_bytes(bd, __umul24(pos, line) + seat_b);      // (33 lines of 768 seats: 24 bits hold a line)
+                bl_ring_issue16(bd, tid, __umul24(pos, line), leaving[k]);      // (33 lines of 768 seats: 24 bits hold a line)
             }
         }
         BLSTAMP(1);
@@ -1662,6 +1715,8 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
         // old.  For every lane, with or without a track: the compiler then knows that no load is in flight at the head of
         // the loop, and does not guard the search's registers with waits that would catch the ring store.
         bl_wait_vmem();
+        BLSTAMP_OWN_TEST(8);
+        bl_ring_taken16(leaving);
         // (the gains' pointer, requested behind the row: taken here by EVERY wave, with or without a live track -- a load
         // left in flight would land in registers the compiler has meanwhile given to something else)
         const BlGainsPtr gq = bl_gains_wait(gains_pending);
@@ -1681,7 +1736,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch(BlKernArgs ka)
                 // vmcnt(0) lgkmcnt(0) waits in the middle of the float64 chain: tests/test_kernel_listing.py)
                 // (hist_cap, lik_min and the rare block's horizons likewise: read from the argument segment here, beside the
                 // gains, they hold no scalar register across the frame)
-                bl_gsff<true>(S, t, bl_kernargs()->t, bd, *gq, tid, head, leave, z0, z1, fresh, grow_at, o0, o1);
+                bl_gsff<true>(S, t, bl_kernargs()->t, bd, *gq, tid, head, leaving, z0, z1, fresh, grow_at, o0, o1);
             }
             else { S.px = z0; S.py = z1; }
         }

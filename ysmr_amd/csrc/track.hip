@@ -2212,6 +2212,7 @@ int ysmr_debug_read_bcounts(unsigned long long *out) { return (int)hipMemcpyFrom
 int ysmr_debug_read_bwaves(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bwaves), sizeof(unsigned long long) * (BL_WAVES + 1)); }
 int ysmr_debug_read_bseats(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bseats), sizeof(unsigned long long) * 2); }
 int ysmr_debug_read_brefresh(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_brefresh), sizeof(unsigned long long) * BL_WAVES * 4); }
+int ysmr_debug_read_bsteady(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bsteady), sizeof(unsigned long long) * BL_WAVES * 16); }
 #endif
 
 int ysmr_tracker_batched(ysmr_tracker *t) { return t && plan::is_batch(t->link()) ? 1 : 0; }
