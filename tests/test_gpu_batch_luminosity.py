@@ -147,6 +147,27 @@ def test_thirds_beyond_4096_take_the_exact_search(torch_cuda):
     _check_clip_against_the_model(torch_cuda, case, 16)
 
 
+def _check_frames_against_the_linker(torch, frames, lk, per_frame, capacity, max_det):
+    """The frames through ONE run call of a 3-D handle in link mode 2: rows, peek() and info() byte-equal to the linker
+    that has seen them (lk) and to its rows (per_frame)."""
+    from ysmr_amd.tracker import rows_to_numpy
+    want = _model_rows(per_frame)
+    trk = _tracker(LC.MAX_DISAPPEARED, capacity, max_det)
+    assert trk.batched
+    det, third, counts = LC.arrays(frames, max_det)
+    rows, n = _rows_buffer(torch, len(want))
+    trk.run(torch.from_numpy(det).cuda(), torch.from_numpy(counts).cuda(), 0, rows, n, third=torch.from_numpy(third).cuda())
+    torch.cuda.synchronize()
+    assert int(n.item()) == len(want)
+    got = rows_to_numpy(rows, len(want))
+    np.testing.assert_array_equal(got["track_id"], want["track_id"])
+    assert got.tobytes() == want.tobytes()
+    ids, xyz, gone = trk.peek()
+    assert list(ids) == list(lk.objects) and list(gone) == [lk.disappeared[i] for i in ids]
+    assert xyz.tobytes() == np.array([lk.objects[i] for i in ids]).tobytes()
+    assert trk.info() == (len(ids), lk.next_id, 0)
+
+
 def _bright_track_frames():
     """The other way into the exact search: a TRACK whose own third coordinate is at or above 4096 in frames whose
     detections all stay far below it.  A dozen stationary blobs, blob 0 at (100, 100) with luminosity 5000 in frame 0 only.
@@ -167,7 +188,6 @@ def _bright_track_frames():
 
 def test_a_track_whose_own_third_is_beyond_4096_takes_the_exact_search(torch_cuda):
     torch = torch_cuda
-    from ysmr_amd.tracker import rows_to_numpy
     frames, col_x, col_y = _bright_track_frames()
     assert all(np.abs(p[:, 2]).max() < 4096.0 for p, _ in frames[1:]), "frames 1.. must not carry the header flag"
     lk, lk2 = M.Linker(LC.MAX_DISAPPEARED), M.Linker(LC.MAX_DISAPPEARED)
@@ -181,20 +201,64 @@ def test_a_track_whose_own_third_is_beyond_4096_takes_the_exact_search(torch_cud
             assert claims[0] == col_y and claims2[0] == col_x
         per_frame.append(lk.rows(f))
     assert lk.min_gap >= 1e-9, f"the expected table hangs on a distance gap of {lk.min_gap}"
-    want = _model_rows(per_frame)
-    trk = _tracker(LC.MAX_DISAPPEARED, 768, 2048)
-    assert trk.batched
-    det, third, counts = LC.arrays(frames, 2048)
-    rows, n = _rows_buffer(torch, len(want))
-    trk.run(torch.from_numpy(det).cuda(), torch.from_numpy(counts).cuda(), 0, rows, n, third=torch.from_numpy(third).cuda())
-    torch.cuda.synchronize()
-    assert int(n.item()) == len(want)
-    got = rows_to_numpy(rows, len(want))
-    np.testing.assert_array_equal(got["track_id"], want["track_id"])
-    assert got.tobytes() == want.tobytes()
-    ids, xyz, gone = trk.peek()
-    assert list(ids) == list(lk.objects) and list(gone) == [lk.disappeared[i] for i in ids]
-    assert xyz.tobytes() == np.array([lk.objects[i] for i in ids]).tobytes()
+    _check_frames_against_the_linker(torch, frames, lk, per_frame, 768, 2048)
+
+
+def _clump_frames():
+    """A run of the 3 x 3 block with more than five entries, and the nearest in space among its sixth and later.  A dozen
+    stationary blobs, blob 0 at (100, 100) with luminosity 50.  In frame 2 blob 0 and six far blobs are missing and a clump
+    of seven detections appears around track 0: six within 28 px in the plane but 29 to 31 away in luminosity, and
+    Y = (108, 100, 51), 8 px away in the plane and the nearest in space (64 + 1 < 9 + 30^2).  The frame's bounding box is
+    72 .. 520 in x and starts at 90 in y, so its 16 x 16 cells are 32 px wide with sides at 40 + 32 k and 58 + 32 k: track 0
+    and the six lie in cell (1, 1), Y in cell (2, 1) -- behind all six in the row's run.  Twelve detections meet twelve
+    tracks: no births, track 0 claims Y and is an ordinary track from then on."""
+    blobs = [(100.0, 100.0, 50.0)] + [(220.0 + 97.0 * (k % 4) + 3.0 * k, 90.0 + 173.0 * (k // 4) + 7.0 * k, 0.5 + 0.25 * k)
+                                       for k in range(11)]
+    box = [(3.0 + k, 2.0, 10.0 * k) for k in range(12)]
+    frame = lambda pts, bx: (np.array(pts), np.array(bx, np.float32))  # noqa: E731
+    clump = [(97.0, 100.0, 80.0), (100.0, 104.0, 80.5), (96.0, 97.0, 79.5), (103.0, 106.0, 81.0), (94.0, 104.0, 79.0), (72.0, 96.0, 80.25)]
+    y = (108.0, 100.0, 51.0)
+    keep = [blobs[k] for k in range(1, 6)]
+    pts = keep[:2] + clump[:3] + [y] + keep[2:] + clump[3:]
+    bx = [box[k] for k in (1, 2)] + [(1.0, 1.0, 0.0)] * 3 + [(2.0, 2.0, 0.0)] + [box[k] for k in (3, 4, 5)] + [(1.0, 1.0, 0.0)] * 3
+    after = frame(blobs[1:] + [y], box[1:] + [(2.0, 2.0, 0.0)])
+    return [frame(blobs, box), frame(blobs, box), frame(pts, bx), after, after], 5      # (frames, column of Y)
+
+
+def test_the_nearest_in_space_among_a_runs_sixth_and_later_candidates(torch_cuda):
+    """bl_block_search's loop over a run's sixth and later candidates in three dimensions (`more`, q_extra): the one place
+    where the search reads the f32 plane outside its fifteen unrolled loads."""
+    torch = torch_cuda
+    import cell_list_model as CL
+    frames, col_y = _clump_frames()
+    assert len(frames) <= 5 and all(np.abs(p[:, 2]).max() < 4096.0 for p, _ in frames), "the float stage must run"
+    lk, lk2 = M.Linker(LC.MAX_DISAPPEARED), M.Linker(LC.MAX_DISAPPEARED)
+    per_frame = []
+    for f, (pts, box) in enumerate(frames):
+        if f == 2:      # the preconditions, on the CPU: the frame's cells as k_bgrid3 makes them, track 0's 3 x 3 block
+            assert len(pts) <= len(lk.objects), "a birth in the frame under test"
+            xy32 = pts[:, :2].astype(np.float32)
+            g, order = CL.bin_frame(xy32)
+            cx, cy, _ = CL.lane_cell(g, lk.objects[0][0], lk.objects[0][1])
+            assert 0 <= cx < g.G and 0 <= cy < g.G
+            xl, xh = max(cx - 1, 0), min(cx + 1, g.G - 1)
+            run0, run1 = int(g.start[cy * g.G + xl]), int(g.start[cy * g.G + xh + 1])
+            assert run1 - run0 >= 7, "track 0's row of cells holds fewer than seven detections"
+            nearest = int(M.cdist(lk.objects[0][None, :], pts)[0].argmin())
+            assert nearest == col_y
+            (pos,) = np.nonzero(order == nearest)[0]
+            assert run0 <= pos < run1, "the nearest in space is not in the run of track 0's own row of cells"
+            ccx = int(np.clip(np.floor((xy32[nearest, 0] - g.x0) * g.inv), 0, g.G - 1))
+            first_of_its_cell = int(g.start[cy * g.G + ccx])
+            # (order inside a cell is free on the device: every position its cell allows lies at or beyond the run's sixth)
+            assert first_of_its_cell - run0 >= 5, "the nearest in space can come among the run's first five"
+        claims, _ = lk.update(pts, [tuple(float(v) for v in b) for b in box])
+        claims2, _ = lk2.update(pts[:, :2], [tuple(float(v) for v in b) for b in box])
+        if f == 2:      # the third coordinate decides: Y in space, a member of the clump in the plane
+            assert claims[0] == col_y and claims2[0] not in (col_y, -1)
+        per_frame.append(lk.rows(f))
+    assert lk.min_gap >= 1e-9, f"the expected table hangs on a distance gap of {lk.min_gap}"
+    _check_frames_against_the_linker(torch, frames, lk, per_frame, 512, 512)
 
 
 # ---- 4. an exact tie between two columns -----------------------------------------------------------------------------------

@@ -191,10 +191,16 @@ __device__ __forceinline__ void bl_quad_list(int c, int q, int G, int m, float x
     bl_rect_list(cx, cy, ax, bx, ay, by, e, G, m, cell, inv, start16, xy, list8, cand);
 }
 
-__global__ __launch_bounds__(BG_THREADS) void k_bgrid(const float *__restrict__ det_all, const int32_t *__restrict__ det_count,
-                                                      int max_det, char *grid, unsigned grid_stride)
+// The binning of one frame by one workgroup, for the planar link (D3 = false: k_bgrid) and the 3-D link (D3 = true: k_bgrid3):
+// the load of the detections, the bounding box, the cells, the counting sort, the scan, the padding, the scatter and the
+// copy-out are one text for both.  The 3-D instance adds the third coordinate -- z[], `wide` / s_wide and header word 7, the
+// z32 plane in the LDS part and the z64 plane in HBM (above k_bgrid3) -- and builds no candidate lists; the planar instance
+// builds them (first pass, split lists, overflow area).  A __shared__ array that an instance does not touch takes no LDS in it.
+template <bool D3>
+__device__ __forceinline__ void bl_bin_frame(const float *__restrict__ det_all, const double *__restrict__ third_all,
+                                             const int32_t *__restrict__ det_count, int max_det, char *grid, unsigned grid_stride)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t s_out[];      // the block as it will lie in HBM
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_out[];      // the block as it will lie in HBM (3-D: its LDS part)
     __shared__ int s_cnt[64 * 64];
     __shared__ float s_red[4][4];
     __shared__ int s_wave_sum[4];
@@ -203,6 +209,7 @@ __global__ __launch_bounds__(BG_THREADS) void k_bgrid(const float *__restrict__ 
     __shared__ unsigned short s_crowded[BL_OVF];                // the cells that get an overflow entry, ascending
     __shared__ int s_crowded_n;                                 // how many of them (at most BL_OVF)
     __shared__ int s_any_crowded;                               // flag: the first pass flagged a cell
+    __shared__ int s_wide;                                      // 3-D: some |third| of the frame is not below 4096
     const float *det = det_all + (size_t)f * max_det * 5;
     int m = det_count[f];
     m = m < 0 ? 0 : (m > max_det ? max_det : m);
@@ -210,15 +217,26 @@ __global__ __launch_bounds__(BG_THREADS) void k_bgrid(const float *__restrict__ 
     unsigned short *start16 = reinterpret_cast<unsigned short *>(s_out + 16);
     float2 *xy = reinterpret_cast<float2 *>(s_out + 16 + bl_start_dwords(G));
     unsigned short *items = reinterpret_cast<unsigned short *>(s_out + 16 + bl_start_dwords(G) + 2 * bl_mp(m));
-    unsigned short *list16 = reinterpret_cast<unsigned short *>(s_out + bl_list_off(m));
+    unsigned short *list16 = reinterpret_cast<unsigned short *>(s_out + bl_list_off(m));      // (planar)
+    // (3-D: the f32 plane stands where the planar block has its lists; the f64 plane does not pass through this kernel's LDS)
+    float *z32 = reinterpret_cast<float *>(s_out + bl_list_off(m));
+    double *z64 = nullptr;
+    if constexpr (D3) z64 = reinterpret_cast<double *>(grid + (size_t)grid_stride * f + 4 * (size_t)bl3_lds_dwords_max(max_det));
     float x[BG_PER], y[BG_PER];
+    double z[BG_PER];
+    bool wide = false;
 #pragma unroll
     for (int k = 0; k < BG_PER; ++k) {
         const int j = tid + k * BG_THREADS;
         x[k] = j < m ? det[(size_t)j * 5] : 0.f;
         y[k] = j < m ? det[(size_t)j * 5 + 1] : 0.f;
+        if constexpr (D3) {      // (a slot at or beyond the frame's count is never read)
+            z[k] = j < m ? (third_all + (size_t)f * max_det)[j] : 0.0;
+            wide = wide || !(fabs(z[k]) < 4096.0);
+        }
     }
     for (int c = tid; c < cells; c += BG_THREADS) s_cnt[c] = 0;
+    if constexpr (D3) { if (tid == 0) s_wide = 0; }
     float lo_x = 3.0e38f, lo_y = 3.0e38f, hi_x = -3.0e38f, hi_y = -3.0e38f;
 #pragma unroll
     for (int k = 0; k < BG_PER; ++k)
@@ -230,6 +248,7 @@ __global__ __launch_bounds__(BG_THREADS) void k_bgrid(const float *__restrict__ 
     }
     if (lane == 0) { s_red[0][w] = lo_x; s_red[1][w] = hi_x; s_red[2][w] = lo_y; s_red[3][w] = hi_y; }
     __syncthreads();
+    if constexpr (D3) { if (wide) s_wide = 1; }
     lo_x = s_red[0][0]; hi_x = s_red[1][0]; lo_y = s_red[2][0]; hi_y = s_red[3][0];
     for (int k = 1; k < 4; ++k) {
         lo_x = fminf(lo_x, s_red[0][k]); hi_x = fmaxf(hi_x, s_red[1][k]);
@@ -244,7 +263,8 @@ __global__ __launch_bounds__(BG_THREADS) void k_bgrid(const float *__restrict__ 
     if (tid == 0) {
         float *h = reinterpret_cast<float *>(s_out);
         h[0] = x0; h[1] = y0; h[2] = cell; h[3] = inv;
-        s_out[4] = (uint32_t)G; s_out[5] = (uint32_t)m; s_out[6] = bl_has_lists(m) ? BL_LIST : 0;
+        s_out[4] = (uint32_t)G; s_out[5] = (uint32_t)m; s_out[6] = !D3 && bl_has_lists(m) ? BL_LIST : 0;
+        if constexpr (D3) s_out[7] = (uint32_t)s_wide;
     }
     int cell_of[BG_PER];
 #pragma unroll
@@ -278,7 +298,10 @@ __global__ __launch_bounds__(BG_THREADS) void k_bgrid(const float *__restrict__ 
         }
     if (tid == BG_THREADS - 1) { start16[cells] = (unsigned short)m; start16[cells + 1] = 0; }
     // (the padding of the lists reads as far away, should a lane ever look at it)
-    for (int j = m + tid; j < bl_mp(m); j += BG_THREADS) { xy[j] = make_float2(1.0e30f, 1.0e30f); items[j] = 0; }
+    for (int j = m + tid; j < bl_mp(m); j += BG_THREADS) {
+        xy[j] = make_float2(1.0e30f, 1.0e30f); items[j] = 0;
+        if constexpr (D3) { z32[j] = 0.f; z64[j] = 0.0; }
+    }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < BG_PER; ++k) {
@@ -287,62 +310,71 @@ __global__ __launch_bounds__(BG_THREADS) void k_bgrid(const float *__restrict__ 
             const int at = atomicAdd(&s_cnt[cell_of[k]], 1);
             items[at] = (unsigned short)j;
             xy[at] = make_float2(x[k], y[k]);
+            if constexpr (D3) { z32[at] = (float)z[k]; z64[at] = z[k]; }      // (rounded into the LDS part, as given into the tail)
         }
     }
-    unsigned short *ovf16 = reinterpret_cast<unsigned short *>(s_out + bl_ovf_off(m));      // (frames with lists only)
-    if (bl_has_lists(m)) {      // (the overflow area starts as zeros; "no crowded cell yet")
+    if (!D3 && bl_has_lists(m)) {      // (the overflow area starts as zeros; "no crowded cell yet")
         for (int i = tid; i < BL_OVF * 4 * BL_LIST / 2; i += BG_THREADS) s_out[bl_ovf_off(m) + i] = 0;
         if (tid == 0) s_any_crowded = 0;
     }
     __syncthreads();
-    if (bl_has_lists(m) && m > 0) {
-        for (int c = tid; c < cells; c += BG_THREADS) {
-            bl_cell_list(c, G, m, x0, y0, cell, inv, start16, xy, list16, &s_cand[0][tid]);
-            if (list16[c * BL_LIST] == BL_FLAG) s_any_crowded = 1;     // (the second pass runs)
+    if constexpr (!D3) {      // the candidate lists: first pass, split lists, overflow area
+        unsigned short *ovf16 = reinterpret_cast<unsigned short *>(s_out + bl_ovf_off(m));      // (frames with lists only)
+        if (bl_has_lists(m) && m > 0) {
+            for (int c = tid; c < cells; c += BG_THREADS) {
+                bl_cell_list(c, G, m, x0, y0, cell, inv, start16, xy, list16, &s_cand[0][tid]);
+                if (list16[c * BL_LIST] == BL_FLAG) s_any_crowded = 1;     // (the second pass runs)
+            }
+            __syncthreads();
         }
-        __syncthreads();
-    }
-    if (bl_has_lists(m) && m > 0 && s_any_crowded) {         // (uniform: read behind the barrier)
-        // Split lists.  The crowded cells (flagged above) are compacted in cell order -- K consecutive cells per thread, the
-        // scan of the counts again -- and the first BL_OVF of them get an overflow entry each; the (entry, quadrant) items
-        // then go out over the workgroup, one per thread: the thread that owned a crowded cell was the slowest of the first
-        // pass already, and four more lists in a row behind it would be the kernel's tail.
-        int mine = 0;
+        if (bl_has_lists(m) && m > 0 && s_any_crowded) {         // (uniform: read behind the barrier)
+            // Split lists.  The crowded cells (flagged above) are compacted in cell order -- K consecutive cells per thread, the
+            // scan of the counts again -- and the first BL_OVF of them get an overflow entry each; the (entry, quadrant) items
+            // then go out over the workgroup, one per thread: the thread that owned a crowded cell was the slowest of the first
+            // pass already, and four more lists in a row behind it would be the kernel's tail.
+            int mine = 0;
 #pragma unroll
-        for (int k = 0; k < 16; ++k)
-            if (k < K) mine += list16[(tid * K + k) * BL_LIST] == BL_FLAG;
-        int inc2 = mine;
+            for (int k = 0; k < 16; ++k)
+                if (k < K) mine += list16[(tid * K + k) * BL_LIST] == BL_FLAG;
+            int inc2 = mine;
 #pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(inc2, d); if (lane >= d) inc2 += o; }
-        if (lane == 63) s_wave_sum[w] = inc2;      // (its readers of the first scan are barriers back)
-        __syncthreads();
-        int at = inc2 - mine;
-        for (int k = 0; k < w; ++k) at += s_wave_sum[k];
-        if (mine)
-            for (int k = 0; k < K; ++k)
-                if (list16[(tid * K + k) * BL_LIST] == BL_FLAG) {
-                    if (at < BL_OVF) s_crowded[at] = (unsigned short)(tid * K + k);
-                    ++at;
-                }
-        if (tid == BG_THREADS - 1) s_crowded_n = min(at, BL_OVF);
-        __syncthreads();
-        const int entries = s_crowded_n;
-        // (quadrant w of entry `lane` on wave w: a wave's lanes run their lists in lockstep, every lane through every other
-        // lane's loops, so the items are spread over the four waves rather than packed into the first)
-        if (lane < entries)
-            bl_quad_list(s_crowded[lane], w, G, m, x0, y0, cell, inv, start16, xy, ovf16 + (4 * lane + w) * BL_LIST, &s_cand[0][tid]);
-        __syncthreads();
-        if (tid < entries) {
-            bool fits = true;
-            for (int q = 0; q < 4; ++q) fits = fits && ovf16[(4 * tid + q) * BL_LIST] != BL_FLAG;
-            // (the slot's first dword: the marker and the entry; a cell with a quadrant that still overflows keeps its flag)
-            if (fits) reinterpret_cast<uint32_t *>(list16)[s_crowded[tid] * (BL_LIST / 2)] = BL_SPLIT | ((uint32_t)tid << 16);
+            for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(inc2, d); if (lane >= d) inc2 += o; }
+            if (lane == 63) s_wave_sum[w] = inc2;      // (its readers of the first scan are barriers back)
+            __syncthreads();
+            int at = inc2 - mine;
+            for (int k = 0; k < w; ++k) at += s_wave_sum[k];
+            if (mine)
+                for (int k = 0; k < K; ++k)
+                    if (list16[(tid * K + k) * BL_LIST] == BL_FLAG) {
+                        if (at < BL_OVF) s_crowded[at] = (unsigned short)(tid * K + k);
+                        ++at;
+                    }
+            if (tid == BG_THREADS - 1) s_crowded_n = min(at, BL_OVF);
+            __syncthreads();
+            const int entries = s_crowded_n;
+            // (quadrant w of entry `lane` on wave w: a wave's lanes run their lists in lockstep, every lane through every other
+            // lane's loops, so the items are spread over the four waves rather than packed into the first)
+            if (lane < entries)
+                bl_quad_list(s_crowded[lane], w, G, m, x0, y0, cell, inv, start16, xy, ovf16 + (4 * lane + w) * BL_LIST, &s_cand[0][tid]);
+            __syncthreads();
+            if (tid < entries) {
+                bool fits = true;
+                for (int q = 0; q < 4; ++q) fits = fits && ovf16[(4 * tid + q) * BL_LIST] != BL_FLAG;
+                // (the slot's first dword: the marker and the entry; a cell with a quadrant that still overflows keeps its flag)
+                if (fits) reinterpret_cast<uint32_t *>(list16)[s_crowded[tid] * (BL_LIST / 2)] = BL_SPLIT | ((uint32_t)tid << 16);
+            }
+            __syncthreads();
         }
-        __syncthreads();
     }
     uint4 *out = reinterpret_cast<uint4 *>(grid + (size_t)grid_stride * f);
     const uint4 *img = reinterpret_cast<const uint4 *>(s_out);
-    for (int i = tid; i < bl_grid_dwords(m) / 4; i += BG_THREADS) out[i] = img[i];
+    for (int i = tid; i < (D3 ? bl3_lds_dwords(m) : bl_grid_dwords(m)) / 4; i += BG_THREADS) out[i] = img[i];
+}
+
+__global__ __launch_bounds__(BG_THREADS) void k_bgrid(const float *__restrict__ det_all, const int32_t *__restrict__ det_count,
+                                                      int max_det, char *grid, unsigned grid_stride)
+{
+    bl_bin_frame<false>(det_all, nullptr, det_count, max_det, grid, grid_stride);
 }
 
 // ---- a track in registers -------------------------------------------------------------------------------------------
@@ -740,6 +772,8 @@ struct BlNear { double s; float zx, zy; int col; bool done; };
 // 64-bit address per access (97 of them in the first build of this kernel).
 extern __shared__ __attribute__((aligned(16))) unsigned long long bl_lds[];
 __device__ __forceinline__ uint32_t *bl_u32(int dword_off) { return reinterpret_cast<uint32_t *>(bl_lds) + dword_off; }
+// (entry i of a 3-D block's f32 plane, z32 its dword offset)
+__device__ __forceinline__ float bl_z32_at(int z32, int i) { return reinterpret_cast<const float *>(bl_u32(z32))[i]; }
 struct BlGridView {
     int start, xy, items, lists, G;      // dword offsets into bl_lds (lists: -1, none); cells per side
     float x0, y0, cell, inv;
@@ -788,17 +822,71 @@ __device__ __forceinline__ float bl_dist2f(float fx, float fy, float2 c)
     const float dx = fx - c.x, dy = fy - c.y;
     return __builtin_fmaf(dy, dy, dx * dx);
 }
+// The 3-D link's (k_batch3, below) result and distances: a third coordinate beside the planar ones.
+struct BlNear3 { double s, z; float zx, zy; int col; bool done; };
+__device__ __forceinline__ double bl_dist3(double px, double py, double pz, float2 c, double cz)
+{
+    // cdist's order (luminosity_model.cdist; rowmin_wave<.., true>): dx * dx + dy * dy + dz * dz, summed left to right
+    const double dx = px - (double)c.x;
+    const double dy = py - (double)c.y;
+    const double dz = pz - cz;
+    double s = dx * dx;
+    s = s + dy * dy;
+    s = s + dz * dz;
+    return s;
+}
+__device__ __forceinline__ float bl_dist3f(float fx, float fy, float fz, float2 c, float cz)
+{
+    const float dx = fx - c.x, dy = fy - c.y, dz = fz - cz;
+    return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+}
+// Float error band of a 3-D squared distance, for |px|, |py|, |pz| and every |third| below 4096 (k_bgrid3 flags a frame
+// with a larger one, the caller tests pz).  (float)px, (float)py and (float)pz are off by at most 2^-24 * 4096 = 2.4e-4; the
+// centres are float already, but the candidate's third coordinate was ROUNDED to float as well: dz is off by 4.9e-4, dx
+// and dy by 2.4e-4.  Unlike a planar distance inside a 3 x 3 block, dz has no bound but 8192, so the error is taken relative
+// to the distance: |s_f - s| <= 2 (|dx| + |dy|) 2.4e-4 + 2 |dz| 4.9e-4 + 4 * 2^-24 s <= 9.8e-4 * sqrt(3 s) + 2.4e-7 s, and with
+// a sqrt(s) <= t + a^2 s / (4 t) at t = 0.05: <= 0.05 + 1.5e-5 s; the key drops 2^-19 s more: e(s) <= 0.05 + 1.7e-5 s.
+// A detection that is truly as near as the float winner (float distance b) has a float distance of at most
+// b + 2 e(s_winner) <= b + 0.1002 + 3.5e-5 b: the band below is that with a margin (twice in the constant, 1.4 x in the slope).
+__device__ __forceinline__ float bl3_band(float best) { return best + (0.2f + 5e-5f * best); }
+// What the searches below, one text for both dimensions, take per dimension: the result, the float key's distance, its
+// band, the exact distance (pz / fz / cz: unused in the plane)
+template <bool D3> using BlNearOf = std::conditional_t<D3, BlNear3, BlNear>;
+template <bool D3> __device__ __forceinline__ float bl_distf(float fx, float fy, float fz, float2 c, float cz)
+{
+    if constexpr (D3) return bl_dist3f(fx, fy, fz, c, cz);
+    else return bl_dist2f(fx, fy, c);
+}
+template <bool D3> __device__ __forceinline__ double bl_dist(double px, double py, double pz, float2 c, double cz)
+{
+    if constexpr (D3) return bl_dist3(px, py, pz, c, cz);
+    else return bl_dist2(px, py, c);
+}
+template <bool D3> __device__ __forceinline__ float bl_band(float best)
+{
+    if constexpr (D3) return bl3_band(best);
+    else return best + (0.2f + 5e-6f * best);
+}
 __device__ __forceinline__ uint32_t bl_med3(uint32_t a, uint32_t b, uint32_t c)
 {
     uint32_t r;                                          // (the compiler spells the median out as three min / max)
     asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
-__device__ __forceinline__ BlNear bl_search_block(const BlGridView &g, double px, double py, int m)
+// One body for the planar link (D3 = false) and the 3-D link (D3 = true), which adds the third coordinate: fz, the f32
+// plane's cz[] beside the centres (z32: the plane's dword offset in LDS), float keys of dx^2 + dy^2 + dz^2 and their band
+// (bl3_band), and the winner's exact third coordinate from the f64 plane in HBM (z64).  "Nothing outside the block is as
+// near" stays a test in the PLANE in both: a detection's 3-D distance is never below its planar distance, so one that lies
+// beyond the block's boundary in the plane is farther than the boundary in space.  The planar branch is spelt as k_batch was
+// compiled with it (its expressions, bl_winner, the sched_barrier): k_batch's register allocation moves at a touch.
+template <bool D3>
+__device__ __forceinline__ BlNearOf<D3> bl_block_search(const BlGridView &g, int z32, const double *__restrict__ z64, double px, double py,
+                                                        double pz, int m)
 {
     constexpr int R = 3, C = 5;
     const int G = g.G;
     const float fx = (float)px, fy = (float)py;
+    [[maybe_unused]] const float fz = (float)pz;
     int cx = (int)floorf((fx - g.x0) * g.inv), cy = (int)floorf((fy - g.y0) * g.inv);
     const bool in_grid = cx >= 0 && cx < G && cy >= 0 && cy < G;
     cx = cx < 0 ? 0 : (cx > G - 1 ? G - 1 : cx);
@@ -814,13 +902,18 @@ __device__ __forceinline__ BlNear bl_search_block(const BlGridView &g, double px
     }
     // every candidate's read is issued before the first is used (left to itself the compiler, short of registers, waits
     // for each read before it issues the next: fifteen LDS round trips in a row); a slot beyond the end of its run reads
-    // whatever follows in LDS and is masked afterwards
+    // whatever follows in LDS and is masked afterwards (3-D: inside the block's LDS part -- a run starts at or below m, and
+    // entry m + 4 lies in the padding or in the next plane)
     float2 c[R * C];
+    float cz[R * C] = {};
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const float2 *run = reinterpret_cast<const float2 *>(bl_u32(g.xy)) + a[r];
 #pragma unroll
-        for (int j = 0; j < C; ++j) c[C * r + j] = run[j];
+        for (int j = 0; j < C; ++j) {
+            c[C * r + j] = run[j];
+            if constexpr (D3) cz[C * r + j] = bl_z32_at(z32, a[r] + j);
+        }
     }
     __builtin_amdgcn_sched_barrier(0);
     uint32_t lo = 0xFFFFFFFFu, hi = 0xFFFFFFFFu;        // the two smallest keys
@@ -828,7 +921,7 @@ __device__ __forceinline__ BlNear bl_search_block(const BlGridView &g, double px
     for (int r = 0; r < R; ++r)
 #pragma unroll
         for (int j = 0; j < C; ++j) {
-            const float d2 = bl_dist2f(fx, fy, c[C * r + j]);
+            const float d2 = bl_distf<D3>(fx, fy, fz, c[C * r + j], cz[C * r + j]);
             uint32_t key = (__float_as_uint(d2) & 0xFFFFFFF0u) | (uint32_t)(C * r + j);
             key = a[r] + j < b[r] ? key : 0xFFFFFFFFu;
             hi = bl_med3(lo, hi, key);
@@ -842,14 +935,14 @@ __device__ __forceinline__ BlNear bl_search_block(const BlGridView &g, double px
 #pragma unroll
         for (int r = 0; r < R; ++r)
             for (int qq = a[r] + C; qq < b[r]; ++qq) {
-                const uint32_t key = (__float_as_uint(bl_dist2f(fx, fy, g.xy_at(qq))) & 0xFFFFFFF0u) | 15u;
+                const uint32_t key = (__float_as_uint(bl_distf<D3>(fx, fy, fz, g.xy_at(qq), D3 ? bl_z32_at(z32, qq) : 0.f)) & 0xFFFFFFF0u) | 15u;
                 q_extra = key < lo ? qq : q_extra;
                 hi = bl_med3(lo, hi, key);
                 lo = min(lo, key);
             }
     }
     const float best = __uint_as_float(lo & 0xFFFFFFF0u), second = __uint_as_float(hi & 0xFFFFFFF0u);
-    const float band = best + (0.2f + 5e-6f * best);   // (twice the error bound: both distances are off)
+    const float band = bl_band<D3>(best);              // (twice the error bound: both distances are off)
     const int slot = (int)(lo & 15u);
     const int run = slot >= 2 * C ? 2 : (slot >= C ? 1 : 0);
     const int bq = slot == 15 ? q_extra : (run == 2 ? a[2] : (run == 1 ? a[1] : a[0])) + slot - C * run;
@@ -857,6 +950,8 @@ __device__ __forceinline__ BlNear bl_search_block(const BlGridView &g, double px
     // block's boundary -- one comparison for nearly every lane; the others measure the distance to the outside of the
     // block (a side on the edge of the grid has nothing beyond it)
     const bool found = lo != 0xFFFFFFFFu;
+    double wz = 0.0;
+    if constexpr (D3) wz = z64[found ? bq : 0];         // (the winner's exact third coordinate: requested at once)
     const float reach = 0.998f * g.cell;
     bool inside = in_grid && band < reach * reach;
     if (!inside) {
@@ -870,12 +965,17 @@ __device__ __forceinline__ BlNear bl_search_block(const BlGridView &g, double px
         inside = bound >= big * 0.5f || (bound > 0.f && bound * bound > band);
     }
     float2 cw;
-    BlNear r;
-    bl_winner(g, found ? bq : 0, cw, r.col);
-    r.s = bl_dist2(px, py, cw);
+    BlNearOf<D3> r;
+    if constexpr (D3) { cw = g.xy_at(found ? bq : 0); r.col = g.item_at(found ? bq : 0); r.z = wz; }
+    else bl_winner(g, found ? bq : 0, cw, r.col);
+    r.s = bl_dist<D3>(px, py, pz, cw, wz);
     r.zx = cw.x; r.zy = cw.y;
     r.done = found && inside && !(second <= band);     // (hi = 0xFFFFFFFF reads as a NaN: no second candidate)
     return r;
+}
+__device__ __forceinline__ BlNear bl_search_block(const BlGridView &g, double px, double py, int m)
+{
+    return bl_block_search<false>(g, 0, nullptr, px, py, 0.0, m);
 }
 
 // The same from the candidate list of the prediction's cell (frames with G <= 32, predictions inside the grid): one LDS
@@ -937,23 +1037,29 @@ __device__ __forceinline__ BlNear bl_search(const BlGridView &g, double px, doub
 // everything: most calls end here).  Otherwise exactly, rowmin_wave's three passes: the smallest squared distance; the
 // lowest column within 2^-48 of it; the rounded roots themselves only if some s differs from the smallest at all.
 // px, py, the result: wave-uniform.
-__device__ __forceinline__ BlNear bl_search_wave(const BlGridView &g, double px, double py, int m, int lane)
+// One body for both dimensions, as bl_block_search, its planar branch spelt as k_batch was compiled with it.  The 3-D
+// instance adds pz and `narrow` (wave-uniform too): its float pre-pass runs only where the 3-D band holds (`narrow`) and reads
+// the f32 plane in LDS; its exact passes read the f64 plane in HBM, coalesced, in cell order like the centres.
+template <bool D3>
+__device__ __forceinline__ BlNearOf<D3> bl_wave_search(const BlGridView &g, int z32, const double *__restrict__ z64, double px, double py,
+                                                       double pz, int m, int lane, bool narrow)
 {
     const double inf = __longlong_as_double(0x7FF0000000000000ll);
-    BlNear r;
+    BlNearOf<D3> r;
     r.done = true;
-    if (m <= 512) {
+    if (m <= 512 && (!D3 || narrow)) {
         const float fx = (float)px, fy = (float)py;
+        [[maybe_unused]] const float fz = (float)pz;
         float sf[8];
         int lo = 0x7F800000;                              // (a non-negative float orders like its bits, as an int too)
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int j = u * 64 + lane;
-            sf[u] = j < m ? bl_dist2f(fx, fy, g.xy_at(min(j, m - 1))) : 3.0e38f;
+            sf[u] = j < m ? bl_distf<D3>(fx, fy, fz, g.xy_at(min(j, m - 1)), D3 ? bl_z32_at(z32, min(j, m - 1)) : 0.f) : 3.0e38f;
             lo = min(lo, (int)__float_as_uint(sf[u]));
         }
         const float best = __uint_as_float((uint32_t)wave_min(lo));
-        const float band = best + (0.2f + 5e-6f * best);
+        const float band = bl_band<D3>(best);
         int n_near = 0, jn = 0;
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
@@ -963,18 +1069,21 @@ __device__ __forceinline__ BlNear bl_search_wave(const BlGridView &g, double px,
         }
         if (n_near == 1) {
             const float2 c = g.xy_at(jn);
-            r.s = bl_dist2(px, py, c); r.zx = c.x; r.zy = c.y; r.col = g.item_at(jn);
+            double wz = 0.0;
+            if constexpr (D3) r.z = wz = z64[jn];
+            r.s = bl_dist<D3>(px, py, pz, c, wz); r.zx = c.x; r.zy = c.y; r.col = g.item_at(jn);
             return r;
         }
     }
     double lane_min = inf;
     for (int j0 = 0; j0 < m; j0 += 512) {
         float2 c[8];
+        double cz[8] = {};
 #pragma unroll
-        for (int u = 0; u < 8; ++u) c[u] = g.xy_at(min(j0 + u * 64 + lane, m - 1));
+        for (int u = 0; u < 8; ++u) { const int j = min(j0 + u * 64 + lane, m - 1); c[u] = g.xy_at(j); if constexpr (D3) cz[u] = z64[j]; }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
-            const double s = bl_dist2(px, py, c[u]);
+            const double s = bl_dist<D3>(px, py, pz, c[u], cz[u]);
             lane_min = (j0 + u * 64 + lane < m) ? __builtin_fmin(lane_min, s) : lane_min;
         }
     }
@@ -984,13 +1093,14 @@ __device__ __forceinline__ BlNear bl_search_wave(const BlGridView &g, double px,
     bool inexact = false;
     for (int j0 = 0; j0 < m; j0 += 512) {
         float2 c[8];
+        double cz[8] = {};
         int it[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) { const int j = min(j0 + u * 64 + lane, m - 1); c[u] = g.xy_at(j); it[u] = g.item_at(j); }
+        for (int u = 0; u < 8; ++u) { const int j = min(j0 + u * 64 + lane, m - 1); c[u] = g.xy_at(j); it[u] = g.item_at(j); if constexpr (D3) cz[u] = z64[j]; }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int j = j0 + u * 64 + lane;
-            const double s = bl_dist2(px, py, c[u]);
+            const double s = bl_dist<D3>(px, py, pz, c[u], cz[u]);
             const bool near = j < m && s <= near_limit;
             cand = near ? min(cand, (it[u] << 15) | j) : cand;          // (column, then position: both below 32768)
             inexact = inexact || (near && s != s_min);
@@ -1000,14 +1110,19 @@ __device__ __forceinline__ BlNear bl_search_wave(const BlGridView &g, double px,
         const double d_min = sqrt(s_min);
         cand = 0x7FFFFFFF;
         for (int j = lane; j < m; j += 64) {
-            const double s = bl_dist2(px, py, g.xy_at(j));
+            const double s = bl_dist<D3>(px, py, pz, g.xy_at(j), D3 ? z64[j] : 0.0);
             if (s <= near_limit && sqrt(s) == d_min) cand = min(cand, (g.item_at(j) << 15) | j);
         }
     }
     const int win = wave_min(cand);
     const float2 c = g.xy_at(win & 0x7FFF);
+    if constexpr (D3) r.z = z64[win & 0x7FFF];
     r.s = s_min; r.zx = c.x; r.zy = c.y; r.col = win >> 15;
     return r;
+}
+__device__ __forceinline__ BlNear bl_search_wave(const BlGridView &g, double px, double py, int m, int lane)
+{
+    return bl_wave_search<false>(g, 0, nullptr, px, py, 0.0, m, lane, true);
 }
 
 // ---- the kernel ----------------------------------------------------------------------------------------------------
@@ -2103,127 +2218,21 @@ __global__ void k_peek_third_batch(TrackerDev t, BatchDev bd, const double *seat
 //      (bl3_lds_dwords_max(max_det) dwords from its start) follows, in HBM only:
 //   [.., + 2 MP)       the third coordinate in cell order as the f64 the caller gave
 // No candidate lists: bl_cell_list drops a detection that is farther IN THE PLANE at every point of the cell, and in three
-// dimensions such a detection can still be the nearest.  The search is the 3 x 3 block's, in every frame.
+// dimensions such a detection can still be the nearest.  The search is the 3 x 3 block's, in every frame: the 3-D instances
+// of the planar link's bl_block_search and bl_wave_search (BlNear3, bl_dist3 / bl_dist3f and bl3_band stand beside them).
 // Why the f64 plane stays in HBM: the two LDS buffers, the three key tables, the id table and the set model take 140 KB at
 // max_det = 2048; an f64 plane in both buffers would add 33 KB, the f32 plane adds 16 (157 KB with the static part, of 160).
 // A lane's float-stage winner costs one 8-byte load from the tail before its claim key is built; the exact wave search
 // reads the tail coalesced, in cell order like the centres.
 
-// One workgroup per frame, as k_bgrid: the same cells and the same counting sort (a frame's centres come out in the same
-// order), without the candidate lists.  The bounding box, the cells' size, the cell of a detection, the scan of the counts
-// and the scatter are k_bgrid's lines VERBATIM (k_bgrid itself is frozen by the tests that read k_batch's listing from the
-// same header; once that lifts, the two should share one __device__ body) -- a fix to the binning there belongs here too.
-// New here: z[], `wide` / s_wide and header word 7, the z32 / z64 planes, and the copy-out's length.  A detection's third coordinate is read where its centre is (slots at or beyond the
-// frame's count are never read) and follows it into its cell: rounded into the LDS part, as it is into the tail -- which
-// does not pass through this kernel's LDS (the block's image here is the LDS part alone).
+// One workgroup per frame: bl_bin_frame's 3-D instance.  The cells lie in the plane and the counting sort is the planar
+// link's, so a frame's centres come out in the order k_bgrid gives them; a detection's third coordinate follows its centre
+// into its cell, rounded to f32 in the LDS part and as given in the tail (which this kernel stores straight to HBM: its
+// block image in LDS is the LDS part alone, and the copy-out ends there).
 __global__ __launch_bounds__(BG_THREADS) void k_bgrid3(const float *__restrict__ det_all, const double *__restrict__ third_all,
                                                        const int32_t *__restrict__ det_count, int max_det, char *grid, unsigned grid_stride)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t s_out[];
-    __shared__ int s_cnt[64 * 64];
-    __shared__ float s_red[4][4];
-    __shared__ int s_wave_sum[4];
-    __shared__ int s_wide;
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const float *det = det_all + (size_t)f * max_det * 5;
-    const double *third = third_all + (size_t)f * max_det;
-    int m = det_count[f];
-    m = m < 0 ? 0 : (m > max_det ? max_det : m);
-    const int G = bl_grid_n(m), cells = G * G;
-    unsigned short *start16 = reinterpret_cast<unsigned short *>(s_out + 16);
-    float2 *xy = reinterpret_cast<float2 *>(s_out + 16 + bl_start_dwords(G));
-    unsigned short *items = reinterpret_cast<unsigned short *>(s_out + 16 + bl_start_dwords(G) + 2 * bl_mp(m));
-    float *z32 = reinterpret_cast<float *>(s_out + bl_list_off(m));
-    double *z64 = reinterpret_cast<double *>(grid + (size_t)grid_stride * f + 4 * (size_t)bl3_lds_dwords_max(max_det));
-    float x[BG_PER], y[BG_PER];
-    double z[BG_PER];
-    bool wide = false;
-#pragma unroll
-    for (int k = 0; k < BG_PER; ++k) {
-        const int j = tid + k * BG_THREADS;
-        x[k] = j < m ? det[(size_t)j * 5] : 0.f;
-        y[k] = j < m ? det[(size_t)j * 5 + 1] : 0.f;
-        z[k] = j < m ? third[j] : 0.0;
-        wide = wide || !(fabs(z[k]) < 4096.0);
-    }
-    for (int c = tid; c < cells; c += BG_THREADS) s_cnt[c] = 0;
-    if (tid == 0) s_wide = 0;
-    float lo_x = 3.0e38f, lo_y = 3.0e38f, hi_x = -3.0e38f, hi_y = -3.0e38f;
-#pragma unroll
-    for (int k = 0; k < BG_PER; ++k)
-        if (tid + k * BG_THREADS < m) { lo_x = fminf(lo_x, x[k]); hi_x = fmaxf(hi_x, x[k]); lo_y = fminf(lo_y, y[k]); hi_y = fmaxf(hi_y, y[k]); }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        lo_x = fminf(lo_x, __shfl_xor(lo_x, d)); hi_x = fmaxf(hi_x, __shfl_xor(hi_x, d));
-        lo_y = fminf(lo_y, __shfl_xor(lo_y, d)); hi_y = fmaxf(hi_y, __shfl_xor(hi_y, d));
-    }
-    if (lane == 0) { s_red[0][w] = lo_x; s_red[1][w] = hi_x; s_red[2][w] = lo_y; s_red[3][w] = hi_y; }
-    __syncthreads();
-    if (wide) s_wide = 1;
-    lo_x = s_red[0][0]; hi_x = s_red[1][0]; lo_y = s_red[2][0]; hi_y = s_red[3][0];
-    for (int k = 1; k < 4; ++k) {
-        lo_x = fminf(lo_x, s_red[0][k]); hi_x = fmaxf(hi_x, s_red[1][k]);
-        lo_y = fminf(lo_y, s_red[2][k]); hi_y = fmaxf(hi_y, s_red[3][k]);
-    }
-    if (m == 0) { lo_x = lo_y = 0.f; hi_x = hi_y = 1.f; }
-    const float extent = fmaxf(fmaxf(hi_x - lo_x, hi_y - lo_y), 1.0f);
-    const float cell = extent / (float)(G - 2), inv = 1.0f / cell;
-    const float x0 = lo_x - cell, y0 = lo_y - cell;
-    if (tid < 16) s_out[tid] = 0;
-    __syncthreads();
-    if (tid == 0) {
-        float *h = reinterpret_cast<float *>(s_out);
-        h[0] = x0; h[1] = y0; h[2] = cell; h[3] = inv;
-        s_out[4] = (uint32_t)G; s_out[5] = (uint32_t)m; s_out[6] = 0; s_out[7] = (uint32_t)s_wide;
-    }
-    int cell_of[BG_PER];
-#pragma unroll
-    for (int k = 0; k < BG_PER; ++k) {
-        int cx = (int)floorf((x[k] - x0) * inv), cy = (int)floorf((y[k] - y0) * inv);
-        cx = cx < 0 ? 0 : (cx > G - 1 ? G - 1 : cx);
-        cy = cy < 0 ? 0 : (cy > G - 1 ? G - 1 : cy);
-        cell_of[k] = cy * G + cx;
-        if (tid + k * BG_THREADS < m) atomicAdd(&s_cnt[cell_of[k]], 1);
-    }
-    __syncthreads();
-    // exclusive scan of the counts, as k_bgrid
-    const int K = cells / BG_THREADS;
-    int local[16], sum = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (k < K) { local[k] = sum; sum += s_cnt[tid * K + k]; }
-    int incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
-    if (lane == 63) s_wave_sum[w] = incl;
-    __syncthreads();
-    int before = incl - sum;
-    for (int k = 0; k < w; ++k) before += s_wave_sum[k];
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (k < K) {
-            const int at = before + local[k];
-            s_cnt[tid * K + k] = at;
-            start16[tid * K + k] = (unsigned short)at;
-        }
-    if (tid == BG_THREADS - 1) { start16[cells] = (unsigned short)m; start16[cells + 1] = 0; }
-    for (int j = m + tid; j < bl_mp(m); j += BG_THREADS) { xy[j] = make_float2(1.0e30f, 1.0e30f); items[j] = 0; z32[j] = 0.f; z64[j] = 0.0; }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < BG_PER; ++k) {
-        const int j = tid + k * BG_THREADS;
-        if (j < m) {
-            const int at = atomicAdd(&s_cnt[cell_of[k]], 1);
-            items[at] = (unsigned short)j;
-            xy[at] = make_float2(x[k], y[k]);
-            z32[at] = (float)z[k];
-            z64[at] = z[k];
-        }
-    }
-    __syncthreads();
-    uint4 *out = reinterpret_cast<uint4 *>(grid + (size_t)grid_stride * f);
-    const uint4 *img = reinterpret_cast<const uint4 *>(s_out);
-    for (int i = tid; i < bl3_lds_dwords(m) / 4; i += BG_THREADS) out[i] = img[i];
+    bl_bin_frame<true>(det_all, third_all, det_count, max_det, grid, grid_stride);
 }
 
 // ---- a 3-D track in registers: the point the reference keeps in objects[id], the box, id, counters -------------------
@@ -2235,206 +2244,6 @@ struct Bl3Seat {
 };
 // rest format: px, py, the box, id, gone, rank and the seat flag where k_batch keeps them in BatchDev (k_peek_batch reads both),
 // history length and mode 0, pz in seat3 f64 [seat_cap]
-
-struct BlNear3 { double s, z; float zx, zy; int col; bool done; };
-
-__device__ __forceinline__ double bl_dist3(double px, double py, double pz, float2 c, double cz)
-{
-    // cdist's order (luminosity_model.cdist; rowmin_wave<.., true>): dx * dx + dy * dy + dz * dz, summed left to right
-    const double dx = px - (double)c.x;
-    const double dy = py - (double)c.y;
-    const double dz = pz - cz;
-    double s = dx * dx;
-    s = s + dy * dy;
-    s = s + dz * dz;
-    return s;
-}
-__device__ __forceinline__ float bl_dist3f(float fx, float fy, float fz, float2 c, float cz)
-{
-    const float dx = fx - c.x, dy = fy - c.y, dz = fz - cz;
-    return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-}
-// Float error band of a 3-D squared distance, for |px|, |py|, |pz| and every |third| below 4096 (k_bgrid3 flags a frame
-// with a larger one, the caller tests pz).  (float)px, (float)py and (float)pz are off by at most 2^-24 * 4096 = 2.4e-4; the
-// centres are float already, but the candidate's third coordinate was ROUNDED to float as well: dz is off by 4.9e-4, dx
-// and dy by 2.4e-4.  Unlike a planar distance inside a 3 x 3 block, dz has no bound but 8192, so the error is taken relative
-// to the distance: |s_f - s| <= 2 (|dx| + |dy|) 2.4e-4 + 2 |dz| 4.9e-4 + 4 * 2^-24 s <= 9.8e-4 * sqrt(3 s) + 2.4e-7 s, and with
-// a sqrt(s) <= t + a^2 s / (4 t) at t = 0.05: <= 0.05 + 1.5e-5 s; the key drops 2^-19 s more: e(s) <= 0.05 + 1.7e-5 s.
-// A detection that is truly as near as the float winner (float distance b) has a float distance of at most
-// b + 2 e(s_winner) <= b + 0.1002 + 3.5e-5 b: the band below is that with a margin (twice in the constant, 1.4 x in the slope).
-__device__ __forceinline__ float bl3_band(float best) { return best + (0.2f + 5e-5f * best); }
-
-// bl_search_block in three dimensions: float keys of dx^2 + dy^2 + dz^2 over the 3 x 3 cells.  "Nothing outside the block
-// is as near" stays a test in the PLANE: a detection's 3-D distance is never below its planar distance, so one that lies
-// beyond the block's boundary in the plane is farther than the boundary in space.  z32: dword offset of the block's f32
-// plane in LDS; z64: its f64 plane in HBM.
-__device__ __forceinline__ BlNear3 bl_search_block3(const BlGridView &g, int z32, const double *__restrict__ z64, double px, double py,
-                                                    double pz, int m)
-{
-    constexpr int R = 3, C = 5;
-    const int G = g.G;
-    const float fx = (float)px, fy = (float)py, fz = (float)pz;
-    int cx = (int)floorf((fx - g.x0) * g.inv), cy = (int)floorf((fy - g.y0) * g.inv);
-    const bool in_grid = cx >= 0 && cx < G && cy >= 0 && cy < G;
-    cx = cx < 0 ? 0 : (cx > G - 1 ? G - 1 : cx);
-    cy = cy < 0 ? 0 : (cy > G - 1 ? G - 1 : cy);
-    const int xl = max(cx - 1, 0), xh = min(cx + 1, G - 1), yl = max(cy - 1, 0), yh = min(cy + 1, G - 1);
-    int a[R], b[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int iy = min(yl + r, G - 1);
-        a[r] = g.start_at(iy * G + xl);
-        b[r] = g.start_at(iy * G + xh + 1);
-        if (yl + r > yh) b[r] = a[r];
-    }
-    // (every read issued before the first is used; a slot beyond the end of its run reads what follows in LDS -- inside the
-    // block's LDS part: a run starts at or below m, and entry m + 4 lies in the padding or in the next plane -- and is masked)
-    float2 c[R * C];
-    float cz[R * C];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const float2 *run = reinterpret_cast<const float2 *>(bl_u32(g.xy)) + a[r];
-        const float *runz = reinterpret_cast<const float *>(bl_u32(z32)) + a[r];
-#pragma unroll
-        for (int j = 0; j < C; ++j) { c[C * r + j] = run[j]; cz[C * r + j] = runz[j]; }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    uint32_t lo = 0xFFFFFFFFu, hi = 0xFFFFFFFFu;
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int j = 0; j < C; ++j) {
-            const float d2 = bl_dist3f(fx, fy, fz, c[C * r + j], cz[C * r + j]);
-            uint32_t key = (__float_as_uint(d2) & 0xFFFFFFF0u) | (uint32_t)(C * r + j);
-            key = a[r] + j < b[r] ? key : 0xFFFFFFFFu;
-            hi = bl_med3(lo, hi, key);
-            lo = min(lo, key);
-        }
-    int q_extra = 0;
-    bool more = false;
-#pragma unroll
-    for (int r = 0; r < R; ++r) more = more || (b[r] - a[r] > C);
-    if (more) {
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-            for (int qq = a[r] + C; qq < b[r]; ++qq) {
-                const float d2 = bl_dist3f(fx, fy, fz, g.xy_at(qq), reinterpret_cast<const float *>(bl_u32(z32))[qq]);
-                const uint32_t key = (__float_as_uint(d2) & 0xFFFFFFF0u) | 15u;
-                q_extra = key < lo ? qq : q_extra;
-                hi = bl_med3(lo, hi, key);
-                lo = min(lo, key);
-            }
-    }
-    const float best = __uint_as_float(lo & 0xFFFFFFF0u), second = __uint_as_float(hi & 0xFFFFFFF0u);
-    const float band = bl3_band(best);
-    const int slot = (int)(lo & 15u);
-    const int run = slot >= 2 * C ? 2 : (slot >= C ? 1 : 0);
-    const int bq = slot == 15 ? q_extra : (run == 2 ? a[2] : (run == 1 ? a[1] : a[0])) + slot - C * run;
-    const bool found = lo != 0xFFFFFFFFu;
-    const double wz = z64[found ? bq : 0];               // (the winner's exact third coordinate: requested at once)
-    const float reach = 0.998f * g.cell;
-    bool inside = in_grid && band < reach * reach;
-    if (!inside) {
-        const float big = 3.0e38f;
-        float bound = big;
-        if (xl > 0) bound = fminf(bound, fx - (g.x0 + (float)xl * g.cell));
-        if (xh < G - 1) bound = fminf(bound, (g.x0 + (float)(xh + 1) * g.cell) - fx);
-        if (yl > 0) bound = fminf(bound, fy - (g.y0 + (float)yl * g.cell));
-        if (yh < G - 1) bound = fminf(bound, (g.y0 + (float)(yh + 1) * g.cell) - fy);
-        bound -= 1e-3f * g.cell;
-        inside = bound >= big * 0.5f || (bound > 0.f && bound * bound > band);
-    }
-    const float2 cw = g.xy_at(found ? bq : 0);
-    BlNear3 r;
-    r.s = bl_dist3(px, py, pz, cw, wz);
-    r.z = wz;
-    r.zx = cw.x; r.zy = cw.y;
-    r.col = g.item_at(found ? bq : 0);
-    r.done = found && inside && !(second <= band);
-    return r;
-}
-
-// bl_search_wave in three dimensions: ONE track by the whole wave over every detection of the frame.  The float pre-pass
-// (frames of at most 512 detections, and only where the band holds: `narrow`) reads the f32 plane in LDS; the exact passes
-// read the f64 plane in HBM, coalesced.  The same three passes and tie rule: the smallest s; the lowest column within 2^-48
-// of it; the rounded roots only if some s differs from the smallest.  px, py, pz, narrow, the result: wave-uniform.
-__device__ __forceinline__ BlNear3 bl_search_wave3(const BlGridView &g, int z32, const double *__restrict__ z64, double px, double py,
-                                                   double pz, int m, int lane, bool narrow)
-{
-    const double inf = __longlong_as_double(0x7FF0000000000000ll);
-    BlNear3 r;
-    r.done = true;
-    if (m <= 512 && narrow) {
-        const float fx = (float)px, fy = (float)py, fz = (float)pz;
-        float sf[8];
-        int lo = 0x7F800000;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int j = u * 64 + lane, jc = min(j, m - 1);
-            sf[u] = j < m ? bl_dist3f(fx, fy, fz, g.xy_at(jc), reinterpret_cast<const float *>(bl_u32(z32))[jc]) : 3.0e38f;
-            lo = min(lo, (int)__float_as_uint(sf[u]));
-        }
-        const float best = __uint_as_float((uint32_t)wave_min(lo));
-        const float band = bl3_band(best);
-        int n_near = 0, jn = 0;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const unsigned long long b = __ballot(sf[u] <= band);
-            n_near += (int)__popcll(b);
-            if (b) jn = u * 64 + __builtin_ctzll(b);
-        }
-        if (n_near == 1) {
-            const float2 c = g.xy_at(jn);
-            r.z = z64[jn];
-            r.s = bl_dist3(px, py, pz, c, r.z); r.zx = c.x; r.zy = c.y; r.col = g.item_at(jn);
-            return r;
-        }
-    }
-    double lane_min = inf;
-    for (int j0 = 0; j0 < m; j0 += 512) {
-        float2 c[8];
-        double cz[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { const int j = min(j0 + u * 64 + lane, m - 1); c[u] = g.xy_at(j); cz[u] = z64[j]; }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const double s = bl_dist3(px, py, pz, c[u], cz[u]);
-            lane_min = (j0 + u * 64 + lane < m) ? __builtin_fmin(lane_min, s) : lane_min;
-        }
-    }
-    const double s_min = wave_min(lane_min);
-    const double near_limit = s_min + s_min * 0x1p-48;
-    int cand = 0x7FFFFFFF;
-    bool inexact = false;
-    for (int j0 = 0; j0 < m; j0 += 512) {
-        float2 c[8];
-        double cz[8];
-        int it[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { const int j = min(j0 + u * 64 + lane, m - 1); c[u] = g.xy_at(j); it[u] = g.item_at(j); cz[u] = z64[j]; }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int j = j0 + u * 64 + lane;
-            const double s = bl_dist3(px, py, pz, c[u], cz[u]);
-            const bool near = j < m && s <= near_limit;
-            cand = near ? min(cand, (it[u] << 15) | j) : cand;
-            inexact = inexact || (near && s != s_min);
-        }
-    }
-    if (__any(inexact)) {
-        const double d_min = sqrt(s_min);
-        cand = 0x7FFFFFFF;
-        for (int j = lane; j < m; j += 64) {
-            const double s = bl_dist3(px, py, pz, g.xy_at(j), z64[j]);
-            if (s <= near_limit && sqrt(s) == d_min) cand = min(cand, (g.item_at(j) << 15) | j);
-        }
-    }
-    const int win = wave_min(cand);
-    const float2 c = g.xy_at(win & 0x7FFF);
-    r.z = z64[win & 0x7FFF];
-    r.s = s_min; r.zx = c.x; r.zy = c.y; r.col = win >> 15;
-    return r;
-}
 
 struct BlKernArgs3 {
     TrackerDev t;
@@ -2576,7 +2385,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch3(BlKernArgs3 ka)
         BlNear3 nr{0.0, 0.0, 0.f, 0.f, 0, true};
         unsigned long long key = 0;
         if (propose) {
-            if (narrow) nr = bl_search_block3(gv, z32, z64, S.px, S.py, S.pz, m);
+            if (narrow) nr = bl_block_search<true>(gv, z32, z64, S.px, S.py, S.pz, m);
             else nr.done = false;
         }
         {
@@ -2588,7 +2397,7 @@ __global__ __launch_bounds__(BL_THREADS) void k_batch3(BlKernArgs3 ka)
                 const int l = __builtin_ctzll(todo);
                 todo &= todo - 1ull;
                 const bool nw = __builtin_amdgcn_readlane((int)narrow, l) != 0;
-                const BlNear3 w = bl_search_wave3(gv, z32, z64, lane_value(S.px, l), lane_value(S.py, l), lane_value(S.pz, l), m, lane, nw);
+                const BlNear3 w = bl_wave_search<true>(gv, z32, z64, lane_value(S.px, l), lane_value(S.py, l), lane_value(S.pz, l), m, lane, nw);
                 if (lane == l) nr = w;
             }
         }
