@@ -808,6 +808,39 @@ size_t ysmr_png_stream_bytes_max(int width, int height);
 int ysmr_png_deflate(void *stream, const uint8_t *rgb_dev, int width, int height, void *workspace_dev, size_t workspace_bytes,
                      uint8_t *out_dev, size_t out_bytes, unsigned long long *out_len_dev);
 
+/* ADDED under ABI 15 as well: the same scanline bytes as a smaller stream.  78 01, ONE deflate block with BFINAL = 1 and
+ * BTYPE = 10 (a dynamic Huffman code, RFC 1951, 3.2.7), the end-of-block code, padding to a byte, Adler-32 big-endian.
+ * Parse -- the pieces are ysmr_png_deflate's, and a piece is parsed on its own, greedily, with FOUR distances: 3, S, S - 3 and
+ * S + 3 (the pixel before, above, above-right, above-left).  A distance d is eligible at stream position p when d <= 32768 and
+ * p >= d; sources are positions of the scanline stream, they cross row ends and include the filter bytes.  At byte i, every
+ * length capped at 258 and at the piece's end, the longest eligible match wins; it must have 3 bytes at distance 3 and 4 at
+ * the other three; ties go in the order 3, S, S - 3, S + 3; no match: the literal.  With the distances 3 and S alone this is
+ * exactly ysmr_png_deflate's rule.
+ * Codes -- the histogram of the 286 literal/length symbols (one end of block among them) and of the 30 distance symbols over
+ * the whole parse; integer atomics only, so two calls give the same bytes.  While fewer than two distance symbols are used,
+ * the lowest unused one counts once (zlib's rule: two distance codes at least).  Code lengths as ysmr_png_code_lengths makes
+ * them, at most 15 bits (7 for the code-length alphabet), codes canonical (RFC 1951, 3.2.2).  The header: HLIT, HDIST, HCLEN
+ * without trailing zero lengths, then the two length sequences run-length coded as ONE sequence, run by run of equal values:
+ * r zeros are 18 (up to 138) while r >= 11, then 17 if r >= 3, then single zeros; r lengths v > 0 are v once, then 16 (up
+ * to 6) while r >= 3 remain, then single v's (csrc/png_codes.h; tests/png_dynamic_model.py restates the stream).
+ * ysmr_png_dynamic_stream_bytes_max: ceil((4498 + 15 H S + 15) / 8) + 6 -- 4498 bits is the longest header, no code spends
+ * more than 15 bits on a byte, the end of block at most 15 -- rounded up to a word, plus a word for the packer; out_dev must
+ * hold that much and is zeroed up to it.  Sizes, alignments and status codes as for ysmr_png_deflate; the calls only
+ * enqueue work on `stream`. */
+size_t ysmr_png_dynamic_workspace_bytes(int width, int height);
+size_t ysmr_png_dynamic_stream_bytes_max(int width, int height);
+int ysmr_png_deflate_dynamic(void *stream, const uint8_t *rgb_dev, int width, int height, void *workspace_dev, size_t workspace_bytes,
+                             uint8_t *out_dev, size_t out_bytes, unsigned long long *out_len_dev);
+
+/* Host only, no GPU touched: the code lengths ysmr_png_deflate_dynamic gives the histogram counts[0 .. n_symbols) under the
+ * limit max_bits, from the same text the kernel compiles (csrc/png_codes.h).  The used symbols (count > 0) are sorted by
+ * (count, symbol); Huffman's tree is built with two queues, the leaf taken on a tie; leaves deeper than max_bits are counted
+ * at max_bits and the Kraft sum is repaired one unit a round (a code of max_bits bits less, one of the longest shorter length
+ * i less, two of i + 1 more); the lengths go, shortest first, to the symbols in descending (count, symbol).  Where Huffman's
+ * tree fits the limit the total cost is the optimum.  One used symbol has length 1, an unused one 0.
+ * 1 <= n_symbols <= 288, 1 <= max_bits <= 15, and no more than 2^max_bits used symbols, else YSMR_ERR_ARG. */
+int ysmr_png_code_lengths(const uint32_t *counts, int n_symbols, int max_bits, uint8_t *lengths_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,11 +2,12 @@
 per figure the device time (upload of the small arrays, kernels), the canvas download, the lettering + PNG encoding and
 the wall time of the public function; the matplotlib scatter loop of the reference's overview on the same table where
 matplotlib is importable; evaluate_tracks with the three keys on and off.  ``--png device`` runs the public functions and
-evaluate_tracks with 'hip png on device'; ``--png-ab`` runs only the comparison of the two PNG paths: per figure the wall
-time of the public function on either path, alternating, the file sizes, and zlib level 1 on the same scanlines.
+evaluate_tracks with 'hip png on device'; ``--png-ab`` runs only the comparison of the three PNG paths (host, device with
+the fixed code, device with 'dynamic'): per figure the wall time of the public function on every path, alternating, the
+file sizes, and zlib level 1 on the same scanlines.
 
   python3 scripts/plots_e2e.py [--frames 1920] [--tmp DIR] [--png host|device] > profiles/plots_e2e.log
-  python3 scripts/plots_e2e.py --png-ab >> profiles/png_e2e.log
+  python3 scripts/plots_e2e.py --frames 600 --png-ab >> profiles/png_dynamic_e2e.log
 """
 import argparse
 import os
@@ -120,25 +121,29 @@ def read_scanlines(path):
 
 
 def png_ab(figures, work, reps):
-    """``figures``: (name, draw(path, png_on_device)).  Per figure and repetition the wall time of ``draw`` on the host path
-    and on the device path, one after the other; then the two files' sizes, zlib level 1 on the same scanlines (what the
-    host path's IDAT is) and whether the two files hold the same pixels."""
+    """``figures``: (name, draw(path, png_on_device)).  Per figure and repetition the wall time of ``draw`` on the host path,
+    on the device path with the fixed code and on the device path with the dynamic code ('dynamic'), one after the other;
+    then the three files' sizes, zlib level 1 on the same scanlines (what the host path's IDAT is) and whether the three
+    files hold the same pixels."""
     import zlib
     for name, draw in figures:
-        host, device = os.path.join(work, name + "_host.png"), os.path.join(work, name + "_device.png")
-        draw(host, False), draw(device, True)                                          # warm-up of either path
+        host, device, dynamic = (os.path.join(work, name + tail) for tail in ("_host.png", "_device.png", "_dynamic.png"))
+        draw(host, False), draw(device, True), draw(dynamic, "dynamic")                # warm-up of every path
         for rep in range(reps):
             _, t_host = timed(lambda: draw(host, False))
             _, t_dev = timed(lambda: draw(device, True))
-            print("rep {}: {:17s} wall time, png on the host {:7.1f} ms, on the device {:7.1f} ms".format(rep, name, t_host, t_dev), flush=True)
-        (head_h, raw_h), (head_d, raw_d) = read_scanlines(host), read_scanlines(device)
+            _, t_dyn = timed(lambda: draw(dynamic, "dynamic"))
+            print("rep {}: {:17s} wall time, png on the host {:7.1f} ms, on the device {:7.1f} ms, on the device 'dynamic' {:7.1f} ms".format(
+                rep, name, t_host, t_dev, t_dyn), flush=True)
+        (head_h, raw_h), (head_d, raw_d), (head_y, raw_y) = read_scanlines(host), read_scanlines(device), read_scanlines(dynamic)
         t0 = time.perf_counter()
         level1 = len(zlib.compress(raw_h, 1))
         t_zlib = (time.perf_counter() - t0) * 1e3
-        print("       {:17s} files: host {} bytes, device {} bytes (ratio {:.3f}); zlib level 1 on the {:.1f} MB of scanlines: {} bytes in {:.1f} ms "
-              "on this host's CPU; same header and pixels: {}".format(name, os.path.getsize(host), os.path.getsize(device),
-                                                                      os.path.getsize(device) / os.path.getsize(host), len(raw_h) / 1e6, level1,
-                                                                      t_zlib, head_h == head_d and raw_h == raw_d), flush=True)
+        sizes = [os.path.getsize(f) for f in (host, device, dynamic)]
+        print("       {:17s} files: host {} bytes, device {} bytes (ratio {:.3f}), device 'dynamic' {} bytes (ratio {:.3f}); zlib level 1 on the "
+              "{:.1f} MB of scanlines: {} bytes in {:.1f} ms on this host's CPU; same header and pixels: {}".format(
+                  name, sizes[0], sizes[1], sizes[1] / sizes[0], sizes[2], sizes[2] / sizes[0], len(raw_h) / 1e6, level1, t_zlib,
+                  head_h == head_d == head_y and raw_h == raw_d == raw_y), flush=True)
 
 
 def track_figures(out, stats, settings):
@@ -169,9 +174,11 @@ def device_png_phases(out, stats, settings, reps):
         for rep in range(reps + 1):
             _, t_stamp = timed(lambda: pf.device_stamp(rgb, stamps))
             stream, t_deflate = timed(lambda: pf.device_deflate(rgb))
+            dynamic, t_dynamic = timed(lambda: pf.device_deflate(rgb, dynamic=True))
             if rep:
                 print("rep {}: overview canvas: ysmr_plot_stamp of {} records {:.2f} ms, ysmr_png_deflate with its downloads {:.2f} ms "
-                      "({} bytes)".format(rep - 1, len(stamps.records), t_stamp, t_deflate, len(stream)), flush=True)
+                      "({} bytes), ysmr_png_deflate_dynamic with its downloads {:.2f} ms ({} bytes)".format(
+                          rep - 1, len(stamps.records), t_stamp, t_deflate, len(stream), t_dynamic, len(dynamic)), flush=True)
 
 
 def matplotlib_loop(out, stats, settings, work):
@@ -246,5 +253,5 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--tmp", default=None, help="where the clip and the figures go (removed afterwards)")
     ap.add_argument("--png", choices=("host", "device"), default="host", help="where the PNG files are made ('hip png on device')")
-    ap.add_argument("--png-ab", action="store_true", help="only compare the two PNG paths: times, file sizes, zlib level 1")
+    ap.add_argument("--png-ab", action="store_true", help="only compare the three PNG paths: times, file sizes, zlib level 1")
     run(ap.parse_args())

@@ -4,7 +4,8 @@ paint with the canvas download, lettering, PNG -- for per-track tables of 500 an
 upstream: seaborn is needed for that.
 
   python3 scripts/violin_e2e.py [--frames 600] [--tmp DIR] [--png host|device] > profiles/violin_e2e.log
-  python3 scripts/violin_e2e.py --png-ab >> profiles/png_e2e.log     (only the two PNG paths, alternating: times and sizes)
+  python3 scripts/violin_e2e.py --png-ab >> profiles/png_dynamic_e2e.log     (only the three PNG paths -- host, device, device 'dynamic' --
+                                                                              alternating: times and sizes)
 """
 import argparse
 import os
@@ -117,5 +118,5 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--tmp", default=None, help="where the clip and the figures go (removed afterwards)")
     ap.add_argument("--png", choices=("host", "device"), default="host", help="where the PNG files are made ('hip png on device')")
-    ap.add_argument("--png-ab", action="store_true", help="only compare the two PNG paths: times, file sizes, zlib level 1")
+    ap.add_argument("--png-ab", action="store_true", help="only compare the three PNG paths: times, file sizes, zlib level 1")
     sys.exit(run(ap.parse_args()))

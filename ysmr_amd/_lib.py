@@ -65,7 +65,8 @@ EXPORTS = ("ysmr_abi_version", "ysmr_last_error", "ysmr_detect_workspace_bytes",
            "ysmr_mjpeg_workspace_bytes", "ysmr_mjpeg_batch", "ysmr_violin_workspace_bytes", "ysmr_violin_stats", "ysmr_plot_violins",
            "ysmr_mjpeg_decode_workspace_bytes", "ysmr_mjpeg_decode_batch",
            "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_batch_sync", "ysmr_mjpeg_decode_sync_geometry",
-           "ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_png_deflate", "ysmr_plot_stamp")
+           "ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_png_deflate", "ysmr_plot_stamp",
+           "ysmr_png_dynamic_workspace_bytes", "ysmr_png_dynamic_stream_bytes_max", "ysmr_png_deflate_dynamic", "ysmr_png_code_lengths")
 
 #: numpy view of ``ysmr_mark`` (16 bytes): one track position of one frame of the annotated video
 MARK_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("track_id", "<u4"), ("style", "<u4")])
@@ -256,8 +257,14 @@ def lib():
     L.ysmr_png_stream_bytes_max.restype = ctypes.c_size_t
     L.ysmr_png_deflate.argtypes = [vp, vp, ci, ci, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]
     L.ysmr_plot_stamp.argtypes = [vp, vp, ci, ci, vp, ci, vp, ctypes.c_size_t]
+    L.ysmr_png_dynamic_workspace_bytes.argtypes = [ci, ci]
+    L.ysmr_png_dynamic_workspace_bytes.restype = ctypes.c_size_t
+    L.ysmr_png_dynamic_stream_bytes_max.argtypes = [ci, ci]
+    L.ysmr_png_dynamic_stream_bytes_max.restype = ctypes.c_size_t
+    L.ysmr_png_deflate_dynamic.argtypes = [vp, vp, ci, ci, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]
+    L.ysmr_png_code_lengths.argtypes = [vp, ci, ci, vp]
     for name in EXPORTS:
-        if name not in ("ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_sync_geometry", "ysmr_mjpeg_decode_workspace_bytes", "ysmr_violin_workspace_bytes", "ysmr_mjpeg_workspace_bytes", "ysmr_plot_workspace_bytes", "ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
+        if name not in ("ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_png_dynamic_workspace_bytes", "ysmr_png_dynamic_stream_bytes_max", "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_sync_geometry", "ysmr_mjpeg_decode_workspace_bytes", "ysmr_violin_workspace_bytes", "ysmr_mjpeg_workspace_bytes", "ysmr_plot_workspace_bytes", "ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
                         "ysmr_rows_sort_workspace_bytes", "ysmr_rows_csv_bound", "ysmr_rows_stream_count",
                         "ysmr_mean_threshold_state_bytes"):
             getattr(L, name).restype = ci

@@ -75,7 +75,9 @@ def _figures(out, stats, settings, title, save_path, device, logger, df_stats=No
     error in the log; the tables and the csv files do not depend on it."""
     from . import plot_functions as pf
     px = settings["pixel per micrometre"]
-    on_device = bool(settings.get("hip png on device"))      # lettering and deflate in csrc/png.hip; absent: the host path
+    # lettering and deflate in csrc/png.hip: absent or false -- the host path; 'dynamic' (any case) -- the dynamic stream,
+    # the smaller files; anything else true -- the fixed code
+    on_device = {None: False, "fixed": True, "dynamic": "dynamic"}[pf.png_mode(settings.get("hip png on device"))]
     jobs = []
     if settings.get("save angle distribution plot / bins"):
         jobs.append(("angle_histogram", lambda path: pf.angle_distribution_plot(

@@ -52,9 +52,19 @@ def write_png(path, rgb, dpi=300):
         fh.write(chunk(b"IEND", b""))
 
 
-def device_deflate(rgb_device):
+def png_mode(png_on_device):
+    """What ``png_on_device`` (and the settings key 'hip png on device') asks for: ``None`` -- the host writes the file;
+    ``'fixed'`` -- any true value: ``ysmr_png_deflate``; ``'dynamic'`` -- the string 'dynamic' in any case:
+    ``ysmr_png_deflate_dynamic``, the smaller file."""
+    if isinstance(png_on_device, str) and png_on_device.strip().lower() == "dynamic":
+        return "dynamic"
+    return "fixed" if png_on_device else None
+
+
+def device_deflate(rgb_device, dynamic=False):
     """``ysmr_png_deflate`` of a u8 [H, W, 3] device tensor: the zlib stream of its PNG scanlines as bytes.  One launch
-    chain; the 8-byte length is downloaded, then the stream."""
+    chain; the 8-byte length is downloaded, then the stream.  ``dynamic``: ``ysmr_png_deflate_dynamic`` instead -- one
+    block in a dynamic Huffman code, matches at four distances: a smaller stream of the same scanlines."""
     import torch
     if rgb_device.dtype != torch.uint8 or rgb_device.dim() != 3 or rgb_device.shape[2] != 3 or not rgb_device.is_contiguous():
         raise ValueError("rgb_device must be a contiguous u8 [H, W, 3] tensor, got {} {}".format(rgb_device.dtype, tuple(rgb_device.shape)))
@@ -62,19 +72,26 @@ def device_deflate(rgb_device):
     dev = rgb_device.device
     h, w = int(rgb_device.shape[0]), int(rgb_device.shape[1])
     with _lib.on(dev):
-        ws = torch.empty(max(L.ysmr_png_workspace_bytes(w, h), 256), dtype=torch.uint8, device=dev)
-        out = torch.empty(max(L.ysmr_png_stream_bytes_max(w, h), 256), dtype=torch.uint8, device=dev)
+        if dynamic:
+            name, deflate = "ysmr_png_deflate_dynamic", L.ysmr_png_deflate_dynamic
+            ws_bytes, out_bytes = L.ysmr_png_dynamic_workspace_bytes(w, h), L.ysmr_png_dynamic_stream_bytes_max(w, h)
+        else:
+            name, deflate = "ysmr_png_deflate", L.ysmr_png_deflate
+            ws_bytes, out_bytes = L.ysmr_png_workspace_bytes(w, h), L.ysmr_png_stream_bytes_max(w, h)
+        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
+        out = torch.empty(max(out_bytes, 256), dtype=torch.uint8, device=dev)
         length = torch.empty(1, dtype=torch.int64, device=dev)
-        _lib.check(L.ysmr_png_deflate(_lib.stream_ptr(dev), rgb_device.data_ptr(), w, h, ws.data_ptr(), ws.numel(), out.data_ptr(),
-                                      out.numel(), length.data_ptr()), "ysmr_png_deflate")
+        _lib.check(deflate(_lib.stream_ptr(dev), rgb_device.data_ptr(), w, h, ws.data_ptr(), ws.numel(), out.data_ptr(),
+                           out.numel(), length.data_ptr()), name)
         n = int(length.item())
         return out[:n].cpu().numpy().tobytes()
 
 
-def write_png_device(path, rgb_device, dpi=300):
+def write_png_device(path, rgb_device, dpi=300, dynamic=False):
     """``write_png`` for a canvas in HBM (u8 [H, W, 3] device tensor): the same chunks in the same layout, the IDAT body
-    deflated on the device (fixed Huffman code, ``csrc/png.hip``) -- the file decodes to the same pixels, its bytes differ."""
-    idat = device_deflate(rgb_device)
+    deflated on the device (``csrc/png.hip``: the fixed Huffman code, or with ``dynamic`` a dynamic one over matches at four
+    distances) -- the file decodes to the same pixels, its bytes differ."""
+    idat = device_deflate(rgb_device, dynamic)
     h, w = int(rgb_device.shape[0]), int(rgb_device.shape[1])
 
     def chunk(kind, body):
@@ -379,12 +396,13 @@ def track_distances(df):
 
 def _finish_figure(rgb, decorate, save_path, dpi, png_on_device):
     """Lettering and file.  ``decorate(canvas)`` stamps into a NumPy canvas -- or, with ``png_on_device`` (``rgb`` is the
-    device tensor then), into a ``StampList`` that the device paints before it deflates the canvas."""
+    device tensor then), into a ``StampList`` that the device paints before it deflates the canvas; ``'dynamic'`` chooses
+    the dynamic stream (``png_mode``)."""
     if png_on_device:
         stamps = StampList(rgb.shape[0], rgb.shape[1])
         decorate(stamps)
         device_stamp(rgb, stamps)
-        write_png_device(save_path, rgb, dpi)
+        write_png_device(save_path, rgb, dpi, dynamic=png_mode(png_on_device) == "dynamic")
     else:
         decorate(rgb)
         write_png(save_path, rgb, dpi)
@@ -410,7 +428,9 @@ def large_xy_plot(df, plot_title_name, save_path, px_to_micrometre=1, dist_min=0
                   distances=None, png_on_device=False):
     """Every track's path on one plot, black dots where the tracks start (plot_functions.py:109-188).  ``distances``:
     the tracks' 'Distance (µm)' in table order (default: the sums of the table's 'travelled_dist').  ``png_on_device``:
-    lettering and deflate on the device, the canvas is not downloaded."""
+    lettering and deflate on the device, the canvas is not downloaded -- ``True``: one block in the fixed Huffman code;
+    ``'dynamic'``: one block in a dynamic code over matches at four distances, the smaller file (``png_mode``).  The same
+    two values are taken by ``rose_graph``, ``angle_distribution_plot`` and ``violin_plot``."""
     _track_figure(df, 0, plot_title_name, save_path, px_to_micrometre, dist_min, dist_max, dpi, device, distances, png_on_device)
 
 
