@@ -222,6 +222,28 @@ int ysmr_mjpeg_batch(void *stream, const uint8_t *dib_dev, int n_frames, int hei
                      void *workspace_dev, size_t workspace_bytes,
                      uint8_t *out_dev, size_t out_capacity, int64_t *offsets_dev, int32_t *status_dev);
 
+/* ADDED under ABI 15 (see above).  ysmr_mjpeg_batch with two choices; ysmr_mjpeg_batch is this call with sampling = 1 and
+ * huffman = 0, and ysmr_mjpeg_workspace_bytes the workspace of that mode.  Arguments, chunks, offsets_dev, status_dev and the
+ * capacity contract are those of ysmr_mjpeg_batch; anything else than the values named here is YSMR_ERR_ARG.
+ * sampling (the codes of ysmr_mjpeg_decode_batch): 1 = 4:4:4, 2 = 4:2:2 (luminance sampled 2 x 1), 3 = 4:2:0 (2 x 2).  The MCU
+ * is 8 h x 8 v pixels, the frame's edges repeated up to a multiple of it; its blocks are the h v luminance blocks row by row,
+ * then Cb, then Cr (T.81 A.2.3); SOF0 says 0x11 / 0x21 / 0x22 for Y and 0x11 for Cb and Cr; one MCU row is one restart
+ * interval, DRI = ceil(width / 8 h).  Cb and Cr are downsampled as libjpeg does, on the clamped 0 .. 255 samples of the
+ * padded frame: 2 x 1 by (a + b + bias) >> 1 with bias 0, 1, 0, 1, ... along the output row, 2 x 2 by
+ * (a + b + c + d + bias) >> 2 with bias 1, 2, 1, 2, ...  4:2:0 has half the blocks of 4:4:4, and about half its workspace.
+ * huffman: 0 = the typical tables of Annex K.3; 1 = four tables built for every frame from that frame's own symbol counts
+ * (ZRL and EOB included): code lengths by the rule of ysmr_png_code_lengths with a limit of 16 bits over the alphabet
+ * {pseudo-symbol with the count 1, symbol 0, symbol 1, ...} -- the pseudo-symbol of T.81 K.2 comes first, so it is the lightest
+ * of all and has a longest code; leaving it out leaves the code of all 1-bits unused --, canonical codes by length, then by
+ * symbol; each DHT segment lists only the symbols the frame uses, so the header's length varies from frame to frame.  The
+ * coefficients are those of huffman = 0: only the bits differ.  The counts are integer sums: two calls give the same bytes.
+ * At most 65535 frames per call.  tests/jpeg_sampled_model.py is the specification of every byte. */
+size_t ysmr_mjpeg_encode_workspace_bytes(int n_frames, int height, int width, int sampling, int huffman);
+int ysmr_mjpeg_encode_batch(void *stream, const uint8_t *dib_dev, int n_frames, int height, int width,
+                            int stride, size_t frame_bytes, int bottom_up, int quality, int sampling, int huffman,
+                            void *workspace_dev, size_t workspace_bytes,
+                            uint8_t *out_dev, size_t out_capacity, int64_t *offsets_dev, int32_t *status_dev);
+
 /* ---- detection: a1-a6 ------------------------------------------------------------------- */
 
 /* Bytes of scratch ysmr_detect_batch needs for this geometry. */

@@ -62,7 +62,7 @@ EXPORTS = ("ysmr_abi_version", "ysmr_last_error", "ysmr_detect_workspace_bytes",
            "ysmr_luminosity_batch", "ysmr_luminosity_batch_host", "ysmr_tracker_dimensions", "ysmr_tracker_update3",
            "ysmr_tracker_run3", "ysmr_tracker_peek3", "ysmr_tracker_prepare3", "ysmr_annotate_batch", "ysmr_plot_colormap",
            "ysmr_plot_extent", "ysmr_plot_workspace_bytes", "ysmr_plot_tracks", "ysmr_plot_angle_histogram", "ysmr_plot_wedges",
-           "ysmr_mjpeg_workspace_bytes", "ysmr_mjpeg_batch", "ysmr_violin_workspace_bytes", "ysmr_violin_stats", "ysmr_plot_violins",
+           "ysmr_mjpeg_workspace_bytes", "ysmr_mjpeg_batch", "ysmr_mjpeg_encode_workspace_bytes", "ysmr_mjpeg_encode_batch", "ysmr_violin_workspace_bytes", "ysmr_violin_stats", "ysmr_plot_violins",
            "ysmr_mjpeg_decode_workspace_bytes", "ysmr_mjpeg_decode_batch",
            "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_batch_sync", "ysmr_mjpeg_decode_sync_geometry",
            "ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_png_deflate", "ysmr_plot_stamp",
@@ -247,6 +247,9 @@ def lib():
     L.ysmr_mjpeg_decode_sync_geometry.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ci)]
     L.ysmr_mjpeg_decode_sync_geometry.restype = None
     L.ysmr_mjpeg_batch.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.c_size_t, ci, ci, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp]
+    L.ysmr_mjpeg_encode_workspace_bytes.argtypes = [ci, ci, ci, ci, ci]
+    L.ysmr_mjpeg_encode_workspace_bytes.restype = ctypes.c_size_t
+    L.ysmr_mjpeg_encode_batch.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.c_size_t, ci, ci, ci, ci, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp]
     L.ysmr_violin_workspace_bytes.argtypes = [ll, ci, ci]
     L.ysmr_violin_workspace_bytes.restype = ctypes.c_size_t
     L.ysmr_violin_stats.argtypes = [vp, ll, vp, ll, vp, ll, ci, vp, vp, vp, ctypes.c_size_t, vp, vp]
@@ -264,7 +267,7 @@ def lib():
     L.ysmr_png_deflate_dynamic.argtypes = [vp, vp, ci, ci, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]
     L.ysmr_png_code_lengths.argtypes = [vp, ci, ci, vp]
     for name in EXPORTS:
-        if name not in ("ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_png_dynamic_workspace_bytes", "ysmr_png_dynamic_stream_bytes_max", "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_sync_geometry", "ysmr_mjpeg_decode_workspace_bytes", "ysmr_violin_workspace_bytes", "ysmr_mjpeg_workspace_bytes", "ysmr_plot_workspace_bytes", "ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
+        if name not in ("ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_png_dynamic_workspace_bytes", "ysmr_png_dynamic_stream_bytes_max", "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_sync_geometry", "ysmr_mjpeg_decode_workspace_bytes", "ysmr_violin_workspace_bytes", "ysmr_mjpeg_workspace_bytes", "ysmr_mjpeg_encode_workspace_bytes", "ysmr_plot_workspace_bytes", "ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
                         "ysmr_rows_sort_workspace_bytes", "ysmr_rows_csv_bound", "ysmr_rows_stream_count",
                         "ysmr_mean_threshold_state_bytes"):
             getattr(L, name).restype = ci

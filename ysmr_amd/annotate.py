@@ -7,7 +7,7 @@ and hands the frames to ``cv2.VideoWriter``.  Here the frames come through ``Dev
 * (uncompressed, the default) a stream of its own copies them into one of two pinned buffers, and a writer thread appends
   those to an uncompressed AVI (``AviWriter``), or
 * (Motion-JPEG: 'save video file extension' ``.avi`` with 'save video fourcc codec' ``MJPG`` / ``JPEG``)
-  ``ysmr_mjpeg_batch`` (``csrc/mjpeg.hip``) turns them into finished ``00dc`` chunks, one baseline JPEG each, on the
+  ``ysmr_mjpeg_encode_batch`` (``csrc/mjpeg.hip``) turns them into finished ``00dc`` chunks, one baseline JPEG each, on the
   device; the copy stream brings over their offsets and then only the bytes those name, and the writer thread appends
   them to a Motion-JPEG AVI (``MjpegAviWriter``).
 
@@ -18,8 +18,11 @@ Departures from upstream, all deliberate:
 * the file is always an ``.avi``, uncompressed 24-bit or Motion-JPEG (no encoder is a dependency of this package: the
   JPEG encoder is the package's own kernels); settings that ask for another container or codec are answered with one
   warning that names what is written;
-* Motion-JPEG is 4:4:4 with the typical Huffman tables of T.81 Annex K at the quality of the optional settings key
-  'hip video jpeg quality' (1 .. 100, default 90), one restart interval per MCU row (``output_format``);
+* Motion-JPEG is, unless asked otherwise, 4:4:4 with the typical Huffman tables of T.81 Annex K at the quality of the
+  optional settings key 'hip video jpeg quality' (1 .. 100, default 90), one restart interval per MCU row
+  (``output_format``).  Upstream's ``cv2.VideoWriter`` writes 4:2:0: 'hip video jpeg subsampling' = '4:2:0' (or '4:2:2')
+  does so too, and 'hip video jpeg huffman' = 'optimised' gives every frame Huffman tables built from its own symbols
+  (``jpeg_mode``; ``ysmr_mjpeg_encode_batch``);
 * the digits are a 5 x 7 bitmap font, not OpenCV's Hershey strokes (placement, size class, colours and dot sizes are
   upstream's);
 * ``select_subtype`` selects the rows whose ``motility_phenotype`` equals the subtype's code (0 immotile, 1 twitching,
@@ -43,7 +46,7 @@ from . import _lib
 from .frames import DeviceFrameFeed, decode_mjpeg_setting, open_video
 from .helper_file import create_results_folder, get_configs, get_data, get_loggers
 
-__all__ = ["annotate_video", "AviWriter", "MjpegAviWriter", "output_format", "build_marks", "subtype_code", "SUBTYPES"]
+__all__ = ["annotate_video", "AviWriter", "MjpegAviWriter", "output_format", "jpeg_mode", "build_marks", "subtype_code", "SUBTYPES"]
 
 SUBTYPES = ("immotile", "twitching", "motile")
 #: one pinned output buffer (there are two) holds at most this many bytes
@@ -53,8 +56,11 @@ _RAW_CODECS = ("", "DIB ", "DIB", "RGB ", "RGB", "RAW ", "RAW", "0")
 #: the names 'save video fourcc codec' has for Motion-JPEG (with 'save video file extension' = .avi)
 _JPEG_CODECS = ("MJPG", "JPEG")
 JPEG_QUALITY_DEFAULT = 90
-#: the encoder's workspace (about 16 bytes per pixel of a batch) is kept at or below this by the batch size
+#: the encoder's workspace (about 16 bytes per pixel of a batch at 4:4:4, 8 at 4:2:0) is kept at or below this by the batch size
 MJPEG_WORKSPACE_MAX = 1 << 30
+#: 'hip video jpeg subsampling' -> the ``sampling`` of ysmr_mjpeg_encode_batch; 'hip video jpeg huffman' -> its ``huffman``
+JPEG_SUBSAMPLINGS = {"4:4:4": 1, "4:2:2": 2, "4:2:0": 3}
+JPEG_HUFFMAN = {"standard": 0, "optimised": 1}
 
 
 class AviWriter:
@@ -276,10 +282,34 @@ class MjpegAviWriter(AviWriter):
             done = run
 
 
+def jpeg_mode(settings):
+    """``(sampling, huffman)`` for ``ysmr_mjpeg_encode_batch`` from the optional settings keys 'hip video jpeg subsampling'
+    ('4:4:4', the default, '4:2:2' or '4:2:0') and 'hip video jpeg huffman' ('standard', the default, or 'optimised': tables
+    built for every frame); ValueError, naming key and value, for anything else."""
+    out = []
+    for key, known in (("hip video jpeg subsampling", JPEG_SUBSAMPLINGS), ("hip video jpeg huffman", JPEG_HUFFMAN)):
+        asked = settings.get(key)
+        if asked is None or asked == "":
+            out.append(next(iter(known.values())))
+        elif isinstance(asked, str) and asked.strip().lower() in known:
+            out.append(known[asked.strip().lower()])
+        else:
+            raise ValueError("{!r} must be one of {}, got {!r}".format(key, ", ".join(repr(k) for k in known), asked))
+    return tuple(out)
+
+
+def jpeg_mode_name(sampling, huffman):
+    """'' for the default mode, else what the log says behind the quality: ', 4:2:0, optimised Huffman tables'."""
+    parts = [name for name, code in JPEG_SUBSAMPLINGS.items() if code == sampling and code != 1]
+    parts += ["{} Huffman tables".format(name) for name, code in JPEG_HUFFMAN.items() if code == huffman and code != 0]
+    return "".join(", " + p for p in parts)
+
+
 def output_format(settings):
     """What 'save video file extension' / 'save video fourcc codec' / 'hip video jpeg quality' ask for:
     ``(format, quality, warning)`` -- ``("mjpeg", 1 .. 100, None)`` exactly when the extension is ``.avi`` and the codec
-    ``MJPG`` or ``JPEG`` (any letter case; the quality defaults to 90; ValueError if it is not 1 .. 100), else
+    ``MJPG`` or ``JPEG`` (any letter case; the quality defaults to 90; ValueError if it is not 1 .. 100, or if
+    'hip video jpeg subsampling' / 'hip video jpeg huffman' hold anything ``jpeg_mode`` does not know), else
     ``("raw", None, warning)`` with the warning (None for ``.avi`` and the name of an uncompressed stream) that the caller
     completes with the file name."""
     ext = str(settings.get("save video file extension") or "")
@@ -292,6 +322,7 @@ def output_format(settings):
             quality = None
         if quality is None or isinstance(asked, bool) or not 1 <= quality <= 100:
             raise ValueError("'hip video jpeg quality' must be an integer from 1 to 100, got {!r}".format(asked))
+        jpeg_mode(settings)
         return "mjpeg", quality, None
     if ext.lower() != ".avi" or codec.upper() not in _RAW_CODECS:
         return "raw", None, ("'save video file extension' = {!r} / 'save video fourcc codec' = {!r}: the HIP path has no encoder; "
@@ -356,9 +387,9 @@ def _csv_table(path, logger, settings):
     return get_data(path, dtype=dtype)
 
 
-def _mjpeg_frames(video, writer, marks, first, n_frames, quality, settings, result_folder, dev, logger):
+def _mjpeg_frames(video, writer, marks, first, n_frames, quality, mode, settings, result_folder, dev, logger):
     """The loop of ``annotate_video`` in Motion-JPEG mode: ``ysmr_annotate_batch`` paints a batch into a device buffer of
-    stored DIB frames, ``ysmr_mjpeg_batch`` encodes that into finished chunks, the copy stream brings the offsets and the
+    stored DIB frames, ``ysmr_mjpeg_encode_batch`` encodes that (``mode``: its sampling and huffman) into finished chunks, the copy stream brings the offsets and the
     status over and then only the bytes the offsets name, and the writer thread appends them.  Two output buffers on the
     device and two pinned ones, as in the uncompressed mode; their default capacity is the batch's uncompressed size, and a
     batch that does not fit is encoded once more into buffers of the size its offsets ask for.  Returns the number of frames
@@ -367,10 +398,11 @@ def _mjpeg_frames(video, writer, marks, first, n_frames, quality, settings, resu
     height, width, channels = video.height, video.width, video.channels
     stride, frame_bytes = writer.stride, writer.frame_bytes
     L = _lib.lib()
+    sampling, huffman = mode
     batch = int(settings.get("hip frames per batch") or 0) or auto_batch(frame_bytes + 8, n_frames)
     batch = max(1, min(batch, auto_batch(frame_bytes + 8, n_frames),
-                       MJPEG_WORKSPACE_MAX // max(1, L.ysmr_mjpeg_workspace_bytes(1, height, width))))
-    ws_bytes = L.ysmr_mjpeg_workspace_bytes(batch, height, width)
+                       MJPEG_WORKSPACE_MAX // max(1, L.ysmr_mjpeg_encode_workspace_bytes(1, height, width, sampling, huffman))))
+    ws_bytes = L.ysmr_mjpeg_encode_workspace_bytes(batch, height, width, sampling, huffman)
     if not ws_bytes:
         raise ValueError("a Motion-JPEG frame is at most 65535 x 65535, got {} x {}".format(width, height))
     with _lib.on(dev):
@@ -406,10 +438,10 @@ def _mjpeg_frames(video, writer, marks, first, n_frames, quality, settings, resu
 
         def encode(stream, k, n):
             """Encode the painted batch into slot k and bring offsets and status over: (offsets, status)."""
-            _lib.check(L.ysmr_mjpeg_batch(
+            _lib.check(L.ysmr_mjpeg_encode_batch(
                 stream.cuda_stream, dib_dev.data_ptr(), n, height, width, stride, frame_bytes, int(writer.bottom_up), quality,
-                workspace.data_ptr(), ws_bytes, out_dev[k].data_ptr(), capacity[k], meta_dev[k].data_ptr(),
-                meta_dev[k].data_ptr() + 8 * (batch + 1)), "ysmr_mjpeg_batch")
+                sampling, huffman, workspace.data_ptr(), ws_bytes, out_dev[k].data_ptr(), capacity[k], meta_dev[k].data_ptr(),
+                meta_dev[k].data_ptr() + 8 * (batch + 1)), "ysmr_mjpeg_encode_batch")
             encoded = torch.cuda.Event()
             encoded.record(stream)
             with torch.cuda.stream(copy_stream):
@@ -451,7 +483,7 @@ def _mjpeg_frames(video, writer, marks, first, n_frames, quality, settings, resu
                     pinned[k] = torch.empty(capacity[k], dtype=torch.uint8, pin_memory=True)
                     offsets, status = encode(stream, k, n)
                 if status:
-                    raise RuntimeError("ysmr_mjpeg_batch: status {} for frames {} .. {} ({} bytes into {})".format(
+                    raise RuntimeError("ysmr_mjpeg_encode_batch: status {} for frames {} .. {} ({} bytes into {})".format(
                         status, f0, f0 + n - 1, offsets[-1], capacity[k]))
                 need, free = offsets[-1] + 24 * n + 4096, shutil.disk_usage(result_folder).free
                 if free < need:
@@ -486,7 +518,9 @@ def annotate_video(video_path, df, output_save=True, settings=None, result_folde
     not moving, white with a larger dot at turn points.  Returns the path of the file, None after any failure (logged on
     'ysmr', never raised).  Optional settings keys: 'hip frames per batch' overrides the batch size; 'hip video jpeg
     quality' (1 .. 100, default 90) is the quality of a Motion-JPEG file (``output_format`` says when one is written;
-    the free space is then checked batch by batch, against the bytes about to be written); 'hip decode mjpeg' (True /
+    the free space is then checked batch by batch, against the bytes about to be written), 'hip video jpeg subsampling'
+    ('4:4:4' / '4:2:2' / '4:2:0') and 'hip video jpeg huffman' ('standard' / 'optimised') its chroma subsampling and
+    whether every frame carries Huffman tables of its own (``jpeg_mode``); 'hip decode mjpeg' (True /
     'always' / False) says whether a Motion-JPEG INPUT is decoded on the device, as in ``track_bacteria``."""
     import pandas as pd
     import torch
@@ -545,9 +579,11 @@ def annotate_video(video_path, df, output_save=True, settings=None, result_folde
         if fmt == "mjpeg":
             marks, first = build_marks(df, n_frames, select_subtype)
             writer = MjpegAviWriter(output_video_name, width, height, fps_of_file)
-            logger.info("Annotated video {}: {} frames of {} x {}, Motion-JPEG, quality {}".format(
-                output_video_name, n_frames, width, height, quality))
-            done = _mjpeg_frames(video, writer, marks, first, n_frames, quality, settings, result_folder, torch.device(device), logger)
+            mode = jpeg_mode(settings)
+            logger.info("Annotated video {}: {} frames of {} x {}, Motion-JPEG, quality {}{}".format(
+                output_video_name, n_frames, width, height, quality, jpeg_mode_name(*mode)))
+            done = _mjpeg_frames(video, writer, marks, first, n_frames, quality, mode, settings, result_folder,
+                                 torch.device(device), logger)
             if done is None:
                 return None
             frame_count = video.frame_count

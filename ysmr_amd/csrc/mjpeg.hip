@@ -21,14 +21,34 @@
 //                 EOI behind them; the wave of a frame's first interval also writes the chunk header and the JPEG header.
 // Every store into out_dev is a byte store guarded by out_capacity.  The worst case of a block is 1658 bits (20 for the DC,
 // 26 for each AC coefficient); the bit buffer has 1664 per block IN THE WORKSPACE -- no kernel has a stack array.
+// TWO CHOICES of ysmr_mjpeg_encode_batch (tests/jpeg_sampled_model.py is their specification; ysmr_mjpeg_batch is (1, 0)):
+//   sampling 2 / 3   4:2:2 / 4:2:0: the MCU is 16 x 8 / 16 x 16 pixels, two / four luminance blocks, then Cb and Cr, each
+//                    libjpeg's average of the 2 / 4 samples it covers; k_mj_blocks_sampled instead of k_mj_blocks, and the
+//                    entropy kernels find a block's table and DC predecessor from its place in the MCU (block_at)
+//   huffman 1        four tables per frame from the frame's own symbols.  Between k_mj_blocks and k_mj_lengths:
+//     k_mj_hist      grid (x, frame), a lane per block: the frame's symbol counts, in LDS first
+//     k_mj_tables    a workgroup per (table, frame): code lengths of at most 16 bits (png_codes.h, with the pseudo-symbol of
+//                    T.81 K.2 so that the code of all 1-bits stays free), canonical codes, the DHT segment
+//                    and k_mj_lengths / k_mj_pack run with the frame as the grid's y, the frame's codes in LDS; the header's
+//                    length varies per frame (k_mj_layout, k_mj_write).
 #include "common.h"
+#include "png_codes.h"
 #include <algorithm>
 
 namespace {
 
 constexpr int HEADER_BYTES = 625;            // SOI .. SOS header: 2 + 18 + 134 + 19 + 2 * (33 + 183) + 6 + 14
-constexpr int BLOCK_WORDS = 52;              // words of bit buffer per block: 1664 bits
+constexpr int HEADER_FRONT = 173;            // SOI, APP0, DQT, SOF0: what stands in front of the DHT segments
+constexpr int HEADER_BACK = 20;              // DRI and the SOS header behind them
+// Words of bit buffer per block.  With the Annex K.3 tables a block has at most 20 + 63 * 26 = 1658 bits: 52 words (1664
+// bits).  A table built per frame may give ANY symbol a 16-bit code, the DC category 11 included: 27 + 63 * 26 = 1665 bits,
+// one more than 52 words hold -- so the per-frame mode has 53.
+constexpr int BLOCK_WORDS = 52, BLOCK_WORDS_BUILT = 53;
 constexpr int MAX_GRID = 2048;
+// One frame's codes, and its histogram, as 768 words: AC luminance [0, 256), AC chrominance [256, 512), DC luminance
+// [512, 528), DC chrominance [528, 544) -- the layout of c_codes below.
+constexpr int CODE_WORDS = 768;
+constexpr int DHT_STRIDE = 192;              // a DHT segment of a built table: 21 + its symbols (at most 162) bytes
 
 struct Header { uint8_t b[640]; };           // (by value into k_mj_write: 625 bytes used)
 struct Quant { uint32_t q[2][64]; };         // divisors in natural order: luminance, chrominance
@@ -116,6 +136,22 @@ __device__ __forceinline__ uint32_t wave_inclusive(uint32_t v, int lane)
 // A WAVE takes one MCU at a time, lane 8 y + x its pixel (y, x); pixels beyond the frame repeat the last column / row.  After
 // the first product lane 8 y + u holds row y's u-th sum, after the second lane 8 v + u the coefficient (v, u); lane k then
 // fetches the k-th coefficient of the zigzag sequence, so that a block is stored as 128 contiguous bytes.
+// The level-shifted sample v of lane 8 y + x becomes, in lane k, the k-th quantised coefficient of the zigzag sequence.
+__device__ __forceinline__ int16_t dct_quantised(int v, const int (&cx)[8], const int (&cy)[8], uint32_t q, int lane, int x, int zz)
+{
+    int rows = 0;                                                  // |rows| <= 128 * 185360 < 2^25
+#pragma unroll
+    for (int k = 0; k < 8; ++k) rows += cx[k] * __shfl(v, (lane & ~7) + k, 64);
+    long long full = 0;                                            // scaled by 2^32, below 2^43
+#pragma unroll
+    for (int k = 0; k < 8; ++k) full += (long long)cy[k] * __shfl(rows, 8 * k + x, 64);
+    const int acc = (int)((full + (1ll << 19)) >> 20);             // 12 fraction bits: |acc| <= 1024 * 4096 + a little
+    const uint32_t mag = ((uint32_t)(acc < 0 ? -acc : acc) + (q << 11)) / (q << 12);
+    int val = acc < 0 ? -(int)mag : (int)mag;
+    val = std::max(lane == 0 ? -1024 : -1023, std::min(1023, val));
+    return (int16_t)__shfl(val, zz, 64);
+}
+
 __global__ __launch_bounds__(256) void k_mj_blocks(const uint8_t *__restrict__ dib, int n, int H, int W, int stride, size_t frame_bytes,
                                                    int bottom_up, Quant qt, int16_t *__restrict__ coef)
 {
@@ -139,29 +175,75 @@ __global__ __launch_bounds__(256) void k_mj_blocks(const uint8_t *__restrict__ d
         s[2] = ((32768 * R - 27439 * G - 5329 * B + 32767) >> 16) + 128;
         int16_t *o = coef + (size_t)m * 192;
 #pragma unroll
-        for (int comp = 0; comp < 3; ++comp) {
-            const int v = std::min(std::max(s[comp], 0), 255) - 128;
-            int rows = 0;                                                  // |rows| <= 128 * 185360 < 2^25
+        for (int comp = 0; comp < 3; ++comp)
+            o[64 * comp + lane] = dct_quantised(std::min(std::max(s[comp], 0), 255) - 128, cx, cy, q_of[comp ? 1 : 0], lane, x, zz);
+    }
+}
+
+// The subsampled frames: the MCU is 8 h x 8 v pixels, (h, v) = (2, 1) or (2, 2).  A WAVE takes one MCU at a time: its h v
+// luminance blocks row by row, lane 8 y + x the pixel (y, x) of each, then Cb and Cr, whose sample (y, x) is libjpeg's
+// average of the h v clamped samples it covers -- (a + b + bias) >> 1 with bias 0, 1, 0, 1, ... along the row, or
+// (a + b + c + d + bias) >> 2 with bias 1, 2, 1, 2, ... -- taken BEFORE the level shift.  Pixels beyond the frame repeat the last
+// column / row, so the padded frame is a whole number of MCUs.  The blocks of an MCU are stored in the order of the scan.
+__global__ __launch_bounds__(256) void k_mj_blocks_sampled(const uint8_t *__restrict__ dib, int n, int H, int W, int stride,
+                                                           size_t frame_bytes, int bottom_up, int v_luma, Quant qt,
+                                                           int16_t *__restrict__ coef)
+{
+    const int lane = threadIdx.x & 63, y = lane >> 3, x = lane & 7;
+    int cx[8], cy[8];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) rows += cx[k] * __shfl(v, (lane & ~7) + k, 64);
-            long long full = 0;                                            // scaled by 2^32, below 2^43
-#pragma unroll
-            for (int k = 0; k < 8; ++k) full += (long long)cy[k] * __shfl(rows, 8 * k + x, 64);
-            const int acc = (int)((full + (1ll << 19)) >> 20);             // 12 fraction bits: |acc| <= 1024 * 4096 + a little
-            const uint32_t q = q_of[comp ? 1 : 0];
-            const uint32_t mag = ((uint32_t)(acc < 0 ? -acc : acc) + (q << 11)) / (q << 12);
-            int val = acc < 0 ? -(int)mag : (int)mag;
-            val = std::max(lane == 0 ? -1024 : -1023, std::min(1023, val));
-            o[64 * comp + lane] = (int16_t)__shfl(val, zz, 64);
+    for (int k = 0; k < 8; ++k) { cx[k] = c_dct[8 * x + k]; cy[k] = c_dct[8 * y + k]; }
+    const uint32_t q_of[2] = {qt.q[0][lane], qt.q[1][lane]};
+    const int zz = c_zigzag[lane];
+    const int hv = 2 * v_luma, Wm = (W + 15) >> 4, Hm = (H + 8 * v_luma - 1) / (8 * v_luma);
+    const long long per_frame = (long long)Hm * Wm, total = per_frame * n;
+    for (long long m = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); m < total; m += (long long)gridDim.x * 4) {
+        const long long f = m / per_frame;
+        const int rem = (int)(m - f * per_frame), r = rem / Wm, c = rem - r * Wm;
+        const uint8_t *frame = dib + (size_t)f * frame_bytes;
+        auto pixel = [&](int py, int px) {
+            py = std::min(py, H - 1);
+            px = std::min(px, W - 1);
+            return frame + (size_t)(bottom_up ? H - 1 - py : py) * (size_t)stride + 3 * (size_t)px;
+        };
+        int16_t *o = coef + (size_t)m * (hv + 2) * 64;
+        for (int k = 0; k < hv; ++k) {
+            const uint8_t *p = pixel(8 * (v_luma * r + (k >> 1)) + y, 8 * (2 * c + (k & 1)) + x);
+            const int B = p[0], G = p[1], R = p[2];
+            const int s = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16;
+            o[64 * k + lane] = dct_quantised(std::min(std::max(s, 0), 255) - 128, cx, cy, q_of[0], lane, x, zz);
         }
+        int cb = hv == 2 ? (x & 1) : 1 + (x & 1), cr = cb;                  // the bias
+        for (int k = 0; k < hv; ++k) {
+            const uint8_t *p = pixel(v_luma * (8 * r + y) + (k >> 1), 2 * (8 * c + x) + (k & 1));
+            const int B = p[0], G = p[1], R = p[2];
+            cb += std::min(std::max(((-11059 * R - 21709 * G + 32768 * B + 32767) >> 16) + 128, 0), 255);
+            cr += std::min(std::max(((32768 * R - 27439 * G - 5329 * B + 32767) >> 16) + 128, 0), 255);
+        }
+        const int shift = hv == 2 ? 1 : 2;
+        o[64 * hv + lane] = dct_quantised((cb >> shift) - 128, cx, cy, q_of[1], lane, x, zz);
+        o[64 * hv + 64 + lane] = dct_quantised((cr >> shift) - 128, cx, cy, q_of[1], lane, x, zz);
     }
 }
 
 // ---- entropy coding -----------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void load_codes(uint32_t *s_codes)
+// The codes of the workgroup into LDS: the Annex K.3 tables, or, where `built` holds a set per frame, those of the frame
+// blockIdx.y -- the grid's y is then the frame, and a workgroup touches no other frame's intervals (span_of).
+__device__ __forceinline__ void load_codes(uint32_t *s_codes, const uint32_t *__restrict__ built)
 {
-    for (int k = threadIdx.x; k < 768; k += blockDim.x) s_codes[k] = c_codes[k >> 8].v[k & 255];
+    if (built)
+        for (int k = threadIdx.x; k < CODE_WORDS; k += blockDim.x) s_codes[k] = built[(size_t)blockIdx.y * CODE_WORDS + k];
+    else
+        for (int k = threadIdx.x; k < CODE_WORDS; k += blockDim.x) s_codes[k] = c_codes[k >> 8].v[k & 255];
     __syncthreads();
+}
+
+// What a workgroup of the entropy kernels works on: all intervals (gridDim.y = 1), or those of the frame blockIdx.y.
+__device__ __forceinline__ void span_of(long long intervals, long long &first, long long &end)
+{
+    const long long per = intervals / gridDim.y;
+    first = per * blockIdx.y;
+    end = first + per;
 }
 
 // The code of a value of size category `size` behind the Huffman code `entry` of its symbol: both in one piece.
@@ -172,23 +254,21 @@ __device__ __forceinline__ void coded(uint32_t entry, int v, int size, uint32_t 
     len = (int)(entry & 255u) + size;
 }
 
-// One block's codes, in order, handed to sink(bits, len) (len <= 27): the DC difference against `pred`, then the AC
-// coefficients with their runs of zeros, ZRL for every 16 zeros in front of a coefficient, EOB if the block ends in zeros.
+// One block's symbols, in order, handed to sink(slot, value, size): the DC difference against `pred`, then the AC
+// coefficients with their runs of zeros, ZRL for every 16 zeros in front of a coefficient, EOB if the block ends in zeros
+// (both with size 0).  slot: the symbol's place among the CODE_WORDS words of a frame's codes or histogram.
 // `blk`: 64 int16 in zigzag order, 16-byte aligned; t: 0 luminance, 1 chrominance.
 template <typename Sink>
-__device__ __forceinline__ void walk_block(const int16_t *__restrict__ blk, int pred, int t, const uint32_t *s_codes, Sink &&sink)
+__device__ __forceinline__ void walk_symbols(const int16_t *__restrict__ blk, int pred, int t, Sink &&sink)
 {
-    const uint32_t *ac = s_codes + 256 * t, *dc = s_codes + 512 + 16 * t;
+    const int ac = 256 * t, dc = 512 + 16 * t;
     int run = -1;                              // (the DC's place counts as a zero below)
     for (int g = 0; g < 8; ++g) {
         uint4 v = *reinterpret_cast<const uint4 *>(blk + 8 * g);
         if (g == 0) {
             const int diff = (int)(int16_t)(v.x & 0xFFFFu) - pred;
             const int size = 32 - __clz(diff < 0 ? -diff : diff);
-            uint32_t bits;
-            int len;
-            coded(dc[size], diff, size, bits, len);
-            sink(bits, len);
+            sink(dc + size, diff, size);
             v.x &= 0xFFFF0000u;
         }
         if (!(v.x | v.y | v.z | v.w)) { run += 8; continue; }
@@ -197,70 +277,189 @@ __device__ __forceinline__ void walk_block(const int16_t *__restrict__ blk, int 
         for (int j = 0; j < 8; ++j) {
             const int c = (int)(int16_t)((w[j >> 1] >> (16 * (j & 1))) & 0xFFFFu);
             if (c == 0) { ++run; continue; }
-            while (run > 15) { sink(ac[0xF0] >> 8, (int)(ac[0xF0] & 255u)); run -= 16; }
+            while (run > 15) { sink(ac + 0xF0, 0, 0); run -= 16; }
             const int size = 32 - __clz(c < 0 ? -c : c);
-            uint32_t bits;
-            int len;
-            coded(ac[(run << 4) | size], c, size, bits, len);
-            sink(bits, len);
+            sink(ac + ((run << 4) | size), c, size);
             run = 0;
         }
     }
-    if (run > 0) sink(ac[0] >> 8, (int)(ac[0] & 255u));
+    if (run > 0) sink(ac, 0, 0);
 }
 
-// The block b (= 3 * MCU + component) of an interval: where it is, what its DC is predicted from.
-__device__ __forceinline__ const int16_t *block_at(const int16_t *coef, long long interval, int nb, int b, int &pred)
+// The same as codes: sink(bits, len), len <= 27 (a code of at most 16 bits and a value of at most 11).
+template <typename Sink>
+__device__ __forceinline__ void walk_block(const int16_t *__restrict__ blk, int pred, int t, const uint32_t *s_codes, Sink &&sink)
+{
+    walk_symbols(blk, pred, t, [&](int slot, int v, int size) {
+        uint32_t bits;
+        int len;
+        coded(s_codes[slot], v, size, bits, len);
+        sink(bits, len);
+    });
+}
+
+// The block b of an interval: where it is, whether it is a chrominance block (t), what its DC is predicted from.  An MCU
+// holds hv luminance blocks, then Cb, then Cr (T.81 A.2.3); a luminance block predicts from the one coded before it, in
+// this MCU or as the last of the MCU before, a chrominance block from its component's block of the MCU before.
+__device__ __forceinline__ const int16_t *block_at(const int16_t *coef, long long interval, int nb, int hv, int b, int &t, int &pred)
 {
     const int16_t *blk = coef + ((size_t)interval * nb + b) * 64;
-    pred = b >= 3 ? (int)blk[-192] : 0;
+    const int mcu = hv == 1 ? b / 3 : hv == 2 ? b >> 2 : b / 6, k = b - mcu * (hv + 2);
+    t = k >= hv;
+    const int back = t ? hv + 2 : k ? 1 : 3;             // (k = 0: behind Cr and Cb of the MCU before)
+    pred = mcu || (k && !t) ? (int)blk[-64 * back] : 0;
     return blk;
 }
 
 // A WAVE takes one restart interval at a time, its lanes 64 blocks at a time.
-__global__ __launch_bounds__(256) void k_mj_lengths(const int16_t *__restrict__ coef, long long intervals, int nb,
-                                                    uint32_t *__restrict__ bit_start, uint32_t *__restrict__ interval_bits,
-                                                    uint32_t *__restrict__ bitbuf)
+__global__ __launch_bounds__(256) void k_mj_lengths(const int16_t *__restrict__ coef, long long intervals, int nb, int hv, int bw,
+                                                    const uint32_t *__restrict__ built, uint32_t *__restrict__ bit_start,
+                                                    uint32_t *__restrict__ interval_bits, uint32_t *__restrict__ bitbuf)
 {
-    __shared__ uint32_t s_codes[768];
-    load_codes(s_codes);
+    __shared__ uint32_t s_codes[CODE_WORDS];
+    load_codes(s_codes, built);
     const int lane = threadIdx.x & 63;
-    for (long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); i < intervals; i += (long long)gridDim.x * 4) {
+    long long first, end;
+    span_of(intervals, first, end);
+    for (long long i = first + (long long)blockIdx.x * 4 + (threadIdx.x >> 6); i < end; i += (long long)gridDim.x * 4) {
         uint32_t carry = 0;
         for (int base = 0; base < nb; base += 64) {
             const int b = base + lane;
             uint32_t mine = 0;
             if (b < nb) {
-                int pred;
-                const int16_t *blk = block_at(coef, i, nb, b, pred);
-                walk_block(blk, pred, b % 3 ? 1 : 0, s_codes, [&](uint32_t, int len) { mine += (uint32_t)len; });
+                int t, pred;
+                const int16_t *blk = block_at(coef, i, nb, hv, b, t, pred);
+                walk_block(blk, pred, t, s_codes, [&](uint32_t, int len) { mine += (uint32_t)len; });
             }
             const uint32_t incl = wave_inclusive(mine, lane);
             if (b < nb) bit_start[(size_t)i * nb + b] = carry + incl - mine;
             carry += (uint32_t)__shfl((int)incl, 63, 64);
         }
         if (lane == 0) interval_bits[i] = carry;
-        uint32_t *words = bitbuf + (size_t)i * nb * BLOCK_WORDS;
-        const uint32_t used = (carry + 31u) >> 5;                          // <= nb * BLOCK_WORDS: a block has <= 1658 bits
+        uint32_t *words = bitbuf + (size_t)i * nb * bw;
+        const uint32_t used = (carry + 31u) >> 5;                          // <= nb * bw: a block has <= 32 bw bits (BLOCK_WORDS)
         for (uint32_t w = lane; w < used; w += 64) words[w] = 0u;
     }
 }
 
+// The symbols of the frame blockIdx.y, a lane per block, counted in LDS and added to the frame's histogram (zeroed by the
+// host's memset): integer sums, so the order does not matter.
+__global__ __launch_bounds__(256) void k_mj_hist(const int16_t *__restrict__ coef, int frame_intervals, int nb, int hv,
+                                                 uint32_t *__restrict__ hist)
+{
+    __shared__ uint32_t s_hist[CODE_WORDS];
+    for (int k = threadIdx.x; k < CODE_WORDS; k += 256) s_hist[k] = 0u;
+    __syncthreads();
+    const long long i0 = (long long)blockIdx.y * frame_intervals;
+    const int blocks = frame_intervals * nb;
+    for (int gb = blockIdx.x * 256 + threadIdx.x; gb < blocks; gb += gridDim.x * 256) {
+        const int r = gb / nb;
+        int t, pred;
+        const int16_t *blk = block_at(coef, i0 + r, nb, hv, gb - r * nb, t, pred);
+        walk_symbols(blk, pred, t, [&](int slot, int, int) { atomicAdd(&s_hist[slot], 1u); });
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < CODE_WORDS; k += 256)
+        if (s_hist[k]) atomicAdd(&hist[(size_t)blockIdx.y * CODE_WORDS + k], s_hist[k]);
+}
+
+// ONE WORKGROUP per (table, frame): blockIdx.x = 0 DC luminance, 1 AC luminance, 2 DC chrominance, 3 AC chrominance, the
+// order of the DHT segments.  The code lengths are those of png_codes.h with a limit of 16 bits over an alphabet of 257:
+// entry 0 is the pseudo-symbol of T.81 K.2 with the count 1, entry s + 1 the symbol s.  Being the first of the lightest, the
+// pseudo-symbol is the LAST to be given a length and so has a longest one; it is then left out, which leaves the last code of
+// that length, the one of all 1-bits, unused.  Codes are canonical (T.81 Annex C): by length, then by symbol.  What is
+// independent per symbol, leaf or length is spread over the threads, as k_png_dcodes does (png.hip).
+// Out: the frame's code words ((code << 8) | length), the DHT segment and its length.
+__global__ __launch_bounds__(256) void k_mj_tables(const uint32_t *__restrict__ hist, uint32_t *__restrict__ built,
+                                                   uint8_t *__restrict__ dht, uint32_t *__restrict__ dht_bytes)
+{
+    namespace pc = ysmr::pngc;
+    constexpr int N = 257;
+    __shared__ pc::Work w;
+    __shared__ uint32_t s_counts[N], s_first[17], s_before[17];
+    __shared__ uint8_t s_len[N];
+    __shared__ int s_used;
+    const int t = threadIdx.x, tb = blockIdx.x, f = blockIdx.y;
+    const int ac = tb & 1, slot0 = ac ? 256 * (tb >> 1) : 512 + 16 * (tb >> 1), n_sym = ac ? 256 : 16;
+    const uint32_t *h = hist + (size_t)f * CODE_WORDS + slot0;
+    for (int s = t; s < N; s += 256) s_counts[s] = s == 0 ? 1u : s <= n_sym ? h[s - 1] : 0u;
+    __syncthreads();
+    if (t == 0) s_used = pc::used_of(s_counts, N);
+    __syncthreads();
+    const int m = s_used;                                      // >= 2: the pseudo-symbol, and a block has a DC and an AC symbol
+    for (int s = t; s < N; s += 256) {
+        s_len[s] = 0;
+        if (s_counts[s]) w.order[pc::rank_of(s_counts, N, s)] = (uint16_t)s;
+    }
+    __syncthreads();
+    for (int i = t; i < m; i += 256) pc::leaf_weight(s_counts, i, w);
+    __syncthreads();
+    if (t == 0) pc::huffman_links(m, w);
+    __syncthreads();
+    for (int i = t; i < m; i += 256) pc::leaf_depth(m, i, w);
+    __syncthreads();
+    if (t >= 1 && t <= 16) pc::count_depth(m, 16, t, w);
+    __syncthreads();
+    if (t == 0) pc::limit_lengths(m, 16, w);
+    __syncthreads();
+    for (int i = t; i < m; i += 256) pc::assign_length(m, 16, i, s_len, w);
+    __syncthreads();
+    if (t >= 1 && t <= 16) {                                   // BITS: the symbols (without the pseudo-symbol) of every length
+        uint32_t c = 0;
+#pragma nounroll
+        for (int s = 1; s < N; ++s) c += s_len[s] == t;
+        w.num[t] = c;
+    }
+    __syncthreads();
+    if (t == 0) {
+        uint32_t code = 0, before = 0;
+#pragma nounroll
+        for (int len = 1; len <= 16; ++len) {
+            s_first[len] = code;
+            s_before[len] = before;
+            code = (code + w.num[len]) << 1;
+            before += w.num[len];
+        }
+        s_before[0] = before;                                  // the number of symbols
+    }
+    __syncthreads();
+    uint8_t *seg = dht + ((size_t)f * 4 + tb) * DHT_STRIDE;
+    const uint32_t n_vals = s_before[0], body = 19 + n_vals;
+    for (int s = t + 1; s <= n_sym; s += 256) {
+        const int len = s_len[s];
+        uint32_t entry = 0;
+        if (len) {
+            uint32_t earlier = 0;
+#pragma nounroll
+            for (int u = 1; u < s; ++u) earlier += s_len[u] == len;
+            entry = ((s_first[len] + earlier) << 8) | (uint32_t)len;
+            seg[21 + s_before[len] + earlier] = (uint8_t)(s - 1);
+        }
+        built[(size_t)f * CODE_WORDS + slot0 + s - 1] = entry;
+    }
+    if (t < 21)
+        seg[t] = t == 0 ? 0xFFu : t == 1 ? 0xC4u : t == 2 ? (uint8_t)(body >> 8) : t == 3 ? (uint8_t)body
+               : t == 4 ? (uint8_t)((ac << 4) | (tb >> 1)) : (uint8_t)w.num[t - 4];
+    if (t == 0) dht_bytes[f * 4 + tb] = 21 + n_vals;
+}
+
 // A LANE takes one block.  The stream is big-endian bit by bit, the buffer is made of little-endian words: 32 finished bits
 // are byte-swapped and OR-ed into their word.
-__global__ __launch_bounds__(256) void k_mj_pack(const int16_t *__restrict__ coef, long long intervals, int nb,
-                                                 const uint32_t *__restrict__ bit_start, const uint32_t *__restrict__ interval_bits,
-                                                 uint32_t *__restrict__ bitbuf)
+__global__ __launch_bounds__(256) void k_mj_pack(const int16_t *__restrict__ coef, long long intervals, int nb, int hv, int bw,
+                                                 const uint32_t *__restrict__ built, const uint32_t *__restrict__ bit_start,
+                                                 const uint32_t *__restrict__ interval_bits, uint32_t *__restrict__ bitbuf)
 {
-    __shared__ uint32_t s_codes[768];
-    load_codes(s_codes);
-    const long long total = intervals * nb;
-    for (long long gb = (long long)blockIdx.x * blockDim.x + threadIdx.x; gb < total; gb += (long long)gridDim.x * blockDim.x) {
+    __shared__ uint32_t s_codes[CODE_WORDS];
+    load_codes(s_codes, built);
+    long long first, end;
+    span_of(intervals, first, end);
+    const long long total = end * nb;
+    for (long long gb = first * nb + (long long)blockIdx.x * blockDim.x + threadIdx.x; gb < total; gb += (long long)gridDim.x * blockDim.x) {
         const long long i = gb / nb;
         const int b = (int)(gb - i * nb);
-        int pred;
-        const int16_t *blk = block_at(coef, i, nb, b, pred);
-        uint32_t *words = bitbuf + (size_t)i * nb * BLOCK_WORDS;
+        int t, pred;
+        const int16_t *blk = block_at(coef, i, nb, hv, b, t, pred);
+        uint32_t *words = bitbuf + (size_t)i * nb * bw;
         const uint32_t start = bit_start[gb];
         uint32_t wi = start >> 5;
         int fill = (int)(start & 31u);
@@ -274,7 +473,7 @@ __global__ __launch_bounds__(256) void k_mj_pack(const int16_t *__restrict__ coe
                 fill -= 32;
             }
         };
-        walk_block(blk, pred, b % 3 ? 1 : 0, s_codes, put);
+        walk_block(blk, pred, t, s_codes, put);
         if (b == nb - 1) {                                                 // the interval ends here: 1-bits up to a byte
             const int pad = (int)(-interval_bits[i] & 7u);
             if (pad) put((1u << pad) - 1u, pad);
@@ -291,11 +490,11 @@ __device__ __forceinline__ uint32_t count_ff(uint32_t v)
 // A WAVE takes one interval: bytes + 0xFF bytes (+ 2 for the RST marker behind every interval of a frame but the last).  The
 // bytes of the last word beyond the interval's end are zero (k_mj_lengths zeroed whole words).
 __global__ __launch_bounds__(256) void k_mj_count(const uint32_t *__restrict__ bitbuf, const uint32_t *__restrict__ interval_bits,
-                                                  long long intervals, int nb, int H8, uint32_t *__restrict__ interval_size)
+                                                  long long intervals, int nb, int bw, int H8, uint32_t *__restrict__ interval_size)
 {
     const int lane = threadIdx.x & 63;
     for (long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); i < intervals; i += (long long)gridDim.x * 4) {
-        const uint32_t *words = bitbuf + (size_t)i * nb * BLOCK_WORDS;
+        const uint32_t *words = bitbuf + (size_t)i * nb * bw;
         const uint32_t bytes = (interval_bits[i] + 7u) >> 3, used = (bytes + 3u) >> 2;
         uint32_t ff = 0;
         for (uint32_t w = lane; w < used; w += 64) ff += count_ff(words[w]);
@@ -304,14 +503,23 @@ __global__ __launch_bounds__(256) void k_mj_count(const uint32_t *__restrict__ b
     }
 }
 
+// SOI .. SOS header of frame f: with built tables (dht_bytes: the frame's four segment lengths) it varies per frame.
+__device__ __forceinline__ uint32_t header_bytes(const uint32_t *__restrict__ dht_bytes, long long f)
+{
+    if (!dht_bytes) return HEADER_BYTES;
+    const uint32_t *d = dht_bytes + 4 * f;
+    return HEADER_FRONT + d[0] + d[1] + d[2] + d[3] + HEADER_BACK;
+}
+
 // ONE WORKGROUP.  A thread sums the intervals of a frame; wave 0 scans the chunk sizes 64 frames at a time; a thread then
 // places its frame's intervals.
 __global__ __launch_bounds__(256) void k_mj_layout(const uint32_t *__restrict__ interval_size, int n, int H8, size_t out_capacity,
-                                                   uint32_t *__restrict__ payload, long long *__restrict__ interval_at,
-                                                   long long *__restrict__ offsets, int *__restrict__ status)
+                                                   const uint32_t *__restrict__ dht_bytes, uint32_t *__restrict__ payload,
+                                                   long long *__restrict__ interval_at, long long *__restrict__ offsets,
+                                                   int *__restrict__ status)
 {
     for (int f = threadIdx.x; f < n; f += 256) {
-        uint32_t sum = HEADER_BYTES + 2;
+        uint32_t sum = header_bytes(dht_bytes, f) + 2;
         for (int r = 0; r < H8; ++r) sum += interval_size[(size_t)f * H8 + r];
         payload[f] = sum;
     }
@@ -338,7 +546,7 @@ __global__ __launch_bounds__(256) void k_mj_layout(const uint32_t *__restrict__ 
     }
     __syncthreads();
     for (int f = threadIdx.x; f < n; f += 256) {
-        long long at = offsets[f] + 8 + HEADER_BYTES;
+        long long at = offsets[f] + 8 + header_bytes(dht_bytes, f);
         for (int r = 0; r < H8; ++r) {
             interval_at[(size_t)f * H8 + r] = at;
             at += interval_size[(size_t)f * H8 + r];
@@ -350,7 +558,8 @@ __global__ __launch_bounds__(256) void k_mj_layout(const uint32_t *__restrict__ 
 // 0xFF), a prefix sum, the bytes.  Nothing at or beyond out_capacity is written.
 __global__ __launch_bounds__(256) void k_mj_write(const uint32_t *__restrict__ bitbuf, const uint32_t *__restrict__ interval_bits,
                                                   const long long *__restrict__ interval_at, const long long *__restrict__ offsets,
-                                                  const uint32_t *__restrict__ payload, long long intervals, int nb, int H8, Header head,
+                                                  const uint32_t *__restrict__ payload, long long intervals, int nb, int bw, int H8,
+                                                  Header head, const uint8_t *__restrict__ dht, const uint32_t *__restrict__ dht_bytes,
                                                   uint8_t *__restrict__ out, size_t out_capacity)
 {
     const int lane = threadIdx.x & 63;
@@ -360,7 +569,7 @@ __global__ __launch_bounds__(256) void k_mj_write(const uint32_t *__restrict__ b
     for (long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); i < intervals; i += (long long)gridDim.x * 4) {
         const long long f = i / H8;
         const int r = (int)(i - f * H8);
-        const uint32_t *words = bitbuf + (size_t)i * nb * BLOCK_WORDS;
+        const uint32_t *words = bitbuf + (size_t)i * nb * bw;
         const uint32_t bytes = (interval_bits[i] + 7u) >> 3;
         const long long at0 = interval_at[i];
         uint32_t carry = 0;
@@ -389,25 +598,44 @@ __global__ __launch_bounds__(256) void k_mj_write(const uint32_t *__restrict__ b
                 if (size & 1u) store(chunk + 8 + size, 0u);
             }
         }
-        if (r == 0)
-            for (int k = lane; k < 8 + HEADER_BYTES; k += 64) {
+        if (r == 0) {
+            // `head` is the whole header with the Annex K.3 tables; the frame's own DHT segments take their place between
+            // its front and its back
+            const uint32_t *d = dht_bytes ? dht_bytes + 4 * f : nullptr;
+            const int d0 = d ? (int)d[0] : 0, d1 = d ? d0 + (int)d[1] : 0, d2 = d ? d1 + (int)d[2] : 0;
+            const int d3 = d ? d2 + (int)d[3] : HEADER_BYTES - HEADER_FRONT - HEADER_BACK;
+            for (int k = lane; k < 8 + HEADER_FRONT + d3 + HEADER_BACK; k += 64) {
                 const uint32_t tag = 0x63643030u;                           // '00dc'
-                store(chunk + k, k < 4 ? (tag >> (8 * k)) & 0xFFu : k < 8 ? (size >> (8 * (k - 4))) & 0xFFu : head.b[k - 8]);
+                const int j = k - 8 - HEADER_FRONT;                         // (the place among the DHT segments)
+                uint32_t byte;
+                if (k < 8) byte = k < 4 ? (tag >> (8 * k)) & 0xFFu : (size >> (8 * (k - 4))) & 0xFFu;
+                else if (!d || j < 0) byte = head.b[k - 8];
+                else if (j >= d3) byte = head.b[HEADER_BYTES - HEADER_BACK + j - d3];
+                else {
+                    const int tb = (j >= d0) + (j >= d1) + (j >= d2);
+                    byte = dht[((size_t)f * 4 + tb) * DHT_STRIDE + (j - (tb == 0 ? 0 : tb == 1 ? d0 : tb == 2 ? d1 : d2))];
+                }
+                store(chunk + k, byte);
             }
+        }
     }
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
+// W8, H8: the frame in MCUs (8 h x 8 v pixels); hv = h v luminance blocks per MCU; nb: blocks per interval; bw: words of bit
+// buffer per block.  hist .. dht_bytes exist only with built tables.
 struct Plan {
-    size_t coef, bit_start, interval_bits, interval_size, interval_at, payload, bitbuf, total;
+    size_t coef, bit_start, interval_bits, interval_size, interval_at, payload, bitbuf, hist, built, dht, dht_bytes, total;
     long long intervals;
-    int W8, H8, nb;
+    int W8, H8, nb, h, v, hv, bw;
 };
 
-Plan plan_of(int n, int H, int W)
+Plan plan_of(int n, int H, int W, int sampling, int huffman)
 {
     Plan p;
-    p.W8 = (W + 7) / 8; p.H8 = (H + 7) / 8; p.nb = 3 * p.W8;
+    p.h = sampling == 1 ? 1 : 2; p.v = sampling == 3 ? 2 : 1; p.hv = p.h * p.v;
+    p.W8 = (W + 8 * p.h - 1) / (8 * p.h); p.H8 = (H + 8 * p.v - 1) / (8 * p.v); p.nb = (p.hv + 2) * p.W8;
+    p.bw = huffman ? BLOCK_WORDS_BUILT : BLOCK_WORDS;
     p.intervals = (long long)n * p.H8;
     const size_t blocks = (size_t)p.intervals * p.nb;
     size_t at = 0;
@@ -418,7 +646,14 @@ Plan plan_of(int n, int H, int W)
     p.interval_size = take((size_t)p.intervals * 4);
     p.interval_at = take((size_t)p.intervals * 8);
     p.payload = take((size_t)n * 4);
-    p.bitbuf = take(blocks * BLOCK_WORDS * 4);
+    p.bitbuf = take(blocks * p.bw * 4);
+    p.hist = p.built = p.dht = p.dht_bytes = 0;
+    if (huffman) {
+        p.hist = take((size_t)n * CODE_WORDS * 4);
+        p.built = take((size_t)n * CODE_WORDS * 4);
+        p.dht = take((size_t)n * 4 * DHT_STRIDE);
+        p.dht_bytes = take((size_t)n * 4 * 4);
+    }
     p.total = at;
     return p;
 }
@@ -432,7 +667,7 @@ void quant_tables(int quality, Quant &qt)
     }
 }
 
-int header_of(int H, int W, const Quant &qt, Header &h)
+int header_of(int H, int W, const Plan &plan, const Quant &qt, Header &h)
 {
     uint8_t *p = h.b;
     auto put = [&](int v) { *p++ = (uint8_t)v; };
@@ -448,7 +683,7 @@ int header_of(int H, int W, const Quant &qt, Header &h)
     }
     marker(0xC0, 15);
     put(8); put(H >> 8); put(H & 255); put(W >> 8); put(W & 255); put(3);
-    for (int c = 0; c < 3; ++c) { put(c + 1); put(0x11); put(c ? 1 : 0); }
+    for (int c = 0; c < 3; ++c) { put(c + 1); put(c ? 0x11 : (plan.h << 4) | plan.v); put(c ? 1 : 0); }
     const struct { int id, n; const uint8_t *bits, *vals; } tables[4] = {
         {0x00, 12, DC_LUM_BITS, DC_VALS}, {0x10, 162, AC_LUM_BITS, AC_LUM_VALS},
         {0x01, 12, DC_CHR_BITS, DC_VALS}, {0x11, 162, AC_CHR_BITS, AC_CHR_VALS}};
@@ -458,7 +693,7 @@ int header_of(int H, int W, const Quant &qt, Header &h)
         for (int k = 0; k < 16; ++k) put(t.bits[k]);
         for (int k = 0; k < t.n; ++k) put(t.vals[k]);
     }
-    const int dri = (W + 7) / 8;
+    const int dri = plan.W8;
     marker(0xDD, 2);
     put(dri >> 8); put(dri & 255);
     marker(0xDA, 10);
@@ -477,35 +712,47 @@ bool geometry_ok(int n, int H, int W)
     return n > 0 && H > 0 && W > 0 && H <= 65535 && W <= 65535;
 }
 
+bool mode_ok(int sampling, int huffman) { return sampling >= 1 && sampling <= 3 && (huffman == 0 || huffman == 1); }
+
 }  // namespace
+
+extern "C" size_t ysmr_mjpeg_encode_workspace_bytes(int n_frames, int height, int width, int sampling, int huffman)
+{
+    if (!geometry_ok(n_frames, height, width) || !mode_ok(sampling, huffman)) return 0;
+    return plan_of(n_frames, height, width, sampling, huffman).total;
+}
 
 extern "C" size_t ysmr_mjpeg_workspace_bytes(int n_frames, int height, int width)
 {
-    if (!geometry_ok(n_frames, height, width)) return 0;
-    return plan_of(n_frames, height, width).total;
+    return ysmr_mjpeg_encode_workspace_bytes(n_frames, height, width, 1, 0);
 }
 
-extern "C" int ysmr_mjpeg_batch(void *stream, const uint8_t *dib_dev, int n_frames, int height, int width, int stride,
-                                size_t frame_bytes, int bottom_up, int quality, void *workspace_dev, size_t workspace_bytes,
-                                uint8_t *out_dev, size_t out_capacity, int64_t *offsets_dev, int32_t *status_dev)
+extern "C" int ysmr_mjpeg_encode_batch(void *stream, const uint8_t *dib_dev, int n_frames, int height, int width, int stride,
+                                       size_t frame_bytes, int bottom_up, int quality, int sampling, int huffman,
+                                       void *workspace_dev, size_t workspace_bytes, uint8_t *out_dev, size_t out_capacity,
+                                       int64_t *offsets_dev, int32_t *status_dev)
 {
     if (!geometry_ok(n_frames, height, width))
         return ysmr::fail(YSMR_ERR_ARG, "n_frames must be positive, height and width 1 .. 65535 (got %d, %d, %d)", n_frames, height, width);
     if (quality < 1 || quality > 100) return ysmr::fail(YSMR_ERR_ARG, "quality must be 1 .. 100, got %d", quality);
+    if (!mode_ok(sampling, huffman))
+        return ysmr::fail(YSMR_ERR_ARG, "sampling must be 1 (4:4:4), 2 (4:2:2) or 3 (4:2:0) and huffman 0 or 1, got %d and %d", sampling,
+                          huffman);
+    if (huffman && n_frames > 65535) return ysmr::fail(YSMR_ERR_ARG, "at most 65535 frames per call with huffman = 1, got %d", n_frames);
     if ((long long)stride < 3LL * width || (stride & 3) || frame_bytes < (size_t)stride * height)
         return ysmr::fail(YSMR_ERR_ARG, "stride %d (a multiple of 4) / frame_bytes %zu too small for %d x %d x 3", stride, frame_bytes,
                           width, height);
     if (!dib_dev || !workspace_dev || !out_dev || !offsets_dev || !status_dev)
         return ysmr::fail(YSMR_ERR_ARG, "dib_dev, workspace_dev, out_dev, offsets_dev and status_dev must not be NULL");
-    const Plan p = plan_of(n_frames, height, width);
+    const Plan p = plan_of(n_frames, height, width, sampling, huffman);
     if (workspace_bytes < p.total)
-        return ysmr::fail(YSMR_ERR_ARG, "workspace of %zu bytes, %zu needed (ysmr_mjpeg_workspace_bytes)", workspace_bytes, p.total);
+        return ysmr::fail(YSMR_ERR_ARG, "workspace of %zu bytes, %zu needed (ysmr_mjpeg_encode_workspace_bytes)", workspace_bytes, p.total);
     if (((uintptr_t)workspace_dev & 255) || ((uintptr_t)offsets_dev & 7) || ((uintptr_t)status_dev & 3))
         return ysmr::fail(YSMR_ERR_ARG, "workspace_dev must be 256-byte aligned, offsets_dev 8-byte, status_dev 4-byte");
     Quant qt;
     Header head = {};
     quant_tables(quality, qt);
-    if (header_of(height, width, qt, head) != HEADER_BYTES) return ysmr::fail(YSMR_ERR_STATE, "JPEG header is not %d bytes", HEADER_BYTES);
+    if (header_of(height, width, p, qt, head) != HEADER_BYTES) return ysmr::fail(YSMR_ERR_STATE, "JPEG header is not %d bytes", HEADER_BYTES);
 
     hipStream_t st = (hipStream_t)stream;
     uint8_t *ws = (uint8_t *)workspace_dev;
@@ -514,23 +761,49 @@ extern "C" int ysmr_mjpeg_batch(void *stream, const uint8_t *dib_dev, int n_fram
     uint32_t *interval_size = (uint32_t *)(ws + p.interval_size), *payload = (uint32_t *)(ws + p.payload);
     uint32_t *bitbuf = (uint32_t *)(ws + p.bitbuf);
     long long *interval_at = (long long *)(ws + p.interval_at);
-    const long long mcus = p.intervals * p.W8, blocks = p.intervals * p.nb;
-    hipLaunchKernelGGL(k_mj_blocks, dim3(grid_of(mcus, 4)), dim3(256), 0, st, dib_dev, n_frames, height, width, stride, frame_bytes,
-                       bottom_up, qt, coef);
+    // with built tables: the frame is the grid's y in the kernels that hold one frame's codes or histogram in LDS
+    uint32_t *hist = huffman ? (uint32_t *)(ws + p.hist) : nullptr, *built = huffman ? (uint32_t *)(ws + p.built) : nullptr;
+    uint32_t *dht_bytes = huffman ? (uint32_t *)(ws + p.dht_bytes) : nullptr;
+    uint8_t *dht = huffman ? ws + p.dht : nullptr;
+    const unsigned gy = huffman ? (unsigned)n_frames : 1u;
+    const long long mcus = p.intervals * p.W8, per_y = huffman ? p.H8 : p.intervals;
+    if (sampling == 1)
+        hipLaunchKernelGGL(k_mj_blocks, dim3(grid_of(mcus, 4)), dim3(256), 0, st, dib_dev, n_frames, height, width, stride, frame_bytes,
+                           bottom_up, qt, coef);
+    else
+        hipLaunchKernelGGL(k_mj_blocks_sampled, dim3(grid_of(mcus, 4)), dim3(256), 0, st, dib_dev, n_frames, height, width, stride,
+                           frame_bytes, bottom_up, p.v, qt, coef);
     YSMR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_mj_lengths, dim3(grid_of(p.intervals, 4)), dim3(256), 0, st, coef, p.intervals, p.nb, bit_start, interval_bits,
-                       bitbuf);
+    if (huffman) {
+        YSMR_HIP_CHECK(hipMemsetAsync(hist, 0, (size_t)n_frames * CODE_WORDS * 4, st));
+        hipLaunchKernelGGL(k_mj_hist, dim3(grid_of((long long)p.H8 * p.nb, 256), gy), dim3(256), 0, st, coef, p.H8, p.nb, p.hv, hist);
+        YSMR_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_mj_tables, dim3(4, gy), dim3(256), 0, st, hist, built, dht, dht_bytes);
+        YSMR_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_mj_lengths, dim3(grid_of(per_y, 4), gy), dim3(256), 0, st, coef, p.intervals, p.nb, p.hv, p.bw, built, bit_start,
+                       interval_bits, bitbuf);
     YSMR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_mj_pack, dim3(grid_of(blocks, 256)), dim3(256), 0, st, coef, p.intervals, p.nb, bit_start, interval_bits, bitbuf);
+    hipLaunchKernelGGL(k_mj_pack, dim3(grid_of(per_y * p.nb, 256), gy), dim3(256), 0, st, coef, p.intervals, p.nb, p.hv, p.bw, built,
+                       bit_start, interval_bits, bitbuf);
     YSMR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_mj_count, dim3(grid_of(p.intervals, 4)), dim3(256), 0, st, bitbuf, interval_bits, p.intervals, p.nb, p.H8,
+    hipLaunchKernelGGL(k_mj_count, dim3(grid_of(p.intervals, 4)), dim3(256), 0, st, bitbuf, interval_bits, p.intervals, p.nb, p.bw, p.H8,
                        interval_size);
     YSMR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_mj_layout, dim3(1), dim3(256), 0, st, interval_size, n_frames, p.H8, out_capacity, payload, interval_at,
-                       (long long *)offsets_dev, (int *)status_dev);
+    hipLaunchKernelGGL(k_mj_layout, dim3(1), dim3(256), 0, st, interval_size, n_frames, p.H8, out_capacity, dht_bytes, payload,
+                       interval_at, (long long *)offsets_dev, (int *)status_dev);
     YSMR_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_mj_write, dim3(grid_of(p.intervals, 4)), dim3(256), 0, st, bitbuf, interval_bits, interval_at,
-                       (const long long *)offsets_dev, payload, p.intervals, p.nb, p.H8, head, out_dev, out_capacity);
+                       (const long long *)offsets_dev, payload, p.intervals, p.nb, p.bw, p.H8, head, dht, dht_bytes, out_dev, out_capacity);
     YSMR_LAUNCH_CHECK();
     return YSMR_OK;
 }
+
+extern "C" int ysmr_mjpeg_batch(void *stream, const uint8_t *dib_dev, int n_frames, int height, int width, int stride,
+                                size_t frame_bytes, int bottom_up, int quality, void *workspace_dev, size_t workspace_bytes,
+                                uint8_t *out_dev, size_t out_capacity, int64_t *offsets_dev, int32_t *status_dev)
+{
+    return ysmr_mjpeg_encode_batch(stream, dib_dev, n_frames, height, width, stride, frame_bytes, bottom_up, quality, 1, 0, workspace_dev,
+                                   workspace_bytes, out_dev, out_capacity, offsets_dev, status_dev);
+}
+

@@ -37,8 +37,8 @@ struct Work {
     uint16_t link[2 * MAX_SYMBOLS];                 // a node's parent
     uint16_t order[MAX_SYMBOLS];                    // the used symbols, ascending by (count, symbol)
     uint16_t depth[MAX_SYMBOLS];                    // of the leaves
-    uint32_t num[16];                               // codes per length
-    uint32_t next[16];                              // the codes of at most that length; canonical: a length's first code
+    uint32_t num[17];                               // codes per length (1 .. 16: mjpeg.hip limits its codes to 16 bits)
+    uint32_t next[17];                              // the codes of at most that length; canonical: a length's first code
 };
 
 YSMR_HD_FORCE int used_of(const uint32_t *counts, int n)
