@@ -666,6 +666,10 @@ int ysmr_evaluate_tracks(void *stream, long long n_rows, const uint32_t *track_i
                          int8_t *turn_points_dev, double *tp_of_tracks_dev, double *travelled_dist_dev,
                          int8_t *motility_phenotype_dev, double *stats_dev, long long *n_tracks_out);
 
+/* HOST function: atan2(y[i], x[i]) as k_ev_heading and the angle histogram take it -- correctly rounded, in double-double
+ * (csrc/atan2_cr.h) -- run on the host, for the CPU tests that compare it with the exact model (tests/atan2_exact.py). */
+int ysmr_atan2_devicelike(const double *y, const double *x, long long n, double *out);
+
 /* ---- the track figures: large_xy_plot, rose_graph, angle_distribution_plot, ysmr/plot_functions.py:29-257 ---- */
 
 /* These entry points were ADDED under ABI 15 (see above).  Inputs are columns of the (TRACK_ID, POSITION_T)-ordered table

@@ -776,7 +776,7 @@ EVAL_ROW_COLUMNS = ["TRACK_ID", "POSITION_T", "POSITION_X", "POSITION_Y", "WIDTH
                     "moving", "turn_points", "tp_of_tracks", "travelled_dist", "motility_phenotype"]
 
 
-def evaluate_tracks_oracle(df, settings, fps):
+def evaluate_tracks_oracle(df, settings, fps, arctan2=np.arctan2):
     """CPU restatement of the arithmetic of ``evaluate_tracks`` on a table of selected tracks (ordered by
     TRACK_ID, POSITION_T, default RangeIndex): the per-row columns of ``*_analysed.csv`` and the per-track
     table of ``*_statistics.csv``.  Parity unpinned, like select_tracks_oracle: track_eval.py imports cv2 at
@@ -784,7 +784,9 @@ def evaluate_tracks_oracle(df, settings, fps):
     NumPy / SciPy primitives are used where their arithmetic matters (groupby sum / mean = Kahan summation,
     float16 ``bac_length`` whose group mean pandas returns as float32, ``scipy.signal.medfilt``,
     ``scipy.signal.argrelextrema``, ``scipy.spatial.distance.pdist``), the control flow is written out anew.
-    Plots, logging and file output are not part of it.  Returns (rows DataFrame, statistics DataFrame)."""
+    Plots, logging and file output are not part of it.  ``arctan2`` is the function the heading is taken with: NumPy's,
+    as upstream, or a model of it (tests/atan2_exact.py) -- NumPy's own result depends on the host's SIMD path within an
+    ulp.  Returns (rows DataFrame, statistics DataFrame)."""
     import pandas as pd
     from scipy.signal import argrelextrema, medfilt
     from scipy.spatial.distance import pdist
@@ -811,7 +813,7 @@ def evaluate_tracks_oracle(df, settings, fps):
     t["moving"] = moving
     # ---- change of heading between rows, heading taken over `compare angle between n frames` rows (:941-961)
     lag = settings["compare angle between n frames"]
-    heading = np.degrees(np.arctan2(by_track["POSITION_X"].diff(lag), by_track["POSITION_Y"].diff(lag)))
+    heading = np.degrees(arctan2(by_track["POSITION_X"].diff(lag), by_track["POSITION_Y"].diff(lag)))
     turn = abs(pd.Series(heading).groupby(tid).diff().fillna(0))
     t["angle_diff"] = np.where(360 - turn <= turn, 360 - turn, turn).astype(np.int32)
     candidates = np.where((t["angle_diff"] > settings["minimal angle in degrees for turning point"]) & (t["moving"] == 1),

@@ -188,8 +188,9 @@ def to_struct(view):
 
 # ---- the angle histogram ---------------------------------------------------------------------------------------------
 
-def headings(ids, x, y, moving, lag):
-    """(selected rows as a mask, heading per row -- NaN where there is none)."""
+def headings(ids, x, y, moving, lag, arctan2=np.arctan2):
+    """(selected rows as a mask, heading per row -- NaN where there is none).  ``arctan2``: NumPy's, or a model of it
+    (atan2_exact.atan2_cr)."""
     ids, x, y, moving = np.asarray(ids), np.asarray(x, np.float64), np.asarray(y, np.float64), np.asarray(moving)
     n = len(ids)
     if n == 0:
@@ -204,12 +205,12 @@ def headings(ids, x, y, moving, lag):
     has = i - lag >= first[seg]
     j = i[has]
     with np.errstate(all="ignore"):
-        h[j] = np.arctan2(x[j] - x[j - lag], y[j] - y[j - lag])
+        h[j] = arctan2(x[j] - x[j - lag], y[j] - y[j - lag])
     return selected, h
 
 
-def angle_histogram(ids, x, y, moving, lag, edges):
-    selected, h = headings(ids, x, y, moving, lag)
+def angle_histogram(ids, x, y, moving, lag, edges, arctan2=np.arctan2):
+    selected, h = headings(ids, x, y, moving, lag, arctan2)
     hs = h[selected]
     counts, _ = np.histogram(hs[~np.isnan(hs)], edges)
     return counts.astype(np.int64), int(selected.sum())

@@ -56,6 +56,85 @@ def make_table(seed, n_tracks=60, height=400, width=600, max_len=260):
     return pd.concat(parts, ignore_index=True)
 
 
+def _shapes_and_holes(rng, n):
+    """The frames kept of a track of n rows (holes, one long gap) and its WIDTH / HEIGHT / DEGREES_ANGLE kinds and lost rows,
+    as make_table draws them."""
+    keep = rng.random(n) > rng.choice([0.0, 0.0, 0.0, 0.02, 0.15])
+    if rng.random() < 0.3 and n > 40:
+        g = int(rng.integers(10, n - 20))
+        keep[g:g + int(rng.integers(3, 12))] = False
+    keep[0] = True
+    m = int(keep.sum())
+    kind = rng.choice(["rod", "rod", "rod", "rod", "big", "round"])
+    w = np.float32(rng.normal(6.0, 0.6, m)).astype(np.float64)
+    h = np.float32(rng.normal(2.0, 0.25, m)).astype(np.float64)
+    if kind == "big":
+        w *= 4
+        h *= 3
+    if kind == "round":
+        w = np.float32(rng.normal(4.2, 0.3, m)).astype(np.float64)
+        h = w * np.float32(0.9)
+    swap = rng.random(m) < 0.5
+    w, h = np.where(swap, h, w), np.where(swap, w, h)
+    lost = rng.random(m) < rng.choice([0.0, 0.0, 0.03, 0.2])
+    w[lost] = 0.0
+    h[lost] = 0.0
+    deg = np.float32(rng.uniform(-90, 0, m)).astype(np.float64)
+    deg[lost] = 0.0
+    return keep, w, h, deg, lost
+
+
+def lattice_table(seed, n_tracks=40, max_len=300, grid=0.5, height=400, width=600):
+    """Tracks whose positions are multiples of `grid`, as the rows of a video tracked with 'disable gsff' are (raw
+    minAreaRect centres: float32 values, mostly multiples of 0.5): a start on the lattice, then steps of -4 .. 4 grid units per
+    axis and frame, about one step in ten zero (a lost track repeats its position: atan2(0, 0)), the positions rounded
+    through float32.  Holes, one long gap, lost rows and the width / height kinds as in make_table.  The headings of such
+    a table, and the turns between them, sit exactly on whole degrees and on histogram edges again and again (steps along
+    the axes and the diagonals): an atan2 that is an ulp off shows."""
+    rng = np.random.default_rng(seed)
+    parts = []
+    for tid in range(n_tracks):
+        n = int(rng.integers(40, max_len))
+        t0 = int(rng.integers(0, 200))
+        keep, w, h, deg, lost = _shapes_and_holes(rng, n)
+        step = rng.integers(-4, 5, (n, 2)).astype(np.float64)
+        step[rng.random(n) < 0.08] = 0.0                             # with the 1 in 81 drawn as (0, 0): about one in ten
+        start = np.round(np.array([rng.uniform(0.1, 0.9) * width, rng.uniform(0.1, 0.9) * height]) / grid)
+        xy = ((np.cumsum(step, axis=0) + start) * grid).astype(np.float32).astype(np.float64)[keep]
+        m = len(xy)
+        parts.append(pd.DataFrame({"TRACK_ID": np.full(m, tid, np.uint32), "POSITION_T": (t0 + np.flatnonzero(keep)).astype(np.uint32),
+                                   "POSITION_X": xy[:, 0], "POSITION_Y": xy[:, 1], "WIDTH": w, "HEIGHT": h, "DEGREES_ANGLE": deg}))
+    return pd.concat(parts, ignore_index=True)
+
+
+def raw_centroid_table(seed, n_tracks=40, max_len=300, height=400, width=600):
+    """Tracks of raw-centroid-like positions: the float32 centres of randomly rotated rectangles (the mean of four float32
+    corners, as minAreaRect forms it), widened to double.  Off the 0.5 lattice, but every step is an exact difference of
+    float32 values -- few significant bits, unlike a float64 random walk."""
+    rng = np.random.default_rng(seed)
+    parts = []
+    for tid in range(n_tracks):
+        n = int(rng.integers(40, max_len))
+        t0 = int(rng.integers(0, 200))
+        keep, w, h, deg, lost = _shapes_and_holes(rng, n)
+        centre = np.cumsum(rng.normal(0, 1.2, (n, 2)), axis=0) + (rng.uniform(0.1, 0.9) * width, rng.uniform(0.1, 0.9) * height)
+        centre[rng.random(n) < 0.1] = np.nan                          # lost: repeats the position before it
+        centre[0] = np.nan_to_num(centre[0], nan=200.0)
+        centre = pd.DataFrame(centre).ffill().to_numpy()
+        th = rng.uniform(0, np.pi, n)
+        hw, hh = rng.uniform(2, 5, n), rng.uniform(0.5, 2, n)
+        corners = np.zeros((n, 4, 2), np.float32)
+        for c, (sa, sb) in enumerate(((-1, -1), (1, -1), (1, 1), (-1, 1))):
+            corners[:, c, 0] = np.round(centre[:, 0] + sa * hw * np.cos(th) - sb * hh * np.sin(th))      # contour points are pixels
+            corners[:, c, 1] = np.round(centre[:, 1] + sa * hw * np.sin(th) + sb * hh * np.cos(th))
+        wobble = np.float32(rng.normal(0, 0.3, (n, 4, 2)))                                                # the fitted box is not on them
+        xy = ((corners + wobble).sum(axis=1, dtype=np.float32) * np.float32(0.25)).astype(np.float64)[keep]
+        m = len(xy)
+        parts.append(pd.DataFrame({"TRACK_ID": np.full(m, tid, np.uint32), "POSITION_T": (t0 + np.flatnonzero(keep)).astype(np.uint32),
+                                   "POSITION_X": xy[:, 0], "POSITION_Y": xy[:, 1], "WIDTH": w, "HEIGHT": h, "DEGREES_ANGLE": deg}))
+    return pd.concat(parts, ignore_index=True)
+
+
 _COLUMNS = ("TRACK_ID", "POSITION_T", "POSITION_X", "POSITION_Y", "WIDTH", "HEIGHT", "DEGREES_ANGLE")
 
 

@@ -16,16 +16,18 @@ def _long_enough(df, rows):
     return df[size >= rows].reset_index(drop=True)
 
 
-def _compare(oracle, df, settings, fps):
+def _compare(oracle, df, settings, fps, **heading):
+    """`heading`: arctan2=..., handed to the oracle (its default is NumPy's)."""
     from ysmr_amd.evaluate import ROW_COLUMNS, STATS_COLUMNS, evaluate_columns, evaluate_params
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        ref_rows, ref_stats = oracle.evaluate_tracks_oracle(df, settings, fps)
+        ref_rows, ref_stats = oracle.evaluate_tracks_oracle(df, settings, fps, **heading)
     rows, stats = evaluate_columns(df.reset_index(drop=True), evaluate_params(settings, fps))
     assert list(ref_rows.columns) == ROW_COLUMNS and list(ref_stats.columns) == STATS_COLUMNS
     assert stats.shape == (len(ref_stats), 12)
-    # the heading goes through atan2, which the device library does not round correctly: a change of heading that
-    # lies within 1e-9 of a whole number of degrees may truncate to the neighbouring integer (never seen; counted)
+    # the heading goes through atan2: the device's is correctly rounded (csrc/atan2_cr.h), the oracle's is NumPy's unless the
+    # caller hands in the exact model.  On float64 random walks an ulp of the heading changes no angle_diff; on lattice
+    # positions it does (test_statistics_on_lattice_positions, which compares with the model).  Counted for the message.
     ang_ref = ref_rows["angle_diff"].to_numpy()
     off = rows["angle_diff"] != ang_ref
     assert off.sum() == 0, f"{off.sum()} of {len(off)} angle_diff values differ"
@@ -144,3 +146,87 @@ def test_analyse_goes_on_to_the_statistics(tmp_path, oracle):
     pd.testing.assert_frame_equal(res[1][STATS_COLUMNS], ref_stats, check_exact=True, check_names=False)
     assert (tmp_path / "res" / "clip_statistics.csv").exists()
     assert analyse(str(path), settings=dict(s), result_folder=str(tmp_path / "res2")) is True
+
+
+# ---- headings on lattice positions: the oracle takes them from the exact model (tests/atan2_exact.py) --------------------
+
+_TABLES = {}
+
+
+def _table(kind, seed):
+    """The lattice / raw-centroid tables, built once."""
+    import select_tables
+    if (kind, seed) not in _TABLES:
+        _TABLES[kind, seed] = _long_enough(getattr(select_tables, kind)(seed), 32)
+    return _TABLES[kind, seed]
+
+
+def _wiggled(y, x):
+    from atan2_exact import atan2_cr, ulp_wiggle
+    return ulp_wiggle(atan2_cr(y, x))
+
+
+@pytest.mark.parametrize("min_angle", [30, 45])
+@pytest.mark.parametrize("fps, seed", [(30.0, 1), (29.97, 3)])
+@pytest.mark.parametrize("lag", [1, 3, 5])
+def test_statistics_on_lattice_positions(oracle, lag, fps, seed, min_angle):
+    """Positions on the 0.5 lattice ('disable gsff': raw float32 centres): changes of heading that are whole numbers of degrees
+    (45, 90, ... -- at 45 the turning-point threshold itself), which truncate differently if a heading is an ulp off.
+    Every row column and every statistic against the oracle with correctly rounded headings, bit for bit."""
+    from atan2_exact import atan2_cr
+    from select_tables import select_settings
+    df = _table("lattice_table", seed)
+    assert len(df) > 5000 and (df[["POSITION_X", "POSITION_Y"]].to_numpy() * 2 % 1 == 0).all()
+    s = select_settings(**{"compare angle between n frames": lag, "minimal angle in degrees for turning point": min_angle})
+    # the table can fail: headings one ulp off, alternately up and down, change what the oracle itself returns
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        rows, stats = oracle.evaluate_tracks_oracle(df, s, fps, arctan2=atan2_cr)
+        rows_off, stats_off = oracle.evaluate_tracks_oracle(df, s, fps, arctan2=_wiggled)
+    changed = float(np.mean(rows["angle_diff"].to_numpy() != rows_off["angle_diff"].to_numpy()))
+    tp_changed = int((rows["turn_points"].to_numpy() != rows_off["turn_points"].to_numpy()).sum())
+    tps_changed = int((stats["Turn Points (TP/s)"].to_numpy() != stats_off["Turn Points (TP/s)"].to_numpy()).sum())
+    print(f"one-ulp headings change {changed:.1%} of angle_diff, {tp_changed} turn_points, {tps_changed} Turn Points (TP/s)")
+    assert changed >= 0.02 and tp_changed >= 1 and tps_changed >= 1
+    ref_rows, _ = _compare(oracle, df, s, fps, arctan2=atan2_cr)
+    assert (ref_rows["angle_diff"] == 45).sum() > 50 and (ref_rows["angle_diff"] == 90).sum() > 50
+
+
+@pytest.mark.parametrize("lag", [1, 3, 5])
+def test_statistics_on_raw_centroid_positions(oracle, lag):
+    """Float32 centres of rotated boxes, widened: off the lattice, every step an exact float32 difference."""
+    from atan2_exact import atan2_cr
+    from select_tables import select_settings
+    df = _table("raw_centroid_table", 2)
+    xy = df[["POSITION_X", "POSITION_Y"]].to_numpy()
+    assert len(df) > 5000 and np.array_equal(xy, xy.astype(np.float32).astype(np.float64)) and (xy * 2 % 1 == 0).mean() < 0.01
+    _compare(oracle, df, select_settings(**{"compare angle between n frames": lag}), 30.0, arctan2=atan2_cr)
+
+
+def test_analyse_without_gsff_matches_the_exact_headings(tmp_path, oracle):
+    """analyse() with 'disable gsff': the table holds the raw centres (a good part of them on the 0.5 lattice, lost tracks
+    repeating their position), and evaluate_tracks' result is the oracle's with correctly rounded headings."""
+    import pandas as pd
+    from atan2_exact import atan2_cr
+    from select_tables import select_settings
+    from ysmr_amd import analyse
+    from ysmr_amd.evaluate import STATS_COLUMNS
+    from ysmr_amd.synth import SyntheticVideo
+    from ysmr_amd.track_eval import track_bacteria
+    frames = SyntheticVideo(200, 260, 14, seed=3, dropout=0.01).frames(120)
+    path = tmp_path / "clip.npy"
+    np.save(path, frames)
+    s = select_settings(**{"minimal frame count": 40, "store generated statistical .csv file": True, "disable gsff": True})
+    os.makedirs(tmp_path / "first")
+    table = track_bacteria(str(path), settings=dict(s), result_folder=str(tmp_path / "first"))[0]
+    selected, info = oracle.select_tracks_oracle(table, s, 30.0, 200, 260)
+    assert selected is not None and info["good_tracks"] >= 3
+    xy = selected[["POSITION_X", "POSITION_Y"]].to_numpy()
+    assert (xy * 2 % 1 == 0).mean() > 0.2                                   # raw centres: many on the lattice
+    res = analyse(str(path), settings=dict(s), result_folder=str(tmp_path / "res"), return_df=True)
+    assert isinstance(res, tuple) and len(res) == 2
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        ref_rows, ref_stats = oracle.evaluate_tracks_oracle(selected, s, 30.0, arctan2=atan2_cr)
+    pd.testing.assert_frame_equal(res[0], ref_rows, check_exact=True)
+    pd.testing.assert_frame_equal(res[1][STATS_COLUMNS], ref_stats, check_exact=True, check_names=False)

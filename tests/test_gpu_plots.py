@@ -213,7 +213,8 @@ def histogram_table(seed):
 def test_histogram_matches_the_model(seed, lag, n_bins):
     ids, x, y, moving = histogram_table(seed)
     edges = np.linspace(-np.pi, np.pi, n_bins + 1)
-    # the device's atan2 is not correctly rounded: the comparison is only meaningful with every heading clear of the edges
+    # this model's headings are NumPy's arctan2, the device's are correctly rounded (an ulp apart on some arguments): the
+    # comparison is only meaningful with every heading clear of the edges (test_histogram_on_lattice_positions: on the edges)
     assert pm.edge_clearance(ids, x, y, moving, lag, edges) > 1e-9
     want, points = pm.angle_histogram(ids, x, y, moving, lag, edges)
     got, got_points = _histogram(ids, x, y, moving, lag, edges)
@@ -252,6 +253,46 @@ def test_histogram_constructed_cases(lag):
         assert got_points == points and np.array_equal(got, want), (got, want)
     none = _histogram(ids[:0], x[:0], y[:0], moving[:0], lag, np.linspace(-np.pi, np.pi, 5))
     assert none[1] == 0 and none[0].tolist() == [0, 0, 0, 0]
+
+
+_LATTICE = {}
+
+
+def lattice_histogram_table(oracle, seed):
+    """A lattice table (select_tables.lattice_table) with the 'moving' column of its own evaluation, built once."""
+    if seed not in _LATTICE:
+        import warnings
+        from atan2_exact import atan2_cr
+        from select_tables import lattice_table, select_settings
+        df = lattice_table(seed)
+        df = df[df.groupby("TRACK_ID")["TRACK_ID"].transform("size") >= 32].reset_index(drop=True)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            rows, _ = oracle.evaluate_tracks_oracle(df, select_settings(), 30.0, arctan2=atan2_cr)
+        _LATTICE[seed] = (df["TRACK_ID"].to_numpy(), df["POSITION_X"].to_numpy(), df["POSITION_Y"].to_numpy(),
+                          rows["moving"].to_numpy().astype(np.int8))
+    return _LATTICE[seed]
+
+
+@pytest.mark.parametrize("n_bins", [36, 8, 4, 7])
+@pytest.mark.parametrize("lag", [1, 3])
+def test_histogram_on_lattice_positions(oracle, lag, n_bins):
+    """Steps on the 0.5 lattice: the correctly rounded heading of many of them IS an edge of np.linspace(-pi, pi, n + 1)
+    (multiples of pi / 4 at 36, 8 and 4 bins; pi alone at 7), and a heading one ulp low falls into the bin before.  No clearance
+    here: the counts against the model with correctly rounded headings (tests/atan2_exact.py)."""
+    from atan2_exact import atan2_cr
+    ids, x, y, moving = lattice_histogram_table(oracle, 1)
+    edges = np.linspace(-np.pi, np.pi, n_bins + 1)
+    selected, h = pm.headings(ids, x, y, moving, lag, atan2_cr)
+    hs = h[selected]
+    hs = hs[~np.isnan(hs)]
+    on_edge = np.isin(hs, edges)
+    print(f"{on_edge.mean():.1%} of {len(hs)} selected headings equal an edge")
+    assert len(hs) > 5000 and (on_edge.mean() >= 0.10 if n_bins != 7 else on_edge.sum() >= 1)
+    want, points = pm.angle_histogram(ids, x, y, moving, lag, edges, atan2_cr)
+    got, got_points = _histogram(ids, x, y, moving, lag, edges)
+    assert got_points == points and 0 < want.sum() <= points < len(ids)
+    assert np.array_equal(got, want), (got - want)
 
 
 # ---- the wedges ------------------------------------------------------------------------------------------------------

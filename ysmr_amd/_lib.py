@@ -58,7 +58,7 @@ EXPORTS = ("ysmr_abi_version", "ysmr_last_error", "ysmr_detect_workspace_bytes",
            "ysmr_tracker_reset", "ysmr_tracker_update", "ysmr_tracker_run", "ysmr_tracker_fused", "ysmr_tracker_batched", "ysmr_tracker_link_mode", "ysmr_tracker_prepare", "ysmr_tracker_peek",
            "ysmr_tracker_info", "ysmr_rows_sort_workspace_bytes", "ysmr_rows_sort", "ysmr_rows_csv_bound",
            "ysmr_rows_format_csv", "ysmr_rows_write_csv", "ysmr_rows_write_csv_columns", "ysmr_rows_format_device_workspace_bytes", "ysmr_rows_format_device", "ysmr_rows_format_csv_devicelike", "ysmr_rows_stream_create", "ysmr_rows_stream_push", "ysmr_rows_stream_count", "ysmr_rows_stream_finish", "ysmr_rows_stream_destroy", "ysmr_rows_columns", "ysmr_select_workspace_bytes", "ysmr_select_tracks",
-           "ysmr_evaluate_workspace_bytes", "ysmr_evaluate_tracks", "ysmr_unpack_dib_batch", "ysmr_file_read",
+           "ysmr_evaluate_workspace_bytes", "ysmr_evaluate_tracks", "ysmr_atan2_devicelike", "ysmr_unpack_dib_batch", "ysmr_file_read",
            "ysmr_luminosity_batch", "ysmr_luminosity_batch_host", "ysmr_tracker_dimensions", "ysmr_tracker_update3",
            "ysmr_tracker_run3", "ysmr_tracker_peek3", "ysmr_tracker_prepare3", "ysmr_annotate_batch", "ysmr_plot_colormap",
            "ysmr_plot_extent", "ysmr_plot_workspace_bytes", "ysmr_plot_tracks", "ysmr_plot_angle_histogram", "ysmr_plot_wedges",
@@ -228,6 +228,7 @@ def lib():
     L.ysmr_evaluate_workspace_bytes.restype = ctypes.c_size_t
     L.ysmr_evaluate_tracks.argtypes = [vp, ctypes.c_longlong, vp, vp, vp, vp, vp, vp, ctypes.POINTER(EvaluateParams), vp,
                                        ctypes.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_longlong)]
+    L.ysmr_atan2_devicelike.argtypes = [vp, vp, ctypes.c_longlong, vp]
     ll = ctypes.c_longlong
     L.ysmr_plot_colormap.argtypes = [vp]
     L.ysmr_plot_extent.argtypes = [vp, ll, vp, vp, vp, ci, cd, vp]

@@ -15,8 +15,9 @@
 //   * df.index // fps is NumPy's float floor_divide (npy_divmod), the median of the per-second sums pandas'
 //     median_linear;
 //   * scipy pdist / np.sqrt(np.square + np.square): s = dx * dx + dy * dy unfused, one correctly rounded sqrt.
-// atan2 is the device library's (not correctly rounded): the heading may differ from glibc's by an ulp, which
-// matters only if a change of heading lies within an ulp of an integer number of degrees (it is truncated).
+// The heading is the CORRECTLY ROUNDED atan2 (atan2_cr.h), not the device library's, which is an ulp off on a quarter of the
+// half-integer step vectors: on lattice positions ('disable gsff') a change of heading is a whole number of degrees again
+// and again, and it is truncated.  NumPy's and glibc's own atan2 differ from each other there; DESIGN.md, "The figures".
 // Compiled with -ffp-contract=off.  One call per video, all grids resident-sized.
 #include <hip/hip_runtime.h>
 
@@ -24,6 +25,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "atan2_cr.h"
 #include "common.h"
 #include "prim.h"
 #include "table.h"
@@ -99,7 +101,7 @@ __global__ __launch_bounds__(256) void k_ev_heading(EvRows r, long long n, EvPar
         const long long a = r.first[r.seg[i]];
         double deg = nan64();
         if (i - p.lag_angle >= a)
-            deg = atan2(r.x[i] - r.x[i - p.lag_angle], r.y[i] - r.y[i - p.lag_angle]) * 57.29577951308232;   // np.degrees
+            deg = ysmr::atan2cr::atan2_cr(r.x[i] - r.x[i - p.lag_angle], r.y[i] - r.y[i - p.lag_angle]) * 57.29577951308232;   // np.degrees
         r.heading[i] = deg;
     }
 }
@@ -294,6 +296,13 @@ uint32_t *ev_carve(Arena &a, long long n, EvRows &r)
 }  // namespace
 
 extern "C" {
+
+int ysmr_atan2_devicelike(const double *y, const double *x, long long n, double *out)
+{
+    if (n < 0 || (n > 0 && (!y || !x || !out))) return ysmr::fail(YSMR_ERR_ARG, "n must be >= 0 and the arrays not NULL");
+    for (long long i = 0; i < n; ++i) out[i] = ysmr::atan2cr::atan2_cr(y[i], x[i]);
+    return YSMR_OK;
+}
 
 size_t ysmr_evaluate_workspace_bytes(long long n_rows)
 {

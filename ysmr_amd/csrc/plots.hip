@@ -17,6 +17,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "atan2_cr.h"
 #include "common.h"
 #include "plot_lut.h"
 #include "prim.h"
@@ -305,7 +306,7 @@ __global__ __launch_bounds__(256) void k_hist(long long n, const uint32_t *__res
         if (!((double)ones / (double)(l - f + 1) > 0.7)) continue;
         atomicAdd(&s_points, 1u);
         if (i - lag < f) continue;
-        const double h = atan2(x[i] - x[i - lag], y[i] - y[i - lag]);
+        const double h = ysmr::atan2cr::atan2_cr(x[i] - x[i - lag], y[i] - y[i - lag]);   // correctly rounded, as k_ev_heading
         if (!(h >= s_edges[0]) || !(h <= s_edges[n_bins])) continue;
         int lo = 0, hi = n_bins;
         while (hi - lo > 1) {
