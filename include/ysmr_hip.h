@@ -11,6 +11,8 @@
  *   ysmr_unpack_dib_batch cv2.VideoCapture.read (uncompressed AVI frames)   ysmr/track_eval.py:159
  *   ysmr_mjpeg_decode_batch cv2.VideoCapture.read (Motion-JPEG AVI frames)  ysmr/track_eval.py:159
  *   ysmr_annotate_batch   cv2.putText + cv2.circle + cv2.VideoWriter.write   ysmr/track_eval.py:1423-1449
+ *   ysmr_view_*           cv2.drawContours + cv2.putText + cv2.circle of the window 'display video analysis' opens, into a file
+ *                         ysmr/track_eval.py:306-325, 353-362
  *   ysmr_mjpeg_batch      cv2.VideoWriter.write with fourcc 'MJPG' ('save video fourcc codec')   ysmr/track_eval.py:1400-1449
  *   ysmr_threshold_batch  cv2.cvtColor + cv2.GaussianBlur + 2 x cv2.adaptiveThreshold
  *                         ysmr/track_eval.py:180-208
@@ -52,7 +54,7 @@ extern "C" {
 #define YSMR_ERR_CAPACITY  3   /* a fixed-capacity buffer would overflow (tracks, workspace) */
 #define YSMR_ERR_STATE     4   /* handle used in the wrong state */
 
-/* 15 still: ysmr_annotate_batch with its mark struct, and later the ysmr_plot_*, ysmr_mjpeg_*, ysmr_violin_* and ysmr_mjpeg_decode_* functions, were ADDED under this number
+/* 15 still: ysmr_annotate_batch with its mark struct, and later the ysmr_plot_*, ysmr_mjpeg_*, ysmr_violin_*, ysmr_mjpeg_decode_* and ysmr_view_* functions, were ADDED under this number
  * -- no existing entry point, struct or constant changed, so every caller written against 15 keeps working; only a caller
  * of a new function needs a library that has it (the loader reports a missing symbol by name). */
 #define YSMR_ABI_VERSION   15
@@ -147,6 +149,42 @@ typedef struct {
 int ysmr_annotate_batch(void *stream, const uint8_t *frames_dev, int n_frames, int height, int width, int channels,
                         const ysmr_mark *marks_dev, const int64_t *first_dev,
                         uint8_t *out_dev, int out_stride, size_t out_frame_bytes, int bottom_up);
+
+/* ---- detection view ---------------------------------------------------------------------- */
+
+/* ADDED under ABI 15 (see above).  What the window "... unfiltered possible detections" of track_bacteria shows
+ * (ysmr/track_eval.py:306-325, 353-362), as stored DIB frames: the frame with every detection's box outlined in blue and
+ * every live track's id and centroid in green.  PIXEL RULE (the project's own; the cv2 half is parity-unpinned, like
+ * ysmr_luminosity_batch's): the frame expanded to B, G, R, then two layers, later over earlier --
+ *   boxes   for every detection d < det_count[frame] the closed outline of np.intp(cv2.boxPoints(rect)), the corners
+ *           ysmr_luminosity_batch reports in corners_dev: the four 8-connected lines corner i-1 -> corner i, each walked from
+ *           its left end, pixels outside the frame dropped and nothing clipped beforehand, (B, G, R) = (255, 0, 0); a box
+ *           whose corners coincide paints that pixel (cv2.drawContours with thickness <= 1 and LINE_8, as recollected);
+ *   tracks  for every row of the frame the id's decimal digits and the single-pixel dot at (int(x), int(y)), truncated
+ *           toward zero: exactly style 0 of ysmr_annotate_batch, (0, 255, 0).  Rows of "disappeared" tracks are painted
+ *           too (upstream goes through objects.items(), which holds them); a row whose position is not finite is not.
+ * Upstream's "FPS: n" lettering is not drawn.  The work per outline is bounded by the frame's size, wherever the corners
+ * are (they are moved to +-2^20 at most).
+ *
+ * ysmr_view_boxes_batch packs the frames exactly as ysmr_annotate_batch does with first_dev = NULL (same arguments, same
+ * layout, same zeroed row padding) and paints the box layer; det_dev / det_count_dev / max_det as ysmr_detect_batch leaves
+ * them (the cv_flavour angle is already in the detections).
+ * ysmr_view_tracks_batch paints the track layer into such frames, later on the same stream or behind an event: the rows
+ * rows_dev[*row_begin_dev .. *row_end_dev) -- two DEVICE integers, e.g. the row counter of ysmr_tracker_run copied before
+ * and after the batch's link, so that no host synchronisation is needed; the range is cut to [0, rows_capacity) -- in any
+ * order; a row goes into frame row.frame - first_frame_index and is skipped if that is outside [0, n_frames).
+ * ysmr_view_batch_host: HOST function, both layers on host arrays with the same pixel-deciding code (row_begin / row_end
+ * are values here; rows_host may be NULL if there are none). */
+int ysmr_view_boxes_batch(void *stream, const uint8_t *frames_dev, int n_frames, int height, int width, int channels,
+                          const float *det_dev, const int32_t *det_count_dev, int max_det,
+                          uint8_t *out_dev, int out_stride, size_t out_frame_bytes, int bottom_up);
+int ysmr_view_tracks_batch(void *stream, const ysmr_row *rows_dev, int64_t rows_capacity, const int64_t *row_begin_dev,
+                           const int64_t *row_end_dev, int32_t first_frame_index, int n_frames, int height, int width,
+                           uint8_t *dib_dev, int stride, size_t frame_bytes, int bottom_up);
+int ysmr_view_batch_host(const uint8_t *frames_host, int n_frames, int height, int width, int channels,
+                         const float *det_host, const int32_t *det_count_host, int max_det,
+                         const ysmr_row *rows_host, int64_t row_begin, int64_t row_end, int32_t first_frame_index,
+                         uint8_t *out_host, int out_stride, size_t out_frame_bytes, int bottom_up);
 
 /* ---- frame ingest: Motion-JPEG ------------------------------------------------------------------ */
 

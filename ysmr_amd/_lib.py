@@ -66,7 +66,8 @@ EXPORTS = ("ysmr_abi_version", "ysmr_last_error", "ysmr_detect_workspace_bytes",
            "ysmr_mjpeg_decode_workspace_bytes", "ysmr_mjpeg_decode_batch",
            "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_batch_sync", "ysmr_mjpeg_decode_sync_geometry",
            "ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_png_deflate", "ysmr_plot_stamp",
-           "ysmr_png_dynamic_workspace_bytes", "ysmr_png_dynamic_stream_bytes_max", "ysmr_png_deflate_dynamic", "ysmr_png_code_lengths")
+           "ysmr_png_dynamic_workspace_bytes", "ysmr_png_dynamic_stream_bytes_max", "ysmr_png_deflate_dynamic", "ysmr_png_code_lengths",
+           "ysmr_view_boxes_batch", "ysmr_view_tracks_batch", "ysmr_view_batch_host")
 
 #: numpy view of ``ysmr_mark`` (16 bytes): one track position of one frame of the annotated video
 MARK_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("track_id", "<u4"), ("style", "<u4")])
@@ -267,6 +268,10 @@ def lib():
     L.ysmr_png_dynamic_stream_bytes_max.restype = ctypes.c_size_t
     L.ysmr_png_deflate_dynamic.argtypes = [vp, vp, ci, ci, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]
     L.ysmr_png_code_lengths.argtypes = [vp, ci, ci, vp]
+    L.ysmr_view_boxes_batch.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, ci, vp, ci, ctypes.c_size_t, ci]
+    L.ysmr_view_tracks_batch.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int32, ci, ci, ci, vp, ci, ctypes.c_size_t, ci]
+    L.ysmr_view_batch_host.argtypes = [vp, ci, ci, ci, ci, vp, vp, ci, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, vp, ci,
+                                       ctypes.c_size_t, ci]
     for name in EXPORTS:
         if name not in ("ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_png_dynamic_workspace_bytes", "ysmr_png_dynamic_stream_bytes_max", "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_sync_geometry", "ysmr_mjpeg_decode_workspace_bytes", "ysmr_violin_workspace_bytes", "ysmr_mjpeg_workspace_bytes", "ysmr_mjpeg_encode_workspace_bytes", "ysmr_plot_workspace_bytes", "ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
                         "ysmr_rows_sort_workspace_bytes", "ysmr_rows_csv_bound", "ysmr_rows_stream_count",

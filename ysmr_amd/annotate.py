@@ -11,7 +11,9 @@ and hands the frames to ``cv2.VideoWriter``.  Here the frames come through ``Dev
   device; the copy stream brings over their offsets and then only the bytes those name, and the writer thread appends
   them to a Motion-JPEG AVI (``MjpegAviWriter``).
 
-Either way the host moves bytes and touches no pixel.
+Either way the host moves bytes and touches no pixel.  The way from the painted device buffer to the file -- two slots, the
+copy stream, the pinned buffers, the writer thread, the encode call -- is ``DibOutput``; the detection view of
+``track_bacteria`` ('hip save detection video', ``track_eval._DetectionView``) leaves through it as well.
 
 Departures from upstream, all deliberate:
 
@@ -46,7 +48,7 @@ from . import _lib
 from .frames import DeviceFrameFeed, decode_mjpeg_setting, open_video
 from .helper_file import create_results_folder, get_configs, get_data, get_loggers
 
-__all__ = ["annotate_video", "AviWriter", "MjpegAviWriter", "output_format", "jpeg_mode", "build_marks", "subtype_code", "SUBTYPES"]
+__all__ = ["annotate_video", "AviWriter", "MjpegAviWriter", "DibOutput", "output_format", "jpeg_mode", "build_marks", "subtype_code", "SUBTYPES"]
 
 SUBTYPES = ("immotile", "twitching", "motile")
 #: one pinned output buffer (there are two) holds at most this many bytes
@@ -387,127 +389,174 @@ def _csv_table(path, logger, settings):
     return get_data(path, dtype=dtype)
 
 
-def _mjpeg_frames(video, writer, marks, first, n_frames, quality, mode, settings, result_folder, dev, logger):
-    """The loop of ``annotate_video`` in Motion-JPEG mode: ``ysmr_annotate_batch`` paints a batch into a device buffer of
-    stored DIB frames, ``ysmr_mjpeg_encode_batch`` encodes that (``mode``: its sampling and huffman) into finished chunks, the copy stream brings the offsets and the
-    status over and then only the bytes the offsets name, and the writer thread appends them.  Two output buffers on the
-    device and two pinned ones, as in the uncompressed mode; their default capacity is the batch's uncompressed size, and a
-    batch that does not fit is encoded once more into buffers of the size its offsets ask for.  Returns the number of frames
-    written, None (after a critical message) if the disk runs full; anything else is raised."""
-    import torch
-    height, width, channels = video.height, video.width, video.channels
-    stride, frame_bytes = writer.stride, writer.frame_bytes
-    L = _lib.lib()
-    sampling, huffman = mode
-    batch = int(settings.get("hip frames per batch") or 0) or auto_batch(frame_bytes + 8, n_frames)
-    batch = max(1, min(batch, auto_batch(frame_bytes + 8, n_frames),
-                       MJPEG_WORKSPACE_MAX // max(1, L.ysmr_mjpeg_encode_workspace_bytes(1, height, width, sampling, huffman))))
-    ws_bytes = L.ysmr_mjpeg_encode_workspace_bytes(batch, height, width, sampling, huffman)
-    if not ws_bytes:
-        raise ValueError("a Motion-JPEG frame is at most 65535 x 65535, got {} x {}".format(width, height))
-    with _lib.on(dev):
-        marks_dev = torch.from_numpy(marks.view(np.uint8).reshape(-1)).to(dev) if len(marks) else \
-            torch.zeros(16, dtype=torch.uint8, device=dev)
-        first_dev = torch.from_numpy(first).to(dev)
-        dib_dev = torch.empty((batch, frame_bytes), dtype=torch.uint8, device=dev)       # (one: paint and encode are in order)
-        workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        capacity = [batch * frame_bytes] * 2
-        out_dev = [torch.empty(capacity[k], dtype=torch.uint8, device=dev) for k in range(2)]
-        pinned = [torch.empty(capacity[k], dtype=torch.uint8, pin_memory=True) for k in range(2)]
-        # offsets [batch + 1] and, in the last element, the status
-        meta_dev = [torch.zeros(batch + 2, dtype=torch.int64, device=dev) for _k in range(2)]
-        meta = [torch.zeros(batch + 2, dtype=torch.int64, pin_memory=True) for _k in range(2)]
-        copy_stream = torch.cuda.Stream(device=dev)
-        free_slots, jobs, failure = queue.Queue(), queue.Queue(), []
+class DibOutput:
+    """The way of painted frames from the device to the file, for ``annotate_video`` and for the detection view of
+    ``track_bacteria``: two slots, each a device buffer of ``batch`` stored DIB frames and a pinned host buffer, a copy
+    stream and a writer thread.
+
+    ``writer`` an ``AviWriter``: every frame has its chunk header in front of it, written once here (the kernels write
+    behind it), so that a batch goes to the file as it is.  A ``MjpegAviWriter`` (``quality`` and ``mode``, its sampling
+    and huffman, are then needed): ``ysmr_mjpeg_encode_batch`` encodes a slot's frames into finished chunks, the copy stream
+    brings the offsets and the status over and then only the bytes the offsets name; the output buffers' default capacity
+    is the batch's uncompressed size, and a batch that does not fit is encoded once more into buffers of the size its
+    offsets ask for; the free space of ``result_folder`` is checked against the bytes about to be written.
+
+    ``acquire`` -> a slot whose last batch has been written; ``frames`` -> where a kernel paints it; ``submit`` hands its
+    first n frames over once ``painted`` (an event) has happened; ``close`` waits for the writer thread.  A failure of the
+    writer thread is raised by the next ``acquire``; after ``close`` it is in ``failure``.  ``submit`` and ``close`` make
+    ``dev`` the current device themselves.  ``dib_slots`` (Motion-JPEG only, where the frames are painted into a DIB buffer
+    and encoded from there): 1 -- paint and encode of a batch follow each other on one stream, as in ``annotate_video``, and
+    one buffer serves both slots; 2 -- a buffer per slot, for a caller that paints a batch while the one before still waits
+    to be encoded (the detection view)."""
+
+    def __init__(self, writer, batch, height, width, dev, quality=None, mode=None, result_folder=None, logger=None, dib_slots=1):
+        import torch
+        self.writer, self.batch, self.dev, self.height, self.width = writer, int(batch), dev, int(height), int(width)
+        self.mjpeg = isinstance(writer, MjpegAviWriter)
+        self.logger, self.result_folder = logger, result_folder
+        self.shortfall = None              # (bytes needed, bytes free) once the disk has run full: nothing more is written
+        self.L = _lib.lib()
+        frame_bytes = writer.frame_bytes
+        with _lib.on(dev):
+            if self.mjpeg:
+                self.quality, (self.sampling, self.huffman) = quality, mode
+                self.ws_bytes = self.L.ysmr_mjpeg_encode_workspace_bytes(self.batch, self.height, self.width, self.sampling, self.huffman)
+                if not self.ws_bytes:
+                    raise ValueError("a Motion-JPEG frame is at most 65535 x 65535, got {} x {}".format(width, height))
+                self.pitch = frame_bytes
+                self.dib = [torch.empty((self.batch, frame_bytes), dtype=torch.uint8, device=dev) for _k in range(2 if dib_slots > 1 else 1)]
+                self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
+                self.capacity = [self.batch * frame_bytes] * 2
+                self.out_dev = [torch.empty(self.capacity[k], dtype=torch.uint8, device=dev) for k in range(2)]
+                self.pinned = [torch.empty(self.capacity[k], dtype=torch.uint8, pin_memory=True) for k in range(2)]
+                # offsets [batch + 1] and, in the last element, the status
+                self.meta_dev = [torch.zeros(self.batch + 2, dtype=torch.int64, device=dev) for _k in range(2)]
+                self.meta = [torch.zeros(self.batch + 2, dtype=torch.int64, pin_memory=True) for _k in range(2)]
+            else:
+                self.pitch = frame_bytes + 8
+                head = torch.from_numpy(np.frombuffer(writer.chunk_header(), np.uint8).copy())
+                self.out_dev, self.pinned = [], []
+                for _k in range(2):
+                    buf = torch.empty((self.batch, self.pitch), dtype=torch.uint8, device=dev)
+                    buf[:, :8] = head.to(dev)
+                    self.out_dev.append(buf)
+                    self.pinned.append(torch.empty((self.batch, self.pitch), dtype=torch.uint8, pin_memory=True))
+            self.copy_stream = torch.cuda.Stream(device=dev)
+        self.free_slots, self.jobs, self.failure = queue.Queue(), queue.Queue(), []
         for k in range(2):
-            free_slots.put(k)
+            self.free_slots.put(k)
+        self.thread = threading.Thread(target=self._write_loop, name="ysmr-annotate-writer", daemon=True)
+        self.thread.start()
 
-        def write_loop():
-            while True:
-                job = jobs.get()
-                if job is None:
-                    return
-                k, offsets, copied = job
-                try:
-                    if not failure:
-                        copied.synchronize()
-                        writer.write_chunks(pinned[k].numpy()[:offsets[-1]], offsets)
-                except BaseException as exc:      # noqa: BLE001 -- handed to the caller's thread
-                    failure.append(exc)
-                free_slots.put(k)
+    @staticmethod
+    def mjpeg_batch_limit(height, width, mode):
+        """The most frames per batch that keep the encoder's workspace at or below MJPEG_WORKSPACE_MAX."""
+        return max(1, MJPEG_WORKSPACE_MAX // max(1, _lib.lib().ysmr_mjpeg_encode_workspace_bytes(1, height, width, mode[0], mode[1])))
 
-        def encode(stream, k, n):
-            """Encode the painted batch into slot k and bring offsets and status over: (offsets, status)."""
-            _lib.check(L.ysmr_mjpeg_encode_batch(
-                stream.cuda_stream, dib_dev.data_ptr(), n, height, width, stride, frame_bytes, int(writer.bottom_up), quality,
-                sampling, huffman, workspace.data_ptr(), ws_bytes, out_dev[k].data_ptr(), capacity[k], meta_dev[k].data_ptr(),
-                meta_dev[k].data_ptr() + 8 * (batch + 1)), "ysmr_mjpeg_encode_batch")
-            encoded = torch.cuda.Event()
-            encoded.record(stream)
-            with torch.cuda.stream(copy_stream):
-                copy_stream.wait_event(encoded)
-                meta[k].copy_(meta_dev[k], non_blocking=True)
-                known = torch.cuda.Event()
-                known.record(copy_stream)
-            known.synchronize()
-            values = meta[k].numpy()
-            return [int(v) for v in values[:n + 1]], int(values[batch + 1]) & 0xFFFFFFFF
+    def _write_loop(self):
+        while True:
+            job = self.jobs.get()
+            if job is None:
+                return
+            k, what, copied = job
+            try:
+                if not self.failure:
+                    copied.synchronize()
+                    if self.mjpeg:
+                        self.writer.write_chunks(self.pinned[k].numpy()[:what[-1]], what)
+                    else:
+                        self.writer.write_chunks(self.pinned[k].numpy()[:what])
+            except BaseException as exc:      # noqa: BLE001 -- handed to the caller's thread
+                self.failure.append(exc)
+            self.free_slots.put(k)
 
-        thread = threading.Thread(target=write_loop, name="ysmr-annotate-writer", daemon=True)
-        thread.start()
-        done, shortfall, feed = 0, None, None
-        try:
-            feed = DeviceFrameFeed(video, batch, dev, depth=2, decode_on_device=decode_mjpeg_setting(settings))
-            for frames_dev, f0, n, slot in feed:
-                n = min(n, n_frames - f0)
-                if n <= 0:
-                    feed.release(slot, True)
-                    break
-                k = free_slots.get()              # its last copy has been written: both buffers of slot k are free
-                if failure:
-                    raise failure[0]
-                stream = torch.cuda.current_stream(dev)
-                _lib.check(L.ysmr_annotate_batch(
-                    stream.cuda_stream, frames_dev.data_ptr(), n, height, width, channels, marks_dev.data_ptr(),
-                    first_dev.data_ptr() + 8 * f0, dib_dev.data_ptr(), stride, frame_bytes, int(writer.bottom_up)),
-                    "ysmr_annotate_batch")
-                painted = torch.cuda.Event()
-                painted.record(stream)
-                feed.release(slot, painted)
-                offsets, status = encode(stream, k, n)
-                if status & 1:
-                    logger.debug("Motion-JPEG: frames {} .. {} take {} bytes, the buffer has {}: encoding them again".format(
-                        f0, f0 + n - 1, offsets[-1], capacity[k]))
-                    capacity[k] = offsets[-1]
-                    out_dev[k] = torch.empty(capacity[k], dtype=torch.uint8, device=dev)
-                    pinned[k] = torch.empty(capacity[k], dtype=torch.uint8, pin_memory=True)
-                    offsets, status = encode(stream, k, n)
-                if status:
-                    raise RuntimeError("ysmr_mjpeg_encode_batch: status {} for frames {} .. {} ({} bytes into {})".format(
-                        status, f0, f0 + n - 1, offsets[-1], capacity[k]))
-                need, free = offsets[-1] + 24 * n + 4096, shutil.disk_usage(result_folder).free
-                if free < need:
-                    shortfall = (need, free)
-                    break
-                with torch.cuda.stream(copy_stream):
-                    pinned[k][:offsets[-1]].copy_(out_dev[k][:offsets[-1]], non_blocking=True)
-                    copied = torch.cuda.Event()
-                    copied.record(copy_stream)
-                jobs.put((k, offsets, copied))
-                done = f0 + n
-        finally:
-            jobs.put(None)
-            thread.join()
-            torch.cuda.synchronize(dev)
-            if feed is not None:
-                feed.close()
-        if failure:
-            raise failure[0]
-        if shortfall:
-            logger.critical("Not enough free space in {} for the annotated video: {} bytes needed, {} free".format(
-                result_folder, shortfall[0], shortfall[1]))
-            return None
-    return done
+    def acquire(self):
+        k = self.free_slots.get()              # its last copy has been written: both buffers of slot k are free
+        if self.failure:
+            raise self.failure[0]
+        return k
+
+    def frames(self, k):
+        """(device pointer of the slot's first stored frame, bytes from one frame to the next)."""
+        return (self.dib[k % len(self.dib)].data_ptr(), self.pitch) if self.mjpeg else (self.out_dev[k].data_ptr() + 8, self.pitch)
+
+    def _encode(self, stream, k, n):
+        """Encode the painted batch into slot k and bring offsets and status over: (offsets, status)."""
+        import torch
+        w = self.writer
+        _lib.check(self.L.ysmr_mjpeg_encode_batch(
+            stream.cuda_stream, self.dib[k % len(self.dib)].data_ptr(), n, self.height, self.width, w.stride, w.frame_bytes, int(w.bottom_up),
+            self.quality, self.sampling, self.huffman, self.workspace.data_ptr(), self.ws_bytes, self.out_dev[k].data_ptr(),
+            self.capacity[k], self.meta_dev[k].data_ptr(), self.meta_dev[k].data_ptr() + 8 * (self.batch + 1)), "ysmr_mjpeg_encode_batch")
+        encoded = torch.cuda.Event()
+        encoded.record(stream)
+        with torch.cuda.stream(self.copy_stream):
+            self.copy_stream.wait_event(encoded)
+            self.meta[k].copy_(self.meta_dev[k], non_blocking=True)
+            known = torch.cuda.Event()
+            known.record(self.copy_stream)
+        known.synchronize()
+        values = self.meta[k].numpy()
+        return [int(v) for v in values[:n + 1]], int(values[self.batch + 1]) & 0xFFFFFFFF
+
+    def submit(self, k, n, first_frame, stream, painted):
+        """The first ``n`` frames of slot k, painted on ``stream`` (``painted``: an event recorded there behind the paint),
+        are frames ``first_frame`` .. of the file.  False: the disk is full (``shortfall``), nothing was handed over."""
+        with _lib.on(self.dev):
+            return self._submit(k, n, first_frame, stream, painted)
+
+    def _submit(self, k, n, first_frame, stream, painted):
+        import torch
+        if not self.mjpeg:
+            with torch.cuda.stream(self.copy_stream):
+                self.copy_stream.wait_event(painted)
+                self.pinned[k][:n].copy_(self.out_dev[k][:n], non_blocking=True)
+                copied = torch.cuda.Event()
+                copied.record(self.copy_stream)
+            self.jobs.put((k, n, copied))
+            return True
+        offsets, status = self._encode(stream, k, n)
+        if status & 1:
+            if self.logger is not None:
+                self.logger.debug("Motion-JPEG: frames {} .. {} take {} bytes, the buffer has {}: encoding them again".format(
+                    first_frame, first_frame + n - 1, offsets[-1], self.capacity[k]))
+            self.capacity[k] = offsets[-1]
+            self.out_dev[k] = torch.empty(self.capacity[k], dtype=torch.uint8, device=self.dev)
+            self.pinned[k] = torch.empty(self.capacity[k], dtype=torch.uint8, pin_memory=True)
+            offsets, status = self._encode(stream, k, n)
+        if status:
+            raise RuntimeError("ysmr_mjpeg_encode_batch: status {} for frames {} .. {} ({} bytes into {})".format(
+                status, first_frame, first_frame + n - 1, offsets[-1], self.capacity[k]))
+        need, free = offsets[-1] + 24 * n + 4096, shutil.disk_usage(self.result_folder).free
+        if free < need:
+            self.shortfall = (need, free)
+            self.free_slots.put(k)
+            return False
+        with torch.cuda.stream(self.copy_stream):
+            self.pinned[k][:offsets[-1]].copy_(self.out_dev[k][:offsets[-1]], non_blocking=True)
+            copied = torch.cuda.Event()
+            copied.record(self.copy_stream)
+        self.jobs.put((k, offsets, copied))
+        return True
+
+    def close(self):
+        """Wait for everything handed over to be written (or given up); safe to call twice."""
+        import torch
+        if self.thread is not None:
+            self.jobs.put(None)
+            self.thread.join()
+            self.thread = None
+            with _lib.on(self.dev):
+                torch.cuda.synchronize(self.dev)
+
+
+def enough_space(result_folder, needed, what, logger):
+    """The free-space check in front of an uncompressed file: False after a critical message."""
+    free = shutil.disk_usage(result_folder).free
+    if free < needed:
+        logger.critical("Not enough free space in {} for the {}: {} bytes needed, {} free".format(result_folder, what, needed, free))
+        return False
+    return True
 
 
 def annotate_video(video_path, df, output_save=True, settings=None, result_folder=None, select_subtype=None,
@@ -576,108 +625,61 @@ def annotate_video(video_path, df, output_save=True, settings=None, result_folde
             logger.critical("Error during cap.read() with file {}".format(video_path))
             return None
         height, width, channels = video.height, video.width, video.channels
+        dev = torch.device(device)
+        L = _lib.lib()
         if fmt == "mjpeg":
             marks, first = build_marks(df, n_frames, select_subtype)
             writer = MjpegAviWriter(output_video_name, width, height, fps_of_file)
             mode = jpeg_mode(settings)
             logger.info("Annotated video {}: {} frames of {} x {}, Motion-JPEG, quality {}{}".format(
                 output_video_name, n_frames, width, height, quality, jpeg_mode_name(*mode)))
-            done = _mjpeg_frames(video, writer, marks, first, n_frames, quality, mode, settings, result_folder,
-                                 torch.device(device), logger)
-            if done is None:
+            batch = int(settings.get("hip frames per batch") or 0) or auto_batch(writer.frame_bytes + 8, n_frames)
+            batch = max(1, min(batch, auto_batch(writer.frame_bytes + 8, n_frames), DibOutput.mjpeg_batch_limit(height, width, mode)))
+        else:
+            mode = None
+            expected = AviWriter.file_bytes(width, height, n_frames)
+            logger.info("Annotated video {}: {} frames of {} x {}, {:.1f} MiB uncompressed".format(
+                output_video_name, n_frames, width, height, expected / 2 ** 20))
+            if not enough_space(result_folder, expected, "annotated video", logger):
                 return None
-            frame_count = video.frame_count
-            if done not in (frame_count, frame_count - 1):
-                logger.critical("Error during cap.read() with file {}".format(video_path))
-            else:
-                logger.debug("Frames from file {} read.".format(os.path.basename(video_path)))
-            writer.close()
-            writer = None
-            written, raw = os.path.getsize(output_video_name), AviWriter.file_bytes(width, height, done)
-            logger.info("Output video file: {}: {:.1f} MiB written, {:.3f} of the {:.1f} MiB of the uncompressed AVI".format(
-                output_video_name, written / 2 ** 20, written / raw, raw / 2 ** 20))
-            return output_video_name
-        expected = AviWriter.file_bytes(width, height, n_frames)
-        logger.info("Annotated video {}: {} frames of {} x {}, {:.1f} MiB uncompressed".format(
-            output_video_name, n_frames, width, height, expected / 2 ** 20))
-        free = shutil.disk_usage(result_folder).free
-        if free < expected:
-            logger.critical("Not enough free space in {} for the annotated video: {} bytes needed, {} free".format(
-                result_folder, expected, free))
-            return None
-        marks, first = build_marks(df, n_frames, select_subtype)
-        writer = AviWriter(output_video_name, width, height, fps_of_file)
-        chunk_bytes = writer.frame_bytes + 8
-        batch = int(settings.get("hip frames per batch") or 0) or auto_batch(chunk_bytes, n_frames)
-        batch = max(1, min(batch, auto_batch(chunk_bytes, n_frames)))
-        dev = torch.device(device)
-        L = _lib.lib()
-        with _lib.on(dev):
-            marks_dev = torch.from_numpy(marks.view(np.uint8).reshape(-1)).to(dev) if len(marks) else \
-                torch.zeros(16, dtype=torch.uint8, device=dev)
-            first_dev = torch.from_numpy(first).to(dev)
-            # two output buffers on the device and two pinned ones; every frame has its chunk header in front of it, written
-            # once here (the kernels write behind it), so that a batch goes to the file as it is
-            head = torch.from_numpy(np.frombuffer(writer.chunk_header(), np.uint8).copy())
-            out_dev, pinned = [], []
-            for _k in range(2):
-                buf = torch.empty((batch, chunk_bytes), dtype=torch.uint8, device=dev)
-                buf[:, :8] = head.to(dev)
-                out_dev.append(buf)
-                pinned.append(torch.empty((batch, chunk_bytes), dtype=torch.uint8, pin_memory=True))
-            copy_stream = torch.cuda.Stream(device=dev)
-            free_slots, jobs, failure = queue.Queue(), queue.Queue(), []
-            for k in range(2):
-                free_slots.put(k)
-
-            def write_loop():
-                while True:
-                    job = jobs.get()
-                    if job is None:
-                        return
-                    k, n, copied = job
-                    try:
-                        if not failure:
-                            copied.synchronize()
-                            writer.write_chunks(pinned[k].numpy()[:n])
-                    except BaseException as exc:      # noqa: BLE001 -- handed to the caller's thread
-                        failure.append(exc)
-                    free_slots.put(k)
-
-            thread = threading.Thread(target=write_loop, name="ysmr-annotate-writer", daemon=True)
-            thread.start()
-            done = 0
-            try:
+            marks, first = build_marks(df, n_frames, select_subtype)
+            writer = AviWriter(output_video_name, width, height, fps_of_file)
+            batch = int(settings.get("hip frames per batch") or 0) or auto_batch(writer.frame_bytes + 8, n_frames)
+            batch = max(1, min(batch, auto_batch(writer.frame_bytes + 8, n_frames)))
+        sink = DibOutput(writer, batch, height, width, dev, quality=quality, mode=mode, result_folder=result_folder, logger=logger)
+        done = 0
+        try:
+            with _lib.on(dev):
+                marks_dev = torch.from_numpy(marks.view(np.uint8).reshape(-1)).to(dev) if len(marks) else \
+                    torch.zeros(16, dtype=torch.uint8, device=dev)
+                first_dev = torch.from_numpy(first).to(dev)
                 feed = DeviceFrameFeed(video, batch, dev, depth=2, decode_on_device=decode_mjpeg_setting(settings))
                 for frames_dev, f0, n, slot in feed:
                     n = min(n, n_frames - f0)
                     if n <= 0:
                         feed.release(slot, True)
                         break
-                    k = free_slots.get()              # its last copy has been written: both buffers of slot k are free
-                    if failure:
-                        raise failure[0]
+                    k = sink.acquire()
                     stream = torch.cuda.current_stream(dev)
+                    out_ptr, pitch = sink.frames(k)
                     _lib.check(L.ysmr_annotate_batch(
                         stream.cuda_stream, frames_dev.data_ptr(), n, height, width, channels, marks_dev.data_ptr(),
-                        first_dev.data_ptr() + 8 * f0, out_dev[k].data_ptr() + 8, writer.stride, chunk_bytes,
-                        int(writer.bottom_up)), "ysmr_annotate_batch")
+                        first_dev.data_ptr() + 8 * f0, out_ptr, writer.stride, pitch, int(writer.bottom_up)), "ysmr_annotate_batch")
                     painted = torch.cuda.Event()
                     painted.record(stream)
                     feed.release(slot, painted)
-                    with torch.cuda.stream(copy_stream):
-                        copy_stream.wait_event(painted)
-                        pinned[k][:n].copy_(out_dev[k][:n], non_blocking=True)
-                        copied = torch.cuda.Event()
-                        copied.record(copy_stream)
-                    jobs.put((k, n, copied))
+                    if not sink.submit(k, n, f0, stream, painted):
+                        break
                     done = f0 + n
-            finally:
-                jobs.put(None)
-                thread.join()
-                torch.cuda.synchronize(dev)
-            if failure:
-                raise failure[0]
+        finally:
+            with _lib.on(dev):
+                sink.close()
+        if sink.failure:
+            raise sink.failure[0]
+        if sink.shortfall:
+            logger.critical("Not enough free space in {} for the annotated video: {} bytes needed, {} free".format(
+                result_folder, sink.shortfall[0], sink.shortfall[1]))
+            return None
         frame_count = video.frame_count
         if done not in (frame_count, frame_count - 1):   # (track_eval.py:1411-1418: some formats report one frame more)
             logger.critical("Error during cap.read() with file {}".format(video_path))
@@ -685,7 +687,12 @@ def annotate_video(video_path, df, output_save=True, settings=None, result_folde
             logger.debug("Frames from file {} read.".format(os.path.basename(video_path)))
         writer.close()
         writer = None
-        logger.debug("Output video file: {}".format(output_video_name))
+        if fmt == "mjpeg":
+            written, raw = os.path.getsize(output_video_name), AviWriter.file_bytes(width, height, done)
+            logger.info("Output video file: {}: {:.1f} MiB written, {:.3f} of the {:.1f} MiB of the uncompressed AVI".format(
+                output_video_name, written / 2 ** 20, written / raw, raw / 2 ** 20))
+        else:
+            logger.debug("Output video file: {}".format(output_video_name))
         return output_video_name
     except Exception as exc:      # noqa: BLE001 -- "log + return None", as every entry point
         logger.critical("Annotating file {} failed: {}: {}".format(video_path, type(exc).__name__, exc))

@@ -11,27 +11,15 @@
 // dot's top), and it stores what the sequential painter leaves there.  No two lanes of the launch write the same byte, so
 // the result does not depend on scheduling; no atomics, no owner map.
 #include "common.h"
+#include "glyph.h"
 #include <algorithm>
 
 namespace {
 
+using namespace ysmr::glyph;   // the digits and where a mark's pixels are: shared with view.hip
+
 constexpr int PACK_BLOCKS = 1024;    // resident grids (see ingest.hip)
 constexpr int PAINT_BLOCKS = 1024;
-constexpr int GLYPH_W = 5, GLYPH_H = 7, GLYPH_STEP = 6;   // a digit cell: 5 x 7 pixels, the next digit starts 6 to the right
-constexpr int TEXT_DX = -10, TEXT_DY = -16;               // top-left pixel of the first digit, from the mark's (x, y)
-
-// 5 x 7 digits, rows top to bottom, five bits each, most significant = left column; row r sits in bits [30 - 5r, 34 - 5r]
-#define YSMR_GLYPH(a, b, c, d, e, f, g)                                                                                     \
-    (((uint64_t)0b##a << 30) | ((uint64_t)0b##b << 25) | ((uint64_t)0b##c << 20) | ((uint64_t)0b##d << 15) |                \
-     ((uint64_t)0b##e << 10) | ((uint64_t)0b##f << 5) | (uint64_t)0b##g)
-__constant__ uint64_t c_glyph[10] = {
-    YSMR_GLYPH(01110, 10001, 10011, 10101, 11001, 10001, 01110), YSMR_GLYPH(00100, 01100, 00100, 00100, 00100, 00100, 01110),
-    YSMR_GLYPH(01110, 10001, 00001, 00010, 00100, 01000, 11111), YSMR_GLYPH(11111, 00010, 00100, 00010, 00001, 10001, 01110),
-    YSMR_GLYPH(00010, 00110, 01010, 10010, 11111, 00010, 00010), YSMR_GLYPH(11111, 10000, 11110, 00001, 00001, 10001, 01110),
-    YSMR_GLYPH(00110, 01000, 10000, 11110, 10001, 10001, 01110), YSMR_GLYPH(11111, 00001, 00010, 00100, 01000, 01000, 01000),
-    YSMR_GLYPH(01110, 10001, 10001, 01110, 10001, 10001, 01110), YSMR_GLYPH(01110, 10001, 10001, 01111, 00001, 00010, 01100)};
-#undef YSMR_GLYPH
-
 __device__ __forceinline__ uint4 ld16(const uint8_t *p) { uint4 v; __builtin_memcpy(&v, p, 16); return v; }
 __device__ __forceinline__ void st16(uint8_t *p, const uint4 &v) { __builtin_memcpy(p, &v, 16); }
 
@@ -73,43 +61,12 @@ __global__ __launch_bounds__(256) void k_pack_dib(const uint8_t *__restrict__ fr
     }
 }
 
-// What the painter needs to know of a mark: where its digits are and which, and how large its dot is.
-struct Mark {
-    long long x, y;       // 64 bits: a coordinate anywhere in int32 stays exact through the offsets below
-    uint64_t digits;      // four bits per decimal digit of the id, the leading one in bits [0, 4)
-    int nd, big;          // number of digits (1 .. 10); dot of radius 1 (style 2)
-};
-
-__device__ __forceinline__ Mark mark_of(const ysmr_mark &m)
-{
-    Mark r;
-    r.x = m.x; r.y = m.y; r.big = m.style == 2u;
-    uint32_t v = m.track_id;
-    r.digits = 0; r.nd = 0;
-    do { r.digits = (r.digits << 4) | (v % 10u); v /= 10u; ++r.nd; } while (v);      // least significant digit in last
-    return r;
-}
-
-// Does `m` paint the pixel (px, py)?  Digit k, row r, column c lands on (x - 10 + 6k + c, y - 16 + r); the dot is (x, y),
-// for the larger one also its four edge neighbours.
-__device__ __forceinline__ bool covers(const Mark &m, long long px, long long py)
-{
-    const long long ax = px > m.x ? px - m.x : m.x - px, ay = py > m.y ? py - m.y : m.y - py;
-    if (ax + ay <= (long long)m.big) return true;
-    const long long dx = px - (m.x + TEXT_DX), dy = py - (m.y + TEXT_DY);
-    if (dx < 0 || dy < 0 || dy >= GLYPH_H || dx >= (long long)GLYPH_STEP * m.nd) return false;
-    const int k = (int)dx / GLYPH_STEP, c = (int)dx - k * GLYPH_STEP;
-    if (c >= GLYPH_W) return false;
-    const uint64_t g = c_glyph[(m.digits >> (4 * k)) & 15u];
-    return (g >> (34 - (GLYPH_W * (int)dy + c))) & 1u;
-}
-
 // A WAVE paints one mark at a time; its pixels -- 35 cells per digit, then the dot's one or five -- are dealt to the lanes
 // 64 at a time (six rounds at most: ten digits and a large dot are 355).  A lane keeps one bit per round: "this pixel is
 // mine, inside the frame, and still visible".  The later marks of the frame are then read 64 at a time, a lane each, and
 // tested box against box; the few whose boxes meet this mark's are gone through one by one, every lane clearing the bits of
 // the pixels that mark paints.  What is left is stored.
-constexpr int MAX_ROUNDS = (10 * GLYPH_W * GLYPH_H + 5 + 63) / 64;
+constexpr int MAX_ROUNDS = (MAX_PIXELS + 63) / 64;
 
 __global__ __launch_bounds__(256) void k_paint_marks(const ysmr_mark *__restrict__ marks, const long long *__restrict__ first,
                                                      int n, int H, int W, int bottom_up, uint8_t *__restrict__ out, int out_stride,
@@ -129,27 +86,14 @@ __global__ __launch_bounds__(256) void k_paint_marks(const ysmr_mark *__restrict
         const long long frame_end = std::min(first[f + 1], end);
         const ysmr_mark raw = marks[item];
         const Mark me = mark_of(raw);
-        const int cells = me.nd * GLYPH_W * GLYPH_H, total = cells + (me.big ? 5 : 1);
 
         // my pixels
         long long px[MAX_ROUNDS], py[MAX_ROUNDS];
         uint32_t alive = 0;
 #pragma unroll
         for (int r = 0; r < MAX_ROUNDS; ++r) {
-            const int p = r * 64 + lane;
-            bool on = false;
             px[r] = py[r] = -1;
-            if (p < cells) {
-                const int k = p / (GLYPH_W * GLYPH_H), q = p - k * (GLYPH_W * GLYPH_H), row = q / GLYPH_W, c = q - row * GLYPH_W;
-                px[r] = me.x + TEXT_DX + GLYPH_STEP * k + c;
-                py[r] = me.y + TEXT_DY + row;
-                on = (c_glyph[(me.digits >> (4 * k)) & 15u] >> (34 - q)) & 1u;
-            } else if (p < total) {
-                const int d = p - cells;                                   // 0: the centre; 1 .. 4: left, right, up, down
-                px[r] = me.x + (d == 1 ? -1 : d == 2 ? 1 : 0);
-                py[r] = me.y + (d == 3 ? -1 : d == 4 ? 1 : 0);
-                on = true;
-            }
+            const bool on = mark_cell(me, r * 64 + lane, px[r], py[r]);
             if (on && px[r] >= 0 && px[r] < W && py[r] >= 0 && py[r] < H) alive |= 1u << r;
         }
 

@@ -6,10 +6,8 @@
 // of random boxes with the set-based model, and a row of two runs would count the gap between them) -- so a lane takes a
 // scanline, works [lo, hi] out in registers and adds the gray bytes under it.
 //
-//   * an edge's pixels on row y in closed form instead of by walking the line: the LineIterator's error term after i major
-//     steps is ((d_major - 2 d_minor i) mod 2 d_major) - 2 d_minor, hence its minor steps so far are
-//     floor((2 d_minor i + d_major - 1) / (2 d_major)); inverted, that gives the x-run of an x-major line on a row and
-//     the one pixel of a y-major line;
+//   * an edge's pixels on row y in closed form instead of by walking the line (quad.h, which also holds the corner
+//     arithmetic: the detection view's outlines, view.hip, are the same lines);
 //   * a group of 16 lanes (a DPP row) per detection, a lane per scanline, larger boxes strided; the two integer sums
 //     are reduced inside the row by four DPP steps; lane 0 of the group writes the results.  No atomics, no LDS;
 //   * gray bytes as aligned dwords with the ends masked off, added with v_sad_u8; BGR pixels are converted with the
@@ -20,6 +18,7 @@
 // suite compares it with the model where no GPU is present.  (cos / sin are the host's libm there and the device's here;
 // both are rounded to float32, so a corner differs only if the double sits within an ulp of a rounding boundary.)
 #include "common.h"
+#include "quad.h"
 #include <cmath>
 #include <cstring>
 
@@ -29,67 +28,6 @@ constexpr int LUM_THREADS = 256;
 constexpr int LUM_GROUP = 16;                        // lanes per detection: one DPP row
 constexpr int LUM_GROUPS = LUM_THREADS / LUM_GROUP;
 constexpr int LUM_MAX_BLOCKS = 1024;                 // 4 workgroups per compute unit
-constexpr float LUM_CLAMP = 1048576.0f;              // corners beyond +-2^20 are moved there (no frame is that large)
-
-struct LumEdge {
-    // the edge as LineIterator(leftToRight) walks it ...
-    int x0, y0, dx, ady, sy;
-    // ... and as the scanline fill's edge table holds it (horizontal edges: yt == yb, never active)
-    int yt, yb;
-    long long xt16, dxs;
-};
-
-struct LumBox { int px[4], py[4]; LumEdge e[4]; int ymin, ymax; };
-
-// floor(num / den) for 0 <= num < 2^52, 0 < den < 2^31: a float64 quotient is off by at most one
-__host__ __device__ __forceinline__ long long lum_floor_div(long long num, long long den)
-{
-    long long q = (long long)((double)num / (double)den);
-    if (q * den > num) --q;
-    else if ((q + 1) * den <= num) ++q;
-    return q;
-}
-
-__host__ __device__ __forceinline__ int lum_trunc(float v)
-{
-    return (int)fminf(fmaxf(v, -LUM_CLAMP), LUM_CLAMP);     // (a NaN ends at -2^20)
-}
-
-// np.intp(cv2.boxPoints(rect)) and the tables of its four edges.  c / s: cos and sin of the angle, already float32.
-__host__ __device__ __forceinline__ void lum_box(float cx, float cy, float w, float h, float c, float s, LumBox &B)
-{
-    const float b = c * 0.5f, a = s * 0.5f;
-    const float p0x = cx - a * h - b * w, p0y = cy + b * h - a * w;
-    const float p1x = cx + a * h - b * w, p1y = cy - b * h - a * w;
-    B.px[0] = lum_trunc(p0x); B.py[0] = lum_trunc(p0y);
-    B.px[1] = lum_trunc(p1x); B.py[1] = lum_trunc(p1y);
-    B.px[2] = lum_trunc(2.0f * cx - p0x); B.py[2] = lum_trunc(2.0f * cy - p0y);
-    B.px[3] = lum_trunc(2.0f * cx - p1x); B.py[3] = lum_trunc(2.0f * cy - p1y);
-    B.ymin = min(min(B.py[0], B.py[1]), min(B.py[2], B.py[3]));
-    B.ymax = max(max(B.py[0], B.py[1]), max(B.py[2], B.py[3]));
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int j = (i + 3) & 3;                      // edge pts[i - 1] -> pts[i]
-        const int ax = B.px[j], ay = B.py[j], bx = B.px[i], by = B.py[i];
-        LumEdge &e = B.e[i];
-        const bool swap = bx < ax;
-        e.x0 = swap ? bx : ax; e.y0 = swap ? by : ay;
-        const int x1 = swap ? ax : bx, y1 = swap ? ay : by;
-        e.dx = x1 - e.x0;
-        e.sy = y1 >= e.y0 ? 1 : -1;
-        e.ady = (y1 - e.y0) * e.sy;
-        const bool down = ay < by;
-        e.yt = down ? ay : by; e.yb = down ? by : ay;
-        const int xt = down ? ax : bx, xb = down ? bx : ax;
-        e.xt16 = (long long)xt << 16;
-        e.dxs = 0;
-        if (e.yb > e.yt) {                              // C division truncates toward zero
-            const long long d = ((long long)xb - xt) << 16;
-            const long long q = lum_floor_div(d < 0 ? -d : d, e.yb - e.yt);
-            e.dxs = d < 0 ? -q : q;
-        }
-    }
-}
 
 // The filled pixels of row y, clipped to [0, W): false when there are none.
 __host__ __device__ __forceinline__ bool lum_row(const LumBox &B, int y, int W, int &lo_out, int &hi_out)
@@ -104,20 +42,8 @@ __host__ __device__ __forceinline__ bool lum_row(const LumBox &B, int y, int W, 
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const LumEdge &e = B.e[i];
-        const int k = (y - e.y0) * e.sy;
-        if (k >= 0 && k <= e.ady) {
-            if (e.ady > e.dx) {                         // y-major: one pixel per row
-                const int x = e.x0 + (int)lum_floor_div(2ll * e.dx * k + e.ady - 1, 2ll * e.ady);
-                take(x, x);
-            } else if (e.ady == 0) {
-                take(e.x0, e.x0 + e.dx);
-            } else {                                    // x-major: the major steps whose minor count is k
-                const long long num = 2ll * e.dx * k - e.dx + 2ll * e.ady;
-                const int i_lo = num < 0 ? 0 : (int)lum_floor_div(num, 2ll * e.ady);
-                const int i_hi = (int)min((long long)e.dx, lum_floor_div(2ll * e.dx * k + e.dx, 2ll * e.ady));
-                take(e.x0 + i_lo, e.x0 + i_hi);
-            }
-        }
+        int a, b;
+        if (lum_edge_row(e, y, a, b)) take(a, b);
         if (y >= e.yt && y < e.yb) {
             const long long x = e.xt16 + (long long)(y - e.yt) * e.dxs;
             if (i == 0) c0 = x;
@@ -184,8 +110,6 @@ __host__ __device__ __forceinline__ double lum_value(uint32_t sum, uint32_t coun
     const double mean = count ? (double)sum * (1.0 / (double)count) : 0.0;
     return mean / 100.0;
 }
-
-__host__ __device__ __forceinline__ double lum_radians(float angle) { return (double)angle * 3.14159265358979323846 / 180.0; }
 
 __device__ __forceinline__ uint32_t row_total(uint32_t v)   // the sum over a DPP row, in every lane of it
 {

@@ -79,6 +79,10 @@ TRACKING_INI = {
     "TEST SETTINGS": [("debugging", False), ("path to test video", "Q:/test_video.avi")],
 }
 
+#: optional keys of the HIP path that a tracking.ini may carry in [ADVANCED VIDEO SETTINGS] (absent: not in the settings dict,
+#: and every reader's default holds) -> how the value is read
+OPTIONAL_HIP_KEYS = {"hip save detection video": "getboolean"}
+
 _LOG_LEVELS = {"debug": logging.DEBUG, "info": logging.INFO, "warning": logging.WARNING,
                "critical": logging.CRITICAL}
 
@@ -212,6 +216,9 @@ def _build_settings(parser, ini_path):
         "tracking_ini_filepath": ini_path,
         "perc_motile_warning": warn,
     })
+    for key, getter in OPTIONAL_HIP_KEYS.items():
+        if vid.get(key) is not None:
+            s[key] = getattr(vid, getter)(key)
     assert s["minimum horizon size"] >= 0, "'minimum horizon size' less than 0"
     assert s["number of LSFFs"] > 1, "'number of LSFFs' less than 2"
     assert s["frames per second"] > 0, "'frames per second' zero or negative"

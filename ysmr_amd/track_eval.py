@@ -34,7 +34,7 @@ from .helper_file import (COLOR_BGR2GRAY, RowStream, create_results_folder, get_
                           rows_to_dataframe, save_list, wait_for_removals)
 from .tracker import DeviceTracker, rows_to_numpy, sort_rows
 
-__all__ = ["track_bacteria", "TrackingPipeline", "select_tracks", "evaluate_tracks", "annotate_video"]
+__all__ = ["track_bacteria", "TrackingPipeline", "select_tracks", "evaluate_tracks", "annotate_video", "detection_video_path"]
 
 #: where the wall time of the last _device_pass went, in seconds since it began (diagnostics: scripts/e2e_profile.py)
 LAST_PASS_MARKS = {}
@@ -339,6 +339,11 @@ def track_bacteria(video_path, settings=None, result_folder=None, batch=None, ma
     (``ysmr_mjpeg_decode_batch``); 'always': one without restart markers too -- what cameras, ffmpeg, OpenCV and Pillow write
     -- by ``ysmr_mjpeg_decode_batch_sync``, which gives such a frame a lane per 64 bytes of its entropy data instead of one in
     all; False: by Pillow on the reader threads (``frames.decode_mjpeg_setting``).
+    'hip save detection video' (default False): what upstream's window "... unfiltered possible detections" shows ('display video
+    analysis', refused here) goes into ``detection_video_path(...)`` during the pass -- every frame with the boxes of its
+    detections in blue and the ids and centroids of the live tracks in green (``ysmr_view_*``, csrc/view.hip); container and
+    codec as ``annotate_video`` chooses them, from the same settings.  The table, the csv and the return value do not change;
+    the batch is at most what ``annotate.py`` allows a pinned buffer (and the JPEG encoder's workspace) to hold.
     """
     logger = logging.getLogger("ysmr").getChild(__name__)
     settings = get_configs(settings)
@@ -363,6 +368,13 @@ def track_bacteria(video_path, settings=None, result_folder=None, batch=None, ma
     if settings["color filter"] != COLOR_BGR2GRAY:
         logger.critical("Only 'color filter = COLOR_BGR2GRAY' is supported by the HIP path")
         return None
+    if settings.get("hip save detection video"):
+        try:      # (what 'save video file extension' / 'save video fourcc codec' / 'hip video jpeg ...' ask for, as annotate_video)
+            from .annotate import output_format
+            output_format(settings)
+        except ValueError as exc:
+            logger.critical(str(exc))
+            return None
     try:
         video = open_video(video_path, default_fps=settings["frames per second"])
     except (OSError, ValueError) as exc:
@@ -400,9 +412,13 @@ def track_bacteria(video_path, settings=None, result_folder=None, batch=None, ma
         batch = int(batch or settings.get("hip frames per batch") or auto_batch(frame_height, frame_width, video.channels))
         max_det = int(max_det or settings.get("hip max detections per frame") or DEFAULT_MAX_DET)
         capacity = int(capacity or settings.get("hip max tracks") or DEFAULT_CAPACITY)
+        if settings.get("hip save detection video"):
+            # (a batch of the view waits in a device buffer and leaves through a pinned one: annotate.py's limits on both)
+            batch = min(batch, _view_batch_limit(frame_height, frame_width, frame_count, settings))
         while True:
             outcome = _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_det, capacity, device,
-                                   settings, logger, list_name if settings.get("hip persist rows") else None)
+                                   settings, logger, list_name if settings.get("hip persist rows") else None,
+                                   detection_video_path(video_path, result_folder, settings))
             if outcome[0] == "overflow" and 2 * max(max_det, capacity) <= LIMIT_MAX:
                 max_det, capacity = 2 * max_det, max(2 * capacity, max_det)
                 logger.warning("More objects than the device buffers hold in file {}: running it again with "
@@ -559,8 +575,146 @@ def _persist_chunk(list_name, rows, first):
         fh.write(rows_to_csv_bytes(rows, header=first, via_pandas=False))
 
 
+def detection_video_path(video_path, result_folder, settings=None):
+    """Where ``track_bacteria`` writes the detection view of ``video_path`` when the optional settings key 'hip save detection
+    video' is on: ``<name>_detections_output.avi`` in the result folder (always an ``.avi``, uncompressed or Motion-JPEG, as
+    ``annotate_video``'s file is)."""
+    return os.path.join(result_folder, "{}_detections_output.avi".format(os.path.splitext(os.path.basename(video_path))[0]))
+
+
+def _view_batch_limit(height, width, frame_count, settings):
+    """The most frames per batch with the detection view on: what keeps one of its pinned buffers, and in Motion-JPEG mode
+    the encoder's workspace, inside ``annotate.py``'s limits."""
+    from . import annotate
+    fmt, _, _ = annotate.output_format(settings)
+    limit = annotate.auto_batch(((3 * width + 3) & ~3) * height + 8, max(frame_count, 1 << 30))
+    if fmt == "mjpeg":
+        limit = min(limit, annotate.DibOutput.mjpeg_batch_limit(height, width, annotate.jpeg_mode(settings)))
+    return max(1, limit)
+
+
+class _DetectionView:
+    """'hip save detection video': the frames of ``_device_pass`` with every detection's box and every live track's id painted
+    in (``ysmr_view_boxes_batch`` / ``ysmr_view_tracks_batch``, csrc/view.hip), written to ``detection_video_path`` during the
+    one pass over the video.  The link runs a batch behind detection and a batch's frames are freed once detected, so a
+    batch is packed into one of the two slots of an ``annotate.DibOutput`` right behind its detection, on the side stream,
+    waits there for its link, gets its tracks on the link stream and leaves through the copy stream and the writer thread.
+    Nothing here touches the detections or the rows.  Whatever goes wrong with the FILE (disk full, a write error) ends the
+    view with a critical message and removes the partial file; tracking goes on."""
+
+    def __init__(self, pipe, video, path, fps, settings, result_folder, frame_count, logger):
+        from . import annotate
+        self.pipe, self.path, self.logger, self.device = pipe, path, logger, pipe.device     # (device: what _on_own_device makes current)
+        self.H, self.W, self.C = video.height, video.width, video.channels
+        self.sink = self.writer = None
+        self.dead = False
+        fmt, quality, warning = annotate.output_format(settings)
+        if warning:
+            logger.warning("{}: {}".format(warning, path))
+        try:
+            os.makedirs(result_folder, exist_ok=True)
+            if fmt == "mjpeg":
+                mode = annotate.jpeg_mode(settings)
+                self.writer = annotate.MjpegAviWriter(path, self.W, self.H, fps)
+            else:
+                mode = None
+                if not annotate.enough_space(result_folder, annotate.AviWriter.file_bytes(self.W, self.H, frame_count), "detection video", logger):
+                    self.dead = True
+                    return
+                self.writer = annotate.AviWriter(path, self.W, self.H, fps)
+        except OSError as exc:         # (the file cannot be opened: no view, and tracking goes on)
+            self._give_up(exc)
+            return
+        try:
+            self.sink = annotate.DibOutput(self.writer, pipe.B, self.H, self.W, pipe.device, quality=quality, mode=mode,
+                                           result_folder=result_folder, logger=logger, dib_slots=2)
+            self.counters = torch.zeros(2, dtype=torch.int64, device=pipe.device)     # the row counter before / after a batch's link
+        except BaseException:      # (nobody holds this object yet: the file just opened goes with it)
+            self.abort()
+            raise
+        self.row_capacity = pipe.rows.numel() // _lib.ROW_DTYPE.itemsize
+        self.L = _lib.lib()
+
+    def _give_up(self, why):
+        self.logger.critical("Detection video {} is not written: {}".format(self.path, why))
+        self.abort()
+
+    @_on_own_device
+    def pack(self, frames_dev, res):
+        """Behind ``detect_async`` of a batch: its frames and boxes into a free slot, on the side stream.  -> (what ``tracks``
+        needs, the event behind which the frames are free)."""
+        if self.dead:
+            return None, None
+        try:
+            k = self.sink.acquire()
+        except OSError as exc:
+            self._give_up(exc)
+            return None, None
+        ptr, pitch = self.sink.frames(k)
+        side = self.pipe.side
+        with torch.cuda.stream(side):
+            _lib.check(self.L.ysmr_view_boxes_batch(
+                side.cuda_stream, frames_dev.data_ptr(), int(frames_dev.shape[0]), self.H, self.W, self.C, res.det.data_ptr(),
+                res.det_count.data_ptr(), self.pipe.det[0].max_det, ptr, self.writer.stride, pitch, int(self.writer.bottom_up)),
+                "ysmr_view_boxes_batch")
+            packed = torch.cuda.Event()
+            packed.record(side)
+        return (k, packed), packed
+
+    @_on_own_device
+    def before_link(self):
+        if not self.dead:
+            self.counters[0:1].copy_(self.pipe.row_count, non_blocking=True)
+
+    @_on_own_device
+    def tracks(self, held, first_frame, n):
+        """Behind ``pipe.link`` of the batch, on the link stream: the rows it emitted into the packed frames, and out."""
+        if self.dead or held is None:
+            return
+        k, packed = held
+        cur = torch.cuda.current_stream(self.device)
+        self.counters[1:2].copy_(self.pipe.row_count, non_blocking=True)
+        cur.wait_event(packed)
+        ptr, pitch = self.sink.frames(k)
+        _lib.check(self.L.ysmr_view_tracks_batch(
+            cur.cuda_stream, self.pipe.rows.data_ptr(), self.row_capacity, self.counters.data_ptr(), self.counters.data_ptr() + 8,
+            int(first_frame), int(n), self.H, self.W, ptr, self.writer.stride, pitch, int(self.writer.bottom_up)),
+            "ysmr_view_tracks_batch")
+        painted = torch.cuda.Event()
+        painted.record(cur)
+        try:
+            if not self.sink.submit(k, int(n), int(first_frame), cur, painted):
+                self._give_up("not enough free space, {} bytes needed, {} free".format(*self.sink.shortfall))
+        except OSError as exc:
+            self._give_up(exc)
+
+    @_on_own_device
+    def finish(self):
+        """Everything linked has been painted and handed over: close the file.  -> its path, or None."""
+        if self.dead:
+            return None
+        self.sink.close()
+        if self.sink.failure:
+            self._give_up(self.sink.failure[0])
+            return None
+        self.writer.close()
+        self.dead = True
+        return self.path
+
+    @_on_own_device
+    def abort(self):
+        """Stop, and remove what there is of the file."""
+        if self.sink is not None:
+            self.sink.close()
+            self.sink = None
+        if self.writer is not None:
+            self.writer.abort()
+            self.writer = None
+        self.dead = True
+
+
 def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_det, capacity, device, settings,
-                 logger, persist_to=None):
+                 logger, persist_to=None, view_path=None):
     """The frame loop of one attempt.  Returns (verdict, sorted rows or None, frames done, error flag,
     start time, time when the last frame was linked); verdict 'overflow' asks for larger buffers."""
     frame_height, frame_width = video.height, video.width
@@ -571,6 +725,7 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
     verdict = "done"
     froze = False
     drain = None
+    view = None
     t_start = t_frames = time.perf_counter()
     try:
         # Rows stay on the device for the whole video when they fit (capacity rows per frame is the
@@ -585,6 +740,8 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
                                 capacity=capacity, device=device, rows_per_flush=row_budget)
         LAST_PIPELINE_FACTS.clear()
         LAST_PIPELINE_FACTS.update(capacity=int(capacity), max_det=int(max_det), batched=bool(pipe.trk.batched), fused=bool(pipe.trk.fused))
+        if settings.get("hip save detection video"):
+            view = _DetectionView(pipe, video, view_path, fps_of_file, settings, os.path.dirname(view_path), frame_count, logger)
         chunks = []
         pending = None
         res = None
@@ -611,9 +768,11 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
         for dev, f0, n_read, feed_slot in feed:
             LAST_PASS_MARKS.setdefault("first batch on the device", time.perf_counter() - t_start)
             nxt = (pipe.detect_async(dev), f0, n_read)
-            feed.release(feed_slot, nxt[0][2])   # the batch's frames are free once its detection has run
+            held, packed = view.pack(dev, nxt[0][1]) if view is not None else (None, None)
+            nxt += (held,)
+            feed.release(feed_slot, nxt[0][2] if packed is None else packed)   # the batch's frames are free once its detection has run (and the view has them)
             if pending is not None:
-                (slot, r, ready), p0, cnt = pending
+                (slot, r, ready), p0, cnt, held = pending
                 if rows_upper + cnt * pipe.capacity > row_capacity:
                     if res is not None:
                         pipe.check(res)
@@ -626,9 +785,13 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
                         if persist_to:
                             _persist_chunk(persist_to, chunks[-1], len(chunks) == 1)
                     rows_upper = 0
+                if view is not None:
+                    view.before_link()
                 res = pipe.link(slot, r, ready, p0)
                 if drain is not None:
                     drain.submit(_linked_event(pipe.device))
+                if view is not None:
+                    view.tracks(held, p0, cnt)
                 rows_upper += cnt * pipe.capacity
                 frames_done = p0 + cnt
                 if not checked_early:           # a video too dense for the buffers is found out after its
@@ -636,7 +799,7 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
                     checked_early = True
             pending = nxt
         if pending is not None:
-            (slot, r, ready), p0, cnt = pending
+            (slot, r, ready), p0, cnt, held = pending
             if rows_upper + cnt * pipe.capacity > row_capacity:
                 if res is not None:
                     pipe.check(res)
@@ -648,9 +811,13 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
                     chunks.append(pipe.take_rows())
                     if persist_to:
                         _persist_chunk(persist_to, chunks[-1], len(chunks) == 1)
+            if view is not None:
+                view.before_link()
             res = pipe.link(slot, r, ready, p0)
             if drain is not None:
                 drain.submit(_linked_event(pipe.device))
+            if view is not None:
+                view.tracks(held, p0, cnt)     # (the last, partial batch)
             frames_done = p0 + cnt
         LAST_PASS_MARKS["last batch issued"] = time.perf_counter() - t_start
         if froze:
@@ -661,6 +828,11 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
             t_frames = time.perf_counter()
             LAST_PASS_MARKS["last batch linked"] = t_frames - t_start
             pipe.check(res)
+            if view is not None:
+                written = view.finish()
+                view = None
+                if written:
+                    logger.info("Detection video: {}".format(written))
             if drain is not None:
                 sorted_rows = drain.finish()       # (a RowStream: _finish orders and writes it)
                 drain = None
@@ -693,6 +865,8 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
             feed.close()
         if drain is not None:       # (an attempt that ended early: its rows go nowhere)
             drain.abort()
+        if view is not None:        # (... and its detection video is removed, as a failed csv is)
+            view.abort()
     return verdict, sorted_rows, frames_done, error_during_read, t_start, t_frames
 
 
