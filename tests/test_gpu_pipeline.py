@@ -635,6 +635,99 @@ def test_rows_can_be_persisted_while_the_video_runs(tmp_path, monkeypatch):
     assert open(whole[4], "rb").read() == open(kept[4], "rb").read()
 
 
+#: the four ways a video's rows leave the device (settings keys on top of ``_settings()``)
+ROW_SINKS = {"default": {}, "host print": {"hip print rows on device": False}, "persist": {"hip persist rows": True},
+             "stream": {"hip stream rows": True}}
+
+
+@pytest.fixture(scope="module")
+def sink_clip(tmp_path_factory):
+    """The 90-frame clip of the two tests above as a file, and its table and csv with ample buffers and the default sink."""
+    from ysmr_amd.synth import SyntheticVideo
+    from ysmr_amd.track_eval import track_bacteria
+    folder = tmp_path_factory.mktemp("sinks")
+    path = str(folder / "v.npy")
+    np.save(path, SyntheticVideo(120, 160, 18, seed=12, dropout=0.02).frames(90))
+    os.makedirs(folder / "reference")
+    want = track_bacteria(path, settings=_settings(), result_folder=str(folder / "reference"), batch=16, max_det=64, capacity=64)
+    assert want is not None and len(want[0]) > 1200
+    return path, want[0], open(want[4], "rb").read()
+
+
+@pytest.mark.parametrize("restarts", [False, True], ids=["buffer holds the video", "buffer restarts"])
+@pytest.mark.parametrize("sink", sorted(ROW_SINKS))
+def test_every_row_sink_leaves_the_same_file_and_table(tmp_path, monkeypatch, sink_clip, sink, restarts):
+    """Resident rows printed on the device or on the host, rows appended to the list file, rows streamed -- each with a
+    row buffer that holds the video and with one that is started over in mid-video (2 x 16 x 64 rows against 90 frames of up
+    to 64 rows: the third batch does not fit): the reference run's csv byte for byte and its DataFrame, dtypes included.
+    That the buffer WAS started over is asserted too."""
+    from ysmr_amd import track_eval
+    path, want_df, want_bytes = sink_clip
+    emptied = {"take_rows": [], "persist": 0, "stream": 0}
+    take_rows, persist_chunk, restart_buffer = (track_eval.TrackingPipeline.take_rows, track_eval._persist_chunk,
+                                                track_eval._RowDrain.restart_buffer)
+
+    def spy_take_rows(self, sort=False):
+        emptied["take_rows"].append(sort)
+        return take_rows(self, sort=sort)
+
+    def spy_persist(list_name, rows, first):
+        emptied["persist"] += 1
+        persist_chunk(list_name, rows, first)
+
+    def spy_restart(self):
+        emptied["stream"] += 1
+        restart_buffer(self)
+
+    monkeypatch.setattr(track_eval.TrackingPipeline, "take_rows", spy_take_rows)
+    monkeypatch.setattr(track_eval, "_persist_chunk", spy_persist)
+    monkeypatch.setattr(track_eval._RowDrain, "restart_buffer", spy_restart)
+    keys = dict(ROW_SINKS[sink])
+    if restarts:
+        keys["list save length interval"] = 100
+        if sink != "persist":       # ('hip persist rows' keeps the buffer that small by its own rule)
+            monkeypatch.setattr(track_eval, "ROW_BUDGET_MAX", 1)
+    got = track_eval.track_bacteria(path, settings=_settings(**keys), result_folder=str(tmp_path), batch=16, max_det=64, capacity=64)
+    assert got is not None and got[0].equals(want_df) and list(got[0].dtypes) == list(want_df.dtypes)
+    assert open(got[4], "rb").read() == want_bytes
+    if restarts and sink == "persist":
+        assert emptied["persist"] >= 2
+    elif restarts and sink == "stream":
+        assert emptied["stream"] >= 1
+    elif restarts:      # every full buffer, and at the end what was left: nothing is ordered before all of it is together
+        assert len(emptied["take_rows"]) >= 2 and not any(emptied["take_rows"])
+
+
+def test_an_aborted_attempt_cleans_up_whatever_sink_it_had(tmp_path, caplog, sink_clip):
+    """18 blobs against max_det = capacity = 8: the first batch overflows and the file is run again with doubled limits
+    until it fits.  Whatever the abandoned attempts had -- the default sink, 'hip persist rows', 'hip stream rows', the
+    detection view -- the table, the csv and the number of re-runs are the default sink's from the same limits (and the
+    table that of ample buffers), no drain thread is left, and a detection video exists for the view alone, once."""
+    import logging
+    import threading
+    from ysmr_amd.track_eval import detection_video_path, track_bacteria
+    path, roomy_df, roomy_bytes = sink_clip
+    want = None
+    for name, keys in (("default", {}), ("persist", {"hip persist rows": True}), ("stream", {"hip stream rows": True}),
+                       ("view", {"hip save detection video": True})):
+        out = tmp_path / name
+        out.mkdir()
+        caplog.clear()
+        settings = _settings(**keys)
+        with caplog.at_level(logging.WARNING, logger="ysmr"):
+            got = track_bacteria(path, settings=settings, result_folder=str(out), batch=16, max_det=8, capacity=8)
+        reruns = sum("running it again" in r.getMessage() for r in caplog.records)
+        assert got is not None and reruns >= 1
+        got = (got[0], open(got[4], "rb").read(), reruns)
+        if want is None:
+            want = got
+            assert got[0].equals(roomy_df) and got[1] == roomy_bytes
+        assert got[0].equals(want[0]) and list(got[0].dtypes) == list(want[0].dtypes) and got[1:] == want[1:]
+        assert not any(t.name == "ysmr-row-drain" and t.is_alive() for t in threading.enumerate())
+        video = detection_video_path(path, str(out), settings)
+        assert sorted(os.listdir(out)) == sorted(["v_list.csv"] + ([os.path.basename(video)] if name == "view" else []))
+
+
 from conftest import ROUND  # noqa: E402
 
 

@@ -304,3 +304,16 @@ def on(device):
         import contextlib
         return contextlib.nullcontext()
     return torch.cuda.device(torch.device(device))
+
+
+def on_own_device(method):
+    """Run a method of an object that has a ``device`` (a Detector, a DeviceTracker, a TrackingPipeline and what hangs on one)
+    with that GPU as the current device (the caller's current device is cuda:0 in a fresh worker, whatever GPU its video
+    was dealt to)."""
+    import functools
+
+    @functools.wraps(method)
+    def wrapped(self, *args, **kwargs):
+        with on(self.device):
+            return method(self, *args, **kwargs)
+    return wrapped

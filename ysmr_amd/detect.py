@@ -13,6 +13,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
+from ._lib import on_own_device
 
 __all__ = ["ThresholdParams", "threshold_params", "MeanGrayParams", "mean_gray_params", "MeanGrayState",
            "Detector", "DetectResult"]
@@ -92,17 +93,6 @@ class DetectResult:
     lum: torch.Tensor | None = None   # f64 [B,max_det]  mean gray under each box / 100 (detectors built with luminosity=True)
 
 
-def _on_own_device(method):
-    """Run a Detector method with the detector's GPU as the current device."""
-    import functools
-
-    @functools.wraps(method)
-    def wrapped(self, *args, **kwargs):
-        with _lib.on(self.device):
-            return method(self, *args, **kwargs)
-    return wrapped
-
-
 def _padded(n_bytes, device):
     return torch.empty((n_bytes + 15) // 16 * 16, dtype=torch.uint8, device=device)
 
@@ -168,7 +158,7 @@ class Detector:
         ch = 1 if frames.dim() == 3 else frames.shape[3]
         return b, ch
 
-    @_on_own_device
+    @on_own_device
     def threshold(self, frames: torch.Tensor, variant: int | None = None, timing=None) -> torch.Tensor:
         """a1-a3 only: class map u8 [b,H,W] (bit0 thresh, bit1 markers).  In the mean-gray branch the
         call also advances the moving-average state by these frames; per-frame mean, stddev, level and
@@ -199,7 +189,7 @@ class Detector:
         _lib.check(rc, "ysmr_threshold_batch")
         return self._view(self._cls, b)
 
-    @_on_own_device
+    @on_own_device
     def components(self, batch=None, cls: torch.Tensor | None = None, frames: torch.Tensor | None = None) -> DetectResult:
         """a4-a6 on the class map left by ``threshold`` (or on a caller-supplied u8 [b,H,W] map).  ``frames``: the frames
         the class map was made from, for a detector built with ``luminosity=True`` (else call ``luminosity`` yourself)."""
@@ -217,7 +207,7 @@ class Detector:
             self.luminosity(frames, b)
         return self._result(b)
 
-    @_on_own_device
+    @on_own_device
     def luminosity(self, frames: torch.Tensor, batch=None, sums=None, counts=None, corners=None) -> torch.Tensor:
         """The mean gray value / 100 under the min-area rectangle of every detection the last ``components`` / ``detect``
         call left in ``det`` (``ysmr_luminosity_batch``): f64 [b,max_det], entries past ``det_count`` are not written.
@@ -241,7 +231,7 @@ class Detector:
                             self._view(self._labels, b), self.det_count[:b], self.det[:b], self.anchors[:b],
                             self.status[:b], None if self.lum is None else self.lum[:b])
 
-    @_on_own_device
+    @on_own_device
     def detect(self, frames: torch.Tensor) -> DetectResult:
         """a1-a6 for a batch of frames resident in HBM.  Asynchronous on the current stream."""
         b, ch = self._check_frames(frames)

@@ -20,14 +20,16 @@ from __future__ import annotations
 
 import logging
 import os
-import threading
 import gc
+import itertools
+import threading
 import time
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._lib import on_own_device
 from .detect import Detector, MeanGrayState, mean_gray_params, threshold_params
 from .frames import DeviceFrameFeed, decode_mjpeg_setting, open_video
 from .helper_file import (COLOR_BGR2GRAY, RowStream, create_results_folder, get_configs, get_loggers, rows_to_csv_bytes, rows_to_csv_file, rows_to_csv_file_and_dataframe, rows_device_to_csv_file_and_dataframe,
@@ -58,20 +60,29 @@ def __getattr__(name):   # select_tracks / evaluate_tracks / annotate_video live
     raise AttributeError(name)
 
 
-def _on_own_device(method):
-    """Run a TrackingPipeline method with the pipeline's GPU as the current device (the caller's current
-    device is cuda:0 in a fresh worker, whatever GPU its video was dealt to)."""
-    import functools
+class HostRows:
+    """A video's rows, ordered, in a NumPy array.  Like ``DeviceRows`` and ``RowStream`` a finished table: ``len()``,
+    ``finish(path)`` -> (bytes of csv, DataFrame) with the csv written to ``path``, no file for None, and ``close()``."""
 
-    @functools.wraps(method)
-    def wrapped(self, *args, **kwargs):
-        with _lib.on(self.device):
-            return method(self, *args, **kwargs)
-    return wrapped
+    def __init__(self, rows):
+        self.rows = rows
+
+    def __len__(self):
+        return len(self.rows)
+
+    def finish(self, path=None):
+        # the csv and the DataFrame's columns come out of ONE native pass over the rows (the values the text is printed from are
+        # the values pandas would read back from it: worked out once, by the formatting threads themselves)
+        if path is not None:
+            return rows_to_csv_file_and_dataframe(self.rows, path)
+        return 0, rows_to_dataframe(self.rows)
+
+    def close(self):
+        pass
 
 
 class DeviceRows:
-    """A video's rows, ordered, still on the device (``TrackingPipeline.take_rows_device``)."""
+    """A video's rows, ordered, still on the device (``TrackingPipeline.take_rows_device``): the same finished table."""
 
     def __init__(self, rows_u8, count):
         self.rows_u8, self.count = rows_u8, int(count)
@@ -79,8 +90,15 @@ class DeviceRows:
     def __len__(self):
         return self.count
 
-    def to_numpy(self):
-        return rows_to_numpy(self.rows_u8, self.count)
+    def finish(self, path=None):
+        # Round 5: text and columns come from the device, where the ordered rows are (shortest digits, CPython's layout, pandas'
+        # reading: csrc/fmt.h) -- the host copies them over and writes the file.  A table with a value the device form does not
+        # print (none that a track produces) is brought over and takes the host path.
+        made = rows_device_to_csv_file_and_dataframe(self.rows_u8, self.count, path)
+        return made if made is not None else HostRows(rows_to_numpy(self.rows_u8, self.count)).finish(path)
+
+    def close(self):
+        pass
 
 
 class TrackingPipeline:
@@ -159,7 +177,7 @@ class TrackingPipeline:
         self._ev = [{k: torch.cuda.Event() for k in ("ready", "done", "thresholded")} for _ in range(2)]
         self._k = 0
 
-    @_on_own_device
+    @on_own_device
     def detect_async(self, frames_dev, threshold_events=None, chain_events=None, events=None, frames_ready=None):
         """Issue detection of one batch on the side stream; returns (slot, result, ready_event).
         ``frames_ready``: what the side stream has to wait for before it reads ``frames_dev`` -- None: everything issued
@@ -230,12 +248,12 @@ class TrackingPipeline:
                 e0.record(stream); e1.record(stream)     # (creates them; the dispatch sets them again)
             det.threshold(frames_dev, timing=(e0, e1))
 
-    @_on_own_device
+    @on_own_device
     def reset(self):
         self.trk.reset()
         self.row_count.zero_()
 
-    @_on_own_device
+    @on_own_device
     def link(self, slot, res, ready, first_frame, link_events=None, events=None):
         """Link one detected batch on the current stream; rows accumulate in self.rows.
         ``link_events``: list that receives a (start, stop, frames, host_seconds) record around the batch's
@@ -263,32 +281,34 @@ class TrackingPipeline:
         self._done[slot] = done
         return res
 
-    @_on_own_device
-    def take_rows(self, sort=False):
-        """Synchronise, download the accumulated rows and reset the row buffer.  ``sort``: order them
-        by (TRACK_ID, POSITION_T) on the device first (``sort_list``, helper_file.py:1538-1574)."""
+    def _rows_held(self):
+        """Synchronise: how many rows the buffer holds (more than it has room for: an error)."""
         n = int(self.row_count.item())
         cap = self.rows.numel() // _lib.ROW_DTYPE.itemsize
         if n > cap:
             raise _lib.YsmrLibraryError(f"row buffer overflow: {n} rows > capacity {cap}")
+        return n
+
+    @on_own_device
+    def take_rows(self, sort=False):
+        """Synchronise, download the accumulated rows and reset the row buffer.  ``sort``: order them
+        by (TRACK_ID, POSITION_T) on the device first (``sort_list``, helper_file.py:1538-1574)."""
+        n = self._rows_held()
         rows = rows_to_numpy(sort_rows(self.rows, n) if sort else self.rows, n)   # (a fresh host array)
         self.row_count.zero_()
         return rows
 
-    @_on_own_device
+    @on_own_device
     def take_rows_device(self):
         """Synchronise, order the accumulated rows by (TRACK_ID, POSITION_T) on the device (``sort_list``,
         helper_file.py:1538-1574), LEAVE them there and reset the row buffer: ``DeviceRows`` for ``_finish``, which prints them
         on the device too."""
-        n = int(self.row_count.item())
-        cap = self.rows.numel() // _lib.ROW_DTYPE.itemsize
-        if n > cap:
-            raise _lib.YsmrLibraryError(f"row buffer overflow: {n} rows > capacity {cap}")
+        n = self._rows_held()
         out = DeviceRows(sort_rows(self.rows, n), n)
         self.row_count.zero_()
         return out
 
-    @_on_own_device
+    @on_own_device
     def check(self, res):
         status = int(res.status.max().item())
         _, _, err = self.trk.info()
@@ -461,11 +481,12 @@ class _RowDrain:
     serial): a thread that, batch by batch, waits for the batch's link launch, brings the rows it added to the device buffer
     to the host through pinned memory on a stream of its own, and hands them to a ``RowStream`` (``ysmr_rows_stream_*``),
     whose threads print them while later batches run.  A row's text does not depend on any other row; its place in the file
-    -- by (TRACK_ID, POSITION_T) -- is worked out once, at the end."""
+    -- by (TRACK_ID, POSITION_T) -- is worked out once, at the end.  This is the frame loop's row sink under 'hip stream
+    rows' (the four calls that ``_BufferedRows`` describes)."""
 
-    def __init__(self, pipe, threads=None):
+    def __init__(self, pipe, t_start, threads=None):
         import queue
-        self.pipe = pipe
+        self.pipe, self.t_start = pipe, t_start
         self.rows_cap = pipe.rows.numel() // _lib.ROW_DTYPE.itemsize
         self.stream = RowStream(via_pandas=True, threads=threads or int(os.environ.get("YSMR_STREAM_THREADS", 0)) or max(2, min(12, usable_cpus() // 2)))
         self.copy_stream = torch.cuda.Stream(device=pipe.device)
@@ -477,9 +498,12 @@ class _RowDrain:
         self.thread = threading.Thread(target=self._run, name="ysmr-row-drain", daemon=True)
         self.thread.start()
 
-    def submit(self, linked_event):
-        """``linked_event``: recorded on the link stream behind the batch's launch."""
-        self.q.put(linked_event)
+    def linked(self):
+        """Behind a batch's link launch: an event of its own there (the pipeline's per-slot events are recorded again two
+        batches on) for the thread to wait on."""
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.pipe.device))
+        self.q.put(ev)
 
     def _run(self):
         size = _lib.ROW_DTYPE.itemsize
@@ -510,22 +534,26 @@ class _RowDrain:
                 finally:
                     self.q.task_done()
 
-    def wait_idle(self):
-        """Every batch submitted so far is in the stream (the device buffer may be reused from its start)."""
+    def make_room(self):
+        """Once every batch linked so far is in the stream, the device buffer starts over."""
         self.q.join()
         if self.error is not None:
             raise self.error
+        self.pipe.row_count.zero_()
+        self.restart_buffer()
 
     def restart_buffer(self):
         self.taken = 0
 
     def finish(self):
-        """-> the RowStream holding every row of the video (its threads may still be printing the last batch)."""
+        """-> the RowStream holding every row of the video (its threads may still be printing the last batch): the finished
+        table, which ``_finish`` orders and writes."""
         self.q.put(None)
         self.thread.join()
         if self.error is not None:
             self.stream.close()
             raise self.error
+        LAST_PASS_MARKS["last rows with the stream"] = time.perf_counter() - self.t_start
         return self.stream
 
     def abort(self):
@@ -561,18 +589,45 @@ def _gc_release():
             _GC_OURS = False
 
 
-def _linked_event(device):
-    """An event of its own behind a batch's link launch (the pipeline's per-slot events are recorded again two batches on)."""
-    ev = torch.cuda.Event()
-    ev.record(torch.cuda.current_stream(device))
-    return ev
-
-
 def _persist_chunk(list_name, rows, first):
     """'hip persist rows': the rows of one full device buffer, in the order they were tracked, appended to the list
     file -- what save_list (helper_file.py:1403-1478) does every 'list save length interval' rows."""
     with open(list_name, "wb" if first else "ab") as fh:
         fh.write(rows_to_csv_bytes(rows, header=first, via_pandas=False))
+
+
+class _BufferedRows:
+    """The row sink of ``_device_pass`` unless 'hip stream rows' is on.  A sink is told by the frame loop to ``make_room()``
+    (the next batch might not fit: the device buffer is left empty), that a batch was ``linked()``, and to ``finish()`` -> the
+    video's rows as a finished table (see ``HostRows``), or to ``abort()`` an attempt that ended early.
+    Here the rows stay in the device buffer and are ordered there at the end; a buffer smaller than the video goes to the
+    host whenever it is full -- with ``persist_to`` ('hip persist rows') each such chunk is also appended to that list file,
+    in the order the rows were tracked -- and everything is gathered and ordered in one go."""
+
+    def __init__(self, pipe, persist_to, print_on_device):
+        self.pipe, self.persist_to, self.print_on_device, self.chunks = pipe, persist_to, print_on_device, []
+
+    def make_room(self):
+        self.chunks.append(self.pipe.take_rows())
+        if self.persist_to:
+            _persist_chunk(self.persist_to, self.chunks[-1], len(self.chunks) == 1)
+
+    def linked(self):
+        pass
+
+    def finish(self):
+        pipe = self.pipe
+        if self.chunks:      # did not fit: gather on the host, order on the device in one go
+            self.chunks.append(pipe.take_rows())
+            everything = np.concatenate(self.chunks)
+            on_dev = torch.from_numpy(everything.view(np.uint8)).to(pipe.device)
+            return HostRows(rows_to_numpy(sort_rows(on_dev, len(everything)), len(everything)))
+        if self.print_on_device:
+            return pipe.take_rows_device()      # (printed there too: ysmr_rows_format_device)
+        return HostRows(pipe.take_rows(sort=True))
+
+    def abort(self):      # (an attempt that ended early: its rows go nowhere)
+        pass
 
 
 def detection_video_path(video_path, result_folder, settings=None):
@@ -639,7 +694,7 @@ class _DetectionView:
         self.logger.critical("Detection video {} is not written: {}".format(self.path, why))
         self.abort()
 
-    @_on_own_device
+    @on_own_device
     def pack(self, frames_dev, res):
         """Behind ``detect_async`` of a batch: its frames and boxes into a free slot, on the side stream.  -> (what ``tracks``
         needs, the event behind which the frames are free)."""
@@ -661,12 +716,12 @@ class _DetectionView:
             packed.record(side)
         return (k, packed), packed
 
-    @_on_own_device
+    @on_own_device
     def before_link(self):
         if not self.dead:
             self.counters[0:1].copy_(self.pipe.row_count, non_blocking=True)
 
-    @_on_own_device
+    @on_own_device
     def tracks(self, held, first_frame, n):
         """Behind ``pipe.link`` of the batch, on the link stream: the rows it emitted into the packed frames, and out."""
         if self.dead or held is None:
@@ -688,7 +743,7 @@ class _DetectionView:
         except OSError as exc:
             self._give_up(exc)
 
-    @_on_own_device
+    @on_own_device
     def finish(self):
         """Everything linked has been painted and handed over: close the file.  -> its path, or None."""
         if self.dead:
@@ -701,7 +756,7 @@ class _DetectionView:
         self.dead = True
         return self.path
 
-    @_on_own_device
+    @on_own_device
     def abort(self):
         """Stop, and remove what there is of the file."""
         if self.sink is not None:
@@ -715,8 +770,8 @@ class _DetectionView:
 
 def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_det, capacity, device, settings,
                  logger, persist_to=None, view_path=None):
-    """The frame loop of one attempt.  Returns (verdict, sorted rows or None, frames done, error flag,
-    start time, time when the last frame was linked); verdict 'overflow' asks for larger buffers."""
+    """The frame loop of one attempt.  Returns (verdict, the video's rows -- what its row sink's ``finish`` gave -- or None,
+    frames done, error flag, start time, time when the last frame was linked); verdict 'overflow' asks for larger buffers."""
     frame_height, frame_width = video.height, video.width
     error_during_read = False
     frames_done = 0
@@ -724,7 +779,7 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
     feed = None
     verdict = "done"
     froze = False
-    drain = None
+    sink = None
     view = None
     t_start = t_frames = time.perf_counter()
     try:
@@ -742,7 +797,6 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
         LAST_PIPELINE_FACTS.update(capacity=int(capacity), max_det=int(max_det), batched=bool(pipe.trk.batched), fused=bool(pipe.trk.fused))
         if settings.get("hip save detection video"):
             view = _DetectionView(pipe, video, view_path, fps_of_file, settings, os.path.dirname(view_path), frame_count, logger)
-        chunks = []
         pending = None
         res = None
         checked_early = False
@@ -757,7 +811,10 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
         # ('hip stream rows', default off: measured on a 16-CPU box the overlap LOSES -- 107-154 ms against the serial tail's 98 for a
         # 1920-frame file, profiles/r05_e2e_stream_threads.log: the loop's one host copy per byte of video and the printing of
         # 971 k rows are 0.43 core-seconds each, and side by side they only slow each other down)
-        drain = _RowDrain(pipe) if (persist_to is None and settings.get("hip stream rows", False)) else None
+        if persist_to is None and settings.get("hip stream rows", False):
+            sink = _RowDrain(pipe, t_start)
+        else:
+            sink = _BufferedRows(pipe, persist_to, settings.get("hip print rows on device", True))
         # A full pass of CPython's garbage collector walks every tracked object of the process (~40 ms with torch, numpy
         # and pandas loaded) and would stall the loop that keeps the GPU fed for as long as 50 batches take; what is alive
         # now is moved out of its sight for the duration of the loop (collections of the loop's own garbage stay on).
@@ -765,31 +822,28 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
         # under the other's loop)
         _gc_hold()
         froze = True
-        for dev, f0, n_read, feed_slot in feed:
-            LAST_PASS_MARKS.setdefault("first batch on the device", time.perf_counter() - t_start)
-            nxt = (pipe.detect_async(dev), f0, n_read)
-            held, packed = view.pack(dev, nxt[0][1]) if view is not None else (None, None)
-            nxt += (held,)
-            feed.release(feed_slot, nxt[0][2] if packed is None else packed)   # the batch's frames are free once its detection has run (and the view has them)
+        # the link runs one batch behind detection: every turn issues a batch's detection and links the one before it, and
+        # one more turn behind the feed's last batch (None) links that
+        for fed in itertools.chain(feed, (None,)):
+            nxt = None
+            if fed is not None:
+                dev, f0, n_read, feed_slot = fed
+                LAST_PASS_MARKS.setdefault("first batch on the device", time.perf_counter() - t_start)
+                detected = pipe.detect_async(dev)
+                held, packed = view.pack(dev, detected[1]) if view is not None else (None, None)
+                nxt = (detected, f0, n_read, held)
+                feed.release(feed_slot, detected[2] if packed is None else packed)   # the batch's frames are free once its detection has run (and the view has them)
             if pending is not None:
                 (slot, r, ready), p0, cnt, held = pending
                 if rows_upper + cnt * pipe.capacity > row_capacity:
                     if res is not None:
                         pipe.check(res)
-                    if drain is not None:       # everything linked so far is with the stream: the buffer starts over
-                        drain.wait_idle()
-                        pipe.row_count.zero_()
-                        drain.restart_buffer()
-                    else:
-                        chunks.append(pipe.take_rows())
-                        if persist_to:
-                            _persist_chunk(persist_to, chunks[-1], len(chunks) == 1)
+                    sink.make_room()
                     rows_upper = 0
                 if view is not None:
                     view.before_link()
                 res = pipe.link(slot, r, ready, p0)
-                if drain is not None:
-                    drain.submit(_linked_event(pipe.device))
+                sink.linked()
                 if view is not None:
                     view.tracks(held, p0, cnt)
                 rows_upper += cnt * pipe.capacity
@@ -798,27 +852,6 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
                     pipe.check(res)             # first batch, not after its last (one sync per video)
                     checked_early = True
             pending = nxt
-        if pending is not None:
-            (slot, r, ready), p0, cnt, held = pending
-            if rows_upper + cnt * pipe.capacity > row_capacity:
-                if res is not None:
-                    pipe.check(res)
-                if drain is not None:
-                    drain.wait_idle()
-                    pipe.row_count.zero_()
-                    drain.restart_buffer()
-                else:
-                    chunks.append(pipe.take_rows())
-                    if persist_to:
-                        _persist_chunk(persist_to, chunks[-1], len(chunks) == 1)
-            if view is not None:
-                view.before_link()
-            res = pipe.link(slot, r, ready, p0)
-            if drain is not None:
-                drain.submit(_linked_event(pipe.device))
-            if view is not None:
-                view.tracks(held, p0, cnt)     # (the last, partial batch)
-            frames_done = p0 + cnt
         LAST_PASS_MARKS["last batch issued"] = time.perf_counter() - t_start
         if froze:
             _gc_release()
@@ -833,19 +866,8 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
                 view = None
                 if written:
                     logger.info("Detection video: {}".format(written))
-            if drain is not None:
-                sorted_rows = drain.finish()       # (a RowStream: _finish orders and writes it)
-                drain = None
-                LAST_PASS_MARKS["last rows with the stream"] = time.perf_counter() - t_start
-            elif chunks:      # did not fit: gather on the host, order on the device in one go
-                chunks.append(pipe.take_rows())
-                everything = np.concatenate(chunks)
-                on_dev = torch.from_numpy(everything.view(np.uint8)).to(pipe.device)
-                sorted_rows = rows_to_numpy(sort_rows(on_dev, len(everything)), len(everything))
-            elif settings.get("hip print rows on device", True):
-                sorted_rows = pipe.take_rows_device()      # (_finish prints them there: ysmr_rows_format_device)
-            else:
-                sorted_rows = pipe.take_rows(sort=True)
+            sorted_rows = sink.finish()
+            sink = None
         # the reference reads until cap.read() fails and accepts that only where the container said it would end, or
         # one frame earlier ("some file formats skip one frame", track_eval.py:170-174); anything else -- frames missing
         # OR frames beyond the reported count -- is its read error (:175-178)
@@ -863,8 +885,8 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
             _gc_release()
         if feed is not None:
             feed.close()
-        if drain is not None:       # (an attempt that ended early: its rows go nowhere)
-            drain.abort()
+        if sink is not None:        # (an attempt that ended early: its rows go nowhere)
+            sink.abort()
         if view is not None:        # (... and its detection video is removed, as a failed csv is)
             view.abort()
     return verdict, sorted_rows, frames_done, error_during_read, t_start, t_frames
@@ -881,11 +903,9 @@ def _finish(video_path, settings, logger, sorted_rows, frames_done, frame_count,
             logger.info("Restoring old list: {}".format(list_name))
         except OSError as exc:
             logger.error("Could not restore {}: {!r}".format(list_name, exc.args))
-    stream = sorted_rows if isinstance(sorted_rows, RowStream) else None
-    on_device = sorted_rows if isinstance(sorted_rows, DeviceRows) else None
     if sorted_rows is None or len(sorted_rows) == 0:
-        if stream is not None:
-            stream.close()
+        if sorted_rows is not None:
+            sorted_rows.close()
         logger.warning("Did not track any objects. File: {}".format(video_path))
         return None
     # track_eval.py:387-392 asks the LAST frame's tracker output for its last object id: a video whose final
@@ -896,53 +916,19 @@ def _finish(video_path, settings, logger, sorted_rows, frames_done, frame_count,
     # the csv with pandas, sorts it and rewrites it; the same DataFrame and the same bytes come
     # straight from the rows here (helper_file.rows_to_dataframe / rows_to_csv_bytes).
     t_rows = time.perf_counter()
-    df_for_eval = None
     keep_file = not settings["delete .csv file after analysis"]   # (else analyse() removes the file anyway, main.py:156)
-    if stream is not None:
-        # the rows were printed while the video ran (_RowDrain): what is left is their order, the file, the columns
-        n_rows_total = len(stream)
+    n_rows_total = len(sorted_rows)
+    try:
         try:
-            try:
-                _, df_for_eval = stream.finish(list_name if keep_file else None)
-            except (OSError, _lib.YsmrLibraryError) as exc:
-                if not keep_file:
-                    raise
-                logger.error("Could not write {}: {}".format(list_name, exc))
-                _, df_for_eval = stream.finish(None)
-        finally:
-            stream.close()
-        alive_at_end = df_for_eval["TRACK_ID"].to_numpy()[df_for_eval["POSITION_T"].to_numpy() == frames_done - 1]
-    if on_device is not None:
-        # Round 5: text and columns come from the device, where the ordered rows are (shortest digits, CPython's layout, pandas'
-        # reading: csrc/fmt.h) -- the host copies them over and writes the file.  A table with a value the device form does not
-        # print (none that a track produces) is brought over and takes the host path below.
-        n_rows_total = len(on_device)
-        made = None
-        try:
-            made = rows_device_to_csv_file_and_dataframe(on_device.rows_u8, n_rows_total, list_name if keep_file else None)
-        except OSError as exc:
+            _, df_for_eval = sorted_rows.finish(list_name if keep_file else None)
+        except (OSError, _lib.YsmrLibraryError) as exc:
             if not keep_file:
                 raise
             logger.error("Could not write {}: {}".format(list_name, exc))
-            made = rows_device_to_csv_file_and_dataframe(on_device.rows_u8, n_rows_total, None)
-        if made is None:
-            sorted_rows = on_device.to_numpy()
-            on_device = None
-        else:
-            df_for_eval = made[1]
-            alive_at_end = df_for_eval["TRACK_ID"].to_numpy()[df_for_eval["POSITION_T"].to_numpy() == frames_done - 1]
-    if stream is None and on_device is None:
-        alive_at_end = sorted_rows["track_id"][sorted_rows["frame"] == frames_done - 1]
-        n_rows_total = len(sorted_rows)
-        # the csv and the DataFrame's columns come out of ONE native pass over the rows (the values the text is printed from are
-        # the values pandas would read back from it: worked out once, by the formatting threads themselves)
-        if keep_file:
-            try:
-                _, df_for_eval = rows_to_csv_file_and_dataframe(sorted_rows, list_name)
-            except (OSError, _lib.YsmrLibraryError) as exc:
-                logger.error("Could not write {}: {}".format(list_name, exc))
-        if df_for_eval is None:
-            df_for_eval = rows_to_dataframe(sorted_rows)
+            _, df_for_eval = sorted_rows.finish(None)
+    finally:
+        sorted_rows.close()
+    alive_at_end = df_for_eval["TRACK_ID"].to_numpy()[df_for_eval["POSITION_T"].to_numpy() == frames_done - 1]
     last_id = int(alive_at_end.max()) if len(alive_at_end) else -1
     t_df = time.perf_counter()
     LAST_PASS_MARKS["csv and DataFrame done"] = t_df - t_start

@@ -16,19 +16,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import on_own_device
 
 __all__ = ["sort_rows", "DeviceTracker", "CentroidTracker"]
-
-
-def _on_own_device(method):
-    """Run a DeviceTracker method with the tracker's GPU as the current device."""
-    import functools
-
-    @functools.wraps(method)
-    def wrapped(self, *args, **kwargs):
-        with _lib.on(self.device):
-            return method(self, *args, **kwargs)
-    return wrapped
 
 
 class DeviceTracker:
@@ -72,11 +62,11 @@ class DeviceTracker:
         except Exception:
             pass
 
-    @_on_own_device
+    @on_own_device
     def reset(self):
         _lib.check(_lib.lib().ysmr_tracker_reset(self._handle, _lib.stream_ptr(self.device)), "ysmr_tracker_reset")
 
-    @_on_own_device
+    @on_own_device
     def update(self, det, m=None, m_dev=None, frame=0, rows=None, n_rows=None, claim=None, n_before=None,
                new_cols=None, n_new=None, third=None):
         """One frame.  det: device tensor [m,5] float32 or float64; third: float64 [m], a 3-D handle's third coordinate."""
@@ -97,7 +87,7 @@ class DeviceTracker:
                                             ptr(n_rows), ptr(claim), ptr(n_before), ptr(new_cols), ptr(n_new))
         _lib.check(rc, "ysmr_tracker_update")
 
-    @_on_own_device
+    @on_own_device
     def run(self, det, det_count, first_frame, rows, row_count, third=None):
         """Frames [first_frame, first_frame + B): det f32 [B,max_det,5], det_count i32 [B] on device;
         rows: uint8 buffer viewed as ysmr_row[]; row_count: int64 device scalar (advanced).  third: f64 [B,max_det], the
@@ -120,7 +110,7 @@ class DeviceTracker:
                                          rows.numel() // _lib.ROW_DTYPE.itemsize, row_count.data_ptr())
         _lib.check(rc, "ysmr_tracker_run")
 
-    @_on_own_device
+    @on_own_device
     def prepare(self, det, det_count, slot, third=None):
         """Bin a batch's detections for the ``run`` that follows, on the CURRENT stream (``ysmr_tracker_prepare``: takes
         that launch off the link stream's chain when called on the detection stream).  No-op unless ``batched``.  A 3-D
@@ -158,7 +148,7 @@ class DeviceTracker:
         The track table is carried over."""
         _lib.check(_lib.lib().ysmr_tracker_link_mode(self._handle, int(mode)), "ysmr_tracker_link_mode")
 
-    @_on_own_device
+    @on_own_device
     def info(self):
         """(live tracks, next id, sticky error bits); synchronises."""
         a, b, c = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
@@ -167,7 +157,7 @@ class DeviceTracker:
         _lib.check(rc, "ysmr_tracker_info")
         return a.value, b.value, c.value
 
-    @_on_own_device
+    @on_own_device
     def peek(self):
         """Current (ids, positions (n,2) float64 -- (n,3) of a 3-D handle --, disappeared) in id order; synchronises."""
         ids = torch.empty(self.capacity, dtype=torch.int32, device=self.device)
