@@ -602,6 +602,54 @@ int    ysmr_rows_format_device(void *stream, const ysmr_row *rows_dev, long long
 int    ysmr_rows_format_csv_devicelike(const ysmr_row *rows_host, long long n_rows, int with_header, int via_pandas, char *out,
                                        size_t out_capacity, size_t *out_length, double *columns5, long long *unserved);
 
+/* DEVICE functions (added under ABI 15): the reading direction -- the text of a `*_list.csv` / `*_selected_data.csv` that is in
+ * device memory -> the seven columns helper_file.get_data returns (pandas.read_csv with upstream's dtype and usecols,
+ * helper_file.py:860-905), bit for bit.  csrc/csv_parse.h states what is served: a header line (read by the HOST, which passes
+ * the number of columns and the position of each of TRACK_ID, POSITION_T, POSITION_X, POSITION_Y, WIDTH, HEIGHT, DEGREES_ANGLE
+ * in it), then lines of exactly that many fields; integers of 1 .. 10 digits up to 2^32 - 1; floats
+ * -?digits(.digits)?([eE][+-]?digits)? read as pandas' precise_xstrtod reads them, with a final decimal exponent in
+ * -325 .. 308.  Nothing else is guessed at: it is flagged or counted, and the caller reads the file with pandas.
+ *
+ * ysmr_csv_index: one pass with 16-byte loads (newline bit map, counts by popcount, flags), a prefix sum, one pass that writes
+ * the byte offset of every line start into the workspace.  Asynchronous on `stream`.  text_dev: 16-byte aligned, n_bytes in
+ * 1 .. 2^31 - 257 (bytes behind n_bytes are never read).  *n_lines_dev: the lines of the file, the header and a last line
+ * without '\n' included.  *flags_dev: 1 a '"', 2 a '\r', 4 a NUL or a byte >= 0x80 (get_data's text-mode read of such a file
+ * is the host's business), 8 more lines than a served file of n_bytes can hold -- any of them: not served.
+ * ysmr_csv_workspace_bytes: 0 for what is refused (0 bytes, more than the 32-bit offsets hold, arithmetic that does not fit).
+ *
+ * ysmr_csv_parse: a line per lane, the lines of a workgroup staged into LDS with 16-byte loads; a line that reaches beyond the
+ * staged span (ysmr_csv_geometry) is PARSED FROM GLOBAL MEMORY, it is not counted unserved.  Same text_dev, n_bytes and
+ * workspace as the index call before it; n_rows <= *n_lines_dev - 1 (rows beyond what the index found are counted unserved
+ * and not read).  wanted[7]: the seven positions, distinct, below n_columns (7 .. 4096).  *unserved_dev (zeroed by the call):
+ * rows that are not served; no value of such a row is written.
+ *
+ * ysmr_csv_order: sort_list (helper_file.py:1538-1574) -- the rows ordered by (TRACK_ID, POSITION_T), equal pairs in file
+ * order as DataFrame.sort_values leaves them: a stable radix sort of key and row number, then a gather of the seven columns
+ * into the (distinct) outputs.  Upstream's "rough check" (sort only when rows 0 .. 5 hold pairwise distinct ids) is the
+ * caller's, on six downloaded ids.
+ *
+ * ysmr_csv_geometry: bytes of text per workgroup of the index pass, lines per workgroup of the parse, bytes of a workgroup's
+ * lines held in LDS (counted from the 16-byte boundary at or before its first line).
+ *
+ * ysmr_csv_parse_devicelike: a HOST function, the same arithmetic (csrc/csv_parse.h) a line at a time on text in host memory,
+ * header line included (it is skipped); what the CPU tests compare with pandas.  *n_rows: the lines behind the header (more
+ * than row_capacity: YSMR_ERR_CAPACITY); *unserved and *flags as above. */
+size_t ysmr_csv_workspace_bytes(size_t n_bytes);
+int    ysmr_csv_index(void *stream, const char *text_dev, size_t n_bytes, void *workspace_dev, size_t workspace_bytes,
+                      uint32_t *n_lines_dev, uint32_t *flags_dev);
+int    ysmr_csv_parse(void *stream, const char *text_dev, size_t n_bytes, const void *workspace_dev, size_t workspace_bytes,
+                      int n_columns, const int32_t *wanted, long long n_rows, uint32_t *track_id_dev, uint32_t *t_dev,
+                      double *x_dev, double *y_dev, double *w_dev, double *h_dev, double *angle_dev, uint32_t *unserved_dev);
+size_t ysmr_csv_order_workspace_bytes(long long n_rows);
+int    ysmr_csv_order(void *stream, long long n_rows, const uint32_t *track_id_dev, const uint32_t *t_dev, const double *x_dev,
+                      const double *y_dev, const double *w_dev, const double *h_dev, const double *angle_dev,
+                      void *workspace_dev, size_t workspace_bytes, uint32_t *track_id_out, uint32_t *t_out, double *x_out,
+                      double *y_out, double *w_out, double *h_out, double *angle_out);
+void   ysmr_csv_geometry(int *index_chunk_bytes, int *rows_per_group, int *staged_span_bytes);
+int    ysmr_csv_parse_devicelike(const char *text_host, size_t n_bytes, int n_columns, const int32_t *wanted,
+                                 long long row_capacity, uint32_t *track_id, uint32_t *t, double *x, double *y, double *w,
+                                 double *h, double *angle, long long *n_rows, long long *unserved, uint32_t *flags);
+
 /* HOST functions (ABI 13): the same csv and columns worked out WHILE the video runs.  Rows go in as the link emits them -- any
  * number of ysmr_rows_stream_push calls with host rows in any order; a call copies its rows and returns, the stream's threads
  * format them meanwhile -- and ysmr_rows_stream_finish orders what has been pushed by (TRACK_ID, POSITION_T) (a row's place is

@@ -67,7 +67,9 @@ EXPORTS = ("ysmr_abi_version", "ysmr_last_error", "ysmr_detect_workspace_bytes",
            "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_batch_sync", "ysmr_mjpeg_decode_sync_geometry",
            "ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_png_deflate", "ysmr_plot_stamp",
            "ysmr_png_dynamic_workspace_bytes", "ysmr_png_dynamic_stream_bytes_max", "ysmr_png_deflate_dynamic", "ysmr_png_code_lengths",
-           "ysmr_view_boxes_batch", "ysmr_view_tracks_batch", "ysmr_view_batch_host")
+           "ysmr_view_boxes_batch", "ysmr_view_tracks_batch", "ysmr_view_batch_host",
+           "ysmr_csv_workspace_bytes", "ysmr_csv_index", "ysmr_csv_parse", "ysmr_csv_order_workspace_bytes", "ysmr_csv_order",
+           "ysmr_csv_geometry", "ysmr_csv_parse_devicelike")
 
 #: numpy view of ``ysmr_mark`` (16 bytes): one track position of one frame of the annotated video
 MARK_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("track_id", "<u4"), ("style", "<u4")])
@@ -272,8 +274,19 @@ def lib():
     L.ysmr_view_tracks_batch.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int32, ci, ci, ci, vp, ci, ctypes.c_size_t, ci]
     L.ysmr_view_batch_host.argtypes = [vp, ci, ci, ci, ci, vp, vp, ci, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, vp, ci,
                                        ctypes.c_size_t, ci]
+    L.ysmr_csv_workspace_bytes.argtypes = [ctypes.c_size_t]
+    L.ysmr_csv_workspace_bytes.restype = ctypes.c_size_t
+    L.ysmr_csv_index.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp]
+    L.ysmr_csv_parse.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ci, vp, ll] + [vp] * 7 + [vp]
+    L.ysmr_csv_order_workspace_bytes.argtypes = [ll]
+    L.ysmr_csv_order_workspace_bytes.restype = ctypes.c_size_t
+    L.ysmr_csv_order.argtypes = [vp, ll] + [vp] * 7 + [vp, ctypes.c_size_t] + [vp] * 7
+    L.ysmr_csv_geometry.argtypes = [ctypes.POINTER(ci)] * 3
+    L.ysmr_csv_geometry.restype = None
+    L.ysmr_csv_parse_devicelike.argtypes = [vp, ctypes.c_size_t, ci, vp, ll] + [vp] * 7 + [ctypes.POINTER(ll), ctypes.POINTER(ll),
+                                                                                        ctypes.POINTER(ctypes.c_uint32)]
     for name in EXPORTS:
-        if name not in ("ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_png_dynamic_workspace_bytes", "ysmr_png_dynamic_stream_bytes_max", "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_sync_geometry", "ysmr_mjpeg_decode_workspace_bytes", "ysmr_violin_workspace_bytes", "ysmr_mjpeg_workspace_bytes", "ysmr_mjpeg_encode_workspace_bytes", "ysmr_plot_workspace_bytes", "ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
+        if name not in ("ysmr_csv_workspace_bytes", "ysmr_csv_order_workspace_bytes", "ysmr_csv_geometry", "ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_png_dynamic_workspace_bytes", "ysmr_png_dynamic_stream_bytes_max", "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_sync_geometry", "ysmr_mjpeg_decode_workspace_bytes", "ysmr_violin_workspace_bytes", "ysmr_mjpeg_workspace_bytes", "ysmr_mjpeg_encode_workspace_bytes", "ysmr_plot_workspace_bytes", "ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
                         "ysmr_rows_sort_workspace_bytes", "ysmr_rows_csv_bound", "ysmr_rows_stream_count",
                         "ysmr_mean_threshold_state_bytes"):
             getattr(L, name).restype = ci

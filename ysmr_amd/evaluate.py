@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .helper_file import create_results_folder, get_configs, get_data, save_df_to_csv
+from .helper_file import create_results_folder, get_configs, get_data, read_table_device, save_df_to_csv
 
 __all__ = ["evaluate_tracks", "evaluate_params", "evaluate_columns"]
 
@@ -122,9 +122,10 @@ def evaluate_params(settings, fps) -> _lib.EvaluateParams:
     return p
 
 
-def evaluate_columns(df, params: _lib.EvaluateParams, device="cuda:0"):
+def evaluate_columns(df, params: _lib.EvaluateParams, device="cuda:0", columns_dev=None):
     """Run ``ysmr_evaluate_tracks`` on the table's six input columns.  Returns (dict of per-row arrays,
-    statistics array [tracks, 12])."""
+    statistics array [tracks, 12]).  ``columns_dev``: those six columns where they are on ``device`` already
+    (``DeviceTable.columns_dev`` of ``helper_file.read_table_device``): nothing is uploaded."""
     import torch
     n = len(df)
     L = _lib.lib()
@@ -133,8 +134,11 @@ def evaluate_columns(df, params: _lib.EvaluateParams, device="cuda:0"):
         def up(name, dtype):
             return torch.from_numpy(np.ascontiguousarray(df[name].to_numpy(), dtype=dtype).view(
                 np.int32 if dtype == np.uint32 else dtype)).to(dev)
-        cols = [up("TRACK_ID", np.uint32), up("POSITION_T", np.uint32), up("POSITION_X", np.float64),
-                up("POSITION_Y", np.float64), up("WIDTH", np.float64), up("HEIGHT", np.float64)]
+        cols = columns_dev if columns_dev is not None else [
+            up("TRACK_ID", np.uint32), up("POSITION_T", np.uint32), up("POSITION_X", np.float64),
+            up("POSITION_Y", np.float64), up("WIDTH", np.float64), up("HEIGHT", np.float64)]
+        if len(cols) != 6 or any(c.numel() != n or not c.is_cuda for c in cols):
+            raise ValueError("columns_dev must be the table's six columns on {}".format(dev))
         ws = torch.empty(max(L.ysmr_evaluate_workspace_bytes(n), 256), dtype=torch.uint8, device=dev)
         f64 = lambda: torch.empty(max(n, 1), dtype=torch.float64, device=dev)   # noqa: E731
         i8 = lambda: torch.empty(max(n, 1), dtype=torch.int8, device=dev)       # noqa: E731
@@ -169,8 +173,15 @@ def evaluate_tracks(path_to_file, results_directory=None, df=None, settings=None
     if results_directory is None:
         results_directory = create_results_folder(path_to_file)
     file_name = os.path.splitext(os.path.basename(path_to_file))[0]
+    columns_dev = None
     if not isinstance(df, pd.DataFrame):
-        df = get_data(path_to_file)
+        if settings.get("hip read csv on device"):
+            # text to numbers on the device (csrc/csv.hip); the columns stay there for the statistics
+            table = read_table_device(path_to_file, device)
+            df = None if table is None else table.to_dataframe()
+            columns_dev = None if table is None else table.columns_dev
+        else:
+            df = get_data(path_to_file)
     if df is None:
         logger.critical("Error reading data frame from file {}".format(path_to_file))
         return None
@@ -183,7 +194,9 @@ def evaluate_tracks(path_to_file, results_directory=None, df=None, settings=None
         logger.critical("POSITION_T contains negative values")
         return None
     try:
-        rows, stats = evaluate_columns(table, evaluate_params(settings, fps), device=device)
+        # (the columns that came from the device a moment ago are not uploaded again)
+        extra = {} if columns_dev is None else {"columns_dev": columns_dev}
+        rows, stats = evaluate_columns(table, evaluate_params(settings, fps), device=device, **extra)
     except (_lib.YsmrLibraryError, RuntimeError) as exc:
         logger.critical("Device path failed for file {}: {}".format(path_to_file, exc))
         return None

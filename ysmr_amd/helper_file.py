@@ -18,7 +18,7 @@ from datetime import datetime
 import numpy as np
 
 __all__ = ["create_configs", "get_configs", "default_settings", "reshape_result", "save_list", "sort_list",
-           "get_data", "create_results_folder", "metadata_file", "get_loggers", "COLOR_BGR2GRAY"]
+           "get_data", "read_table_device", "create_results_folder", "metadata_file", "get_loggers", "COLOR_BGR2GRAY"]
 
 COLOR_BGR2GRAY = 6  # value of cv2.COLOR_BGR2GRAY; the only colour filter the HIP path implements
 
@@ -620,9 +620,15 @@ _DTYPES = {"TRACK_ID": np.uint32, "POSITION_T": np.uint32, "POSITION_X": np.floa
            "WIDTH": np.float64, "HEIGHT": np.float64, "DEGREES_ANGLE": np.float64}
 
 
-def get_data(csv_file_path, dtype=None, check_sorted=True):
-    """Load a ``*_list.csv`` into a DataFrame with the reference's dtypes (helper_file.py:881-889)."""
+def get_data(csv_file_path, dtype=None, check_sorted=True, device=None):
+    """Load a ``*_list.csv`` into a DataFrame with the reference's dtypes (helper_file.py:881-889).
+
+    ``device`` (None: pandas on the host, as ever) with the default ``dtype``: the file is read on that GPU
+    (:func:`read_table_device`) -- the same DataFrame, or None, for every file."""
     import pandas as pd
+    if device is not None and dtype is None:
+        table = read_table_device(csv_file_path, device, check_sorted=check_sorted)
+        return None if table is None else table.to_dataframe()
     dtype = _DTYPES if dtype is None else dtype
     try:
         with open(csv_file_path, "r", newline="\n") as fh:
@@ -648,6 +654,196 @@ def sort_list(file_path=None, sort=None, df=None, save_file=False):
     if save_file and file_path is not None:
         df.to_csv(file_path, index=False)
     return df
+
+
+#: (diagnostics) seconds since the call began at which the last read_table_device reached its steps
+LAST_CSV_READ_MARKS = {}
+#: flags of ysmr_csv_index (include/ysmr_hip.h)
+CSV_FLAG_QUOTE, CSV_FLAG_CR, CSV_FLAG_NOT_PLAIN, CSV_FLAG_TOO_MANY_LINES = 1, 2, 4, 8
+
+
+def csv_header_plan(line):
+    """The header line of a table's csv (bytes, without its newline) -> ``(n_columns, positions)``: the position of each of
+    the seven default columns, in the order of ``_DTYPES``.  None for a header the device reader does not serve: a wanted
+    name missing or there twice, bytes that are not ASCII, fewer than 7 or more than 4096 names."""
+    try:
+        names = bytes(line).decode("ascii").split(",")
+    except UnicodeDecodeError:
+        return None
+    if not 7 <= len(names) <= 4096 or any(names.count(k) != 1 for k in _DTYPES):
+        return None
+    return len(names), [names.index(k) for k in _DTYPES]
+
+
+def _frame_of(columns, positions):
+    """The DataFrame of seven host columns (in the order of ``_DTYPES``): pandas keeps the FILE's column order under usecols."""
+    import pandas as pd
+    names = list(_DTYPES)
+    order = sorted(range(7), key=lambda k: positions[k])
+    return pd.DataFrame({names[k]: columns[k] for k in order})
+
+
+def parse_csv_devicelike(data):
+    """``ysmr_csv_parse_devicelike`` on the bytes of a csv: the arithmetic of the device reader (csrc/csv_parse.h) on the host,
+    for the CPU tests.  Returns ``(columns, n_rows, unserved, flags, positions)``; ``columns`` are seven arrays pre-filled
+    with ones' bits (0xFFFFFFFF, a NaN), which a row that is not served leaves as they are.  None: the header is refused."""
+    import ctypes
+    from . import _lib
+    data = bytes(data)
+    end = data.find(b"\n")
+    plan = csv_header_plan(data if end < 0 else data[:end])
+    if plan is None or not data:
+        return None
+    n_columns, positions = plan
+    cap = data.count(b"\n") + 1
+    ids, t = np.full(cap, 0xFFFFFFFF, np.uint32), np.full(cap, 0xFFFFFFFF, np.uint32)
+    cols = [np.full(cap, -1, np.int64).view(np.float64) for _ in range(5)]
+    wanted = np.asarray(positions, np.int32)
+    n, bad, flags = ctypes.c_longlong(0), ctypes.c_longlong(0), ctypes.c_uint32(0)
+    _lib.check(_lib.lib().ysmr_csv_parse_devicelike(data, len(data), n_columns, wanted.ctypes.data, cap, ids.ctypes.data, t.ctypes.data,
+                                                    *[c.ctypes.data for c in cols], ctypes.byref(n), ctypes.byref(bad),
+                                                    ctypes.byref(flags)), "ysmr_csv_parse_devicelike")
+    return [a[:n.value] for a in [ids, t] + cols], n.value, bad.value, flags.value, positions
+
+
+class DeviceTable:
+    """What :func:`read_table_device` returns.  ``path_taken``: 'device' -- the seven columns were parsed (and ordered) on the
+    GPU and are held there (``columns``: name -> tensor, the two uint32 columns as int32 bits; ``columns_dev``: the six that
+    ``select_rows`` / ``evaluate_columns`` take) -- or 'host': the file is not one the device reader serves and the DataFrame
+    is ``get_data``'s.  ``unserved``: rows the parse kernel counted (0 on the device path), ``flags``: of the index pass."""
+
+    def __init__(self, path_taken, n_rows=0, columns=None, positions=None, df=None, unserved=0, flags=0, device=None, buffer=None):
+        self.path_taken, self.n_rows, self.columns, self.unserved, self.flags = path_taken, n_rows, columns, unserved, flags
+        self.device, self._positions, self._df, self._buffer = device, positions, df, buffer
+
+    @property
+    def columns_dev(self):
+        if self.path_taken != "device" or not self.n_rows:
+            return None
+        return [self.columns[k] for k in list(_DTYPES)[:6]]
+
+    def __len__(self):
+        return self.n_rows
+
+    def to_dataframe(self):
+        """The DataFrame ``get_data`` returns for the file: the reference's dtypes, a RangeIndex."""
+        if self._df is not None:
+            return self._df
+        import time
+        import torch
+        t0 = time.perf_counter()
+        n = self.n_rows
+        if n == 0:
+            cols = [np.empty(0, dt) for dt in _DTYPES.values()]
+        else:
+            with torch.cuda.device(self.device):
+                host = _pinned("columns", 48 * n)
+                host.copy_(self._buffer[:48 * n], non_blocking=True)
+                torch.cuda.current_stream(self.device).synchronize()
+            hc = host.numpy()
+            cols = [hc[:4 * n].view(np.uint32), hc[4 * n:8 * n].view(np.uint32)] + list(hc[8 * n:48 * n].view(np.float64).reshape(5, n))
+        LAST_CSV_READ_MARKS["download"] = time.perf_counter() - t0
+        # (the DataFrame copies its columns into its own blocks: the pinned staging is free for the next file)
+        self._df = _frame_of(cols, self._positions)
+        LAST_CSV_READ_MARKS["frame"] = time.perf_counter() - t0
+        return self._df
+
+
+def _split_columns(buf, n):
+    import torch
+    return {"TRACK_ID": buf[:4 * n].view(torch.int32), "POSITION_T": buf[4 * n:8 * n].view(torch.int32),
+            **{name: buf[(8 + 8 * k) * n:(16 + 8 * k) * n].view(torch.float64) for k, name in enumerate(list(_DTYPES)[2:])}}
+
+
+def read_table_device(path, device="cuda:0", check_sorted=True, sync_phases=False):
+    """``get_data`` with the text-to-number work on the GPU: the file goes into a pinned buffer and up to ``device``; there
+    its lines are indexed (``ysmr_csv_index``), parsed a line per lane (``ysmr_csv_parse``) and -- ``check_sorted`` and
+    upstream's rough check on the first six ids -- ordered by (TRACK_ID, POSITION_T) (``ysmr_csv_order``).  Returns a
+    :class:`DeviceTable`; None where ``get_data`` returns None.  A file the device reader does not serve (csrc/csv_parse.h:
+    quotes, carriage returns, empty lines or fields, NaN, a header without the seven names, ...) is read by ``get_data``
+    itself, exceptions and log lines included: ``path_taken == 'host'``.  ``sync_phases``: wait for the device after the
+    upload and the ordering too, so that ``LAST_CSV_READ_MARKS`` tells them apart (scripts/csv_read_e2e.py)."""
+    import ctypes
+    import time
+    import torch
+    from . import _lib
+    t0 = time.perf_counter()
+    marks = LAST_CSV_READ_MARKS
+    marks.clear()
+
+    def host(unserved=0, flags=0):
+        df = get_data(path, check_sorted=check_sorted)
+        return None if df is None else DeviceTable("host", n_rows=len(df), df=df, unserved=unserved, flags=flags)
+
+    L = _lib.lib()
+    dev = torch.device(device)
+    try:
+        with open(path, "rb", buffering=0) as fh:
+            size = os.fstat(fh.fileno()).st_size
+            ws_bytes = int(L.ysmr_csv_workspace_bytes(size))
+            if ws_bytes == 0:
+                return host()
+            staged = _pinned("csv text", size)
+            view, at = memoryview(staged.numpy()), 0
+            while at < size:
+                got = fh.readinto(view[at:])
+                if not got:
+                    return host()               # (the file shrank under the read)
+                at += got
+    except OSError:
+        return host()
+    marks["file read"] = time.perf_counter() - t0
+    window = 1 << 16
+    while True:
+        head = view[:min(window, size)].tobytes().find(b"\n")
+        if head >= 0 or window >= size:
+            break
+        window *= 16
+    plan = csv_header_plan(view[:head] if head >= 0 else view[:size])
+    if plan is None:
+        return host()
+    n_columns, positions = plan
+    wanted = np.asarray(positions, np.int32)
+    with torch.cuda.device(dev):
+        stream = _lib.stream_ptr(dev)
+        text = torch.empty((size + 255) // 256 * 256, dtype=torch.uint8, device=dev)
+        text[:size].copy_(staged, non_blocking=True)
+        if sync_phases:
+            torch.cuda.current_stream(dev).synchronize()
+            marks["upload"] = time.perf_counter() - t0
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        meta = torch.zeros(4, dtype=torch.int32, device=dev)             # lines, flags, unserved
+        _lib.check(L.ysmr_csv_index(stream, text.data_ptr(), size, ws.data_ptr(), ws_bytes, meta.data_ptr(), meta[1:].data_ptr()),
+                   "ysmr_csv_index")
+        n_lines, flags = (int(v) & 0xFFFFFFFF for v in meta[:2].cpu())
+        marks["index"] = time.perf_counter() - t0
+        if flags:
+            return host(flags=flags)
+        n = n_lines - 1
+        buf = torch.empty(max(48 * n, 8), dtype=torch.uint8, device=dev)
+        base = buf.data_ptr()
+        _lib.check(L.ysmr_csv_parse(stream, text.data_ptr(), size, ws.data_ptr(), ws_bytes, n_columns, wanted.ctypes.data, n, base,
+                                    base + 4 * n, *[base + 8 * n + 8 * n * k for k in range(5)], meta[2:].data_ptr()), "ysmr_csv_parse")
+        # the rows not served, and the six ids of upstream's rough check (helper_file.py:892-905), in one copy
+        first = min(n, 6)
+        back = torch.cat([meta[2:3], buf[:4 * first].view(torch.int32)]).cpu().numpy()
+        marks["parse"] = time.perf_counter() - t0
+        unserved = int(back[0]) & 0xFFFFFFFF
+        if unserved:
+            return host(unserved=unserved)
+        del text, ws
+        if check_sorted and n and len(set(back[1:].tolist())) == first:
+            ordered = torch.empty(48 * n, dtype=torch.uint8, device=dev)
+            ows_bytes = int(L.ysmr_csv_order_workspace_bytes(n))
+            ows = torch.empty(ows_bytes, dtype=torch.uint8, device=dev)
+            to = ordered.data_ptr()
+            _lib.check(L.ysmr_csv_order(stream, n, base, base + 4 * n, *[base + 8 * n + 8 * n * k for k in range(5)], ows.data_ptr(),
+                                        ows_bytes, to, to + 4 * n, *[to + 8 * n + 8 * n * k for k in range(5)]), "ysmr_csv_order")
+            buf = ordered
+            if sync_phases:
+                torch.cuda.current_stream(dev).synchronize()
+            marks["order"] = time.perf_counter() - t0
+    return DeviceTable("device", n_rows=n, columns=_split_columns(buf, n) if n else None, positions=positions, device=dev, buffer=buf)
 
 
 def save_df_to_csv(df, save_path, rename_old_file=True):

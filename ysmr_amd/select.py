@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .helper_file import create_results_folder, get_configs, get_data, save_df_to_csv
+from .helper_file import create_results_folder, get_configs, get_data, read_table_device, save_df_to_csv
 
 __all__ = ["select_tracks", "select_params", "select_rows"]
 
@@ -46,9 +46,11 @@ def select_params(settings, fps, frame_height, frame_width) -> _lib.SelectParams
     return p
 
 
-def select_rows(df, params: _lib.SelectParams, device="cuda:0"):
+def select_rows(df, params: _lib.SelectParams, device="cuda:0", columns_dev=None):
     """Run ``ysmr_select_tracks`` on the six columns the selection reads.
-    Returns (rows of ``df``, their index in the cleaned table, summary)."""
+    Returns (rows of ``df``, their index in the cleaned table, summary).
+    ``columns_dev``: those six columns of ``df`` where they are on ``device`` already (``DeviceTable.columns_dev`` of
+    ``helper_file.read_table_device``): nothing is uploaded."""
     import torch
     n = len(df)
     summary = _lib.SelectSummary()
@@ -58,8 +60,11 @@ def select_rows(df, params: _lib.SelectParams, device="cuda:0"):
         def up(name, dtype):
             return torch.from_numpy(np.ascontiguousarray(df[name].to_numpy(), dtype=dtype).view(
                 np.int32 if dtype == np.uint32 else dtype)).to(dev)
-        cols = [up("TRACK_ID", np.uint32), up("POSITION_T", np.uint32), up("POSITION_X", np.float64),
-                up("POSITION_Y", np.float64), up("WIDTH", np.float64), up("HEIGHT", np.float64)]
+        cols = columns_dev if columns_dev is not None else [
+            up("TRACK_ID", np.uint32), up("POSITION_T", np.uint32), up("POSITION_X", np.float64),
+            up("POSITION_Y", np.float64), up("WIDTH", np.float64), up("HEIGHT", np.float64)]
+        if len(cols) != 6 or any(c.numel() != n or not c.is_cuda for c in cols):
+            raise ValueError("columns_dev must be the table's six columns on {}".format(dev))
         ws_bytes = L.ysmr_select_workspace_bytes(n, params.max_recursion)
         ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
         sel_row = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
@@ -110,14 +115,23 @@ def select_tracks(path_to_file=None, df=None, results_directory=None, fps=None, 
         if not holds:
             logger.critical(complaint)
             return None
+    columns_dev = None
     if not isinstance(df, pd.DataFrame):
-        df = get_data(path_to_file)
+        if settings.get("hip read csv on device"):
+            # text to numbers on the device (csrc/csv.hip); the columns stay there for the selection
+            table = read_table_device(path_to_file, device)
+            df = None if table is None else table.to_dataframe()
+            columns_dev = None if table is None else table.columns_dev
+        else:
+            df = get_data(path_to_file)
     if df is None:
         logger.critical("Error reading data frame from file {}".format(path_to_file))
         return None
     params = select_params(settings, fps, frame_height, frame_width)
     try:
-        rows, index, s = select_rows(df, params, device=device)
+        # (the columns that came from the device a moment ago are not uploaded again)
+        extra = {} if columns_dev is None else {"columns_dev": columns_dev}
+        rows, index, s = select_rows(df, params, device=device, **extra)
     except (_lib.YsmrLibraryError, RuntimeError) as exc:
         logger.critical("Device path failed for file {}: {}".format(path_to_file, exc))
         return None
