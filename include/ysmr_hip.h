@@ -650,6 +650,48 @@ int    ysmr_csv_parse_devicelike(const char *text_host, size_t n_bytes, int n_co
                                  long long row_capacity, uint32_t *track_id, uint32_t *t, double *x, double *y, double *w,
                                  double *h, double *angle, long long *n_rows, long long *unserved, uint32_t *flags);
 
+/* DEVICE functions (added under ABI 15): the writing direction for ANY table of typed columns -- what
+ * DataFrame.to_csv(index=False) writes with '\n' line ends (helper_file.py:1366-1400, save_df_to_csv: `<name>_selected_data.csv`,
+ * `<name>_analysed.csv`), byte for byte, from columns that are in device memory.  The header's bytes are written as given; each
+ * row is a line of n_columns (1 .. 16) fields separated by ',' and ended by '\n'.  Integers are plain decimals; a float64 is its
+ * repr (shortest round-trip digits, CPython's layout) for EVERY finite value, 0.0 / -0.0, inf / -inf, and NaN is the empty field.
+ * (A NaN that is its line's only field is written "", as the csv module quotes a line that would be empty.)
+ * The widest fields are 10 / 20 / 11 / 4 / 24 bytes for the five types.
+ *
+ * ysmr_table_csv_bound: header_bytes + n_rows x the sum of (width + 1).  0 for what is refused: a negative count, no or more than
+ * 16 columns, an unknown type, arithmetic beyond size_t, a bound above 2^32 - 1 (the scans are 32-bit).  Nothing is truncated.
+ * ysmr_table_format_workspace_bytes: 0 for the same; 256 for n_rows = 0.
+ *
+ * ysmr_table_format_device: asynchronous on `stream`, no host synchronisation inside.  columns: a HOST array whose data pointers
+ * are DEVICE pointers to n_rows values each; header_host: host memory (may be NULL with header_bytes = 0).  csv_capacity >=
+ * the bound, else YSMR_ERR_CAPACITY and nothing is launched; *csv_length_dev receives the bytes written, *wide_cells_dev the
+ * number of float64 cells outside 0 and 2^-20 <= |v| < 2^24 (finite): those are printed by a kernel of their own (k_table_wide,
+ * multi-word integers) into side slots and copied by the row printer, whose steady path prints everything else once, a row per
+ * lane, staged in LDS and sent out compacted.  The text depends on the input alone (no ordering comes from atomics).
+ *
+ * ysmr_table_format_geometry: rows per workgroup of the row printer, and the largest staging in LDS (sixteen float64 columns;
+ * a table's own is rows_per_group x its longest line rounded up to 4).
+ *
+ * ysmr_table_format_devicelike: a HOST function, the same arithmetic (csrc/fmt.h) a row at a time on columns in host memory;
+ * what the CPU tests compare with pandas.  ysmr_fmt_f64_text: a HOST function, n float64 fields into 24-byte slots (zero filled
+ * behind the text) with their lengths; printer 0: the fast printer (length 255 for a value it declines), 1: the wide printer
+ * for every finite non-zero value, 2: the writer's choice between the two. */
+#define YSMR_COL_U32 0
+#define YSMR_COL_I64 1
+#define YSMR_COL_I32 2
+#define YSMR_COL_I8  3
+#define YSMR_COL_F64 4
+typedef struct { const void *data; int32_t type; int32_t reserved; } ysmr_table_column;
+size_t ysmr_table_csv_bound(long long n_rows, int n_columns, const ysmr_table_column *columns, size_t header_bytes);
+size_t ysmr_table_format_workspace_bytes(long long n_rows, int n_columns, const ysmr_table_column *columns);
+int    ysmr_table_format_device(void *stream, long long n_rows, int n_columns, const ysmr_table_column *columns,
+                                const char *header_host, size_t header_bytes, void *workspace_dev, size_t workspace_bytes,
+                                char *csv_dev, size_t csv_capacity, unsigned long long *csv_length_dev, uint32_t *wide_cells_dev);
+void   ysmr_table_format_geometry(int *rows_per_group, int *staged_bytes);
+int    ysmr_table_format_devicelike(long long n_rows, int n_columns, const ysmr_table_column *columns, const char *header,
+                                    size_t header_bytes, char *out, size_t out_capacity, size_t *out_length, long long *wide_cells);
+int    ysmr_fmt_f64_text(const double *values, long long n, int printer, char *slots, uint8_t *lengths);
+
 /* HOST functions (ABI 13): the same csv and columns worked out WHILE the video runs.  Rows go in as the link emits them -- any
  * number of ysmr_rows_stream_push calls with host rows in any order; a call copies its rows and returns, the stream's threads
  * format them meanwhile -- and ysmr_rows_stream_finish orders what has been pushed by (TRACK_ID, POSITION_T) (a row's place is

@@ -3,7 +3,8 @@
 //   helper_file.py:1403-1478 (save_list: str() of every value), :860-905 (get_data: pandas.read_csv), :1366-1400 (save_df_to_csv)
 // Shortest digits that round-trip, by Steele & White / Burger & Dybvig's free-format algorithm in 128-bit fixed point: enough for
 // 2^-20 <= |v| < 2^24 (a track's coordinates, sizes and angles; everything else -- and NaN, infinities -- is left to the host:
-// `in_range`).  No tables, no division: a digit is at most nine subtractions.
+// `in_range`).  No tables, no division: a digit is at most nine subtractions.  The table writer (table_csv.hip) prints every
+// float64: what shortest() declines goes through shortest_wide() further down, the same algorithm on multi-word integers.
 #pragma once
 #include <stdint.h>
 #include "hd.h"
@@ -181,6 +182,208 @@ YSMR_FMT_HD char *put_u32(char *p, uint32_t v)
     do { t[n++] = (char)('0' + v % 10u); v /= 10u; } while (v);
     while (n) *p++ = t[--n];
     return p;
+}
+
+// ---- every finite float64: the printer of the rare cell (table_csv.hip: k_table_wide) ---------------------------------------
+// The same free-format algorithm as shortest() -- Burger & Dybvig's R, S, M+, M- with the round-to-even boundaries -- on
+// integers of WIDE_WORDS x 32 bits instead of 128-bit fixed point, so that it holds for every finite non-zero double, 5e-324
+// (2^-1074) to 1.7976931348623157e+308.  The largest numbers met: S = 2^1076 for a subnormal (times ten if the first guess of
+// the decimal exponent is one low), 4 x 10^309 < 2^1029 at the top, R + M+ below 10 S in the digit loop: under 2^1084 of the
+// 1152 bits.  No tables: a power of ten is multiplied in nine decimal digits at a time.  Slow on purpose (a few thousand word
+// operations a value) and not forced inline: it may use scratch memory for its integers, which is why the steady kernels
+// never call it.
+constexpr int WIDE_WORDS = 36;
+
+struct Wide {
+    uint32_t w[WIDE_WORDS];     // little endian; w[n - 1] != 0
+    int n;                      // words in use (0: the value is zero)
+};
+
+YSMR_HD inline void wide_set(Wide &a, uint64_t m, int shift)        // a = m << shift  (m < 2^54, shift <= 1078)
+{
+    for (int i = 0; i < WIDE_WORDS; ++i) a.w[i] = 0u;
+    const int word = shift >> 5, bit = shift & 31;
+    const uint32_t lo = (uint32_t)m, hi = (uint32_t)(m >> 32);
+    a.w[word] = lo << bit;
+    a.w[word + 1] = (hi << bit) | (bit ? lo >> (32 - bit) : 0u);
+    a.w[word + 2] = bit ? hi >> (32 - bit) : 0u;
+    a.n = word + 3;
+    while (a.n > 0 && a.w[a.n - 1] == 0u) --a.n;
+}
+
+YSMR_HD inline void wide_mul_small(Wide &a, uint32_t c)
+{
+    uint64_t carry = 0;
+    for (int i = 0; i < a.n; ++i) {
+        const uint64_t t = (uint64_t)a.w[i] * c + carry;
+        a.w[i] = (uint32_t)t;
+        carry = t >> 32;
+    }
+    if (carry && a.n < WIDE_WORDS) a.w[a.n++] = (uint32_t)carry;
+}
+
+YSMR_HD inline void wide_mul_pow10(Wide &a, int k)
+{
+    for (; k >= 9; k -= 9) wide_mul_small(a, 1000000000u);
+    uint32_t c = 1u;
+    for (int i = 0; i < k; ++i) c *= 10u;
+    if (c > 1u) wide_mul_small(a, c);
+}
+
+YSMR_HD inline int wide_cmp(const Wide &a, const Wide &b)          // -1, 0, 1
+{
+    if (a.n != b.n) return a.n < b.n ? -1 : 1;
+    for (int i = a.n - 1; i >= 0; --i)
+        if (a.w[i] != b.w[i]) return a.w[i] < b.w[i] ? -1 : 1;
+    return 0;
+}
+
+YSMR_HD inline void wide_add(Wide &out, const Wide &a, const Wide &b)
+{
+    const int n = a.n > b.n ? a.n : b.n;
+    uint64_t carry = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint64_t t = (uint64_t)(i < a.n ? a.w[i] : 0u) + (i < b.n ? b.w[i] : 0u) + carry;
+        out.w[i] = (uint32_t)t;
+        carry = t >> 32;
+    }
+    out.n = n;
+    if (carry && out.n < WIDE_WORDS) out.w[out.n++] = (uint32_t)carry;
+}
+
+YSMR_HD inline void wide_sub(Wide &a, const Wide &b)               // a -= b, a >= b
+{
+    uint64_t borrow = 0;
+    for (int i = 0; i < a.n; ++i) {
+        const uint64_t t = (uint64_t)a.w[i] - (i < b.n ? b.w[i] : 0u) - borrow;
+        a.w[i] = (uint32_t)t;
+        borrow = (t >> 32) & 1u;
+    }
+    while (a.n > 0 && a.w[a.n - 1] == 0u) --a.n;
+}
+
+// v > 0 and finite
+YSMR_HD inline void shortest_wide(double v, Digits &out)
+{
+    const uint64_t b = bits_of(v);
+    const uint64_t frac = b & ((1ull << 52) - 1ull);
+    const int be = (int)((b >> 52) & 0x7FFu);
+    const uint64_t m = be ? (1ull << 52) | frac : frac;     // v = m 2^e2
+    const int e2 = (be ? be : 1) - 1075;
+    const int u = (frac == 0 && be > 1) ? 1 : 0;            // the gap below a power of two is half as wide (not below 2^-1022)
+    const bool even = (m & 1ull) == 0;
+    Wide R, S, Mp, Mm, T;
+    if (e2 >= 0) { wide_set(R, m, e2 + 1 + u); wide_set(S, 1ull, 1 + u); wide_set(Mm, 1ull, e2); wide_set(Mp, 1ull, e2 + u); }
+    else { wide_set(R, m, 1 + u); wide_set(S, 1ull, 1 - e2 + u); wide_set(Mm, 1ull, 0); wide_set(Mp, 1ull, u); }
+    // a first guess of the decimal exponent from the binary one, floor(e log10 2) + 1; the two loops settle it as in shortest()
+    int top = 63;
+    while (!((m >> top) & 1ull)) --top;
+    int k = (((e2 + top) * 78913) >> 18) + 1;
+    if (k > 0) wide_mul_pow10(S, k);
+    else if (k < 0) { wide_mul_pow10(R, -k); wide_mul_pow10(Mp, -k); wide_mul_pow10(Mm, -k); }
+    // scale: (R + Mp) / S in [1/10, 1)
+    for (;;) {
+        wide_add(T, R, Mp);
+        const int c = wide_cmp(T, S);
+        if (!(even ? c >= 0 : c > 0)) break;
+        wide_mul_small(S, 10u); ++k;
+    }
+    for (;;) {
+        wide_add(T, R, Mp);
+        wide_mul_small(T, 10u);
+        const int c = wide_cmp(T, S);
+        if (even ? c >= 0 : c > 0) break;
+        wide_mul_small(R, 10u); wide_mul_small(Mp, 10u); wide_mul_small(Mm, 10u); --k;
+    }
+    int n = 0;
+    while (true) {
+        wide_mul_small(R, 10u); wide_mul_small(Mp, 10u); wide_mul_small(Mm, 10u);
+        int d = 0;
+        while (wide_cmp(R, S) >= 0) { wide_sub(R, S); ++d; }
+        const int cl = wide_cmp(R, Mm);
+        const bool low = even ? cl <= 0 : cl < 0;
+        wide_add(T, R, Mp);
+        const int ch = wide_cmp(T, S);
+        const bool high = even ? ch >= 0 : ch > 0;
+        if (!low && !high && n < 17) { out.d[n++] = (char)('0' + d); continue; }
+        if (low && high) {                                   // the nearer neighbour, a tie to the even digit (as shortest())
+            wide_add(T, R, R);
+            const int c2 = wide_cmp(T, S);
+            d += c2 < 0 ? 0 : (c2 > 0 ? 1 : (d & 1));
+        }
+        else if (high) d += 1;
+        out.d[n++] = (char)('0' + d);
+        break;
+    }
+    out.n = n;
+    out.exp10 = k - 1;
+}
+
+// ---- a float64 field of a csv as DataFrame.to_csv writes it -----------------------------------------------------------------
+// NaN is the empty field, then inf / -inf, 0.0 / -0.0, and every other value its repr.  The widest is 24 bytes
+// (-1.2345678901234567e-308).
+// a wide cell: finite, non-zero and outside in_range -- the steady row printer copies its text from a side slot
+YSMR_FMT_HD bool is_wide_cell(double v)
+{
+    const uint64_t a = bits_of(v) & 0x7FFFFFFFFFFFFFFFull;
+    return a != 0 && a < 0x7FF0000000000000ull && !in_range(double_of(a));
+}
+
+// every value that is NOT a wide cell, with shortest(): the steady path.  `g` is the caller's, so that a kernel can keep it
+// where dynamic indexing costs no scratch memory (LDS).
+YSMR_FMT_HD char *put_f64_steady(char *p, double v, Digits &g)
+{
+    const uint64_t b = bits_of(v);
+    const bool neg = (b >> 63) != 0;
+    const uint64_t a = b & 0x7FFFFFFFFFFFFFFFull;
+    if (a > 0x7FF0000000000000ull) return p;                 // NaN
+    if (neg) *p++ = '-';
+    if (a == 0x7FF0000000000000ull) { *p++ = 'i'; *p++ = 'n'; *p++ = 'f'; return p; }
+    if (a == 0) { *p++ = '0'; *p++ = '.'; *p++ = '0'; return p; }
+    shortest(double_of(a), g);
+    return layout(p, g);
+}
+
+// a wide cell, with shortest_wide()
+YSMR_HD inline char *put_f64_wide(char *p, double v)
+{
+    const uint64_t b = bits_of(v);
+    if (b >> 63) *p++ = '-';
+    Digits g;
+    shortest_wide(double_of(b & 0x7FFFFFFFFFFFFFFFull), g);
+    return layout(p, g);
+}
+
+YSMR_HD inline char *put_f64_field(char *p, double v)
+{
+    if (is_wide_cell(v)) return put_f64_wide(p, v);
+    Digits g;
+    return put_f64_steady(p, v, g);
+}
+
+// Integers straight into their place, last digit first once the count is known: no array of digits that a kernel would have to
+// keep in scratch memory (put_u32 above keeps one).
+YSMR_FMT_HD char *put_dec32(char *p, uint32_t v)
+{
+    int n = 1;
+    for (uint32_t t = v; t >= 10u; t /= 10u) ++n;
+    for (int i = n - 1; i >= 0; --i) { p[i] = (char)('0' + v % 10u); v /= 10u; }
+    return p + n;
+}
+
+YSMR_FMT_HD char *put_dec64(char *p, uint64_t v)
+{
+    if (v <= 0xFFFFFFFFull) return put_dec32(p, (uint32_t)v);
+    int n = 1;
+    for (uint64_t t = v; t >= 10u; t /= 10u) ++n;
+    for (int i = n - 1; i >= 0; --i) { p[i] = (char)('0' + (int)(v % 10u)); v /= 10u; }
+    return p + n;
+}
+
+YSMR_FMT_HD char *put_int64(char *p, int64_t v)
+{
+    if (v < 0) { *p++ = '-'; return put_dec64(p, 0ull - (uint64_t)v); }    // (-2^63: its own negation as an unsigned number)
+    return put_dec64(p, (uint64_t)v);
 }
 
 }  // namespace ysmr_fmt

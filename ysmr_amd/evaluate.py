@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .helper_file import create_results_folder, get_configs, get_data, read_table_device, save_df_to_csv
+from .helper_file import create_results_folder, get_configs, get_data, read_table_device, save_df_to_csv, write_table_device
 
 __all__ = ["evaluate_tracks", "evaluate_params", "evaluate_columns"]
 
@@ -122,10 +122,12 @@ def evaluate_params(settings, fps) -> _lib.EvaluateParams:
     return p
 
 
-def evaluate_columns(df, params: _lib.EvaluateParams, device="cuda:0", columns_dev=None):
+def evaluate_columns(df, params: _lib.EvaluateParams, device="cuda:0", columns_dev=None, keep_device=False):
     """Run ``ysmr_evaluate_tracks`` on the table's six input columns.  Returns (dict of per-row arrays,
     statistics array [tracks, 12]).  ``columns_dev``: those six columns where they are on ``device`` already
-    (``DeviceTable.columns_dev`` of ``helper_file.read_table_device``): nothing is uploaded."""
+    (``DeviceTable.columns_dev`` of ``helper_file.read_table_device``): nothing is uploaded.  ``keep_device``: a third
+    value, name -> tensor of the columns of ``<name>_analysed.csv`` that are on the device now -- the eight output columns
+    and the four inputs they do not replace -- for ``helper_file.write_table_device``."""
     import torch
     n = len(df)
     L = _lib.lib()
@@ -152,7 +154,12 @@ def evaluate_columns(df, params: _lib.EvaluateParams, device="cuda:0", columns_d
                                     out["travelled_dist"].data_ptr(), out["motility_phenotype"].data_ptr(), stats.data_ptr(),
                                     ctypes.byref(n_tracks))
         _lib.check(rc, "ysmr_evaluate_tracks")
-        return {k: v[:n].cpu().numpy() for k, v in out.items()}, stats[: n_tracks.value].cpu().numpy()
+        host = {k: v[:n].cpu().numpy() for k, v in out.items()}, stats[: n_tracks.value].cpu().numpy()
+        if not keep_device:
+            return host
+        held = dict(zip(("TRACK_ID", "POSITION_T", "POSITION_X", "POSITION_Y"), cols[:4]))
+        held.update({k: v[:n] for k, v in out.items()})
+        return host + (held,)
 
 
 def evaluate_tracks(path_to_file, results_directory=None, df=None, settings=None, fps=None, device="cuda:0", **_):
@@ -196,7 +203,12 @@ def evaluate_tracks(path_to_file, results_directory=None, df=None, settings=None
     try:
         # (the columns that came from the device a moment ago are not uploaded again)
         extra = {} if columns_dev is None else {"columns_dev": columns_dev}
-        rows, stats = evaluate_columns(table, evaluate_params(settings, fps), device=device, **extra)
+        held = None
+        if settings.get("hip write csv on device") and settings["store final analysed .csv file"]:
+            # (... and what the analysed csv is printed from stays there)
+            rows, stats, held = evaluate_columns(table, evaluate_params(settings, fps), device=device, keep_device=True, **extra)
+        else:
+            rows, stats = evaluate_columns(table, evaluate_params(settings, fps), device=device, **extra)
     except (_lib.YsmrLibraryError, RuntimeError) as exc:
         logger.critical("Device path failed for file {}: {}".format(path_to_file, exc))
         return None
@@ -232,7 +244,11 @@ def evaluate_tracks(path_to_file, results_directory=None, df=None, settings=None
     if asked and not violins:
         logger.info("Plots are not part of the HIP path; skipped: {}".format(", ".join(asked)))
     if settings["store final analysed .csv file"]:
-        save_df_to_csv(df=out, save_path=save_path.format("analysed", ".csv"))
+        if held is not None:
+            # numbers to text on the device (csrc/table_csv.hip): the same bytes; DEGREES_ANGLE is the one column uploaded
+            write_table_device(out, save_path.format("analysed", ".csv"), device, columns_dev=held)
+        else:
+            save_df_to_csv(df=out, save_path=save_path.format("analysed", ".csv"))
     if violins or any(settings.get(k) for k in ("save large plots", "save rose plot", "save angle distribution plot / bins")):
         _figures(out, stats, settings, plot_title(file_name), save_path, device, logger, df_stats, parameter)
     logging.info("Done evaluating file {}".format(file_name))

@@ -241,7 +241,14 @@ def default_settings(**overrides):
 def get_configs(tracking_ini_filepath=None):
     """Read ``tracking.ini`` into the flat settings dict, or pass an existing dict through
     (helper_file.py:595-596).  A missing or broken file is regenerated with defaults and ``None`` is
-    returned, as upstream (helper_file.py:840-843)."""
+    returned, as upstream (helper_file.py:840-843).
+
+    Keys that tracking.ini does not know are opt-in switches of this package, set in a settings dict and read with
+    ``settings.get`` (absent: the path runs as it always has): ``'hip read csv on device'`` -- ``select_tracks`` and
+    ``evaluate_tracks`` read their csv through :func:`read_table_device`; ``'hip write csv on device'`` -- they write
+    ``<name>_selected_data.csv`` and ``<name>_analysed.csv`` through :func:`write_table_device` (the same bytes;
+    ``<name>_statistics.csv``, one row per track, stays with pandas); ``'hip png on device'`` and ``'hip violin plots'`` -- the
+    figures (``evaluate.py``, ``plot_functions.py``)."""
     if isinstance(tracking_ini_filepath, dict):
         return tracking_ini_filepath
     if tracking_ini_filepath is None:
@@ -846,19 +853,158 @@ def read_table_device(path, device="cuda:0", check_sorted=True, sync_phases=Fals
     return DeviceTable("device", n_rows=n, columns=_split_columns(buf, n) if n else None, positions=positions, device=dev, buffer=buf)
 
 
+def _move_aside(save_path):
+    """An existing ``save_path`` becomes ``<yymmddHHMMSS>.<old file name>`` beside it (helper_file.py:1366-1400)."""
+    folder, name = os.path.split(save_path)
+    try:
+        moved = os.path.join(folder, "{}.{}".format(datetime.now().strftime("%y%m%d%H%M%S"), name))
+        os.rename(save_path, moved)
+        _logger().critical("Old {} renamed to {}".format(name, moved))
+    except (FileNotFoundError, FileExistsError):
+        pass
+    except OSError as exc:
+        _logger().exception("Could not move previous file {} aside: {}".format(save_path, exc))
+
+
+#: (diagnostics) seconds since the call began at which the last write_table_device reached its steps
+LAST_TABLE_WRITE_MARKS = {}
+
+
+def table_csv_plan(df):
+    """What the device writer (csrc/table_csv.hip) needs to know of a DataFrame: ``(header bytes, [numpy dtype per column])``,
+    or None for a frame it does not serve -- then ``DataFrame.to_csv`` writes the whole file: no or more than 16 columns,
+    column labels that are not one level of strings, a name ``to_csv`` would quote (it holds ``,``, ``"``, ``\\r`` or ``\\n``,
+    or is empty) or that is not UTF-8 text, a dtype other than uint32, int64, int32, int8 and float64 (``float32`` and
+    ``object`` among them)."""
+    from . import _lib
+    names = list(df.columns)
+    if not 1 <= len(names) <= _lib.TABLE_MAX_COLUMNS or getattr(df.columns, "nlevels", 1) != 1:
+        return None
+    if any(not isinstance(k, str) or k == "" or any(ch in k for ch in ',"\r\n') for k in names):
+        return None
+    dtypes = [df.iloc[:, k].dtype for k in range(len(names))]
+    if any(not isinstance(dt, np.dtype) or dt not in _lib.TABLE_COLUMN_TYPES for dt in dtypes):
+        return None
+    try:
+        header = (",".join(names) + "\n").encode("utf-8")
+    except UnicodeEncodeError:
+        return None
+    return header, dtypes
+
+
+def _table_columns(pointers, dtypes):
+    from . import _lib
+    cols = (_lib.TableColumn * len(dtypes))()
+    for k, (ptr, dt) in enumerate(zip(pointers, dtypes)):
+        cols[k].data, cols[k].type = ptr, _lib.TABLE_COLUMN_TYPES[np.dtype(dt)]
+    return cols
+
+
+def table_csv_devicelike(df, header=None):
+    """``ysmr_table_format_devicelike`` on a DataFrame: the arithmetic of the device writer (csrc/fmt.h) on the host, for the
+    CPU tests.  Returns ``(bytes, wide_cells)``; None for a frame :func:`table_csv_plan` refuses.  ``header``: bytes to write
+    in place of the column names' line."""
+    import ctypes
+    from . import _lib
+    plan = table_csv_plan(df)
+    if plan is None:
+        return None
+    L = _lib.lib()
+    head, dtypes = plan
+    head = head if header is None else bytes(header)
+    arrays = [np.ascontiguousarray(df.iloc[:, k].to_numpy()) for k in range(len(dtypes))]
+    cols = _table_columns([a.ctypes.data for a in arrays], dtypes)
+    n = len(df)
+    cap = int(L.ysmr_table_csv_bound(n, len(dtypes), cols, len(head)))
+    out = np.empty(max(cap, 1), np.uint8)
+    length, wide = ctypes.c_size_t(0), ctypes.c_longlong(0)
+    _lib.check(L.ysmr_table_format_devicelike(n, len(dtypes), cols, head, len(head), out.ctypes.data, cap, ctypes.byref(length),
+                                              ctypes.byref(wide)), "ysmr_table_format_devicelike")
+    return out[:length.value].tobytes(), wide.value
+
+
+def table_format_device(tensors, dtypes, n, header, device):
+    """``ysmr_table_format_device`` on columns that are on ``device`` (``tensors``: one per column, ``n`` values of the numpy
+    dtype in ``dtypes`` each, a uint32 column as its int32 bits).  Returns ``(csv, length, wide_cells)`` -- the text as a uint8
+    tensor on the device, its length and the number of wide cells, read back with one copy -- or None where the plan refuses
+    (more text than the 32-bit offsets hold)."""
+    import torch
+    from . import _lib
+    L = _lib.lib()
+    cols = _table_columns([t.data_ptr() if n else 0 for t in tensors], dtypes)
+    cap = int(L.ysmr_table_csv_bound(n, len(dtypes), cols, len(header)))
+    ws_bytes = int(L.ysmr_table_format_workspace_bytes(n, len(dtypes), cols))
+    if (cap == 0 and (n or header)) or ws_bytes == 0:
+        return None
+    with torch.cuda.device(device):
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+        csv = torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
+        meta = torch.zeros(2, dtype=torch.int64, device=device)          # csv length; wide cells (low 32 bits)
+        _lib.check(L.ysmr_table_format_device(_lib.stream_ptr(device), n, len(dtypes), cols, header, len(header), ws.data_ptr(), ws_bytes,
+                                              csv.data_ptr(), cap, meta.data_ptr(), meta[1:].data_ptr()), "ysmr_table_format_device")
+        length, wide = (int(v) for v in meta.cpu())
+    return csv, length, wide & 0xFFFFFFFF
+
+
+def write_table_device(df, save_path, device="cuda:0", columns_dev=None, rename_old_file=True):
+    """:func:`save_df_to_csv` with the printing on the GPU (csrc/table_csv.hip): the same file, byte for byte.  The header line
+    is built here, the columns that are not on ``device`` already are uploaded (``columns_dev``: name -> tensor of a column's
+    values there, a uint32 column as its int32 bits; one that does not have the frame's length and item size is ignored), the
+    text is printed there (``ysmr_table_format_device``), copied into a pinned buffer and written as the list's is.  The
+    renaming of an older file, the log lines and the swallowing of an ``OSError`` are ``save_df_to_csv``'s; like it, the index
+    is never written.  A frame the device writer does not serve (:func:`table_csv_plan`; a refusal by the plan's sizes) goes to
+    ``save_df_to_csv`` unchanged, for the whole file.  Returns which path ran: ``'device'`` or ``'host'``."""
+    import time
+    import torch
+    t0 = time.perf_counter()
+    marks = LAST_TABLE_WRITE_MARKS
+    marks.clear()
+    plan = table_csv_plan(df)
+    if plan is None:
+        save_df_to_csv(df, save_path, rename_old_file=rename_old_file)
+        return "host"
+    header, dtypes = plan
+    n = len(df)
+    dev = torch.device(device)
+    columns_dev = columns_dev or {}
+    with torch.cuda.device(dev):
+        tensors = []
+        for k, (name, dt) in enumerate(zip(df.columns, dtypes)):
+            held = columns_dev.get(name)
+            if held is not None and held.is_cuda and held.device == dev and held.dim() == 1 and held.numel() == n and \
+                    held.element_size() == dt.itemsize and held.is_contiguous() and held.dtype.is_floating_point == (dt.kind == "f"):
+                tensors.append(held)
+                continue
+            values = np.ascontiguousarray(df.iloc[:, k].to_numpy())
+            tensors.append(torch.from_numpy(values.view(np.int32) if dt == np.uint32 else values).to(dev, non_blocking=False))
+        marks["upload"] = time.perf_counter() - t0
+        done = table_format_device(tensors, dtypes, n, header, dev)
+        if done is None:
+            save_df_to_csv(df, save_path, rename_old_file=rename_old_file)
+            return "host"
+        csv, length, wide = done
+        marks["format"] = time.perf_counter() - t0
+        marks["wide cells"] = wide
+        text = _pinned("table text", length)
+        text.copy_(csv[:length], non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+    marks["download"] = time.perf_counter() - t0
+    if rename_old_file:
+        _move_aside(save_path)
+    try:
+        _write_file(save_path, text.numpy())
+        _logger().debug("Selected results saved to: {}".format(save_path))
+    except OSError as exc:
+        _logger().exception("Could not save {}: {}".format(save_path, exc))
+    marks["written"] = time.perf_counter() - t0
+    return "device"
+
+
 def save_df_to_csv(df, save_path, rename_old_file=True):
     """Write a DataFrame as csv without its index (helper_file.py:1366-1400); an existing file of the
     same name is first moved aside to ``<yymmddHHMMSS>.<old file name>``."""
     if rename_old_file:
-        folder, name = os.path.split(save_path)
-        try:
-            moved = os.path.join(folder, "{}.{}".format(datetime.now().strftime("%y%m%d%H%M%S"), name))
-            os.rename(save_path, moved)
-            _logger().critical("Old {} renamed to {}".format(name, moved))
-        except (FileNotFoundError, FileExistsError):
-            pass
-        except OSError as exc:
-            _logger().exception("Could not move previous file {} aside: {}".format(save_path, exc))
+        _move_aside(save_path)
     try:
         with open(save_path, "w+", newline="\n") as fh:
             df.to_csv(fh, index=False, encoding="utf-8")

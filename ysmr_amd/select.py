@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .helper_file import create_results_folder, get_configs, get_data, read_table_device, save_df_to_csv
+from .helper_file import create_results_folder, get_configs, get_data, read_table_device, save_df_to_csv, write_table_device
 
 __all__ = ["select_tracks", "select_params", "select_rows"]
 
@@ -177,5 +177,10 @@ def select_tracks(path_to_file=None, df=None, results_directory=None, fps=None, 
     out.insert(0, "index", index)            # the reference's reset_index(inplace=True) keeps the old index as a column
     out.reset_index(drop=True, inplace=True)
     if settings["store processed .csv file"]:
-        save_df_to_csv(df=out, save_path=os.path.join(results_directory, file_name) + "_selected_data.csv")
+        save_path = os.path.join(results_directory, file_name) + "_selected_data.csv"
+        if settings.get("hip write csv on device"):
+            # numbers to text on the device (csrc/table_csv.hip): the same bytes
+            write_table_device(out, save_path, device)
+        else:
+            save_df_to_csv(df=out, save_path=save_path)
     return out
