@@ -5,6 +5,12 @@ What is pinned, and by what:
   * gsff_*.npz, tracker_*.npz -- outputs of the REFERENCE's own ``ysmr/gsff.py`` and
     ``ysmr/tracker.py`` (imported from /root/reference without executing the package __init__,
     which needs cv2).  Only inputs and outputs are stored -- no reference source.
+    tracker_nine_waves / tracker_twelve_waves / tracker_crowded_cells pin the link to the reference ITSELF at the
+    counts the product runs at: more than 512 and more than 704 live tracks in every frame (nine and all twelve waves of
+    k_batch), frames of more than 600 detections (48 x 48 cells, no candidate lists) and frames whose crowded cells are
+    served from split lists or stay flagged -- with births, deaths and the full filter bank inside ~24 frames.  They are
+    off the half-pixel grid (on it, at these counts, half a percent of the rows belong to tie-assigned tracks) and are
+    refused unless the oracle's shadow filters find no ill-conditioned row at all (operating_point_fixture).
   * propagation.npz           -- outputs of ``scipy.ndimage.binary_propagation`` (the function the
     reference calls at ysmr/track_eval.py:211-214) on small marker/mask pairs.
 The image-side cv2 stages (a1/a2/a3/a5/a6) cannot be pinned: cv2 is not installed and the
@@ -104,7 +110,7 @@ def tracker_scenario(rng, n_obj, n_frames, area, dropout=0.03, birth=0.02, speck
     return frames
 
 
-def run_tracker(tracker_mod, frames, fps, use_gsff, n_min=0, n_max=30, n_f=3, max_disappeared=None):
+def run_tracker(tracker_mod, frames, fps, use_gsff, n_min=0, n_max=30, n_f=3, max_disappeared=None, probe=None):
     ct = tracker_mod.CentroidTracker(max_disappeared=fps if max_disappeared is None else max_disappeared,
                                      fps=fps, n_min=n_min, n_max=n_max, n_f=n_f, use_gsff=use_gsff)
     out = {}
@@ -137,12 +143,137 @@ def run_tracker(tracker_mod, frames, fps, use_gsff, n_min=0, n_max=30, n_f=3, ma
         off.append(off[-1] + len(ids))
         claims_all.append(np.array(claims, dtype=np.int64).reshape(-1, 2)); claim_off.append(claim_off[-1] + len(claims))
         next_id.append(ct.nextObjectID)
+        if probe is not None:
+            probe(f, ct)
     out.update(det=np.concatenate(det_all), det_info=np.concatenate(info_all), det_off=np.array(det_off),
                ids=np.concatenate(ids_all), xy=np.concatenate(xy_all), info=np.concatenate(info_out),
                disappeared=np.concatenate(gone_all), off=np.array(off),
                claims=np.concatenate(claims_all), claim_off=np.array(claim_off), next_id=np.array(next_id),
                fps=np.float64(fps), use_gsff=np.bool_(use_gsff), n_min=np.int64(n_min),
                n_max=np.int64(-1 if n_max is None else n_max), n_f=np.int64(n_f))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# The link at its operating point: nine and twelve waves of k_batch, frames of more than 600 detections, crowded cells.
+# Every such fixture draws from a generator of its OWN, so that the fixtures above regenerate array for array.
+OPERATING_POINT = {
+    # name: (seed, scenario arguments, max_disappeared, (live tracks: more than, at most), (detections: more than, at most))
+    "tracker_nine_waves.npz": (20260901, dict(n_obj=545, n_frames=24, area=1100.0), 3, (512, 576), (128, 600)),
+    "tracker_twelve_waves.npz": (20260902, dict(n_obj=731, n_frames=22, area=1100.0), 3, (704, 768), (600, 768)),
+    "tracker_crowded_cells.npz": (20260903, dict(n_obj=400, n_frames=24, area=1500.0, loose=10, tight=3, period=6), 4, (299, 500), (128, 600)),
+}
+OP_FPS, OP_N_MAX = 12.0, 12          # horizons 4, 8, 12: every track alive from frame 0 is in mode 3 from frame 8 on
+
+
+def operating_point_scenario(rng, n_obj, n_frames, area, loose=0, tight=0, period=5, leave=8, arrive=8, speckle=3, dropout=0.02):
+    """Random-walk blobs off the grid whose number stays within a band: every `period`-th frame shows everything plus
+    `arrive` new blobs and `speckle` spurious detections (the reference registers only in a frame that holds more detections
+    than tracks), the frame after it `leave` blobs go for good (their tracks and the spurious ones are dropped before the
+    next such frame), the other frames lose `dropout` of the detections.  `loose` clusters of twelve blobs ~9 px apart (a
+    cell's candidate list overflows, its quadrants' lists do not) and `tight` clusters of eleven ~4.5 px apart (a quadrant's
+    list overflows too) drift rigidly and slowly over a background kept three cells away from them; their members are never
+    dropped for good.  Detections are rounded to float32 BEFORE the reference sees them (the device is handed float32),
+    boxes lie on a grid of 1/8 px and 1/4 degree (they pass through unchanged; it keeps the file small)."""
+    pos = rng.uniform(10, area - 10, (n_obj, 2))
+    vel = rng.normal(0, 1.0, (n_obj, 2))
+    rigid = np.zeros(n_obj, bool)
+    if loose + tight:
+        cell = area / 30.0                                     # 128 < m <= 600: 32 cells per side, 30 across the extent
+        centres = np.zeros((0, 2))
+        while len(centres) < loose + tight:
+            c = rng.uniform(3 * cell, area - 3 * cell, 2)
+            if len(centres) == 0 or np.linalg.norm(centres - c, axis=1).min() > 5 * cell:
+                centres = np.vstack([centres, c])
+        pos = pos[np.linalg.norm(pos[:, None, :] - centres[None], axis=2).min(1) > 3 * cell]
+        vel = vel[:len(pos)]
+        for k, c in enumerate(centres):
+            pitch, cols, n = (9.0, 4, 12) if k < loose else (4.5, 4, 11)
+            lattice = np.array([(i % cols, i // cols) for i in range(n)], float)
+            members = c + (lattice - lattice.mean(0)) * pitch + rng.uniform(-0.2, 0.2, (n, 2)) * pitch
+            pos = np.vstack([pos, members])
+            vel = np.vstack([vel, np.tile(rng.normal(0, 0.25, 2), (n, 1))])
+        rigid = np.arange(len(pos)) >= len(pos) - 12 * loose - 11 * tight
+    alive = np.ones(len(pos), bool)
+    frames = []
+    for f in range(n_frames):
+        vel[~rigid] += rng.normal(0, 0.2, (int((~rigid).sum()), 2))
+        pos = pos + vel
+        full = f % period == 0
+        if f % period == 1:
+            alive[rng.choice(np.flatnonzero(alive & ~rigid), leave, replace=False)] = False
+        if full and f:
+            fresh = rng.uniform(10, area - 10, (arrive, 2))
+            if loose + tight:
+                fresh = fresh[np.linalg.norm(fresh[:, None, :] - centres[None], axis=2).min(1) > 3 * cell]
+            pos = np.vstack([pos, fresh]); vel = np.vstack([vel, rng.normal(0, 1.0, fresh.shape)])
+            alive = np.concatenate([alive, np.ones(len(fresh), bool)]); rigid = np.concatenate([rigid, np.zeros(len(fresh), bool)])
+        keep = alive & (full | (rng.random(len(pos)) >= dropout))
+        det = pos[keep] + rng.normal(0, 0.1, (int(keep.sum()), 2))
+        if full and f:
+            det = np.vstack([det, rng.uniform(0, area, (speckle, 2))])
+        det = det[rng.permutation(len(det))].astype(np.float32).astype(np.float64)
+        info = np.stack([rng.integers(8, 57, len(det)) / 8.0, rng.integers(8, 57, len(det)) / 8.0,
+                         -rng.integers(0, 361, len(det)) / 4.0], 1)
+        frames.append((det, info))
+    return frames
+
+
+def crowded_cells_of(frames):
+    """Per frame (split cells, cells that stay flagged), by tests/cell_list_model.py -- what k_bgrid makes of the frame."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import cell_list_model as cm
+    out = []
+    for det, _ in frames:
+        grid, order = cm.bin_frame(det)
+        lists, _ = cm.frame_lists(grid, np.asarray(det, np.float32)[order]) if cm.has_lists(len(det)) else (np.zeros((0, 8), np.uint16), None)
+        out.append((int((lists[:, 0] == cm.SPLIT).sum()), int((lists[:, 0] == cm.FLAG).sum())))
+    return out
+
+
+def operating_point_fixture(tracker_mod, name):
+    """One of OPERATING_POINT, or an AssertionError: a fixture is refused unless it is in the state its tests are about in
+    EVERY frame, holds births, deaths and ten frames of the full filter bank, has no distance tie, and the oracle's shadow
+    filters (oracle/ysmr_oracle.py: OracleTracker, shadows=2), run beside the reference on the same frames, find NO row
+    that a one-ulp change moves by more than ILL_CONDITIONED and NO tie-assigned track.  The two zeros are what lets the
+    GPU tests hold every row to 1e-9 unconditionally.  A seed that misses is replaced -- never a cap, and never by what the
+    device computes (this program has no device)."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from oracle.ysmr_oracle import OracleTracker
+    seed, scenario, max_gone, (live_above, live_most), (det_above, det_most) = OPERATING_POINT[name]
+    frames = operating_point_scenario(np.random.default_rng(seed), **scenario)
+    ot = OracleTracker(max_disappeared=max_gone, fps=OP_FPS, n_min=0, n_max=OP_N_MAX, n_f=3, use_gsff=True, shadows=2)
+    seen = dict(live=[], mode3=[], spread=0.0)
+
+    def probe(f, ct):
+        ids, xy, _, _ = ot.update([((float(d[0]), float(d[1])), tuple(map(float, i))) for d, i in zip(*frames[f])])
+        assert ids == list(ct.objects.keys()), f"{name}: the oracle's table differs in frame {f}"
+        sens = ot.last_sens
+        assert not np.isinf(sens).any(), f"{name}: {int(np.isinf(sens).sum())} rows of tie-assigned tracks in frame {f}"
+        assert sens.max() <= OracleTracker.ILL_CONDITIONED, f"{name}: ill-conditioned row in frame {f} (sens {sens.max():.3g})"
+        seen["spread"] = max(seen["spread"], float(sens.max()))
+        seen["live"].append(len(ids))
+        seen["mode3"].append(any(s["mode"] == 3 for s in ct.gsff_dict.values()))
+
+    out = run_tracker(tracker_mod, frames, OP_FPS, True, n_max=OP_N_MAX, max_disappeared=max_gone, probe=probe)
+    live, m = np.array(seen["live"]), np.diff(out["det_off"])
+    assert live.min() > live_above and live.max() <= live_most, f"{name}: {live.min()} .. {live.max()} live tracks"
+    assert m.min() > det_above and m.max() <= det_most, f"{name}: {m.min()} .. {m.max()} detections"
+    issued = int(out["next_id"][-1] - out["next_id"][0])
+    dropped = int(out["next_id"][-1] - live[-1])
+    assert issued >= 20 and dropped >= 20, f"{name}: {issued} ids issued after frame 0, {dropped} tracks deregistered"
+    assert True in seen["mode3"] and len(frames) - 1 - seen["mode3"].index(True) >= 10, f"{name}: too few frames in mode 3"
+    note = f"live {live.min()}..{live.max()} det {m.min()}..{m.max()} issued {issued} dropped {dropped} shadow spread {seen['spread']:.2g}"
+    if name == "tracker_crowded_cells.npz":
+        cells = crowded_cells_of(frames)
+        with_split = sum(1 for s, _ in cells if s)
+        assert 2 * with_split >= len(frames) and any(k for _, k in cells), f"{name}: {cells}"
+        note += f" frames with a split cell {with_split} with a flagged cell {sum(1 for _, k in cells if k)}"
+    print(name, note)
+    out["det_info"] = out["det_info"].astype(np.float32)       # float32-valued: the file stays below the size limit
+    out["info"] = out["info"].astype(np.float32)
+    assert np.array_equal(out["det_info"].astype(np.float64), np.concatenate([i for _, i in frames]))
+    out["max_disappeared"] = np.float64(max_gone)
     return out
 
 
@@ -201,6 +332,10 @@ def main():
     np.savez_compressed(os.path.join(HERE, "tracker_2997.npz"),
                         **run_tracker(tracker_mod, sc, 29.97, True, n_max=None, max_disappeared=6))
     np.savez_compressed(os.path.join(HERE, "propagation.npz"), **propagation_cases(rng))
+    for name in OPERATING_POINT:
+        path = os.path.join(HERE, name)
+        np.savez_compressed(path, **operating_point_fixture(tracker_mod, name))
+        assert os.path.getsize(path) <= 575596, f"{name}: {os.path.getsize(path)} bytes"      # the largest fixture before them
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)))

@@ -23,13 +23,17 @@ def torch_cuda():
 
 
 TRACKER_CASES = [("tracker_small_gsff.npz", None), ("tracker_small_nogsff.npz", None), ("tracker_mid_gsff.npz", None),
-                 ("tracker_gap.npz", 5), ("tracker_2997.npz", 6)]
+                 ("tracker_gap.npz", 5), ("tracker_2997.npz", 6),
+                 # the reference at the link's operating point (they carry their own max_disappeared)
+                 ("tracker_nine_waves.npz", None), ("tracker_twelve_waves.npz", None), ("tracker_crowded_cells.npz", None)]
 
 
 @pytest.mark.parametrize("name,max_gone", TRACKER_CASES)
 def test_centroid_tracker_matches_reference_fixture(torch_cuda, name, max_gone):
     from ysmr_amd.tracker import CentroidTracker
     g = golden(name)
+    if "max_disappeared" in g.files:
+        max_gone = float(g["max_disappeared"])
     fps = float(g["fps"])
     n_max = None if int(g["n_max"]) < 0 else int(g["n_max"])
     ct = CentroidTracker(max_disappeared=fps if max_gone is None else max_gone, fps=fps, n_min=int(g["n_min"]),

@@ -47,7 +47,8 @@ def test_gsff_horizons_and_closed_form(oracle):
 
 
 TRACKER_CASES = ["tracker_small_gsff.npz", "tracker_small_nogsff.npz", "tracker_mid_gsff.npz",
-                 "tracker_gap.npz", "tracker_2997.npz"]
+                 "tracker_gap.npz", "tracker_2997.npz",
+                 "tracker_nine_waves.npz", "tracker_twelve_waves.npz", "tracker_crowded_cells.npz"]
 
 
 @pytest.mark.parametrize("name", TRACKER_CASES)
@@ -55,7 +56,7 @@ def test_tracker_matches_reference(oracle, name):
     g = golden(name)
     fps = float(g["fps"])
     n_max = None if int(g["n_max"]) < 0 else int(g["n_max"])
-    max_gone = {"tracker_gap.npz": 5, "tracker_2997.npz": 6}.get(name, fps)
+    max_gone = float(g["max_disappeared"]) if "max_disappeared" in g.files else {"tracker_gap.npz": 5, "tracker_2997.npz": 6}.get(name, fps)
     tr = oracle.OracleTracker(max_disappeared=max_gone, fps=fps, n_min=int(g["n_min"]), n_max=n_max,
                               n_f=int(g["n_f"]), use_gsff=bool(g["use_gsff"]))
     off, coff = g["off"], g["claim_off"]
@@ -90,3 +91,44 @@ def test_batch_link_clips_reach_the_states_their_gpu_tests_are_about(oracle):
         rows, live, ot = oracle_rows(oracle, frames, use_gsff=not stationary, **kw)
         m = np.array([len(d) for d, _ in frames])
         assert live.max() <= 768 and live.min() > 704 and m.min() > 600 and m.max() <= 768
+
+
+# name: (live tracks: more than, at most), (detections per frame: more than, at most) -- tests/golden/gen_golden.py: OPERATING_POINT
+OPERATING_POINT = {"tracker_nine_waves.npz": ((512, 576), (128, 600)), "tracker_twelve_waves.npz": ((704, 768), (600, 768)),
+                   "tracker_crowded_cells.npz": ((299, 500), (128, 600))}
+
+
+@pytest.mark.parametrize("name", list(OPERATING_POINT))
+def test_operating_point_fixtures_hold_the_states_their_gpu_tests_are_about(name):
+    """The three fixtures that pin the link to the reference at its operating point, from the committed files alone: live
+    tracks (nine waves: 513 .. 576, twelve: 705 .. 768) and detections (twelve waves: more than 600, i.e. 48 cells per side
+    and no candidate lists) in EVERY frame, at least 20 ids issued after frame 0, at least 20 tracks deregistered, at least
+    ten frames after the first in which a track has its third filter (a track of frame 0 that was never dropped has
+    n_i[2] = n_max measurements in its window from frame n_max - n_i[0] on), and for the crowded clip, by the model of
+    k_bgrid's lists (tests/cell_list_model.py), a split cell in at least half of the frames and a cell that stays flagged
+    (the 3 x 3 search) in at least one.  A regenerated fixture cannot quietly move a GPU test off its path."""
+    import cell_list_model as cm
+    g = golden(name)
+    (live_above, live_most), (det_above, det_most) = OPERATING_POINT[name]
+    live, m = np.diff(g["off"]), np.diff(g["det_off"])
+    assert live.min() > live_above and live.max() <= live_most, (live.min(), live.max())
+    assert m.min() > det_above and m.max() <= det_most, (m.min(), m.max())
+    assert bool(g["use_gsff"]) and int(g["n_f"]) == 3 and int(g["n_min"]) == 0 and 3 <= float(g["max_disappeared"]) <= 5
+    assert g["det_info"].dtype == np.float32 and g["info"].dtype == np.float32
+    assert np.array_equal(g["det"], g["det"].astype(np.float32).astype(np.float64))       # what the device is handed
+    next_id = g["next_id"]
+    assert next_id[0] == live[0] and next_id[-1] - next_id[0] >= 20                        # births after frame 0
+    assert next_id[-1] - live[-1] >= 20                                                    # deaths
+    n_max = int(g["n_max"])
+    first_full_bank = n_max - n_max // 3
+    ids = [set(g["ids"][g["off"][f]:g["off"][f + 1]].tolist()) for f in range(len(live))]
+    assert set.intersection(*ids[:first_full_bank + 1]) and len(live) - 1 - first_full_bank >= 10
+    if name == "tracker_crowded_cells.npz":
+        split = flagged = 0
+        for det, _ in tracker_frames(g):
+            grid, order = cm.bin_frame(det)
+            assert cm.has_lists(len(det))
+            lists, _ = cm.frame_lists(grid, det.astype(np.float32)[order])
+            split += bool((lists[:, 0] == cm.SPLIT).any())
+            flagged += bool((lists[:, 0] == cm.FLAG).any())
+        assert 2 * split >= len(live) and flagged >= 1, (split, flagged)

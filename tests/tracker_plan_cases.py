@@ -16,12 +16,20 @@ tests/test_tracker_plan_sanitized.py compares all of it with what tests/tracker_
 tests/test_gpu_link.py creates a handle per case (capacity <= 8192) and asks it.
 
 Gains: "closed" = the library's closed form (gains NULL); "cross" = the closed form with a y column of filter 0's x row set
-(not decoupled); "bent" = the closed form with the oldest x gain of filter 0 moved (decoupled, not affine in the age).
+(not decoupled); "bent" = the closed form with the oldest x gain of filter 0 moved (decoupled, not affine in the age);
+"faint" = "cross" with a term of 1e-300: not decoupled for the plan, which asks whether the term is zero, while no estimate
+changes by a bit (1e-300 times a coordinate is far below half an ulp of the sum it is added to) -- the shape on which the
+reference's fixtures reach the wave path with the reference's own three filters.
+
+The ``fixture_*`` rows are the shapes on which tests/test_gpu_batch_link.py runs the operating-point fixtures of
+tests/golden/ (FIXTURE has their filter bank); their ``fused`` / ``batched`` follow from the path (they were added after
+tracker_plan.h and have no older library to be recorded from).
 """
 DEFAULT = dict(max_disappeared=30.0, fps=30.0, n_min=0, n_max=30.0, n_f=3, use_gsff=1, capacity=768, max_det=2048,
                gains="closed", dims=2, link_mode=0)
 BIG = dict(capacity=2048, max_det=2500)                   # beyond k_frame: the two-launch paths
 D3 = dict(use_gsff=0, dims=3)
+FIXTURE = dict(max_disappeared=3.0, fps=12.0, n_max=12.0)  # tests/golden/tracker_{nine,twelve}_waves.npz (crowded_cells: 4.0)
 
 ALL = "frame lanes batch link_lds"
 ALL3 = "frame lanes batch batch3 link_lds"
@@ -88,7 +96,13 @@ CASES = [
     ("cap_65536_md_65536", dict(capacity=65536, max_det=65536), "lanes", "lanes", False, False, dict(block=102238720)),
     ("cap_65537", dict(capacity=65537), "error:size", "", None, None, {}),
     ("md_65537", dict(max_det=65537), "error:size", "", None, None, {}),
+    # the operating-point fixtures: one launch per batch, per frame, two per frame with a track per lane / per wave
+    ("fixture_batch", dict(FIXTURE), "batch", ALL, False, True, {}),
+    ("fixture_frame", dict(FIXTURE, link_mode=1), "frame", ALL, True, False, {}),
+    ("fixture_lanes", dict(FIXTURE, **BIG), "lanes", "lanes link_lds", False, False, {}),
+    ("fixture_waves", dict(FIXTURE, **BIG, gains="faint"), "waves", "link_lds", False, False, {}),
 ]
+BY_NAME = {c[0]: c for c in CASES}
 
 
 def arguments(changes):
@@ -102,6 +116,8 @@ def perturb_gains(kind, gains):
         gains[1] = 0.01         # filter 0, x row, the y column of the oldest measurement
     elif kind == "bent":
         gains[0] += 0.01        # filter 0, x row, the x column of the oldest measurement
+    elif kind == "faint":
+        gains[1] = 1e-300
     return gains
 
 

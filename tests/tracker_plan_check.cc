@@ -56,6 +56,7 @@ static std::vector<double> case_gains(const std::string &kind, double fps, int n
     for (int i = 0; i < n_f; ++i) { plan::closed_form_gain(n_i[i], g.data() + off); off += 4 * (size_t)n_i[i]; }
     if (kind == "cross") g[1] = 0.01;
     if (kind == "bent") g[0] += 0.01;
+    if (kind == "faint") g[1] = 1e-300;
     return g;
 }
 
