@@ -37,6 +37,10 @@
  *   ysmr_plot_violins                                                          ysmr/track_eval.py:1151-1303
  *   ysmr_rows_columns,    save_list text + get_data (pandas.read_csv) + save_df_to_csv
  *   ysmr_rows_format_csv  ysmr/helper_file.py:1403-1478, 860-905, 1366-1400  (host functions)
+ *   ysmr_csv_parse_typed  get_data (pandas.read_csv with the dtype annotate_video passes) for an `*_analysed.csv`
+ *                         ysmr/helper_file.py:860-905, ysmr/track_eval.py:1354-1369
+ *   ysmr_marks_build,     the table's rows looked up frame by frame (curr_frame_data, one mark per row)
+ *   ysmr_marks_workspace_bytes   ysmr/track_eval.py:1419-1447
  */
 #ifndef YSMR_HIP_H
 #define YSMR_HIP_H
@@ -54,7 +58,7 @@ extern "C" {
 #define YSMR_ERR_CAPACITY  3   /* a fixed-capacity buffer would overflow (tracks, workspace) */
 #define YSMR_ERR_STATE     4   /* handle used in the wrong state */
 
-/* 15 still: ysmr_annotate_batch with its mark struct, and later the ysmr_plot_*, ysmr_mjpeg_*, ysmr_violin_*, ysmr_mjpeg_decode_* and ysmr_view_* functions, were ADDED under this number
+/* 15 still: ysmr_annotate_batch with its mark struct, and later the ysmr_plot_*, ysmr_mjpeg_*, ysmr_violin_*, ysmr_mjpeg_decode_*, ysmr_view_*, ysmr_csv_*, ysmr_table_* and ysmr_marks_* functions, were ADDED under this number
  * -- no existing entry point, struct or constant changed, so every caller written against 15 keeps working; only a caller
  * of a new function needs a library that has it (the loader reports a missing symbol by name). */
 #define YSMR_ABI_VERSION   15
@@ -691,6 +695,46 @@ void   ysmr_table_format_geometry(int *rows_per_group, int *staged_bytes);
 int    ysmr_table_format_devicelike(long long n_rows, int n_columns, const ysmr_table_column *columns, const char *header,
                                     size_t header_bytes, char *out, size_t out_capacity, size_t *out_length, long long *wide_cells);
 int    ysmr_fmt_f64_text(const double *values, long long n, int printer, char *slots, uint8_t *lengths);
+
+/* DEVICE functions (added under ABI 15): the reading direction for 1 .. 16 TYPED columns -- what
+ * pandas.read_csv(usecols, dtype) gives for the columns of an `*_analysed.csv` that annotate_video reads (track_eval.py:1321-1472),
+ * bit for bit.  ysmr_csv_parse_typed runs behind the same ysmr_csv_index call as ysmr_csv_parse, with the same text, workspace,
+ * staged span and line-per-lane layout (a line beyond the staged span is parsed from global memory); ysmr_csv_parse and its
+ * arguments are as they were.  fields: a HOST array of n_fields (1 .. 16) entries; data: DEVICE pointers to n_rows values of the
+ * type, aligned to it (HOST pointers for the _devicelike twin); type: one of YSMR_COL_*; column: the position of the column in the
+ * header, all distinct and below n_columns (1 .. 4096); flags: 0, or YSMR_CSV_EMPTY_IS_NAN on a YSMR_COL_F64 field.
+ * Served (csrc/csv_parse.h): lines of exactly n_columns fields, fields that are not wanted skipped whatever they hold;
+ *   U32  1 .. 10 digits, value <= 2^32 - 1;     I64  -?digits, 1 .. 18 digits;
+ *   I32, I8  -?digits (at most 18 behind leading zeros), the value inside the type;
+ *   F64  as ysmr_csv_parse reads it; with YSMR_CSV_EMPTY_IS_NAN an empty field is served too and is the quiet NaN pandas gives
+ *        (0x7FF8000000000000).
+ * Anything else -- nan, NA, inf, "+1", "1.", a blank, an empty integer field, a value out of range, too few or too many fields --
+ * makes the row unserved: it is counted in *unserved_dev (zeroed by the call), no value of it is written, and the caller reads
+ * the file with pandas.  No byte at or behind n_bytes is read; nothing is written outside n_rows values per field.
+ * ysmr_csv_parse_typed_devicelike: a HOST function, the same text (csrc/csv_parse.h) a line at a time, header line skipped. */
+#define YSMR_CSV_EMPTY_IS_NAN 1
+typedef struct { void *data; int32_t type; int32_t column; int32_t flags; int32_t reserved; } ysmr_csv_field;
+int    ysmr_csv_parse_typed(void *stream, const char *text_dev, size_t n_bytes, const void *workspace_dev, size_t workspace_bytes,
+                            int n_columns, int n_fields, const ysmr_csv_field *fields, long long n_rows, uint32_t *unserved_dev);
+int    ysmr_csv_parse_typed_devicelike(const char *text_host, size_t n_bytes, int n_columns, int n_fields, const ysmr_csv_field *fields,
+                                       long long row_capacity, long long *n_rows, long long *unserved, uint32_t *flags);
+
+/* DEVICE functions (added under ABI 15): the marks of a whole annotated video from the columns of the evaluated table --
+ * annotate.build_marks on the device, the same bytes.  A row is kept if x and y are finite, 0 <= t < n_frames and (with
+ * phenotype_dev) phenotype == subtype; its mark is x, y truncated toward zero and clipped to int32, the 32 bits of the id, style 1
+ * where moving == 0, else 2 where turn_points == 1, else 0 (csrc/marks_rule.h).  marks_dev [n_rows]: the marks ordered by frame
+ * and inside a frame in TABLE order, the entries behind the last mark zeroed; first_dev [n_frames + 1]: first[i] = the marks of
+ * the frames below i -- what ysmr_annotate_batch takes.  Table order is get_data's: sort_rule 0 file order, 1 the table sorted by
+ * (TRACK_ID, POSITION_T) with equal pairs in file order, 2 the latter exactly when rows 0 .. 5 (all rows of a shorter table) hold
+ * pairwise distinct ids -- upstream's rough check, made on the device.  One stable radix sort of the 64-bit key (t << 32 | id)
+ * -- (t << 32) for file order -- with the row number as payload, a gather and a binary search per frame: no atomics, two calls
+ * give the same bytes; asynchronous on `stream`, no host synchronisation inside.
+ * ysmr_marks_workspace_bytes: 0 for what is refused (n_rows outside 0 .. 2^31 - 1, n_frames outside 1 .. 2^31 - 2). */
+size_t ysmr_marks_workspace_bytes(long long n_rows, int n_frames);
+int    ysmr_marks_build(void *stream, long long n_rows, const uint32_t *track_id_dev, const int64_t *t_dev, const double *x_dev,
+                        const double *y_dev, const int8_t *moving_dev, const int8_t *turn_points_dev,
+                        const double *phenotype_dev /* NULL: every subtype */, int subtype, int n_frames, int sort_rule,
+                        void *workspace_dev, size_t workspace_bytes, ysmr_mark *marks_dev /* n_rows */, int64_t *first_dev /* n_frames + 1 */);
 
 /* HOST functions (ABI 13): the same csv and columns worked out WHILE the video runs.  Rows go in as the link emits them -- any
  * number of ysmr_rows_stream_push calls with host rows in any order; a call copies its rows and returns, the stream's threads

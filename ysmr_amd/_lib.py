@@ -71,7 +71,8 @@ EXPORTS = ("ysmr_abi_version", "ysmr_last_error", "ysmr_detect_workspace_bytes",
            "ysmr_csv_workspace_bytes", "ysmr_csv_index", "ysmr_csv_parse", "ysmr_csv_order_workspace_bytes", "ysmr_csv_order",
            "ysmr_csv_geometry", "ysmr_csv_parse_devicelike",
            "ysmr_table_csv_bound", "ysmr_table_format_workspace_bytes", "ysmr_table_format_device", "ysmr_table_format_geometry",
-           "ysmr_table_format_devicelike", "ysmr_fmt_f64_text")
+           "ysmr_table_format_devicelike", "ysmr_fmt_f64_text",
+           "ysmr_csv_parse_typed", "ysmr_csv_parse_typed_devicelike", "ysmr_marks_workspace_bytes", "ysmr_marks_build")
 
 #: column types of ``ysmr_table_format_device`` (include/ysmr_hip.h: YSMR_COL_*), by numpy dtype
 TABLE_COLUMN_TYPES = {np.dtype(np.uint32): 0, np.dtype(np.int64): 1, np.dtype(np.int32): 2, np.dtype(np.int8): 3, np.dtype(np.float64): 4}
@@ -81,6 +82,15 @@ TABLE_MAX_COLUMNS = 16
 class TableColumn(ctypes.Structure):
     """``ysmr_table_column``"""
     _fields_ = [("data", ctypes.c_void_p), ("type", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+#: ``flags`` of a ``ysmr_csv_field`` (YSMR_CSV_EMPTY_IS_NAN): an empty float64 field is served and is NaN
+CSV_EMPTY_IS_NAN = 1
+
+
+class CsvField(ctypes.Structure):
+    """``ysmr_csv_field``"""
+    _fields_ = [("data", ctypes.c_void_p), ("type", ctypes.c_int32), ("column", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
 
 #: numpy view of ``ysmr_mark`` (16 bytes): one track position of one frame of the annotated video
 MARK_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("track_id", "<u4"), ("style", "<u4")])
@@ -307,8 +317,15 @@ def lib():
     L.ysmr_table_format_devicelike.argtypes = [ll, ci, tc, ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
                                                ctypes.POINTER(ll)]
     L.ysmr_fmt_f64_text.argtypes = [vp, ll, ci, vp, vp]
+    cf = ctypes.POINTER(CsvField)
+    L.ysmr_csv_parse_typed.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ci, ci, cf, ll, vp]
+    L.ysmr_csv_parse_typed_devicelike.argtypes = [vp, ctypes.c_size_t, ci, ci, cf, ll, ctypes.POINTER(ll), ctypes.POINTER(ll),
+                                                  ctypes.POINTER(ctypes.c_uint32)]
+    L.ysmr_marks_workspace_bytes.argtypes = [ll, ci]
+    L.ysmr_marks_workspace_bytes.restype = ctypes.c_size_t
+    L.ysmr_marks_build.argtypes = [vp, ll] + [vp] * 7 + [ci, ci, ci, vp, ctypes.c_size_t, vp, vp]
     for name in EXPORTS:
-        if name not in ("ysmr_table_csv_bound", "ysmr_table_format_workspace_bytes", "ysmr_table_format_geometry", "ysmr_csv_workspace_bytes", "ysmr_csv_order_workspace_bytes", "ysmr_csv_geometry", "ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_png_dynamic_workspace_bytes", "ysmr_png_dynamic_stream_bytes_max", "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_sync_geometry", "ysmr_mjpeg_decode_workspace_bytes", "ysmr_violin_workspace_bytes", "ysmr_mjpeg_workspace_bytes", "ysmr_mjpeg_encode_workspace_bytes", "ysmr_plot_workspace_bytes", "ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
+        if name not in ("ysmr_table_csv_bound", "ysmr_table_format_workspace_bytes", "ysmr_table_format_geometry", "ysmr_csv_workspace_bytes", "ysmr_csv_order_workspace_bytes", "ysmr_marks_workspace_bytes", "ysmr_csv_geometry", "ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_png_dynamic_workspace_bytes", "ysmr_png_dynamic_stream_bytes_max", "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_sync_geometry", "ysmr_mjpeg_decode_workspace_bytes", "ysmr_violin_workspace_bytes", "ysmr_mjpeg_workspace_bytes", "ysmr_mjpeg_encode_workspace_bytes", "ysmr_plot_workspace_bytes", "ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
                         "ysmr_rows_sort_workspace_bytes", "ysmr_rows_csv_bound", "ysmr_rows_stream_count",
                         "ysmr_mean_threshold_state_bytes"):
             getattr(L, name).restype = ci

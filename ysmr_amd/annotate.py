@@ -48,7 +48,7 @@ from . import _lib
 from .frames import DeviceFrameFeed, decode_mjpeg_setting, open_video
 from .helper_file import create_results_folder, get_configs, get_data, get_loggers
 
-__all__ = ["annotate_video", "AviWriter", "MjpegAviWriter", "DibOutput", "output_format", "jpeg_mode", "build_marks", "subtype_code", "SUBTYPES"]
+__all__ = ["annotate_video", "AviWriter", "MjpegAviWriter", "DibOutput", "output_format", "jpeg_mode", "build_marks", "build_marks_device", "LAST_MARKS", "subtype_code", "SUBTYPES"]
 
 SUBTYPES = ("immotile", "twitching", "motile")
 #: one pinned output buffer (there are two) holds at most this many bytes
@@ -389,6 +389,59 @@ def _csv_table(path, logger, settings):
     return get_data(path, dtype=dtype)
 
 
+#: which way the marks of the last ``annotate_video`` call came: "device" (csv read and marks built on the GPU), "host" (the
+#: csv through pandas and ``build_marks``) or "frame" (a DataFrame argument); the rows of the table and the marks they gave
+LAST_MARKS = {}
+#: (diagnostics) seconds since ``annotate_video`` began at which its marks were on the device
+LAST_MARKS_TIMES = {}
+
+
+def _csv_fields(select_subtype):
+    """The columns ``_csv_table`` reads, as the typed device reader takes them.  TRACK_ID as uint32: an id beyond it sends
+    the file to pandas.  motility_phenotype only where it is looked at (its name has to be in the header either way)."""
+    fields = [("TRACK_ID", np.uint32), ("POSITION_T", np.int64), ("POSITION_X", np.float64, True), ("POSITION_Y", np.float64, True),
+              ("moving", np.int8), ("turn_points", np.int8)]
+    if select_subtype is not None:
+        fields.append(("motility_phenotype", np.float64, True))
+    return fields
+
+
+def build_marks_device(columns, n_rows, n_frames, select_subtype=None, sort_rule=2, device="cuda:0"):
+    """``build_marks`` on the device (``ysmr_marks_build``, csrc/marks.hip): ``columns`` name -> tensor on ``device`` with
+    TRACK_ID (32-bit), POSITION_T (int64), POSITION_X / POSITION_Y (float64), moving / turn_points (int8) and, with
+    ``select_subtype``, motility_phenotype (float64, NaN where it is empty) -- what ``read_typed_device`` gives for
+    ``_csv_fields``.  ``sort_rule``: what "table order" means -- 0 the order of the rows, 1 sorted by (TRACK_ID, POSITION_T),
+    2 (``get_data``'s) the latter when upstream's rough check on the first six ids says so.  Returns ``(marks_dev,
+    first_dev)``: uint8 [16 * n_rows] holding the marks (zeros behind the last one) and int64 [n_frames + 1], the same bytes
+    as ``build_marks``' arrays; None where the library refuses the sizes.  Nothing waits for the device."""
+    import torch
+    L = _lib.lib()
+    dev = torch.device(device)
+    n_rows, n_frames = int(n_rows), int(n_frames)
+    subtype = -1 if select_subtype is None else subtype_code(select_subtype)
+    ws_bytes = int(L.ysmr_marks_workspace_bytes(n_rows, n_frames)) if 0 < n_frames < 2 ** 31 else 0
+    if ws_bytes == 0:
+        return None
+    wanted = {"TRACK_ID": 4, "POSITION_T": 8, "POSITION_X": 8, "POSITION_Y": 8, "moving": 1, "turn_points": 1}
+    if select_subtype is not None:
+        wanted["motility_phenotype"] = 8
+    pointers = []
+    for name, size in wanted.items():
+        col = columns[name]
+        if col.device != dev or not col.is_contiguous() or col.element_size() != size or col.numel() < n_rows:
+            raise ValueError("column {!r}: {} contiguous values of {} bytes on {} are needed".format(name, n_rows, size, dev))
+        pointers.append(col.data_ptr() if n_rows else 0)
+    if select_subtype is None:
+        pointers.append(0)
+    with _lib.on(dev):
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        marks_dev = torch.empty(max(16 * n_rows, 16), dtype=torch.uint8, device=dev)
+        first_dev = torch.empty(n_frames + 1, dtype=torch.int64, device=dev)
+        _lib.check(L.ysmr_marks_build(_lib.stream_ptr(dev), n_rows, *pointers, subtype, n_frames, int(sort_rule), ws.data_ptr(), ws_bytes,
+                                      marks_dev.data_ptr(), first_dev.data_ptr()), "ysmr_marks_build")
+    return marks_dev, first_dev
+
+
 class DibOutput:
     """The way of painted frames from the device to the file, for ``annotate_video`` and for the detection view of
     ``track_bacteria``: two slots, each a device buffer of ``batch`` stored DIB frames and a pinned host buffer, a copy
@@ -570,9 +623,16 @@ def annotate_video(video_path, df, output_save=True, settings=None, result_folde
     the free space is then checked batch by batch, against the bytes about to be written), 'hip video jpeg subsampling'
     ('4:4:4' / '4:2:2' / '4:2:0') and 'hip video jpeg huffman' ('standard' / 'optimised') its chroma subsampling and
     whether every frame carries Huffman tables of its own (``jpeg_mode``); 'hip decode mjpeg' (True /
-    'always' / False) says whether a Motion-JPEG INPUT is decoded on the device, as in ``track_bacteria``."""
+    'always' / False) says whether a Motion-JPEG INPUT is decoded on the device, as in ``track_bacteria``; a true 'hip read
+    csv on device' reads a csv ``df`` and builds its marks on the device (``read_typed_device``, ``build_marks_device``) --
+    the same file; a csv the device reader does not serve is read by pandas as without the key.  ``LAST_MARKS`` says which
+    way the call went."""
+    import time
     import pandas as pd
     import torch
+    started = time.perf_counter()
+    LAST_MARKS.clear()
+    LAST_MARKS_TIMES.clear()
     logger = logging.getLogger("ysmr").getChild(__name__)
     settings = get_configs(settings)
     if settings is None:
@@ -594,10 +654,32 @@ def annotate_video(video_path, df, output_save=True, settings=None, result_folde
         if not result_folder:
             result_folder = create_results_folder(video_path)
         os.makedirs(result_folder, exist_ok=True)
+        csv_path = typed = None
         if not isinstance(df, pd.DataFrame):
-            df = _csv_table(df, logger, settings)
-            if df is None:
-                return None
+            csv_path = df
+            if settings.get("hip read csv on device"):
+                # (a file the device reader does not serve is read by pandas, here, as without the key)
+                from .helper_file import read_typed_device
+                typed = read_typed_device(csv_path, _csv_fields(select_subtype), torch.device(device), also_in_header=("motility_phenotype",))
+                typed = typed if typed.path_taken == "device" else None
+            if typed is None:
+                df = _csv_table(csv_path, logger, settings)
+                if df is None:
+                    return None
+
+        def table_marks():
+            """(marks, first) of the table: tensors from the device path, arrays from the host's; None as ``_csv_table``."""
+            nonlocal df
+            if typed is not None:
+                built = build_marks_device(typed.columns, typed.n_rows, n_frames, select_subtype, sort_rule=2, device=dev)
+                if built is not None:
+                    LAST_MARKS.update(path="device", rows=typed.n_rows)
+                    return built
+                df = _csv_table(csv_path, logger, settings)
+                if df is None:
+                    return None
+            LAST_MARKS.update(path="frame" if csv_path is None else "host", rows=len(df))
+            return build_marks(df, n_frames, select_subtype)
         fps_of_file = video.fps
         if not fps_of_file or not fps_of_file > 0:
             if settings["frames per second"] <= 0:
@@ -628,7 +710,9 @@ def annotate_video(video_path, df, output_save=True, settings=None, result_folde
         dev = torch.device(device)
         L = _lib.lib()
         if fmt == "mjpeg":
-            marks, first = build_marks(df, n_frames, select_subtype)
+            built = table_marks()
+            if built is None:
+                return None
             writer = MjpegAviWriter(output_video_name, width, height, fps_of_file)
             mode = jpeg_mode(settings)
             logger.info("Annotated video {}: {} frames of {} x {}, Motion-JPEG, quality {}{}".format(
@@ -642,7 +726,9 @@ def annotate_video(video_path, df, output_save=True, settings=None, result_folde
                 output_video_name, n_frames, width, height, expected / 2 ** 20))
             if not enough_space(result_folder, expected, "annotated video", logger):
                 return None
-            marks, first = build_marks(df, n_frames, select_subtype)
+            built = table_marks()
+            if built is None:
+                return None
             writer = AviWriter(output_video_name, width, height, fps_of_file)
             batch = int(settings.get("hip frames per batch") or 0) or auto_batch(writer.frame_bytes + 8, n_frames)
             batch = max(1, min(batch, auto_batch(writer.frame_bytes + 8, n_frames)))
@@ -650,9 +736,16 @@ def annotate_video(video_path, df, output_save=True, settings=None, result_folde
         done = 0
         try:
             with _lib.on(dev):
-                marks_dev = torch.from_numpy(marks.view(np.uint8).reshape(-1)).to(dev) if len(marks) else \
-                    torch.zeros(16, dtype=torch.uint8, device=dev)
-                first_dev = torch.from_numpy(first).to(dev)
+                if LAST_MARKS["path"] == "device":
+                    marks_dev, first_dev = built
+                    LAST_MARKS["marks"] = int(first_dev[-1:].cpu()[0])
+                else:
+                    marks, first = built
+                    marks_dev = torch.from_numpy(marks.view(np.uint8).reshape(-1)).to(dev) if len(marks) else \
+                        torch.zeros(16, dtype=torch.uint8, device=dev)
+                    first_dev = torch.from_numpy(first).to(dev)
+                    LAST_MARKS["marks"] = len(marks)
+                LAST_MARKS_TIMES["marks on device"] = time.perf_counter() - started
                 feed = DeviceFrameFeed(video, batch, dev, depth=2, decode_on_device=decode_mjpeg_setting(settings))
                 for frames_dev, f0, n, slot in feed:
                     n = min(n, n_frames - f0)

@@ -7,6 +7,8 @@
 //   ysmr_csv_parse   a line per lane; a workgroup's lines are one contiguous span, staged into LDS with 16-byte loads and
 //                    parsed from there.  What lies beyond the staged span (a long line, through skipped columns) is PARSED
 //                    FROM GLOBAL MEMORY, byte by byte: it comes out right, only slower
+//   ysmr_csv_parse_typed  the same behind the same index, for 1 .. 16 columns of the table writer's five types (uint32, int64,
+//                    int32, int8, float64 with an empty field as NaN on request): what annotate_video reads of an `*_analysed.csv`
 //   ysmr_csv_order   stable radix sort of (TRACK_ID << 32 | POSITION_T) with the row number as payload (prim.h), then a gather
 //                    of the seven columns
 #include <hip/hip_runtime.h>
@@ -190,6 +192,54 @@ __global__ __launch_bounds__(256) void k_csv_parse(const unsigned char *__restri
     if ((threadIdx.x & 63) == 0 && bad) atomicAdd(unserved, (uint32_t)__popcll(bad));
 }
 
+struct TypedColumns { void *data[ysmr_csv::MAX_FIELDS]; };
+
+// k_csv_parse for 1 .. 16 typed columns (csv_parse.h: parse_line_typed): the same grid, staging and line-per-lane layout.
+// A served row's fields go out in the order of the plan, each a coalesced store of its own width
+__global__ __launch_bounds__(256) void k_csv_parse_typed(const unsigned char *__restrict__ text, uint32_t n_bytes,
+                                                         const uint32_t *__restrict__ starts, const uint32_t *__restrict__ meta,
+                                                         int n_columns, ysmr_csv::TypedPlan plan, uint32_t n_rows, TypedColumns cols,
+                                                         uint32_t *unserved)
+{
+    __shared__ uint4 s_text[STAGED_SPAN / 16];
+    const uint32_t lines = meta[1];
+    const uint32_t r0 = blockIdx.x * 256u;
+    const uint32_t here = min(256u, n_rows - r0);
+    const uint32_t known = r0 + 1u < lines ? min(here, lines - 1u - r0) : 0u;
+    uint32_t a0 = 0u;
+    if (known) {
+        const uint32_t span0 = starts[r0 + 1u], span1 = min(starts[r0 + known + 1u] - 1u, n_bytes);
+        a0 = span0 & ~15u;
+        const uint32_t stop = min(span1, a0 + (uint32_t)STAGED_SPAN);
+        for (uint32_t i = threadIdx.x; a0 + 16u * i < stop && i < (uint32_t)(STAGED_SPAN / 16); i += 256u) {
+            const uint32_t pos = a0 + 16u * i;
+            if (pos + 16u <= n_bytes) s_text[i] = *(const uint4 *)(text + pos);
+            else
+                for (uint32_t k = 0; pos + k < n_bytes; ++k) ((unsigned char *)s_text)[16u * i + k] = text[pos + k];
+        }
+    }
+    __syncthreads();
+    bool ok = false;
+    const uint32_t row = r0 + threadIdx.x;
+    if (threadIdx.x < here) {
+        ysmr_csv::TypedRow out;
+        if (threadIdx.x < known) {
+            const uint32_t begin = starts[row + 1u], next = starts[row + 2u];
+            if (next > begin && next - 1u <= n_bytes) {
+                const StagedText at{(const unsigned char *)s_text, text, a0};
+                ok = ysmr_csv::parse_line_typed(at, (long long)begin, (long long)(next - 1u), n_columns, plan, out);
+            }
+        }
+        if (ok) {
+#pragma unroll
+            for (int k = 0; k < ysmr_csv::MAX_FIELDS; ++k)
+                if (k < plan.n_fields) ysmr_csv::store_typed(cols.data[k], plan.type[k], (long long)row, out.bits[k]);
+        }
+    }
+    const unsigned long long bad = __ballot(threadIdx.x < here && !ok);
+    if ((threadIdx.x & 63) == 0 && bad) atomicAdd(unserved, (uint32_t)__popcll(bad));
+}
+
 __global__ __launch_bounds__(256) void k_csv_keys(const uint32_t *__restrict__ id, const uint32_t *__restrict__ t, long long n,
                                                   unsigned long long *__restrict__ keys, uint32_t *__restrict__ idx)
 {
@@ -225,6 +275,35 @@ bool wanted_of(int n_columns, const int32_t *wanted, ysmr_csv::Wanted &w)
         w.column[k] = wanted[k];
     }
     return true;
+}
+
+static_assert(csvp::MAX_COLUMNS == ysmr_csv::MAX_COLUMNS && csvp::MAX_FIELDS == ysmr_csv::MAX_FIELDS && csvp::FIELD_F64 == ysmr_csv::TYPE_F64 &&
+              csvp::FIELD_EMPTY_IS_NAN == ysmr_csv::TYPED_EMPTY_IS_NAN && YSMR_CSV_EMPTY_IS_NAN == ysmr_csv::TYPED_EMPTY_IS_NAN &&
+              YSMR_COL_U32 == ysmr_csv::TYPE_U32 && YSMR_COL_I64 == ysmr_csv::TYPE_I64 && YSMR_COL_I32 == ysmr_csv::TYPE_I32 &&
+              YSMR_COL_I8 == ysmr_csv::TYPE_I8 && YSMR_COL_F64 == ysmr_csv::TYPE_F64, "csv_plan.h, csv_parse.h and ysmr_hip.h name the same types");
+
+// the caller's fields -> the plan and the columns in the order of the plan; NULL, or what is wrong with them
+const char *typed_plan_of(int n_columns, int n_fields, const ysmr_csv_field *fields, bool need_data, ysmr_csv::TypedPlan &plan, TypedColumns &cols)
+{
+    if (!fields) return "fields must be set";
+    if (n_fields < 1 || n_fields > ysmr_csv::MAX_FIELDS) return "n_fields must be in 1..16 and at most n_columns";
+    int32_t type[ysmr_csv::MAX_FIELDS], column[ysmr_csv::MAX_FIELDS], flags[ysmr_csv::MAX_FIELDS];
+    int order[ysmr_csv::MAX_FIELDS];
+    for (int k = 0; k < n_fields; ++k) { type[k] = fields[k].type; column[k] = fields[k].column; flags[k] = fields[k].flags; }
+    if (const char *why = csvp::typed_fields_rule(n_columns, n_fields, type, column, flags, order)) return why;
+    plan = ysmr_csv::TypedPlan{};
+    cols = TypedColumns{};
+    plan.n_fields = n_fields;
+    for (int k = 0; k < n_fields; ++k) {
+        const ysmr_csv_field &f = fields[order[k]];
+        const uintptr_t align = f.type == YSMR_COL_I8 ? 1u : f.type == YSMR_COL_U32 || f.type == YSMR_COL_I32 ? 4u : 8u;
+        if (need_data && (!f.data || ((uintptr_t)f.data & (align - 1u)))) return "every field's data must be set and aligned to its type";
+        plan.column[k] = f.column;
+        plan.type[k] = (uint8_t)f.type;
+        plan.flags[k] = (uint8_t)f.flags;
+        cols.data[k] = f.data;
+    }
+    return nullptr;
 }
 
 }  // namespace
@@ -355,6 +434,67 @@ int ysmr_csv_parse_devicelike(const char *text_host, size_t n_bytes, int n_colum
             if (ysmr_csv::parse_line(at, (long long)begin, (long long)end, n_columns, wnt, out)) {
                 track_id[rows] = out.id; t[rows] = out.t;
                 for (int k = 0; k < 5; ++k) v[k][rows] = out.v[k];
+            } else ++bad;
+            ++rows;
+        }
+        ++line;
+        begin = end + 1;
+    }
+    *n_rows = rows;
+    *unserved = bad;
+    return YSMR_OK;
+}
+
+int ysmr_csv_parse_typed(void *stream, const char *text_dev, size_t n_bytes, const void *workspace_dev, size_t workspace_bytes,
+                         int n_columns, int n_fields, const ysmr_csv_field *fields, long long n_rows, uint32_t *unserved_dev)
+{
+    csvp::Plan p;
+    if (!csvp::plan_of(n_bytes, p)) return ysmr::fail(YSMR_ERR_ARG, "n_bytes must be in 1..%zu, got %zu", csvp::MAX_BYTES, n_bytes);
+    if (n_rows < 0 || (unsigned long long)n_rows + 2ull > p.line_capacity)
+        return ysmr::fail(YSMR_ERR_ARG, "n_rows must be in 0..%zu for %zu bytes of text, got %lld", p.line_capacity - 2, n_bytes, n_rows);
+    ysmr_csv::TypedPlan plan;
+    TypedColumns cols;
+    if (const char *why = typed_plan_of(n_columns, n_fields, fields, n_rows > 0, plan, cols))
+        return ysmr::fail(YSMR_ERR_ARG, "%s (n_columns %d, n_fields %d)", why, n_columns, n_fields);
+    if (!unserved_dev) return ysmr::fail(YSMR_ERR_ARG, "unserved_dev must be set");
+    hipStream_t st = (hipStream_t)stream;
+    YSMR_HIP_CHECK(hipMemsetAsync(unserved_dev, 0, sizeof(uint32_t), st));
+    if (n_rows == 0) return YSMR_OK;
+    if (!text_dev || !workspace_dev) return ysmr::fail(YSMR_ERR_ARG, "text_dev and workspace_dev must be set");
+    if (((uintptr_t)text_dev & 15u) || ((uintptr_t)workspace_dev & 15u)) return ysmr::fail(YSMR_ERR_ARG, "text_dev and workspace_dev must be 16-byte aligned");
+    if (workspace_bytes < p.total) return ysmr::fail(YSMR_ERR_CAPACITY, "csv workspace too small: %zu < %zu bytes", workspace_bytes, p.total);
+    const char *w = (const char *)workspace_dev;
+    hipLaunchKernelGGL(k_csv_parse_typed, dim3(csvp::parse_groups(n_rows)), dim3(256), 0, st, (const unsigned char *)text_dev, (uint32_t)n_bytes,
+                       (const uint32_t *)(w + p.starts), (const uint32_t *)(w + p.meta), n_columns, plan, (uint32_t)n_rows, cols, unserved_dev);
+    YSMR_LAUNCH_CHECK();
+    return YSMR_OK;
+}
+
+int ysmr_csv_parse_typed_devicelike(const char *text_host, size_t n_bytes, int n_columns, int n_fields, const ysmr_csv_field *fields,
+                                    long long row_capacity, long long *n_rows, long long *unserved, uint32_t *flags)
+{
+    if (!text_host || n_bytes == 0 || n_bytes > csvp::MAX_BYTES || !n_rows || !unserved || !flags || row_capacity < 0)
+        return ysmr::fail(YSMR_ERR_ARG, "text_host (1..%zu bytes), n_rows, unserved and flags must be set", csvp::MAX_BYTES);
+    ysmr_csv::TypedPlan plan;
+    TypedColumns cols;
+    if (const char *why = typed_plan_of(n_columns, n_fields, fields, row_capacity > 0, plan, cols))
+        return ysmr::fail(YSMR_ERR_ARG, "%s (n_columns %d, n_fields %d)", why, n_columns, n_fields);
+    const unsigned char *s = (const unsigned char *)text_host;
+    uint32_t f = 0;
+    for (size_t i = 0; i < n_bytes; ++i)
+        f |= (s[i] == '"' ? ysmr_csv::FLAG_QUOTE : 0u) | (s[i] == '\r' ? ysmr_csv::FLAG_CR : 0u) | (s[i] == 0 || s[i] >= 0x80 ? ysmr_csv::FLAG_NOT_PLAIN : 0u);
+    *flags = f;
+    const HostText at{s};
+    long long line = 0, rows = 0, bad = 0;
+    size_t begin = 0;
+    while (begin < n_bytes) {
+        const void *nl = std::memchr(s + begin, '\n', n_bytes - begin);
+        const size_t end = nl ? (size_t)((const unsigned char *)nl - s) : n_bytes;
+        if (line > 0) {
+            if (rows >= row_capacity) return ysmr::fail(YSMR_ERR_CAPACITY, "more than %lld rows", row_capacity);
+            ysmr_csv::TypedRow out;
+            if (ysmr_csv::parse_line_typed(at, (long long)begin, (long long)end, n_columns, plan, out)) {
+                for (int k = 0; k < plan.n_fields; ++k) ysmr_csv::store_typed(cols.data[k], plan.type[k], rows, out.bits[k]);
             } else ++bad;
             ++rows;
         }

@@ -179,4 +179,111 @@ YSMR_FMT_HD bool parse_line(const Fetch &at, long long begin, long long end, int
     return true;
 }
 
+// ---- the typed parse: 1 .. 16 wanted columns of the table writer's five types (ysmr_csv_parse_typed, csv.hip) ----------------
+// What pandas.read_csv(usecols, dtype) gives for a line, for the dtypes uint32 / int64 / int32 / int8 / float64:
+//   * U32: parse_u32 above;
+//   * I64: -?digits, 1 .. 18 digits in all; I32, I8: -?digits with at most 18 digits behind the leading zeros, the value
+//     inside the type;
+//   * F64: parse_f64 above; with TYPED_EMPTY_IS_NAN an empty field is served too and is the quiet NaN pandas gives it.
+// Everything else (see the head of this file; an empty integer field, a value out of range) is not served.
+constexpr int MAX_FIELDS = 16;
+constexpr int TYPE_U32 = 0, TYPE_I64 = 1, TYPE_I32 = 2, TYPE_I8 = 3, TYPE_F64 = 4;      // YSMR_COL_* of include/ysmr_hip.h
+constexpr int TYPED_EMPTY_IS_NAN = 1;                                                  // YSMR_CSV_EMPTY_IS_NAN
+constexpr uint64_t QUIET_NAN = 0x7FF8000000000000ull;
+
+// the wanted fields in the order of their columns: all lanes of a wave look at column `col` in the same iteration, so
+// "is this column wanted, and as what" is one compare with the next wanted position, the same for every lane
+struct TypedPlan {
+    int32_t n_fields;
+    int32_t column[MAX_FIELDS];         // ascending
+    uint8_t type[MAX_FIELDS], flags[MAX_FIELDS];
+};
+struct TypedRow { uint64_t bits[MAX_FIELDS]; };     // field k's value in the low bytes of bits[k], in the order of the plan
+
+// -?digits at [p, end): at most max_digits digits (behind the leading zeros if zeros_free), lo <= value <= hi
+template <class Fetch>
+YSMR_FMT_HD long long parse_int(const Fetch &at, long long p, long long end, int max_digits, bool zeros_free, int64_t lo, int64_t hi,
+                                int64_t &out)
+{
+    bool neg = false;
+    if (p < end && at(p) == '-') { neg = true; ++p; }
+    int64_t v = 0;
+    int nd = 0, any = 0;
+    while (p < end) {
+        const int c = at(p);
+        if (!is_digit(c)) break;
+        any = 1;
+        if (!(zeros_free && nd == 0 && c == '0') && ++nd > max_digits) return -1;
+        v = v * 10 + (int64_t)(c - '0');             // (18 digits: below 2^63)
+        ++p;
+    }
+    if (!any) return -1;
+    if (p < end && at(p) != ',') return -1;
+    if (neg) v = -v;
+    if (v < lo || v > hi) return -1;
+    out = v;
+    return p;
+}
+
+// The line [begin, end) (without its '\n').  true: served, row.bits[k] holds field k for every k < plan.n_fields.
+template <class Fetch>
+YSMR_FMT_HD bool parse_line_typed(const Fetch &at, long long begin, long long end, int n_columns, const TypedPlan &plan, TypedRow &row)
+{
+    if (end <= begin) return false;                               // an empty line
+    long long p = begin;
+    uint64_t v[MAX_FIELDS];
+#pragma unroll
+    for (int k = 0; k < MAX_FIELDS; ++k) v[k] = 0;
+    int next = 0, want = plan.column[0];
+    for (int col = 0; col < n_columns; ++col) {
+        if (col) {
+            if (p >= end) return false;                           // too few fields
+            ++p;                                                  // (the ',' the field before stopped at)
+        }
+        if (col != want) {
+            while (p < end && at(p) != ',') ++p;
+            continue;
+        }
+        const int type = plan.type[next];
+        uint64_t bits = 0;
+        if (type == TYPE_F64) {
+            if ((plan.flags[next] & TYPED_EMPTY_IS_NAN) && (p >= end || at(p) == ',')) bits = QUIET_NAN;
+            else {
+                union { double d; uint64_t u; } u;
+                u.d = 0.0;
+                p = parse_f64(at, p, end, u.d);
+                bits = u.u;
+            }
+        } else if (type == TYPE_U32) {
+            uint32_t u = 0;
+            p = parse_u32(at, p, end, u);
+            bits = u;
+        } else {
+            int64_t i = 0;
+            if (type == TYPE_I64) p = parse_int(at, p, end, 18, false, INT64_MIN, INT64_MAX, i);
+            else if (type == TYPE_I32) p = parse_int(at, p, end, 18, true, INT32_MIN, INT32_MAX, i);
+            else p = parse_int(at, p, end, 18, true, INT8_MIN, INT8_MAX, i);
+            bits = (uint64_t)i;
+        }
+        if (p < 0) return false;
+        // (no indexing by `next`: on the device the values stay in registers)
+#pragma unroll
+        for (int k = 0; k < MAX_FIELDS; ++k) v[k] = next == k ? bits : v[k];
+        ++next;
+        want = next < plan.n_fields ? plan.column[next] : -1;
+    }
+    if (p != end) return false;                                   // too many fields
+#pragma unroll
+    for (int k = 0; k < MAX_FIELDS; ++k) row.bits[k] = v[k];
+    return true;
+}
+
+// field k of a served row into its column
+YSMR_FMT_HD void store_typed(void *data, int type, long long r, uint64_t bits)
+{
+    if (type == TYPE_F64 || type == TYPE_I64) ((uint64_t *)data)[r] = bits;
+    else if (type == TYPE_I8) ((int8_t *)data)[r] = (int8_t)bits;
+    else ((uint32_t *)data)[r] = (uint32_t)bits;
+}
+
 }  // namespace ysmr_csv

@@ -90,6 +90,28 @@ inline bool order_plan_of(long long n_rows, OrderPlan &p)
     return fits;
 }
 
+// ---- the typed parse: the rules of its field list ----------------------------------------------------------------------------
+constexpr int MAX_COLUMNS = 4096, MAX_FIELDS = 16, FIELD_TYPES = 5, FIELD_F64 = 4, FIELD_EMPTY_IS_NAN = 1;   // (csv.hip asserts them)
+
+// NULL and order[0 .. n_fields): the fields by ascending column -- or what is wrong with the list.  type / column / flags: one
+// entry per field.
+inline const char *typed_fields_rule(int n_columns, int n_fields, const int32_t *type, const int32_t *column, const int32_t *flags,
+                                     int *order)
+{
+    if (n_columns < 1 || n_columns > MAX_COLUMNS) return "n_columns must be in 1..4096";
+    if (n_fields < 1 || n_fields > MAX_FIELDS || n_fields > n_columns) return "n_fields must be in 1..16 and at most n_columns";
+    for (int k = 0; k < n_fields; ++k) {
+        if (type[k] < 0 || type[k] >= FIELD_TYPES) return "a field's type must be one of YSMR_COL_U32 / I64 / I32 / I8 / F64";
+        if (column[k] < 0 || column[k] >= n_columns) return "a field's column must be below n_columns";
+        if ((flags[k] & ~FIELD_EMPTY_IS_NAN) || (flags[k] && type[k] != FIELD_F64)) return "a field's flags: YSMR_CSV_EMPTY_IS_NAN, on YSMR_COL_F64 only";
+        int at = k;                                   // insertion by column
+        for (; at > 0 && column[order[at - 1]] > column[k]; --at) order[at] = order[at - 1];
+        if (at > 0 && column[order[at - 1]] == column[k]) return "the fields' columns must be distinct";
+        order[at] = k;
+    }
+    return nullptr;
+}
+
 // the grid of the parse: a workgroup per ROWS_PER_GROUP lines
 inline unsigned parse_groups(long long n_rows) { return (unsigned)((n_rows + ROWS_PER_GROUP - 1) / ROWS_PER_GROUP); }
 

@@ -245,7 +245,8 @@ def get_configs(tracking_ini_filepath=None):
 
     Keys that tracking.ini does not know are opt-in switches of this package, set in a settings dict and read with
     ``settings.get`` (absent: the path runs as it always has): ``'hip read csv on device'`` -- ``select_tracks`` and
-    ``evaluate_tracks`` read their csv through :func:`read_table_device`; ``'hip write csv on device'`` -- they write
+    ``evaluate_tracks`` read their csv through :func:`read_table_device`, ``annotate_video`` reads an ``*_analysed.csv``
+    through :func:`read_typed_device` and builds its marks on the device; ``'hip write csv on device'`` -- they write
     ``<name>_selected_data.csv`` and ``<name>_analysed.csv`` through :func:`write_table_device` (the same bytes;
     ``<name>_statistics.csv``, one row per track, stays with pandas); ``'hip png on device'`` and ``'hip violin plots'`` -- the
     figures (``evaluate.py``, ``plot_functions.py``)."""
@@ -851,6 +852,151 @@ def read_table_device(path, device="cuda:0", check_sorted=True, sync_phases=Fals
                 torch.cuda.current_stream(dev).synchronize()
             marks["order"] = time.perf_counter() - t0
     return DeviceTable("device", n_rows=n, columns=_split_columns(buf, n) if n else None, positions=positions, device=dev, buffer=buf)
+
+
+def csv_typed_plan(header_line, names):
+    """The header line of a csv (bytes, without its newline) -> ``(n_columns, positions)``: the position of each of ``names``,
+    in their order.  ``csv_header_plan``'s rules for any list of names: None where a name is missing or there twice, the
+    bytes are not ASCII, or the header holds more than 4096 names."""
+    try:
+        header = bytes(header_line).decode("ascii").split(",")
+    except UnicodeDecodeError:
+        return None
+    names = list(names)
+    if not 1 <= len(header) <= 4096 or not names or len(set(names)) != len(names) or any(header.count(k) != 1 for k in names):
+        return None
+    return len(header), [header.index(k) for k in names]
+
+
+def _typed_fields(fields):
+    """``fields``: (name, dtype) or (name, dtype, empty_is_nan) each -> [(name, numpy dtype, type code, flags)]."""
+    from . import _lib
+    out = []
+    for field in fields:
+        name, dtype = field[0], np.dtype(field[1])
+        if dtype not in _lib.TABLE_COLUMN_TYPES:
+            raise ValueError("column {!r}: the typed csv reader has uint32, int64, int32, int8 and float64, not {}".format(name, dtype))
+        nan = len(field) > 2 and bool(field[2])
+        if nan and dtype != np.float64:
+            raise ValueError("column {!r}: only a float64 column reads an empty field as NaN".format(name))
+        out.append((name, dtype, _lib.TABLE_COLUMN_TYPES[dtype], _lib.CSV_EMPTY_IS_NAN if nan else 0))
+    if not 1 <= len(out) <= _lib.TABLE_MAX_COLUMNS:
+        raise ValueError("the typed csv reader takes 1 .. {} columns, got {}".format(_lib.TABLE_MAX_COLUMNS, len(out)))
+    return out
+
+
+def _csv_field_array(fields, positions, pointers):
+    from . import _lib
+    arr = (_lib.CsvField * len(fields))()
+    for k, (_name, _dtype, code, flags) in enumerate(fields):
+        arr[k].data, arr[k].type, arr[k].column, arr[k].flags = pointers[k], code, positions[k], flags
+    return arr
+
+
+def parse_csv_typed_devicelike(data, fields):
+    """``ysmr_csv_parse_typed_devicelike`` on the bytes of a csv: the arithmetic of the typed device reader (csrc/csv_parse.h)
+    on the host, for the CPU tests.  ``fields``: (name, dtype[, empty_is_nan]) each.  Returns ``(columns, n_rows, unserved,
+    flags)``; ``columns``: name -> array, pre-filled with ones' bits, which a row that is not served leaves as they are.
+    None: the header is refused."""
+    import ctypes
+    from . import _lib
+    data = bytes(data)
+    fields = _typed_fields(fields)
+    end = data.find(b"\n")
+    plan = csv_typed_plan(data if end < 0 else data[:end], [f[0] for f in fields])
+    if plan is None or not data:
+        return None
+    n_columns, positions = plan
+    cap = data.count(b"\n") + 1
+    cols = [np.full(cap * f[1].itemsize, 0xFF, np.uint8).view(f[1]) for f in fields]
+    n, bad, flags = ctypes.c_longlong(0), ctypes.c_longlong(0), ctypes.c_uint32(0)
+    arr = _csv_field_array(fields, positions, [c.ctypes.data for c in cols])
+    _lib.check(_lib.lib().ysmr_csv_parse_typed_devicelike(data, len(data), n_columns, len(fields), arr, cap, ctypes.byref(n),
+                                                          ctypes.byref(bad), ctypes.byref(flags)), "ysmr_csv_parse_typed_devicelike")
+    return {f[0]: c[:n.value] for f, c in zip(fields, cols)}, n.value, bad.value, flags.value
+
+
+class TypedTable:
+    """What :func:`read_typed_device` returns.  ``path_taken``: 'device' -- every row was parsed on the GPU and ``columns``
+    (name -> tensor of ``n_rows`` values; a uint32 column as int32 bits) holds them -- or 'host': the file is not one the
+    typed reader serves, nothing was read, and the caller reads it with pandas.  ``unserved``: rows the parse kernel counted
+    (0 on the device path), ``flags``: of the index pass."""
+
+    def __init__(self, path_taken, n_rows=0, columns=None, unserved=0, flags=0, device=None):
+        self.path_taken, self.n_rows, self.columns, self.unserved, self.flags, self.device = path_taken, n_rows, columns, unserved, flags, device
+
+    def __len__(self):
+        return self.n_rows
+
+
+def read_typed_device(path, fields, device="cuda:0", also_in_header=()):
+    """The columns ``fields`` -- (name, dtype[, empty_is_nan]) each, dtype one of uint32 / int64 / int32 / int8 / float64 -- of
+    the csv at ``path``, as ``pandas.read_csv(usecols, dtype)`` gives them, read on ``device``: the file goes into a pinned
+    buffer and up, its lines are indexed (``ysmr_csv_index``) and parsed a line per lane (``ysmr_csv_parse_typed``).  Returns
+    a :class:`TypedTable`.  What csrc/csv_parse.h does not serve -- a header without one of the names (or of
+    ``also_in_header``, names that pandas' ``usecols`` would demand), quotes, carriage returns, nan / inf, an empty integer
+    field, a value out of range, ... -- or a file that cannot be read gives ``path_taken == 'host'`` and no columns: the
+    caller's pandas read then reports what is wrong with the file, as ever."""
+    import ctypes
+    import torch
+    from . import _lib
+    fields = _typed_fields(fields)
+    L = _lib.lib()
+    dev = torch.device(device)
+    try:
+        with open(path, "rb", buffering=0) as fh:
+            size = os.fstat(fh.fileno()).st_size
+            ws_bytes = int(L.ysmr_csv_workspace_bytes(size))
+            if ws_bytes == 0:
+                return TypedTable("host")
+            staged = _pinned("csv text", size)
+            view, at = memoryview(staged.numpy()), 0
+            while at < size:
+                got = fh.readinto(view[at:])
+                if not got:
+                    return TypedTable("host")           # (the file shrank under the read)
+                at += got
+    except OSError:
+        return TypedTable("host")
+    window = 1 << 16
+    while True:
+        head = view[:min(window, size)].tobytes().find(b"\n")
+        if head >= 0 or window >= size:
+            break
+        window *= 16
+    names = [f[0] for f in fields]
+    plan = csv_typed_plan(view[:head] if head >= 0 else view[:size], names + [k for k in also_in_header if k not in names])
+    if plan is None:
+        return TypedTable("host")
+    n_columns, positions = plan
+    with torch.cuda.device(dev):
+        stream = _lib.stream_ptr(dev)
+        text = torch.empty((size + 255) // 256 * 256, dtype=torch.uint8, device=dev)
+        text[:size].copy_(staged, non_blocking=True)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        meta = torch.zeros(4, dtype=torch.int32, device=dev)             # lines, flags, unserved
+        _lib.check(L.ysmr_csv_index(stream, text.data_ptr(), size, ws.data_ptr(), ws_bytes, meta.data_ptr(), meta[1:].data_ptr()),
+                   "ysmr_csv_index")
+        n_lines, flags = (int(v) & 0xFFFFFFFF for v in meta[:2].cpu())
+        if flags:
+            return TypedTable("host", flags=flags)
+        n = n_lines - 1
+        # the columns one behind the other in one buffer, each from a 16-byte boundary
+        offsets, total = [], 0
+        for _name, dtype, _code, _flags in fields:
+            offsets.append(total)
+            total += (dtype.itemsize * n + 15) // 16 * 16
+        buf = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+        arr = _csv_field_array(fields, positions, [buf.data_ptr() + o for o in offsets])
+        _lib.check(L.ysmr_csv_parse_typed(stream, text.data_ptr(), size, ws.data_ptr(), ws_bytes, n_columns, len(fields), arr, n,
+                                          meta[2:].data_ptr()), "ysmr_csv_parse_typed")
+        unserved = int(meta[2:3].cpu()[0]) & 0xFFFFFFFF
+        if unserved:
+            return TypedTable("host", unserved=unserved)
+        kinds = {np.dtype(np.uint32): torch.int32, np.dtype(np.int64): torch.int64, np.dtype(np.int32): torch.int32,
+                 np.dtype(np.int8): torch.int8, np.dtype(np.float64): torch.float64}
+        columns = {name: buf[o:o + dtype.itemsize * n].view(kinds[dtype]) for (name, dtype, _c, _f), o in zip(fields, offsets)}
+    return TypedTable("device", n_rows=n, columns=columns, device=dev)
 
 
 def _move_aside(save_path):
