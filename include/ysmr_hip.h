@@ -190,6 +190,30 @@ int ysmr_view_batch_host(const uint8_t *frames_host, int n_frames, int height, i
                          const ysmr_row *rows_host, int64_t row_begin, int64_t row_end, int32_t first_frame_index,
                          uint8_t *out_host, int out_stride, size_t out_frame_bytes, int bottom_up);
 
+/* ---- threshold view ---------------------------------------------------------------------- */
+
+/* ADDED under ABI 15 (see above).  What the windows 'threshold' (the final mask behind binary_propagation,
+ * ysmr/track_eval.py:271) and 'Adaptive double threshold markers' (:210) of track_bacteria show, and a composite of both over
+ * the frame, as stored DIB frames laid out as ysmr_annotate_batch's (out_stride a multiple of 4 and >= 3 * width, the bytes
+ * behind a row's pixels zeroed, out_frame_bytes >= out_stride * height, out_dev 4-byte aligned, the last row first if
+ * bottom_up; bytes between two frames are not touched).  cls_dev / mask_dev: u8 [n_frames][height][width], contiguous, as
+ * ysmr_detect_batch leaves them (cls bit 0 thresh, bit 1 markers, other bits ignored; mask != 0: kept).  PIXEL RULE, (B, G, R):
+ *   mode 0 (mask)     255, 255, 255 where mask != 0, else 0, 0, 0;
+ *   mode 1 (markers)  255, 255, 255 where bit 1 of cls is set, else 0, 0, 0 (mask_dev may be NULL);
+ *   mode 2 (classes)  the first that holds: mask != 0 and bit 1 set (0, 0, 255); mask != 0 (0, 255, 255); bit 0 set
+ *                     (255, 0, 0) -- passed the low threshold, dropped by the hysteresis --; else the frame's own pixel
+ *                     (gray g: g, g, g).  A function of (cls & 3, mask != 0) alone, total.
+ * frames_dev: u8 [n_frames][height][width][channels], channels 1 or 3; read in mode 2 only and may be NULL otherwise.
+ * YSMR_ERR_ARG, nothing launched or written: NULL cls or out, NULL mask in modes 0 and 2, NULL frames in mode 2, channels
+ * outside {1, 3}, a mode outside 0 .. 2, a layout that breaks the conditions above.
+ * ysmr_thrview_batch_host: HOST function, the same on host arrays with the same pixel-deciding code. */
+int ysmr_thrview_batch(void *stream, const uint8_t *frames_dev, const uint8_t *cls_dev, const uint8_t *mask_dev,
+                       int n_frames, int height, int width, int channels, int mode,
+                       uint8_t *out_dev, int out_stride, size_t out_frame_bytes, int bottom_up);
+int ysmr_thrview_batch_host(const uint8_t *frames_host, const uint8_t *cls_host, const uint8_t *mask_host,
+                            int n_frames, int height, int width, int channels, int mode,
+                            uint8_t *out_host, int out_stride, size_t out_frame_bytes, int bottom_up);
+
 /* ---- frame ingest: Motion-JPEG ------------------------------------------------------------------ */
 
 /* ADDED under ABI 15 (see above).  bits of status_dev[i] of ysmr_mjpeg_decode_batch */

@@ -67,7 +67,7 @@ EXPORTS = ("ysmr_abi_version", "ysmr_last_error", "ysmr_detect_workspace_bytes",
            "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_batch_sync", "ysmr_mjpeg_decode_sync_geometry",
            "ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_png_deflate", "ysmr_plot_stamp",
            "ysmr_png_dynamic_workspace_bytes", "ysmr_png_dynamic_stream_bytes_max", "ysmr_png_deflate_dynamic", "ysmr_png_code_lengths",
-           "ysmr_view_boxes_batch", "ysmr_view_tracks_batch", "ysmr_view_batch_host",
+           "ysmr_view_boxes_batch", "ysmr_view_tracks_batch", "ysmr_view_batch_host", "ysmr_thrview_batch", "ysmr_thrview_batch_host",
            "ysmr_csv_workspace_bytes", "ysmr_csv_index", "ysmr_csv_parse", "ysmr_csv_order_workspace_bytes", "ysmr_csv_order",
            "ysmr_csv_geometry", "ysmr_csv_parse_devicelike",
            "ysmr_table_csv_bound", "ysmr_table_format_workspace_bytes", "ysmr_table_format_device", "ysmr_table_format_geometry",
@@ -295,6 +295,8 @@ def lib():
     L.ysmr_view_tracks_batch.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int32, ci, ci, ci, vp, ci, ctypes.c_size_t, ci]
     L.ysmr_view_batch_host.argtypes = [vp, ci, ci, ci, ci, vp, vp, ci, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, vp, ci,
                                        ctypes.c_size_t, ci]
+    L.ysmr_thrview_batch.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, ci, ctypes.c_size_t, ci]
+    L.ysmr_thrview_batch_host.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, ci, ctypes.c_size_t, ci]
     L.ysmr_csv_workspace_bytes.argtypes = [ctypes.c_size_t]
     L.ysmr_csv_workspace_bytes.restype = ctypes.c_size_t
     L.ysmr_csv_index.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp]

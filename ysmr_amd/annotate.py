@@ -12,8 +12,9 @@ and hands the frames to ``cv2.VideoWriter``.  Here the frames come through ``Dev
   them to a Motion-JPEG AVI (``MjpegAviWriter``).
 
 Either way the host moves bytes and touches no pixel.  The way from the painted device buffer to the file -- two slots, the
-copy stream, the pinned buffers, the writer thread, the encode call -- is ``DibOutput``; the detection view of
-``track_bacteria`` ('hip save detection video', ``track_eval._DetectionView``) leaves through it as well.
+copy stream, the pinned buffers, the writer thread, the encode call -- is ``DibOutput``; the detection view and the
+threshold view of ``track_bacteria`` ('hip save detection video', 'hip save threshold video': ``track_eval._DetectionView``,
+``_ThresholdView``) leave through it as well.
 
 Departures from upstream, all deliberate:
 

@@ -81,7 +81,8 @@ TRACKING_INI = {
 
 #: optional keys of the HIP path that a tracking.ini may carry in [ADVANCED VIDEO SETTINGS] (absent: not in the settings dict,
 #: and every reader's default holds) -> how the value is read
-OPTIONAL_HIP_KEYS = {"hip save detection video": "getboolean"}
+OPTIONAL_HIP_KEYS = {"hip save detection video": "getboolean",
+                     "hip save threshold video": "get"}     # (a word: track_eval.threshold_view_mode reads it)
 
 _LOG_LEVELS = {"debug": logging.DEBUG, "info": logging.INFO, "warning": logging.WARNING,
                "critical": logging.CRITICAL}

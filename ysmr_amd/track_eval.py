@@ -36,7 +36,8 @@ from .helper_file import (COLOR_BGR2GRAY, RowStream, create_results_folder, get_
                           rows_to_dataframe, save_list, wait_for_removals)
 from .tracker import DeviceTracker, rows_to_numpy, sort_rows
 
-__all__ = ["track_bacteria", "TrackingPipeline", "select_tracks", "evaluate_tracks", "annotate_video", "detection_video_path"]
+__all__ = ["track_bacteria", "TrackingPipeline", "select_tracks", "evaluate_tracks", "annotate_video", "detection_video_path",
+           "threshold_video_path", "threshold_view_mode"]
 
 #: where the wall time of the last _device_pass went, in seconds since it began (diagnostics: scripts/e2e_profile.py)
 LAST_PASS_MARKS = {}
@@ -364,6 +365,11 @@ def track_bacteria(video_path, settings=None, result_folder=None, batch=None, ma
     detections in blue and the ids and centroids of the live tracks in green (``ysmr_view_*``, csrc/view.hip); container and
     codec as ``annotate_video`` chooses them, from the same settings.  The table, the csv and the return value do not change;
     the batch is at most what ``annotate.py`` allows a pinned buffer (and the JPEG encoder's workspace) to hold.
+    'hip save threshold video' (default False): what upstream's other two windows show goes into ``threshold_video_path(...)``
+    in the same way (``ysmr_thrview_batch``, csrc/thrview.hip) -- True or 'mask': the window 'threshold', white where the final
+    mask is set; 'markers': the window 'Adaptive double threshold markers' (only with 'adaptive double threshold' > 0: else one
+    warning and no file); 'classes': the frame with kept marker pixels in red, other kept pixels in yellow and pixels that
+    passed the low threshold but were dropped by the hysteresis in blue.  Any other value: a critical message and ``None``.
     """
     logger = logging.getLogger("ysmr").getChild(__name__)
     settings = get_configs(settings)
@@ -388,10 +394,13 @@ def track_bacteria(video_path, settings=None, result_folder=None, batch=None, ma
     if settings["color filter"] != COLOR_BGR2GRAY:
         logger.critical("Only 'color filter = COLOR_BGR2GRAY' is supported by the HIP path")
         return None
-    if settings.get("hip save detection video"):
+    threshold_view = None
+    if settings.get("hip save detection video") or settings.get("hip save threshold video"):
         try:      # (what 'save video file extension' / 'save video fourcc codec' / 'hip video jpeg ...' ask for, as annotate_video)
             from .annotate import output_format
-            output_format(settings)
+            threshold_view = _threshold_view_of(settings, logger)
+            if settings.get("hip save detection video") or threshold_view is not None:
+                output_format(settings)
         except ValueError as exc:
             logger.critical(str(exc))
             return None
@@ -432,13 +441,15 @@ def track_bacteria(video_path, settings=None, result_folder=None, batch=None, ma
         batch = int(batch or settings.get("hip frames per batch") or auto_batch(frame_height, frame_width, video.channels))
         max_det = int(max_det or settings.get("hip max detections per frame") or DEFAULT_MAX_DET)
         capacity = int(capacity or settings.get("hip max tracks") or DEFAULT_CAPACITY)
-        if settings.get("hip save detection video"):
-            # (a batch of the view waits in a device buffer and leaves through a pinned one: annotate.py's limits on both)
+        if settings.get("hip save detection video") or threshold_view is not None:
+            # (a batch of a view waits in a device buffer and leaves through a pinned one: annotate.py's limits on both)
             batch = min(batch, _view_batch_limit(frame_height, frame_width, frame_count, settings))
+        if threshold_view is not None:
+            threshold_view = (threshold_video_path(video_path, result_folder, settings), threshold_view)
         while True:
             outcome = _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_det, capacity, device,
                                    settings, logger, list_name if settings.get("hip persist rows") else None,
-                                   detection_video_path(video_path, result_folder, settings))
+                                   detection_video_path(video_path, result_folder, settings), threshold_view)
             if outcome[0] == "overflow" and 2 * max(max_det, capacity) <= LIMIT_MAX:
                 max_det, capacity = 2 * max_det, max(2 * capacity, max_det)
                 logger.warning("More objects than the device buffers hold in file {}: running it again with "
@@ -648,14 +659,56 @@ def _view_batch_limit(height, width, frame_count, settings):
     return max(1, limit)
 
 
-class _DetectionView:
-    """'hip save detection video': the frames of ``_device_pass`` with every detection's box and every live track's id painted
-    in (``ysmr_view_boxes_batch`` / ``ysmr_view_tracks_batch``, csrc/view.hip), written to ``detection_video_path`` during the
-    one pass over the video.  The link runs a batch behind detection and a batch's frames are freed once detected, so a
-    batch is packed into one of the two slots of an ``annotate.DibOutput`` right behind its detection, on the side stream,
-    waits there for its link, gets its tracks on the link stream and leaves through the copy stream and the writer thread.
-    Nothing here touches the detections or the rows.  Whatever goes wrong with the FILE (disk full, a write error) ends the
-    view with a critical message and removes the partial file; tracking goes on."""
+def threshold_video_path(video_path, result_folder, settings=None):
+    """Where ``track_bacteria`` writes the threshold view of ``video_path`` when the optional settings key 'hip save threshold
+    video' is on: ``<name>_threshold_output.avi`` in the result folder (an ``.avi``, uncompressed or Motion-JPEG, as
+    ``detection_video_path``'s file is)."""
+    return os.path.join(result_folder, "{}_threshold_output.avi".format(os.path.splitext(os.path.basename(video_path))[0]))
+
+
+#: 'hip save threshold video' -> the ``mode`` of ysmr_thrview_batch (csrc/thrview_rule.h)
+THRESHOLD_VIEW_MODES = {"mask": 0, "markers": 1, "classes": 2}
+
+
+def threshold_view_mode(settings):
+    """What the optional settings key 'hip save threshold video' asks for: None (absent, False, or a tracking.ini's word for
+    it), else the mode of ``ysmr_thrview_batch`` -- 0 for True or 'mask', 1 for 'markers', 2 for 'classes', in any letter case;
+    ValueError, naming key and value, for anything else."""
+    asked = settings.get("hip save threshold video")
+    if asked is None or asked is False or asked is True:
+        return 0 if asked else None
+    if isinstance(asked, str):
+        word = asked.strip().lower()
+        if word in THRESHOLD_VIEW_MODES:
+            return THRESHOLD_VIEW_MODES[word]
+        if word in ("true", "yes", "on", "1"):
+            return 0
+        if word in ("", "false", "no", "off", "0"):
+            return None
+    elif isinstance(asked, int) and asked == 0:
+        return None
+    raise ValueError("'hip save threshold video' must be True, False or one of {}, got {!r}".format(
+        ", ".join(repr(k) for k in THRESHOLD_VIEW_MODES), asked))
+
+
+def _threshold_view_of(settings, logger):
+    """``threshold_view_mode``, and None after one warning for 'markers' where there is no marker threshold: upstream has that
+    window only in the branch of 'adaptive double threshold' > 0 (ysmr/track_eval.py:189-210)."""
+    mode = threshold_view_mode(settings)
+    if mode == THRESHOLD_VIEW_MODES["markers"] and not settings["adaptive double threshold"] > 0:
+        logger.warning("'hip save threshold video' = 'markers' needs 'adaptive double threshold' > 0 (it is {}): there are no markers, "
+                       "no threshold video is written".format(settings["adaptive double threshold"]))
+        return None
+    return mode
+
+
+class _ViewFile:
+    """What the view files of ``_device_pass`` share: the file -- an ``AviWriter`` or a ``MjpegAviWriter`` on ``path``, as
+    ``annotate.output_format`` reads the settings -- behind an ``annotate.DibOutput`` with a device buffer per slot, and how it
+    ends.  Whatever goes wrong with the FILE (it cannot be opened, the disk is full, a write error) ends the view with a
+    critical message and removes the partial file (``dead``); tracking goes on.  ``TITLE`` names the file in messages."""
+
+    TITLE = "View video"
 
     def __init__(self, pipe, video, path, fps, settings, result_folder, frame_count, logger):
         from . import annotate
@@ -673,7 +726,7 @@ class _DetectionView:
                 self.writer = annotate.MjpegAviWriter(path, self.W, self.H, fps)
             else:
                 mode = None
-                if not annotate.enough_space(result_folder, annotate.AviWriter.file_bytes(self.W, self.H, frame_count), "detection video", logger):
+                if not annotate.enough_space(result_folder, annotate.AviWriter.file_bytes(self.W, self.H, frame_count), self.TITLE.lower(), logger):
                     self.dead = True
                     return
                 self.writer = annotate.AviWriter(path, self.W, self.H, fps)
@@ -683,16 +736,104 @@ class _DetectionView:
         try:
             self.sink = annotate.DibOutput(self.writer, pipe.B, self.H, self.W, pipe.device, quality=quality, mode=mode,
                                            result_folder=result_folder, logger=logger, dib_slots=2)
-            self.counters = torch.zeros(2, dtype=torch.int64, device=pipe.device)     # the row counter before / after a batch's link
+            self._buffers()
         except BaseException:      # (nobody holds this object yet: the file just opened goes with it)
             self.abort()
             raise
-        self.row_capacity = pipe.rows.numel() // _lib.ROW_DTYPE.itemsize
         self.L = _lib.lib()
 
+    def _buffers(self):
+        """Device buffers of the view's own, made once the file and its ``DibOutput`` are there."""
+
     def _give_up(self, why):
-        self.logger.critical("Detection video {} is not written: {}".format(self.path, why))
+        self.logger.critical("{} {} is not written: {}".format(self.TITLE, self.path, why))
         self.abort()
+
+    @on_own_device
+    def finish(self):
+        """Everything has been painted and handed over: close the file.  -> its path, or None."""
+        if self.dead:
+            return None
+        self.sink.close()
+        if self.sink.failure:
+            self._give_up(self.sink.failure[0])
+            return None
+        self.writer.close()
+        self.dead = True
+        return self.path
+
+    @on_own_device
+    def abort(self):
+        """Stop, and remove what there is of the file."""
+        if self.sink is not None:
+            self.sink.close()
+            self.sink = None
+        if self.writer is not None:
+            self.writer.abort()
+            self.writer = None
+        self.dead = True
+
+
+class _ThresholdView(_ViewFile):
+    """'hip save threshold video': the class map and the final mask of every batch of ``_device_pass`` as pictures
+    (``ysmr_thrview_batch``, csrc/thrview.hip: the mask, the markers, or both painted over the frame), written to
+    ``threshold_video_path`` during the one pass over the video.  A sibling of ``_DetectionView`` with less to wait for: a
+    batch is painted into one of the two slots of its ``annotate.DibOutput`` right behind its detection, on the side
+    stream, and handed over at once -- nothing here depends on the link.  Nothing here touches the detections or the rows."""
+
+    TITLE = "Threshold video"
+
+    def __init__(self, pipe, video, path, mode, fps, settings, result_folder, frame_count, logger):
+        self.mode = int(mode)
+        super().__init__(pipe, video, path, fps, settings, result_folder, frame_count, logger)
+
+    @on_own_device
+    def pack(self, frames_dev, res, first_frame):
+        """Behind ``detect_async`` of a batch: its maps into a free slot, on the side stream, and out.  -> the event behind
+        which the frames and the detector's maps have been read, or None."""
+        if self.dead:
+            return None
+        try:
+            k = self.sink.acquire()
+        except OSError as exc:
+            self._give_up(exc)
+            return None
+        ptr, pitch = self.sink.frames(k)
+        side = self.pipe.side
+        n = int(frames_dev.shape[0])
+        with torch.cuda.stream(side):
+            _lib.check(self.L.ysmr_thrview_batch(
+                side.cuda_stream, frames_dev.data_ptr() if self.mode == 2 else None, res.cls.data_ptr(), res.mask.data_ptr(), n, self.H,
+                self.W, self.C, self.mode, ptr, self.writer.stride, pitch, int(self.writer.bottom_up)), "ysmr_thrview_batch")
+            packed = torch.cuda.Event()
+            packed.record(side)
+        if self.pipe.exclusive_threshold:
+            # (that measurement mode thresholds the batch after next on the CALLER's stream, into the class map read here)
+            torch.cuda.current_stream(self.device).wait_event(packed)
+        try:
+            if not self.sink.submit(k, n, int(first_frame), side, packed):
+                self._give_up("not enough free space, {} bytes needed, {} free".format(*self.sink.shortfall))
+        except OSError as exc:
+            self._give_up(exc)
+        return packed
+
+
+class _DetectionView(_ViewFile):
+    """'hip save detection video': the frames of ``_device_pass`` with every detection's box and every live track's id painted
+    in (``ysmr_view_boxes_batch`` / ``ysmr_view_tracks_batch``, csrc/view.hip), written to ``detection_video_path`` during the
+    one pass over the video.  The link runs a batch behind detection and a batch's frames are freed once detected, so a
+    batch is packed into one of the two slots of an ``annotate.DibOutput`` right behind its detection, on the side stream,
+    waits there for its link, gets its tracks on the link stream and leaves through the copy stream and the writer thread.
+    Nothing here touches the detections or the rows."""
+
+    TITLE = "Detection video"
+
+    def __init__(self, pipe, video, path, fps, settings, result_folder, frame_count, logger):
+        super().__init__(pipe, video, path, fps, settings, result_folder, frame_count, logger)
+        self.row_capacity = pipe.rows.numel() // _lib.ROW_DTYPE.itemsize
+
+    def _buffers(self):
+        self.counters = torch.zeros(2, dtype=torch.int64, device=self.pipe.device)     # the row counter before / after a batch's link
 
     @on_own_device
     def pack(self, frames_dev, res):
@@ -743,33 +884,9 @@ class _DetectionView:
         except OSError as exc:
             self._give_up(exc)
 
-    @on_own_device
-    def finish(self):
-        """Everything linked has been painted and handed over: close the file.  -> its path, or None."""
-        if self.dead:
-            return None
-        self.sink.close()
-        if self.sink.failure:
-            self._give_up(self.sink.failure[0])
-            return None
-        self.writer.close()
-        self.dead = True
-        return self.path
-
-    @on_own_device
-    def abort(self):
-        """Stop, and remove what there is of the file."""
-        if self.sink is not None:
-            self.sink.close()
-            self.sink = None
-        if self.writer is not None:
-            self.writer.abort()
-            self.writer = None
-        self.dead = True
-
 
 def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_det, capacity, device, settings,
-                 logger, persist_to=None, view_path=None):
+                 logger, persist_to=None, view_path=None, threshold_view=None):
     """The frame loop of one attempt.  Returns (verdict, the video's rows -- what its row sink's ``finish`` gave -- or None,
     frames done, error flag, start time, time when the last frame was linked); verdict 'overflow' asks for larger buffers."""
     frame_height, frame_width = video.height, video.width
@@ -781,6 +898,7 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
     froze = False
     sink = None
     view = None
+    thr_view = None
     t_start = t_frames = time.perf_counter()
     try:
         # Rows stay on the device for the whole video when they fit (capacity rows per frame is the
@@ -797,6 +915,9 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
         LAST_PIPELINE_FACTS.update(capacity=int(capacity), max_det=int(max_det), batched=bool(pipe.trk.batched), fused=bool(pipe.trk.fused))
         if settings.get("hip save detection video"):
             view = _DetectionView(pipe, video, view_path, fps_of_file, settings, os.path.dirname(view_path), frame_count, logger)
+        if threshold_view is not None:      # (path, mode)
+            thr_view = _ThresholdView(pipe, video, threshold_view[0], threshold_view[1], fps_of_file, settings,
+                                      os.path.dirname(threshold_view[0]), frame_count, logger)
         pending = None
         res = None
         checked_early = False
@@ -831,6 +952,8 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
                 LAST_PASS_MARKS.setdefault("first batch on the device", time.perf_counter() - t_start)
                 detected = pipe.detect_async(dev)
                 held, packed = view.pack(dev, detected[1]) if view is not None else (None, None)
+                if thr_view is not None:       # (on the side stream too, behind the other view's: its event covers both)
+                    packed = thr_view.pack(dev, detected[1], f0) or packed
                 nxt = (detected, f0, n_read, held)
                 feed.release(feed_slot, detected[2] if packed is None else packed)   # the batch's frames are free once its detection has run (and the view has them)
             if pending is not None:
@@ -866,6 +989,11 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
                 view = None
                 if written:
                     logger.info("Detection video: {}".format(written))
+            if thr_view is not None:
+                written = thr_view.finish()
+                thr_view = None
+                if written:
+                    logger.info("Threshold video: {}".format(written))
             sorted_rows = sink.finish()
             sink = None
         # the reference reads until cap.read() fails and accepts that only where the container said it would end, or
@@ -889,6 +1017,8 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
             sink.abort()
         if view is not None:        # (... and its detection video is removed, as a failed csv is)
             view.abort()
+        if thr_view is not None:
+            thr_view.abort()
     return verdict, sorted_rows, frames_done, error_during_read, t_start, t_frames
 
 
