@@ -58,7 +58,7 @@ extern "C" {
 #define YSMR_ERR_CAPACITY  3   /* a fixed-capacity buffer would overflow (tracks, workspace) */
 #define YSMR_ERR_STATE     4   /* handle used in the wrong state */
 
-/* 15 still: ysmr_annotate_batch with its mark struct, and later the ysmr_plot_*, ysmr_mjpeg_*, ysmr_violin_*, ysmr_mjpeg_decode_*, ysmr_view_*, ysmr_csv_*, ysmr_table_* and ysmr_marks_* functions, were ADDED under this number
+/* 15 still: ysmr_annotate_batch with its mark struct, and later the ysmr_plot_*, ysmr_mjpeg_*, ysmr_violin_*, ysmr_mjpeg_decode_*, ysmr_view_*, ysmr_csv_*, ysmr_table_*, ysmr_marks_* and ysmr_xlsx_* functions, were ADDED under this number
  * -- no existing entry point, struct or constant changed, so every caller written against 15 keeps working; only a caller
  * of a new function needs a library that has it (the loader reports a missing symbol by name). */
 #define YSMR_ABI_VERSION   15
@@ -742,6 +742,59 @@ int    ysmr_csv_parse_typed(void *stream, const char *text_dev, size_t n_bytes, 
                             int n_columns, int n_fields, const ysmr_csv_field *fields, long long n_rows, uint32_t *unserved_dev);
 int    ysmr_csv_parse_typed_devicelike(const char *text_host, size_t n_bytes, int n_columns, int n_fields, const ysmr_csv_field *fields,
                                        long long row_capacity, long long *n_rows, long long *unserved, uint32_t *flags);
+
+/* DEVICE functions (added under ABI 15): the collated workbook (helper_file.py:92-137 upstream, collate_results_csv_to_xlsx: a
+ * sheet per `*statistics.csv`, DataFrame.to_excel) -- the kinds of a csv file's columns and a sheet's rows as SpreadsheetML.
+ *
+ * ysmr_csv_column_kinds runs behind the same ysmr_csv_index call as the two parsers, with the same text, workspace, staged span
+ * and line-per-lane layout.  kinds_dev: 17 words, zeroed by the call.  Word c < n_columns (1 .. 16) ORs over the n_rows lines
+ * behind the header YSMR_KIND_NOT_INT (a field that is not -?[0-9]{1,18}), YSMR_KIND_NOT_NUMBER (a field that is neither empty
+ * nor a float64 field ysmr_csv_parse_typed serves; a run of more than 18 digits with no '.' or exponent sets it too) and
+ * YSMR_KIND_EMPTY; word 16 holds YSMR_KIND_BAD_LINE for an empty line or one whose field count is not n_columns.  A ballot per
+ * bit, then one atomic OR per wave and column: two runs give the same words.  No bit: pandas.read_csv makes the column int64
+ * (YSMR_COL_I64); only NOT_INT / EMPTY: float64 with NaN for the empty fields (YSMR_COL_F64, YSMR_CSV_EMPTY_IS_NAN); anything
+ * else is not guessed at: the caller reads the file with pandas.  ysmr_csv_column_kinds_devicelike: a HOST function, the same
+ * text (csrc/csv_parse.h) a line at a time; *n_rows: the lines behind the header, *flags: as the index pass sets them.
+ *
+ * ysmr_xlsx_sheet_device: the n_rows rows of 1 .. 16 typed columns (DEVICE pointers in a HOST array, as for
+ * ysmr_table_format_device) as <row r="N">, a cell per value and </row> (csrc/xlsx_row.h), between prefix_host and suffix_host,
+ * which are written as given (the XML head, <sheetData> and the header row; the closing tags).  Table row 0 is sheet row
+ * first_row; with_index: column A holds the table's row number in cell style 1 and the columns follow from B, else they start at
+ * A.  Every cell carries its reference (letters A .. Q, rows of 1 .. 7 digits); integers are plain decimals, a float64 the text
+ * ysmr_table_format_device prints for it, for every finite value; a NaN cell is not written at all (a row of only NaN is its
+ * <row>, its index cell, </row>); an infinity is the string cell <c r="B7" t="str"><v>inf</v></c>.  Asynchronous on `stream`, no
+ * host synchronisation inside; *xml_length_dev receives the bytes written, *wide_cells_dev the float64 cells printed by the
+ * wide printer; nothing is written at or behind xml_dev + the length.  A row per lane printed once into LDS, the workgroup's
+ * text compacted there and sent out in 16-byte stores, a prefix sum over the pieces, a packing launch: the text depends on the
+ * input alone.  Refused (YSMR_ERR_ARG, nothing launched): a column count outside 1 .. 16, an unknown type, first_row < 1 or
+ * first_row + n_rows - 1 > 1048576; (YSMR_ERR_CAPACITY, nothing launched) a bound above 2^32 - 1, xml_capacity below the bound,
+ * workspace_bytes below ysmr_xlsx_sheet_workspace_bytes.  Nothing is truncated.
+ * ysmr_xlsx_sheet_bound: prefix_bytes + n_rows x the longest row + suffix_bytes, the longest row being that of the declared types'
+ * widest values under the digits of the table's last sheet row and last row number; 0 for what is refused.
+ * ysmr_xlsx_sheet_workspace_bytes: 0 for the same (the suffix waits in the workspace: never 0 for what is served).
+ * ysmr_xlsx_sheet_geometry: rows per workgroup of the row printer, its largest staging in LDS, and the longest row there is
+ * (sixteen float64 columns behind the index).  ysmr_xlsx_sheet_devicelike: a HOST function, the same text a row at a time on
+ * columns in host memory. */
+#define YSMR_KIND_NOT_INT    1
+#define YSMR_KIND_NOT_NUMBER 2
+#define YSMR_KIND_EMPTY      4
+#define YSMR_KIND_BAD_LINE   1
+int    ysmr_csv_column_kinds(void *stream, const char *text_dev, size_t n_bytes, const void *workspace_dev, size_t workspace_bytes,
+                             int n_columns, long long n_rows, uint32_t *kinds_dev /* 17 */);
+int    ysmr_csv_column_kinds_devicelike(const char *text_host, size_t n_bytes, int n_columns, uint32_t *kinds /* 17 */,
+                                        long long *n_rows, uint32_t *flags);
+size_t ysmr_xlsx_sheet_bound(long long n_rows, int n_columns, const ysmr_table_column *columns, long long first_row, int with_index,
+                             size_t prefix_bytes, size_t suffix_bytes);
+size_t ysmr_xlsx_sheet_workspace_bytes(long long n_rows, int n_columns, const ysmr_table_column *columns, long long first_row,
+                                       int with_index, size_t suffix_bytes);
+void   ysmr_xlsx_sheet_geometry(int *rows_per_group, int *staged_bytes, int *max_row_bytes);
+int    ysmr_xlsx_sheet_device(void *stream, long long n_rows, int n_columns, const ysmr_table_column *columns, long long first_row,
+                              int with_index, const char *prefix_host, size_t prefix_bytes, const char *suffix_host,
+                              size_t suffix_bytes, void *workspace_dev, size_t workspace_bytes, char *xml_dev, size_t xml_capacity,
+                              unsigned long long *xml_length_dev, uint32_t *wide_cells_dev);
+int    ysmr_xlsx_sheet_devicelike(long long n_rows, int n_columns, const ysmr_table_column *columns, long long first_row,
+                                  int with_index, const char *prefix, size_t prefix_bytes, const char *suffix, size_t suffix_bytes,
+                                  char *out, size_t out_capacity, size_t *out_length, long long *wide_cells);
 
 /* DEVICE functions (added under ABI 15): the marks of a whole annotated video from the columns of the evaluated table --
  * annotate.build_marks on the device, the same bytes.  A row is kept if x and y are finite, 0 <= t < n_frames and (with

@@ -72,7 +72,12 @@ EXPORTS = ("ysmr_abi_version", "ysmr_last_error", "ysmr_detect_workspace_bytes",
            "ysmr_csv_geometry", "ysmr_csv_parse_devicelike",
            "ysmr_table_csv_bound", "ysmr_table_format_workspace_bytes", "ysmr_table_format_device", "ysmr_table_format_geometry",
            "ysmr_table_format_devicelike", "ysmr_fmt_f64_text",
-           "ysmr_csv_parse_typed", "ysmr_csv_parse_typed_devicelike", "ysmr_marks_workspace_bytes", "ysmr_marks_build")
+           "ysmr_csv_parse_typed", "ysmr_csv_parse_typed_devicelike", "ysmr_marks_workspace_bytes", "ysmr_marks_build",
+           "ysmr_csv_column_kinds", "ysmr_csv_column_kinds_devicelike", "ysmr_xlsx_sheet_bound", "ysmr_xlsx_sheet_workspace_bytes",
+           "ysmr_xlsx_sheet_geometry", "ysmr_xlsx_sheet_device", "ysmr_xlsx_sheet_devicelike")
+
+#: bits of ``ysmr_csv_column_kinds`` (YSMR_KIND_*): words 0 .. 15 a column each, word 16 the file's
+KIND_NOT_INT, KIND_NOT_NUMBER, KIND_EMPTY, KIND_BAD_LINE, KIND_WORDS = 1, 2, 4, 1, 17
 
 #: column types of ``ysmr_table_format_device`` (include/ysmr_hip.h: YSMR_COL_*), by numpy dtype
 TABLE_COLUMN_TYPES = {np.dtype(np.uint32): 0, np.dtype(np.int64): 1, np.dtype(np.int32): 2, np.dtype(np.int8): 3, np.dtype(np.float64): 4}
@@ -326,8 +331,20 @@ def lib():
     L.ysmr_marks_workspace_bytes.argtypes = [ll, ci]
     L.ysmr_marks_workspace_bytes.restype = ctypes.c_size_t
     L.ysmr_marks_build.argtypes = [vp, ll] + [vp] * 7 + [ci, ci, ci, vp, ctypes.c_size_t, vp, vp]
+    L.ysmr_csv_column_kinds.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ci, ll, vp]
+    L.ysmr_csv_column_kinds_devicelike.argtypes = [vp, ctypes.c_size_t, ci, vp, ctypes.POINTER(ll), ctypes.POINTER(ctypes.c_uint32)]
+    L.ysmr_xlsx_sheet_bound.argtypes = [ll, ci, tc, ll, ci, ctypes.c_size_t, ctypes.c_size_t]
+    L.ysmr_xlsx_sheet_bound.restype = ctypes.c_size_t
+    L.ysmr_xlsx_sheet_workspace_bytes.argtypes = [ll, ci, tc, ll, ci, ctypes.c_size_t]
+    L.ysmr_xlsx_sheet_workspace_bytes.restype = ctypes.c_size_t
+    L.ysmr_xlsx_sheet_geometry.argtypes = [ctypes.POINTER(ci)] * 3
+    L.ysmr_xlsx_sheet_geometry.restype = None
+    L.ysmr_xlsx_sheet_device.argtypes = [vp, ll, ci, tc, ll, ci, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, vp,
+                                         ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp]
+    L.ysmr_xlsx_sheet_devicelike.argtypes = [ll, ci, tc, ll, ci, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, vp,
+                                             ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ll)]
     for name in EXPORTS:
-        if name not in ("ysmr_table_csv_bound", "ysmr_table_format_workspace_bytes", "ysmr_table_format_geometry", "ysmr_csv_workspace_bytes", "ysmr_csv_order_workspace_bytes", "ysmr_marks_workspace_bytes", "ysmr_csv_geometry", "ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_png_dynamic_workspace_bytes", "ysmr_png_dynamic_stream_bytes_max", "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_sync_geometry", "ysmr_mjpeg_decode_workspace_bytes", "ysmr_violin_workspace_bytes", "ysmr_mjpeg_workspace_bytes", "ysmr_mjpeg_encode_workspace_bytes", "ysmr_plot_workspace_bytes", "ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
+        if name not in ("ysmr_xlsx_sheet_bound", "ysmr_xlsx_sheet_workspace_bytes", "ysmr_xlsx_sheet_geometry", "ysmr_table_csv_bound", "ysmr_table_format_workspace_bytes", "ysmr_table_format_geometry", "ysmr_csv_workspace_bytes", "ysmr_csv_order_workspace_bytes", "ysmr_marks_workspace_bytes", "ysmr_csv_geometry", "ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_png_dynamic_workspace_bytes", "ysmr_png_dynamic_stream_bytes_max", "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_sync_geometry", "ysmr_mjpeg_decode_workspace_bytes", "ysmr_violin_workspace_bytes", "ysmr_mjpeg_workspace_bytes", "ysmr_mjpeg_encode_workspace_bytes", "ysmr_plot_workspace_bytes", "ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
                         "ysmr_rows_sort_workspace_bytes", "ysmr_rows_csv_bound", "ysmr_rows_stream_count",
                         "ysmr_mean_threshold_state_bytes"):
             getattr(L, name).restype = ci

@@ -9,6 +9,9 @@
 //                    FROM GLOBAL MEMORY, byte by byte: it comes out right, only slower
 //   ysmr_csv_parse_typed  the same behind the same index, for 1 .. 16 columns of the table writer's five types (uint32, int64,
 //                    int32, int8, float64 with an empty field as NaN on request): what annotate_video reads of an `*_analysed.csv`
+//   ysmr_csv_column_kinds  the same behind the same index: per column, whether every field is an int64 field, whether every
+//                    field is a float64 field or empty, whether one is empty -- what the collated workbook's reader needs to
+//                    know before it names the types of ysmr_csv_parse_typed, as pandas.read_csv infers them
 //   ysmr_csv_order   stable radix sort of (TRACK_ID << 32 | POSITION_T) with the row number as payload (prim.h), then a gather
 //                    of the seven columns
 #include <hip/hip_runtime.h>
@@ -240,6 +243,58 @@ __global__ __launch_bounds__(256) void k_csv_parse_typed(const unsigned char *__
     if ((threadIdx.x & 63) == 0 && bad) atomicAdd(unserved, (uint32_t)__popcll(bad));
 }
 
+// The kinds of the first n_columns columns (csv_parse.h: classify_field): the same grid, staging and line-per-lane layout as the
+// two parsers.  All lanes look at column `col` in the same iteration, so a column's bits are gathered by three ballots and go
+// out in ONE atomic per wave and column, and only where a bit is set; OR has no order, two runs give the same words
+__global__ __launch_bounds__(256) void k_csv_kinds(const unsigned char *__restrict__ text, uint32_t n_bytes, const uint32_t *__restrict__ starts,
+                                                   const uint32_t *__restrict__ meta, int n_columns, uint32_t n_rows, uint32_t *__restrict__ kinds)
+{
+    __shared__ uint4 s_text[STAGED_SPAN / 16];
+    const uint32_t lines = meta[1];
+    const uint32_t r0 = blockIdx.x * 256u;
+    const uint32_t here = min(256u, n_rows - r0);
+    const uint32_t known = r0 + 1u < lines ? min(here, lines - 1u - r0) : 0u;
+    uint32_t a0 = 0u;
+    if (known) {
+        const uint32_t span0 = starts[r0 + 1u], span1 = min(starts[r0 + known + 1u] - 1u, n_bytes);
+        a0 = span0 & ~15u;
+        const uint32_t stop = min(span1, a0 + (uint32_t)STAGED_SPAN);
+        for (uint32_t i = threadIdx.x; a0 + 16u * i < stop && i < (uint32_t)(STAGED_SPAN / 16); i += 256u) {
+            const uint32_t pos = a0 + 16u * i;
+            if (pos + 16u <= n_bytes) s_text[i] = *(const uint4 *)(text + pos);
+            else
+                for (uint32_t k = 0; pos + k < n_bytes; ++k) ((unsigned char *)s_text)[16u * i + k] = text[pos + k];
+        }
+    }
+    __syncthreads();
+    const uint32_t row = r0 + threadIdx.x;
+    const bool mine = threadIdx.x < here;
+    bool bad = mine;                                             // (a row the index did not find, an empty line)
+    long long p = 0, end = 0;
+    if (threadIdx.x < known) {
+        const uint32_t begin = starts[row + 1u], next = starts[row + 2u];
+        if (next > begin + 1u && next - 1u <= n_bytes) { p = (long long)begin; end = (long long)(next - 1u); bad = false; }
+    }
+    const StagedText at{(const unsigned char *)s_text, text, a0};
+    for (int col = 0; col < n_columns; ++col) {
+        uint32_t bits = 0u;
+        if (mine && !bad) {
+            if (col) {
+                if (p >= end) bad = true;                        // too few fields
+                else ++p;                                        // (the ',' the field before stopped at)
+            }
+            if (!bad) p = ysmr_csv::classify_field(at, p, end, bits);
+        }
+        const bool not_int = __ballot((bits & ysmr_csv::KIND_NOT_INT) != 0u) != 0ull;
+        const bool not_number = __ballot((bits & ysmr_csv::KIND_NOT_NUMBER) != 0u) != 0ull;
+        const bool empty = __ballot((bits & ysmr_csv::KIND_EMPTY) != 0u) != 0ull;
+        const uint32_t word = (not_int ? ysmr_csv::KIND_NOT_INT : 0u) | (not_number ? ysmr_csv::KIND_NOT_NUMBER : 0u) | (empty ? ysmr_csv::KIND_EMPTY : 0u);
+        if ((threadIdx.x & 63) == 0 && word) atomicOr(&kinds[col], word);
+    }
+    if (mine && !bad && p != end) bad = true;                    // too many fields
+    if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&kinds[ysmr_csv::MAX_FIELDS], ysmr_csv::KIND_BAD_LINE);
+}
+
 __global__ __launch_bounds__(256) void k_csv_keys(const uint32_t *__restrict__ id, const uint32_t *__restrict__ t, long long n,
                                                   unsigned long long *__restrict__ keys, uint32_t *__restrict__ idx)
 {
@@ -281,6 +336,9 @@ static_assert(csvp::MAX_COLUMNS == ysmr_csv::MAX_COLUMNS && csvp::MAX_FIELDS == 
               csvp::FIELD_EMPTY_IS_NAN == ysmr_csv::TYPED_EMPTY_IS_NAN && YSMR_CSV_EMPTY_IS_NAN == ysmr_csv::TYPED_EMPTY_IS_NAN &&
               YSMR_COL_U32 == ysmr_csv::TYPE_U32 && YSMR_COL_I64 == ysmr_csv::TYPE_I64 && YSMR_COL_I32 == ysmr_csv::TYPE_I32 &&
               YSMR_COL_I8 == ysmr_csv::TYPE_I8 && YSMR_COL_F64 == ysmr_csv::TYPE_F64, "csv_plan.h, csv_parse.h and ysmr_hip.h name the same types");
+
+static_assert(YSMR_KIND_NOT_INT == ysmr_csv::KIND_NOT_INT && YSMR_KIND_NOT_NUMBER == ysmr_csv::KIND_NOT_NUMBER && YSMR_KIND_EMPTY == ysmr_csv::KIND_EMPTY &&
+              YSMR_KIND_BAD_LINE == ysmr_csv::KIND_BAD_LINE && ysmr_csv::KIND_WORDS == 17, "csv_parse.h and ysmr_hip.h name the same kinds");
 
 // the caller's fields -> the plan and the columns in the order of the plan; NULL, or what is wrong with them
 const char *typed_plan_of(int n_columns, int n_fields, const ysmr_csv_field *fields, bool need_data, ysmr_csv::TypedPlan &plan, TypedColumns &cols)
@@ -503,6 +561,68 @@ int ysmr_csv_parse_typed_devicelike(const char *text_host, size_t n_bytes, int n
     }
     *n_rows = rows;
     *unserved = bad;
+    return YSMR_OK;
+}
+
+int ysmr_csv_column_kinds(void *stream, const char *text_dev, size_t n_bytes, const void *workspace_dev, size_t workspace_bytes,
+                          int n_columns, long long n_rows, uint32_t *kinds_dev)
+{
+    csvp::Plan p;
+    if (!csvp::plan_of(n_bytes, p)) return ysmr::fail(YSMR_ERR_ARG, "n_bytes must be in 1..%zu, got %zu", csvp::MAX_BYTES, n_bytes);
+    if (n_rows < 0 || (unsigned long long)n_rows + 2ull > p.line_capacity)
+        return ysmr::fail(YSMR_ERR_ARG, "n_rows must be in 0..%zu for %zu bytes of text, got %lld", p.line_capacity - 2, n_bytes, n_rows);
+    if (n_columns < 1 || n_columns > ysmr_csv::MAX_FIELDS) return ysmr::fail(YSMR_ERR_ARG, "n_columns must be in 1..%d, got %d", ysmr_csv::MAX_FIELDS, n_columns);
+    if (!kinds_dev) return ysmr::fail(YSMR_ERR_ARG, "kinds_dev must be set");
+    hipStream_t st = (hipStream_t)stream;
+    YSMR_HIP_CHECK(hipMemsetAsync(kinds_dev, 0, ysmr_csv::KIND_WORDS * sizeof(uint32_t), st));
+    if (n_rows == 0) return YSMR_OK;
+    if (!text_dev || !workspace_dev) return ysmr::fail(YSMR_ERR_ARG, "text_dev and workspace_dev must be set");
+    if (((uintptr_t)text_dev & 15u) || ((uintptr_t)workspace_dev & 15u)) return ysmr::fail(YSMR_ERR_ARG, "text_dev and workspace_dev must be 16-byte aligned");
+    if (workspace_bytes < p.total) return ysmr::fail(YSMR_ERR_CAPACITY, "csv workspace too small: %zu < %zu bytes", workspace_bytes, p.total);
+    const char *w = (const char *)workspace_dev;
+    hipLaunchKernelGGL(k_csv_kinds, dim3(csvp::parse_groups(n_rows)), dim3(256), 0, st, (const unsigned char *)text_dev, (uint32_t)n_bytes,
+                       (const uint32_t *)(w + p.starts), (const uint32_t *)(w + p.meta), n_columns, (uint32_t)n_rows, kinds_dev);
+    YSMR_LAUNCH_CHECK();
+    return YSMR_OK;
+}
+
+int ysmr_csv_column_kinds_devicelike(const char *text_host, size_t n_bytes, int n_columns, uint32_t *kinds, long long *n_rows, uint32_t *flags)
+{
+    if (!text_host || n_bytes == 0 || n_bytes > csvp::MAX_BYTES || !kinds || !n_rows || !flags)
+        return ysmr::fail(YSMR_ERR_ARG, "text_host (1..%zu bytes), kinds, n_rows and flags must be set", csvp::MAX_BYTES);
+    if (n_columns < 1 || n_columns > ysmr_csv::MAX_FIELDS) return ysmr::fail(YSMR_ERR_ARG, "n_columns must be in 1..%d, got %d", ysmr_csv::MAX_FIELDS, n_columns);
+    const unsigned char *s = (const unsigned char *)text_host;
+    uint32_t f = 0;
+    for (size_t i = 0; i < n_bytes; ++i)
+        f |= (s[i] == '"' ? ysmr_csv::FLAG_QUOTE : 0u) | (s[i] == '\r' ? ysmr_csv::FLAG_CR : 0u) | (s[i] == 0 || s[i] >= 0x80 ? ysmr_csv::FLAG_NOT_PLAIN : 0u);
+    *flags = f;
+    for (int k = 0; k < ysmr_csv::KIND_WORDS; ++k) kinds[k] = 0u;
+    const HostText at{s};
+    long long line = 0, rows = 0;
+    size_t begin = 0;
+    while (begin < n_bytes) {
+        const void *nl = std::memchr(s + begin, '\n', n_bytes - begin);
+        const size_t stop = nl ? (size_t)((const unsigned char *)nl - s) : n_bytes;
+        if (line > 0) {
+            long long p = (long long)begin;
+            const long long end = (long long)stop;
+            bool bad = end <= p;
+            for (int col = 0; col < n_columns && !bad; ++col) {
+                if (col) {
+                    if (p >= end) { bad = true; break; }
+                    ++p;
+                }
+                uint32_t bits = 0u;
+                p = ysmr_csv::classify_field(at, p, end, bits);
+                kinds[col] |= bits;
+            }
+            if (bad || p != end) kinds[ysmr_csv::MAX_FIELDS] |= ysmr_csv::KIND_BAD_LINE;
+            ++rows;
+        }
+        ++line;
+        begin = stop + 1;
+    }
+    *n_rows = rows;
     return YSMR_OK;
 }
 

@@ -286,4 +286,36 @@ YSMR_FMT_HD void store_typed(void *data, int type, long long r, uint64_t bits)
     else ((uint32_t *)data)[r] = (uint32_t)bits;
 }
 
+// ---- the kinds of a file's columns: what pandas.read_csv would infer, as far as the typed parse can serve it -----------------
+// (ysmr_csv_column_kinds, csv.hip.)  Three bits per column, ORed over the lines:
+//   KIND_NOT_INT     a field that is not -?[0-9]{1,18} (what parse_int reads for TYPE_I64)
+//   KIND_NOT_NUMBER  a field that is neither empty nor a float64 field parse_f64 serves -- and a run of more than 18 digits
+//                    with no '.' or exponent: pandas makes such a column int64, uint64 or object, none of which is guessed at
+//   KIND_EMPTY       an empty field
+// and one bit for the file: KIND_BAD_LINE, a line that is empty (pandas skips it) or whose field count is not n_columns.
+// No bit: the column is int64.  Only NOT_INT / EMPTY: it is float64, NaN where a field is empty.
+constexpr uint32_t KIND_NOT_INT = 1u, KIND_NOT_NUMBER = 2u, KIND_EMPTY = 4u, KIND_BAD_LINE = 1u;
+constexpr int KIND_WORDS = MAX_FIELDS + 1;          // a word per column, then the file's
+
+// the field at [p, end): its bits into `bits`; returns the position behind it -- end, or that of its ','
+template <class Fetch>
+YSMR_FMT_HD long long classify_field(const Fetch &at, long long p, long long end, uint32_t &bits)
+{
+    if (p >= end || at(p) == ',') { bits = KIND_EMPTY | KIND_NOT_INT; return p; }
+    int64_t i = 0;
+    long long q = parse_int(at, p, end, 18, false, INT64_MIN, INT64_MAX, i);
+    if (q >= 0) { bits = 0u; return q; }
+    q = p + (at(p) == '-' ? 1 : 0);
+    const long long digits_from = q;
+    while (q < end && is_digit(at(q))) ++q;
+    if (q > digits_from && (q >= end || at(q) == ',')) { bits = KIND_NOT_INT | KIND_NOT_NUMBER; return q; }    // (more than 18 digits)
+    double d = 0.0;
+    q = parse_f64(at, p, end, d);
+    if (q >= 0) { bits = KIND_NOT_INT; return q; }
+    bits = KIND_NOT_INT | KIND_NOT_NUMBER;
+    q = p;
+    while (q < end && at(q) != ',') ++q;
+    return q;
+}
+
 }  // namespace ysmr_csv

@@ -28,6 +28,7 @@
 #include "fmt.h"
 #include "table_csv_plan.h"
 #include "table_csv_row.h"
+#include "table_wide.h"
 
 static_assert(tablep::SCAN_TILE == ysmr::prim::SCAN_TILE, "table_csv_plan.h restates prim.h's scan tile");
 static_assert(tablep::COL_U32 == YSMR_COL_U32 && tablep::COL_I64 == YSMR_COL_I64 && tablep::COL_I32 == YSMR_COL_I32 &&
@@ -215,6 +216,18 @@ int check_bound(long long n_rows, int n_columns, const int32_t *types, size_t he
 
 }  // namespace
 
+void tablep::launch_wide_cells(hipStream_t st, int n_columns, const void *const *data, const int32_t *types, long long n_rows,
+                               uint32_t *wide_incl, uint32_t *wide_temp, char *slots, uint8_t *slot_len, uint32_t *wide_cells_dev)
+{
+    Columns cols{};
+    cols.n = n_columns;
+    for (int c = 0; c < n_columns; ++c) { cols.data[c] = data[c]; cols.type[c] = types[c]; }
+    const unsigned grid = (unsigned)std::min<long long>((n_rows + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_table_prepass, dim3(grid), dim3(256), 0, st, cols, n_rows, wide_incl);
+    ysmr::prim::inclusive_scan_u32(st, wide_incl, wide_incl, (size_t)n_rows, wide_temp);
+    hipLaunchKernelGGL(k_table_wide, dim3(WIDE_GRID), dim3(64), 0, st, cols, n_rows, (const uint32_t *)wide_incl, slots, slot_len, wide_cells_dev);
+}
+
 extern "C" {
 
 size_t ysmr_table_csv_bound(long long n_rows, int n_columns, const ysmr_table_column *columns, size_t header_bytes)
@@ -275,13 +288,9 @@ int ysmr_table_format_device(void *stream, long long n_rows, int n_columns, cons
         uint32_t *wide_incl = p.n_f64 ? (uint32_t *)(w + p.wide_incl) : nullptr;
         char *slots = w + p.wide_slots;
         uint8_t *slot_len = (uint8_t *)(w + p.wide_len);
-        if (p.n_f64) {
-            const unsigned grid = (unsigned)std::min<long long>((n_rows + 255) / 256, 2048);
-            hipLaunchKernelGGL(k_table_prepass, dim3(grid), dim3(256), 0, st, cols, n_rows, wide_incl);
-            ysmr::prim::inclusive_scan_u32(st, wide_incl, wide_incl, (size_t)n_rows, (uint32_t *)(w + p.wide_temp));
-            hipLaunchKernelGGL(k_table_wide, dim3(WIDE_GRID), dim3(64), 0, st, cols, n_rows, (const uint32_t *)wide_incl, slots, slot_len,
-                               wide_cells_dev);
-        } else YSMR_HIP_CHECK(hipMemsetAsync(wide_cells_dev, 0, sizeof(uint32_t), st));
+        if (p.n_f64) tablep::launch_wide_cells(st, n_columns, cols.data, cols.type, n_rows, wide_incl, (uint32_t *)(w + p.wide_temp), slots, slot_len,
+                                               wide_cells_dev);
+        else YSMR_HIP_CHECK(hipMemsetAsync(wide_cells_dev, 0, sizeof(uint32_t), st));
         uint32_t *piece_len = (uint32_t *)(w + p.piece_len), *piece_incl = (uint32_t *)(w + p.piece_incl);
         hipLaunchKernelGGL(k_table_rows, dim3((unsigned)p.groups), dim3(R), (size_t)R * p.row_stride, st, cols, n_rows, p.row_stride,
                            (const uint32_t *)wide_incl, (const char *)slots, (const uint8_t *)slot_len, w + p.pieces, p.piece_stride, piece_len);

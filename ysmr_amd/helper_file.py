@@ -18,7 +18,9 @@ from datetime import datetime
 import numpy as np
 
 __all__ = ["create_configs", "get_configs", "default_settings", "reshape_result", "save_list", "sort_list",
-           "get_data", "read_table_device", "create_results_folder", "metadata_file", "get_loggers", "COLOR_BGR2GRAY"]
+           "get_data", "read_table_device", "create_results_folder", "metadata_file", "get_loggers", "COLOR_BGR2GRAY",
+           "find_paths", "creation_date", "collate_results_csv_to_xlsx", "collate_xlsx_mode", "sheet_xml_host", "XLSX_MAX_ROWS",
+           "LAST_COLLATE"]
 
 COLOR_BGR2GRAY = 6  # value of cv2.COLOR_BGR2GRAY; the only colour filter the HIP path implements
 
@@ -83,6 +85,8 @@ TRACKING_INI = {
 #: and every reader's default holds) -> how the value is read
 OPTIONAL_HIP_KEYS = {"hip save detection video": "getboolean",
                      "hip save threshold video": "get"}     # (a word: track_eval.threshold_view_mode reads it)
+#: ... and in [RESULTS SETTINGS], beside 'collate results csv to xlsx' (a word: collate_xlsx_mode reads it)
+OPTIONAL_HIP_RESULT_KEYS = {"hip collate xlsx": "get"}
 
 _LOG_LEVELS = {"debug": logging.DEBUG, "info": logging.INFO, "warning": logging.WARNING,
                "critical": logging.CRITICAL}
@@ -220,6 +224,9 @@ def _build_settings(parser, ini_path):
     for key, getter in OPTIONAL_HIP_KEYS.items():
         if vid.get(key) is not None:
             s[key] = getattr(vid, getter)(key)
+    for key, getter in OPTIONAL_HIP_RESULT_KEYS.items():
+        if res.get(key) is not None:
+            s[key] = getattr(res, getter)(key)
     assert s["minimum horizon size"] >= 0, "'minimum horizon size' less than 0"
     assert s["number of LSFFs"] > 1, "'number of LSFFs' less than 2"
     assert s["frames per second"] > 0, "'frames per second' zero or negative"
@@ -250,7 +257,9 @@ def get_configs(tracking_ini_filepath=None):
     through :func:`read_typed_device` and builds its marks on the device; ``'hip write csv on device'`` -- they write
     ``<name>_selected_data.csv`` and ``<name>_analysed.csv`` through :func:`write_table_device` (the same bytes;
     ``<name>_statistics.csv``, one row per track, stays with pandas); ``'hip png on device'`` and ``'hip violin plots'`` -- the
-    figures (``evaluate.py``, ``plot_functions.py``)."""
+    figures (``evaluate.py``, ``plot_functions.py``); ``'hip collate xlsx'`` -- ``ysmr()`` ends with the collated workbook
+    (:func:`collate_results_csv_to_xlsx`; the word 'deflate': compressed entries), also read from a tracking.ini's
+    [RESULTS SETTINGS]."""
     if isinstance(tracking_ini_filepath, dict):
         return tracking_ini_filepath
     if tracking_ini_filepath is None:
@@ -1158,6 +1167,454 @@ def save_df_to_csv(df, save_path, rename_old_file=True):
         _logger().debug("Selected results saved to: {}".format(save_path))
     except OSError as exc:
         _logger().exception("Could not save {}: {}".format(save_path, exc))
+
+
+def creation_date(path_to_file):
+    """Seconds since the file was created -- since it was last modified where the platform keeps no creation time, as on
+    Linux -- or None if there is no such file (helper_file.py:408-436)."""
+    import platform
+    if not os.path.isfile(path_to_file):
+        return None
+    if platform.system() == "Windows":
+        then = os.path.getctime(path_to_file)
+    else:
+        stat = os.stat(path_to_file)
+        then = getattr(stat, "st_birthtime", stat.st_mtime)
+    return (datetime.now() - datetime.fromtimestamp(then)).total_seconds()
+
+
+def find_paths(base_path, extension, minimal_age=0, maximal_age=np.inf, recursive=True):
+    """The files below ``base_path`` whose names end in ``extension`` and whose age in seconds (:func:`creation_date`) lies in
+    ``minimal_age .. maximal_age``, with ``/`` as separator, in glob's order; ``recursive``: sub-folders too.  A file "from the
+    future" is left out with a warning unless ``minimal_age`` is negative; a path that does not exist gives None and a warning
+    (helper_file.py:476-516)."""
+    from glob import glob
+    if not os.path.exists(base_path):
+        _logger().warning("Path could not be found: {}".format(base_path))
+        return None
+    base_path = os.fspath(base_path)
+    if base_path[-1] != "/":
+        base_path += "/"
+    pattern = ("{}**/*{}" if recursive else "{}*{}").format(base_path, extension)
+    found = []
+    for name in glob(pattern, recursive=recursive):
+        name = name.replace(os.sep, "/")
+        age = creation_date(name)
+        if age is None:
+            continue        # (a folder of that name: upstream's comparison with None raises here)
+        if age < 0 and minimal_age >= 0:
+            _logger().warning("The file appears to be {:.2f} seconds from the future and was thus not selected. "
+                              "File: {}".format(abs(age), name))
+        elif age < 0 or minimal_age <= age <= maximal_age:
+            found.append(name)
+    return found
+
+
+# ---- the collated workbook (helper_file.py:92-137 upstream: collate_results_csv_to_xlsx) -------------------------------------
+#: data rows of a sheet: Excel's 1 048 576 rows less the header's
+XLSX_MAX_ROWS = 2 ** 20 - 1
+#: (diagnostics) which path built each sheet of the last collate_results_csv_to_xlsx: file path -> 'device' or 'host'
+LAST_COLLATE = {}
+#: (diagnostics) seconds the last collate_results_csv_to_xlsx spent in each phase, summed over its files
+LAST_COLLATE_TIMES = {}
+
+_XML_HEAD = '<?xml version="1.0" encoding="UTF-8" standalone="yes"?>\n'
+_NS_MAIN = "http://schemas.openxmlformats.org/spreadsheetml/2006/main"
+_NS_REL = "http://schemas.openxmlformats.org/officeDocument/2006/relationships"
+_NS_PKG_REL = "http://schemas.openxmlformats.org/package/2006/relationships"
+_SHEET_SUFFIX = b"</sheetData></worksheet>"
+#: cell formats: 0 the default; 1 bold, thin border, centred -- what pandas gives header and index cells
+_STYLES_XML = (
+    _XML_HEAD + '<styleSheet xmlns="' + _NS_MAIN + '">'
+    '<fonts count="2"><font><sz val="11"/><name val="Calibri"/><family val="2"/></font>'
+    '<font><b/><sz val="11"/><name val="Calibri"/><family val="2"/></font></fonts>'
+    '<fills count="2"><fill><patternFill patternType="none"/></fill><fill><patternFill patternType="gray125"/></fill></fills>'
+    '<borders count="2"><border><left/><right/><top/><bottom/><diagonal/></border>'
+    '<border><left style="thin"><color auto="1"/></left><right style="thin"><color auto="1"/></right>'
+    '<top style="thin"><color auto="1"/></top><bottom style="thin"><color auto="1"/></bottom><diagonal/></border></borders>'
+    '<cellStyleXfs count="1"><xf numFmtId="0" fontId="0" fillId="0" borderId="0"/></cellStyleXfs>'
+    '<cellXfs count="2"><xf numFmtId="0" fontId="0" fillId="0" borderId="0" xfId="0"/>'
+    '<xf numFmtId="0" fontId="1" fillId="0" borderId="1" xfId="0" applyFont="1" applyBorder="1" applyAlignment="1">'
+    '<alignment horizontal="center" vertical="top"/></xf></cellXfs>'
+    '<cellStyles count="1"><cellStyle name="Normal" xfId="0" builtinId="0"/></cellStyles></styleSheet>')
+
+
+def collate_xlsx_mode(settings):
+    """What the optional settings key 'hip collate xlsx' asks for: None (absent, false, or a tracking.ini's word for false),
+    'deflate' for that word in any letter case, 'stored' for every other true value."""
+    asked = settings.get("hip collate xlsx")
+    if isinstance(asked, str):
+        word = asked.strip().lower()
+        if word == "deflate":
+            return "deflate"
+        return None if word in ("", "false", "no", "off", "0") else "stored"
+    return "stored" if asked else None
+
+
+def _xml_text(text):
+    """``text`` as character data or an attribute's value; what XML 1.0 cannot hold becomes Excel's ``_xHHHH_``."""
+    out = str(text).replace("&", "&amp;").replace("<", "&lt;").replace(">", "&gt;").replace('"', "&quot;")
+    if any(ord(ch) < 32 and ch not in "\t\n\r" or ch in "\ufffe\uffff" for ch in out):
+        out = "".join("_x{:04X}_".format(ord(ch)) if ord(ch) < 32 and ch not in "\t\n\r" or ch in "\ufffe\uffff" else ch for ch in out)
+    return out
+
+
+def _column_letters(k):
+    """0 -> A, 25 -> Z, 26 -> AA, ..."""
+    letters = ""
+    k += 1
+    while k:
+        k, rest = divmod(k - 1, 26)
+        letters = chr(65 + rest) + letters
+    return letters
+
+
+def _string_cell(ref, text, style=""):
+    text = str(text)
+    space = ' xml:space="preserve"' if text != text.strip() else ""
+    return '<c r="{}"{} t="inlineStr"><is><t{}>{}</t></is></c>'.format(ref, style, space, _xml_text(text))
+
+
+def sheet_prefix(names, header_row=1):
+    """The head of a sheet's XML up to and with the header row: ``names`` in B, C, ... of row ``header_row`` as inline strings
+    of style 1, column A left empty -- what ``to_excel`` writes above a frame with its RangeIndex."""
+    cells = "".join(_string_cell("{}{}".format(_column_letters(k + 1), header_row), name, ' s="1"') for k, name in enumerate(names))
+    return (_XML_HEAD + '<worksheet xmlns="' + _NS_MAIN + '"><sheetData><row r="{}">{}</row>'.format(header_row, cells)).encode("utf-8")
+
+
+def _value_cell(ref, value):
+    """One cell of the host path, '' for a missing value.  The device path's rules (csrc/xlsx_row.h) for integers and floats."""
+    if value is None:
+        return ""
+    if isinstance(value, (bool, np.bool_)):
+        return '<c r="{}" t="b"><v>{}</v></c>'.format(ref, int(value))
+    if isinstance(value, (int, np.integer)):
+        return '<c r="{}"><v>{}</v></c>'.format(ref, int(value))
+    if isinstance(value, (float, np.floating)):
+        value = float(value)
+        if value != value:
+            return ""
+        if value in (np.inf, -np.inf):
+            return _string_cell(ref, "inf" if value > 0 else "-inf")
+        return '<c r="{}"><v>{}</v></c>'.format(ref, repr(value))
+    try:
+        import pandas as pd
+        if pd.isna(value):
+            return ""
+    except (TypeError, ValueError):
+        pass
+    return _string_cell(ref, value)
+
+
+def sheet_xml_host(df, first_row=2):
+    """A sheet's XML for a DataFrame with a RangeIndex, in plain Python: the header row ``first_row - 1`` (:func:`sheet_prefix`),
+    then a ``<row>`` per row from ``first_row`` on -- the index 0, 1, ... in column A with style 1, integers as plain decimals,
+    a float64 as its shortest round-trip text (``repr``; the exact double, not ``%.16G``), a missing value not written at all,
+    ``inf`` / ``-inf`` and every string as inline strings, booleans as ``t="b"``.  For a table the device path serves
+    (``ysmr_xlsx_sheet_device``) these are the same bytes."""
+    parts = [sheet_prefix([str(k) for k in df.columns], first_row - 1).decode("utf-8")]
+    letters = [_column_letters(k + 1) for k in range(df.shape[1])]
+    columns = [df.iloc[:, k].tolist() for k in range(df.shape[1])]       # (Python ints, floats, bools and objects)
+    for r in range(len(df)):
+        n = first_row + r
+        cells = ['<c r="A{}" s="1"><v>{}</v></c>'.format(n, r)]
+        cells.extend(_value_cell("{}{}".format(letters[k], n), columns[k][r]) for k in range(len(columns)))
+        parts.append('<row r="{}">{}</row>'.format(n, "".join(cells)))
+    parts.append(_SHEET_SUFFIX.decode("ascii"))
+    return "".join(parts).encode("utf-8")
+
+
+def xlsx_sheet_names(paths):
+    """A sheet name per path, unique in the workbook: the file name without its extension, every character Excel forbids
+    (``[ ] : * ? / \\``) as ``_``, cut to 31 characters; a name the workbook already has -- compared without regard to case,
+    as Excel does -- gets its tail replaced by ``~2``, ``~3``, ... so that it still fits."""
+    used, names = set(), []
+    for path in paths:
+        base = os.path.splitext(os.path.basename(path))[0]
+        base = "".join("_" if ch in "[]:*?/\\" else ch for ch in base)[:31] or "_"
+        name, k = base, 1
+        while name.lower() in used:
+            k += 1
+            tail = "~{}".format(k)
+            name = base[:31 - len(tail)] + tail
+        used.add(name.lower())
+        names.append(name)
+    return names
+
+
+def xlsx_sheet_devicelike(df, first_row=2, with_index=True, prefix=None, suffix=None):
+    """``ysmr_xlsx_sheet_devicelike`` on a DataFrame of the five column types: the text of the device printer
+    (csrc/xlsx_row.h) on the host, for the CPU tests.  Returns ``(bytes, wide_cells)``; None for a frame
+    :func:`table_csv_plan` refuses."""
+    import ctypes
+    from . import _lib
+    plan = table_csv_plan(df)
+    if plan is None:
+        return None
+    L = _lib.lib()
+    dtypes = plan[1]
+    prefix = sheet_prefix(list(df.columns), first_row - 1) if prefix is None else bytes(prefix)
+    suffix = _SHEET_SUFFIX if suffix is None else bytes(suffix)
+    arrays = [np.ascontiguousarray(df.iloc[:, k].to_numpy()) for k in range(len(dtypes))]
+    cols = _table_columns([a.ctypes.data for a in arrays], dtypes)
+    n = len(df)
+    cap = int(L.ysmr_xlsx_sheet_bound(n, len(dtypes), cols, first_row, int(with_index), len(prefix), len(suffix)))
+    out = np.empty(max(cap, 1), np.uint8)
+    length, wide = ctypes.c_size_t(0), ctypes.c_longlong(0)
+    _lib.check(L.ysmr_xlsx_sheet_devicelike(n, len(dtypes), cols, first_row, int(with_index), prefix, len(prefix), suffix, len(suffix),
+                                            out.ctypes.data, cap, ctypes.byref(length), ctypes.byref(wide)), "ysmr_xlsx_sheet_devicelike")
+    return out[:length.value].tobytes(), wide.value
+
+
+def xlsx_sheet_device(tensors, dtypes, n, first_row, with_index, prefix, suffix, device):
+    """``ysmr_xlsx_sheet_device`` on columns that are on ``device`` (``tensors`` as for :func:`table_format_device`).  Returns
+    ``(xml, length, wide_cells)`` -- the text as a uint8 tensor on the device, its length and the number of wide cells, read
+    back with one copy -- or None where the plan refuses."""
+    import torch
+    from . import _lib
+    L = _lib.lib()
+    cols = _table_columns([t.data_ptr() if n else 0 for t in tensors], dtypes)
+    cap = int(L.ysmr_xlsx_sheet_bound(n, len(dtypes), cols, first_row, int(with_index), len(prefix), len(suffix)))
+    ws_bytes = int(L.ysmr_xlsx_sheet_workspace_bytes(n, len(dtypes), cols, first_row, int(with_index), len(suffix)))
+    if (cap == 0 and (n or prefix or suffix)) or ws_bytes == 0:
+        return None
+    with torch.cuda.device(device):
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+        xml = torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
+        meta = torch.zeros(2, dtype=torch.int64, device=device)          # length; wide cells (low 32 bits)
+        _lib.check(L.ysmr_xlsx_sheet_device(_lib.stream_ptr(device), n, len(dtypes), cols, first_row, int(with_index), prefix, len(prefix),
+                                            suffix, len(suffix), ws.data_ptr(), ws_bytes, xml.data_ptr(), cap, meta.data_ptr(),
+                                            meta[1:].data_ptr()), "ysmr_xlsx_sheet_device")
+        length, wide = (int(v) for v in meta.cpu())
+    return xml, length, wide & 0xFFFFFFFF
+
+
+def csv_column_kinds_devicelike(data, n_columns):
+    """``ysmr_csv_column_kinds_devicelike`` on the bytes of a csv (header line included): ``(kinds, n_rows, flags)``, ``kinds``
+    a uint32 array of 17 words (``_lib.KIND_*``)."""
+    import ctypes
+    from . import _lib
+    data = bytes(data)
+    kinds = np.zeros(_lib.KIND_WORDS, np.uint32)
+    n, flags = ctypes.c_longlong(0), ctypes.c_uint32(0)
+    _lib.check(_lib.lib().ysmr_csv_column_kinds_devicelike(data, len(data), n_columns, kinds.ctypes.data, ctypes.byref(n), ctypes.byref(flags)),
+               "ysmr_csv_column_kinds_devicelike")
+    return kinds, n.value, flags.value
+
+
+def column_dtypes_of_kinds(kinds, n_columns):
+    """What ``pandas.read_csv`` infers for the columns whose kinds ``ysmr_csv_column_kinds`` gave: a list of ``numpy.int64`` (no
+    bit set) / ``numpy.float64`` (only NOT_INT / EMPTY: NaN for the empty fields), or None -- the file goes to pandas -- where a
+    line is empty or has another field count, or a column holds a field that is not a number the typed parse serves."""
+    from . import _lib
+    if int(kinds[_lib.KIND_WORDS - 1]):
+        return None
+    out = []
+    for word in (int(w) for w in kinds[:n_columns]):
+        if word & _lib.KIND_NOT_NUMBER:
+            return None
+        out.append(np.dtype(np.float64) if word else np.dtype(np.int64))
+    return out
+
+
+def xlsx_header_names(line):
+    """The header line of a csv (bytes, without its newline) -> its names, or None where pandas would not take them as they
+    stand: not UTF-8, a quote or a carriage return, more than 16 names, an empty name or one that is there twice (pandas
+    renames those)."""
+    from . import _lib
+    try:
+        names = bytes(line).decode("utf-8").split(",")
+    except UnicodeDecodeError:
+        return None
+    if any(ch in name for name in names for ch in '"\r\x00') or not 1 <= len(names) <= _lib.TABLE_MAX_COLUMNS:
+        return None
+    if any(name == "" for name in names) or len(set(names)) != len(names) or names[0].startswith("\ufeff"):
+        return None
+    return names
+
+
+def _sheet_xml_device(path, device, times):
+    """The sheet of the csv at ``path`` built on ``device``: its XML in a pinned buffer (a uint8 array, valid until the next
+    call of this thread) and whether rows were cut at ``XLSX_MAX_ROWS`` -- or None: the file is one for the host path."""
+    import time
+    import torch
+    from . import _lib
+    L = _lib.lib()
+    dev = torch.device(device)
+    clock = time.perf_counter
+    t0 = clock()
+
+    def lap(phase):
+        nonlocal t0
+        now = clock()
+        times[phase] = times.get(phase, 0.0) + now - t0
+        t0 = now
+    try:
+        with open(path, "rb", buffering=0) as fh:
+            size = os.fstat(fh.fileno()).st_size
+            ws_bytes = int(L.ysmr_csv_workspace_bytes(size))
+            if ws_bytes == 0:
+                return None
+            staged = _pinned("csv text", size)
+            view, at = memoryview(staged.numpy()), 0
+            while at < size:
+                got = fh.readinto(view[at:])
+                if not got:
+                    return None
+                at += got
+    except OSError:
+        return None
+    window = 1 << 16
+    while True:
+        head = view[:min(window, size)].tobytes().find(b"\n")
+        if head >= 0 or window >= size:
+            break
+        window *= 16
+    if head < 0:
+        return None                                     # (a header and nothing else: pandas' empty frame)
+    names = xlsx_header_names(view[:head])
+    if names is None:
+        return None
+    # the index pass refuses a file with a byte >= 0x80 anywhere, and a statistics file has one in 'Distance (µm)': the
+    # names are read, so the device gets the body behind an ASCII stand-in of the header line's length
+    staged.numpy()[:head] = ord("h")
+    lap("file read")
+    with torch.cuda.device(dev):
+        stream = _lib.stream_ptr(dev)
+        text = torch.empty((size + 255) // 256 * 256, dtype=torch.uint8, device=dev)
+        text[:size].copy_(staged, non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+        lap("upload")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        meta = torch.zeros(4 + _lib.KIND_WORDS, dtype=torch.int32, device=dev)        # lines, flags, unserved, -, the kinds
+        _lib.check(L.ysmr_csv_index(stream, text.data_ptr(), size, ws.data_ptr(), ws_bytes, meta.data_ptr(), meta[1:].data_ptr()),
+                   "ysmr_csv_index")
+        n_lines, flags = (int(v) & 0xFFFFFFFF for v in meta[:2].cpu())
+        if flags:
+            return None
+        n_all = n_lines - 1
+        _lib.check(L.ysmr_csv_column_kinds(stream, text.data_ptr(), size, ws.data_ptr(), ws_bytes, len(names), n_all, meta[4:].data_ptr()),
+                   "ysmr_csv_column_kinds")
+        kinds = meta[4:].cpu().numpy().view(np.uint32)
+        lap("index + kinds")
+        dtypes = column_dtypes_of_kinds(kinds, len(names))
+        if dtypes is None:
+            return None
+        n = min(n_all, XLSX_MAX_ROWS)
+        fields = [(name, dt, _lib.TABLE_COLUMN_TYPES[dt], _lib.CSV_EMPTY_IS_NAN if dt == np.float64 else 0) for name, dt in zip(names, dtypes)]
+        buf = torch.empty(max(8 * n * len(fields), 16), dtype=torch.uint8, device=dev)
+        pointers = [buf.data_ptr() + 8 * n * k for k in range(len(fields))]
+        arr = _csv_field_array(fields, list(range(len(fields))), pointers)
+        _lib.check(L.ysmr_csv_parse_typed(stream, text.data_ptr(), size, ws.data_ptr(), ws_bytes, len(names), len(fields), arr, n,
+                                          meta[2:].data_ptr()), "ysmr_csv_parse_typed")
+        if int(meta[2:3].cpu()[0]) & 0xFFFFFFFF:
+            return None
+        lap("parse")
+        tensors = [buf[8 * n * k:8 * n * (k + 1)] for k in range(len(fields))]
+        done = xlsx_sheet_device(tensors, dtypes, n, 2, True, sheet_prefix(names), _SHEET_SUFFIX, dev)
+        if done is None:
+            return None
+        xml, length, _wide = done
+        lap("print")
+        out = _pinned("sheet xml", length)
+        out.copy_(xml[:length], non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+        lap("download")
+    return out.numpy(), n_all > n
+
+
+def _sheet_xml_host_of(path):
+    """The host path's sheet of the csv at ``path`` (upstream's ``read_csv`` call) and whether rows were cut."""
+    import pandas as pd
+    with open(path, "r", newline="\n", encoding="utf-8") as fh:
+        df = pd.read_csv(fh, sep=",", header=0, encoding="utf-8")
+    return sheet_xml_host(df.iloc[:XLSX_MAX_ROWS]), len(df) > XLSX_MAX_ROWS
+
+
+def collate_results_csv_to_xlsx(path=None, save_path=None, csv_extension="statistics.csv", device="cuda:0", compress=False):
+    """All csv files below ``path`` that end in ``csv_extension`` as the sheets of one workbook,
+    ``<save_path or './'>/<yymmddHHMMSS>_collated_statistics.xlsx`` (helper_file.py:92-137), written without a third-party
+    writer: a sheet per file of ``find_paths(path, csv_extension)``, in that order, named by :func:`xlsx_sheet_names`; row 1
+    the column names, column A the RangeIndex, at most ``XLSX_MAX_ROWS`` data rows (one warning per file cut).  A file the
+    device reader serves -- comma separated columns that ``pandas.read_csv`` infers as int64 or float64, up to 16 of them,
+    distinct names, no quotes or carriage returns -- is read, typed and printed on ``device`` (``ysmr_csv_column_kinds``,
+    ``ysmr_csv_parse_typed``, ``ysmr_xlsx_sheet_device``); every other file is read by pandas and printed by
+    :func:`sheet_xml_host`: the same bytes where both serve a file.  ``device=None``: the host path for every file.
+    ``LAST_COLLATE`` says which path each file took.  The container is ``zipfile``'s, stored or (``compress``) deflated, every
+    entry dated 1980-01-01: the same input gives the same workbook.  Returns the workbook's path; None -- nothing written --
+    where ``path`` is None (no file dialog here) or holds no such file."""
+    import time
+    import zipfile
+    logger = _logger()
+    LAST_COLLATE.clear()
+    LAST_COLLATE_TIMES.clear()
+    if path is None:
+        logger.critical("collate_results_csv_to_xlsx needs the folder with the csv files ('path': there is no file dialog here).")
+        return None
+    if save_path is None:
+        save_path = "./"
+    file_path = os.path.join(save_path, "{}_collated_statistics.xlsx".format(datetime.now().strftime("%y%m%d%H%M%S")))
+    paths = find_paths(base_path=path, extension=csv_extension)
+    if not paths:
+        logger.warning("Could not find paths.")
+        return None
+    names = xlsx_sheet_names(paths)
+    times = LAST_COLLATE_TIMES
+    method = zipfile.ZIP_DEFLATED if compress else zipfile.ZIP_STORED
+
+    def entry(archive, name, data):
+        info = zipfile.ZipInfo(name, date_time=(1980, 1, 1, 0, 0, 0))
+        info.compress_type = method
+        t0 = time.perf_counter()
+        archive.writestr(info, data)
+        times["zip"] = times.get("zip", 0.0) + time.perf_counter() - t0
+
+    count = len(paths)
+
+    def write(archive):
+        entry(archive, "[Content_Types].xml", _XML_HEAD + (
+            '<Types xmlns="http://schemas.openxmlformats.org/package/2006/content-types">'
+            '<Default Extension="rels" ContentType="application/vnd.openxmlformats-package.relationships+xml"/>'
+            '<Default Extension="xml" ContentType="application/xml"/>'
+            '<Override PartName="/xl/workbook.xml" ContentType="application/vnd.openxmlformats-officedocument.spreadsheetml.sheet.main+xml"/>'
+            '<Override PartName="/xl/styles.xml" ContentType="application/vnd.openxmlformats-officedocument.spreadsheetml.styles+xml"/>'
+            + "".join('<Override PartName="/xl/worksheets/sheet{}.xml" ContentType="application/vnd.openxmlformats-officedocument.'
+                      'spreadsheetml.worksheet+xml"/>'.format(k + 1) for k in range(count)) + "</Types>"))
+        entry(archive, "_rels/.rels", _XML_HEAD + (
+            '<Relationships xmlns="' + _NS_PKG_REL + '"><Relationship Id="rId1" Type="' + _NS_REL + '/officeDocument" '
+            'Target="xl/workbook.xml"/></Relationships>'))
+        entry(archive, "xl/workbook.xml", _XML_HEAD + (
+            '<workbook xmlns="' + _NS_MAIN + '" xmlns:r="' + _NS_REL + '"><sheets>'
+            + "".join('<sheet name="{}" sheetId="{}" r:id="rId{}"/>'.format(_xml_text(name), k + 1, k + 1) for k, name in enumerate(names))
+            + "</sheets></workbook>"))
+        entry(archive, "xl/_rels/workbook.xml.rels", _XML_HEAD + (
+            '<Relationships xmlns="' + _NS_PKG_REL + '">'
+            + "".join('<Relationship Id="rId{}" Type="{}/worksheet" Target="worksheets/sheet{}.xml"/>'.format(k + 1, _NS_REL, k + 1)
+                      for k in range(count))
+            + '<Relationship Id="rId{}" Type="{}/styles" Target="styles.xml"/></Relationships>'.format(count + 1, _NS_REL)))
+        entry(archive, "xl/styles.xml", _STYLES_XML)
+        for k, csv_path in enumerate(paths):
+            done = _sheet_xml_device(csv_path, device, times) if device is not None else None
+            LAST_COLLATE[csv_path] = "device" if done is not None else "host"
+            if done is None:
+                t0 = time.perf_counter()
+                done = _sheet_xml_host_of(csv_path)
+                times["host sheet"] = times.get("host sheet", 0.0) + time.perf_counter() - t0
+            xml, cut = done
+            if cut:
+                logger.warning("{}: more than {} rows, the sheet holds the first {}.".format(csv_path, XLSX_MAX_ROWS, XLSX_MAX_ROWS))
+            entry(archive, "xl/worksheets/sheet{}.xml".format(k + 1), memoryview(xml))
+    try:
+        with zipfile.ZipFile(file_path, "w", method) as archive:
+            write(archive)
+    except BaseException:
+        try:                                 # (half a workbook is none: a reader would take it for the run's result)
+            os.remove(file_path)
+        except OSError:
+            pass
+        raise
+    logger.info("Collated {} file(s) into {}".format(count, file_path))
+    return file_path
 
 
 def _meta_path_of(path):

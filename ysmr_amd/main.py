@@ -3,7 +3,8 @@
 ``analyse`` runs detect-and-link (``track_bacteria``), ``select_tracks`` and the statistics of
 ``evaluate_tracks`` on the device, and with 'save video' set ``annotate_video`` writes the annotated video from the
 evaluated table; the track figures are painted on the device, the violin plots too under 'hip violin plots' (without
-that key they are skipped with a log message, like the xlsx collation).  It returns the last stage's result (``return_df=True``:
+that key they are skipped with a log message).  ``ysmr`` ends with the collated workbook under 'hip collate xlsx'
+(``helper_file.collate_results_csv_to_xlsx``; without that key there is none).  It returns the last stage's result (``return_df=True``:
 a DataFrame, or evaluate_tracks' ``(df, df_stats)``) or ``True``; ``None`` signals an error, as upstream.
 
 Independent videos are embarrassingly parallel (the reference runs one process per path,
@@ -17,7 +18,8 @@ import os
 from datetime import datetime
 
 from .annotate import annotate_video
-from .helper_file import create_results_folder, get_configs, get_loggers, metadata_file
+from .helper_file import (collate_results_csv_to_xlsx, collate_xlsx_mode, create_results_folder, get_configs, get_loggers,
+                          metadata_file)
 from .evaluate import evaluate_tracks
 from .select import select_tracks
 from .track_eval import track_bacteria
@@ -253,4 +255,12 @@ def ysmr(paths=None, settings=None, result_folder=None, multiprocess=False, stre
             logger.critical("{}".format(p))
     else:
         logger.info("Finished with all files.")
+    # the workbook of every *statistics.csv in the result folder (main.py:326-328 upstream) -- under the opt-in key
+    # 'hip collate xlsx' ('deflate': compressed entries); without it nothing is collated, as before
+    mode = collate_xlsx_mode(settings)
+    if settings["collate results csv to xlsx"] and mode:
+        try:
+            collate_results_csv_to_xlsx(result_folder, result_folder, compress=mode == "deflate")
+        except Exception as exc:  # noqa: BLE001 -- the videos are analysed: a workbook that fails must not lose their results
+            logger.exception("Could not collate the results to xlsx: {}".format(exc))
     return finished
