@@ -1,7 +1,8 @@
 """Resources of the collated workbook's kernels (csrc/xlsx.hip, and ``k_csv_kinds`` of csrc/csv.hip), read from the built
-library's gfx950 code objects (no GPU needed), as test_kernel_table_csv_resources.py does for the csv writer: all three are
-there, none needs scratch memory or spills a register -- a row's digits are kept in LDS, integers, cell references and tags are
-printed straight into their place, a line's kinds stay in registers.  The row printer's staging is dynamic LDS of at most
+library's gfx950 code objects (no GPU needed), as test_kernel_table_csv_resources.py does for the csv writer, which also holds
+the packing kernel the two printers share: both are there, none needs scratch memory or spills a register -- a row's digits are
+kept in LDS, integers, cell references and tags are printed straight into their place, a line's kinds stay in registers.  The
+row printer's staging is dynamic LDS of at most
 what ``ysmr_xlsx_sheet_geometry`` reports; its static LDS (row offsets, a lane's digits) is a few KiB, and both together stay
 inside the 64 KiB a workgroup may have.  ``k_csv_kinds`` holds the parse's staged span and nothing else."""
 import ctypes
@@ -9,7 +10,7 @@ import re
 
 import test_kernel_png_resources as base
 
-KERNELS = ("k_xlsx_rows", "k_xlsx_pack", "k_csv_kinds")
+KERNELS = ("k_xlsx_rows", "k_csv_kinds")
 
 
 def test_xlsx_kernels_need_no_scratch_and_only_the_staging_lds(tmp_path, monkeypatch):

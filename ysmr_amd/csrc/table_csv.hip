@@ -14,8 +14,12 @@
 //                     for HBM compacted, as one piece, in 16-byte stores a lane each
 //   (prim.h scan)     inclusive sums of the pieces' lengths
 //   k_table_pack      a workgroup per piece: the piece to its place behind the header, 16-byte stores on the destination's
-//                     alignment, the source realigned in registers
+//                     alignment, the source realigned in registers; one more workgroup for a suffix behind the last piece
+//                     (the csv has none) and the length
 // The text is a function of the input alone: no place comes from an atomic.  The host-only arithmetic is table_csv_plan.h.
+// Who owns what: this source owns the csv line (table_csv_row.h) and the loop of k_table_rows over its cells, and it DEFINES
+// what table_print.h declares for every printer of typed columns -- check_columns, types_of, the wide-cell kernels behind
+// launch_wide_cells, k_table_pack behind launch_pack.  The row kernel's tail and the float64 cell are table_print.h's templates.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,7 +32,7 @@
 #include "fmt.h"
 #include "table_csv_plan.h"
 #include "table_csv_row.h"
-#include "table_wide.h"
+#include "table_print.h"
 
 static_assert(tablep::SCAN_TILE == ysmr::prim::SCAN_TILE, "table_csv_plan.h restates prim.h's scan tile");
 static_assert(tablep::COL_U32 == YSMR_COL_U32 && tablep::COL_I64 == YSMR_COL_I64 && tablep::COL_I32 == YSMR_COL_I32 &&
@@ -39,11 +43,7 @@ namespace {
 constexpr int R = tablep::ROWS_PER_GROUP;
 constexpr int WIDE_GRID = 256;                     // workgroups of k_table_wide, a wave each
 
-struct Columns {
-    const void *data[tablep::MAX_COLUMNS];
-    int32_t type[tablep::MAX_COLUMNS];
-    int32_t n;
-};
+using tablep::Columns;
 
 __global__ __launch_bounds__(256) void k_table_prepass(Columns cols, long long n_rows, uint32_t *__restrict__ wide_count)
 {
@@ -104,65 +104,30 @@ __global__ __launch_bounds__(R) void k_table_rows(Columns cols, long long n_rows
         for (int c = 0; c < cols.n; ++c) {
             const void *data = cols.data[c];
             const int type = cols.type[c];
-            if (type == YSMR_COL_F64) {
-                const double v = ((const double *)data)[row];
-                if (ysmr_fmt::is_wide_cell(v)) {
-                    const char *slot = slots + (size_t)wide_at * tablep::WIDE_SLOT;
-                    const int l = slot_len[wide_at];
-                    for (int b = 0; b < l; ++b) q[b] = slot[b];
-                    q += l;
-                    ++wide_at;
-                } else q = ysmr_fmt::put_f64_steady(q, v, s_digits[lane]);
-            } else q = tablep::put_int_cell(q, type, data, row);
+            if (type == YSMR_COL_F64)
+                q = tablep::put_f64_cell(q, ((const double *)data)[row], slots, slot_len, wide_at, s_digits[lane]);
+            else q = tablep::put_int_cell(q, type, data, row);
             *q++ = ',';
         }
         len = (uint32_t)(tablep::end_line(mine, q) - mine);
     }
-    // where every row goes in the piece
-    const uint32_t incl = ysmr::prim::wave_inclusive_sum(len);
-    if ((lane & 63) == 63) s_wave[lane >> 6] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-    for (int w = 0; w < (lane >> 6); ++w) before += s_wave[w];
-    if (lane == 0) s_off[0] = 0u;
-    s_off[lane + 1] = before + incl;
-    __syncthreads();
-    const uint32_t total = s_off[R];
-    if (lane == 0) piece_len[blockIdx.x] = total;
-    // the piece leaves compacted: lane after lane sixteen consecutive bytes of it, gathered from the rows they lie in
-    uint4 *const out = (uint4 *)(pieces + (size_t)blockIdx.x * piece_stride);
-    for (uint32_t chunk = (uint32_t)lane; chunk * 16u < total; chunk += (uint32_t)R) {
-        const uint32_t first = chunk * 16u;
-        int r = 0;
-#pragma unroll
-        for (int step = R / 2; step; step >>= 1)                 // the last row that begins at or before `first`
-            if (s_off[r + step] <= first) r += step;
-        uint32_t pos = first - s_off[r], row_len = s_off[r + 1] - s_off[r];
-        const char *src = s_text + (size_t)r * row_stride;
-        uint32_t word[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            uint32_t w = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                if (first + 4u * k + b < total) {
-                    w |= (uint32_t)(uint8_t)src[pos] << (8 * b);
-                    if (++pos == row_len && r + 1 < R) { ++r; src += row_stride; pos = 0; row_len = s_off[r + 1] - s_off[r]; }
-                }
-            }
-            word[k] = w;
-        }
-        out[chunk] = make_uint4(word[0], word[1], word[2], word[3]);
-    }
+    tablep::store_piece<R>(len, s_text, row_stride, s_off, s_wave, pieces, piece_stride, piece_len);
 }
 
-// (header: it is in csv[0, head) already)
+// (the head: it is in out[0, head) already.)  Workgroups 0 .. n_pieces - 1 move a piece each; workgroup n_pieces writes the
+// suffix behind the last piece, and the length
 __global__ __launch_bounds__(256) void k_table_pack(const char *__restrict__ pieces, size_t piece_stride, const uint32_t *__restrict__ piece_len,
                                                     const uint32_t *__restrict__ piece_incl, unsigned n_pieces, size_t head,
-                                                    char *__restrict__ csv, size_t capacity, unsigned long long *csv_length)
+                                                    const char *__restrict__ suffix, uint32_t suffix_bytes, char *__restrict__ out,
+                                                    size_t capacity, unsigned long long *out_length)
 {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *csv_length = (unsigned long long)head + (n_pieces ? piece_incl[n_pieces - 1] : 0u);
-    if (blockIdx.x >= n_pieces) return;
+    if (blockIdx.x >= n_pieces) {
+        const size_t at = head + (n_pieces ? piece_incl[n_pieces - 1] : 0u);
+        for (uint32_t b = threadIdx.x; b < suffix_bytes; b += 256u)
+            if (at + b < capacity) out[at + b] = suffix[b];
+        if (threadIdx.x == 0) *out_length = (unsigned long long)at + suffix_bytes;
+        return;
+    }
     const uint32_t len = piece_len[blockIdx.x];
     const size_t at = head + (size_t)(piece_incl[blockIdx.x] - len);
     const char *src = pieces + (size_t)blockIdx.x * piece_stride;          // 16-byte aligned, 16 bytes of slack behind the text
@@ -170,12 +135,12 @@ __global__ __launch_bounds__(256) void k_table_pack(const char *__restrict__ pie
     const uint32_t lead = to_boundary < len ? to_boundary : len;
     const uint32_t body = (len - lead) / 16u, tail_at = lead + body * 16u;
     for (uint32_t b = threadIdx.x; b < lead; b += 256u)
-        if (at + b < capacity) csv[at + b] = src[b];
+        if (at + b < capacity) out[at + b] = src[b];
     for (uint32_t b = tail_at + threadIdx.x; b < len; b += 256u)
-        if (at + b < capacity) csv[at + b] = src[b];
+        if (at + b < capacity) out[at + b] = src[b];
     const uint32_t shift = (lead & 3u) * 8u;
     const uint32_t *words = (const uint32_t *)src + (lead >> 2);
-    uint4 *dst = (uint4 *)(csv + at + lead);
+    uint4 *dst = (uint4 *)(out + at + lead);
     for (uint32_t i = threadIdx.x; i < body; i += 256u) {
         uint32_t w[5];
 #pragma unroll
@@ -185,21 +150,6 @@ __global__ __launch_bounds__(256) void k_table_pack(const char *__restrict__ pie
         for (int k = 0; k < 4; ++k) o[k] = (uint32_t)((((uint64_t)w[k + 1] << 32) | w[k]) >> shift);
         if (at + lead + 16ull * i + 16ull <= capacity) dst[i] = make_uint4(o[0], o[1], o[2], o[3]);
     }
-}
-
-// the types of the columns, or why the call is refused
-int check_columns(int n_columns, const ysmr_table_column *columns, long long n_rows, int32_t *types)
-{
-    if (n_columns < 1 || n_columns > tablep::MAX_COLUMNS)
-        return ysmr::fail(YSMR_ERR_ARG, "n_columns must be in 1..%d, got %d", tablep::MAX_COLUMNS, n_columns);
-    if (!columns) return ysmr::fail(YSMR_ERR_ARG, "columns must be set");
-    for (int c = 0; c < n_columns; ++c) {
-        if (columns[c].type < 0 || columns[c].type >= tablep::N_TYPES)
-            return ysmr::fail(YSMR_ERR_ARG, "column %d: unknown type %d", c, (int)columns[c].type);
-        if (n_rows > 0 && !columns[c].data) return ysmr::fail(YSMR_ERR_ARG, "column %d: data is NULL", c);
-        types[c] = columns[c].type;
-    }
-    return YSMR_OK;
 }
 
 int check_bound(long long n_rows, int n_columns, const int32_t *types, size_t header_bytes, size_t capacity, size_t &bound)
@@ -216,6 +166,28 @@ int check_bound(long long n_rows, int n_columns, const int32_t *types, size_t he
 
 }  // namespace
 
+// the types of the columns, or why the call is refused
+int tablep::check_columns(int n_columns, const ysmr_table_column *columns, long long n_rows, int32_t *types)
+{
+    if (n_columns < 1 || n_columns > tablep::MAX_COLUMNS)
+        return ysmr::fail(YSMR_ERR_ARG, "n_columns must be in 1..%d, got %d", tablep::MAX_COLUMNS, n_columns);
+    if (!columns) return ysmr::fail(YSMR_ERR_ARG, "columns must be set");
+    for (int c = 0; c < n_columns; ++c) {
+        if (columns[c].type < 0 || columns[c].type >= tablep::N_TYPES)
+            return ysmr::fail(YSMR_ERR_ARG, "column %d: unknown type %d", c, (int)columns[c].type);
+        if (n_rows > 0 && !columns[c].data) return ysmr::fail(YSMR_ERR_ARG, "column %d: data is NULL", c);
+        types[c] = columns[c].type;
+    }
+    return YSMR_OK;
+}
+
+bool tablep::types_of(int n_columns, const ysmr_table_column *columns, int32_t *types)
+{
+    if (n_columns < 1 || n_columns > tablep::MAX_COLUMNS || !columns) return false;
+    for (int c = 0; c < n_columns; ++c) types[c] = columns[c].type;
+    return true;
+}
+
 void tablep::launch_wide_cells(hipStream_t st, int n_columns, const void *const *data, const int32_t *types, long long n_rows,
                                uint32_t *wide_incl, uint32_t *wide_temp, char *slots, uint8_t *slot_len, uint32_t *wide_cells_dev)
 {
@@ -228,16 +200,24 @@ void tablep::launch_wide_cells(hipStream_t st, int n_columns, const void *const 
     hipLaunchKernelGGL(k_table_wide, dim3(WIDE_GRID), dim3(64), 0, st, cols, n_rows, (const uint32_t *)wide_incl, slots, slot_len, wide_cells_dev);
 }
 
+void tablep::launch_pack(hipStream_t st, const char *pieces, size_t piece_stride, const uint32_t *piece_len, const uint32_t *piece_incl,
+                         unsigned n_pieces, size_t head, const char *suffix_dev, uint32_t suffix_bytes, char *out, size_t capacity,
+                         unsigned long long *length_dev)
+{
+    hipLaunchKernelGGL(k_table_pack, dim3(n_pieces + 1u), dim3(256), 0, st, pieces, piece_stride, piece_len, piece_incl, n_pieces, head,
+                       suffix_dev, suffix_bytes, out, capacity, length_dev);
+}
+
 extern "C" {
 
 size_t ysmr_table_csv_bound(long long n_rows, int n_columns, const ysmr_table_column *columns, size_t header_bytes)
 {
     int32_t types[tablep::MAX_COLUMNS];
-    if (n_columns < 1 || n_columns > tablep::MAX_COLUMNS || !columns) return 0;
-    for (int c = 0; c < n_columns; ++c) types[c] = columns[c].type;
     int row_bytes = 0, n_f64 = 0;
     size_t bound = 0;
-    if (!tablep::row_of(n_columns, types, row_bytes, n_f64) || !tablep::bound_of(n_rows, row_bytes, header_bytes, bound)) return 0;
+    if (!tablep::types_of(n_columns, columns, types) || !tablep::row_of(n_columns, types, row_bytes, n_f64) ||
+        !tablep::bound_of(n_rows, row_bytes, header_bytes, bound))
+        return 0;
     return bound;
 }
 
@@ -245,10 +225,8 @@ size_t ysmr_table_csv_bound(long long n_rows, int n_columns, const ysmr_table_co
 size_t ysmr_table_format_workspace_bytes(long long n_rows, int n_columns, const ysmr_table_column *columns)
 {
     int32_t types[tablep::MAX_COLUMNS];
-    if (n_columns < 1 || n_columns > tablep::MAX_COLUMNS || !columns) return 0;
-    for (int c = 0; c < n_columns; ++c) types[c] = columns[c].type;
     int row_bytes = 0, n_f64 = 0;
-    if (!tablep::row_of(n_columns, types, row_bytes, n_f64)) return 0;
+    if (!tablep::types_of(n_columns, columns, types) || !tablep::row_of(n_columns, types, row_bytes, n_f64)) return 0;
     if (n_rows == 0) return 256;
     tablep::Plan p{};
     return tablep::plan_of(n_rows, n_columns, types, p) ? p.total : 0;
@@ -265,7 +243,7 @@ int ysmr_table_format_device(void *stream, long long n_rows, int n_columns, cons
                              unsigned long long *csv_length_dev, uint32_t *wide_cells_dev)
 {
     int32_t types[tablep::MAX_COLUMNS];
-    if (const int rc = check_columns(n_columns, columns, n_rows, types)) return rc;
+    if (const int rc = tablep::check_columns(n_columns, columns, n_rows, types)) return rc;
     if (!csv_dev || !csv_length_dev || !wide_cells_dev || (header_bytes && !header_host))
         return ysmr::fail(YSMR_ERR_ARG, "header_host, csv_dev, csv_length_dev and wide_cells_dev must be set");
     size_t bound = 0;
@@ -281,28 +259,25 @@ int ysmr_table_format_device(void *stream, long long n_rows, int n_columns, cons
     hipStream_t st = (hipStream_t)stream;
     if (header_bytes) YSMR_HIP_CHECK(hipMemcpyAsync(csv_dev, header_host, header_bytes, hipMemcpyHostToDevice, st));
     char *w = (char *)workspace_dev;
+    const bool wide = p.n_f64 && n_rows;
+    if (!wide) YSMR_HIP_CHECK(hipMemsetAsync(wide_cells_dev, 0, sizeof(uint32_t), st));
+    uint32_t *piece_len = (uint32_t *)(w + p.piece_len), *piece_incl = (uint32_t *)(w + p.piece_incl);
     if (n_rows) {
         Columns cols{};
         cols.n = n_columns;
         for (int c = 0; c < n_columns; ++c) { cols.data[c] = columns[c].data; cols.type[c] = types[c]; }
-        uint32_t *wide_incl = p.n_f64 ? (uint32_t *)(w + p.wide_incl) : nullptr;
+        uint32_t *wide_incl = wide ? (uint32_t *)(w + p.wide_incl) : nullptr;
         char *slots = w + p.wide_slots;
         uint8_t *slot_len = (uint8_t *)(w + p.wide_len);
-        if (p.n_f64) tablep::launch_wide_cells(st, n_columns, cols.data, cols.type, n_rows, wide_incl, (uint32_t *)(w + p.wide_temp), slots, slot_len,
-                                               wide_cells_dev);
-        else YSMR_HIP_CHECK(hipMemsetAsync(wide_cells_dev, 0, sizeof(uint32_t), st));
-        uint32_t *piece_len = (uint32_t *)(w + p.piece_len), *piece_incl = (uint32_t *)(w + p.piece_incl);
+        if (wide) tablep::launch_wide_cells(st, n_columns, cols.data, cols.type, n_rows, wide_incl, (uint32_t *)(w + p.wide_temp), slots, slot_len,
+                                            wide_cells_dev);
         hipLaunchKernelGGL(k_table_rows, dim3((unsigned)p.groups), dim3(R), (size_t)R * p.row_stride, st, cols, n_rows, p.row_stride,
                            (const uint32_t *)wide_incl, (const char *)slots, (const uint8_t *)slot_len, w + p.pieces, p.piece_stride, piece_len);
         ysmr::prim::inclusive_scan_u32(st, piece_len, piece_incl, p.groups, (uint32_t *)(w + p.piece_temp));
-        hipLaunchKernelGGL(k_table_pack, dim3((unsigned)p.groups), dim3(256), 0, st, (const char *)(w + p.pieces), p.piece_stride,
-                           (const uint32_t *)piece_len, (const uint32_t *)piece_incl, (unsigned)p.groups, header_bytes, csv_dev, csv_capacity,
-                           csv_length_dev);
-    } else {
-        YSMR_HIP_CHECK(hipMemsetAsync(wide_cells_dev, 0, sizeof(uint32_t), st));
-        hipLaunchKernelGGL(k_table_pack, dim3(1), dim3(256), 0, st, (const char *)nullptr, (size_t)0, (const uint32_t *)nullptr,
-                           (const uint32_t *)nullptr, 0u, header_bytes, csv_dev, csv_capacity, csv_length_dev);
     }
+    // (no row: p is empty, no piece, and the packing launch writes the header's length alone)
+    tablep::launch_pack(st, w + p.pieces, p.piece_stride, piece_len, piece_incl, (unsigned)p.groups, header_bytes, nullptr, 0, csv_dev, csv_capacity,
+                        csv_length_dev);
     YSMR_LAUNCH_CHECK();
     return YSMR_OK;
 }
@@ -312,7 +287,7 @@ int ysmr_table_format_devicelike(long long n_rows, int n_columns, const ysmr_tab
                                  char *out, size_t out_capacity, size_t *out_length, long long *wide_cells)
 {
     int32_t types[tablep::MAX_COLUMNS];
-    if (const int rc = check_columns(n_columns, columns, n_rows, types)) return rc;
+    if (const int rc = tablep::check_columns(n_columns, columns, n_rows, types)) return rc;
     if (!out || !out_length || !wide_cells || (header_bytes && !header))
         return ysmr::fail(YSMR_ERR_ARG, "header, out, out_length and wide_cells must be set");
     size_t bound = 0;

@@ -24,12 +24,12 @@ constexpr int SCAN_TILE = 2048;                                      // prim.h: 
 constexpr size_t MAX_TEXT = 0xFFFFFFFFull;
 
 struct Plan {
-    int row_bytes;          // sum of (width + 1) over the columns: the longest line
+    int row_bytes;          // the longest row the declared types can give (csv: the sum of (width + 1) over the columns)
     int row_stride;         // ... rounded up to 4: a row's place in the staging
     int n_f64;              // float64 columns: those that may hold wide cells
     size_t groups;          // workgroups of the row printer = pieces
     size_t piece_stride;    // bytes between two pieces in the workspace (a multiple of 16, with 16 bytes of slack behind the text)
-    size_t wide_incl, wide_temp, wide_slots, wide_len, piece_len, piece_incl, piece_temp, pieces, total;
+    size_t suffix, wide_incl, wide_temp, wide_slots, wide_len, piece_len, piece_incl, piece_temp, pieces, total;   // layout_of
 };
 
 inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
@@ -71,15 +71,12 @@ inline bool bound_of(long long n_rows, int row_bytes, size_t header_bytes, size_
     return true;
 }
 
-// the workspace of n_rows > 0 rows (n_rows = 0 needs none); false as bound_of with no header
-inline bool plan_of(long long n_rows, int n_columns, const int32_t *types, Plan &p)
+// The workspace's areas, one layout for the two printers: `suffix` (suffix_area bytes: table_csv.hip has none, xlsx.hip keeps
+// its sheet's end there), the wide cells' counts, scan words, slots and lengths, the pieces' lengths, sums and scan words, the
+// pieces.  n rows of n_f64 float64 columns whose text fits MAX_TEXT (so n * n_f64 is far from overflow); n = 0 is served and
+// has the suffix area alone.  false: a size beyond size_t
+inline bool layout_of(size_t n, int n_f64, size_t groups, size_t piece_stride, size_t suffix_area, Plan &p)
 {
-    size_t text;
-    if (!row_of(n_columns, types, p.row_bytes, p.n_f64) || n_rows <= 0 || !bound_of(n_rows, p.row_bytes, 0, text)) return false;
-    const size_t n = (size_t)n_rows;
-    p.row_stride = (p.row_bytes + 3) / 4 * 4;
-    p.groups = (n + ROWS_PER_GROUP - 1) / ROWS_PER_GROUP;
-    p.piece_stride = ((size_t)ROWS_PER_GROUP * (size_t)p.row_bytes + 15) / 16 * 16 + 16;
     size_t at = 0;
     bool fits = true;
     auto take = [&](size_t count, size_t each) {
@@ -89,18 +86,31 @@ inline bool plan_of(long long n_rows, int n_columns, const int32_t *types, Plan 
         return here;
     };
     // (every float64 cell may be a wide one, and the host is not asked in between: the side slots are sized for that)
-    size_t cells;
-    if (__builtin_mul_overflow(n, (size_t)p.n_f64, &cells)) return false;
-    p.wide_incl = take(p.n_f64 ? n : 0, sizeof(uint32_t));               // wide cells per row, then their inclusive sums
-    p.wide_temp = take(p.n_f64 ? scan_words(n) : 0, sizeof(uint32_t));
+    const bool wide = n_f64 && n;
+    const size_t cells = n * (size_t)n_f64;
+    p.suffix = take(suffix_area, 1);
+    p.wide_incl = take(wide ? n : 0, sizeof(uint32_t));                  // wide cells per row, then their inclusive sums
+    p.wide_temp = take(wide ? scan_words(n) : 0, sizeof(uint32_t));
     p.wide_slots = take(cells, WIDE_SLOT);
     p.wide_len = take(cells, 1);
-    p.piece_len = take(p.groups, sizeof(uint32_t));
-    p.piece_incl = take(p.groups, sizeof(uint32_t));
-    p.piece_temp = take(scan_words(p.groups), sizeof(uint32_t));
-    p.pieces = take(p.groups, p.piece_stride);
+    p.piece_len = take(groups, sizeof(uint32_t));
+    p.piece_incl = take(groups, sizeof(uint32_t));
+    p.piece_temp = take(n ? scan_words(groups) : 0, sizeof(uint32_t));
+    p.pieces = take(groups, piece_stride);
     p.total = at;
     return fits;
+}
+
+// the workspace of n_rows > 0 rows (n_rows = 0 needs none); false as bound_of with no header
+inline bool plan_of(long long n_rows, int n_columns, const int32_t *types, Plan &p)
+{
+    size_t text;
+    if (!row_of(n_columns, types, p.row_bytes, p.n_f64) || n_rows <= 0 || !bound_of(n_rows, p.row_bytes, 0, text)) return false;
+    const size_t n = (size_t)n_rows;
+    p.row_stride = (p.row_bytes + 3) / 4 * 4;
+    p.groups = (n + ROWS_PER_GROUP - 1) / ROWS_PER_GROUP;
+    p.piece_stride = ((size_t)ROWS_PER_GROUP * (size_t)p.row_bytes + 15) / 16 * 16 + 16;
+    return layout_of(n, p.n_f64, p.groups, p.piece_stride, 0, p);
 }
 
 }  // namespace tablep

@@ -1,15 +1,16 @@
 // libysmr_hip -- a table of typed columns as the rows of a worksheet of an .xlsx workbook (helper_file.py:92-137 upstream:
 // collate_results_csv_to_xlsx, DataFrame.to_excel of every `*statistics.csv`), printed on the device from columns that are
-// there.  The structure is table_csv.hip's, the row is xlsx_row.h's instead of a csv line:
-//   (table_wide.h)    the wide float64 cells into their side slots: table_csv.hip's pre-pass, scan and wide printer as they are
+// there.
+//   (launch_wide_cells) the wide float64 cells into their side slots: table_csv.hip's pre-pass, scan and wide printer
 //   k_xlsx_rows       a lane per row, 64 rows (a wave) per workgroup: every value is printed once, straight into the row's place
-//                     in LDS (a stride of the longest row the DECLARED types can give), wide cells copied from their slots; a
-//                     prefix sum over the rows' lengths (wave shuffles) and the workgroup's text leaves for HBM compacted, as
-//                     one piece, in 16-byte stores a lane each
+//                     in LDS (a stride of the longest row the DECLARED types can give), wide cells copied from their slots;
+//                     then table_print.h's tail: the prefix sum over the rows' lengths and the compacted piece
 //   (prim.h scan)     inclusive sums of the pieces' lengths
-//   k_xlsx_pack       a workgroup per piece: the piece to its place behind the prefix, 16-byte stores on the destination's
-//                     alignment, the source realigned in registers; the suffix behind the last piece, and the length
-// The text is a function of the input alone: no place comes from an atomic.  The host-only arithmetic is xlsx_plan.h.
+//   (launch_pack)     table_csv.hip's k_table_pack: the pieces behind the prefix, the suffix behind the last piece, the length
+// Who owns what: this source owns the worksheet row (xlsx_row.h), the loop of k_xlsx_rows over its cells, and the sheet's
+// bound and geometry (xlsx_plan.h).  Staging, compaction, the wide cells, the packing kernel, the column checks and the
+// workspace layout are table_print.h's and table_csv_plan.h's, shared with the csv printer.
+// The text is a function of the input alone: no place comes from an atomic.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -17,20 +18,17 @@
 #include "common.h"
 #include "prim.h"
 #include "fmt.h"
-#include "table_wide.h"
+#include "table_print.h"
 #include "xlsx_plan.h"
 #include "xlsx_row.h"
 
 namespace {
 
 constexpr int R = xlsxp::ROWS_PER_GROUP;
-static_assert(R == 64, "k_xlsx_rows is one wave: its prefix sum is wave_inclusive_sum alone");
-
-struct Columns {
-    const void *data[xlsxp::MAX_COLUMNS];
-    int32_t type[xlsxp::MAX_COLUMNS];
-    int32_t n;
-};
+static_assert(R == 64, "k_xlsx_rows is one wave: the shared tail needs no s_wave and one barrier");
+using tablep::Columns;
+using tablep::check_columns;
+using tablep::types_of;
 
 extern __shared__ __align__(16) char s_text[];      // R rows of row_stride bytes
 
@@ -59,13 +57,7 @@ __global__ __launch_bounds__(R) void k_xlsx_rows(Columns cols, long long n_rows,
                 const double v = ((const double *)data)[row];
                 if (xlsxp::is_nan(v)) continue;
                 q = xlsxp::cell_open(q, column, sheet_row, xlsxp::is_inf(v));
-                if (ysmr_fmt::is_wide_cell(v)) {
-                    const char *slot = slots + (size_t)wide_at * tablep::WIDE_SLOT;
-                    const int l = slot_len[wide_at];
-                    for (int b = 0; b < l; ++b) q[b] = slot[b];
-                    q += l;
-                    ++wide_at;
-                } else q = ysmr_fmt::put_f64_steady(q, v, s_digits[lane]);
+                q = tablep::put_f64_cell(q, v, slots, slot_len, wide_at, s_digits[lane]);
             } else {
                 q = xlsxp::cell_open(q, column, sheet_row, false);
                 q = tablep::put_int_cell(q, type, data, row);
@@ -74,90 +66,7 @@ __global__ __launch_bounds__(R) void k_xlsx_rows(Columns cols, long long n_rows,
         }
         len = (uint32_t)(xlsxp::row_close(q) - mine);
     }
-    // where every row goes in the piece
-    const uint32_t incl = ysmr::prim::wave_inclusive_sum(len);
-    if (lane == 0) s_off[0] = 0u;
-    s_off[lane + 1] = incl;
-    __syncthreads();
-    const uint32_t total = s_off[R];
-    if (lane == 0) piece_len[blockIdx.x] = total;
-    // the piece leaves compacted: lane after lane sixteen consecutive bytes of it, gathered from the rows they lie in
-    uint4 *const out = (uint4 *)(pieces + (size_t)blockIdx.x * piece_stride);
-    for (uint32_t chunk = (uint32_t)lane; chunk * 16u < total; chunk += (uint32_t)R) {
-        const uint32_t first = chunk * 16u;
-        int r = 0;
-#pragma unroll
-        for (int step = R / 2; step; step >>= 1)                 // the last row that begins at or before `first`
-            if (s_off[r + step] <= first) r += step;
-        uint32_t pos = first - s_off[r], row_len = s_off[r + 1] - s_off[r];
-        const char *src = s_text + (size_t)r * row_stride;
-        uint32_t word[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            uint32_t w = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                if (first + 4u * k + b < total) {
-                    w |= (uint32_t)(uint8_t)src[pos] << (8 * b);
-                    if (++pos == row_len && r + 1 < R) { ++r; src += row_stride; pos = 0; row_len = s_off[r + 1] - s_off[r]; }
-                }
-            }
-            word[k] = w;
-        }
-        out[chunk] = make_uint4(word[0], word[1], word[2], word[3]);
-    }
-}
-
-// (prefix: it is in xml[0, head) already.)  Workgroups 0 .. n_pieces - 1 move a piece each, workgroup n_pieces the suffix
-__global__ __launch_bounds__(256) void k_xlsx_pack(const char *__restrict__ pieces, size_t piece_stride, const uint32_t *__restrict__ piece_len,
-                                                   const uint32_t *__restrict__ piece_incl, unsigned n_pieces, size_t head,
-                                                   const char *__restrict__ suffix, uint32_t suffix_bytes, char *__restrict__ xml,
-                                                   size_t capacity, unsigned long long *xml_length)
-{
-    if (blockIdx.x >= n_pieces) {
-        const size_t at = head + (n_pieces ? piece_incl[n_pieces - 1] : 0u);
-        for (uint32_t b = threadIdx.x; b < suffix_bytes; b += 256u)
-            if (at + b < capacity) xml[at + b] = suffix[b];
-        if (threadIdx.x == 0) *xml_length = (unsigned long long)at + suffix_bytes;
-        return;
-    }
-    const uint32_t len = piece_len[blockIdx.x];
-    const size_t at = head + (size_t)(piece_incl[blockIdx.x] - len);
-    const char *src = pieces + (size_t)blockIdx.x * piece_stride;          // 16-byte aligned, 16 bytes of slack behind the text
-    const uint32_t to_boundary = (uint32_t)((16u - (at & 15u)) & 15u);
-    const uint32_t lead = to_boundary < len ? to_boundary : len;
-    const uint32_t body = (len - lead) / 16u, tail_at = lead + body * 16u;
-    for (uint32_t b = threadIdx.x; b < lead; b += 256u)
-        if (at + b < capacity) xml[at + b] = src[b];
-    for (uint32_t b = tail_at + threadIdx.x; b < len; b += 256u)
-        if (at + b < capacity) xml[at + b] = src[b];
-    const uint32_t shift = (lead & 3u) * 8u;
-    const uint32_t *words = (const uint32_t *)src + (lead >> 2);
-    uint4 *dst = (uint4 *)(xml + at + lead);
-    for (uint32_t i = threadIdx.x; i < body; i += 256u) {
-        uint32_t w[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) w[k] = words[4u * i + k];
-        uint32_t o[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = (uint32_t)((((uint64_t)w[k + 1] << 32) | w[k]) >> shift);
-        if (at + lead + 16ull * i + 16ull <= capacity) dst[i] = make_uint4(o[0], o[1], o[2], o[3]);
-    }
-}
-
-// the types of the columns, or why the call is refused
-int check_columns(int n_columns, const ysmr_table_column *columns, long long n_rows, int32_t *types)
-{
-    if (n_columns < 1 || n_columns > xlsxp::MAX_COLUMNS)
-        return ysmr::fail(YSMR_ERR_ARG, "n_columns must be in 1..%d, got %d", xlsxp::MAX_COLUMNS, n_columns);
-    if (!columns) return ysmr::fail(YSMR_ERR_ARG, "columns must be set");
-    for (int c = 0; c < n_columns; ++c) {
-        if (columns[c].type < 0 || columns[c].type >= tablep::N_TYPES)
-            return ysmr::fail(YSMR_ERR_ARG, "column %d: unknown type %d", c, (int)columns[c].type);
-        if (n_rows > 0 && !columns[c].data) return ysmr::fail(YSMR_ERR_ARG, "column %d: data is NULL", c);
-        types[c] = columns[c].type;
-    }
-    return YSMR_OK;
+    tablep::store_piece<R>(len, s_text, row_stride, s_off, nullptr, pieces, piece_stride, piece_len);
 }
 
 int check_bound(long long n_rows, long long first_row, int n_columns, const int32_t *types, bool with_index, size_t prefix_bytes,
@@ -171,13 +80,6 @@ int check_bound(long long n_rows, long long first_row, int n_columns, const int3
                           row_bytes, prefix_bytes, suffix_bytes);
     if (capacity < bound) return ysmr::fail(YSMR_ERR_CAPACITY, "sheet buffer too small: %zu < %zu bytes", capacity, bound);
     return YSMR_OK;
-}
-
-bool types_of(int n_columns, const ysmr_table_column *columns, int32_t *types)
-{
-    if (n_columns < 1 || n_columns > xlsxp::MAX_COLUMNS || !columns) return false;
-    for (int c = 0; c < n_columns; ++c) types[c] = columns[c].type;
-    return true;
 }
 
 }  // namespace
@@ -250,9 +152,8 @@ int ysmr_xlsx_sheet_device(void *stream, long long n_rows, int n_columns, const 
                            w + p.pieces, p.piece_stride, piece_len);
         ysmr::prim::inclusive_scan_u32(st, piece_len, piece_incl, p.groups, (uint32_t *)(w + p.piece_temp));
     }
-    hipLaunchKernelGGL(k_xlsx_pack, dim3((unsigned)p.groups + 1u), dim3(256), 0, st, (const char *)(w + p.pieces), p.piece_stride,
-                       (const uint32_t *)piece_len, (const uint32_t *)piece_incl, (unsigned)p.groups, prefix_bytes, (const char *)(w + p.suffix),
-                       (uint32_t)suffix_bytes, xml_dev, xml_capacity, xml_length_dev);
+    tablep::launch_pack(st, w + p.pieces, p.piece_stride, piece_len, piece_incl, (unsigned)p.groups, prefix_bytes, w + p.suffix, (uint32_t)suffix_bytes,
+                        xml_dev, xml_capacity, xml_length_dev);
     YSMR_LAUNCH_CHECK();
     return YSMR_OK;
 }

@@ -32,14 +32,7 @@ constexpr int STAGED_BYTES = ROWS_PER_GROUP * MAX_ROW_STRIDE;
 static_assert(STAGED_BYTES + 4096 <= 65536, "the staging of the widest row, the offsets and the digits fit a workgroup's LDS");
 constexpr size_t MAX_TEXT = tablep::MAX_TEXT;               // byte offsets and counts are 32-bit numbers in the scans
 
-struct Plan {
-    int row_bytes;          // the longest row of the declared types
-    int row_stride;         // ... rounded up to 4: a row's place in the staging
-    int n_f64;              // float64 columns: those that may hold wide cells
-    size_t groups;          // workgroups of the row printer = pieces
-    size_t piece_stride;    // bytes between two pieces in the workspace (a multiple of 16, with 16 bytes of slack behind the text)
-    size_t suffix, wide_incl, wide_temp, wide_slots, wide_len, piece_len, piece_incl, piece_temp, pieces, total;
-};
+using Plan = tablep::Plan;                                  // (its `suffix` area holds the sheet's end for the packing launch)
 
 // table row 0 is sheet row first_row: false where a row would lie outside the sheet
 inline bool rows_fit(long long n_rows, long long first_row)
@@ -95,27 +88,7 @@ inline bool plan_of(long long n_rows, long long first_row, int n_columns, const 
     p.row_stride = (p.row_bytes + 3) / 4 * 4;
     p.groups = (n + ROWS_PER_GROUP - 1) / ROWS_PER_GROUP;
     p.piece_stride = ((size_t)ROWS_PER_GROUP * (size_t)p.row_bytes + 15) / 16 * 16 + 16;
-    size_t at = 0;
-    bool fits = true;
-    auto take = [&](size_t count, size_t each) {
-        const size_t here = at;
-        size_t bytes;
-        if (__builtin_mul_overflow(count, each, &bytes) || bytes > SIZE_MAX - 255 || __builtin_add_overflow(at, tablep::align256(bytes), &at)) fits = false;
-        return here;
-    };
-    const bool wide = p.n_f64 && n;
-    const size_t cells = n * (size_t)p.n_f64;                             // (at most 2^20 x 16)
-    p.suffix = take(suffix_bytes + 1, 1);
-    p.wide_incl = take(wide ? n : 0, sizeof(uint32_t));                  // wide cells per row, then their inclusive sums
-    p.wide_temp = take(wide ? tablep::scan_words(n) : 0, sizeof(uint32_t));
-    p.wide_slots = take(cells, tablep::WIDE_SLOT);
-    p.wide_len = take(cells, 1);
-    p.piece_len = take(p.groups, sizeof(uint32_t));
-    p.piece_incl = take(p.groups, sizeof(uint32_t));
-    p.piece_temp = take(n ? tablep::scan_words(p.groups) : 0, sizeof(uint32_t));
-    p.pieces = take(p.groups, p.piece_stride);
-    p.total = at;
-    return fits;
+    return tablep::layout_of(n, p.n_f64, p.groups, p.piece_stride, suffix_bytes + 1, p);
 }
 
 }  // namespace xlsxp

@@ -1056,11 +1056,36 @@ def _table_columns(pointers, dtypes):
     return cols
 
 
+def _table_print_host(cap, call):
+    """A printer's host twin: a buffer of the bound ``cap`` and ``call(out, cap, length, wide)`` -> ``(bytes, wide_cells)``."""
+    import ctypes
+    out = np.empty(max(cap, 1), np.uint8)
+    length, wide = ctypes.c_size_t(0), ctypes.c_longlong(0)
+    call(out.ctypes.data, cap, ctypes.byref(length), ctypes.byref(wide))
+    return out[:length.value].tobytes(), wide.value
+
+
+def _table_print_device(device, cap, refused, ws_bytes, launch):
+    """A printer's device call: the text's buffer of the bound ``cap``, a workspace of ``ws_bytes`` and
+    ``launch(stream, ws, ws_bytes, text, cap, length, wide_cells)`` with the device addresses -> ``(text, length, wide_cells)``,
+    the two numbers read back with one copy; None where the sizes say the plan refuses (``refused``, or no workspace size)."""
+    import torch
+    from . import _lib
+    if refused or ws_bytes == 0:
+        return None
+    with torch.cuda.device(device):
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+        text = torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
+        meta = torch.zeros(2, dtype=torch.int64, device=device)          # length; wide cells (low 32 bits)
+        launch(_lib.stream_ptr(device), ws.data_ptr(), ws_bytes, text.data_ptr(), cap, meta.data_ptr(), meta[1:].data_ptr())
+        length, wide = (int(v) for v in meta.cpu())
+    return text, length, wide & 0xFFFFFFFF
+
+
 def table_csv_devicelike(df, header=None):
     """``ysmr_table_format_devicelike`` on a DataFrame: the arithmetic of the device writer (csrc/fmt.h) on the host, for the
     CPU tests.  Returns ``(bytes, wide_cells)``; None for a frame :func:`table_csv_plan` refuses.  ``header``: bytes to write
     in place of the column names' line."""
-    import ctypes
     from . import _lib
     plan = table_csv_plan(df)
     if plan is None:
@@ -1071,12 +1096,9 @@ def table_csv_devicelike(df, header=None):
     arrays = [np.ascontiguousarray(df.iloc[:, k].to_numpy()) for k in range(len(dtypes))]
     cols = _table_columns([a.ctypes.data for a in arrays], dtypes)
     n = len(df)
-    cap = int(L.ysmr_table_csv_bound(n, len(dtypes), cols, len(head)))
-    out = np.empty(max(cap, 1), np.uint8)
-    length, wide = ctypes.c_size_t(0), ctypes.c_longlong(0)
-    _lib.check(L.ysmr_table_format_devicelike(n, len(dtypes), cols, head, len(head), out.ctypes.data, cap, ctypes.byref(length),
-                                              ctypes.byref(wide)), "ysmr_table_format_devicelike")
-    return out[:length.value].tobytes(), wide.value
+    return _table_print_host(
+        int(L.ysmr_table_csv_bound(n, len(dtypes), cols, len(head))),
+        lambda *where: _lib.check(L.ysmr_table_format_devicelike(n, len(dtypes), cols, head, len(head), *where), "ysmr_table_format_devicelike"))
 
 
 def table_format_device(tensors, dtypes, n, header, device):
@@ -1084,22 +1106,14 @@ def table_format_device(tensors, dtypes, n, header, device):
     dtype in ``dtypes`` each, a uint32 column as its int32 bits).  Returns ``(csv, length, wide_cells)`` -- the text as a uint8
     tensor on the device, its length and the number of wide cells, read back with one copy -- or None where the plan refuses
     (more text than the 32-bit offsets hold)."""
-    import torch
     from . import _lib
     L = _lib.lib()
     cols = _table_columns([t.data_ptr() if n else 0 for t in tensors], dtypes)
     cap = int(L.ysmr_table_csv_bound(n, len(dtypes), cols, len(header)))
-    ws_bytes = int(L.ysmr_table_format_workspace_bytes(n, len(dtypes), cols))
-    if (cap == 0 and (n or header)) or ws_bytes == 0:
-        return None
-    with torch.cuda.device(device):
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
-        csv = torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
-        meta = torch.zeros(2, dtype=torch.int64, device=device)          # csv length; wide cells (low 32 bits)
-        _lib.check(L.ysmr_table_format_device(_lib.stream_ptr(device), n, len(dtypes), cols, header, len(header), ws.data_ptr(), ws_bytes,
-                                              csv.data_ptr(), cap, meta.data_ptr(), meta[1:].data_ptr()), "ysmr_table_format_device")
-        length, wide = (int(v) for v in meta.cpu())
-    return csv, length, wide & 0xFFFFFFFF
+    return _table_print_device(
+        device, cap, cap == 0 and bool(n or header), int(L.ysmr_table_format_workspace_bytes(n, len(dtypes), cols)),
+        lambda stream, *where: _lib.check(L.ysmr_table_format_device(stream, n, len(dtypes), cols, header, len(header), *where),
+                                          "ysmr_table_format_device"))
 
 
 def write_table_device(df, save_path, device="cuda:0", columns_dev=None, rename_old_file=True):
@@ -1346,7 +1360,6 @@ def xlsx_sheet_devicelike(df, first_row=2, with_index=True, prefix=None, suffix=
     """``ysmr_xlsx_sheet_devicelike`` on a DataFrame of the five column types: the text of the device printer
     (csrc/xlsx_row.h) on the host, for the CPU tests.  Returns ``(bytes, wide_cells)``; None for a frame
     :func:`table_csv_plan` refuses."""
-    import ctypes
     from . import _lib
     plan = table_csv_plan(df)
     if plan is None:
@@ -1358,35 +1371,25 @@ def xlsx_sheet_devicelike(df, first_row=2, with_index=True, prefix=None, suffix=
     arrays = [np.ascontiguousarray(df.iloc[:, k].to_numpy()) for k in range(len(dtypes))]
     cols = _table_columns([a.ctypes.data for a in arrays], dtypes)
     n = len(df)
-    cap = int(L.ysmr_xlsx_sheet_bound(n, len(dtypes), cols, first_row, int(with_index), len(prefix), len(suffix)))
-    out = np.empty(max(cap, 1), np.uint8)
-    length, wide = ctypes.c_size_t(0), ctypes.c_longlong(0)
-    _lib.check(L.ysmr_xlsx_sheet_devicelike(n, len(dtypes), cols, first_row, int(with_index), prefix, len(prefix), suffix, len(suffix),
-                                            out.ctypes.data, cap, ctypes.byref(length), ctypes.byref(wide)), "ysmr_xlsx_sheet_devicelike")
-    return out[:length.value].tobytes(), wide.value
+    return _table_print_host(
+        int(L.ysmr_xlsx_sheet_bound(n, len(dtypes), cols, first_row, int(with_index), len(prefix), len(suffix))),
+        lambda *where: _lib.check(L.ysmr_xlsx_sheet_devicelike(n, len(dtypes), cols, first_row, int(with_index), prefix, len(prefix), suffix,
+                                                               len(suffix), *where), "ysmr_xlsx_sheet_devicelike"))
 
 
 def xlsx_sheet_device(tensors, dtypes, n, first_row, with_index, prefix, suffix, device):
     """``ysmr_xlsx_sheet_device`` on columns that are on ``device`` (``tensors`` as for :func:`table_format_device`).  Returns
     ``(xml, length, wide_cells)`` -- the text as a uint8 tensor on the device, its length and the number of wide cells, read
     back with one copy -- or None where the plan refuses."""
-    import torch
     from . import _lib
     L = _lib.lib()
     cols = _table_columns([t.data_ptr() if n else 0 for t in tensors], dtypes)
     cap = int(L.ysmr_xlsx_sheet_bound(n, len(dtypes), cols, first_row, int(with_index), len(prefix), len(suffix)))
-    ws_bytes = int(L.ysmr_xlsx_sheet_workspace_bytes(n, len(dtypes), cols, first_row, int(with_index), len(suffix)))
-    if (cap == 0 and (n or prefix or suffix)) or ws_bytes == 0:
-        return None
-    with torch.cuda.device(device):
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
-        xml = torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
-        meta = torch.zeros(2, dtype=torch.int64, device=device)          # length; wide cells (low 32 bits)
-        _lib.check(L.ysmr_xlsx_sheet_device(_lib.stream_ptr(device), n, len(dtypes), cols, first_row, int(with_index), prefix, len(prefix),
-                                            suffix, len(suffix), ws.data_ptr(), ws_bytes, xml.data_ptr(), cap, meta.data_ptr(),
-                                            meta[1:].data_ptr()), "ysmr_xlsx_sheet_device")
-        length, wide = (int(v) for v in meta.cpu())
-    return xml, length, wide & 0xFFFFFFFF
+    return _table_print_device(
+        device, cap, cap == 0 and bool(n or prefix or suffix),
+        int(L.ysmr_xlsx_sheet_workspace_bytes(n, len(dtypes), cols, first_row, int(with_index), len(suffix))),
+        lambda stream, *where: _lib.check(L.ysmr_xlsx_sheet_device(stream, n, len(dtypes), cols, first_row, int(with_index), prefix, len(prefix),
+                                                                   suffix, len(suffix), *where), "ysmr_xlsx_sheet_device"))
 
 
 def csv_column_kinds_devicelike(data, n_columns):
