@@ -259,6 +259,39 @@ int    ysmr_mjpeg_decode_batch_sync(void *stream, const uint8_t *chunks_dev, con
  * that cross these boundaries).  Either pointer may be NULL. */
 void   ysmr_mjpeg_decode_sync_geometry(int *subsequence_bytes, int *subsequences_per_pass);
 
+/* ---- frame ingest: TIFF stacks ------------------------------------------------------------------- */
+
+/* ADDED under ABI 15 (see above).  bits of status_dev[i] of ysmr_tiff_decode_batch: what any strip of frame i met */
+#define YSMR_TIFFD_BAD_CODE 1   /* LZW: a code above the next free entry (after a Clear: any code above 255 but Clear and EOI),
+                                   or a 3839th data code without a Clear, for which the table has no room */
+#define YSMR_TIFFD_SHORT    2   /* the strip's data (or an LZW EOI) ends before the strip's rows are full */
+#define YSMR_TIFFD_OVERRUN  4   /* PackBits: a run that would pass the end of the strip */
+#define YSMR_TIFFD_OLD_LZW  8   /* LZW: the body begins 0x00, then an odd byte -- the old LSB-first variant (libtiff's test) */
+#define YSMR_TIFFD_TABLE    16  /* a row of strips_dev outside the call's geometry: nothing of it was read or written */
+
+/* Bytes of scratch ysmr_tiff_decode_batch needs for n_frames frames cut into strips of rows_per_strip rows (the last one of
+ * a frame shorter where the height is no multiple) whose bodies are body_bytes bytes together.  0 for what the call refuses:
+ * n_frames, height or width not positive; channels not 1 or 3; compression not 1 (none), 5 (LZW) or 32773 (PackBits);
+ * predictor not 1 or 2; photometric not 0 or 1 (one channel) or 2 (three); rows_per_strip not 1 .. height; body_bytes, the
+ * bytes of a frame or the number of strips beyond 2^31 - 1. */
+size_t ysmr_tiff_decode_workspace_bytes(int n_frames, int height, int width, int channels, int compression, int predictor,
+                                        int photometric, int rows_per_strip, long long body_bytes);
+
+/* The strips of n_frames pages of a TIFF stack, as they are stored, to frames: strips_dev is int32 [n_strips][5] = (frame,
+ * first row, rows, offset of the body in bodies_dev, bytes of the body); n_strips / n_frames strips of equal height (but for
+ * the last) tile a frame.  A body may begin at ANY byte; no byte outside [offset, offset + bytes) is read, and a strip
+ * writes its own rows * width * channels bytes of its frame and nothing else.  compression 5 is LZW as TIFF 6.0 defines and
+ * libtiff decodes it (MSB first, 9 .. 12 bits, the width grows one code early; a stream without a leading Clear starts from
+ * the cleared table; decoding ends at EOI or when the strip is full), 32773 PackBits, 1 none.  Then predictor 2 (a running
+ * sum mod 256 along a row, per channel), photometric 0 (inverted) and 2 (R, G, B stored, B, G, R delivered).  frames_out: u8
+ * [n_frames][height][width][channels], the layout ysmr_threshold_batch reads.  status_dev[i] = 0 or YSMR_TIFFD_* bits; a
+ * flagged frame's pixels are undefined, inside its own bytes.  Asynchronous on `stream`.  workspace_dev: 256-byte aligned,
+ * workspace_bytes >= ysmr_tiff_decode_workspace_bytes(...); afterwards it holds an int32 per strip, that strip's bits. */
+int    ysmr_tiff_decode_batch(void *stream, const uint8_t *bodies_dev, const int32_t *strips_dev, int n_strips, int n_frames,
+                              int height, int width, int channels, int compression, int predictor, int photometric,
+                              void *workspace_dev, size_t workspace_bytes,
+                              uint8_t *frames_out, int32_t *status_dev /* [n_frames] */);
+
 /* ---- annotated output video as Motion-JPEG --------------------------------------------------- */
 
 /* bit of *status_dev of ysmr_mjpeg_batch */

@@ -74,7 +74,11 @@ EXPORTS = ("ysmr_abi_version", "ysmr_last_error", "ysmr_detect_workspace_bytes",
            "ysmr_table_format_devicelike", "ysmr_fmt_f64_text",
            "ysmr_csv_parse_typed", "ysmr_csv_parse_typed_devicelike", "ysmr_marks_workspace_bytes", "ysmr_marks_build",
            "ysmr_csv_column_kinds", "ysmr_csv_column_kinds_devicelike", "ysmr_xlsx_sheet_bound", "ysmr_xlsx_sheet_workspace_bytes",
-           "ysmr_xlsx_sheet_geometry", "ysmr_xlsx_sheet_device", "ysmr_xlsx_sheet_devicelike")
+           "ysmr_xlsx_sheet_geometry", "ysmr_xlsx_sheet_device", "ysmr_xlsx_sheet_devicelike",
+           "ysmr_tiff_decode_workspace_bytes", "ysmr_tiff_decode_batch")
+
+#: bits of ``status_dev`` of ``ysmr_tiff_decode_batch`` (YSMR_TIFFD_*)
+TIFFD_BAD_CODE, TIFFD_SHORT, TIFFD_OVERRUN, TIFFD_OLD_LZW, TIFFD_TABLE = 1, 2, 4, 8, 16
 
 #: bits of ``ysmr_csv_column_kinds`` (YSMR_KIND_*): words 0 .. 15 a column each, word 16 the file's
 KIND_NOT_INT, KIND_NOT_NUMBER, KIND_EMPTY, KIND_BAD_LINE, KIND_WORDS = 1, 2, 4, 1, 17
@@ -343,8 +347,11 @@ def lib():
                                          ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp]
     L.ysmr_xlsx_sheet_devicelike.argtypes = [ll, ci, tc, ll, ci, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, vp,
                                              ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ll)]
+    L.ysmr_tiff_decode_workspace_bytes.argtypes = [ci] * 8 + [ll]
+    L.ysmr_tiff_decode_workspace_bytes.restype = ctypes.c_size_t
+    L.ysmr_tiff_decode_batch.argtypes = [vp, vp, vp] + [ci] * 8 + [vp, ctypes.c_size_t, vp, vp]
     for name in EXPORTS:
-        if name not in ("ysmr_xlsx_sheet_bound", "ysmr_xlsx_sheet_workspace_bytes", "ysmr_xlsx_sheet_geometry", "ysmr_table_csv_bound", "ysmr_table_format_workspace_bytes", "ysmr_table_format_geometry", "ysmr_csv_workspace_bytes", "ysmr_csv_order_workspace_bytes", "ysmr_marks_workspace_bytes", "ysmr_csv_geometry", "ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_png_dynamic_workspace_bytes", "ysmr_png_dynamic_stream_bytes_max", "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_sync_geometry", "ysmr_mjpeg_decode_workspace_bytes", "ysmr_violin_workspace_bytes", "ysmr_mjpeg_workspace_bytes", "ysmr_mjpeg_encode_workspace_bytes", "ysmr_plot_workspace_bytes", "ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
+        if name not in ("ysmr_tiff_decode_workspace_bytes", "ysmr_xlsx_sheet_bound", "ysmr_xlsx_sheet_workspace_bytes", "ysmr_xlsx_sheet_geometry", "ysmr_table_csv_bound", "ysmr_table_format_workspace_bytes", "ysmr_table_format_geometry", "ysmr_csv_workspace_bytes", "ysmr_csv_order_workspace_bytes", "ysmr_marks_workspace_bytes", "ysmr_csv_geometry", "ysmr_png_workspace_bytes", "ysmr_png_stream_bytes_max", "ysmr_png_dynamic_workspace_bytes", "ysmr_png_dynamic_stream_bytes_max", "ysmr_mjpeg_decode_sync_workspace_bytes", "ysmr_mjpeg_decode_sync_geometry", "ysmr_mjpeg_decode_workspace_bytes", "ysmr_violin_workspace_bytes", "ysmr_mjpeg_workspace_bytes", "ysmr_mjpeg_encode_workspace_bytes", "ysmr_plot_workspace_bytes", "ysmr_evaluate_workspace_bytes", "ysmr_select_workspace_bytes", "ysmr_last_error", "ysmr_detect_workspace_bytes", "ysmr_abi_version",
                         "ysmr_rows_sort_workspace_bytes", "ysmr_rows_csv_bound", "ysmr_rows_stream_count",
                         "ysmr_mean_threshold_state_bytes"):
             getattr(L, name).restype = ci

@@ -46,7 +46,7 @@ from fractions import Fraction
 import numpy as np
 
 from . import _lib
-from .frames import DeviceFrameFeed, decode_mjpeg_setting, open_video
+from .frames import DeviceFrameFeed, decode_mjpeg_setting, decode_tiff_setting, open_video
 from .helper_file import create_results_folder, get_configs, get_data, get_loggers
 
 __all__ = ["annotate_video", "AviWriter", "MjpegAviWriter", "DibOutput", "output_format", "jpeg_mode", "build_marks", "build_marks_device", "LAST_MARKS", "subtype_code", "SUBTYPES"]
@@ -624,7 +624,8 @@ def annotate_video(video_path, df, output_save=True, settings=None, result_folde
     the free space is then checked batch by batch, against the bytes about to be written), 'hip video jpeg subsampling'
     ('4:4:4' / '4:2:2' / '4:2:0') and 'hip video jpeg huffman' ('standard' / 'optimised') its chroma subsampling and
     whether every frame carries Huffman tables of its own (``jpeg_mode``); 'hip decode mjpeg' (True /
-    'always' / False) says whether a Motion-JPEG INPUT is decoded on the device, as in ``track_bacteria``; a true 'hip read
+    'always' / False) says whether a Motion-JPEG INPUT is decoded on the device, and 'hip decode tiff' (True / False) whether a
+    TIFF stack is, as in ``track_bacteria``; a true 'hip read
     csv on device' reads a csv ``df`` and builds its marks on the device (``read_typed_device``, ``build_marks_device``) --
     the same file; a csv the device reader does not serve is read by pandas as without the key.  ``LAST_MARKS`` says which
     way the call went."""
@@ -747,7 +748,8 @@ def annotate_video(video_path, df, output_save=True, settings=None, result_folde
                     first_dev = torch.from_numpy(first).to(dev)
                     LAST_MARKS["marks"] = len(marks)
                 LAST_MARKS_TIMES["marks on device"] = time.perf_counter() - started
-                feed = DeviceFrameFeed(video, batch, dev, depth=2, decode_on_device=decode_mjpeg_setting(settings))
+                feed = DeviceFrameFeed(video, batch, dev, depth=2, decode_on_device=decode_mjpeg_setting(settings),
+                                       decode_tiff=decode_tiff_setting(settings))
                 for frames_dev, f0, n, slot in feed:
                     n = min(n, n_frames - f0)
                     if n <= 0:

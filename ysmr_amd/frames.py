@@ -13,6 +13,9 @@ it happens to be importable:
                frames (gray, 4:4:4, 4:2:2, 4:2:0) are uploaded as they are and decoded on the device
                (``ysmr_mjpeg_decode_batch``), anything else by Pillow on the reader threads, if it can be imported; other
                compressed streams go to cv2
+* ``.tif`` / ``.tiff`` -- multi-page TIFF stack, a page per frame (``TiffVideo``): 8-bit gray or RGB strips, uncompressed,
+               LZW (with or without the horizontal predictor) or PackBits, are uploaded as stored and decoded on the device
+               (``ysmr_tiff_decode_batch``); other pages by Pillow, if it can be imported; fps from the tracking.ini value
 * anything else -- ``cv2.VideoCapture`` if cv2 can be imported, otherwise an error
 
 Every source exposes ``frame_count`` (what the container reports: cv2's CAP_PROP_FRAME_COUNT), optionally
@@ -26,7 +29,7 @@ import os
 
 import numpy as np
 
-__all__ = ["open_video", "NpyVideo", "Y4mVideo", "AviVideo", "Cv2Video", "DeviceFrameFeed"]
+__all__ = ["open_video", "NpyVideo", "Y4mVideo", "AviVideo", "TiffVideo", "Cv2Video", "DeviceFrameFeed"]
 
 
 class NpyVideo:
@@ -467,6 +470,299 @@ class AviVideo:
         self._fh.close()
 
 
+class TiffVideo:
+    """Multi-page TIFF stack (what ImageJ / Fiji, Micro-Manager, Bio-Formats and camera software write) without OpenCV, and
+    without Pillow where it can be: classic TIFF of either byte order, one page per frame.
+
+    Served natively -- the host path reads uncompressed strips itself, ``DeviceFrameFeed`` uploads the stored strips and
+    ``ysmr_tiff_decode_batch`` decodes them -- are pages of 8 bits per sample, photometric 0 (WhiteIsZero, delivered inverted as
+    Pillow delivers it), 1 (BlackIsZero) or 2 (RGB, delivered B, G, R), one sample per pixel or three chunky ones, compression 1
+    (none), 5 (LZW, MSB first) or 32773 (PackBits), predictor 1 or 2, in strips, every page like the first.  Anything else --
+    deflate, JPEG, tiles, palettes, 16 bit, planar RGB, extra samples, old-style LZW, a page unlike the first -- is decoded by
+    Pillow page by page, with whatever Pillow raises; without Pillow it is a ValueError naming the tag.  BigTIFF is refused.
+    ImageJ's convention for stacks above 4 GB (ONE directory, ``images=N`` in the description, the planes behind one another)
+    is not followed: such a file reads as the one page its directory describes.
+
+    TIFF has no frame rate: ``fps`` is ``default_fps`` (tracking.ini's 'frames per second')."""
+
+    _SIZES = {1: 1, 2: 1, 3: 2, 4: 4, 5: 8, 6: 1, 7: 1, 8: 2, 9: 4, 10: 8, 11: 4, 12: 8, 13: 4}
+    _LETTER = {1: "B", 3: "H", 4: "I", 6: "b", 8: "h", 9: "i", 13: "I"}
+    _NAMES = {256: "ImageWidth", 257: "ImageLength", 258: "BitsPerSample", 259: "Compression", 262: "PhotometricInterpretation",
+              266: "FillOrder", 273: "StripOffsets", 277: "SamplesPerPixel", 278: "RowsPerStrip", 279: "StripByteCounts",
+              284: "PlanarConfiguration", 317: "Predictor", 322: "TileWidth", 338: "ExtraSamples"}
+
+    def __init__(self, path, default_fps=30.0):
+        import logging
+        import threading
+        self.path = path
+        self._fh = open(path, "rb")
+        try:
+            self._parse(path)
+        except BaseException:
+            self._fh.close()
+            raise
+        self.fps = float(default_fps)
+        self._local, self._opened = threading.local(), []
+        logging.getLogger("ysmr").info("%s: a TIFF stack carries no frame rate; using 'frames per second' = %s", path, self.fps)
+
+    # ---- the directories
+    def _parse(self, path):
+        import struct
+        fh = self._fh
+        size = os.path.getsize(path)
+        head = fh.read(8)
+        if len(head) < 8 or head[:2] not in (b"II", b"MM"):
+            raise ValueError(f"{path}: not a TIFF file")
+        e = self._endian = "<" if head[:2] == b"II" else ">"
+        version, at = struct.unpack(e + "HI", head[2:])
+        if version == 43:
+            raise ValueError(f"{path}: BigTIFF (version 43) is not read; save the stack as classic TIFF")
+        if version != 42:
+            raise ValueError(f"{path}: not a TIFF file (version {version})")
+        wanted = set(self._NAMES)
+        self._pages, seen = [], set()
+        while at:
+            if at in seen or at + 2 > size:
+                raise ValueError(f"{path}: damaged directory chain at offset {at}")
+            seen.add(at)
+            fh.seek(at)
+            (count,) = struct.unpack(e + "H", fh.read(2))
+            raw = fh.read(12 * count + 4)
+            if len(raw) < 12 * count + 4:
+                raise ValueError(f"{path}: directory at offset {at} is truncated")
+            tags = {}
+            for k in range(count):
+                tag, kind, n = struct.unpack(e + "HHI", raw[12 * k:12 * k + 8])
+                if tag not in wanted:
+                    continue
+                letter, width = self._LETTER.get(kind), self._SIZES.get(kind, 0)
+                if letter is None:
+                    raise ValueError(f"{path}: tag {tag} ({self._NAMES[tag]}) has type {kind}")
+                if n * width <= 4:
+                    data = raw[12 * k + 8:12 * k + 8 + n * width]
+                else:
+                    (where,) = struct.unpack(e + "I", raw[12 * k + 8:12 * k + 12])
+                    fh.seek(where)
+                    data = fh.read(n * width)
+                    if len(data) < n * width:
+                        raise ValueError(f"{path}: tag {tag} ({self._NAMES[tag]}) points outside the file")
+                tags[tag] = np.frombuffer(data, np.dtype(e + {"B": "u1", "H": "u2", "I": "u4", "b": "i1", "h": "i2", "i": "i4"}[letter]),
+                                          n).astype(np.int64)
+            self._pages.append(tags)
+            (at,) = struct.unpack(e + "I", raw[12 * count:])
+        if not self._pages:
+            raise ValueError(f"{path}: no pages")
+        first = self._pages[0]
+        if 256 not in first or 257 not in first:
+            raise ValueError(f"{path}: the first directory has no ImageWidth / ImageLength")
+        self.width, self.height = int(first[256][0]), int(first[257][0])
+        self.frame_count = self.frames_available = len(self._pages)
+        try:
+            from PIL import Image
+            self._Image, self._no_pillow = Image, None
+        except ImportError as exc:
+            self._Image, self._no_pillow = None, str(exc)
+        self._why = [self._outside(k) for k in range(len(self._pages))]      # None: the page is in the native subset
+        if self._why[0] is None:
+            self.channels = int(self._tag(first, 277, 1))
+            self._compression, self._predictor = int(self._tag(first, 259, 1)), int(self._tag(first, 317, 1))
+            self._photometric = int(self._tag(first, 262, 1))
+            self._rows_per_strip = min(self.height, int(self._tag(first, 278, self.height)))
+            self._strips_per_frame = -(-self.height // self._rows_per_strip)
+        elif self._Image is None:
+            raise ValueError(f"{path}: {self._why[0]}; such a file needs Pillow ({self._no_pillow})")
+        else:
+            with self._Image.open(path) as im:
+                self.channels = 1 if im.mode in ("1", "L", "I", "F") or im.mode.startswith("I;16") else 3
+
+    @staticmethod
+    def _tag(tags, tag, default):
+        return tags[tag][0] if tag in tags and len(tags[tag]) else default
+
+    _SAME = (256, 257, 258, 259, 262, 277, 278, 284, 317)
+
+    def _outside(self, k):
+        """None, or why page k is not in the native subset: '<tag name> <tag> = <value>'."""
+        tags, first = self._pages[k], self._pages[0]
+
+        def says(tag, value):
+            return "page {}: {} ({}) = {}".format(k, self._NAMES[tag], tag, value)
+
+        samples = int(self._tag(tags, 277, 1))
+        bits = [int(b) for b in tags.get(258, [1])]
+        if any(b != 8 for b in bits):
+            return says(258, bits if len(bits) > 1 else bits[0])
+        if samples not in (1, 3) or 338 in tags:
+            return says(338, list(tags[338])) if 338 in tags else says(277, samples)
+        photometric = int(self._tag(tags, 262, -1))
+        if photometric not in ((0, 1) if samples == 1 else (2,)):
+            return says(262, photometric)
+        if int(self._tag(tags, 259, 1)) not in (1, 5, 32773):
+            return says(259, int(self._tag(tags, 259, 1)))
+        if int(self._tag(tags, 317, 1)) not in (1, 2):
+            return says(317, int(self._tag(tags, 317, 1)))
+        if samples == 3 and int(self._tag(tags, 284, 1)) != 1:
+            return says(284, int(self._tag(tags, 284, 1)))
+        if int(self._tag(tags, 266, 1)) != 1:
+            return says(266, int(self._tag(tags, 266, 1)))
+        if 322 in tags:
+            return says(322, int(tags[322][0]))
+        if 273 not in tags or 279 not in tags:
+            return "page {}: no StripOffsets (273) / StripByteCounts (279)".format(k)
+        height, width = int(self._tag(tags, 257, 0)), int(self._tag(tags, 256, 0))
+        if height <= 0 or width <= 0:
+            return says(257, height)
+        rows = min(height, int(self._tag(tags, 278, height)))
+        if rows <= 0:
+            return says(278, rows)
+        strips = -(-height // rows)
+        if len(tags[273]) != strips or len(tags[279]) != strips:
+            return says(273, "{} offsets, {} rows in strips of {}".format(len(tags[273]), height, rows))
+        for tag in self._SAME:
+            if k and int(self._tag(tags, tag, 1 if tag != 278 else height)) != int(self._tag(first, tag, 1 if tag != 278 else height)):
+                return says(tag, "{}, the first page has {}".format(int(self._tag(tags, tag, 1)), int(self._tag(first, tag, 1))))
+        if int(self._tag(tags, 259, 1)) == 5:          # libtiff's test for the old LSB-first LZW
+            for where, size in zip(tags[273], tags[279]):
+                self._fh.seek(int(where))
+                start = self._fh.read(2)
+                if size >= 2 and len(start) == 2 and start[0] == 0 and start[1] & 1:
+                    return says(259, "5 in its old LSB-first form")
+                break                                     # (the first strip tells; a later one is the device's to flag)
+        return None
+
+    @property
+    def native(self):
+        """Every page is in the subset this reader and the device serve without Pillow."""
+        return all(w is None for w in self._why)
+
+    def strips_of(self, k):
+        """(offsets, byte counts) of page k, int64 arrays."""
+        return self._pages[k][273], self._pages[k][279]
+
+    # ---- the host path
+    def read(self, start, count):
+        n = max(0, min(count, self.frames_available - start))
+        out = np.empty((n, self.height, self.width) + ((3,) if self.channels == 3 else ()), np.uint8)
+        self.read_into(start, n, out)
+        return out
+
+    def _pillow_page(self, k, dst):
+        if self._Image is None:
+            raise ValueError(f"{self.path}: {self._why[k] or 'a compressed page'}; the host path needs Pillow ({self._no_pillow})")
+        im = getattr(self._local, "im", None)
+        if im is None:
+            im = self._local.im = self._Image.open(self.path)        # (one per reader thread: a seek walks the directories)
+            self._opened.append(im)
+        im.seek(k)
+        if self.channels == 1:
+            dst[...] = np.asarray(im.convert("L"))
+        else:
+            dst[...] = np.asarray(im.convert("RGB"))[:, :, ::-1]         # B, G, R: what cv2.VideoCapture delivers
+
+    def _decode_page(self, k, dst):
+        """Page k into ``dst`` on the host: uncompressed strips of the native subset by this reader, the rest by Pillow."""
+        if self._why[k] is not None or self._compression != 1:
+            return self._pillow_page(k, dst)
+        offsets, counts = self.strips_of(k)
+        row_bytes = self.width * self.channels
+        plain = self._predictor == 1 and self._photometric == 1 and dst.flags["C_CONTIGUOUS"]
+        raw = dst.reshape(-1) if plain else np.empty(self.height * row_bytes, np.uint8)
+        fd = self._fh.fileno()
+        for s in range(len(offsets)):
+            lo = s * self._rows_per_strip * row_bytes
+            need = min(self._rows_per_strip, self.height - s * self._rows_per_strip) * row_bytes
+            if counts[s] < need:
+                raise ValueError(f"{self.path}: page {k}, strip {s} holds {counts[s]} bytes, its rows need {need}")
+            view, got = memoryview(raw[lo:lo + need]), 0
+            while got < need:
+                n = os.preadv(fd, [view[got:]], int(offsets[s]) + got)
+                if n <= 0:
+                    raise ValueError(f"{self.path}: page {k} is truncated")
+                got += n
+        if not plain:
+            a = raw.reshape(self.height, self.width, self.channels)
+            if self._predictor == 2:
+                a = np.cumsum(a, axis=1, dtype=np.uint32).astype(np.uint8)
+            if self._photometric == 0:
+                a = ~a
+            dst[...] = a[:, :, ::-1] if self.channels == 3 else a[:, :, 0]
+
+    def read_into(self, start, count, out, pool=None):
+        n = max(0, min(count, self.frames_available - start))
+        if pool is None or n < 2:
+            for i in range(n):
+                self._decode_page(start + i, out[i])
+        else:
+            for job in [pool.submit(self._decode_page, start + i, out[i]) for i in range(n)]:
+                job.result()
+        return n
+
+    # ---- strips as they are in the file, for decoding on the device (DeviceFrameFeed, ysmr_tiff_decode_batch)
+    def tiff_layout_for(self, batch):
+        """None, or what a caller of ``ysmr_tiff_decode_batch`` needs to know before it reads this file: (compression, predictor,
+        photometric, rows per strip, strips per frame, most body bytes of any ``batch`` consecutive pages).  None where a page
+        is outside the native subset, and where the device entry refuses the sizes.  (A page of ONE strip is one wave's serial
+        work on the device, and still faster there than on the host: profiles/tiff_decode_e2e.log.)"""
+        if not self.native:
+            return None
+        sizes = np.array([int(p[279].sum()) for p in self._pages], np.int64)
+        total = np.concatenate([[0], np.cumsum(sizes)])
+        k = max(1, min(int(batch), len(sizes)))
+        most = int((total[k:] - total[:-k]).max())
+        from . import _lib
+        if _lib.lib().ysmr_tiff_decode_workspace_bytes(int(batch), self.height, self.width, self.channels, self._compression,
+                                                       self._predictor, self._photometric, self._rows_per_strip, most) == 0:
+            return None
+        return self._compression, self._predictor, self._photometric, self._rows_per_strip, self._strips_per_frame, most
+
+    def read_tiff_into(self, start, count, out, table, pool=None):
+        """Strip bodies of pages [start, start + count) back to back into ``out`` (u8 [bytes], e.g. pinned memory) and the
+        strip table into ``table[:n * strips per frame]`` (int32 [.., 5]: frame of the batch, first row, rows, offset in
+        ``out``, bytes): file reads only (``os.preadv``, strips that follow one another in the file in one read, spread over
+        the threads of ``pool`` if one is given), nothing is decoded.  Returns (pages, bytes used)."""
+        n = max(0, min(count, self.frames_available - start))
+        fd, spf, rps = self._fh.fileno(), self._strips_per_frame, self._rows_per_strip
+        at, reads = 0, []
+        for i in range(n):
+            offsets, counts = self.strips_of(start + i)
+            rows = table[i * spf:(i + 1) * spf]
+            rows[:, 0] = i
+            rows[:, 1] = np.arange(spf) * rps
+            rows[:, 2] = np.minimum(rps, self.height - rows[:, 1])
+            rows[:, 3] = at + np.concatenate([[0], np.cumsum(counts[:-1])])
+            rows[:, 4] = counts
+            ends = offsets + counts
+            cuts = np.flatnonzero(offsets[1:] != ends[:-1]) + 1          # where a strip does not follow its predecessor
+            for lo, hi in zip(np.concatenate([[0], cuts]), np.concatenate([cuts, [spf]])):
+                reads.append((int(offsets[lo]), int(rows[lo, 3]), int(counts[lo:hi].sum()), start + i))
+            at += int(counts.sum())
+        if at > out.size:
+            raise ValueError(f"{self.path}: pages {start} .. {start + n - 1} hold {at} bytes, the buffer {out.size}")
+        flat = memoryview(out).cast("B")
+
+        def one(job):
+            where, to, need, page = job
+            got, view = 0, flat[to:to + need]
+            while got < need:
+                k = os.preadv(fd, [view[got:]], where + got)
+                if k <= 0:
+                    raise ValueError(f"{self.path}: page {page} is truncated")
+                got += k
+
+        if pool is None or len(reads) < 2:
+            for job in reads:
+                one(job)
+        else:
+            for job in [pool.submit(one, job) for job in reads]:
+                job.result()
+        return n, at
+
+    def close(self):
+        self._fh.close()
+        while self._opened:
+            self._opened.pop().close()
+
+
 class Cv2Video:
     """Fallback for compressed containers when OpenCV is installed (decode stays on the host)."""
 
@@ -565,9 +861,13 @@ class DeviceFrameFeed:
     ``ysmr_mjpeg_decode_batch_sync``, which decodes a frame without restart markers with a lane per 64 bytes of its entropy data
     (and one with them as the other call does); the per-frame status comes back once per batch, and a frame it flags
     (outside the supported subset, or damaged) is decoded again by the host path and copied into its place -- with whatever
-    that path raises.  False: every frame takes the host path."""
+    that path raises.  False: every frame takes the host path.
 
-    def __init__(self, video, batch, device, depth=3, readers=16, pieces=4, near_gpu=True, decode_on_device=True):
+    ``decode_tiff`` (the settings key 'hip decode tiff'): True -- a TIFF stack whose ``tiff_layout_for`` is not None is uploaded as
+    [strip table][strip bodies as stored] and decoded on the copy stream by ``ysmr_tiff_decode_batch``, with the same handling
+    of flagged frames.  False: the host path."""
+
+    def __init__(self, video, batch, device, depth=3, readers=16, pieces=4, near_gpu=True, decode_on_device=True, decode_tiff=True):
         import queue
         import threading
         from concurrent.futures import ThreadPoolExecutor
@@ -585,6 +885,9 @@ class DeviceFrameFeed:
         self._decode_on_device = decode_on_device
         self._jpeg = video.jpeg_layout_for(self.B, needs_restart=decode_on_device != "always") \
             if decode_on_device and hasattr(video, "jpeg_layout_for") else None
+        # TIFF stack: the strips go to the device as they are stored and are decoded there
+        self._tiff = video.tiff_layout_for(self.B) if decode_tiff and hasattr(video, "tiff_layout_for") else None
+        self._stored = self._jpeg is not None or self._tiff is not None
         self._cpus = cpus_near_gpu(self.device) if near_gpu else None
         with _ThreadOn(self._cpus):      # (pinned pages are the calling thread's node's)
             self._allocate(shape)
@@ -602,17 +905,29 @@ class DeviceFrameFeed:
 
     def _allocate(self, shape):
         import torch
-        if self._jpeg is not None:
+        if self._stored:
             from . import _lib
-            sampling, _, batch_bytes = self._jpeg
-            # [offsets int64 [B + 1]] [chunk bodies]: one copy per batch, of the bytes used
-            self._jpeg_head = 8 * (self.B + 1)
-            size = self._jpeg_head + batch_bytes
+            # [head: where the pieces lie] [the bytes as stored]: one copy per batch, of the bytes used
+            if self._jpeg is not None:
+                sampling, _, batch_bytes = self._jpeg
+                self._stored_head = 8 * (self.B + 1)                          # offsets int64 [B + 1], then the chunk bodies
+            else:
+                batch_bytes = self._tiff[5]
+                self._stored_head = (20 * self.B * self._tiff[4] + 255) // 256 * 256   # strips int32 [B * strips per frame][5], then their bodies
+            size = self._stored_head + batch_bytes
             self._pinned = [torch.empty(size, dtype=torch.uint8, pin_memory=True) for _ in range(self.depth)]
-            self._jpeg_dev = [torch.empty(size, dtype=torch.uint8, device=self.device) for _ in range(self.depth)]
+            self._stored_dev = [torch.empty(size, dtype=torch.uint8, device=self.device) for _ in range(self.depth)]
             self._status_dev = [torch.empty(self.B, dtype=torch.int32, device=self.device) for _ in range(self.depth)]
             self._status = [torch.empty(self.B, dtype=torch.int32, pin_memory=True) for _ in range(self.depth)]
             self._frame_host = torch.empty(shape[1:], dtype=torch.uint8, pin_memory=True)       # for a frame the host decodes
+        if self._tiff is not None:
+            compression, predictor, photometric, rows_per_strip, _, batch_bytes = self._tiff
+            ws = _lib.lib().ysmr_tiff_decode_workspace_bytes(self.B, shape[1], shape[2], self.video.channels, compression, predictor,
+                                                             photometric, rows_per_strip, batch_bytes)
+            if ws == 0:
+                raise ValueError("ysmr_tiff_decode_workspace_bytes refuses {} frames of {} x {}".format(self.B, shape[2], shape[1]))
+            self._stored_ws = torch.empty(ws, dtype=torch.uint8, device=self.device)
+        elif self._jpeg is not None:
             # 'always': the entry that also decodes a frame without restart markers with many lanes; it sizes its workspace
             # by the file's largest chunk
             self._jpeg_sync = self._decode_on_device == "always"
@@ -624,7 +939,7 @@ class DeviceFrameFeed:
             if ws == 0:
                 raise ValueError("ysmr_mjpeg_decode_{}workspace_bytes refuses {} frames of {} x {} (largest chunk {} bytes)".format(
                     "sync_" if self._jpeg_sync else "", self.B, shape[2], shape[1], self._jpeg[1]))
-            self._jpeg_ws = torch.empty(ws, dtype=torch.uint8, device=self.device)             # (the slots' decodes are serial)
+            self._stored_ws = torch.empty(ws, dtype=torch.uint8, device=self.device)           # (the slots' decodes are serial)
         elif self._raw is not None:
             raw_bytes, _, _, _, palette = self._raw
             self._pinned = [torch.empty((self.B, raw_bytes), dtype=torch.uint8, pin_memory=True) for _ in range(self.depth)]
@@ -651,7 +966,7 @@ class DeviceFrameFeed:
                 with self._cv:
                     busy = self._released[slot] is None
                 if busy:
-                    self._finish_jpeg()      # (the consumer frees this slot only after it has been given what is pending)
+                    self._finish_stored()      # (the consumer frees this slot only after it has been given what is pending)
                 with self._cv:
                     while self._released[slot] is None and not self._stop:
                         self._cv.wait(0.05)
@@ -661,8 +976,8 @@ class DeviceFrameFeed:
                 if self._uploaded[slot] is not None:
                     self._uploaded[slot].synchronize()          # staging buffer free again
                 host = self._pinned[slot].numpy()
-                if self._jpeg is not None:
-                    n = self._produce_jpeg(f0, slot, released, host)
+                if self._stored:
+                    n = self._produce_stored(f0, slot, released, host)
                     if n == 0:
                         break
                     i += 1
@@ -708,59 +1023,81 @@ class DeviceFrameFeed:
                 self._uploaded[slot] = ev
                 self._q.put((slot, f0, n, ev))
                 i += 1
-            self._finish_jpeg()
+            self._finish_stored()
             self._q.put(None)
         except BaseException as exc:   # hand the failure to the consumer
             self._q.put(exc)
 
-    _jpeg_pending = None
+    _stored_pending = None
 
-    def _produce_jpeg(self, f0, slot, released, host):
-        """Batch ``f0`` as chunk bodies: read, upload, decode on the copy stream.  The batch is handed on when its status has
-        come back, which is waited for only after the NEXT batch has been read and issued (``_finish_jpeg``)."""
+    def _produce_stored(self, f0, slot, released, host):
+        """Batch ``f0`` as it is stored (Motion-JPEG chunk bodies, or TIFF strips): read, upload, decode on the copy stream.  The
+        batch is handed on when its status has come back, which is waited for only after the NEXT batch has been read and
+        issued (``_finish_stored``)."""
         import torch
-        from . import _lib
-        video, head = self.video, self._jpeg_head
-        offsets = host[:head].view(np.int64)
-        n = video.read_jpeg_into(f0, self.B, host[head:], offsets, self._pool)
+        video, head = self.video, self._stored_head
+        if self._jpeg is not None:
+            offsets = host[:head].view(np.int64)
+            n = video.read_jpeg_into(f0, self.B, host[head:], offsets, self._pool)
+            used = head + int(offsets[n])
+        else:
+            table = host[:20 * self.B * self._tiff[4]].view(np.int32).reshape(-1, 5)
+            n, body_bytes = video.read_tiff_into(f0, self.B, host[head:], table, self._pool)
+            used = head + body_bytes
         if n == 0:
             return 0
-        used = head + int(offsets[n])
         with torch.cuda.stream(self._copy_stream):
             if released is not True:
                 self._copy_stream.wait_event(released)          # the kernels that read this device buffer are done
-            self._jpeg_dev[slot][:used].copy_(self._pinned[slot][:used], non_blocking=True)
-            if self._jpeg_sync:
-                _lib.check(_lib.lib().ysmr_mjpeg_decode_batch_sync(
-                    self._copy_stream.cuda_stream, self._jpeg_dev[slot].data_ptr() + head, self._jpeg_dev[slot].data_ptr(), n,
-                    video.height, video.width, video.channels, self._jpeg[0], self._jpeg[1], self._jpeg_ws.data_ptr(),
-                    self._jpeg_ws.numel(), self._dev[slot].data_ptr(), self._status_dev[slot].data_ptr()), "ysmr_mjpeg_decode_batch_sync")
-            else:
-                _lib.check(_lib.lib().ysmr_mjpeg_decode_batch(
-                    self._copy_stream.cuda_stream, self._jpeg_dev[slot].data_ptr() + head, self._jpeg_dev[slot].data_ptr(), n,
-                    video.height, video.width, video.channels, self._jpeg[0], self._jpeg_ws.data_ptr(), self._jpeg_ws.numel(),
-                    self._dev[slot].data_ptr(), self._status_dev[slot].data_ptr()), "ysmr_mjpeg_decode_batch")
+            self._stored_dev[slot][:used].copy_(self._pinned[slot][:used], non_blocking=True)
+            self._decode_stored(slot, n)
             self._status[slot][:n].copy_(self._status_dev[slot][:n], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self._copy_stream)
         self._uploaded[slot] = ev
-        self._finish_jpeg()
-        self._jpeg_pending = (slot, f0, n, ev)
+        self._finish_stored()
+        self._stored_pending = (slot, f0, n, ev)
         return n
 
-    def _finish_jpeg(self):
-        """Hand the pending Motion-JPEG batch to the consumer: its status is here once its event has passed; the frames the
+    def _decode_stored(self, slot, n):
+        """The decode of the ``n`` frames uploaded into ``slot``, issued on the copy stream."""
+        from . import _lib
+        video, head, L = self.video, self._stored_head, _lib.lib()
+        stream, stored = self._copy_stream.cuda_stream, self._stored_dev[slot].data_ptr()
+        ws, frames, status = self._stored_ws, self._dev[slot].data_ptr(), self._status_dev[slot].data_ptr()
+        if self._tiff is not None:
+            compression, predictor, photometric, _, strips_per_frame, _ = self._tiff
+            _lib.check(L.ysmr_tiff_decode_batch(stream, stored + head, stored, n * strips_per_frame, n, video.height, video.width,
+                                                video.channels, compression, predictor, photometric, ws.data_ptr(), ws.numel(), frames,
+                                                status), "ysmr_tiff_decode_batch")
+        elif self._jpeg_sync:
+            _lib.check(L.ysmr_mjpeg_decode_batch_sync(stream, stored + head, stored, n, video.height, video.width, video.channels,
+                                                      self._jpeg[0], self._jpeg[1], ws.data_ptr(), ws.numel(), frames, status),
+                       "ysmr_mjpeg_decode_batch_sync")
+        else:
+            _lib.check(L.ysmr_mjpeg_decode_batch(stream, stored + head, stored, n, video.height, video.width, video.channels,
+                                                 self._jpeg[0], ws.data_ptr(), ws.numel(), frames, status), "ysmr_mjpeg_decode_batch")
+
+    def _host_frame(self, k, dst):
+        """Frame ``k`` by the video's host path."""
+        if self._tiff is not None:
+            self.video._decode_page(k, dst)
+        else:
+            self.video._decode_jpeg(self.video._chunk(k), dst)
+
+    def _finish_stored(self):
+        """Hand the pending batch of stored bytes to the consumer: its status is here once its event has passed; the frames the
         device flagged are decoded by the host path (which raises what it raises today) and copied into their places."""
         import torch
-        if self._jpeg_pending is None:
+        if self._stored_pending is None:
             return
-        (slot, f0, n, ev), self._jpeg_pending = self._jpeg_pending, None
+        (slot, f0, n, ev), self._stored_pending = self._stored_pending, None
         ev.synchronize()
         flagged = np.flatnonzero(self._status[slot][:n].numpy())
         if len(flagged):
             with torch.cuda.stream(self._copy_stream):
                 for k in flagged:
-                    self.video._decode_jpeg(self.video._chunk(f0 + int(k)), self._frame_host.numpy())
+                    self._host_frame(f0 + int(k), self._frame_host.numpy())
                     self._dev[slot][int(k)].copy_(self._frame_host, non_blocking=True)
                     self._copy_stream.synchronize()             # (the one staging frame is free again)
                 ev = torch.cuda.Event()
@@ -813,8 +1150,26 @@ def decode_mjpeg_setting(settings):
     return bool(value)
 
 
+#: what 'hip decode tiff' is without the key: on one MI355X the device path's whole range lay above the host path's on the LZW file
+#: with libtiff's default strips (6.3 - 6.5 k frames/s against 409 - 460, profiles/tiff_decode_e2e.log)
+DECODE_TIFF_DEFAULT = True
+
+
+def decode_tiff_setting(settings):
+    """The ``decode_tiff`` argument of ``DeviceFrameFeed`` from the optional settings key 'hip decode tiff': true -- a TIFF stack
+    that ``TiffVideo.tiff_layout_for`` serves is uploaded as stored strips and decoded on the device -- or false -- every frame
+    by the host path (uncompressed strips read directly, compressed ones by Pillow on the reader threads).  Without the key:
+    ``DECODE_TIFF_DEFAULT``."""
+    value = settings.get("hip decode tiff", DECODE_TIFF_DEFAULT)
+    if isinstance(value, str):
+        return value.strip().lower() not in ("false", "0", "no", "off", "")
+    return bool(value)
+
+
 def open_video(path, default_fps=30.0):
     ext = os.path.splitext(path)[1].lower()
+    if ext in (".tif", ".tiff"):
+        return TiffVideo(path, default_fps)
     if ext == ".npy":
         return NpyVideo(path, default_fps)
     if ext == ".y4m":

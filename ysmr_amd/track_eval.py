@@ -31,7 +31,7 @@ import torch
 from . import _lib
 from ._lib import on_own_device
 from .detect import Detector, MeanGrayState, mean_gray_params, threshold_params
-from .frames import DeviceFrameFeed, decode_mjpeg_setting, open_video
+from .frames import DeviceFrameFeed, decode_mjpeg_setting, decode_tiff_setting, open_video
 from .helper_file import (COLOR_BGR2GRAY, RowStream, create_results_folder, get_configs, get_loggers, rows_to_csv_bytes, rows_to_csv_file, rows_to_csv_file_and_dataframe, rows_device_to_csv_file_and_dataframe,
                           rows_to_dataframe, save_list, wait_for_removals)
 from .tracker import DeviceTracker, rows_to_numpy, sort_rows
@@ -360,6 +360,11 @@ def track_bacteria(video_path, settings=None, result_folder=None, batch=None, ma
     (``ysmr_mjpeg_decode_batch``); 'always': one without restart markers too -- what cameras, ffmpeg, OpenCV and Pillow write
     -- by ``ysmr_mjpeg_decode_batch_sync``, which gives such a frame a lane per 64 bytes of its entropy data instead of one in
     all; False: by Pillow on the reader threads (``frames.decode_mjpeg_setting``).
+    A ``.tif`` / ``.tiff`` path is a multi-page TIFF stack, a page per frame (``frames.TiffVideo``; fps is 'frames per second', TIFF
+    has none): 8-bit gray or chunky RGB strips, uncompressed, LZW (with or without the horizontal predictor) or PackBits, are
+    uploaded as stored and decoded on the device (``ysmr_tiff_decode_batch``) under 'hip decode tiff' (default True; False: the
+    host path -- uncompressed strips read directly, compressed ones by Pillow on the reader threads;
+    ``frames.decode_tiff_setting``); other pages, and frames the device flags, are Pillow's either way.
     'hip save detection video' (default False): what upstream's window "... unfiltered possible detections" shows ('display video
     analysis', refused here) goes into ``detection_video_path(...)`` during the pass -- every frame with the boxes of its
     detections in blue and the ids and centroids of the live tracks in green (``ysmr_view_*``, csrc/view.hip); container and
@@ -925,7 +930,8 @@ def _device_pass(video, video_path, frame_count, fps_of_file, local, batch, max_
         rows_upper = 0     # host-side bound on the rows in the device buffer (no sync per batch)
         LAST_PASS_MARKS.clear()
         LAST_PASS_MARKS["pipeline built"] = time.perf_counter() - t_start
-        feed = DeviceFrameFeed(video, pipe.B, pipe.device, decode_on_device=decode_mjpeg_setting(settings))
+        feed = DeviceFrameFeed(video, pipe.B, pipe.device, decode_on_device=decode_mjpeg_setting(settings),
+                               decode_tiff=decode_tiff_setting(settings))
         LAST_PASS_MARKS["feed built"] = time.perf_counter() - t_start
         # (rows leave for the host and are printed batch by batch, while later batches run -- unless they are to be appended
         # to the list file in the order they were tracked, 'hip persist rows', which is the older, serial path)
